@@ -11,11 +11,16 @@ composes every sample's element maps, the launch that streams the particles thro
 (moments accumulated in its epilogue), the moment finalisation, and (N > 1) the RCCL
 all-gather of the per-sample moment records.
 Particles, lattice parameters and outputs are resident in HBM when the timed region starts.
-Order of a run: CPU baseline (rank 0 of a one-GPU run -- the launcher parent of an N-GPU run --, before the GPU is
-opened), W warm-up steps, barrier, K timed steps, barrier (the COLD leg: `ms_per_step_cold`, exactly what the command
-line asks for), the plain-copy calibration of this box's HBM ceiling (every rank, about 0.1 s), barrier, the same K
-timed steps again, barrier (`value`, `ms_per_step`: the streaming kernel's 20-30 ms start-up transient is behind it by
-then).  `hbm_copy_kernel_when` in the line says so; LYNX_BENCH_CALIBRATE_FIRST=0: no cold leg, calibration last.
+Order of a plain run: W warm-up steps, barrier, K timed steps, barrier (`value`, `ms_per_step`), the JSON line.
+`--dump-outputs DIR` then writes what the last timed step returned (`dump_outputs`).
+
+`--full` adds everything else the line can carry, in this order: CPU baseline (rank 0 of a one-GPU run -- the
+launcher parent of an N-GPU run --, before the GPU is opened), W warm-up steps, barrier, K timed steps, barrier (the
+COLD leg: `ms_per_step_cold`), the plain-copy calibration of this box's HBM ceiling (every rank, about 0.1 s),
+barrier, the same K timed steps again, barrier (`value`, `ms_per_step`: the streaming kernel's 20-30 ms start-up
+transient is behind it by then), with the streaming kernel's launches bracketed by HIP events in both legs
+(`roofline.achieved`, `launch_ms`).  `hbm_copy_kernel_when` in the line says so; LYNX_BENCH_CALIBRATE_FIRST=0: no
+cold leg, calibration last.
 
 N > 1: one process per GPU.  Started plainly (`WORLD_SIZE` not in the environment) this process
 becomes the LAUNCHER: it starts N fresh children of itself with RANK / LOCAL_RANK / WORLD_SIZE and a
@@ -266,6 +271,68 @@ def cpu_baseline(name, particles, cells, dtype, budget_s=10.0):
                            "sample": f"{bs} samples x {n} particles x {E} elements, {reps} passes in {dt:.1f} s"}}
 
 
+DUMP_LIMIT_BYTES = 64 << 20      # everything --dump-outputs writes
+DUMP_PARTICLE_BYTES = 32 << 20   # of which the sample of the outgoing particles
+DUMP_MAX_SAMPLES = 64
+# entries every moment record carries (include/lynx_hip.h): the 7 means, the six variances, cov(x, x'), cov(y, y');
+# a record of the property set marks the rest of the covariance with NaN
+RECORD_PROPERTY_SET = list(range(7)) + [7, 8, 13, 18, 19, 22, 25, 27]
+RECORD_KEEP = RECORD_PROPERTY_SET + [35]  # ... and the particle count
+
+
+def particle_sample(rt, beam, seed=0):
+    """
+    A fixed, seeded sample of `beam`'s particles, (samples, particles, 7): at most DUMP_MAX_SAMPLES samples of the batch
+    and in each the same particles, all of them when they fit in DUMP_PARTICLE_BYTES.  Only the chosen samples are
+    copied from HBM.
+    """
+    p = beam.particles  # a DeviceArray while the beam lives in HBM only
+    n_samples, n = int(np.prod(p.shape[:-2], dtype=np.int64)), int(p.shape[-2])
+    rng = np.random.default_rng(seed)
+    rows = np.sort(rng.choice(n_samples, size=min(n_samples, DUMP_MAX_SAMPLES), replace=False))
+    keep = min(n, DUMP_PARTICLE_BYTES // (len(rows) * 7 * np.dtype(p.dtype).itemsize))
+    cols = np.sort(rng.choice(n, size=keep, replace=False)) if keep < n else slice(None)
+    if isinstance(p, np.ndarray):
+        return np.ascontiguousarray(p.reshape(n_samples, n, 7)[rows][:, cols])
+    out = np.empty((len(rows), keep, 7), p.dtype)
+    row = np.empty((n, 7), p.dtype)
+    for i, r in enumerate(rows):
+        rt.check(rt.lib.lynx_buf_d2h(rt.ctx, row.ctypes.data, p.ptr + int(r) * row.nbytes, row.nbytes))
+        out[i] = row[cols]
+    return out
+
+
+def dump_outputs(directory: Path, rt, segment, out, extra, grad: bool, counts):
+    """
+    What the last timed step returned to its caller, as `directory/<name>.npy`, float32 or float64, finite,
+    DUMP_LIMIT_BYTES at most: `particles` -- `particle_sample` of the outgoing beam (the same samples and particles for
+    the same arguments), `energy` -- its energy per sample, `moments` -- the RECORD_KEEP entries of its fused moment
+    records when the step accumulated them, `moments_gathered` -- the same entries of every rank's records (N > 1; rank
+    r sent `counts[r]` rows, the rest is padding), `grad_energy` and `grad_<element index>_<parameter>` -- the reverse
+    pass's gradients (--grad).
+    """
+    arrays = {"particles": particle_sample(rt, out), "energy": out.energy}
+    if out._moments is not None:
+        arrays["moments"] = out.moment_record()[..., RECORD_KEEP]
+    if grad:
+        arrays["grad_energy"] = extra.energy
+        for i, element in enumerate(segment.elements):
+            if element in extra:
+                arrays.update({f"grad_{i:03d}_{name}": v for name, v in extra[element].items()})
+    elif extra is not None:
+        g = np.asarray(extra)
+        arrays["moments_gathered"] = np.concatenate([g[r, :n][:, RECORD_KEEP] for r, n in enumerate(counts)])
+    arrays = {name: np.asarray(v) for name, v in arrays.items()}
+    arrays = {name: v if v.dtype in (np.float32, np.float64) else v.astype(np.float64) for name, v in arrays.items()}
+    bad = [name for name, v in arrays.items() if not np.all(np.isfinite(v))]
+    assert not bad, f"bench: outputs that are not finite: {bad}"
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"bench: {total} bytes of outputs to dump, more than {DUMP_LIMIT_BYTES}"
+    directory.mkdir(parents=True, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(directory / f"{name}.npy", v)
+
+
 METRIC = "particle-element-steps/sec (whole node) + achieved HBM GB/s, Segment.track ParticleBeam"
 
 
@@ -402,7 +469,12 @@ def main():
                     help="N > 1: every GPU tracks the whole per-GPU workload (global batch = batch x N) instead of "
                          "a slice of ONE workload")
     ap.add_argument("--no-moments", action="store_true", help="track without the fused moment epilogue")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU-baseline legs, the cold leg, the plain-copy calibration and the per-launch "
+                         "kernel times (a plain run: warm-up and the K timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-baseline legs")
     ap.add_argument("--shared-input", action="store_true",
                     help="variant (SURVEY.md section 8d): ONE incoming beam broadcast lazily over the batch instead of "
                          "one physical beam per sample; reported with its own algorithmic bytes, never the default")
@@ -412,8 +484,8 @@ def main():
                     help="N > 1 only: if the RCCL communicator cannot be built, gather the moment records through the "
                          "rendezvous sockets instead of failing (config.gather says so); without it the run exits 3")
     ap.add_argument("--no-kernel-timing", action="store_true",
-                    help="do not bracket the streaming kernel with HIP events (then `roofline.achieved` is null): "
-                         "shows what the per-launch time stamps themselves cost a step")
+                    help="--full without bracketing the streaming kernel with HIP events (then `roofline.achieved` is "
+                         "null): shows what the per-launch time stamps themselves cost a step")
     ap.add_argument("--sync-every-step", action="store_true",
                     help="latency mode: wait for the GPU after every step (no overlap between consecutive calls)")
     ap.add_argument("--rendezvous-only", action="store_true",
@@ -426,7 +498,7 @@ def main():
         w = WORKLOADS[args.workload]
         parent_baseline = None
         # (a rehearsal runs it only when a test asks for it: LYNX_BENCH_TEST_CPU_BASELINE=1)
-        if not args.no_cpu_baseline and (not args.rendezvous_only or os.environ.get("LYNX_BENCH_TEST_CPU_BASELINE") == "1"):
+        if args.full and not args.no_cpu_baseline and (not args.rendezvous_only or os.environ.get("LYNX_BENCH_TEST_CPU_BASELINE") == "1"):
             parent_baseline = cpu_baseline(args.workload, args.particles or w[1], w[2], np.dtype(w[3]).type,
                                            budget_s=float(os.environ.get("LYNX_BENCH_CPU_BUDGET_S", "10")))
         sys.exit(launch_ranks(args.gpus, parent_baseline))
@@ -444,7 +516,7 @@ def main():
 
     # CPU baseline first: it forks worker processes, which must happen before this process opens the GPU
     baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rendezvous_only:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not args.rendezvous_only:
         baseline = cpu_baseline(args.workload, particles, cells, dtype,
                                 budget_s=float(os.environ.get("LYNX_BENCH_CPU_BUDGET_S", "10")))
     elif rank == 0 and os.environ.get("LYNX_BENCH_CPU_BASELINE_FILE"):  # the launcher parent ran it (N > 1)
@@ -458,7 +530,8 @@ def main():
     # this rank's piece of the job
     global_batch, sample_ids, my_particles, total_particles, parallelism = shard_of(batch, particles, world, rank, args.weak)
     my_batch = len(sample_ids)
-    rows = max(len(shard_of(batch, particles, world, r, args.weak)[1]) for r in range(world))  # gathered rows per rank
+    counts = [len(shard_of(batch, particles, world, r, args.weak)[1]) for r in range(world)]  # samples of every rank
+    rows = max(counts)  # gathered rows per rank
     strong = world > 1 and not args.weak
 
     rdzv = Rendezvous(rank, world)  # standard-library sockets; no second communication stack in the process
@@ -466,7 +539,7 @@ def main():
               "particles": total_particles, "particles_per_gpu": my_particles, "elements": None,
               "fused_moments": not args.no_moments, "reverse_pass": bool(args.grad),
               "incoming_beam": "one beam shared by the batch (lazy broadcast)" if args.shared_input else "one physical beam per sample",
-              "gather": "none", "parallelism": parallelism, "pipelined_calls": not args.sync_every_step,
+              "gather": "none", "parallelism": parallelism, "pipelined_calls": not args.sync_every_step, "full": args.full,
               "launcher": "none (one process)" if world == 1 and "WORLD_SIZE" not in os.environ
                           else "torchrun/external" if os.environ.get("TORCHELASTIC_RUN_ID") or "LYNX_RDZV_KEY" not in os.environ
                           else "bench.py"}
@@ -600,9 +673,11 @@ def main():
     # copies show none: profiles/r03_first_launches.txt), and five warm-up steps end inside it.
     # Behind the calibration's copies the kernel's second start is much milder (1.00 -> 0.94 over the 20 timed steps),
     # which is closer to what a long job sees.  LYNX_BENCH_CALIBRATE_FIRST=0 puts the calibration behind the timed
-    # region again (rank 0 of a one-GPU run only).
+    # region again (rank 0 of a one-GPU run only).  All of this is `--full` only: a plain run times the K steps
+    # right behind the W warm-up steps, without per-launch events.
     copy_gbs = None
     calibrate_first = os.environ.get("LYNX_BENCH_CALIBRATE_FIRST", "1") != "0"
+    kernel_timing = args.full and not args.no_kernel_timing
 
     def calibrate():
         nbytes = min(batch * particles * 7 * np.dtype(dtype).itemsize, 4 << 30)
@@ -619,7 +694,7 @@ def main():
         nonlocal last
         rdzv.barrier()
         rt.sync()
-        if not args.no_kernel_timing:
+        if kernel_timing:
             rt.profile_begin()
         t0 = time.perf_counter()
         for _ in range(steps):
@@ -627,16 +702,16 @@ def main():
         rt.sync()
         mine = time.perf_counter() - t0  # this rank's K steps, GPU drained
         rdzv.barrier()
-        kern_ms, launches = rt.profile_end() if not args.no_kernel_timing else (0.0, 0)
-        per_launch = rt.profile_launches() if not args.no_kernel_timing else []
-        gathers = rt.profile_gathers() if not args.no_kernel_timing else []
+        kern_ms, launches = rt.profile_end() if kernel_timing else (0.0, 0)
+        per_launch = rt.profile_launches() if kernel_timing else []
+        gathers = rt.profile_gathers() if kernel_timing else []
         return rdzv.max(mine), mine, kern_ms, launches, per_launch, gathers
 
-    # The same K steps twice.  COLD: right behind the W warm-up steps, as the command line says -- this is what a short
-    # job sees (`ms_per_step_cold`, `launch_ms_cold`).  Then the calibration copies, then the K steps `value` is
+    # --full: the same K steps twice.  COLD: right behind the W warm-up steps, as the command line says -- this is what
+    # a short job sees (`ms_per_step_cold`, `launch_ms_cold`).  Then the calibration copies, then the K steps `value` is
     # computed from (LYNX_BENCH_CALIBRATE_FIRST=0: no cold leg, calibration behind the timed region).
     cold = None
-    if calibrate_first:
+    if args.full and calibrate_first:
         cold = timed(args.steps)
         copy_gbs = calibrate()
     elapsed, my_elapsed, kern_ms, launches, per_launch, gather_ms = timed(args.steps)
@@ -649,7 +724,7 @@ def main():
     if out._moments is not None:
         rec = out.moment_record()
         have = ~np.isnan(rec)  # a property-set record marks the covariance entries it does not carry with NaN
-        assert np.all(have[..., :7]) and np.all(have[..., [7, 8, 13, 18, 19, 22, 25, 27]]), "bench: moments missing"
+        assert np.all(have[..., RECORD_PROPERTY_SET]), "bench: moments missing"
         assert np.all(np.isfinite(rec[have])) and np.all(rec[..., 35] == particles), "bench: bad moment records"
     if gathered is not None and not args.grad:
         g = np.asarray(gathered)
@@ -670,7 +745,10 @@ def main():
             assert whole.shape == (global_batch, 36) and np.all(whole[:, 35] == total_particles), "bench: bad gathered records"
             assert np.all(np.isfinite(whole[~np.isnan(whole)])), "bench: bad gathered records"
 
-    if not calibrate_first and rank == 0 and world == 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(Path(args.dump_outputs), rt, segment, out, gathered, args.grad, counts)
+
+    if args.full and not calibrate_first and rank == 0 and world == 1:
         copy_gbs = calibrate()
 
     # HBM traffic of the streaming kernel as measured with rocprofv3 PMC counters (separate
@@ -738,7 +816,8 @@ def main():
             # the practical ceiling: best plain-copy shape measured in this process (MI355X_MICROARCH.md: ~6.3 TB/s)
             "hbm_copy_kernel_gbs": max(copy_gbs.values()) if copy_gbs else None,
             "hbm_copy_kernel_shapes": copy_gbs,
-            "hbm_copy_kernel_when": "between the cold leg (W warm-up steps + K timed steps: ms_per_step_cold) and the timed region of `value`"
+            "hbm_copy_kernel_when": None if not args.full
+                                    else "between the cold leg (W warm-up steps + K timed steps: ms_per_step_cold) and the timed region of `value`"
                                     if calibrate_first else "after the timed region",
             "device": rt.info(),
         }

@@ -7,7 +7,7 @@ tail -3 $OUT/pytest.log
 run() { local name=$1; shift
   for mode in p w; do
     extra=""; [ $mode == w ] && extra="--sync-every-step"
-    env "$@" timeout -k 10 200 python bench.py --workload c2 --steps 1000 --warmup 50 --no-cpu-baseline --no-kernel-timing $extra > $OUT/${name}_$mode.json 2> $OUT/${name}_$mode.err
+    env "$@" timeout -k 10 200 python bench.py --full --workload c2 --steps 1000 --warmup 50 --no-cpu-baseline --no-kernel-timing $extra > $OUT/${name}_$mode.json 2> $OUT/${name}_$mode.err
     python - $OUT/${name}_$mode.json $name $mode <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -7,34 +7,34 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 S=${SERIES:-a}; OUT=gpurun_out/prof_r4_$S; rm -rf $OUT; mkdir -p $OUT
 for w in c4 c4a c3 c3big c5 c2; do
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$w -- python3 bench.py --workload $w --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_$w.json 2> $OUT/trace_$w.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$w -- python3 bench.py --full --workload $w --steps 10 --warmup 2 --no-cpu-baseline > $OUT/trace_$w.json 2> $OUT/trace_$w.err
 done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c5grad -- python3 bench.py --workload c5 --grad --steps 5 --warmup 1 --no-cpu-baseline > $OUT/trace_c5grad.json 2> $OUT/trace_c5grad.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_c5grad -- python3 bench.py --full --workload c5 --grad --steps 5 --warmup 1 --no-cpu-baseline > $OUT/trace_c5grad.json 2> $OUT/trace_c5grad.err
 for w in c4 c4a c3big c5; do
-  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$w -- python3 bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_fetch_$w.json 2> $OUT/pmc_fetch_$w.err
-  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$w -- python3 bench.py --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_write_$w.json 2> $OUT/pmc_write_$w.err
+  timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_$w -- python3 bench.py --full --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_fetch_$w.json 2> $OUT/pmc_fetch_$w.err
+  timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_$w -- python3 bench.py --full --workload $w --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_write_$w.json 2> $OUT/pmc_write_$w.err
 done
 echo "progress: traces and traffic counters done"
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/default.json 2> $OUT/default.err
-LYNX_FORCE_COMM=1 timeout -k 10 300 python bench.py --no-cpu-baseline --steps 10 > $OUT/rccl_world1.json 2> $OUT/rccl_world1.err
-timeout -k 10 300 python bench.py --workload c4a --steps 20 --warmup 5 > $OUT/c4a_default.json 2> $OUT/c4a_default.err
+timeout -k 10 400 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/default.json 2> $OUT/default.err
+LYNX_FORCE_COMM=1 timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 > $OUT/rccl_world1.json 2> $OUT/rccl_world1.err
+timeout -k 10 300 python bench.py --full --workload c4a --steps 20 --warmup 5 > $OUT/c4a_default.json 2> $OUT/c4a_default.err
 for w in c3 c2; do
-  timeout -k 10 200 python bench.py --workload $w --steps 300 --warmup 20 --no-cpu-baseline > $OUT/steady_$w.json 2> $OUT/steady_$w.err
-  timeout -k 10 200 python bench.py --workload $w --steps 300 --warmup 20 --no-cpu-baseline --sync-every-step > $OUT/latency_$w.json 2> $OUT/latency_$w.err
+  timeout -k 10 200 python bench.py --full --workload $w --steps 300 --warmup 20 --no-cpu-baseline > $OUT/steady_$w.json 2> $OUT/steady_$w.err
+  timeout -k 10 200 python bench.py --full --workload $w --steps 300 --warmup 20 --no-cpu-baseline --sync-every-step > $OUT/latency_$w.json 2> $OUT/latency_$w.err
 done
 PYTHONPATH=$GRAFT_REPO_ROOT timeout -k 10 300 python scripts/gpu/latency.py > $OUT/latency_table.json 2> $OUT/latency_table.err
 echo "progress: bench lines done"
 for rep in 1 2 3; do for b in 1024 512 256 128; do
-  LYNX_FORCE_COMM=1 LYNX_PLAIN_EVENTS=1 timeout -k 10 200 python bench.py --no-cpu-baseline --batch $b --steps 60 --warmup 5 > $OUT/shard_b${b}_$rep.json 2> $OUT/shard_b${b}_$rep.err
+  LYNX_FORCE_COMM=1 LYNX_PLAIN_EVENTS=1 timeout -k 10 200 python bench.py --full --no-cpu-baseline --batch $b --steps 60 --warmup 5 > $OUT/shard_b${b}_$rep.json 2> $OUT/shard_b${b}_$rep.err
 done; done
 for un in 1 0; do
-  LYNX_TRACK_UNITS=$un timeout -k 10 200 python bench.py --workload c5 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/c5_units$un.json 2> $OUT/c5_units$un.err
+  LYNX_TRACK_UNITS=$un timeout -k 10 200 python bench.py --full --workload c5 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/c5_units$un.json 2> $OUT/c5_units$un.err
 done
-LYNX_UNIT_PAIRS=0 timeout -k 10 200 python bench.py --workload c5 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/c5_general.json 2> $OUT/c5_general.err
-timeout -k 10 300 python bench.py --workload c5 --steps 20 --warmup 3 > $OUT/c5_default.json 2> $OUT/c5_default.err
-timeout -k 10 200 python bench.py --workload c5 --grad --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c5grad.json 2> $OUT/c5grad.err
-LYNX_BWD_UNITS=0 timeout -k 10 200 python bench.py --workload c5 --grad --steps 10 --warmup 2 --no-cpu-baseline > $OUT/c5grad_dense.json 2> $OUT/c5grad_dense.err
-timeout -k 10 200 python bench.py --workload c3big --steps 100 --warmup 5 --no-cpu-baseline > $OUT/steady_c3big.json 2> $OUT/steady_c3big.err
+LYNX_UNIT_PAIRS=0 timeout -k 10 200 python bench.py --full --workload c5 --steps 40 --warmup 5 --no-cpu-baseline > $OUT/c5_general.json 2> $OUT/c5_general.err
+timeout -k 10 300 python bench.py --full --workload c5 --steps 20 --warmup 3 > $OUT/c5_default.json 2> $OUT/c5_default.err
+timeout -k 10 200 python bench.py --full --workload c5 --grad --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c5grad.json 2> $OUT/c5grad.err
+LYNX_BWD_UNITS=0 timeout -k 10 200 python bench.py --full --workload c5 --grad --steps 10 --warmup 2 --no-cpu-baseline > $OUT/c5grad_dense.json 2> $OUT/c5grad_dense.err
+timeout -k 10 200 python bench.py --full --workload c3big --steps 100 --warmup 5 --no-cpu-baseline > $OUT/steady_c3big.json 2> $OUT/steady_c3big.err
 echo "progress: shards and config 5 done"
 bash scripts/gpu/r4/pmc_grad.sh prof_r4_$S/pmc_c5 > $OUT/pmc_c5.log 2>&1
 bash scripts/gpu/r4/timeline.sh prof_r4_$S/timeline > $OUT/timeline.txt 2>&1

@@ -3,7 +3,7 @@
 # pass over the SAME incoming beam left in the 256 MB Infinity Cache is what the next pass reads first.
 TAG=${1:-r4alt}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 run() { local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"
+  timeout -k 10 300 python bench.py --full "$@" --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"
   python - $OUT/$name.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for n in 4 5 6; do
   OUT=gpurun_out/r4bwdphase_$n; mkdir -p $OUT
-  LYNX_HIP_LIBRARY=$GRAFT_REPO_ROOT/build/liblynxhip_stop$n.so timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --workload c5 --grad --steps 6 --warmup 2 --no-cpu-baseline > $OUT/b.json 2> $OUT/b.err
+  LYNX_HIP_LIBRARY=$PWD/build/liblynxhip_stop$n.so timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --workload c5 --grad --steps 6 --warmup 2 --no-cpu-baseline > $OUT/b.json 2> $OUT/b.err
   python3 - $OUT $n <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/trace/**/*kernel_stats.csv", recursive=True)

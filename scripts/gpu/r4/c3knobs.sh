@@ -4,7 +4,7 @@ OUT=gpurun_out/r4c3knobs; mkdir -p $OUT
 run() { local name=$1; shift
   for mode in p w; do
     extra=""; [ $mode == w ] && extra="--sync-every-step"
-    env "$@" timeout -k 10 200 python bench.py --workload c3 --steps 300 --warmup 20 --no-cpu-baseline $extra > $OUT/${name}_$mode.json 2> $OUT/${name}_$mode.err
+    env "$@" timeout -k 10 200 python bench.py --full --workload c3 --steps 300 --warmup 20 --no-cpu-baseline $extra > $OUT/${name}_$mode.json 2> $OUT/${name}_$mode.err
     python - $OUT/${name}_$mode.json $name $mode <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

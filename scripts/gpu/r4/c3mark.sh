@@ -6,7 +6,7 @@ for mode in p w; do
   extra=""; [ $mode == w ] && extra="--sync-every-step"
   for kt in timing notiming; do
     flag=""; [ $kt == notiming ] && flag="--no-kernel-timing"
-    timeout -k 10 200 python bench.py --workload c3 --steps 300 --warmup 20 --no-cpu-baseline $flag $extra > $OUT/c3_${mode}_${kt}_$rep.json 2> $OUT/c3_${mode}_${kt}_$rep.err
+    timeout -k 10 200 python bench.py --full --workload c3 --steps 300 --warmup 20 --no-cpu-baseline $flag $extra > $OUT/c3_${mode}_${kt}_$rep.json 2> $OUT/c3_${mode}_${kt}_$rep.err
     python - $OUT/c3_${mode}_${kt}_$rep.json $mode $kt <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -3,7 +3,7 @@
 # moment epilogue, by tiles per workgroup and particles per lane.
 OUT=gpurun_out/${1:-r4c3parts}; mkdir -p $OUT
 run() { local name=$1; shift; local extra=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --workload c3 --steps 200 --warmup 20 --no-cpu-baseline $extra > $OUT/$name.json 2> $OUT/$name.err
+  env "$@" timeout -k 10 200 python bench.py --full --workload c3 --steps 200 --warmup 20 --no-cpu-baseline $extra > $OUT/$name.json 2> $OUT/$name.err
   python - $OUT/$name.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -2,7 +2,7 @@
 # Round 4: BASELINE config 3 with at most LYNX_ONE_ROUND workgroups per CU in the launch (pipelined, waited for, without moments).
 OUT=gpurun_out/${1:-r4c3round}; mkdir -p $OUT
 run() { local name=$1; shift; local extra=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --workload c3 --steps 200 --warmup 20 --no-cpu-baseline $extra > $OUT/$name.json 2> $OUT/$name.err
+  env "$@" timeout -k 10 200 python bench.py --full --workload c3 --steps 200 --warmup 20 --no-cpu-baseline $extra > $OUT/$name.json 2> $OUT/$name.err
   python - $OUT/$name.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -10,7 +10,7 @@ grep -A8 "structured-dense" $OUT/pytest_grad.log | head -10
 for rep in 1 2; do
   for mode in fwd grad; do
     extra=""; [ $mode == grad ] && extra="--grad"
-    timeout -k 10 200 python bench.py --workload c5 $extra --steps 30 --warmup 5 --no-cpu-baseline > $OUT/c5_${mode}_$rep.json 2> $OUT/c5_${mode}_$rep.err || echo "c5 $mode failed"
+    timeout -k 10 200 python bench.py --full --workload c5 $extra --steps 30 --warmup 5 --no-cpu-baseline > $OUT/c5_${mode}_$rep.json 2> $OUT/c5_${mode}_$rep.err || echo "c5 $mode failed"
     python - $OUT/c5_${mode}_$rep.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

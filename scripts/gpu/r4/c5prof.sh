@@ -4,7 +4,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 TAG=${1:-r4c5prof}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for e in "$@"; do export "$e"; done
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --workload c5 --grad --steps 10 --warmup 2 --no-cpu-baseline > $OUT/c5grad.json 2> $OUT/c5grad.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --workload c5 --grad --steps 10 --warmup 2 --no-cpu-baseline > $OUT/c5grad.json 2> $OUT/c5grad.err
 python3 - $OUT <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/trace/**/*kernel_stats.csv", recursive=True)

@@ -3,7 +3,7 @@
 # system-scope fence; 1 = hipEventReleaseToDevice; 2 = hipEventDisableSystemFence) over the workloads.  Usage: evscope.sh <tag>
 TAG=${1:-r4evscope}; OUT=gpurun_out/$TAG; mkdir -p $OUT
 run() { local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"
+  timeout -k 10 300 python bench.py --full "$@" --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"
   python - $OUT/$name.json $name <<'PY'
 import json, sys
 try:

@@ -10,7 +10,7 @@ echo "pytest exit $?" | tee -a $OUT/pytest.log
 tail -5 $OUT/pytest.log
 run() {  # name, args...
   local name=$1; shift
-  timeout -k 10 300 python bench.py "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed ($?)"
+  timeout -k 10 300 python bench.py --full "$@" > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed ($?)"
   python - "$OUT/$name.json" <<'PY'
 import json, sys
 try:

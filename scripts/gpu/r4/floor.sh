@@ -10,9 +10,9 @@ for kv in unset 0 1; do
     for mode in p w; do
       extra=""; [ $mode == w ] && extra="--sync-every-step"
       if [ $kv == unset ]; then
-        timeout -k 10 200 python bench.py --workload $w --steps 300 --warmup 20 --no-cpu-baseline $extra > $OUT/${w}_${mode}_kernarg_$kv.json 2> $OUT/${w}_${mode}_kernarg_$kv.err
+        timeout -k 10 200 python bench.py --full --workload $w --steps 300 --warmup 20 --no-cpu-baseline $extra > $OUT/${w}_${mode}_kernarg_$kv.json 2> $OUT/${w}_${mode}_kernarg_$kv.err
       else
-        HIP_FORCE_DEV_KERNARG=$kv timeout -k 10 200 python bench.py --workload $w --steps 300 --warmup 20 --no-cpu-baseline $extra > $OUT/${w}_${mode}_kernarg_$kv.json 2> $OUT/${w}_${mode}_kernarg_$kv.err
+        HIP_FORCE_DEV_KERNARG=$kv timeout -k 10 200 python bench.py --full --workload $w --steps 300 --warmup 20 --no-cpu-baseline $extra > $OUT/${w}_${mode}_kernarg_$kv.json 2> $OUT/${w}_${mode}_kernarg_$kv.err
       fi
       python - $OUT/${w}_${mode}_kernarg_$kv.json $w $mode $kv <<'PY'
 import json, sys

@@ -5,7 +5,7 @@ TAG=${1:-r4h}; shift
 OUT=gpurun_out/$TAG; mkdir -p $OUT
 for e in "$@"; do export "$e"; done
 run() { local name=$1; shift
-  timeout -k 10 200 python bench.py "$@" --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"
+  timeout -k 10 200 python bench.py --full "$@" --no-cpu-baseline > $OUT/$name.json 2> $OUT/$name.err || echo "$name failed"
   python - $OUT/$name.json <<'PY'
 import json, sys
 try:

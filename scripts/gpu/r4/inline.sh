@@ -8,7 +8,7 @@ tail -4 $OUT/pytest.log
 run() { local name=$1; shift
   for w in c2 c3; do for mode in p w; do
     extra=""; [ $mode == w ] && extra="--sync-every-step"
-    env "$@" timeout -k 10 200 python bench.py --workload $w --steps 500 --warmup 50 --no-cpu-baseline --no-kernel-timing $extra > $OUT/${name}_${w}_$mode.json 2> $OUT/${name}_${w}_$mode.err
+    env "$@" timeout -k 10 200 python bench.py --full --workload $w --steps 500 --warmup 50 --no-cpu-baseline --no-kernel-timing $extra > $OUT/${name}_${w}_$mode.json 2> $OUT/${name}_${w}_$mode.err
     python - $OUT/${name}_${w}_$mode.json $name $w $mode <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -5,7 +5,7 @@ OUT=gpurun_out/r4ldsmap; mkdir -p $OUT
 for rep in 1 2 3; do
   for v in base ldsmap; do
     lib=lynx_amd/_lib/liblynxhip.so; [ $v == ldsmap ] && lib=build/liblynxhip_ldsmap.so
-    LYNX_HIP_LIBRARY=$PWD/$lib timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${v}_$rep.json 2> $OUT/${v}_$rep.err
+    LYNX_HIP_LIBRARY=$PWD/$lib timeout -k 10 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${v}_$rep.json 2> $OUT/${v}_$rep.err
     python - $OUT/${v}_$rep.json $v <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r = d["roofline"]

@@ -3,8 +3,8 @@
 # every workload), into gpurun_out/<tag>/c5_pmc_traffic.json.
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 OUT=gpurun_out/${1:-r4pmc_c5}; mkdir -p $OUT
-timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c5 -- python3 bench.py --workload c5 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_fetch_c5.json 2> $OUT/pmc_fetch_c5.err || exit 1
-timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c5 -- python3 bench.py --workload c5 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_write_c5.json 2> $OUT/pmc_write_c5.err || exit 1
+timeout -k 10 300 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch_c5 -- python3 bench.py --full --workload c5 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_fetch_c5.json 2> $OUT/pmc_fetch_c5.err || exit 1
+timeout -k 10 300 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/pmc_write_c5 -- python3 bench.py --full --workload c5 --steps 5 --warmup 1 --no-cpu-baseline > $OUT/pmc_write_c5.json 2> $OUT/pmc_write_c5.err || exit 1
 python3 - $OUT <<'PY'
 import csv, glob, collections, json, sys
 out = sys.argv[1]

@@ -6,7 +6,7 @@ G1="SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_AN
 G2="SQ_INSTS_VALU SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS SQ_INSTS_VMEM_RD"
 G3="GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VMEM_WR SQ_INST_CYCLES_VMEM"
 for g in G1 G2 G3; do eval grp=\$$g
-  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/grad_$g -- python3 bench.py --workload c5 --grad --steps 3 --warmup 1 --no-cpu-baseline > $OUT/grad_$g.json 2> $OUT/grad_$g.err || echo "failed: $g"
+  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d $OUT/grad_$g -- python3 bench.py --full --workload c5 --grad --steps 3 --warmup 1 --no-cpu-baseline > $OUT/grad_$g.json 2> $OUT/grad_$g.err || echo "failed: $g"
 done
 python3 - <<PY
 import csv,glob,collections,json,os

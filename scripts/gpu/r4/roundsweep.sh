@@ -2,7 +2,7 @@
 # Round 4: the same cap (LYNX_ONE_ROUND) over launches of many rounds: c3big, the 128-sample shard of config 4, config 4, config 2.
 OUT=gpurun_out/${1:-r4roundsweep}; mkdir -p $OUT
 run() { local name=$1; shift; local extra=$1; shift
-  env "$@" timeout -k 10 200 python bench.py --no-cpu-baseline $extra > $OUT/$name.json 2> $OUT/$name.err
+  env "$@" timeout -k 10 200 python bench.py --full --no-cpu-baseline $extra > $OUT/$name.json 2> $OUT/$name.err
   python - $OUT/$name.json $name <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

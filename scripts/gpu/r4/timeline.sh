@@ -8,7 +8,7 @@ for e in "$@"; do export "$e"; done
 for w in c3 c2; do
   for mode in pipelined waited; do
     extra=""; [ $mode == waited ] && extra="--sync-every-step"
-    timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/${w}_$mode -- python3 bench.py --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-timing $extra > $OUT/${w}_$mode.json 2> $OUT/${w}_$mode.err
+    timeout -k 10 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/${w}_$mode -- python3 bench.py --full --workload $w --steps 30 --warmup 5 --no-cpu-baseline --no-kernel-timing $extra > $OUT/${w}_$mode.json 2> $OUT/${w}_$mode.err
     python3 - $OUT/${w}_$mode <<'PY'
 import csv, glob, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)

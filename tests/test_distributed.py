@@ -340,8 +340,13 @@ def test_bench_launcher_retries_once_without_the_ipc_variable_when_every_rank_fa
 
 def test_bench_launcher_runs_the_cpu_baseline_before_the_ranks_and_rank_0_reports_it():
     """N > 1: the CPU-baseline legs run in the launcher parent (they fork; no rank waits for them) and reach the line."""
-    rc, lines, err = _bench("--gpus", "2", "--rendezvous-only", "--particles", "2000",
+    rc, lines, err = _bench("--gpus", "2", "--rendezvous-only", "--particles", "2000", "--full",
                             env={"LYNX_BENCH_TEST_CPU_BASELINE": "1", "LYNX_BENCH_CPU_BUDGET_S": "0.2"})
     assert rc == 0, err
     base = lines[0]["cpu_baseline"]
     assert base["kind"] == "port" and base["value"] > 0 and base["cores"] >= 1 and base["one_thread"]["value"] > 0
+    # a plain run (no --full) leaves them out
+    rc, lines, err = _bench("--gpus", "2", "--rendezvous-only", "--particles", "2000",
+                            env={"LYNX_BENCH_TEST_CPU_BASELINE": "1", "LYNX_BENCH_CPU_BUDGET_S": "0.2"})
+    assert rc == 0, err
+    assert "cpu_baseline" not in lines[0] and lines[0]["config"]["full"] is False
