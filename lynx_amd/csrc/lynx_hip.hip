@@ -127,7 +127,13 @@ struct lynx_ctx {
     }
   } fwd_table;
   const void* main_wrote = nullptr;   // energy buffer the last streaming kernel published on the main stream
-  std::mutex mu;                      // allocator maps: finalizers may run on other threads
+  std::mutex mu;                      // allocator maps and fwd_table: finalizers may run on other threads
+  // every entry point that writes device memory on the caller's behalf says so here, under the lock
+  void wrote(const void* dst, size_t bytes) {
+    if (!dst || bytes == 0) return;
+    std::lock_guard<std::mutex> lock(mu);
+    fwd_table.written(dst, bytes);
+  }
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;
   // host-mapped status words the kernels can raise a flag in (k_cavity_flags: energy <= 0 at a cavity); the host
   // looks at them whenever it has waited for the GPU anyway
@@ -267,6 +273,12 @@ static int fail(lynx_ctx* ctx, int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+
+// the context (or lattice) an entry point is handed: NULL is an argument error, answered before anything touches it
+#define LYNX_NEED(p)                                                                        \
+  do {                                                                                      \
+    if (!(p)) return fail(nullptr, LYNX_ERR_INVALID, "null " #p);                           \
+  } while (0)
 
 #define HIP_TRY(ctx, expr)                                                                  \
   do {                                                                                      \
@@ -632,6 +644,7 @@ int lynx_ctx_destroy(lynx_ctx* ctx) {
 const char* lynx_last_error(lynx_ctx* ctx) { return ctx ? ctx->err.c_str() : g_err.c_str(); }
 
 int lynx_device_info(lynx_ctx* ctx, lynx_device_info_t* out) {
+  LYNX_NEED(ctx);
   memset(out, 0, sizeof(*out));
   snprintf(out->arch, sizeof(out->arch), "%s", ctx->prop.gcnArchName);
   // some driver stacks report no marketing name: the architecture then stands in for it
@@ -707,6 +720,7 @@ static int join_side(lynx_ctx* ctx) {
 }
 
 int lynx_sync(lynx_ctx* ctx) {
+  LYNX_NEED(ctx);
   HIP_TRY(ctx, use_device(ctx));
   HIP_TRY(ctx, sync_main(ctx));
   const int rc = wait_for_side(ctx);
@@ -714,12 +728,14 @@ int lynx_sync(lynx_ctx* ctx) {
 }
 
 int lynx_timer_start(lynx_ctx* ctx) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
   return LYNX_OK;
 }
 
 int lynx_timer_stop(lynx_ctx* ctx, float* elapsed_ms) {
+  LYNX_NEED(ctx);
   HIP_TRY(ctx, hipEventRecord(ctx->ev_stop, ctx->stream));
   HIP_TRY(ctx, hipEventSynchronize(ctx->ev_stop));
   ctx->main_idle = true;
@@ -728,6 +744,7 @@ int lynx_timer_stop(lynx_ctx* ctx, float* elapsed_ms) {
 }
 
 int lynx_profile_begin(lynx_ctx* ctx) {
+  LYNX_NEED(ctx);
   // events of an earlier, unfinished profile may still stand in for step-table slots' "streamed" events: nothing may
   // wait on them once they are destroyed
   if (!ctx->prof_events.empty()) {
@@ -751,6 +768,7 @@ int lynx_profile_begin(lynx_ctx* ctx) {
 }
 
 int lynx_profile_end(lynx_ctx* ctx, double* total_ms, int64_t* launches) {
+  LYNX_NEED(ctx);
   ctx->profiling = false;
   HIP_TRY(ctx, sync_main(ctx));
   // every build is followed by its streaming kernel on the main stream, so both streams are idle now;
@@ -808,6 +826,7 @@ int lynx_ctx_reload_knobs(lynx_ctx* ctx) {
 }
 
 int lynx_buf_alloc(lynx_ctx* ctx, size_t bytes, void** d_out) {
+  LYNX_NEED(ctx);
   HIP_TRY(ctx, use_device(ctx));
   return ctx_alloc(ctx, bytes, d_out);
 }
@@ -816,19 +835,21 @@ int lynx_buf_alloc(lynx_ctx* ctx, size_t bytes, void** d_out) {
 // ones come from host memory the GPU writes through, so that lynx_buf_d2h is a wait and a memcpy (ctx_alloc_host_visible);
 // large ones, and all of them once the context has a communicator, are device memory like any other block.
 int lynx_buf_alloc_result(lynx_ctx* ctx, size_t bytes, void** d_out) {
+  LYNX_NEED(ctx);
   HIP_TRY(ctx, use_device(ctx));
   if (bytes <= kHostVisibleMax && ctx->comm_ranks == 0 && ctx->knobs.host_visible_records) return ctx_alloc_host_visible(ctx, bytes, d_out);
   return ctx_alloc(ctx, bytes, d_out);
 }
 
 int lynx_buf_free(lynx_ctx* ctx, void* d_ptr) {
-  if (ctx && d_ptr) ctx->fwd_table.written(d_ptr, 1);  // (a freed energy block may come back with other contents)
+  if (ctx && d_ptr) ctx->wrote(d_ptr, 1);  // (a freed energy block may come back with other contents)
   return ctx_free(ctx, d_ptr);
 }
 
 int lynx_buf_h2d(lynx_ctx* ctx, void* d_dst, const void* h_src, size_t bytes) {
+  LYNX_NEED(ctx);
   if (bytes == 0) return LYNX_OK;
-  ctx->fwd_table.written(d_dst, bytes);
+  ctx->wrote(d_dst, bytes);
   if (is_host_visible(ctx, d_dst)) {  // host memory the GPU reads through: wait for whoever still uses it, then write
     const int rc = wait_for_side(ctx);
     if (rc) return rc;
@@ -842,6 +863,7 @@ int lynx_buf_h2d(lynx_ctx* ctx, void* d_dst, const void* h_src, size_t bytes) {
 }
 
 int lynx_buf_d2h(lynx_ctx* ctx, void* h_dst, const void* d_src, size_t bytes) {
+  LYNX_NEED(ctx);
   if (bytes == 0) return LYNX_OK;
   {
     const int rc = wait_for_side(ctx);  // the block may be a moment record or a gathered block
@@ -858,13 +880,14 @@ int lynx_buf_d2h(lynx_ctx* ctx, void* h_dst, const void* d_src, size_t bytes) {
 }
 
 int lynx_buf_d2d(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (bytes == 0) return LYNX_OK;
   {
     const int rc = join_side(ctx);  // the source may be a moment record the side stream is still reducing
     if (rc) return rc;
   }
-  ctx->fwd_table.written(d_dst, bytes);
+  ctx->wrote(d_dst, bytes);
   // (either side may be a host-visible block: the runtime works the direction out from the addresses)
   HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDefault, ctx->stream));
   ctx->main_dirty = true;
@@ -872,19 +895,21 @@ int lynx_buf_d2d(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes) {
 }
 
 int lynx_buf_memset(lynx_ctx* ctx, void* d_dst, int value, size_t bytes) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (bytes == 0) return LYNX_OK;
   {
     const int rc = join_side(ctx);
     if (rc) return rc;
   }
-  ctx->fwd_table.written(d_dst, bytes);
+  ctx->wrote(d_dst, bytes);
   HIP_TRY(ctx, hipMemsetAsync(d_dst, value, bytes, ctx->stream));
   ctx->main_dirty = true;
   return LYNX_OK;
 }
 
 int lynx_pool_trim(lynx_ctx* ctx) {
+  LYNX_NEED(ctx);
   HIP_TRY(ctx, hipStreamSynchronize(ctx->s_build));
   HIP_TRY(ctx, sync_main(ctx));
   {
@@ -945,6 +970,7 @@ static int sync_pool(lynx_ctx* ctx, lynx_lattice* lat) {
 int lynx_lattice_create(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_elems,
                         const lynx_elem* elems, int32_t n_steps, const lynx_step* steps,
                         const void* pool, int64_t pool_count, lynx_lattice** out) {
+  LYNX_NEED(ctx);
   *out = nullptr;
   if (dtype != LYNX_F32 && dtype != LYNX_F64) return fail(ctx, LYNX_ERR_INVALID, "bad dtype");
   if (batch <= 0 || n_elems < 0 || n_steps < 0 || pool_count < 0)
@@ -1039,6 +1065,7 @@ int lynx_lattice_create(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_elems
 }
 
 int lynx_lattice_update_params(lynx_lattice* lat, int64_t offset, int64_t count, const void* host) {
+  LYNX_NEED(lat);
   lynx_ctx* ctx = lat->ctx;
   if (offset < 0 || count < 0 || offset + count > lat->pool_count)
     return fail(ctx, LYNX_ERR_INVALID, "lynx_lattice_update_params: range outside the pool");
@@ -1055,6 +1082,7 @@ int lynx_lattice_update_params(lynx_lattice* lat, int64_t offset, int64_t count,
 }
 
 int lynx_lattice_set_flags(lynx_lattice* lat, const int32_t* elem_flags, const int32_t* step_flags) {
+  LYNX_NEED(lat);
   lynx_ctx* ctx = lat->ctx;
   for (int32_t e = 0; e < lat->n_elems; ++e) lat->h_elems[e].flags = elem_flags[e];
   for (int32_t s = 0; s < lat->n_steps; ++s) lat->h_steps[s].flags = step_flags[s];
@@ -1073,7 +1101,10 @@ int lynx_lattice_set_flags(lynx_lattice* lat, const int32_t* elem_flags, const i
 int lynx_lattice_destroy(lynx_lattice* lat) {
   if (!lat) return LYNX_OK;
   lynx_ctx* ctx = lat->ctx;
-  if (ctx->fwd_table.lat == lat) ctx->fwd_table.valid = false;  // (the next lattice may get this address)
+  {
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (ctx->fwd_table.lat == lat) ctx->fwd_table.valid = false;  // (the next lattice may get this address)
+  }
   ctx_free(ctx, lat->d_elems);
   ctx_free(ctx, lat->d_steps);
   ctx_free(ctx, lat->d_elem_step);
@@ -1206,10 +1237,14 @@ static int plan_lanes_build(lynx_ctx* ctx, lynx_lattice* lat, int L) {
       (rc = ctx_alloc(ctx, std::max<size_t>(1, tasks.size()) * sizeof(PairTask), (void**)&lat->d_tasks)) ||
       (rc = ctx_alloc(ctx, step_slot.size() * sizeof(int32_t), (void**)&lat->d_step_slot)))
     return rc;
-  // plain synchronous copies: planning happens once per lattice structure
-  HIP_TRY(ctx, hipMemcpy(lat->d_pieces, pieces.data(), pieces.size() * sizeof(BuildPiece), hipMemcpyHostToDevice));
-  if (!tasks.empty()) HIP_TRY(ctx, hipMemcpy(lat->d_tasks, tasks.data(), tasks.size() * sizeof(PairTask), hipMemcpyHostToDevice));
-  HIP_TRY(ctx, hipMemcpy(lat->d_step_slot, step_slot.data(), step_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  // copies on the main stream and a wait for them (planning happens once per lattice structure): the blocks come from
+  // the caching allocator and a kernel on the context's streams -- which do not synchronise with the null stream -- may
+  // still be reading what they held before
+  HIP_TRY(ctx, hipMemcpyAsync(lat->d_pieces, pieces.data(), pieces.size() * sizeof(BuildPiece), hipMemcpyHostToDevice, ctx->stream));
+  if (!tasks.empty())
+    HIP_TRY(ctx, hipMemcpyAsync(lat->d_tasks, tasks.data(), tasks.size() * sizeof(PairTask), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, hipMemcpyAsync(lat->d_step_slot, step_slot.data(), step_slot.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, sync_main(ctx));  // (the host vectors go out of scope)
   lat->plan_piece_len = L;
   lat->n_pieces = (int32_t)pieces.size();
   lat->n_slots = next;
@@ -1318,11 +1353,15 @@ static int launch_build(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stream, co
 
 int lynx_build_compose(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, void* d_steps_out,
                        void* d_energy_out) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !lat || !d_energy_in || !d_steps_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
   HIP_TRY(ctx, use_device(ctx));
   ctx->main_dirty = true;
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_steps_out, (size_t)lat->batch * lat->n_steps * LYNX_STEP_STRIDE * es);
+  ctx->wrote(d_energy_out, (size_t)lat->batch * es);
   return lat->dtype == LYNX_F64 ? launch_build<double>(ctx, lat, ctx->stream, d_energy_in, d_steps_out, d_energy_out)
                                 : launch_build<float>(ctx, lat, ctx->stream, d_energy_in, d_steps_out, d_energy_out);
 }
@@ -1621,6 +1660,12 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   int slot = -1;
   bool async_build = false;
   bool short_call = false;
+  // what this call writes for the caller may hold the incoming energy of the table kept for a reverse pass (a fused
+  // call takes no table slot and keeps no table: nothing else would notice)
+  ctx->wrote(d_p_out, (size_t)B * N * 7 * sizeof(T));
+  ctx->wrote(d_energy_out, (size_t)B * sizeof(T));
+  ctx->wrote(d_moments_out, (size_t)B * LYNX_MOMENT_STRIDE * sizeof(double));
+  ctx->wrote(d_observations, lat ? (size_t)B * lat->n_observers * 2 * sizeof(double) : 0);
   if (S > 0 && !fused) {
     slot = (int)(ctx->seq++ % (unsigned)lynx_ctx::kTableSlots);
     const size_t need = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
@@ -1716,6 +1761,7 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
       else HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_built[slot], 0));
     }
     d_steps = ctx->scratch_steps[slot];
+    std::lock_guard<std::mutex> lock(ctx->mu);
     ctx->fwd_table.lat = lat;
     ctx->fwd_table.version = lat->version;
     ctx->fwd_table.energy = d_energy_in;
@@ -1953,7 +1999,9 @@ static int ensure_bwd_tasks(lynx_ctx* ctx, lynx_lattice* lat) {
   if (tasks.empty()) tasks.assign(64, 0xffffu);
   int rc = ctx_alloc(ctx, tasks.size() * sizeof(unsigned short), (void**)&lat->d_bwd_tasks);
   if (rc) return rc;
-  HIP_TRY(ctx, hipMemcpy(lat->d_bwd_tasks, tasks.data(), tasks.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
+  // on the main stream, not the null stream: the block may be one a kernel still in flight there was reading
+  HIP_TRY(ctx, hipMemcpyAsync(lat->d_bwd_tasks, tasks.data(), tasks.size() * sizeof(unsigned short), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(ctx, sync_main(ctx));  // (the host vector goes out of scope)
   lat->n_bwd_tasks = (int32_t)tasks.size();
   return LYNX_OK;
 }
@@ -2025,7 +2073,9 @@ static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const v
   }
   // the forward call this reverse pass belongs to has built exactly this table (and these unit records) a moment ago:
   // read them where they are -- and make the slot's next build wait for this reverse pass too
-  const lynx_ctx::FwdTable& ft = ctx->fwd_table;
+  std::unique_lock<std::mutex> table_lock(ctx->mu);
+  const lynx_ctx::FwdTable ft = ctx->fwd_table;
+  table_lock.unlock();
   const bool reuse = ctx->knobs.bwd_reuse_table && ft.valid && ft.lat == lat && ft.version == lat->version &&
                      ft.energy == d_energy_in && ft.seq == ctx->seq && ft.merged == merged &&
                      ctx->scratch_steps_bytes[ft.slot] >= steps_bytes;
@@ -2164,6 +2214,7 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
                                   const void* d_p_in, const double* d_moments_fwd, const double* d_grad_moments,
                                   void* d_grad_params, void* d_grad_energy_in, void* d_grad_p_in,
                                   const double* d_grad_observations) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !lat || !d_energy_in || !d_p_in || !d_moments_fwd || !d_grad_moments || !d_grad_params || !d_grad_energy_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
@@ -2175,7 +2226,7 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
     const int rc = join_side(ctx);  // d_moments_fwd is what a reduction on the side stream writes
     if (rc) return rc;
   }
-  return lat->dtype == LYNX_F64
+  const int rc = lat->dtype == LYNX_F64
              ? track_backward_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_moments_fwd, d_grad_moments,
                                         d_grad_params, d_grad_energy_in, d_grad_p_in, d_grad_observations)
          : ctx->knobs.bwd_pairs
@@ -2184,6 +2235,12 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
                                                    d_grad_observations)
              : track_backward_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_moments_fwd, d_grad_moments,
                                        d_grad_params, d_grad_energy_in, d_grad_p_in, d_grad_observations);
+  // the gradients it wrote for the caller (after the reverse pass has read the forward call's table)
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
+  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+  ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * es);
+  return rc;
 }
 
 template <typename T>
@@ -2229,6 +2286,7 @@ int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
                                 const void* d_cov_in, const void* d_mu_bar, const void* d_cov_bar,
                                 void* d_grad_params, void* d_grad_energy_in, void* d_grad_mu_in,
                                 void* d_grad_cov_in) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_bar || !d_cov_bar || !d_grad_params ||
       !d_grad_energy_in || !d_grad_mu_in || !d_grad_cov_in)
@@ -2236,6 +2294,13 @@ int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
   if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program");
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
   HIP_TRY(ctx, use_device(ctx));
+  {
+    const size_t es = dtype_size(lat->dtype);
+    ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
+    ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+    ctx->wrote(d_grad_mu_in, (size_t)lat->batch * 7 * es);
+    ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
+  }
   return lat->dtype == LYNX_F64
              ? moments_backward_t<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_bar, d_cov_bar, d_grad_params,
                                           d_grad_energy_in, d_grad_mu_in, d_grad_cov_in)
@@ -2245,6 +2310,7 @@ int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
 
 int lynx_moments(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                  double* d_moments_out, int32_t covariance) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_p || !d_moments_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (batch <= 0 || n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad shape");
@@ -2311,10 +2377,14 @@ static int launch_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
 
 int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                        const void* d_cov_in, void* d_mu_out, void* d_cov_out, void* d_energy_out) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (ctx && d_energy_out) ctx->fwd_table.written(d_energy_out, 1);
   if (!ctx || !lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_out || !d_cov_out)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_energy_out, (size_t)lat->batch * es);
+  ctx->wrote(d_mu_out, (size_t)lat->batch * 7 * es);
+  ctx->wrote(d_cov_out, (size_t)lat->batch * 49 * es);
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
   HIP_TRY(ctx, use_device(ctx));
   ctx->main_dirty = true;
@@ -2327,10 +2397,12 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
 
 int lynx_histogram2d(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                      const void* d_xedges, const void* d_yedges, int32_t nx, int32_t ny, int32_t* d_image) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_p || !d_xedges || !d_yedges || !d_image || batch <= 0 || n_particles <= 0 || nx <= 0 || ny <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_image, (size_t)batch * nx * ny * sizeof(int32_t));
   const size_t es = dtype_size(dtype);
   const size_t lds = ((size_t)nx + ny + 2) * es;
   if (lds > 64 * 1024) return fail(ctx, LYNX_ERR_INVALID, "screen resolution too large for the edge table");
@@ -2351,9 +2423,12 @@ int lynx_histogram2d(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particle
 }
 
 int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t packed, float* d_sin, float* d_cos) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_x || !d_sin || !d_cos || n <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_sin, (size_t)n * sizeof(float));
+  ctx->wrote(d_cos, (size_t)n * sizeof(float));
   const int64_t threads = (n + 1) / 2;
   hipLaunchKernelGGL(k_diag_phase_trig, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, d_x, n,
                      (int)packed, d_sin, d_cos);
@@ -2366,6 +2441,7 @@ int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t pac
 int lynx_aperture_mask(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                        const void* d_x_max, const void* d_y_max, int32_t param_stride, int32_t elliptical,
                        unsigned char* d_mask, int32_t* d_counts, int64_t* d_offsets, int64_t* d_totals) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_p || !d_x_max || !d_y_max || !d_mask || !d_counts || !d_offsets || !d_totals || batch <= 0 ||
       n_particles <= 0 || (param_stride != 0 && param_stride != 1))
@@ -2373,6 +2449,10 @@ int lynx_aperture_mask(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
   HIP_TRY(ctx, use_device(ctx));
   const int64_t chunks = (n_particles + kApertureChunk - 1) / kApertureChunk;
   if (batch * chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
+  ctx->wrote(d_mask, (size_t)batch * n_particles);
+  ctx->wrote(d_counts, (size_t)batch * chunks * sizeof(int32_t));
+  ctx->wrote(d_offsets, (size_t)batch * chunks * sizeof(int64_t));
+  ctx->wrote(d_totals, (size_t)batch * sizeof(int64_t));
   if (dtype == LYNX_F64)
     hipLaunchKernelGGL(k_aperture_mask<double>, dim3((unsigned)(batch * chunks)), dim3(256), 0, ctx->stream,
                        (const double*)d_p, n_particles, (int)chunks, (const double*)d_x_max, (const double*)d_y_max,
@@ -2390,10 +2470,13 @@ int lynx_aperture_mask(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
 
 int lynx_aperture_compact(lynx_ctx* ctx, int dtype, int64_t n_particles, const void* d_p, const unsigned char* d_mask,
                           const int64_t* d_offsets, void* d_kept, void* d_lost) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_p || !d_mask || !d_offsets || !d_kept || !d_lost || n_particles <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_kept, (size_t)n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
+  ctx->wrote(d_lost, (size_t)n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
   const int64_t chunks = (n_particles + kApertureChunk - 1) / kApertureChunk;
   if (dtype == LYNX_F64)
     hipLaunchKernelGGL(k_aperture_compact<double>, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, (const double*)d_p,
@@ -2407,10 +2490,12 @@ int lynx_aperture_compact(lynx_ctx* ctx, int dtype, int64_t n_particles, const v
 
 int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_mu, const void* d_cov,
                         const void* d_xs, const void* d_ys, int32_t nx, int32_t ny, void* d_image) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_mu || !d_cov || !d_xs || !d_ys || !d_image || batch <= 0 || nx <= 0 || ny <= 0 || batch > 65535)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_image, (size_t)batch * nx * ny * (dtype == LYNX_F64 ? 8 : 4));
   const unsigned gx = (unsigned)(((int64_t)nx * ny + 255) / 256);
   if (dtype == LYNX_F64)
     hipLaunchKernelGGL(k_gaussian_image<double>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream,
@@ -2428,10 +2513,12 @@ int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_m
 
 int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const double* mu,
                        const double* sigma, uint64_t seed, void* d_p) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !d_p || !mu || !sigma || batch <= 0 || n_particles <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_p, (size_t)batch * n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
   GaussArgs g;
   for (int i = 0; i < 6; ++i) {
     g.mu[i] = mu[i];
@@ -2451,12 +2538,14 @@ int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
 
 int lynx_diag_copy(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes, int repeats, int vec_per_thread,
                    float* avg_ms) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   const int per_thread = vec_per_thread >= 100 ? vec_per_thread - 100 : vec_per_thread;  // >= 100: non-temporal stores
   if (!ctx || !d_dst || !d_src || bytes % 16 || repeats <= 0 || vec_per_thread < 0 || per_thread > 64 ||
       (vec_per_thread >= 100 && per_thread == 0))
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_dst, bytes);
   const int64_t n_vec = (int64_t)(bytes / 16);
   const int vpt = vec_per_thread;  // 0 = grid-stride
   const unsigned grid = per_thread > 0 ? (unsigned)((n_vec + 256LL * per_thread - 1) / (256LL * per_thread))
@@ -2540,9 +2629,11 @@ int lynx_comm_info(lynx_ctx* ctx, int32_t* rccl_version, int32_t* n_ranks, int32
 }
 
 int lynx_gather_moments(lynx_ctx* ctx, const double* d_send, double* d_recv, int64_t count) {
+  LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   if (!ctx || !ctx->comm) return fail(ctx, LYNX_ERR_INVALID, "communicator not initialised");
   HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_recv, (size_t)std::max(1, ctx->comm_ranks) * count * sizeof(double));
   // Default with more than one rank: the side stream.  With one rank (LYNX_FORCE_COMM rehearsals) the "gather" is
   // a copy; it follows the reduction wherever that ran.
   const bool produced_on_side = ctx->side_wrote && ctx->side_wrote == (const void*)d_send;

@@ -632,9 +632,41 @@ def _apply_map(tm, beam):
     return {"type": "particle", "particles": new_particles, "energy": beam["energy"]}
 
 
-def cavity_track(spec, beam, dtype):
-    """lynx/accelerator/cavity.py:97-246 (`_track_beam`)."""
+KICK_FORMS = ("reference", "product")
+COS_DIFFERENCE_SMALL = 0.25  # lynx_device.hpp: kCosDifferenceSmall
+
+
+def cos_difference(d, phi, form="reference"):
+    """
+    cos(phi + d) - cos(phi) in the dtype of `d`, the difference of cosines of the cavity kick (cavity.py:150-160, with
+    d = -s beta0 k).
+    "reference": the two cosines subtracted, as the reference writes it.
+    "product":   the form the HIP kernels use for float32 (lynx_device.hpp: cos_difference): for |d| <= 0.25,
+                 cos(phi) (cos d - 1) - sin(phi) sin d, with cos d - 1 = -2 sin^2(d / 2) -- no cancellation between
+                 two cosines that agree to four or five digits; above that, the two cosines.
+    """
+    assert form in KICK_FORMS, form
+    d = np.asarray(d)
+    phi = np.asarray(phi, dtype=d.dtype)
+    two = d.dtype.type(2.0)
+    with np.errstate(all="ignore"):
+        plain = np.cos(d + phi) - np.cos(phi)
+        if form == "reference":
+            return plain
+        h = np.sin(d / two)
+        small = np.cos(phi) * (-two * h * h) - np.sin(phi) * np.sin(d)
+        return np.where(np.abs(d) <= d.dtype.type(COS_DIFFERENCE_SMALL), small, plain).astype(d.dtype)
+
+
+def cavity_track(spec, beam, dtype, kick="reference"):
+    """
+    lynx/accelerator/cavity.py:97-246 (`_track_beam`).  `kick`: how float32 forms the difference of cosines of the
+    kick (`cos_difference`): "reference" as the reference writes it, "product" as the HIP kernels do -- for both beam
+    types.  float64 takes the reference's form either way, as the kernels do.
+    """
+    assert kick in KICK_FORMS, kick
     dtype = np.dtype(dtype)
+    form = kick if dtype == np.float32 else "reference"
     length = np.asarray(spec["length"], dtype=dtype)
     voltage = _p(spec, "voltage", length, dtype)
     phase = _p(spec, "phase", length, dtype)
@@ -676,20 +708,24 @@ def cavity_track(spec, beam, dtype):
 
             if beam["type"] == "parameter":
                 mu_in, cov_in = beam["mu"], beam["cov"]
+                if form == "reference":
+                    dcos = np.cos(-mu_in[..., 4] * beta0 * k + phi) - np.cos(phi)
+                else:  # the kernels' argument: -1 * s * (beta0 k), the product rounded once
+                    dcos = cos_difference(-one * mu_in[..., 4] * (beta0 * k), phi, form)
                 out["mu"][..., 5] = mu_in[..., 5] * energy * beta0 / (
                     outgoing_energy * beta1
-                ) + voltage * beta0 / (outgoing_energy * beta1) * (
-                    np.cos(-mu_in[..., 4] * beta0 * k + phi) - np.cos(phi)
-                )
+                ) + voltage * beta0 / (outgoing_energy * beta1) * dcos
                 out["cov"][..., 5, 5] = cov_in[..., 5, 5]
             else:
                 P = beam["particles"]
                 u = lambda v: v[..., None]  # noqa: E731  (unsqueeze(-1))
+                if form == "reference":
+                    dcos = np.cos(-one * P[..., 4] * u(beta0) * u(k) + u(phi)) - u(np.cos(phi))
+                else:
+                    dcos = cos_difference(-one * P[..., 4] * u(beta0 * k), u(phi), form)
                 out["particles"][..., 5] = P[..., 5] * u(energy) * u(beta0) / (
                     u(outgoing_energy) * u(beta1)
-                ) + u(voltage) * u(beta0) / (u(outgoing_energy) * u(beta1)) * (
-                    np.cos(-one * P[..., 4] * u(beta0) * u(k) + u(phi)) - u(np.cos(phi))
-                )
+                ) + u(voltage) * u(beta0) / (u(outgoing_energy) * u(beta1)) * dcos
 
             dgamma = voltage / me
             if np.any(delta_energy > 0):  # :164 -- whole batch
@@ -750,16 +786,21 @@ def segment_is_skippable(elements) -> bool:
     return all(is_skippable(e) for e in elements)
 
 
-def segment_transfer_map(elements, energy, dtype=np.float32):
-    """lynx/accelerator/segment.py:329-338: tm = I; tm = M_e @ tm for e in order."""
+def segment_transfer_map(elements, energy, dtype=np.float32, compose="reference"):
+    """
+    lynx/accelerator/segment.py:329-338: tm = I; tm = M_e @ tm for e in order.  `compose="float64"`: the element maps
+    (built in `dtype`) multiplied in float64 and rounded once, as the HIP build does (deviation (i)).
+    """
     dtype = np.dtype(dtype)
     energy = np.asarray(energy, dtype=dtype)
     if not segment_is_skippable(elements):
         return None
-    tm = _eye(energy.shape, dtype)
+    assert compose in ("reference", "float64"), compose
+    wide = np.float64 if compose == "float64" else dtype
+    tm = _eye(energy.shape, wide)
     for spec in elements:
-        tm = _matmul(element_transfer_map(spec, energy, dtype), tm)
-    return tm
+        tm = _matmul(element_transfer_map(spec, energy, dtype).astype(wide), tm)
+    return tm.astype(dtype)
 
 
 def partition(elements):
@@ -779,23 +820,24 @@ def partition(elements):
     return todos
 
 
-def segment_track(elements, beam, dtype=np.float32, bpm_readings=None):
+def segment_track(elements, beam, dtype=np.float32, bpm_readings=None, kick="reference", compose="reference"):
     """
     lynx/accelerator/segment.py:340-356.  `bpm_readings`, if a list, receives
-    (element_index, stack([mu_x, mu_y])) for every active BPM (bpm.py:48-58).
+    (element_index, stack([mu_x, mu_y])) for every active BPM (bpm.py:48-58).  `kick`: see `cavity_track`;
+    `compose`: see `segment_transfer_map`.
     """
     dtype = np.dtype(dtype)
     if segment_is_skippable(elements):
-        tm = segment_transfer_map(elements, beam["energy"], dtype)
+        tm = segment_transfer_map(elements, beam["energy"], dtype, compose)
         return _apply_map(tm, beam)
     for what, payload in partition(elements):
         if what == "run":
-            tm = segment_transfer_map(payload, beam["energy"], dtype)
+            tm = segment_transfer_map(payload, beam["energy"], dtype, compose)
             beam = _apply_map(tm, beam)
         else:
             spec = payload
             if spec["kind"] == "cavity":
-                beam = cavity_track(spec, beam, dtype)
+                beam = cavity_track(spec, beam, dtype, kick=kick)
             elif spec["kind"] == "bpm":
                 if bpm_readings is not None:
                     m = beam_moments(beam)

@@ -743,3 +743,84 @@ def test_gradients_through_active_bpms(lx, beam_type):
                           float(np.asarray(g[elements[1]]["length"]).reshape(-1)[0]), rtol=1e-3)
     with pytest.raises(KeyError):
         vjp(mu_bar=w_mu, readings={elements[0]: r_a})  # an inactive BPM reads nothing
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+@pytest.mark.parametrize("writer", ["build_compose", "fused_forward"])
+def test_a_reverse_pass_does_not_read_a_table_whose_energy_was_overwritten(lx, monkeypatch, writer, dtype):
+    """
+    The reverse pass reuses the forward call's step table when the energy POINTER, the table sequence and the lattice
+    version match (lynx_ctx::FwdTable).  Through the C ABI: a forward call on energy buffer E; then something else
+    writes new energies into E on the caller's behalf -- lynx_build_compose with d_energy_out = E, or a forward call in
+    the fused form (LYNX_FUSE_MAX_CHUNKS), which takes no table slot -- and then the reverse pass on E.  Its gradients
+    must be those of a reverse pass that builds its own table from what E holds now (LYNX_BWD_REUSE_TABLE=0), bit for
+    bit; and they must differ from the gradients at E's old contents (otherwise the test would prove nothing).
+    Both passes walk the steps one by one (LYNX_TRACK_SEQUENTIAL_STEPS, LYNX_BWD_MERGE=0), so that their merge forms
+    agree and the reverse pass does take the forward table whenever it may, in float32 as in float64: without the fix
+    every variant reads the stale table.
+    """
+    import ctypes as C
+
+    from lynx_amd import _ffi, engine
+    from lynx_amd.device import get_runtime
+
+    rt = get_runtime()
+    dtype = np.dtype(dtype)
+    B, N = 3, 4000
+    rng = np.random.default_rng(61)
+    f = lambda v: np.full(B, v)  # noqa: E731
+    desc = []
+    for _ in range(2):
+        desc += [("drift", dict(length=f(0.3))), ("quadrupole", dict(length=f(0.1), k1=rng.uniform(-5, 5, B))),
+                 ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, B), phase=rng.uniform(-10, 10, B),
+                                 frequency=f(1.3e9)))]
+    elements, _ = make_lattice(desc, dtype.type, lx)
+    seg = lx.Segment(elements)
+    P = o.gaussian_particles((B,), N, seed=9, dtype=dtype, sigma=[1e-3, 1e-4, 1e-3, 1e-4, 1e-3, 1e-3])
+    e1 = rng.uniform(6e6, 8e6, B).astype(dtype)
+    e2 = (1.5 * e1).astype(dtype)
+    program, = engine.plan(seg, seg.elements, False, fuse_observers=True)
+    lat = engine._ready(seg.__dict__.setdefault("_lattice_cache", engine.LatticeCache()), program, (B,), dtype, e1)
+    S = len(program.steps)
+    E = rt.to_device(e1)
+    other = rt.to_device(e2)
+    p_in = rt.to_device(P)
+    p_out = rt.empty((B, N, 7), dtype)
+    e_out = rt.empty((B,), dtype)
+    mom = rt.empty((B, _ffi.MOMENT_STRIDE), np.float64)
+    mom2 = rt.empty((B, _ffi.MOMENT_STRIDE), np.float64)
+    steps = rt.empty((B, S, _ffi.STEP_STRIDE), dtype)
+    rec = np.zeros((B, _ffi.MOMENT_STRIDE))
+    rec[:, :28] = rng.normal(size=(B, 28))
+    rec[:, 7:28] *= 1e3
+    g_rec = rt.to_device(rec)
+    g_par = rt.empty((B, max(lat.E, 1), 8), dtype)
+    g_en = rt.empty((B,), dtype)
+    p = lambda a: C.c_void_p(a.ptr)  # noqa: E731
+    one_by_one = _ffi.TRACK_MOMENTS | _ffi.TRACK_SEQUENTIAL_STEPS
+    monkeypatch.setenv("LYNX_BWD_MERGE", "0")
+    if writer == "fused_forward":
+        monkeypatch.setenv("LYNX_FUSE_MAX_CHUNKS", "64")
+        monkeypatch.setenv("LYNX_UNROLL", "1")
+
+    def run(reuse, overwrite=True):
+        monkeypatch.setenv("LYNX_BWD_REUSE_TABLE", reuse)
+        rt.check(rt.lib.lynx_buf_h2d(rt.ctx, p(E), e1.ctypes.data, e1.nbytes))
+        # (the fused knobs let a call without LYNX_TRACK_TWO_KERNEL take the fused form: this one keeps its slot)
+        rt.check(rt.lib.lynx_track_particles(rt.ctx, lat.handle, N, p(E), p(p_in), p(p_out), p(e_out), p(mom),
+                                             one_by_one | _ffi.TRACK_TWO_KERNEL, None))
+        if overwrite and writer == "build_compose":
+            rt.check(rt.lib.lynx_build_compose(rt.ctx, lat.handle, p(other), p(steps), p(E)))
+        elif overwrite:
+            rt.check(rt.lib.lynx_track_particles(rt.ctx, lat.handle, N, p(other), p(p_in), p(p_out), p(E), p(mom2),
+                                                 one_by_one, None))
+        rt.check(rt.lib.lynx_track_particles_backward(rt.ctx, lat.handle, N, p(E), p(p_in), p(mom), p(g_rec), p(g_par),
+                                                      p(g_en), None, None))
+        return g_par.numpy().copy(), g_en.numpy().copy(), E.numpy().copy()
+
+    fresh = run("0")
+    reused = run("1")
+    stale = run("1", overwrite=False)
+    assert not np.array_equal(fresh[2], e1) and np.array_equal(reused[2], fresh[2])  # E was overwritten, the same way
+    assert not np.array_equal(fresh[0], stale[0])  # the energy matters to the gradients
+    assert np.array_equal(reused[0], fresh[0], equal_nan=True) and np.array_equal(reused[1], fresh[1], equal_nan=True)

@@ -37,9 +37,10 @@ def _particle_case(lx, desc, dtype, batch_shape, n, seed, energy=1e8, sigma=None
                              sigma=sigma or [1e-4, 1e-5, 1e-4, 1e-5, 1e-5, 1e-3])
     e = np.full(batch_shape, energy, dtype=dtype)
     out = lx.Segment(elements).track(lx.ParticleBeam(P, e, dtype=dtype))
-    ref = o.segment_track(specs, o.particle_beam(P, e, dtype), dtype)
+    # float32 behind an active cavity: the chain with the kernels' form of the kick (see _assert_moments)
+    ref = o.segment_track(specs, o.particle_beam(P, e, dtype), dtype, kick="product")
     if dtype == np.float32 and any(kind == "cavity" for kind, _ in desc):
-        # behind an active cavity the float32 chain is not its own measure (see _assert_moments): the float64 chain next to it
+        # ... and the float64 chain next to it, for the moments the kick decides
         up = lambda v: np.asarray(np.asarray(v, dtype=np.float32), dtype=np.float64) if isinstance(v, (np.ndarray, list, float)) else v  # noqa: E731
         _, specs64 = make_lattice([(kind, {k: up(v) for k, v in kw.items()}) for kind, kw in desc], np.float64)
         ref["float64_chain"] = o.segment_track(specs64, o.particle_beam(P.astype(np.float64), e.astype(np.float64), np.float64), np.float64)
@@ -55,28 +56,24 @@ def _assert_particles(out, ref, dtype):
     assert rel_err(out.energy, ref["energy"]) < 1e-6
 
 
+KICK_MOMENTS = ("mu_s", "mu_p", "sigma_s", "sigma_p")  # what the cavity kick decides
+TOL_KICK_F64 = 1e-5  # float32 product against the float64 chain in those (measured: 1e-8 .. 3e-6)
+
+
 def _assert_moments(out, ref, dtype):
     """
-    Every beam moment within north_star's tolerance of the reference's chain.  float32 lattices with an active cavity
-    (`_particle_case` then hands the float64 chain over too): within the tolerance of the float32 chain OR of the
-    float64 chain.  The kick subtracts two cosines (cavity.py:150-160) that agree to four or five digits on a short
-    bunch, at an argument all particles of a sample practically share -- the float32 chain's mean of delta carries
-    that cosine's rounding as a whole, up to 5e-4 of |mu_p| + sigma_p on BASELINE config 5's bench beam; the product
-    forms the difference without the cancellation (device_cavity_kick) and sits on the float64 chain to 1e-6.
+    Every beam moment within north_star's tolerance of the oracle's chain.  float32 lattices with an active cavity:
+    `ref` is the chain with the kernels' form of the kick (o.segment_track(..., kick="product")) -- the reference
+    subtracts two cosines (cavity.py:150-160) that agree to four or five digits on a short bunch, and its float32 mean
+    of delta carries that cosine's rounding as a whole (2e-4 .. 5e-4 of |mu_p| + sigma_p on BASELINE config 5's beam),
+    the kernels form cos(phi)(cos d - 1) - sin(phi) sin d (device_cavity_kick) -- and, when `_particle_case` hands the
+    float64 chain over too, the moments the kick decides are also held within TOL_KICK_F64 of that chain.
     """
-    chains = [o.beam_moments(ref, ddof=1)] + ([o.beam_moments(ref["float64_chain"], ddof=1)] if "float64_chain" in ref else [])
-    scale = chains[-1]
-
-    def within(key, tolerance_scale):
-        got = np.asarray(getattr(out, key), dtype=np.float64)
-        return np.any([np.abs(got - np.asarray(m[key], dtype=np.float64)) <= TOL_MOM[dtype] * tolerance_scale for m in chains], axis=0)
-
-    for key in ("mu_x", "mu_xp", "mu_y", "mu_yp", "mu_s", "mu_p"):
-        assert np.all(within(key, np.abs(scale[key]) + scale["sigma" + key[2:]])), key
-    for key in ("sigma_x", "sigma_xp", "sigma_y", "sigma_yp", "sigma_s", "sigma_p"):
-        assert np.all(within(key, scale[key])), key
-    for key, a, b in (("sigma_xxp", "sigma_x", "sigma_xp"), ("sigma_yyp", "sigma_y", "sigma_yp")):
-        assert np.all(within(key, scale[a] * scale[b])), key
+    d = moment_distances(out, o.beam_moments(ref, ddof=1))
+    assert max(d.values()) <= TOL_MOM[dtype], d
+    if "float64_chain" in ref:
+        d64 = moment_distances(out, o.beam_moments(ref["float64_chain"], ddof=1))
+        assert max(d64[key] for key in KICK_MOMENTS) <= TOL_KICK_F64, d64
 
 
 # ---------------------------------------------------------------------------------------------
@@ -298,10 +295,9 @@ def test_c5_cavity_lattice_particles(lx, dtype):
     out, ref = _particle_case(lx, desc, dtype, (B,), 2500, seed=3, energy=6e6,
                               sigma=[1e-4, 1e-5, 1e-4, 1e-5, 1e-4, 1e-3])
     got = np.asarray(out.particles)
-    # delta goes through cos(phi + eps) - cos(phi) in the working precision (cavity.py:150-160): fp32 agreement is
-    # bounded by that cancellation, not by the kernel -- measured 6e-5 .. 1.6e-4 from the float32 oracle, which is
-    # itself 4e-5 .. 1e-4 away from the float64 one (scripts/gpu/r3_c5_particles.py); s: 4e-7 .. 2.5e-6
-    tol = {np.float32: [1e-4] * 4 + [1e-4, 5e-4, 1e-6], np.float64: [1e-9] * 7}[dtype]
+    # delta goes through cos(phi + eps) - cos(phi): against the chain with the kernels' form of the kick (float32), at
+    # the suite's tolerance like every other coordinate
+    tol = {np.float32: [1e-4] * 6 + [1e-6], np.float64: [1e-9] * 7}[dtype]
     for c in range(7):
         assert rel_err(got[..., c], ref["particles"][..., c]) < tol[c], (c, rel_err(got[..., c], ref["particles"][..., c]))
     assert rel_err(out.energy, ref["energy"]) < 1e-6
@@ -358,7 +354,7 @@ def test_c4_shape_moments_match_the_reference_chain(lx):
         assert rel_err(got[..., c], ref["particles"][..., c]) < 1e-4, c
 
 
-def test_the_bench_plan_of_config_4_against_the_oracle(lx):
+def test_the_bench_plan_of_config_4_against_the_oracle(lx, record_property):
     """
     The kernel / launch combination `bench.py`'s headline number runs on, end to end against the oracle: FODO k1
     scan, float32, B = 320 (>= 256: lanes = samples build; not a multiple of 64: a cut wave of samples), N = 100 000
@@ -366,8 +362,9 @@ def test_the_bench_plan_of_config_4_against_the_oracle(lx):
     build wait, moment reduction on the side stream), two-tile workgroups, default environment, beam generated in HBM
     like the bench's.  THREE consecutive `track` calls, so that the builds of calls two and three run underneath the
     previous streaming kernel and every step-table slot is used.  Oracle: `o.segment_track` on the k1 values of
-    samples {0, 63, 64, 255, 319} -- moments at north_star's 1e-4, particles of every one of them at 1e-4 of the
-    coordinate's scale.  (segment.py:329-342, element.py:83-92.)
+    samples {0, 63, 64, 255, 319} and three drawn per run (seed recorded) -- moments at north_star's 1e-4, particles of
+    every one of them at 1e-4 of the coordinate's scale -- and the moments of ALL 320 samples at 1e-4 (the oracle takes
+    them 64 at a time; the three calls' records are the same bits).  (segment.py:329-342, element.py:83-92.)
     """
     B, N = 320, 100_000
     dtype = np.float32
@@ -377,7 +374,7 @@ def test_the_bench_plan_of_config_4_against_the_oracle(lx):
     beam = lx.ParticleBeam.synthetic((B,), N, sigma=[1e-4, 1e-5, 1e-4, 1e-5, 1e-5, 1e-3], energy=1e8, seed=2, dtype=dtype)
     outs = [segment.track(beam) for _ in range(3)]
     P = np.asarray(beam.particles)
-    pick = [0, 63, 64, 255, 319]
+    pick, _ = random_samples(B, 3, always=(0, 63, 64, 255, 319), record=record_property)
     sub = [(kind, {k: np.asarray(v)[pick] for k, v in kw.items()}) for kind, kw in desc]
     _, specs = make_lattice(sub, dtype)
     e = np.full(len(pick), 1e8, dtype=dtype)
@@ -399,9 +396,16 @@ def test_the_bench_plan_of_config_4_against_the_oracle(lx):
         assert rel_err(tracked[pick][..., c], ref["particles"][..., c]) < 1e-4, c
     assert np.array_equal(tracked, np.asarray(outs[0].particles))
     assert np.all(records[0][:, 35] == N)
+    got = {key: np.asarray(getattr(outs[0], key)) for key in MOMENT_KEYS}
+    for lo in range(0, B, 64):
+        chunk = list(range(lo, min(lo + 64, B)))
+        _, specs = make_lattice(_subset(desc, chunk), dtype)
+        mc = o.beam_moments(o.segment_track(specs, o.particle_beam(P[chunk], np.full(len(chunk), 1e8, dtype=dtype), dtype), dtype), ddof=1)
+        d = moment_distances({key: got[key][chunk] for key in MOMENT_KEYS}, mc)
+        assert max(d.values()) <= 1e-4, (lo, d)
 
 
-def test_config_4_at_its_full_size_is_exactly_linear_and_matches_the_oracle_on_three_samples(lx):
+def test_config_4_at_its_full_size_is_exactly_linear_and_matches_the_oracle(lx, record_property):
     """
     BASELINE config 4 as the bench runs it -- 1024 samples x 100 000 particles x 128-element FODO, float32, beam made
     in HBM -- is too large to run through the oracle whole.  Two checks that do not depend on the size:
@@ -409,8 +413,10 @@ def test_config_4_at_its_full_size_is_exactly_linear_and_matches_the_oracle_on_t
     beam by 2 is exact in binary floating point: the beam with twice the sigmas (same seed) must come out exactly
     twice as large -- every particle of every sample bit for bit, the means times 2, the second moments times 4 --
     whatever the launch plan, tile order and reduction tree did on the way (element.py:83-92: P T^T).
-    (2) samples 0, 511 and 1023 against `o.segment_track` on their k1 values: particles at 1e-4 of each coordinate's
-    scale, moments at north_star's 1e-4.
+    (2) against `o.segment_track` on their k1 values: the moments of ALL 1024 samples at north_star's 1e-4 (the
+    oracle takes them 128 at a time) -- the linearity of (1) cannot see a sample tracked with its neighbour's k1 --
+    and the particles of the two ends of the scan and three samples drawn per run (seed recorded) at 1e-4 of each
+    coordinate's scale.
     """
     B, N = 1024, 100_000
     dtype = np.float32
@@ -420,8 +426,9 @@ def test_config_4_at_its_full_size_is_exactly_linear_and_matches_the_oracle_on_t
     sigma = np.array([1e-4, 1e-5, 1e-4, 1e-5, 1e-5, 1e-3])
     beam = lx.ParticleBeam.synthetic((B,), N, sigma=sigma, energy=1e8, seed=2, dtype=dtype)
     twice = lx.ParticleBeam.synthetic((B,), N, sigma=2 * sigma, energy=1e8, seed=2, dtype=dtype)
-    pick = [0, 511, 1023]
-    P = np.asarray(beam.particles)[pick]
+    pick, _ = random_samples(B, 3, always=(0, 1023), record=record_property)
+    P_all = np.asarray(beam.particles)
+    P = P_all[pick]
     P2 = np.asarray(twice.particles)[pick]
     assert np.array_equal(P2[..., :6], 2 * P[..., :6]) and np.all(P2[..., 6] == 1)
     out, out2 = segment.track(beam), segment.track(twice)
@@ -435,14 +442,18 @@ def test_config_4_at_its_full_size_is_exactly_linear_and_matches_the_oracle_on_t
     sub = [(kind, {k: np.asarray(v)[pick] for k, v in kw.items()}) for kind, kw in desc]
     _, specs = make_lattice(sub, dtype)
     ref = o.segment_track(specs, o.particle_beam(P, np.full(len(pick), 1e8, dtype=dtype), dtype), dtype)
-    m = o.beam_moments(ref, ddof=1)
     for c in range(7):
         assert rel_err(a[pick][..., c], ref["particles"][..., c]) < 1e-4, c
-    for key in ("mu_x", "mu_xp", "mu_y", "mu_yp", "mu_s", "mu_p"):
-        sig = m["sigma" + key[2:]]
-        assert np.all(np.abs(np.asarray(getattr(out, key))[pick] - m[key]) <= 1e-4 * (np.abs(m[key]) + sig)), key
-    for key in ("sigma_x", "sigma_xp", "sigma_y", "sigma_yp", "sigma_s", "sigma_p"):
-        assert np.allclose(np.asarray(getattr(out, key))[pick], m[key], rtol=1e-4, atol=0), key
+    got = {key: np.asarray(getattr(out, key)) for key in MOMENT_KEYS}
+    worst = 0.0
+    for lo in range(0, B, 128):
+        chunk = list(range(lo, lo + 128))
+        _, specs = make_lattice(_subset(desc, chunk), dtype)
+        m = o.beam_moments(o.segment_track(specs, o.particle_beam(P_all[chunk], np.full(128, 1e8, dtype=dtype), dtype), dtype), ddof=1)
+        d = moment_distances({key: got[key][chunk] for key in MOMENT_KEYS}, m)
+        assert max(d.values()) <= 1e-4, (lo, d)
+        worst = max(worst, max(d.values()))
+    print(f"config 4 at its full size: all 1024 samples' moments within {worst:.1e} of the float32 oracle")
 
 
 def test_config_5_at_its_full_size_structured_equals_dense_and_matches_the_oracle_on_three_samples(lx, monkeypatch):
@@ -451,7 +462,8 @@ def test_config_5_at_its_full_size_structured_equals_dense_and_matches_the_oracl
     Drift, Cavity] x 8, float32 -- through the structured step loop (k_track_units, insisted on) and through the dense
     one: every particle, every energy and every moment record of the two bit for bit (lynx_units.hpp: skipped terms
     are exact zeros); and environments 0, 2047 and 4095 against `o.segment_track`: moments at north_star's 1e-4,
-    particle coordinates at 1e-4 of their scale, delta behind eight cavities at 5e-4 (measured 6e-5 .. 1.6e-4: the
+    particle coordinates at 1e-4 of their scale, delta behind eight cavities included, against the chain with the
+    kernels' form of the kick (o.segment_track(..., kick="product"); with the reference's form delta was 6e-5 .. 1.6e-4 away: the
     float32 cosines of eight kicks, the float32 oracle itself is 4e-5 .. 1e-4 away from the float64 one there:
     scripts/gpu/r3_c5_particles.py).  (cavity.py:97-246, quadrupole.py:66-80.)
     """
@@ -482,11 +494,11 @@ def test_config_5_at_its_full_size_structured_equals_dense_and_matches_the_oracl
     P = np.asarray(beam.particles)[pick]
     sub = [(kind, {k: np.asarray(v)[pick] for k, v in kw.items()}) for kind, kw in desc]
     _, specs = make_lattice(sub, dtype)
-    ref = o.segment_track(specs, o.particle_beam(P, np.full(len(pick), 6e6, dtype=dtype), dtype), dtype)
+    ref = o.segment_track(specs, o.particle_beam(P, np.full(len(pick), 6e6, dtype=dtype), dtype), dtype, kick="product")
     m = o.beam_moments(ref, ddof=1)
     got = outs["2"][0][pick]
     for c in range(7):
-        assert rel_err(got[..., c], ref["particles"][..., c]) < (5e-4 if c == 5 else 1e-4), c
+        assert rel_err(got[..., c], ref["particles"][..., c]) < 1e-4, c
     assert rel_err(outs["2"][1][pick], ref["energy"]) < 1e-6
     for key in ("mu_x", "mu_xp", "mu_y", "mu_yp", "mu_s", "mu_p"):
         sig = m["sigma" + key[2:]]
@@ -541,9 +553,9 @@ def test_config_5_on_the_bench_beam_product_oracle32_oracle64_distances(lx):
     count), and with that the product is ON the float64 chain -- mu_p 2e-8, sigma_p 1e-6, mu_s 2e-7 -- in every
     environment; its distance from the float32 chain is that chain's own distance from float64.
 
-    Asserted, per environment and per moment: within 1e-4 of the float32 chain or of the float64 chain, and -- the
-    round-3 verdict's criterion -- d(product, float32 chain) <= max(1e-4, 2 d(float32 chain, float64 chain)); for the
-    moments the kick decides (mu_s, mu_p, sigma_s, sigma_p) within 1e-5 of the float64 chain.
+    Asserted, per environment and per moment: within 1e-4 of the float32 chain with the kernels' form of the kick
+    (o.segment_track(..., kick="product")), and for the moments the kick decides (mu_s, mu_p, sigma_s, sigma_p) within
+    1e-5 of the float64 chain.  The reference-form float32 chain is computed next to them and its distances printed.
     """
     dtype = np.float32
     desc, segment, beam, energy = _bench_workload(lx, "c5", dtype)
@@ -554,7 +566,7 @@ def test_config_5_on_the_bench_beam_product_oracle32_oracle64_distances(lx):
     P_all = np.asarray(beam.particles)
     tracked_all = np.asarray(out.particles)
     energy_all = np.asarray(out.energy)
-    worst = {key: np.zeros(3) for key in MOMENT_KEYS}  # product-oracle32, product-oracle64, oracle32-oracle64
+    worst = {key: np.zeros(4) for key in MOMENT_KEYS}  # product-oracle32, product-oracle64, oracle32-oracle64, product-kick32
     for lo in range(0, B, 128):
         pick = list(range(lo, lo + 128))
         P = P_all[pick]
@@ -562,8 +574,9 @@ def test_config_5_on_the_bench_beam_product_oracle32_oracle64_distances(lx):
         _, specs64 = make_lattice(_subset(desc, pick, cast=np.float64), np.float64)
         e = np.full(len(pick), energy, dtype=dtype)
         ref32 = o.segment_track(specs32, o.particle_beam(P, e, dtype), dtype)
+        kick32 = o.segment_track(specs32, o.particle_beam(P, e, dtype), dtype, kick="product")
         ref64 = o.segment_track(specs64, o.particle_beam(P.astype(np.float64), e.astype(np.float64), np.float64), np.float64)
-        m32, m64 = o.beam_moments(ref32, ddof=1), o.beam_moments(ref64, ddof=1)
+        m32, m64, mk = o.beam_moments(ref32, ddof=1), o.beam_moments(ref64, ddof=1), o.beam_moments(kick32, ddof=1)
         for key in MOMENT_KEYS:
             if key.startswith("mu_"):
                 scale = np.abs(m64[key]) + m64["sigma" + key[2:]]
@@ -575,20 +588,20 @@ def test_config_5_on_the_bench_beam_product_oracle32_oracle64_distances(lx):
             d_p32 = np.abs(got_all[key][pick] - r32) / scale
             d_p64 = np.abs(got_all[key][pick] - m64[key]) / scale
             d_3264 = np.abs(r32 - m64[key]) / scale
-            assert np.all(np.minimum(d_p32, d_p64) <= 1e-4), (key, lo, float(np.max(np.minimum(d_p32, d_p64))))
-            assert np.all(d_p32 <= np.maximum(1e-4, 2 * d_3264)), (key, lo, float(np.max(d_p32)), float(np.max(d_3264)))
-            if key in ("mu_s", "mu_p", "sigma_s", "sigma_p"):
-                assert np.all(d_p64 <= 1e-5), (key, lo, float(np.max(d_p64)))
-            worst[key] = np.maximum(worst[key], [d_p32.max(), d_p64.max(), d_3264.max()])
+            d_pk = np.abs(got_all[key][pick] - np.asarray(mk[key], dtype=np.float64)) / scale
+            assert np.all(d_pk <= 1e-4), (key, lo, float(np.max(d_pk)))
+            if key in KICK_MOMENTS:
+                assert np.all(d_p64 <= TOL_KICK_F64), (key, lo, float(np.max(d_p64)))
+            worst[key] = np.maximum(worst[key], [d_p32.max(), d_p64.max(), d_3264.max(), d_pk.max()])
         if lo % 1024 == 0:  # the particles of a stretch of samples, and their energies
             for c in range(7):
-                err = rel_err(tracked_all[pick][..., c], ref32["particles"][..., c])
-                assert err < (5e-4 if c == 5 else 1e-4), (lo, c, err)
-            assert rel_err(energy_all[pick], ref32["energy"]) < 1e-6
+                err = rel_err(tracked_all[pick][..., c], kick32["particles"][..., c])
+                assert err < 1e-4, (lo, c, err)
+            assert rel_err(energy_all[pick], kick32["energy"]) < 1e-6
     print("config 5 on the bench beam (sigma_s = 1e-5), all 4096 environments: worst distance per moment")
-    print(f"{'moment':>10} {'product-oracle32':>18} {'product-oracle64':>18} {'oracle32-oracle64':>18}")
+    print(f"{'moment':>10} {'product-oracle32':>18} {'product-oracle64':>18} {'oracle32-oracle64':>18} {'product-kick32':>18}")
     for key in MOMENT_KEYS:
-        print(f"{key:>10} {worst[key][0]:18.2e} {worst[key][1]:18.2e} {worst[key][2]:18.2e}")
+        print(f"{key:>10} {worst[key][0]:18.2e} {worst[key][1]:18.2e} {worst[key][2]:18.2e} {worst[key][3]:18.2e}")
     assert np.all(np.asarray(out.moment_record())[:, 35] == N)
 
 
@@ -693,9 +706,10 @@ def test_c5_shape_moments(lx):
     BASELINE config 5's shape ([Drift, misaligned Quad, Drift, Cavity] x 8 at 6 MeV, 10 000 particles,
     float32): every beam moment within north_star's 1e-4 of the reference's chain in float32 or in float64
     (_assert_moments).  mu_p and sigma_p pass through eight cavity kicks cos(phi + eps) - cos(phi) (cavity.py:150-160):
-    evaluated in float32 as two cosines -- the oracle -- the mean of delta is 2e-4 of its scale away from the float64
-    chain even on this 0.1 mm bunch; the kernel forms the difference without the cancellation and is asserted within
-    1e-4 of the float64 chain as a whole (measured: 1e-6).  Both distances are printed.
+    evaluated in float32 as two cosines -- the reference's form -- the mean of delta is 2e-4 of its scale away from the
+    float64 chain even on this 0.1 mm bunch; the kernel forms the difference without the cancellation.  Asserted: every
+    moment within 1e-4 of the float32 chain with the kernels' form (kick="product"), within 1e-4 of the float64 chain as
+    a whole and within 1e-5 of it in the moments the kick decides.  The distances are printed.
     """
     B, N = 16, 10_000
     rng = np.random.default_rng(3)
@@ -710,14 +724,18 @@ def test_c5_shape_moments(lx):
     sigma = [1e-4, 1e-5, 1e-4, 1e-5, 1e-4, 1e-3]
     out, ref = _particle_case(lx, desc, np.float32, (B,), N, seed=3, energy=6e6, sigma=sigma)
     _assert_moments(out, ref, np.float32)
+    _, ref_specs32 = make_lattice(desc, np.float32)
     _, specs64 = make_lattice([(k, {a: np.asarray(v, dtype=np.float32).astype(np.float64) for a, v in kw.items()})
                                for k, kw in desc], np.float64)
     P = o.gaussian_particles((B,), N, seed=3, dtype=np.float32, sigma=sigma)
     ref64 = o.segment_track(specs64, o.particle_beam(P.astype(np.float64), np.full(B, 6e6), np.float64), np.float64)
     d32 = _moment_distance(out, o.beam_moments(ref, ddof=1))
     d64 = _moment_distance(out, o.beam_moments(ref64, ddof=1))
-    print(f"C5 shape: moments {d32:.2e} from the float32 reference, {d64:.2e} from float64")
-    assert d64 < 1e-4 and d32 < 1e-3
+    dref = _moment_distance(out, o.beam_moments(o.segment_track(ref_specs32, o.particle_beam(P, np.full(B, 6e6, np.float32), np.float32),
+                                                                np.float32), ddof=1))
+    print(f"C5 shape: moments {d32:.2e} from the float32 product-kick chain, {d64:.2e} from float64, "
+          f"{dref:.2e} from the float32 reference-kick chain")
+    assert d64 < 1e-4 and d32 < 1e-4
 
 
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
@@ -792,7 +810,7 @@ def test_lanes_build_agrees_with_the_workgroup_build(lx, dtype, B, monkeypatch):
         out, ref = _particle_case(lx, desc, dtype, (B,), 700, seed=8, energy=6e6, sigma=[1e-4, 1e-5, 1e-4, 1e-5, 1e-4, 1e-3])
         results[name] = (np.asarray(out.particles), np.asarray(out.energy), out.moment_record().copy())
         got = np.asarray(out.particles)
-        tol = {np.float32: [1e-4] * 4 + [1e-4, 5e-4, 1e-6], np.float64: [1e-9] * 7}[dtype]
+        tol = {np.float32: [1e-4] * 6 + [1e-6], np.float64: [1e-9] * 7}[dtype]  # (float32: the product-kick chain)
         for c in range(7):
             assert rel_err(got[..., c], ref["particles"][..., c]) < tol[c], (name, c)
         assert rel_err(out.energy, ref["energy"]) < 1e-6
@@ -1105,7 +1123,7 @@ def test_parameter_beam_through_mixed_lattice(lx, dtype):
     beam = lx.ParameterBeam.from_parameters(**kw, dtype=dtype)
     ref_in = o.parameter_beam_from_parameters(dtype=dtype, **kw)
     out = lx.Segment(elements).track(beam)
-    ref = o.segment_track(specs, ref_in, dtype)
+    ref = o.segment_track(specs, ref_in, dtype, kick="product")  # (float32 behind an active cavity: _assert_moments)
     # north_star's tolerances, entry by entry.  Measured on MI355X (scripts/gpu/r3_pb_study.py, float32): product vs
     # float32 oracle 2.8e-5 (mu) / 4.0e-6 (cov), float32 oracle vs float64 oracle 7.9e-7 / 3.1e-5 -- nothing in
     # cavity.py:134-140, 202-218 cancels in float32 on this lattice.
@@ -1456,7 +1474,7 @@ def test_active_bpms_are_read_inside_the_streaming_pass(lx, dtype, n):
     assert len(items) == 1 and len(items[0].observers) == 4  # one program: nothing splits the pass
     out = seg.track(beam)
     readings = []
-    ref = o.segment_track(specs, o.particle_beam(P, energy, dtype), dtype, bpm_readings=readings)
+    ref = o.segment_track(specs, o.particle_beam(P, energy, dtype), dtype, bpm_readings=readings, kick="product")
     assert len(readings) == 4
     tol = TOL_MOM[dtype]
     sig_x = float(np.std(P[..., 0])) + 1e-4
@@ -1466,7 +1484,7 @@ def test_active_bpms_are_read_inside_the_streaming_pass(lx, dtype, n):
         assert np.all(np.abs(got - want) <= tol * (np.abs(want) + 3 * sig_x)), (name, got, want)
     assert seg.idle.reading is None
     got = np.asarray(out.particles)
-    ptol = {np.float32: [1e-4] * 4 + [1e-4, 5e-4, 1e-6], np.float64: [1e-9] * 7}[dtype]
+    ptol = {np.float32: [1e-4] * 6 + [1e-6], np.float64: [1e-9] * 7}[dtype]
     for c in range(7):
         assert rel_err(got[..., c], ref["particles"][..., c]) < ptol[c], c
     _assert_moments(out, ref, dtype)
@@ -1554,8 +1572,9 @@ def test_cavity_predicates_are_evaluated_on_the_device(lx, dtype):
     assert first._energy._host is None  # and tracking it did not read it back
     assert np.allclose(second.energy, 6e6 + 2e7, rtol=1e-6)
     ref1 = o.segment_track([o.Cavity(f(1.0), voltage=f(1e7), phase=f(0.0), frequency=f(1.3e9)), o.Drift(f(0.3))],
-                           o.particle_beam(P, f(6e6), dtype), dtype)
-    ref2 = o.segment_track([o.Cavity(f(1.0), voltage=f(1e7), phase=f(0.0), frequency=f(1.3e9)), o.Drift(f(0.3))], ref1, dtype)
+                           o.particle_beam(P, f(6e6), dtype), dtype, kick="product")
+    ref2 = o.segment_track([o.Cavity(f(1.0), voltage=f(1e7), phase=f(0.0), frequency=f(1.3e9)), o.Drift(f(0.3))], ref1, dtype,
+                           kick="product")
     _assert_moments(second, ref2, dtype)
 
 

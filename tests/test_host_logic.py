@@ -366,3 +366,59 @@ def test_objects_that_outlive_a_closed_runtime_are_dropped_quietly(built_library
     comm.rt = rt
     comm.close()
     rt.close()  # idempotent
+
+
+def _takes_ctx_or_lattice():
+    """Every declared function with a `lynx_ctx*` or `lynx_lattice*` parameter (not the `**` out-parameters)."""
+    header = re.sub(r"/\*.*?\*/", "", (ROOT / "include" / "lynx_hip.h").read_text(), flags=re.S)
+    out = []
+    for name, params in re.findall(r"\b(lynx_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header):
+        if re.search(r"\blynx_(ctx|lattice)\s*\*(?!\s*\*)", params):
+            out.append(name)
+    return sorted(out)
+
+
+_NULL_CALL = r"""
+import ctypes as C, sys
+sys.path.insert(0, sys.argv[1])
+from lynx_amd import _ffi
+lib = _ffi.load()
+name = sys.argv[2]
+restype, argtypes = _ffi.SIGNATURES[name]
+args = []
+for t in argtypes:
+    if t in (C.c_int, C.c_int32, C.c_int64, C.c_size_t, C.c_uint64):
+        args.append(t(1))  # a size of 0 may return early: every count is 1
+    else:
+        args.append(None)
+rc = getattr(lib, name)(*args)
+print("RC", 0 if restype is C.c_char_p else rc)
+"""
+
+
+@pytest.mark.parametrize("name", _takes_ctx_or_lattice())
+def test_a_null_context_or_lattice_is_an_error_not_a_crash(built_library, name):
+    """
+    Every entry point that takes a context or a lattice, called with NULL for it (and for every other pointer): an
+    error code -- LYNX_OK for the destroy / free calls, which accept NULL like free() -- and no crash.  Each call runs in
+    a child process, so that a segmentation fault fails this test instead of ending the run.
+    """
+    import subprocess
+    import sys
+
+    proc = subprocess.run([sys.executable, "-c", _NULL_CALL, str(ROOT), name], capture_output=True, text=True,
+                          timeout=120)
+    assert proc.returncode == 0, (name, proc.returncode, proc.stderr[-2000:])
+    rc = int(proc.stdout.split("RC")[-1])
+    if _ffi.SIGNATURES[name][0] is ctypes.c_char_p:  # lynx_last_error(NULL): the thread's last message
+        return
+    if name.endswith(("_destroy", "_free")):
+        assert rc in (0, -1), (name, rc)
+    else:
+        assert rc == -1, (name, rc)  # LYNX_ERR_INVALID
+
+
+def test_every_export_that_takes_a_context_or_a_lattice_is_covered():
+    names = _takes_ctx_or_lattice()
+    assert len(names) >= 35 and set(names) <= set(_ffi.SIGNATURES), names
+    assert "lynx_lattice_update_params" in names and "lynx_track_moments" in names

@@ -5,7 +5,8 @@ SURVEY.md section 8c: the reference's own tests hold no absolute numbers for dip
 misalignments or the cavity matrix ("parity unpinned" rows A1, A2, A6, A7, A9).  The oracle follows the
 reference line by line; these tests check the same maps against closed forms every accelerator-optics text
 derives (sector bend, thick quadrupole, thin edge wedge, Rosenzweig-Serafini cavity), so that a misreading of
-the reference would have to coincide with a physics error to go unnoticed.  float64, CPU only.
+the reference would have to coincide with a physics error to go unnoticed.  float64, CPU only.  At the end: the two
+forms of the cavity kick's difference of cosines the oracle can compute (float32 and float64).
 """
 
 import numpy as np
@@ -195,3 +196,99 @@ def test_cavity_off_crest_chirps_the_bunch():
     expect = V * s0 * k * np.sin(np.deg2rad(phase)) / e_out
     got = out["particles"][0, 1, 5] - out["particles"][0, 0, 5]
     assert np.isclose(got, expect, rtol=1e-3), (got, expect)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The two forms of the cavity kick's difference of cosines (oracle: cos_difference, kick="reference" | "product")
+# ---------------------------------------------------------------------------------------------------------------------
+
+
+def test_the_two_forms_of_the_difference_of_cosines_agree_in_float64():
+    """cos(phi) (cos d - 1) - sin(phi) sin d is cos(phi + d) - cos(phi): in float64 the forms agree to 1e-12 of the
+    difference's size (helpers.rel_err: relative to the largest |difference| of the set -- the difference crosses zero,
+    where the reference form's own rounding, 1e-16 absolute, is all there is), down to spreads of 1e-3 rad.  (Below that
+    the reference form's rounding alone is 1e-12 of the difference.)"""
+    from .helpers import rel_err
+
+    rng = np.random.default_rng(11)
+    for spread in (0.3, 1e-2, 1e-3):  # (C5: s beta0 k ~ 3e-4 for sigma_s = 1e-5)
+        d = np.concatenate([rng.uniform(-spread, spread, 2000), [0.0, spread, -spread]])
+        phi = np.deg2rad(rng.uniform(-30, 30, d.size))
+        a, b = o.cos_difference(d, phi, "product"), o.cos_difference(d, phi, "reference")
+        assert a.dtype == np.float64
+        assert rel_err(a, b) <= 1e-12, (spread, rel_err(a, b))
+    d = np.array([0.0, 0.25, -0.25, 0.2500001, 0.3, -1.0])
+    phi = np.deg2rad(np.array([3.0, -7.0, 10.0, 0.5, -2.0, 1.0]))
+    a, b = o.cos_difference(d, phi, "product"), o.cos_difference(d, phi, "reference")
+    # above |d| = 0.25 the product subtracts the two cosines itself: the same bits
+    big = np.abs(d) > o.COS_DIFFERENCE_SMALL
+    assert big.any() and np.array_equal(a[big], b[big])
+
+
+def _c5_like(B=16, N=10_000, sigma_s=1e-5):
+    """Eight cells of [Drift, misaligned Quadrupole, Drift, Cavity] at 6 MeV, 1.3 GHz: BASELINE config 5's shape."""
+    from .helpers import make_lattice
+
+    rng = np.random.default_rng(3)
+    f = lambda v: np.full(B, v)  # noqa: E731
+    desc = []
+    for _ in range(8):
+        desc += [("drift", dict(length=f(0.3))),
+                 ("quadrupole", dict(length=f(0.1), k1=rng.uniform(-5, 5, B), misalignment=rng.normal(0, 1e-4, (B, 2)))),
+                 ("drift", dict(length=f(0.3))),
+                 ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, B), phase=rng.uniform(-10, 10, B),
+                                 frequency=f(1.3e9)))]
+    _, s32 = make_lattice(desc, np.float32)
+    _, s64 = make_lattice([(k, {a: np.asarray(v, dtype=np.float32).astype(np.float64) for a, v in kw.items()})
+                           for k, kw in desc], np.float64)
+    P = o.gaussian_particles((B,), N, seed=3, dtype=np.float32, sigma=[1e-4, 1e-5, 1e-4, 1e-5, sigma_s, 1e-3])
+    e = np.full(B, 6e6, dtype=np.float32)
+    return s32, s64, P, e
+
+
+@pytest.mark.parametrize("sigma_s", [1e-5, 1e-4])
+def test_float32_product_kick_sits_on_the_float64_chain_and_the_reference_kick_does_not(sigma_s):
+    """
+    On a C5-like beam the float32 chain with the kernels' form of the kick is within 1e-6 of the float64 chain in mu_s,
+    mu_p and sigma_p (measured: 4e-9 .. 9e-8, 2e-7 .. 7e-7), the moments the kick decides.  sigma_s is set by the
+    float32 cavity MAP, not by the kick: it is the same under both forms (3e-6 from float64, measured).  The float32
+    chain with the reference's form -- two cosines that agree to four or five digits, subtracted -- is 2e-4 away in
+    mu_p: why a float32 rule built on it cannot be strict, and why the oracle computes the product's form.
+    """
+    from .helpers import moment_distances
+
+    s32, s64, P, e = _c5_like(sigma_s=sigma_s)
+    prod = o.segment_track(s32, o.particle_beam(P, e, np.float32), np.float32, kick="product")
+    ref = o.segment_track(s32, o.particle_beam(P, e, np.float32), np.float32, kick="reference")
+    r64 = o.segment_track(s64, o.particle_beam(P.astype(np.float64), e.astype(np.float64), np.float64), np.float64)
+    m64 = o.beam_moments(r64)
+    dp = moment_distances(o.beam_moments(prod), m64)
+    dr = moment_distances(o.beam_moments(ref), m64)
+    for key in ("mu_s", "mu_p", "sigma_p"):
+        assert dp[key] <= 1e-6, (key, dp[key])
+    assert dp["sigma_s"] <= 5e-6 and abs(dp["sigma_s"] - dr["sigma_s"]) <= 1e-7, (dp["sigma_s"], dr["sigma_s"])
+    assert dr["mu_p"] >= 1e-4 > 100 * dp["mu_p"], (dr["mu_p"], dp["mu_p"])
+    # only delta and s are touched by the form: the transverse coordinates are the same bits
+    assert np.array_equal(prod["particles"][..., :4], ref["particles"][..., :4])
+    assert np.array_equal(prod["energy"], ref["energy"])
+
+
+def test_the_product_kick_form_covers_the_parameter_beam_and_leaves_float64_alone():
+    s32, s64, _, e = _c5_like(B=4)
+    pb32 = o.parameter_beam_from_parameters(np.float32, sigma_x=np.full(4, 1e-4), sigma_xp=np.full(4, 1e-5),
+                                            mu_x=np.full(4, 1e-4), sigma_s=np.full(4, 1e-5), sigma_p=np.full(4, 1e-3),
+                                            energy=np.full(4, 6e6))
+    pb32["mu"][..., 4] = np.float32(2e-5)  # a bunch off the crest's reference point: the kick sees mu_s
+    prod = o.segment_track(s32, pb32, np.float32, kick="product")
+    ref = o.segment_track(s32, pb32, np.float32, kick="reference")
+    pb64 = {k: (v.astype(np.float64) if isinstance(v, np.ndarray) else v) for k, v in pb32.items()}
+    r64 = o.segment_track(s64, pb64, np.float64)
+    scale = np.abs(r64["mu"][..., 5]) + np.sqrt(r64["cov"][..., 5, 5])
+    d_prod = np.max(np.abs(prod["mu"][..., 5] - r64["mu"][..., 5]) / scale)
+    d_ref = np.max(np.abs(ref["mu"][..., 5] - r64["mu"][..., 5]) / scale)
+    assert d_prod <= 1e-6 and d_ref > 10 * d_prod, (d_prod, d_ref)
+    assert np.array_equal(prod["cov"], ref["cov"]) and np.array_equal(prod["mu"][..., :4], ref["mu"][..., :4])
+    q64 = o.segment_track(s64, pb64, np.float64, kick="product")
+    assert np.array_equal(q64["mu"], r64["mu"]) and np.array_equal(q64["cov"], r64["cov"])
+    with pytest.raises(AssertionError):
+        o.segment_track(s32, pb32, np.float32, kick="fast")
