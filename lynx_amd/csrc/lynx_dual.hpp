@@ -4,10 +4,20 @@
 // parameter.  Instead of hand-deriving the partials of base_rmatrix / dipole edges / the
 // cavity's T566..T555 terms, the builders of lynx_maps.hpp are instantiated a second time
 // with T = Dual<float|double>: one seeded evaluation per (element, parameter) yields the
-// exact derivative of all 49 map entries and of the 8 cavity coefficients.
+// derivative of all 49 map entries and of the 8 cavity coefficients.
 // Comparisons act on the value part, so the builders take the same branches as the forward
-// pass (including `k1 == 0 -> 1e-12`, whose derivative is 0 exactly as in an autograd trace
-// of the reference).
+// pass.  The derivative is that of the continuous map, not of the formulas as written where
+// those cancel:
+//  - `k1 == 0 -> 1e-12` (track_methods.py:67-68) keeps the derivative part, so a quadrupole at
+//    k1 = 0 gets the limit of dM/dk1 (an autograd trace of the reference gives 0 there only
+//    because the substitution is an in-place write);
+//  - cos(sqrt(k2) L) and sin(sqrt(k2) L)/sqrt(k2) keep their values and take their derivative
+//    from the power series in x = k2 L^2 while |x| < 1 (dual_series below): the closed form
+//    differentiates to (L C - S)/(2 k2), which loses all digits as k2 -> 0;
+//  - the bend's (1 - C)/k2 and (L - S)/k2 are that series, value and derivative (base_dx_dual):
+//    their values, as the reference writes them, cancel in the same way;
+//  - so does the solenoid's sin(kL)/k (solenoid_s_k_dual);
+//  - the cavity's r55 bracket does not cancel (cavity_r55_bracket_dual).
 #pragma once
 
 #include "lynx_maps.hpp"
@@ -65,7 +75,22 @@ LYNX_DUAL_ALL(float)
 LYNX_DUAL_ALL(double)
 #undef LYNX_DUAL_ALL
 
-// cs_of (lynx_maps.hpp) for dual numbers, inline for the same reason
+// sum_{m >= 0} (-x)^m j! / (2m + j)!  =  1 - x / ((j+1)(j+2)) (1 - x / ((j+3)(j+4)) (1 - ...)), nested from the inside.
+// With x = k2 L^2:  C = P_0(x),  S = L P_1(x),  (1 - C)/k2 = L^2 P_2(x) / 2,  (L - S)/k2 = L^3 P_3(x) / 6 -- entire
+// functions of k2 whose derivatives (through the dual arithmetic, in k2 and L alike) do not cancel.  For |x| < 1 the
+// first left-out term is below 1/12! (float, 6 terms) and 1/20! (double, 10 terms): under the type's epsilon.
+template <typename R> LYNX_HD Dual<R> dual_series(Dual<R> x, int j) {
+  constexpr int N = sizeof(R) == 4 ? 6 : 10;
+  const Dual<R> one(R(1));
+  Dual<R> t = one;
+#pragma unroll
+  for (int m = N - 1; m >= 1; --m) t = one - x * t / Dual<R>(R((j + 2 * m - 1) * (j + 2 * m)));
+  return t;
+}
+template <typename R> LYNX_HD bool dual_series_converges(Dual<R> x) { return x.v > R(-1) && x.v < R(1); }
+
+// cs_of (lynx_maps.hpp) for dual numbers, inline for the same reason; values as the plain builder's, derivatives from the
+// series near k2 = 0 (dS/dk2 written out is (L C - S) / (2 k2))
 template <typename R> LYNX_HD void cs_of(Dual<R> k2, Dual<R> L, Dual<R> s_at_zero, Dual<R>& c, Dual<R>& s) {
   if (k2.v > R(0)) {
     const Dual<R> a = t_sqrt(k2), x = a * L;
@@ -79,7 +104,47 @@ template <typename R> LYNX_HD void cs_of(Dual<R> k2, Dual<R> L, Dual<R> s_at_zer
     c = Dual<R>(R(1));
     s = s_at_zero;
   }
+  const Dual<R> x = k2 * (L * L);
+  if (dual_series_converges(x)) {
+    c.d = dual_series(x, 0).d;
+    s.d = (L * dual_series(x, 1)).d;
+  }
 }
+
+// nonzero_k1, base_dx, base_r56_bend (lynx_maps.hpp) for dual numbers: the substitution keeps the derivative part; the
+// bend's (1 - cx)/kx2 and (L - sx)/kx2 are the series while it converges, value and derivative.  The values matter too:
+// the edges and the tilt multiply M[0][5], M[4][1], M[4][5] into other entries, so the derivative of those entries is
+// as good as these values (the plain form's (1 - cx) is 0 in float32 below |x| ~ 1e-8, where dx is hx L^2 / 2)
+template <typename R> LYNX_HD Dual<R> nonzero_k1_dual(Dual<R> k1) { return k1.v == R(0) ? Dual<R>(R(1e-12), k1.d) : k1; }
+template <typename R> LYNX_HD Dual<R> base_dx_dual(Dual<R> hx, Dual<R> kx2, Dual<R> L, Dual<R> cx) {
+  const Dual<R> x = kx2 * (L * L);
+  if (dual_series_converges(x)) return hx * (L * L) * dual_series(x, 2) / Dual<R>(R(2));
+  return hx / kx2 * (Dual<R>(R(1)) - cx);
+}
+template <typename R> LYNX_HD Dual<R> base_r56_bend_dual(Dual<R> hx, Dual<R> kx2, Dual<R> L, Dual<R> sx, Dual<R> beta) {
+  const Dual<R> x = kx2 * (L * L);
+  if (dual_series_converges(x)) return hx * hx * (L * L * L) * dual_series(x, 3) / Dual<R>(R(6)) / (beta * beta);
+  return hx * hx * (L - sx) / kx2 / (beta * beta);
+}
+// solenoid_s_k: sin(kL)/k is S of k2 = k^2; its value as the plain builder's, its derivative from the series
+template <typename R> LYNX_HD Dual<R> solenoid_s_k_dual(Dual<R> s, Dual<R> k, Dual<R> L) {
+  Dual<R> s_k = k.v != R(0) ? s / k : L;
+  const Dual<R> kl = k * L, x = kl * kl;
+  if (dual_series_converges(x)) s_k.d = (L * dual_series(x, 1)).d;
+  return s_k;
+}
+#define LYNX_DUAL_BASE(R)                                                                                                  \
+  template <> LYNX_HD Dual<R> nonzero_k1<Dual<R>>(Dual<R> k1) { return nonzero_k1_dual<R>(k1); }                            \
+  template <> LYNX_HD Dual<R> base_dx<Dual<R>>(Dual<R> hx, Dual<R> kx2, Dual<R> L, Dual<R> cx) {                            \
+    return base_dx_dual<R>(hx, kx2, L, cx);                                                                                  \
+  }                                                                                                                          \
+  template <> LYNX_HD Dual<R> base_r56_bend<Dual<R>>(Dual<R> hx, Dual<R> kx2, Dual<R> L, Dual<R> sx, Dual<R> beta) {        \
+    return base_r56_bend_dual<R>(hx, kx2, L, sx, beta);                                                                      \
+  }                                                                                                                          \
+  template <> LYNX_HD Dual<R> solenoid_s_k<Dual<R>>(Dual<R> s, Dual<R> k, Dual<R> L) { return solenoid_s_k_dual<R>(s, k, L); }
+LYNX_DUAL_BASE(float)
+LYNX_DUAL_BASE(double)
+#undef LYNX_DUAL_BASE
 
 // cavity_r55_bracket (lynx_maps.hpp) without its cancellations: with a = 1/g0^2, b = 1/g1^2,
 //   beta0 beta1 - 1 = ((1 - a)(1 - b) - 1) / (beta0 beta1 + 1) = -(a + b - a b) / (1 + beta0 beta1)          =: -eps

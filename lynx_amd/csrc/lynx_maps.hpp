@@ -173,6 +173,16 @@ template <typename T> LYNX_FN void build_drift(T L, T energy, T* M) {
   M[4 * 7 + 5] = -L / (beta * beta) * igamma2;
 }
 
+// Three expressions of base_rmatrix (track_methods.py:67-81) as the reference writes them.  Each is a function of its own
+// so that the dual-number instantiation (lynx_dual.hpp) can specialise it, as it does cavity_r55_bracket: there the
+// substitution keeps the derivative part, and the two quotients that cancel as kx2 -> 0 get their derivative from a
+// series.  The plain builders compile exactly these operations.
+template <typename T> LYNX_HD T nonzero_k1(T k1) { return k1 == T(0) ? T(1e-12) : k1; }  // :67-68
+template <typename T> LYNX_HD T base_dx(T hx, T kx2, T L, T cx) { return hx / kx2 * (T(1) - cx); }  // :80
+template <typename T> LYNX_HD T base_r56_bend(T hx, T kx2, T L, T sx, T beta) {  // :81
+  return hx * hx * (L - sx) / kx2 / (beta * beta);
+}
+
 // The scalars of lynx/track_methods.py:37-99 (`base_rmatrix` without the tilt rotation): what both the 7x7 builder below
 // and the 16-entry builder of structured maps (build_entries_u) put into their matrices.
 template <typename T> struct BaseScalars {
@@ -184,15 +194,15 @@ template <typename T> LYNX_HD void base_rmatrix_scalars(T L, T k1, T hx, T energ
   if (gamma != T(0)) igamma2 = T(1) / (gamma * gamma);
   T beta = t_sqrt(T(1) - igamma2);
 
-  if (k1 == T(0)) k1 = T(1e-12);  // :67-68
+  k1 = nonzero_k1(k1);  // :67-68
 
   T kx2 = k1 + hx * hx;
   T ky2 = -k1;
   T cx, sx, cy, sy;
   cs_of(kx2, L, T(0) / T(0) * L, cx, sx);  // kx == 0: sin(0)/0 -> NaN (:79)
   cs_of(ky2, L, L, cy, sy);                // ky == 0: sy = length   (:76)
-  T dx = hx / kx2 * (T(1) - cx);
-  T r56 = hx * hx * (L - sx) / kx2 / (beta * beta);
+  T dx = base_dx(hx, kx2, L, cx);
+  T r56 = base_r56_bend(hx, kx2, L, sx, beta);
   r56 = r56 - L / (beta * beta) * igamma2;
   o.cx = cx; o.sx = sx; o.cy = cy; o.sy = sy; o.dx = dx; o.r56 = r56; o.kx2 = kx2; o.ky2 = ky2; o.beta = beta;
 }
@@ -416,13 +426,16 @@ template <typename T> LYNX_FN T build_cavity(const T* p, int flags, T energy, T*
   return energy_out;
 }
 
+// sin(kL)/k as solenoid.py:68-70 writes it; a function of its own for the dual-number specialisation (lynx_dual.hpp),
+// whose derivative of it cancels as k -> 0 like that of base_rmatrix's S
+template <typename T> LYNX_HD T solenoid_s_k(T s, T k, T L) { return k != T(0) ? s / k : L; }
+
 // lynx/accelerator/solenoid.py:61-105.  p = [L, k, mx, my]
 template <typename T> LYNX_FN void build_solenoid(const T* p, int flags, T energy, T* M) {
   const T L = p[0], k = p[1];
   const T gamma = energy / T(LYNX_REST_ENERGY);
   const T c = t_cos(L * k), s = t_sin(L * k);
-  T s_k = L;
-  if (k != T(0)) s_k = s / k;  // :68-70
+  const T s_k = solenoid_s_k(s, k, L);  // :68-70
   T r56 = T(0);
   if (gamma != T(0)) {  // :73-76
     const T gamma2 = gamma * gamma;

@@ -62,3 +62,26 @@ extern "C" int harness_entries_u_f64(int kind, int flags, const double* p, doubl
   for (int k = 0; k < 16; ++k) m16[k] = m[k];
   return ok ? 1 : 0;
 }
+
+// ... and its dual-number evaluation, the builder k_build_bwd differentiates class-U kinds with: entries and their
+// derivative w.r.t. parameter `seed` (seed == n_params: the beam energy); returns 1, or 0 for the other kinds.
+template <typename R>
+static int entries_u_dual(int kind, int flags, const R* p, int n_params, R energy, int seed, R* m16, R* dm16, R* coef,
+                          R* dcoef) {
+  lynx::Dual<R> dp[8], m[16], dc[8];
+  for (int q = 0; q < 8; ++q) dp[q] = lynx::Dual<R>(q < n_params ? p[q] : R(0), q == seed ? R(1) : R(0));
+  for (int q = 0; q < 8; ++q) dc[q] = lynx::Dual<R>(R(0));
+  const lynx::Dual<R> de(energy, seed == n_params ? R(1) : R(0));
+  const bool ok = lynx::build_entries_u<lynx::Dual<R>>(kind, flags, dp, de, m, dc);
+  for (int k = 0; k < 16; ++k) { m16[k] = m[k].v; dm16[k] = m[k].d; }
+  for (int q = 0; q < 8; ++q) { coef[q] = dc[q].v; dcoef[q] = dc[q].d; }
+  return ok ? 1 : 0;
+}
+extern "C" int harness_entries_u_dual_f32(int kind, int flags, const float* p, int n_params, float energy, int seed,
+                                          float* m16, float* dm16, float* coef, float* dcoef) {
+  return entries_u_dual<float>(kind, flags, p, n_params, energy, seed, m16, dm16, coef, dcoef);
+}
+extern "C" int harness_entries_u_dual_f64(int kind, int flags, const double* p, int n_params, double energy, int seed,
+                                          double* m16, double* dm16, double* coef, double* dcoef) {
+  return entries_u_dual<double>(kind, flags, p, n_params, energy, seed, m16, dm16, coef, dcoef);
+}
