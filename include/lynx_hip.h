@@ -228,6 +228,26 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
                        const void* d_mu_in, const void* d_cov_in, void* d_mu_out,
                        void* d_cov_out, void* d_energy_out);
 
+/* The beam ALONG the lattice: the moment record and the beam energy at the entrance (point 0) and behind every step
+ * (point k), from one pass over the particles (reference: the loop of Segment.plot_twiss / plot_twiss_over_lattice,
+ * segment.py -- `element.track(beam)` element by element and beta_x, beta_y of every intermediate beam -- and
+ * plot_reference_particle_traces; 2 E passes over the particle array there).  The program is expected to hold every
+ * element as a step of its own (LYNX_STEP_FLAG_RAW: element.py:72,84 applies the element's map as it is; active
+ * cavities as cavity steps, cavity.py:81-246); P = n_steps + 1 points, no limit on n_steps other than memory.
+ *   d_p_in           [B][N][7] ([N][7] with LYNX_TRACK_SHARED_INPUT, the only flag)
+ *   d_p_out          [B][N][7] or NULL: moments only, half the traffic (may alias d_p_in unless that is shared)
+ *   d_energy_trace   [B][P]     beam energy at every point, particle dtype
+ *   d_trace_out      [B][P][36] float64 moment records, layout of LYNX_MOMENT_STRIDE, slot 34 = 1 (whole triangle)
+ * The sums are taken about a reference point that travels with the beam (the sample's first particle, taken through
+ * the same maps) and added in a fixed order: the same call returns the same bits.                                  */
+int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                               const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags);
+
+/* ... of a ParameterBeam (reference: the same loop; element.py:71-82 mu' = T mu, cov' = T cov T^T per element,
+ * cavity.py:134-140,202-218): d_mu_trace [B][P][7], d_cov_trace [B][P][7][7], d_energy_trace [B][P].              */
+int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
+                             const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace);
+
 /* Reverse pass of lynx_track_particles: gradient of a scalar function L of the outgoing
  * beam's moment record with respect to every element parameter and the incoming energy
  * (the reference only claims differentiability, setup.py:14-17,

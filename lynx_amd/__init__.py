@@ -9,6 +9,7 @@ from . import config
 from .accelerator import *  # noqa: F401,F403  (the element classes and Segment)
 from .accelerator import __all__ as _elements
 from .particles import Beam, ParameterBeam, ParticleBeam
+from .trace import BeamTrace
 
-__all__ = ["config", "Beam", "ParameterBeam", "ParticleBeam", *_elements]
+__all__ = ["config", "Beam", "BeamTrace", "ParameterBeam", "ParticleBeam", *_elements]
 __version__ = "0.1.0"

@@ -199,6 +199,19 @@ class Segment(Element):
         """segment.py:340-356."""
         return engine.track(self, self.elements, incoming)
 
+    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True):
+        """
+        The beam ALONG the lattice: its moments and energy at the entrance and behind every leaf element (nested
+        segments opened up), for every batch sample, from one pass over the particles -- the data behind the reference's
+        `plot_twiss` / `plot_twiss_over_lattice` (segment.py: `element.track` element by element) and, with
+        `resolution`, `plot_reference_particle_traces` (the lattice is `split(resolution)` first).  Returns a
+        `lynx_amd.trace.BeamTrace`; `keep_outgoing=False` does not store the tracked particles (moments only).
+        Unlike `plot_twiss`, zero-length elements are tracked and have a point (`BeamTrace.where_length_changes()`).
+        """
+        if resolution is not None:
+            return Segment(self.split(resolution), name=self.name).track_along(incoming, keep_outgoing=keep_outgoing)
+        return engine.track_along(self, self._leaves(), incoming, keep_outgoing)
+
     def forward(self, incoming):
         return self.track(incoming)
 

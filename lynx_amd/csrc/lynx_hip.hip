@@ -21,6 +21,7 @@
 #include "lynx_grad.hpp"
 #include "lynx_units.hpp"
 #include "lynx_grad_units.hpp"
+#include "lynx_trace.hpp"
 
 using namespace lynx;
 
@@ -166,9 +167,11 @@ struct lynx_ctx {
   size_t scratch_products_bytes = 0;
   void* scratch_coefs = nullptr;     // ... and cavity coefficients [S][8][Bp]
   size_t scratch_coefs_bytes = 0;
-  static constexpr int kTableBwd = kTableSlots, kTablePb = kTableSlots + 1;
-  void* scratch_steps[kTableSlots + 2] = {};  // the ring of step tables, the reverse pass's own, the ParameterBeam lanes path's
-  size_t scratch_steps_bytes[kTableSlots + 2] = {};
+  static constexpr int kTableBwd = kTableSlots, kTablePb = kTableSlots + 1, kTableTrace = kTableSlots + 2;
+  void* scratch_steps[kTableSlots + 3] = {};  // the ring of step tables, the reverse pass's own, the ParameterBeam lanes path's, the beam trace's
+  size_t scratch_steps_bytes[kTableSlots + 3] = {};
+  void* scratch_trace[2] = {nullptr, nullptr};  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
+  size_t scratch_trace_bytes[2] = {0, 0};
   void* scratch_units_bwd[2] = {nullptr, nullptr};  // ... and of the reverse pass's own table
   size_t scratch_units_bwd_bytes[2] = {0, 0};
   void* scratch_units[2 * kTableSlots] = {};  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
@@ -618,8 +621,10 @@ int lynx_ctx_destroy(lynx_ctx* ctx) {
   if (ctx->d_spec_valid) (void)hipFree(ctx->d_spec_valid);
   if (ctx->scratch_products) (void)hipFree(ctx->scratch_products);
   if (ctx->scratch_coefs) (void)hipFree(ctx->scratch_coefs);
-  for (int i = 0; i < lynx_ctx::kTableSlots + 2; ++i)
+  for (int i = 0; i < lynx_ctx::kTableSlots + 3; ++i)
     if (ctx->scratch_steps[i]) (void)hipFree(ctx->scratch_steps[i]);
+  for (int i = 0; i < 2; ++i)
+    if (ctx->scratch_trace[i]) (void)hipFree(ctx->scratch_trace[i]);
   for (int i = 0; i < 2 * lynx_ctx::kTableSlots; ++i)
     if (ctx->scratch_units[i]) (void)hipFree(ctx->scratch_units[i]);
   for (int i = 0; i < 2; ++i)
@@ -1305,10 +1310,11 @@ static int launch_build_lanes(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stre
 template <typename T>
 static int launch_build(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stream, const void* d_energy_in,
                         void* d_steps_out, void* d_energy_out, int merge_pairs = 0, bool underneath = false,
-                        float* d_units = nullptr, float* d_extras = nullptr) {
+                        float* d_units = nullptr, float* d_extras = nullptr, bool force_lanes = false) {
   // large batches: lanes = samples (an order of magnitude fewer wave-instructions); small ones: one
   // workgroup per sample, whose tree is shallower than a chain of launches
-  const bool lanes = lat->n_steps > 0 && lat->batch >= ctx->knobs.lanes_build_min_batch;
+  // (`force_lanes`: the workgroup build keeps the whole table in LDS; a caller whose table would not fit says so)
+  const bool lanes = lat->n_steps > 0 && (force_lanes || lat->batch >= ctx->knobs.lanes_build_min_batch);
   {
     const int rc = launch_cavity_flags<T>(ctx, lat, stream, d_energy_in, lanes);
     if (rc) return rc;
@@ -2391,6 +2397,137 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
   return lat->dtype == LYNX_F64
              ? launch_track_moments<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_out, d_cov_out, d_energy_out)
              : launch_track_moments<float>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_out, d_cov_out, d_energy_out);
+}
+
+// ---- beam trace: the moments at every element of the lattice ---------------------------------
+
+// The table of a program whose every element is a step of its own, [B][E][64], in the trace's own slot (the ring of
+// the forward calls -- and with it the table a reverse pass may still want -- is left alone), on the main stream.
+template <typename T>
+static int trace_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in) {
+  int rc;
+  const size_t need = std::max<size_t>(1, (size_t)lat->batch * lat->n_steps) * LYNX_STEP_STRIDE * sizeof(T);
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableTrace], &ctx->scratch_steps_bytes[lynx_ctx::kTableTrace], need)))
+    return rc;
+  if (lat->n_steps == 0) return LYNX_OK;
+  // no limit on the number of elements: where the workgroup build's table would not fit its LDS, lanes = samples
+  int threads, chunk;
+  build_shape<T>(ctx, lat, false, &threads, &chunk);
+  const size_t lds = build_scratch_bytes(chunk, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1) * sizeof(T);
+  return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableTrace], nullptr, 0, false, nullptr,
+                         nullptr, lds > (size_t)64 * 1024);
+}
+
+template <typename T>
+static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in, const void* d_p_in,
+                                   void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags) {
+  constexpr int U = sizeof(T) == 4 ? 4 : 2;  // particles per lane (float32: two packed pairs)
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps, P = S + 1;
+  int rc;
+  if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
+  // Waves per sample: enough of them to fill the GPU three waves per SIMD deep over the whole batch, whole workgroups
+  // of four, never more than there are tiles -- and few enough for the slabs (256 bytes per wave and point) to stay
+  // below 1 GiB.  The plan depends on the shapes alone: the same call adds the same numbers in the same order.
+  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t tiles = (N + 64 * U - 1) / (64 * U);
+  int64_t waves = std::max<int64_t>(1, (cus * 12 + B - 1) / B);
+  const int64_t slab_cap = std::max<int64_t>(1, ((int64_t)1 << 30) / (B * P * kTraceSlab * (int64_t)sizeof(double)));
+  waves = std::min(std::min(waves, tiles), slab_cap);
+  const int64_t tiles_per_wave = (tiles + waves - 1) / waves;
+  waves = ((tiles + tiles_per_wave - 1) / tiles_per_wave + 3) / 4 * 4;
+  if (B * (waves / 4) > 0x7fffffffLL || B * P > 0x7fffffffLL || tiles_per_wave > 0x7fffffffLL)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace: batch x points too large for one launch");
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace[0], &ctx->scratch_trace_bytes[0],
+                           (size_t)B * waves * P * kTraceSlab * sizeof(double))) ||
+      (rc = ensure_scratch(ctx, &ctx->scratch_trace[1], &ctx->scratch_trace_bytes[1], (size_t)B * P * kTraceRef * sizeof(T))))
+    return rc;
+  TraceArgs a{};
+  a.n_particles = N;
+  a.in_stride = (flags & LYNX_TRACK_SHARED_INPUT) ? 0 : N * 7;
+  a.waves = (int32_t)waves;
+  a.tiles_per_wave = (int32_t)tiles_per_wave;
+  a.store = d_p_out ? 1 : 0;
+  a.points = P;
+  const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
+  hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
+                     (const T*)d_energy_in, (const T*)d_p_in, a.in_stride, (T*)ctx->scratch_trace[1], (T*)d_energy_trace);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL((k_trace_particles<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, S, table,
+                     (const T*)ctx->scratch_trace[1], (const T*)d_p_in, (T*)d_p_out, (double*)ctx->scratch_trace[0]);
+  HIP_TRY(ctx, hipGetLastError());
+  // (few waves per sample: 8 groups of them; hundreds to thousands -- few samples of many particles: 32)
+  if (waves > 256)
+    hipLaunchKernelGGL((k_trace_finalize<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
+                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, N, d_trace_out);
+  else
+    hipLaunchKernelGGL((k_trace_finalize<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
+                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, N, d_trace_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                               const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
+  if (flags & ~LYNX_TRACK_SHARED_INPUT) return fail(ctx, LYNX_ERR_INVALID, "beam trace: LYNX_TRACK_SHARED_INPUT is the only flag");
+  if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out)
+    return fail(ctx, LYNX_ERR_INVALID, "a shared incoming beam cannot be tracked in place");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
+  HIP_TRY(ctx, use_device(ctx));
+  ctx->main_dirty = true;
+  const size_t es = dtype_size(lat->dtype);
+  const size_t points = (size_t)lat->n_steps + 1;
+  ctx->wrote(d_p_out, (size_t)lat->batch * n_particles * 7 * es);
+  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
+  ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
+  return lat->dtype == LYNX_F64
+             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags)
+             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags);
+}
+
+template <typename T>
+static int track_moments_along_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
+                                 const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace) {
+  int rc;
+  if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
+  const int64_t B = lat->batch;
+  const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
+  hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
+                     (const T*)d_energy_in, (const T*)nullptr, (int64_t)0, (T*)nullptr, (T*)d_energy_trace);
+  HIP_TRY(ctx, hipGetLastError());
+  // large float32 batches: lanes = samples (float64: 98 registers of covariance per lane, see launch_track_moments)
+  if (sizeof(T) == 4 && B >= ctx->knobs.lanes_build_min_batch) {
+    hipLaunchKernelGGL(k_trace_moments_lanes<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), apply_moments_lds<T>(), ctx->stream,
+                       dev_view(lat), table, (const T*)d_mu_in, (const T*)d_cov_in, (T*)d_mu_trace, (T*)d_cov_trace);
+  } else {
+    hipLaunchKernelGGL(k_trace_moments<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, dev_view(lat), table, (const T*)d_mu_in,
+                       (const T*)d_cov_in, (T*)d_mu_trace, (T*)d_cov_trace);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
+                             const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  if (!lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_trace || !d_cov_trace || !d_energy_trace)
+    return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
+  HIP_TRY(ctx, use_device(ctx));
+  ctx->main_dirty = true;
+  const size_t es = dtype_size(lat->dtype);
+  const size_t points = (size_t)lat->n_steps + 1;
+  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
+  ctx->wrote(d_mu_trace, (size_t)lat->batch * points * 7 * es);
+  ctx->wrote(d_cov_trace, (size_t)lat->batch * points * 49 * es);
+  return lat->dtype == LYNX_F64
+             ? track_moments_along_t<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace)
+             : track_moments_along_t<float>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace);
 }
 
 // ---- screen read-out -------------------------------------------------------------------------

@@ -1,0 +1,556 @@
+// gfx950 kernels of the beam trace: the moments of the beam at the entrance and behind EVERY element of a
+// lattice from one pass over the particles (lynx_track_particles_along), and the ParameterBeam's counterpart
+// (lynx_track_moments_along).  Included only by lynx_hip.hip, behind lynx_device.hpp.
+//
+// What the reference does for this is the loop of `Segment.plot_twiss` (segment.py: `element.track(beam)` element by
+// element, `beta_x`, `beta_y` of every intermediate beam): 2 E passes over the particle array.  Here:
+//
+//   table      [B][E][64]   every element a step of its own (the existing builders; LYNX_STEP_FLAG_RAW)
+//   k_trace_reference       one lane per sample takes the sample's FIRST particle through the E steps and writes its
+//                           coordinates at every point, [B][P][8], next to the beam energy there, [B][P].  That
+//                           trajectory is the reference point the sums of every point are taken about: it moves with the
+//                           centroid (correctors, misaligned quadrupoles, a cavity's delta), so float32 products do
+//                           not cancel; it is the same for every wave of a sample, so the records add up as they are.
+//   k_trace_particles       a wave loads a tile of 64 U particles ONCE, keeps them in registers and takes them through
+//                           the E steps; at every point each lane forms the 28 shifted sums of its U particles
+//                           (6 first moments, the 7th column, 21 products), the wave folds them with a transposing
+//                           butterfly (32 exchanges for all 28 sums, not 6 x 28) and adds the result into ITS OWN
+//                           float64 slab [P][32] in memory -- the same lane reads and writes the same cell, tile after
+//                           tile: no atomics, one fixed order.
+//   k_trace_finalize        adds the waves' slabs of a (sample, point) in a fixed order and writes the moment record
+//                           [B][P][36] (layout of LYNX_MOMENT_STRIDE, slot 34 = 1).
+#pragma once
+
+#include "lynx_device.hpp"
+
+namespace lynx {
+
+constexpr int kTraceSlab = 32;  // float64 cells per (wave, point): 28 sums, padded to a power of two for the butterfly
+constexpr int kTraceRef = 8;    // scalars per (sample, point) of the reference trajectory (6 used)
+
+struct TraceArgs {
+  int64_t n_particles;
+  int64_t in_stride;      // scalars between the samples of p_in: N * 7, or 0 for one shared incoming beam
+  int32_t waves;          // waves per sample (a multiple of 4: whole workgroups)
+  int32_t tiles_per_wave;
+  int32_t store;          // 1: write p_out
+  int32_t points;         // P = E + 1
+};
+
+// ---------------------------------------------------------------------------------------
+// k_trace_reference: reference trajectory and energies, one lane per sample.
+// Energy behind an active cavity: E + V cos(phi), the expression of energy_before_step (cavity.py:130).
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_reference(LatticeDev lat, const T* __restrict__ steps,
+                                                        const T* __restrict__ energy_in, const T* __restrict__ p_in,
+                                                        int64_t in_stride, T* __restrict__ ref_out /* null: energies only */,
+                                                        T* __restrict__ energy_trace) {
+  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (b >= lat.batch) return;
+  const int S = lat.n_steps, P = S + 1;
+  const T* pool = static_cast<const T*>(lat.pool);
+  T z[7] = {T(0), T(0), T(0), T(0), T(0), T(0), T(1)};
+  if (ref_out) load_particle(p_in + b * in_stride, z);
+  T e = energy_in[b];
+  for (int s = 0; s <= S; ++s) {
+    if (ref_out) {
+      T* r = ref_out + (b * P + s) * kTraceRef;
+#pragma unroll
+      for (int k = 0; k < 7; ++k) r[k] = z[k];
+      r[7] = T(0);
+    }
+    energy_trace[b * P + s] = e;
+    if (s == S) break;
+    const T* M = steps + (b * S + s) * LYNX_STEP_STRIDE;
+    const int desc = (int)M[LYNX_FLAGS_OFFSET];
+    const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
+    if (ref_out) apply_step<T>(M, skind, sflags, z);
+    if (skind == LYNX_STEP_CAVITY && (sflags & LYNX_FLAG_CAV_GAIN)) {
+      const lynx_elem el = lat.elems[lat.steps[s].first];
+      const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
+      e = e + p[1] * t_cos(p[2] * T(LYNX_PI / 180.0));
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// The transposing butterfly: every lane holds 32 values; afterwards v[0] of lane l is the sum over all 64 lanes of
+// value (l >> 1).  Level by level a lane keeps one half of its values and hands the other half to the lane whose
+// index differs in one bit: 16 + 8 + 4 + 2 + 1 exchanges, then one more between neighbours.
+// ---------------------------------------------------------------------------------------
+// The two widest levels (partner 32 and 16 lanes away) as gfx950's lane swaps: v_permlane32_swap exchanges the upper
+// half of its first operand with the lower half of its second, v_permlane16_swap the odd rows of 16 lanes of the first
+// with the even rows of the second -- afterwards one register holds, in every lane, this lane's kept value and the
+// other the value it was handed: one swap and one add per pair, no select, nothing through the LDS crossbar.
+template <int HALF>
+__device__ __forceinline__ void trace_lane_swap(unsigned& a, unsigned& b) {
+  static_assert(HALF == 16 || HALF == 8, "partner 32 or 16 lanes away");
+  if constexpr (HALF == 16) {
+    const auto r = __builtin_amdgcn_permlane32_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+  } else {
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    a = r[0];
+    b = r[1];
+  }
+}
+template <int HALF>
+__device__ __forceinline__ float trace_swap_add(float lo, float hi) {
+  unsigned a = __float_as_uint(lo), b = __float_as_uint(hi);
+  trace_lane_swap<HALF>(a, b);
+  return __uint_as_float(a) + __uint_as_float(b);
+}
+template <int HALF>
+__device__ __forceinline__ double trace_swap_add(double lo, double hi) {
+  const unsigned long long x = (unsigned long long)__double_as_longlong(lo), y = (unsigned long long)__double_as_longlong(hi);
+  unsigned a0 = (unsigned)(x & 0xffffffffull), a1 = (unsigned)(x >> 32), b0 = (unsigned)(y & 0xffffffffull), b1 = (unsigned)(y >> 32);
+  trace_lane_swap<HALF>(a0, b0);
+  trace_lane_swap<HALF>(a1, b1);
+  return __longlong_as_double((long long)(((unsigned long long)a1 << 32) | a0)) +
+         __longlong_as_double((long long)(((unsigned long long)b1 << 32) | b0));
+}
+
+template <typename R, int HALF>
+__device__ __forceinline__ void trace_fold(R (&v)[kTraceSlab], int lane) {
+  if constexpr (HALF >= 8) {
+#pragma unroll
+    for (int i = 0; i < HALF; ++i) v[i] = trace_swap_add<HALF>(v[i], v[i + HALF]);
+    return;
+  }
+  const bool up = (lane & (HALF * 2)) != 0;
+#pragma unroll
+  for (int i = 0; i < HALF; ++i) {
+    const R keep = up ? v[i + HALF] : v[i];
+    const R send = up ? v[i] : v[i + HALF];
+    v[i] = keep + __shfl_xor(send, HALF * 2, 64);
+  }
+}
+template <typename R>
+__device__ __forceinline__ R trace_wave_sums(R (&v)[kTraceSlab], int lane) {
+  trace_fold<R, 16>(v, lane);
+  trace_fold<R, 8>(v, lane);
+  trace_fold<R, 4>(v, lane);
+  trace_fold<R, 2>(v, lane);
+  trace_fold<R, 1>(v, lane);
+  return v[0] + __shfl_xor(v[0], 1, 64);
+}
+
+__device__ __forceinline__ double vfma(double a, double b, double c) { return fma(a, b, c); }
+
+// products of the shifted coordinates, the 21 of the upper triangle, spelled out by recursion (see LaneSums)
+template <typename V, int K>
+__device__ __forceinline__ void trace_products(const V (&e)[6], V (&acc)[28]) {
+  if constexpr (K < 21) {
+    constexpr int r = MomentSet<true>::tri_row(K), c = MomentSet<true>::tri_col(K);
+    acc[7 + K] = vfma(e[r], e[c], acc[7 + K]);
+    trace_products<V, K + 1>(e, acc);
+  }
+}
+// This wave's sums at one point: into cell (lane >> 1) of the point's slab row.
+template <typename R>
+__device__ __forceinline__ void trace_deposit(R (&v)[kTraceSlab], int lane, bool first, double* __restrict__ row) {
+  const R total = trace_wave_sums<R>(v, lane);
+  if ((lane & 1) == 0) {
+    double* cell = row + (lane >> 1);
+    const double before = first ? 0.0 : *cell;
+    *cell = before + (double)total;
+  }
+}
+
+// float32: two particles per lane as packed pairs (apply_step_pair: the same operations in the same order per
+// component as apply_step<float>), the sums of a pair in packed registers as well -- v_pk_fma_f32 / v_pk_add_f32 for
+// the map AND the 27 accumulations; the two halves are added when the lane's values go into the butterfly.
+template <int U, bool MASKED>
+__device__ __forceinline__ void trace_point(const lynx_f32x2 (&zp)[U / 2][7], const float* __restrict__ ref,
+                                            const bool (&live)[U], int lane, bool first, double* __restrict__ row) {
+  lynx_f32x2 acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = lynx_f32x2{0.f, 0.f};
+  float c[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c[k] = uniform_value(ref[k]);
+#pragma unroll
+  for (int h = 0; h < U / 2; ++h) {
+    lynx_f32x2 e[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      e[k] = zp[h][k] - lynx_f32x2{c[k], c[k]};
+      if (MASKED) {
+        e[k].x = live[2 * h] ? e[k].x : 0.f;
+        e[k].y = live[2 * h + 1] ? e[k].y : 0.f;
+      }
+      acc[k] += e[k];
+    }
+    lynx_f32x2 one = zp[h][6];
+    if (MASKED) {
+      one.x = live[2 * h] ? one.x : 0.f;
+      one.y = live[2 * h + 1] ? one.y : 0.f;
+    }
+    acc[6] += one;
+    trace_products<lynx_f32x2, 0>(e, acc);
+  }
+  float v[kTraceSlab];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) v[k] = acc[k].x + acc[k].y;
+#pragma unroll
+  for (int k = 28; k < kTraceSlab; ++k) v[k] = 0.f;
+  trace_deposit<float>(v, lane, first, row);
+}
+
+// float64: one particle at a time, everything in float64
+template <int U, bool MASKED>
+__device__ __forceinline__ void trace_point(const double (&z)[U][7], const double* __restrict__ ref,
+                                            const bool (&live)[U], int lane, bool first, double* __restrict__ row) {
+  double acc[28];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) acc[k] = 0.0;
+  double c[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) c[k] = ref[k];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    double e[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+      e[k] = z[u][k] - c[k];
+      if (MASKED) e[k] = live[u] ? e[k] : 0.0;
+      acc[k] += e[k];
+    }
+    acc[6] += (MASKED && !live[u]) ? 0.0 : z[u][6];
+    trace_products<double, 0>(e, acc);
+  }
+  double v[kTraceSlab];
+#pragma unroll
+  for (int k = 0; k < 28; ++k) v[k] = acc[k];
+#pragma unroll
+  for (int k = 28; k < kTraceSlab; ++k) v[k] = 0.0;
+  trace_deposit<double>(v, lane, first, row);
+}
+
+// one tile of a wave through the whole lattice
+template <typename T, int U, bool MASKED>
+__device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* __restrict__ steps /* of this sample */,
+                                           const T* __restrict__ ref /* of this sample */, const T* __restrict__ src,
+                                           T* __restrict__ dst, int64_t base, int lane, bool first,
+                                           double* __restrict__ slab /* of this wave */) {
+  bool live[U];
+  T z[U][7];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t i = base + lane + 64 * u;
+    live[u] = !MASKED || i < a.n_particles;
+    // (a lane beyond the end of the sample carries the sample's last particle: finite work, no part in any sum)
+    load_particle(src + (live[u] ? i : a.n_particles - 1) * 7, z[u]);
+  }
+  if constexpr (sizeof(T) == 4) {
+    lynx_f32x2 zp[U / 2][7];
+#pragma unroll
+    for (int u = 0; u < U; u += 2)
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        zp[u / 2][c].x = z[u][c];
+        zp[u / 2][c].y = z[u + 1][c];
+      }
+    for (int s = 0; s <= S; ++s) {
+      trace_point<U, MASKED>(zp, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
+      if (s == S) break;
+      const T* tab = steps + s * LYNX_STEP_STRIDE;  // global, wave-uniform: scalar loads
+      const int desc = (int)uniform_value(tab[LYNX_FLAGS_OFFSET]);
+      const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
+      T m[LYNX_STEP_SCALARS];
+#pragma unroll
+      for (int q = 0; q < LYNX_STEP_SCALARS; ++q) m[q] = uniform_value(tab[q]);
+      // apply_step_pair's operations, with the 7x7 of EVERY pair in front of the kicks: the 49 map entries are dead
+      // by the time the cosine is called (as one call per pair they were parked in VGPR lanes around each of them)
+      lynx_f32x2 o[U / 2][7];
+#pragma unroll
+      for (int h = 0; h < U / 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+          lynx_f32x2 acc = zp[h][0] * m[i * 7 + 0];
+#pragma unroll
+          for (int j = 1; j < 7; ++j) acc = pk_fma(zp[h][j], m[i * 7 + j], acc);
+          o[h][i] = acc;
+        }
+      if (skind == LYNX_STEP_CAVITY && (sflags & LYNX_FLAG_CAV_GAIN)) {  // uniform
+        const float* coef = m + LYNX_COEF_OFFSET;
+#pragma unroll
+        for (int h = 0; h < U / 2; ++h) {
+          const lynx_f32x2 dcos = cos_difference(-1.0f * zp[h][4] * coef[LYNX_C_BK], coef[LYNX_C_PHI],
+                                                 coef[LYNX_SINPHI_OFFSET - LYNX_COEF_OFFSET], coef[LYNX_C_COSPHI]);
+          kick_outputs<lynx_f32x2>(coef, zp[h][4], zp[h][5], dcos, o[h][4], o[h][5]);
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < U / 2; ++h)
+#pragma unroll
+        for (int i = 0; i < 7; ++i) zp[h][i] = o[h][i];
+    }
+#pragma unroll
+    for (int u = 0; u < U; u += 2)
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        z[u][c] = zp[u / 2][c].x;
+        z[u + 1][c] = zp[u / 2][c].y;
+      }
+  } else {
+    for (int s = 0; s <= S; ++s) {
+      trace_point<U, MASKED>(z, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
+      if (s == S) break;
+      const T* tab = steps + s * LYNX_STEP_STRIDE;
+      const int desc = (int)tab[LYNX_FLAGS_OFFSET];
+      const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
+#pragma unroll
+      for (int u = 0; u < U; ++u) apply_step<T>(tab, skind, sflags, z[u]);
+    }
+  }
+  if (a.store) {
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (live[u]) store_particle(dst + (base + lane + 64 * u) * 7, z[u]);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_particles: grid.x = B * waves / 4, 256 threads; wave w of a sample owns the particles
+// [w * tiles_per_wave * 64 U, (w + 1) * tiles_per_wave * 64 U).  No LDS, no barrier.  A wave whose range lies
+// beyond the end of the sample writes a slab of zeros (the finalizer adds every wave's slab).
+// ---------------------------------------------------------------------------------------
+template <typename T, int U>
+__global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, const T* __restrict__ steps,
+                                                         const T* __restrict__ ref, const T* __restrict__ p_in,
+                                                         T* __restrict__ p_out, double* __restrict__ slabs) {
+  const int wgs = a.waves / 4;
+  const int64_t b = blockIdx.x / wgs;
+  const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int P = S + 1;
+  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const T* sample_ref = ref + b * (int64_t)P * kTraceRef;
+  const T* src = p_in + b * a.in_stride;
+  T* dst = p_out + b * a.n_particles * 7;
+  double* slab = slabs + (b * a.waves + w) * (int64_t)P * kTraceSlab;
+  constexpr int64_t kTile = 64 * U;
+  const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
+  if (begin >= a.n_particles) {
+    for (int64_t i = lane; i < (int64_t)P * kTraceSlab; i += 64) slab[i] = 0.0;
+    return;
+  }
+  for (int t = 0; t < a.tiles_per_wave; ++t) {
+    const int64_t base = begin + t * kTile;
+    if (base >= a.n_particles) break;
+    if (base + kTile <= a.n_particles)
+      trace_tile<T, U, false>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab);
+    else
+      trace_tile<T, U, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_finalize: grid.x = B * P, THREADS = 32 G threads.  The slabs of the sample's waves at this point: group g
+// adds the g-th of G contiguous ranges of waves in wave order (one thread per cell), the G sums are added in group
+// order -- a fixed association for a given launch plan -- and the record is written as write_moment_record writes
+// it: every slab was taken about the same reference point, so there is nothing to move.
+// (One group alone: 2608 dependent additions per cell for one sample of 10^6 particles, 577 us -- more than the
+// streaming kernel's 122.)
+// ---------------------------------------------------------------------------------------
+template <typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __restrict__ slabs, const T* __restrict__ ref,
+                                                            int waves, int P, int64_t n_particles,
+                                                            double* __restrict__ out) {
+  constexpr int G = THREADS / kTraceSlab;
+  __shared__ double s_part[G][kTraceSlab];
+  __shared__ double s[kPartialStride];
+  const int tid = threadIdx.x, cellid = tid & (kTraceSlab - 1), g = tid / kTraceSlab;
+  const int64_t b = blockIdx.x / P;
+  const int k = (int)(blockIdx.x - b * P);
+  {
+    const int per = (waves + G - 1) / G;
+    const int w0 = g * per, w1 = min(waves, w0 + per);
+    const double* cell = slabs + ((b * waves) * (int64_t)P + k) * kTraceSlab + cellid;
+    double v = 0.0;
+#pragma unroll 8
+    for (int w = w0; w < w1; ++w) v += cell[(int64_t)w * P * kTraceSlab];
+    s_part[g][cellid] = v;
+  }
+  __syncthreads();
+  if (tid < kPartialStride) {
+    double v = 0.0;
+    if (tid < 28) {
+#pragma unroll
+      for (int q = 0; q < G; ++q) v += s_part[q][tid];
+    } else if (tid < 34) {
+      v = (double)ref[(b * P + k) * kTraceRef + (tid - 28)];
+    } else if (tid == 34) {
+      v = 1.0;
+    } else {
+      v = (double)n_particles;
+    }
+    s[tid] = v;
+  }
+  __syncthreads();
+  if (tid < kPartialStride) write_moment_record(s, out + (b * P + k) * kPartialStride, tid);
+}
+
+// ---------------------------------------------------------------------------------------
+// ParameterBeam: mu_k = M_k mu_{k-1}, cov_k = M_k cov_{k-1} M_k^T (element.py:71-82), the cavity branch of
+// cavity.py:134-140, 202-218 -- the operations of k_track_moments / k_apply_moments_lanes in the same order, every
+// intermediate written: mu [B][P][7], cov [B][P][7][7].  (The energies come from k_trace_reference.)
+//
+// k_trace_moments: one wave per sample, 49 lanes busy; the table is read from memory.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_moments(LatticeDev lat, const T* __restrict__ steps,
+                                                      const T* __restrict__ mu_in, const T* __restrict__ cov_in,
+                                                      T* __restrict__ mu_trace, T* __restrict__ cov_trace) {
+  __shared__ T s_mu[8], s_cov[49], s_x[49], s_in[10];
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x, S = lat.n_steps, P = S + 1;
+  if (lane < 7) s_mu[lane] = mu_in[b * 7 + lane];
+  if (lane < 49) s_cov[lane] = cov_in[b * 49 + lane];
+  __syncthreads();
+  const int cl = lane < 49 ? lane : 48;
+  const int i = cl / 7, j = cl % 7;
+  for (int s = 0; s <= S; ++s) {
+    if (lane < 7) mu_trace[(b * P + s) * 7 + lane] = s_mu[lane];
+    if (lane < 49) cov_trace[(b * P + s) * 49 + lane] = s_cov[lane];
+    if (s == S) break;
+    const T* M = steps + (b * S + s) * LYNX_STEP_STRIDE;
+    const int desc = (int)M[LYNX_FLAGS_OFFSET];
+    const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
+    if (lane < 7) s_in[lane] = s_mu[lane];
+    if (lane == 7) s_in[7] = s_cov[4 * 7 + 4];
+    if (lane == 8) s_in[8] = s_cov[4 * 7 + 5];
+    if (lane == 9) s_in[9] = s_cov[5 * 7 + 5];
+    T mu_new = T(0);
+    if (lane < 7) {
+      mu_new = M[lane * 7 + 0] * s_mu[0];
+#pragma unroll
+      for (int k = 1; k < 7; ++k) mu_new = t_fma(M[lane * 7 + k], s_mu[k], mu_new);
+    }
+    T x = s_cov[i * 7 + 0] * M[j * 7 + 0];  // X = cov . T^T
+#pragma unroll
+    for (int k = 1; k < 7; ++k) x = t_fma(s_cov[i * 7 + k], M[j * 7 + k], x);
+    __syncthreads();
+    if (lane < 49) s_x[lane] = x;
+    if (lane < 7) s_mu[lane] = mu_new;
+    __syncthreads();
+    T c = M[i * 7 + 0] * s_x[0 * 7 + j];  // cov' = T . X
+#pragma unroll
+    for (int k = 1; k < 7; ++k) c = t_fma(M[i * 7 + k], s_x[k * 7 + j], c);
+    __syncthreads();
+    if (lane < 49) s_cov[lane] = c;
+    __syncthreads();
+    if (kick && lane == 0) {
+      const T* coef = M + LYNX_COEF_OFFSET;
+      T s_o = s_mu[4], d_o;
+      device_cavity_kick<T>(coef, s_in[4], s_in[5], s_o, d_o);  // cavity.py:134-140, 202-206
+      s_mu[4] = s_o;
+      s_mu[5] = d_o;
+      const T c44 = s_in[7], c45 = s_in[8], c55 = s_in[9];
+      s_cov[5 * 7 + 5] = c55;  // cavity.py:140
+      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
+      s_cov[4 * 7 + 4] = v;
+      s_cov[4 * 7 + 5] = v;
+      s_cov[5 * 7 + 4] = v;
+    }
+    __syncthreads();
+  }
+}
+
+// k_trace_moments_lanes: large float32 batches, lanes = samples (the form of k_apply_moments_lanes: a wave stages the
+// 64 table rows of a step in LDS with coalesced loads, every lane propagates its own sample's moments in registers).
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_moments_lanes(LatticeDev lat, const T* __restrict__ steps,
+                                                            const T* __restrict__ mu_in, const T* __restrict__ cov_in,
+                                                            T* __restrict__ mu_trace, T* __restrict__ cov_trace) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  using V = typename VecOf<T, true>::type;
+  constexpr int W = VecOf<T, true>::width, kVecPerRow = LYNX_STEP_STRIDE / W;
+  T* rows = reinterpret_cast<T*>(smem_raw);
+  const int lane = threadIdx.x, S = lat.n_steps, P = S + 1;
+  const int64_t b0 = (int64_t)blockIdx.x * 64, B = lat.batch;
+  const bool alive = b0 + lane < B;
+  const int64_t b = alive ? b0 + lane : B - 1;
+  T mu[7], C[49];
+#pragma unroll
+  for (int q = 0; q < 7; ++q) mu[q] = mu_in[b * 7 + q];
+#pragma unroll
+  for (int q = 0; q < 49; ++q) C[q] = cov_in[b * 49 + q];
+  for (int s = 0; s <= S; ++s) {
+    if (alive) {
+#pragma unroll
+      for (int q = 0; q < 7; ++q) mu_trace[(b * P + s) * 7 + q] = mu[q];
+#pragma unroll
+      for (int q = 0; q < 49; ++q) cov_trace[(b * P + s) * 49 + q] = C[q];
+    }
+    if (s == S) break;
+    wave_fence();
+#pragma unroll 4
+    for (int v = lane; v < 64 * kVecPerRow; v += 64) {
+      const int r = v / kVecPerRow, piece = v - r * kVecPerRow;
+      const int64_t br = (b0 + r < B) ? b0 + r : B - 1;
+      const V x = *reinterpret_cast<const V*>(steps + (br * S + s) * LYNX_STEP_STRIDE + piece * W);
+      *reinterpret_cast<V*>(rows + r * 68 + piece * W) = x;
+    }
+    wave_fence();
+    const T* M = rows + lane * 68;
+    const int desc = (int)M[LYNX_FLAGS_OFFSET];
+    const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
+    const T s_in = mu[4], d_in = mu[5], c44 = C[4 * 7 + 4], c45 = C[4 * 7 + 5], c55 = C[5 * 7 + 5];
+    {
+      T out[7];
+#pragma unroll
+      for (int i = 0; i < 7; ++i) {
+        T acc = M[i * 7] * mu[0];
+#pragma unroll
+        for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], mu[k], acc);
+        out[i] = acc;
+      }
+#pragma unroll
+      for (int i = 0; i < 7; ++i) mu[i] = out[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {  // X = cov . T^T, row i of X from row i of cov
+      T out[7];
+#pragma unroll
+      for (int j = 0; j < 7; ++j) {
+        T acc = C[i * 7] * M[j * 7];
+#pragma unroll
+        for (int k = 1; k < 7; ++k) acc = t_fma(C[i * 7 + k], M[j * 7 + k], acc);
+        out[j] = acc;
+      }
+#pragma unroll
+      for (int j = 0; j < 7; ++j) C[i * 7 + j] = out[j];
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {  // cov' = T . X, column j of cov' from column j of X
+      T out[7];
+#pragma unroll
+      for (int i = 0; i < 7; ++i) {
+        T acc = M[i * 7] * C[j];
+#pragma unroll
+        for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], C[k * 7 + j], acc);
+        out[i] = acc;
+      }
+#pragma unroll
+      for (int i = 0; i < 7; ++i) C[i * 7 + j] = out[i];
+    }
+    if (kick) {
+      const T* coef = M + LYNX_COEF_OFFSET;
+      T s_o = mu[4], d_o;
+      device_cavity_kick<T>(coef, s_in, d_in, s_o, d_o);  // cavity.py:134-140, 202-206
+      mu[4] = s_o;
+      mu[5] = d_o;
+      C[5 * 7 + 5] = c55;  // cavity.py:140
+      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
+      C[4 * 7 + 4] = v;
+      C[4 * 7 + 5] = v;
+      C[5 * 7 + 4] = v;
+    }
+  }
+}
+
+}  // namespace lynx

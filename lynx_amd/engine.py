@@ -470,6 +470,110 @@ def track(owner, elements, incoming, raw: bool = False):
     return beam
 
 
+# -------------------------------------------------------------------------------------------
+# the beam along the lattice (Segment.track_along)
+# -------------------------------------------------------------------------------------------
+
+
+def trace_program(leaves) -> Program:
+    """
+    The lattice with every leaf element a step of its own, as the loop of the reference's `plot_twiss` tracks it
+    (`element.track(beam)`: the element's OWN map, taken as it is -- LYNX_STEP_FLAG_RAW; an active cavity by
+    `Cavity._track_beam`).  An active BPM is an identity element whose reading comes from the trace, so the observer
+    limit of `Segment.track` does not apply; an active Screen or Aperture has no place inside one streaming pass.
+    """
+    program = Program(raw=True)
+    for el in leaves:
+        if el.is_skippable or getattr(el, "_fusable_observer", False):
+            program.add_run_element(el, True)
+        elif el._kind == _ffi.KIND_CAVITY:
+            program.add_cavity(el)
+        else:
+            raise NotImplementedError(
+                f"track_along: active {type(el).__name__} {el.name!r} -- a lattice with an active Screen or Aperture is "
+                "not traced in one pass; trace the stretches on either side of it")
+    return program
+
+
+def _trace_plan(owner, leaves) -> Program:
+    """`trace_program` remembered on `owner` like `plan` remembers the partition of `track`."""
+    token = (_late().STRUCTURE[0], tuple(map(id, leaves)))
+    remembered = owner.__dict__.get("_trace_plan")
+    if remembered is not None and remembered[0] == token:
+        return remembered[1]
+    program = trace_program(leaves)
+    owner.__dict__["_trace_plan"] = (token, program)
+    return program
+
+
+def track_along(owner, leaves, incoming, keep_outgoing: bool = True):
+    """
+    `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
+    `lynx_track_moments_along`).  The packed "every element its own step" lattice is cached on `owner` (its own
+    LatticeCache: a parameter write between two calls rewrites that element's block only).
+    """
+    from .trace import BeamTrace
+
+    late = _late()
+    ParameterBeam, ParticleBeam = late.ParameterBeam, late.ParticleBeam
+    leaves = list(leaves)
+    program = _trace_plan(owner, leaves)  # (raises for an active Screen or Aperture before anything touches the GPU)
+    if not isinstance(incoming, (ParameterBeam, ParticleBeam)):
+        raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
+    rt = get_runtime()
+    cache = owner.__dict__.setdefault("_trace_cache", LatticeCache())
+    dtype, batch_shape = incoming.dtype, incoming.batch_shape
+    lat = _ready(cache, program, batch_shape, dtype, incoming._energy._host)
+    P = lat.S + 1
+    e_in = incoming._energy.broadcast_device(rt, batch_shape)
+    e_trace = rt.empty_result((lat.B, P), dtype)
+    lengths = [getattr(el, "length", None) for el in leaves]
+    names = [el.name for el in leaves]
+    if isinstance(incoming, ParticleBeam):
+        n = incoming.num_particles
+        p_in = incoming._particles.device(rt)
+        p_out = rt.empty((*batch_shape, n, 7), dtype) if keep_outgoing else None
+        records = rt.empty_result((lat.B, P, _ffi.MOMENT_STRIDE), _F64)
+        rt.check(rt.lib.lynx_track_particles_along(
+            rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records),
+            _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0))
+        rec = records.numpy().reshape(*batch_shape, P, _ffi.MOMENT_STRIDE)
+        energy = e_trace.numpy().reshape(*batch_shape, P)
+        trace = BeamTrace.from_records(rec, energy, lengths, names, dtype)
+        trace.num_particles = n
+        centre = rec[..., :, (0, 2)].astype(dtype)  # mean x, y at every point
+        if keep_outgoing:
+            out = ParticleBeam.__new__(ParticleBeam)
+            charges = incoming._charges
+            if charges is not None and incoming.is_shared:
+                charges = np.ascontiguousarray(incoming.particle_charges)
+            out._init_raw(Dual(dev=p_out), Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
+                          charges, dtype, moments=Dual(np.ascontiguousarray(rec[..., -1, :])))
+            trace.outgoing = out
+    else:
+        mu_t = rt.empty((lat.B, P, 7), dtype)
+        cov_t = rt.empty((lat.B, P, 7, 7), dtype)
+        rt.check(rt.lib.lynx_track_moments_along(
+            rt.ctx, lat.handle, _ptr(e_in), _ptr(incoming._mu_d.device(rt)), _ptr(incoming._cov_d.device(rt)),
+            _ptr(mu_t), _ptr(cov_t), _ptr(e_trace)))
+        mu = mu_t.numpy().reshape(*batch_shape, P, 7)
+        cov = cov_t.numpy().reshape(*batch_shape, P, 7, 7)
+        energy = e_trace.numpy().reshape(*batch_shape, P)
+        trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype)
+        centre = mu[..., :, (0, 2)]
+        if keep_outgoing:
+            out = ParameterBeam.__new__(ParameterBeam)
+            out._init_raw(Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
+                          Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
+                          incoming.total_charge, dtype)
+            trace.outgoing = out
+    trace.total_charge = incoming.total_charge
+    for k, el in enumerate(leaves):  # an active BPM reads the beam that ENTERS it: point k (bpm.py:48-54)
+        if getattr(el, "_fusable_observer", False):
+            el.reading = np.stack([centre[..., k, 0], centre[..., k, 1]]).astype(dtype)
+    return trace
+
+
 def transfer_map(owner, elements, energy, dtype, raw: bool = False) -> np.ndarray:
     """`transfer_map(energy)` of a skippable element list -> host array (*batch, 7, 7)."""
     rt = get_runtime()

@@ -1,0 +1,168 @@
+"""
+`BeamTrace`: the beam ALONG a lattice -- its moments and energy at the entrance (point 0) and behind every leaf element
+(point k), for every batch sample; what `Segment.track_along` returns.
+
+The reference holds this data in the loop of `Segment.plot_twiss` / `plot_twiss_over_lattice` (lynx/accelerator/
+segment.py: `element.track(beam)` element by element, `beta_x`, `beta_y` of every intermediate beam) and in
+`plot_reference_particle_traces`; the plots themselves are out of scope.  One deliberate departure: `plot_twiss` skips
+elements of zero length altogether (it does not track through them); here every element is tracked and has a point,
+and `where_length_changes()` gives the reference's subset.
+
+Every moment property a beam has is here too, shaped (*batch, P): the formulas are the beam classes' own
+(`ParticleBeam._std` with `LYNX_STD_DDOF`, `ParameterBeam._sigma`, the Twiss properties of `particles/beam.py`), applied
+to all points at once.
+"""
+
+from __future__ import annotations
+
+import numpy as np
+
+from .particles.beam import Beam
+from .particles.parameter_beam import ParameterBeam
+from .particles.particle_beam import ParticleBeam, _tri
+
+_MOMENTS = ("mu_x", "mu_xp", "mu_y", "mu_yp", "mu_s", "mu_p", "sigma_x", "sigma_xp", "sigma_y", "sigma_yp", "sigma_s",
+            "sigma_p", "sigma_xxp", "sigma_yyp")
+_DERIVED = ("emittance_x", "emittance_y", "normalized_emittance_x", "normalized_emittance_y", "beta_x", "beta_y",
+            "alpha_x", "alpha_y")
+
+
+def _cumulative_s(lengths, batch_shape, dtype) -> np.ndarray:
+    """(P, *batch): 0, then the running sum of the elements' lengths (each broadcast over the batch)."""
+    s = np.zeros((len(lengths) + 1, *batch_shape), dtype=dtype)
+    for k, length in enumerate(lengths):
+        length = np.asarray(0.0 if length is None else length, dtype=dtype)
+        if length.size == 1:  # (an element without a length of its own carries [0.] whatever the batch)
+            length = length.reshape(())
+        s[k + 1] = s[k] + np.broadcast_to(length, batch_shape)
+    return s
+
+
+class BeamTrace(Beam):
+    """
+    :ivar s: position of every point, (P, *batch) -- cumulative `length`, per sample because lengths are batched; a
+        zero-length element's point has the `s` of the one before it.
+    :ivar names: the P - 1 element names; point k lies behind `names[k - 1]`.
+    :ivar mu: (*batch, P, 6), :ivar cov: (*batch, P, 6, 6), :ivar energy: (*batch, P).
+    :ivar outgoing: the tracked beam (None if it was not kept); its moments are the last point's.
+    """
+
+    outgoing = None
+    num_particles = None
+    total_charge = None
+
+    def _set_common(self, energy, lengths, names, dtype, batch_shape):
+        self.dtype = np.dtype(dtype)
+        self.batch_shape = tuple(batch_shape)
+        self._energy_trace = np.asarray(energy, dtype=self.dtype)
+        self.names = list(names)
+        self._lengths = [np.asarray(0.0 if length is None else length, dtype=self.dtype) for length in lengths]
+        self.s = _cumulative_s(self._lengths, self.batch_shape, self.dtype)
+        assert len(self.names) == len(self._lengths) == self.num_points - 1
+
+    @staticmethod
+    def from_records(records, energy, lengths, names, dtype=np.float32) -> "BeamTrace":
+        """
+        A particle trace from host arrays: `records` (*batch, P, 36) float64 moment records (layout of
+        LYNX_MOMENT_STRIDE, include/lynx_hip.h; whole covariance triangle), `energy` (*batch, P), `lengths` the P - 1
+        element lengths (each broadcastable to the batch), `names` the P - 1 element names.
+        """
+        trace = ParticleBeamTrace.__new__(ParticleBeamTrace)
+        trace.records = np.asarray(records, dtype=np.float64)
+        assert trace.records.ndim >= 2 and trace.records.shape[-1] == 36, trace.records.shape
+        trace._set_common(energy, lengths, names, dtype, trace.records.shape[:-2])
+        n = trace.records[..., 35]
+        trace.num_particles = int(n.flat[0]) if n.size else 0
+        return trace
+
+    @staticmethod
+    def from_moments(mu, cov, energy, lengths, names, dtype=np.float32) -> "BeamTrace":
+        """A ParameterBeam trace: `mu` (*batch, P, 7), `cov` (*batch, P, 7, 7), the rest as for `from_records`."""
+        trace = ParameterBeamTrace.__new__(ParameterBeamTrace)
+        trace._mu = np.asarray(mu, dtype=dtype)
+        trace._cov = np.asarray(cov, dtype=dtype)
+        trace._set_common(energy, lengths, names, dtype, trace._mu.shape[:-2])
+        return trace
+
+    @property
+    def energy(self) -> np.ndarray:
+        return self._energy_trace
+
+    @property
+    def num_points(self) -> int:
+        return int(self._energy_trace.shape[-1])
+
+    def __len__(self) -> int:
+        return self.num_points
+
+    def where_length_changes(self) -> np.ndarray:
+        """
+        (P,) bool: point 0 and the points behind elements whose length is not zero -- the points the reference's
+        `plot_twiss` has (it passes over `length == 0` elements without tracking through them).
+        """
+        return np.array([True] + [bool(np.any(length != 0)) for length in self._lengths])
+
+    def index_of(self, name_or_index) -> int:
+        """Point index: an int as it is (negative from the end); a name -> the point behind the first element so named."""
+        if isinstance(name_or_index, str):
+            if name_or_index not in self.names:
+                raise KeyError(f"no element named {name_or_index!r} in this trace")
+            return self.names.index(name_or_index) + 1
+        k = int(name_or_index)
+        if not -self.num_points <= k < self.num_points:
+            raise IndexError(f"point {k} of a trace of {self.num_points}")
+        return k % self.num_points
+
+    def at(self, name_or_index) -> dict:
+        """Everything known about one point: `s`, `name` (None for point 0), `energy`, `mu`, `cov` and every moment."""
+        k = self.index_of(name_or_index)
+        out = {"index": k, "name": self.names[k - 1] if k else None, "s": self.s[k], "energy": self.energy[..., k],
+               "mu": self.mu[..., k, :], "cov": self.cov[..., k, :, :]}
+        for key in _MOMENTS + _DERIVED:
+            out[key] = getattr(self, key)[..., k]
+        return out
+
+    def __repr__(self) -> str:
+        return f"{type(self).__name__}(points={self.num_points}, batch={self.batch_shape}, dtype={self.dtype.name})"
+
+
+class ParticleBeamTrace(BeamTrace):
+    """Trace of a `ParticleBeam`: one float64 moment record per sample and point (`records`, (*batch, P, 36))."""
+
+    def moment_record(self, covariance: bool = False) -> np.ndarray:
+        return self.records
+
+    # the ParticleBeam's own read-out of a record (LYNX_STD_DDOF and all), on (*batch, P) records
+    _mean, _std, _cov = ParticleBeam._mean, ParticleBeam._std, ParticleBeam._cov
+
+    @property
+    def mu(self) -> np.ndarray:
+        return self.records[..., :6].astype(self.dtype)
+
+    @property
+    def cov(self) -> np.ndarray:
+        """Biased 6 x 6 covariance of the particles at every point, (*batch, P, 6, 6)."""
+        out = np.empty((*self.records.shape[:-1], 6, 6), dtype=self.dtype)
+        for i in range(6):
+            for j in range(i, 6):
+                out[..., i, j] = out[..., j, i] = self.records[..., _tri(i, j)]
+        return out
+
+
+class ParameterBeamTrace(BeamTrace):
+    """Trace of a `ParameterBeam`: `mu` and `cov` as the kernels wrote them."""
+
+    _sigma = ParameterBeam._sigma
+
+    @property
+    def mu(self) -> np.ndarray:
+        return self._mu[..., :6]
+
+    @property
+    def cov(self) -> np.ndarray:
+        return self._cov[..., :6, :6]
+
+
+for _key in _MOMENTS:
+    setattr(ParticleBeamTrace, _key, getattr(ParticleBeam, _key))
+    setattr(ParameterBeamTrace, _key, getattr(ParameterBeam, _key))
