@@ -248,6 +248,38 @@ int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_parti
 int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                              const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace);
 
+/* Reverse pass of lynx_track_moments_along: gradient of a scalar function of the moments and the energy at EVERY point
+ * of the lattice (the losses written along a beamline: Twiss values at markers, beam sizes below an aperture, the
+ * centroid at every BPM) with respect to every element parameter, the incoming energy and the incoming mu and cov.
+ * One reverse sweep of the moment recursion with a cotangent injected at every point; the states come from the forward
+ * trace, nothing is tracked again.  The program is the one the trace was made with (every element a step of its own,
+ * LYNX_STEP_FLAG_RAW), at most 256 elements (LYNX_ERR_INVALID beyond); P = n_steps + 1.
+ *   d_mu_trace [B][P][7], d_cov_trace [B][P][7][7]   what lynx_track_moments_along wrote
+ *   d_mu_bar [B][P][7], d_cov_bar [B][P][7][7]       dL/d(mu), dL/d(cov) at every point, entry by entry
+ *   d_energy_bar [B][P] or NULL                      dL/d(beam energy at every point)
+ *   d_grad_params [B][E][8], d_grad_energy_in [B]    as for lynx_track_particles_backward
+ *   d_grad_mu_in [B][7], d_grad_cov_in [B][7][7]     dL/d(incoming mu), dL/d(incoming cov)
+ * All in the lattice's dtype.  Sums in a fixed order, no atomics: the same call returns the same bits.               */
+int lynx_track_moments_along_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                                      const void* d_cov_trace, const void* d_mu_bar, const void* d_cov_bar,
+                                      const void* d_energy_bar, void* d_grad_params, void* d_grad_energy_in,
+                                      void* d_grad_mu_in, void* d_grad_cov_in);
+
+/* ... of lynx_track_particles_along.  Without a kicking cavity every element is an affine map, so the particles' mean
+ * and biased covariance obey the ParameterBeam's recursion exactly and the gradient needs no pass over the particles:
+ * the records and their cotangents become the states and cotangents of the sweep above, on the device.
+ *   d_trace_fwd  [B][P][36] float64   what lynx_track_particles_along wrote
+ *   d_grad_trace [B][P][36] float64   [0..6] d/dmean, [7..27] d/dcov upper triangle, an off-diagonal entry counted once
+ *                                     (the convention of lynx_track_particles_backward)
+ *   d_energy_bar [B][P] or NULL, d_grad_params, d_grad_energy_in: as above (lattice dtype)
+ *   d_grad_mean_in [B][7], d_grad_cov_in [B][7][7]   dL/d(mean), dL/d(biased covariance) of the incoming particles
+ * LYNX_ERR_INVALID if the program has a cavity step (the moments are not closed under its kick) or more than 256
+ * elements.                                                                                                         */
+int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                        const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
+                                        void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
+                                        void* d_grad_cov_in);
+
 /* Reverse pass of lynx_track_particles: gradient of a scalar function L of the outgoing
  * beam's moment record with respect to every element parameter and the incoming energy
  * (the reference only claims differentiability, setup.py:14-17,

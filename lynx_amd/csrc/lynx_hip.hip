@@ -22,6 +22,7 @@
 #include "lynx_units.hpp"
 #include "lynx_grad_units.hpp"
 #include "lynx_trace.hpp"
+#include "lynx_trace_grad.hpp"
 
 using namespace lynx;
 
@@ -2528,6 +2529,143 @@ int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ene
   return lat->dtype == LYNX_F64
              ? track_moments_along_t<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace)
              : track_moments_along_t<float>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace);
+}
+
+// ---- reverse pass of the beam trace: gradients of the moments at every point -----------------
+
+constexpr int32_t kTraceBwdMaxSteps = 256;  // k_build_bwd deals the steps of a program to its 256 threads (`if (tid < S)`)
+
+// What both entry points share: the trace table, the reverse sweep of the moment recursion with a cotangent at every
+// point (k_trace_moments_bwd), k_build_bwd on the "every element a step of its own" program, the energy cotangents.
+template <typename T, typename ST = T>
+static int trace_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                            const void* d_cov_trace, const void* d_mu_bar, const void* d_cov_bar, const void* d_energy_bar,
+                            void* d_grad_params, void* d_grad_energy_in, void* d_grad_mu_in, void* d_grad_cov_in) {
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps, E = lat->n_elems;
+  int rc;
+  if ((rc = sync_pool(ctx, lat))) return rc;  // (k_build_bwd and k_trace_energy_bwd read the parameters from memory)
+  if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
+  ctx->main_dirty = true;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], (size_t)B * S * kGradStride * sizeof(T))))
+    return rc;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2],
+                           (size_t)B * (2 * E + S + 1) * 49 * sizeof(T))))
+    return rc;
+  const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
+  LatticeDev lv = dev_view(lat);
+  hipLaunchKernelGGL((k_trace_moments_bwd<T, ST>), dim3((unsigned)B), dim3(64), 0, ctx->stream, (int)S, table,
+                     (const ST*)d_mu_trace, (const ST*)d_cov_trace, (const ST*)d_mu_bar, (const ST*)d_cov_bar,
+                     (T*)ctx->scratch_grad[1], (T*)d_grad_mu_in, (T*)d_grad_cov_in);
+  HIP_TRY(ctx, hipGetLastError());
+  size_t lds2 = build_bwd_lds_fixed<T>(S, E);
+  const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
+  if ((rc = ensure_bwd_tasks(ctx, lat))) return rc;
+  const int maps_in_lds = lds2 + maps_bytes <= kBwdMapsLdsBytes;
+  if (maps_in_lds) lds2 += maps_bytes;
+  if ((rc = allow_lds(ctx, k_build_bwd<T>, lds2))) return rc;
+  HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
+  hipLaunchKernelGGL(k_build_bwd<T>, dim3((unsigned)B), dim3(256), lds2, ctx->stream, lv, (const T*)d_energy_in,
+                     (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, 0,
+                     maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
+  HIP_TRY(ctx, hipGetLastError());
+  if (d_energy_bar) {
+    hipLaunchKernelGGL(k_trace_energy_bwd<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, lv, table,
+                       (const T*)d_energy_bar, (T*)d_grad_params, (T*)d_grad_energy_in);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  return LYNX_OK;
+}
+
+static int trace_backward_check(lynx_ctx* ctx, lynx_lattice* lat) {
+  if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program");
+  if (lat->n_steps > kTraceBwdMaxSteps || lat->n_elems > kTraceBwdMaxSteps)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients: more than 256 elements");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
+  if ((int64_t)lat->batch * (lat->n_steps + 1) > 0x7fffffffLL)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace: batch x points too large for one launch");
+  return LYNX_OK;
+}
+
+static void trace_backward_wrote(lynx_ctx* ctx, lynx_lattice* lat, void* d_grad_params, void* d_grad_energy_in,
+                                 void* d_grad_mu_in, void* d_grad_cov_in) {
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
+  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+  ctx->wrote(d_grad_mu_in, (size_t)lat->batch * 7 * es);
+  ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
+}
+
+int lynx_track_moments_along_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                                      const void* d_cov_trace, const void* d_mu_bar, const void* d_cov_bar,
+                                      const void* d_energy_bar, void* d_grad_params, void* d_grad_energy_in,
+                                      void* d_grad_mu_in, void* d_grad_cov_in) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  if (!lat || !d_energy_in || !d_mu_trace || !d_cov_trace || !d_mu_bar || !d_cov_bar || !d_grad_params ||
+      !d_grad_energy_in || !d_grad_mu_in || !d_grad_cov_in)
+    return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  {
+    const int rc = trace_backward_check(ctx, lat);
+    if (rc) return rc;
+  }
+  HIP_TRY(ctx, use_device(ctx));
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  return lat->dtype == LYNX_F64
+             ? trace_backward_t<double>(ctx, lat, d_energy_in, d_mu_trace, d_cov_trace, d_mu_bar, d_cov_bar, d_energy_bar,
+                                        d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in)
+             : trace_backward_t<float>(ctx, lat, d_energy_in, d_mu_trace, d_cov_trace, d_mu_bar, d_cov_bar, d_energy_bar,
+                                       d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+}
+
+template <typename T>
+static int particles_along_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const double* d_trace_fwd,
+                                      const double* d_grad_trace, const void* d_energy_bar, void* d_grad_params,
+                                      void* d_grad_energy_in, void* d_grad_mean_in, void* d_grad_cov_in) {
+  const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
+  int rc;
+  // states and cotangents of the sweep: mu [7] | cov [49] | mu_bar [7] | cov_bar [49] per (sample, point), block by block,
+  // in the float64 of the records
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (size_t)points * 112 * sizeof(double)))) return rc;
+  double* mu = (double*)ctx->scratch_grad[0];
+  double* cov = mu + points * 7;
+  double* mu_bar = cov + points * 49;
+  double* cov_bar = mu_bar + points * 7;
+  hipLaunchKernelGGL(k_trace_records_to_states, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, d_grad_trace,
+                     mu, cov, mu_bar, cov_bar);
+  HIP_TRY(ctx, hipGetLastError());
+  return trace_backward_t<T, double>(ctx, lat, d_energy_in, mu, cov, mu_bar, cov_bar, d_energy_bar, d_grad_params, d_grad_energy_in,
+                             d_grad_mean_in, d_grad_cov_in);
+}
+
+int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                        const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
+                                        void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
+                                        void* d_grad_cov_in) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  if (!lat || !d_energy_in || !d_trace_fwd || !d_grad_trace || !d_grad_params || !d_grad_energy_in || !d_grad_mean_in ||
+      !d_grad_cov_in)
+    return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
+  {
+    const int rc = trace_backward_check(ctx, lat);
+    if (rc) return rc;
+  }
+  // the moments of the particles are closed under affine maps only: behind a cavity's kick they are not a function of
+  // the moments in front of it
+  for (int32_t s = 0; s < lat->n_steps; ++s)
+    if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
+      return fail(ctx, LYNX_ERR_INVALID,
+                  "beam trace gradients of a ParticleBeam: step " + std::to_string(s) +
+                      " is a cavity step (the particles' moments are not closed under its kick)");
+  HIP_TRY(ctx, use_device(ctx));
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+  return lat->dtype == LYNX_F64
+             ? particles_along_backward_t<double>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
+                                                  d_grad_energy_in, d_grad_mean_in, d_grad_cov_in)
+             : particles_along_backward_t<float>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
+                                                 d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
 }
 
 // ---- screen read-out -------------------------------------------------------------------------

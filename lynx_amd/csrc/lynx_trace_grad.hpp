@@ -1,0 +1,233 @@
+// gfx950 kernels of the beam trace's reverse pass: the gradient of any function of the beam moments at EVERY point of
+// a lattice (lynx_track_moments_along_backward, lynx_track_particles_along_backward).  Included only by lynx_hip.hip,
+// behind lynx_grad.hpp and lynx_trace.hpp.
+//
+// For a lattice without a kicking cavity every element is an affine map of the 7-vector, so the mean and the biased
+// covariance of a ParticleBeam obey the ParameterBeam's recursion exactly: mu_k = M_k mu_{k-1},
+// C_k = M_k C_{k-1} M_k^T.  The gradient of a function of the moments at all points therefore needs no pass over the
+// particles: it is the reverse sweep of the moment recursion with a cotangent injected at every point,
+//
+//   m = 0, G = 0
+//   for k = S .. 1:                      (point k lies behind step k - 1)
+//     m += mu_bar[k], G += cov_bar[k]
+//     (active cavity: the direct terms and coefficient cotangents of k_moments_bwd)
+//     T_bar[k-1] = m (x) mu[k-1] + (G M) C[k-1]^T + (G^T M) C[k-1]
+//     m <- M^T m,  G <- M^T G M
+//   grad_mu_in = m + mu_bar[0],  grad_cov_in = G + cov_bar[0]
+//
+// with mu[k], C[k] read from the forward trace.  T_bar leaves in the layout k_build_bwd consumes.
+//
+// The sweep's own arithmetic is float64 for every lattice dtype.  The cotangent of a Twiss value carries
+// -(beta / 2 eps) C^-1, and (G M) C^T then forms C^-1 C = 1 as gamma beta - alpha^2: a sum that cancels (1 + alpha^2)-fold
+// (240-fold for a beam that enters a FODO channel with five times its matched beta, 5000-fold at thirty times).  In
+// float32 that cancellation, carried through 128 steps, left gradients 5e-3 .. 0.3 from the float64 pass; the sweep is
+// 49 lanes of small products per step and costs the same either way.  A ParticleBeam's states and cotangents stay the
+// float64 they are in the records; a ParameterBeam's are read in the lattice's dtype.
+//
+//   k_trace_records_to_states   ParticleBeam: moment records and record cotangents [B][P][36] float64 -> mu, C, mu_bar,
+//                               cov_bar of the sweep
+//   k_trace_moments_bwd         the sweep, one wave per sample
+//   k_trace_energy_bwd          the cotangents of the beam energy at every point -> incoming energy and the gaining
+//                               cavities' voltage and phase (adds into what k_build_bwd wrote)
+#pragma once
+
+#include "lynx_device.hpp"
+#include "lynx_grad.hpp"
+
+namespace lynx {
+
+// ---------------------------------------------------------------------------------------
+// k_trace_records_to_states: grid = B * P, 64 threads.  Record layout of LYNX_MOMENT_STRIDE: [0..6] mean, [7..27] the
+// upper triangle of the biased covariance.  A record cotangent counts an off-diagonal entry once (the convention of
+// lynx_track_particles_backward): G_ii = c_ii, G_ij = G_ji = c_ij / 2.  The 7th row and column of C are zero (the 7th
+// coordinate is 1 for every particle); the 7th column of cov_bar multiplies them, so it is zero as well.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void k_trace_records_to_states(const double* __restrict__ trace_fwd,
+                                                                const double* __restrict__ grad_trace,
+                                                                double* __restrict__ mu, double* __restrict__ cov,
+                                                                double* __restrict__ mu_bar, double* __restrict__ cov_bar) {
+  const int64_t p = blockIdx.x;
+  const int lane = threadIdx.x;
+  const double* rec = trace_fwd + p * LYNX_MOMENT_STRIDE;
+  const double* g = grad_trace + p * LYNX_MOMENT_STRIDE;
+  if (lane < 7) {
+    mu[p * 7 + lane] = lane < 6 ? rec[lane] : 1.0;
+    mu_bar[p * 7 + lane] = g[lane];
+  }
+  if (lane < 49) {
+    const int i = lane / 7, j = lane - i * 7;
+    double c = 0.0, cb = 0.0;
+    if (i < 6 && j < 6) {
+      const int r = i < j ? i : j, q = i < j ? j : i;
+      const int t = 7 + r * 6 - (r * (r - 1)) / 2 + (q - r);
+      c = rec[t];
+      cb = i == j ? g[t] : 0.5 * g[t];
+    }
+    cov[p * 49 + lane] = c;
+    cov_bar[p * 49 + lane] = cb;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_moments_bwd: grid = B, one wave per sample, 49 lanes busy (lane = entry i * 7 + j), the formulas of
+// k_moments_bwd's reverse sweep.  Nothing is recomputed and nothing parked: the state that ENTERS step s is point s of
+// the forward trace.  The cotangent of point s + 1 is added BEFORE step s is reversed, so a cotangent on the entries an
+// active cavity overwrites (mu[5], cov[4,4], cov[4,5], cov[5,4], cov[5,5]) goes through the kick's formulas, not
+// through M.  What step s - 1 needs from memory (state, table row, cotangents: independent of the sweep) is fetched
+// while step s is worked on -- the sweep is a chain of small dependent products, and a sample's wave would otherwise
+// wait for memory once per step.  One lane owns every cell it writes, the sums run in a fixed order: the same call
+// returns the same bits.
+// ---------------------------------------------------------------------------------------
+template <typename T, typename ST>
+__global__ __launch_bounds__(64) void k_trace_moments_bwd(int S, const T* __restrict__ steps,
+                                                          const ST* __restrict__ mu_trace, const ST* __restrict__ cov_trace,
+                                                          const ST* __restrict__ mu_bar, const ST* __restrict__ cov_bar,
+                                                          T* __restrict__ tbar, T* __restrict__ grad_mu_in,
+                                                          T* __restrict__ grad_cov_in) {
+  using A = double;  // the sweep's own arithmetic, whatever the lattice's dtype (see the head of this file)
+  __shared__ A s_mu[8], s_c[49], s_x[49], s_y[49], s_g[49], s_mb[8], s_m[64], s_k[16];
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  const int cl = lane < 49 ? lane : 48, l7 = lane < 7 ? lane : 6;
+  const int i = cl / 7, j = cl % 7;
+  const int P = S + 1;
+  const T* g_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const ST* g_mu = mu_trace + b * (int64_t)P * 7;
+  const ST* g_c = cov_trace + b * (int64_t)P * 49;
+  const ST* g_mb = mu_bar + b * (int64_t)P * 7;
+  const ST* g_cb = cov_bar + b * (int64_t)P * 49;
+
+  if (lane < 7) s_mb[lane] = A(0);
+  if (lane < 49) s_g[lane] = A(0);
+  // (clamped lanes read a valid cell twice and use nothing of it)
+  A n_mu = A(0), n_c = A(0), n_m = A(0), n_mb = g_mb[(int64_t)S * 7 + l7], n_cb = g_cb[(int64_t)S * 49 + cl];
+  if (S > 0) {
+    n_mu = g_mu[(int64_t)(S - 1) * 7 + l7];
+    n_c = g_c[(int64_t)(S - 1) * 49 + cl];
+    n_m = g_steps[(int64_t)(S - 1) * LYNX_STEP_STRIDE + lane];
+  }
+  __syncthreads();
+  for (int s = S - 1; s >= 0; --s) {
+    if (lane < 7) {
+      s_mb[lane] += n_mb;  // cotangent of point s + 1
+      s_mu[lane] = n_mu;   // state at point s
+    }
+    if (lane < 49) {
+      s_g[lane] += n_cb;
+      s_c[lane] = n_c;
+    }
+    s_m[lane] = n_m;
+    if (lane < 16) s_k[lane] = A(0);
+    n_mb = g_mb[(int64_t)s * 7 + l7];
+    n_cb = g_cb[(int64_t)s * 49 + cl];
+    if (s > 0) {
+      n_mu = g_mu[(int64_t)(s - 1) * 7 + l7];
+      n_c = g_c[(int64_t)(s - 1) * 49 + cl];
+      n_m = g_steps[(int64_t)(s - 1) * LYNX_STEP_STRIDE + lane];
+    }
+    __syncthreads();
+    const int desc = (int)s_m[LYNX_FLAGS_OFFSET];
+    const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
+    if (kick && lane == 0) {
+      const A* cf = s_m + LYNX_COEF_OFFSET;
+      const A z4 = s_mu[4], z5 = s_mu[5], c44 = s_c[32], c45 = s_c[33], c55 = s_c[40];
+      const A m4 = s_mb[4], m5 = s_mb[5];
+      const A vb = s_g[32] + s_g[33] + s_g[39];
+      A sphi, cphi, kc[8], d4, d5;
+      phase_sincos(cf[LYNX_C_PHI], sphi, cphi);
+      kick_cotangents<A, A>(cf, sphi, cphi, z4, z5, m4, m5, kc, d4, d5);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) s_k[q] = kc[q];
+      s_k[LYNX_C_T566] += vb * (c55 * c55);
+      s_k[LYNX_C_T556] += vb * (c45 * c55);
+      s_k[LYNX_C_T555] += vb * (c44 * c44);
+      s_k[8] = d4;  // d/d mu_in[4]
+      s_k[9] = d5;  // d/d mu_in[5]
+      s_k[10] = vb * A(2) * cf[LYNX_C_T555] * c44;                                                   // d/d c44
+      s_k[11] = vb * cf[LYNX_C_T556] * c55;                                                          // d/d c45
+      s_k[12] = s_g[40] + vb * (A(2) * cf[LYNX_C_T566] * c55 + cf[LYNX_C_T556] * c45);               // d/d c55
+      s_mb[5] = A(0);  // these outputs were overwritten by the kick
+      s_g[32] = A(0);
+      s_g[33] = A(0);
+      s_g[39] = A(0);
+      s_g[40] = A(0);
+    }
+    __syncthreads();
+    // P = G M, Q = G^T M
+    A pv = s_g[i * 7] * s_m[j], qv = s_g[i] * s_m[j];
+#pragma unroll
+    for (int k = 1; k < 7; ++k) {
+      pv = t_fma(s_g[i * 7 + k], s_m[k * 7 + j], pv);
+      qv = t_fma(s_g[k * 7 + i], s_m[k * 7 + j], qv);
+    }
+    if (lane < 49) {
+      s_x[lane] = pv;
+      s_y[lane] = qv;
+    }
+    __syncthreads();
+    A tb = s_mb[i] * s_mu[j], cb = A(0), mbn = A(0);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      tb = t_fma(s_x[i * 7 + k], s_c[j * 7 + k], tb);
+      tb = t_fma(s_y[i * 7 + k], s_c[k * 7 + j], tb);
+      cb = t_fma(s_m[k * 7 + i], s_x[k * 7 + j], cb);
+    }
+    if (lane < 7) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) mbn = t_fma(s_m[k * 7 + lane], s_mb[k], mbn);
+    }
+    T* tb_out = tbar + (b * S + s) * (int64_t)kGradStride;
+    if (lane < 49) tb_out[lane] = tb;
+    else if (lane < 57) tb_out[lane] = s_k[lane - 49];
+    else tb_out[lane] = A(0);
+    __syncthreads();
+    if (lane < 49) s_g[lane] = cb;
+    if (lane < 7) s_mb[lane] = mbn;
+    __syncthreads();
+    if (kick && lane == 0) {
+      s_mb[4] += s_k[8];
+      s_mb[5] += s_k[9];
+      s_g[32] += s_k[10];
+      s_g[33] += s_k[11];
+      s_g[40] += s_k[12];
+    }
+    __syncthreads();
+  }
+  if (lane < 7) grad_mu_in[b * 7 + lane] = s_mb[lane] + n_mb;     // + the cotangent of point 0
+  if (lane < 49) grad_cov_in[b * 49 + lane] = s_g[lane] + n_cb;
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_energy_bwd: one lane per sample, behind k_build_bwd on the same stream.  The energy at point k is
+// E_in + sum of V cos(phi) over the gaining cavities in front of it (k_trace_reference), so with
+// carry_s = sum of energy_bar[k] over k > s -- the cotangent of the energy leaving step s, as in step 4 of
+// k_build_bwd -- a gaining cavity at step s receives carry_s dE/dV, carry_s dE/dphase and the incoming energy the
+// sum over all points.  Adds into grad_params and grad_energy.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_energy_bwd(LatticeDev lat, const T* __restrict__ steps,
+                                                         const T* __restrict__ energy_bar /* [B][P] */,
+                                                         T* __restrict__ grad_params /* [B][E][8] */,
+                                                         T* __restrict__ grad_energy /* [B] */) {
+  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (b >= lat.batch) return;
+  const int S = lat.n_steps, P = S + 1, E = lat.n_elems;
+  const T* pool = static_cast<const T*>(lat.pool);
+  T carry = T(0);
+  for (int s = S - 1; s >= 0; --s) {
+    carry += energy_bar[b * P + s + 1];
+    const int desc = (int)steps[(b * S + s) * LYNX_STEP_STRIDE + LYNX_FLAGS_OFFSET];
+    if (((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN)) {
+      const int first = lat.steps[s].first;
+      const lynx_elem el = lat.elems[first];
+      const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
+      const T phi = p[2] * T(LYNX_PI / 180.0);
+      T* gp = grad_params + (b * E + first) * (int64_t)kGradParams;
+      gp[1] += carry * t_cos(phi);                                   // dE_out/dV
+      gp[2] += carry * (-p[1] * t_sin(phi)) * T(LYNX_PI / 180.0);    // dE_out/dphase[deg]
+    }
+  }
+  grad_energy[b] += carry + energy_bar[b * P];
+}
+
+}  // namespace lynx

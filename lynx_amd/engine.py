@@ -506,11 +506,12 @@ def _trace_plan(owner, leaves) -> Program:
     return program
 
 
-def track_along(owner, leaves, incoming, keep_outgoing: bool = True):
+def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False):
     """
     `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
     `lynx_track_moments_along`).  The packed "every element its own step" lattice is cached on `owner` (its own
-    LatticeCache: a parameter write between two calls rewrites that element's block only).
+    LatticeCache: a parameter write between two calls rewrites that element's block only).  `keep_device`: the trace
+    keeps the device arrays the kernels wrote (`trace._device`) -- what the reverse pass of `grad.track_along_vjp` reads.
     """
     from .trace import BeamTrace
 
@@ -542,6 +543,7 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True):
         trace = BeamTrace.from_records(rec, energy, lengths, names, dtype)
         trace.num_particles = n
         centre = rec[..., :, (0, 2)].astype(dtype)  # mean x, y at every point
+        device = {"records": records}
         if keep_outgoing:
             out = ParticleBeam.__new__(ParticleBeam)
             charges = incoming._charges
@@ -561,6 +563,7 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True):
         energy = e_trace.numpy().reshape(*batch_shape, P)
         trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype)
         centre = mu[..., :, (0, 2)]
+        device = {"mu": mu_t, "cov": cov_t}
         if keep_outgoing:
             out = ParameterBeam.__new__(ParameterBeam)
             out._init_raw(Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
@@ -568,6 +571,8 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True):
                           incoming.total_charge, dtype)
             trace.outgoing = out
     trace.total_charge = incoming.total_charge
+    if keep_device:
+        trace._device = device
     for k, el in enumerate(leaves):  # an active BPM reads the beam that ENTERS it: point k (bpm.py:48-54)
         if getattr(el, "_fusable_observer", False):
             el.reading = np.stack([centre[..., k, 0], centre[..., k, 1]]).astype(dtype)

@@ -369,6 +369,229 @@ class MomentsVJP:
         return parts[0] if len(parts) == 1 else ChainedGradients(parts)
 
 
+# -------------------------------------------------------------------------------------------
+# gradients of the beam ALONG the lattice (Segment.track_along)
+# -------------------------------------------------------------------------------------------
+
+MAX_TRACE_LEAVES = 256  # lynx_track_*_along_backward: k_build_bwd deals the steps of a program to its 256 threads
+
+
+def trace_property_cotangents(trace, named: dict):
+    """
+    Cotangents of named properties of a `BeamTrace`, each (*batch, P) (broadcastable: a scalar is the same weight at
+    every point) -> (mu_bar (*batch, P, 7), cov_bar (*batch, P, 7, 7) entry by entry, energy_bar (*batch, P)), float64.
+    The formulas are the ones the traces evaluate:
+      ParticleBeamTrace   sigma_c = sqrt(cov_cc n / (n - ddof)) (`config.std_ddof`), sigma_xxp = cov_01 as it is;
+      ParameterBeamTrace  sigma_c = sqrt(max(cov_cc, 1e-20)): derivative 0 where clamped;
+      both                emittance = sqrt(max(sigma^2 sigma_p^2 - sigma_xxp^2, tiny)) (`Beam._emittance`, 0 where
+                          clamped), beta = sigma^2 / emittance, alpha = -sigma_xxp / emittance,
+                          normalized_emittance = emittance sqrt(gamma^2 - 1) -- which also depends on the energy there.
+    """
+    from . import config
+    from .trace import ParticleBeamTrace
+
+    shape = (*trace.batch_shape, trace.num_points)
+    mu_bar, cov_bar, energy_bar = np.zeros((*shape, 7)), np.zeros((*shape, 7, 7)), np.zeros(shape)
+    if isinstance(trace, ParticleBeamTrace):
+        rec = np.asarray(trace.records, dtype=np.float64)
+        n = rec[..., 35]
+        scale = n / (n - config.std_ddof)
+        variance = lambda c: rec[..., _tri(c, c)]  # noqa: E731
+        cross_of = lambda a: rec[..., _tri(a, a + 1)]  # noqa: E731
+        floor = None
+    else:
+        cov = np.asarray(trace._cov, dtype=np.float64)
+        scale = np.ones(shape)
+        variance = lambda c: cov[..., c, c]  # noqa: E731
+        cross_of = lambda a: cov[..., a, a + 1]  # noqa: E731
+        floor = float(trace.dtype.type(1e-20))
+    tiny = float(np.finfo(trace.dtype).tiny)
+
+    def sigma_squared(c):
+        """sigma_c^2 and its derivative with respect to cov_cc."""
+        v = variance(c)
+        if floor is None:
+            return v * scale, scale
+        return np.maximum(v, floor), (v > floor).astype(np.float64)
+
+    # what a plane's properties are written in: s2 = sigma^2, p2 = sigma_p^2, the cross term
+    plane_bars = {}
+
+    def plane(a):
+        if a not in plane_bars:
+            plane_bars[a] = {"s2": np.zeros(shape), "p2": np.zeros(shape), "cross": np.zeros(shape)}
+        return plane_bars[a]
+
+    def emittance(a):
+        s2, p2, cross = sigma_squared(a)[0], sigma_squared(a + 1)[0], cross_of(a)
+        q = s2 * p2 - cross**2
+        return np.sqrt(np.maximum(q, tiny)), q > tiny, s2, p2, cross
+
+    def emittance_bar(a, bar):
+        eps, free, s2, p2, cross = emittance(a)
+        with np.errstate(all="ignore"):
+            w = np.where(free, bar / (2.0 * eps), 0.0)
+        acc = plane(a)
+        acc["s2"] += w * p2
+        acc["p2"] += w * s2
+        acc["cross"] += -2.0 * w * cross
+
+    for name, bar in named.items():
+        bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), shape)
+        kind, _, coord = name.partition("_")
+        if name == "energy":
+            energy_bar += bar
+        elif kind == "mu" and coord in _COORDINATES:
+            mu_bar[..., _COORDINATES.index(coord)] += bar
+        elif kind == "sigma" and coord in _COORDINATES:
+            c = _COORDINATES.index(coord)
+            s2, ds2 = sigma_squared(c)
+            with np.errstate(all="ignore"):
+                cov_bar[..., c, c] += np.where(ds2 != 0, bar * ds2 / (2.0 * np.sqrt(s2)), 0.0)
+        elif name in ("sigma_xxp", "sigma_yyp"):
+            plane(0 if name == "sigma_xxp" else 2)["cross"] += bar
+        elif name in ("emittance_x", "emittance_y"):
+            emittance_bar(0 if name.endswith("x") else 2, bar)
+        elif name in ("normalized_emittance_x", "normalized_emittance_y"):
+            a = 0 if name.endswith("x") else 2
+            gamma = np.asarray(trace.energy, dtype=np.float64) / engine.ELECTRON_MASS_EV
+            moving = np.abs(gamma) > 0
+            with np.errstate(all="ignore"):
+                bg = np.where(moving, np.sqrt(1 - 1 / gamma**2) * gamma, 0.0)  # relativistic beta . gamma
+                dbg = np.where(moving, gamma / np.sqrt(gamma**2 - 1), 0.0) / engine.ELECTRON_MASS_EV
+            emittance_bar(a, bar * bg)
+            energy_bar += bar * emittance(a)[0] * dbg
+        elif name in ("beta_x", "beta_y"):
+            a = 0 if name.endswith("x") else 2
+            eps, _, s2, _, _ = emittance(a)
+            plane(a)["s2"] += bar / eps
+            emittance_bar(a, -bar * s2 / eps**2)
+        elif name in ("alpha_x", "alpha_y"):
+            a = 0 if name.endswith("x") else 2
+            eps, _, _, _, cross = emittance(a)
+            plane(a)["cross"] += -bar / eps
+            emittance_bar(a, bar * cross / eps**2)
+        else:
+            raise KeyError(f"no cotangent rule for trace property {name!r}")
+    for a, acc in plane_bars.items():
+        cov_bar[..., a, a] += acc["s2"] * sigma_squared(a)[1]
+        cov_bar[..., a + 1, a + 1] += acc["p2"] * sigma_squared(a + 1)[1]
+        cov_bar[..., a, a + 1] += acc["cross"]
+    return mu_bar, cov_bar, energy_bar
+
+
+class TrackAlongVJP:
+    """
+    Vector-Jacobian product of `Segment.track_along`: gradients of any function of the beam moments and the energy at
+    EVERY point of the lattice (lynx_track_moments_along_backward / lynx_track_particles_along_backward).  Without a
+    kicking cavity every element is an affine map, so a ParticleBeam's mean and covariance obey the ParameterBeam's
+    recursion: one reverse sweep of that recursion over the forward trace serves both beam classes, and no particle is
+    tracked a second time.
+    """
+
+    def __init__(self, segment, beam):
+        from .particles.parameter_beam import ParameterBeam
+
+        if not isinstance(beam, (ParameterBeam, ParticleBeam)):
+            raise TypeError(f"track_along_vjp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
+        leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
+        # (raises for an active Screen or Aperture, naming it, before anything touches the GPU)
+        self.program = engine._trace_plan(segment, leaves)
+        if len(leaves) > MAX_TRACE_LEAVES:
+            raise NotImplementedError(
+                f"track_along_vjp: {len(leaves)} leaf elements, more than {MAX_TRACE_LEAVES} (the first one beyond is "
+                f"{leaves[MAX_TRACE_LEAVES].name!r}) -- differentiate the lattice in stretches")
+        if isinstance(beam, ParticleBeam):
+            for kind, first, _ in self.program.steps:
+                if kind == _ffi.STEP_CAVITY:
+                    raise NotImplementedError(
+                        f"track_along_vjp: active Cavity {leaves[first].name!r} -- the moments of a ParticleBeam are not "
+                        "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated")
+        self.segment, self.beam, self.leaves = segment, beam, leaves
+        self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True)
+
+    def _cotangents(self, mu_bar, cov_bar, energy_bar, readings, properties):
+        batch_shape = self.beam.batch_shape
+        P = self.trace.num_points
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        mb, cb, eb = np.zeros((B, P, 7)), np.zeros((B, P, 7, 7)), np.zeros((B, P))
+        if properties:
+            pm, pc, pe = trace_property_cotangents(self.trace, properties)
+            mb += pm.reshape(B, P, 7)
+            cb += pc.reshape(B, P, 7, 7)
+            eb += pe.reshape(B, P)
+        if mu_bar is not None:
+            mu_bar = np.asarray(mu_bar, dtype=np.float64)
+            k = mu_bar.shape[-1]
+            mb[..., :k] += np.broadcast_to(mu_bar, (*batch_shape, P, k)).reshape(B, P, k)
+        if cov_bar is not None:
+            cov_bar = np.asarray(cov_bar, dtype=np.float64)
+            k = cov_bar.shape[-1]
+            cb[..., :k, :k] += np.broadcast_to(cov_bar, (*batch_shape, P, k, k)).reshape(B, P, k, k)
+        if energy_bar is not None:
+            eb += np.broadcast_to(np.asarray(energy_bar, dtype=np.float64), (*batch_shape, P)).reshape(B, P)
+        for element, bar in (readings or {}).items():
+            points = [k for k, el in enumerate(self.leaves) if el is element and getattr(el, "_fusable_observer", False)]
+            if not points:
+                raise KeyError(f"{element!r} is not an active BPM of this lattice")
+            bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), (2, *batch_shape))
+            for k in points:  # an active BPM reads (mu_x, mu_y) of the beam that ENTERS it: point k (bpm.py:48-54)
+                mb[:, k, 0] += bar[0].reshape(B)
+                mb[:, k, 2] += bar[1].reshape(B)
+        return mb, cb, eb
+
+    def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, **properties) -> Gradients:
+        """
+        `mu_bar` (*batch, P, 6|7), `cov_bar` (*batch, P, 6|7, 6|7) entry by entry, `energy_bar` (*batch, P): cotangents at
+        every point; `properties`: cotangents (*batch, P) of any moment property of the trace and of `energy`;
+        `readings={bpm: bar}`: of the readings of active BPMs, shaped like `bpm.reading` -- (2, *batch).
+        """
+        mb, cb, eb = self._cotangents(mu_bar, cov_bar, energy_bar, readings, properties)
+        rt = get_runtime()
+        beam, program = self.beam, self.program
+        batch_shape, dtype = beam.batch_shape, beam.dtype
+        B, P = mb.shape[:2]
+        cache = self.segment.__dict__.setdefault("_trace_cache", engine.LatticeCache())
+        lat = engine._ready(cache, program, batch_shape, dtype, beam._energy._host)
+        g_par = rt.empty((B, max(lat.E, 1), 8), dtype)
+        g_en = rt.empty((B,), dtype)
+        g_mu = rt.empty((*batch_shape, 7), dtype)
+        g_cov = rt.empty((*batch_shape, 7, 7), dtype)
+        e_in = beam._energy.broadcast_device(rt, batch_shape)
+        p = lambda a: None if a is None else C.c_void_p(a.ptr)  # noqa: E731
+        # named, so that the uploads stay allocated until the call has been enqueued
+        eb_dev = rt.to_device(eb.astype(dtype)) if np.any(eb) else None
+        states = self.trace._device
+        if isinstance(beam, ParticleBeam):
+            rec = np.zeros((B, P, _ffi.MOMENT_STRIDE), dtype=np.float64)
+            rec[..., :7] = mb
+            rows, cols = np.triu_indices(6)  # (the order of the record's triangle, `_tri`)
+            rec[..., 7:28] = (cb[..., rows, cols] + cb[..., cols, rows]) * np.where(rows == cols, 0.5, 1.0)
+            rec_dev = rt.to_device(rec)
+            rt.check(rt.lib.lynx_track_particles_along_backward(
+                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]), p(rec_dev), p(eb_dev),
+                p(g_par), p(g_en), p(g_mu), p(g_cov)))
+        else:
+            mb_dev, cb_dev = rt.to_device(mb.astype(dtype)), rt.to_device(cb.astype(dtype))
+            rt.check(rt.lib.lynx_track_moments_along_backward(
+                rt.ctx, lat.handle, p(e_in), p(states["mu"]), p(states["cov"]), p(mb_dev), p(cb_dev), p(eb_dev),
+                p(g_par), p(g_en), p(g_mu), p(g_cov)))
+        return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
+
+
+def track_along_vjp(segment, beam):
+    """
+    Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
+    callable vector-Jacobian product of the moments and energies at every point:
+
+        vjp = lynx_amd.grad.track_along_vjp(segment, beam)
+        g = vjp(beta_x=w_x, beta_y=w_y)          # cotangents (*batch, P) of any property of the trace, or
+        g = vjp(mu_bar=..., cov_bar=..., energy_bar=..., readings={bpm: ...})
+        g[segment.Q1]["k1"], g.energy, g.mu, g.cov
+    """
+    return TrackAlongVJP(segment, beam)
+
+
 def track_vjp(segment, beam):
     """Forward pass through `segment`; returns the callable vector-Jacobian product."""
     from .particles.parameter_beam import ParameterBeam
