@@ -243,6 +243,24 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
 int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags);
 
+/* ... with particle losses: steps that are ACTIVE apertures (reference: aperture.py:69-108, which compacts the particle
+ * array) clear the particles outside them from every later point instead; nothing is compacted, so samples may lose
+ * different numbers of particles.  Arguments as above, and
+ *   apertures     host [n_apertures][2]: step index (increasing; the step itself is an identity step of the program),
+ *                 1 for an elliptical aperture / 0 for a rectangular one
+ *   d_limits      [B][n_apertures][2] (limit_stride = 2 n_apertures) or [n_apertures][2] shared by the batch
+ *                 (limit_stride = 0): x_max, y_max in the lattice's dtype
+ *   d_lost_at     [B][N] int32 or NULL: ordinal (row of `apertures`) of the aperture that removed the particle, -1 for
+ *                 a survivor
+ * Aperture k tests the particles that ENTER its step (point `step`), by lynx_aperture_mask's comparison; a particle
+ * that fails takes no part in the sums of any later point.  Slot 35 of a record is the number of particles alive at
+ * that point; a point with none has count 0 and NaN moments.  d_p_out holds every particle, a lost one as far as the
+ * maps took it (possibly inf or NaN).  The reference point stays the sample's first particle, lost or not.           */
+int lynx_track_particles_along_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                      const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                      int32_t n_apertures, const int32_t* apertures, const void* d_limits,
+                                      int64_t limit_stride, int32_t* d_lost_at);
+
 /* ... of a ParameterBeam (reference: the same loop; element.py:71-82 mu' = T mu, cov' = T cov T^T per element,
  * cavity.py:134-140,202-218): d_mu_trace [B][P][7], d_cov_trace [B][P][7][7], d_energy_trace [B][P].              */
 int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,

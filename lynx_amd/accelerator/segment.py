@@ -199,7 +199,7 @@ class Segment(Element):
         """segment.py:340-356."""
         return engine.track(self, self.elements, incoming)
 
-    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True):
+    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True, losses=False):
         """
         The beam ALONG the lattice: its moments and energy at the entrance and behind every leaf element (nested
         segments opened up), for every batch sample, from one pass over the particles -- the data behind the reference's
@@ -207,10 +207,19 @@ class Segment(Element):
         `resolution`, `plot_reference_particle_traces` (the lattice is `split(resolution)` first).  Returns a
         `lynx_amd.trace.BeamTrace`; `keep_outgoing=False` does not store the tracked particles (moments only).
         Unlike `plot_twiss`, zero-length elements are tracked and have a point (`BeamTrace.where_length_changes()`).
+
+        An active `Aperture` is refused unless `losses` is set.  `losses=True`: aperture k tests the particles that enter
+        it (point k; its own `x_max`, `y_max`, `shape`, batched or shared) and a particle that fails is dead from point
+        k + 1 on -- nothing is compacted, so every sample of a batch may lose its own particles.  The trace then has
+        `num_survivors`, `transmission`, `apertures`, `lost_in`; every moment of a point is taken over the particles alive
+        there (count 0: NaN); `outgoing` is the tracked beam if no sample lost a particle and None otherwise.
+        `losses="particles"` also brings back `lost_at` (*batch, N): which aperture removed each particle, -1 for a
+        survivor.  A `ParameterBeam` passes active apertures unchanged (aperture.py:70-72) and has no loss attributes.
         """
         if resolution is not None:
-            return Segment(self.split(resolution), name=self.name).track_along(incoming, keep_outgoing=keep_outgoing)
-        return engine.track_along(self, self._leaves(), incoming, keep_outgoing)
+            return Segment(self.split(resolution), name=self.name).track_along(incoming, keep_outgoing=keep_outgoing,
+                                                                               losses=losses)
+        return engine.track_along(self, self._leaves(), incoming, keep_outgoing, losses=losses)
 
     def forward(self, incoming):
         return self.track(incoming)

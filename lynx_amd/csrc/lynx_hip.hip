@@ -173,6 +173,9 @@ struct lynx_ctx {
   size_t scratch_steps_bytes[kTableSlots + 3] = {};
   void* scratch_trace[2] = {nullptr, nullptr};  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
   size_t scratch_trace_bytes[2] = {0, 0};
+  void* scratch_trace_codes = nullptr;  // ... with losses: which steps are apertures (TraceLosses.codes), and what was uploaded last
+  size_t scratch_trace_codes_bytes = 0;
+  std::vector<int32_t> trace_codes;
   void* scratch_units_bwd[2] = {nullptr, nullptr};  // ... and of the reverse pass's own table
   size_t scratch_units_bwd_bytes[2] = {0, 0};
   void* scratch_units[2 * kTableSlots] = {};  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
@@ -626,6 +629,7 @@ int lynx_ctx_destroy(lynx_ctx* ctx) {
     if (ctx->scratch_steps[i]) (void)hipFree(ctx->scratch_steps[i]);
   for (int i = 0; i < 2; ++i)
     if (ctx->scratch_trace[i]) (void)hipFree(ctx->scratch_trace[i]);
+  if (ctx->scratch_trace_codes) (void)hipFree(ctx->scratch_trace_codes);
   for (int i = 0; i < 2 * lynx_ctx::kTableSlots; ++i)
     if (ctx->scratch_units[i]) (void)hipFree(ctx->scratch_units[i]);
   for (int i = 0; i < 2; ++i)
@@ -2419,9 +2423,37 @@ static int trace_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
                          nullptr, lds > (size_t)64 * 1024);
 }
 
+// The apertures of a trace with losses as the host hands them over.
+struct TraceApertures {
+  int32_t count;
+  const int32_t* pairs;  // [count][2]: step, elliptical
+  const void* d_limits;
+  int64_t limit_stride;
+  int32_t* d_lost_at;
+};
+
+// TraceLosses.codes of this call on the device.  The list is uploaded when it differs from the one that is there (a scan
+// calls with the same lattice over and over); the wait that upload needs is paid once per lattice structure.
+static int trace_codes(lynx_ctx* ctx, int32_t S, const TraceApertures& ap) {
+  std::vector<int32_t> codes(std::max<int32_t>(1, S), -1);
+  for (int32_t k = 0; k < ap.count; ++k) codes[ap.pairs[2 * k]] = (k << 1) | (ap.pairs[2 * k + 1] ? 1 : 0);
+  const size_t need = codes.size() * sizeof(int32_t);
+  const bool fresh = ctx->scratch_trace_codes_bytes < need;
+  int rc;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace_codes, &ctx->scratch_trace_codes_bytes, need))) return rc;
+  if (fresh || codes != ctx->trace_codes) {
+    ctx->trace_codes.clear();
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_trace_codes, codes.data(), need, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, sync_main(ctx));  // (kernels of earlier calls have read the old list; the host vector is ours again)
+    ctx->trace_codes.swap(codes);
+  }
+  return LYNX_OK;
+}
+
 template <typename T>
 static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in, const void* d_p_in,
-                                   void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags) {
+                                   void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                   const TraceApertures* ap = nullptr) {
   constexpr int U = sizeof(T) == 4 ? 4 : 2;  // particles per lane (float32: two packed pairs)
   const int64_t B = lat->batch;
   const int32_t S = lat->n_steps, P = S + 1;
@@ -2451,9 +2483,27 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   a.store = d_p_out ? 1 : 0;
   a.points = P;
   const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
+  if (ap && (rc = trace_codes(ctx, S, *ap))) return rc;
   hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
                      (const T*)d_energy_in, (const T*)d_p_in, a.in_stride, (T*)ctx->scratch_trace[1], (T*)d_energy_trace);
   HIP_TRY(ctx, hipGetLastError());
+  if (ap) {
+    if (ap->d_lost_at)  // every byte 0xff: -1, "survivor"; the kernel writes the cells of the lost
+      HIP_TRY(ctx, hipMemsetAsync(ap->d_lost_at, 0xff, (size_t)B * N * sizeof(int32_t), ctx->stream));
+    const TraceLosses loss{(const int32_t*)ctx->scratch_trace_codes, ap->d_limits, ap->limit_stride, ap->d_lost_at};
+    hipLaunchKernelGGL((k_trace_particles_losses<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, S,
+                       table, (const T*)ctx->scratch_trace[1], (const T*)d_p_in, (T*)d_p_out, (double*)ctx->scratch_trace[0],
+                       loss);
+    HIP_TRY(ctx, hipGetLastError());
+    if (waves > 256)
+      hipLaunchKernelGGL((k_trace_finalize_counted<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
+                         (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, d_trace_out);
+    else
+      hipLaunchKernelGGL((k_trace_finalize_counted<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
+                         (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, d_trace_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return LYNX_OK;
+  }
   hipLaunchKernelGGL((k_trace_particles<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, S, table,
                      (const T*)ctx->scratch_trace[1], (const T*)d_p_in, (T*)d_p_out, (double*)ctx->scratch_trace[0]);
   HIP_TRY(ctx, hipGetLastError());
@@ -2488,6 +2538,41 @@ int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_parti
   return lat->dtype == LYNX_F64
              ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags)
              : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags);
+}
+
+int lynx_track_particles_along_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                      const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                      int32_t n_apertures, const int32_t* apertures, const void* d_limits,
+                                      int64_t limit_stride, int32_t* d_lost_at) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
+  if (flags & ~LYNX_TRACK_SHARED_INPUT) return fail(ctx, LYNX_ERR_INVALID, "beam trace: LYNX_TRACK_SHARED_INPUT is the only flag");
+  if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out)
+    return fail(ctx, LYNX_ERR_INVALID, "a shared incoming beam cannot be tracked in place");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
+  if (n_apertures < 0 || n_apertures > 0x3fffffff || (n_apertures > 0 && (!apertures || !d_limits)))
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace with losses: bad aperture list");
+  if (limit_stride != 0 && limit_stride != 2 * (int64_t)n_apertures)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace with losses: the limits' sample stride is 0 or 2 * n_apertures");
+  for (int32_t k = 0; k < n_apertures; ++k) {  // lattice order, every step at most once
+    const int32_t step = apertures[2 * k];
+    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= apertures[2 * k - 2]))
+      return fail(ctx, LYNX_ERR_INVALID, "beam trace with losses: aperture steps must be increasing and inside the program");
+  }
+  HIP_TRY(ctx, use_device(ctx));
+  ctx->main_dirty = true;
+  const size_t es = dtype_size(lat->dtype);
+  const size_t points = (size_t)lat->n_steps + 1;
+  ctx->wrote(d_p_out, (size_t)lat->batch * n_particles * 7 * es);
+  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
+  ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
+  ctx->wrote(d_lost_at, (size_t)lat->batch * n_particles * sizeof(int32_t));
+  const TraceApertures ap{n_apertures, apertures, d_limits, limit_stride, d_lost_at};
+  return lat->dtype == LYNX_F64
+             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap)
+             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap);
 }
 
 template <typename T>

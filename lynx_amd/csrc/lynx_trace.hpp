@@ -19,6 +19,11 @@
 //                           tile: no atomics, one fixed order.
 //   k_trace_finalize        adds the waves' slabs of a (sample, point) in a fixed order and writes the moment record
 //                           [B][P][36] (layout of LYNX_MOMENT_STRIDE, slot 34 = 1).
+//
+// With particle losses (lynx_track_particles_along_losses; k_trace_particles_losses, k_trace_finalize_counted) an active
+// aperture is an identity step that clears the `live` bit of the particles outside it: nothing is compacted, a lost
+// particle stays in its lane and is kept out of every later sum by a select, and the number of particles a record
+// stands for is the point's own sum of the 7th coordinate (slot 6 of the slab row) instead of N.
 #pragma once
 
 #include "lynx_device.hpp"
@@ -35,6 +40,17 @@ struct TraceArgs {
   int32_t tiles_per_wave;
   int32_t store;          // 1: write p_out
   int32_t points;         // P = E + 1
+};
+
+// The apertures of a trace with losses.  `codes` [S]: -1, or (ordinal of the aperture << 1) | elliptical for a step that
+// is an active aperture; `limits` [B or 1][A][2]: x_max, y_max in the lattice's dtype.
+struct TraceLosses {
+  const int32_t* codes;
+  const void* limits;
+  int64_t limit_stride;  // scalars between the samples of `limits`: 2 A, or 0 for limits the batch shares
+  int32_t* lost_at;      // [B][N], -1 everywhere before the launch: a particle's cell is written when (and if) an aperture
+                         // removes it, with the aperture's ordinal (keeping the ordinals in registers until the end of
+                         // the tile costs the float32 kernel its third wave per SIMD); or null
 };
 
 // ---------------------------------------------------------------------------------------
@@ -229,12 +245,34 @@ __device__ __forceinline__ void trace_point(const double (&z)[U][7], const doubl
   trace_deposit<double>(v, lane, first, row);
 }
 
+// Step s of a trace with losses, after point s has been deposited: if the step is an aperture (wave-uniform: a scalar
+// load), the particles whose coordinates ENTERING it lie outside are dead from the next point on.  The comparison is
+// k_aperture_mask's own (aperture_survives<T>, aperture.py:78-86).
+template <typename T, int U, typename X>
+__device__ __forceinline__ void trace_aperture(const TraceLosses& loss, const T* __restrict__ limits /* of this sample */,
+                                               int s, X&& xy, bool (&live)[U], int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
+  const int code = __builtin_amdgcn_readfirstlane(loss.codes[s]);
+  if (code < 0) return;
+  const int ordinal = code >> 1;
+  const T xm = uniform_value(limits[ordinal * 2]), ym = uniform_value(limits[ordinal * 2 + 1]);
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    T x, y;
+    xy(u, x, y);
+    const bool out = live[u] && !aperture_survives<T>(x, y, xm, ym, code & 1);
+    if (out && tile_lost_at) tile_lost_at[lane + 64 * u] = ordinal;  // (once: the particle is dead from here on)
+    live[u] = live[u] && !out;
+  }
+}
+
 // one tile of a wave through the whole lattice
-template <typename T, int U, bool MASKED>
+template <typename T, int U, bool MASKED, bool LOSSES = false>
 __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* __restrict__ steps /* of this sample */,
                                            const T* __restrict__ ref /* of this sample */, const T* __restrict__ src,
                                            T* __restrict__ dst, int64_t base, int lane, bool first,
-                                           double* __restrict__ slab /* of this wave */) {
+                                           double* __restrict__ slab /* of this wave */, const TraceLosses& loss = TraceLosses{},
+                                           const T* __restrict__ limits = nullptr, int32_t* __restrict__ lost_at = nullptr) {
+  static_assert(MASKED || !LOSSES, "a trace with losses always takes the masked path");
   bool live[U];
   T z[U][7];
 #pragma unroll
@@ -256,6 +294,11 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
     for (int s = 0; s <= S; ++s) {
       trace_point<U, MASKED>(zp, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
       if (s == S) break;
+      if constexpr (LOSSES)
+        trace_aperture<T, U>(loss, limits, s, [&](int u, T& x, T& y) {
+          x = (u & 1) ? zp[u / 2][0].y : zp[u / 2][0].x;
+          y = (u & 1) ? zp[u / 2][2].y : zp[u / 2][2].x;
+        }, live, lost_at ? lost_at + base : nullptr, lane);
       const T* tab = steps + s * LYNX_STEP_STRIDE;  // global, wave-uniform: scalar loads
       const int desc = (int)uniform_value(tab[LYNX_FLAGS_OFFSET]);
       const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
@@ -299,6 +342,11 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
     for (int s = 0; s <= S; ++s) {
       trace_point<U, MASKED>(z, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
       if (s == S) break;
+      if constexpr (LOSSES)
+        trace_aperture<T, U>(loss, limits, s, [&](int u, T& x, T& y) {
+          x = z[u][0];
+          y = z[u][2];
+        }, live, lost_at ? lost_at + base : nullptr, lane);
       const T* tab = steps + s * LYNX_STEP_STRIDE;
       const int desc = (int)tab[LYNX_FLAGS_OFFSET];
       const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
@@ -306,7 +354,16 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
       for (int u = 0; u < U; ++u) apply_step<T>(tab, skind, sflags, z[u]);
     }
   }
-  if (a.store) {
+  if constexpr (LOSSES) {
+    // (a lost particle is stored as far as it was propagated; its `lost_at` -- written where it was lost -- says so)
+    if (a.store) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int64_t i = base + lane + 64 * u;
+        if (i < a.n_particles) store_particle(dst + i * 7, z[u]);
+      }
+    }
+  } else if (a.store) {
 #pragma unroll
     for (int u = 0; u < U; ++u)
       if (live[u]) store_particle(dst + (base + lane + 64 * u) * 7, z[u]);
@@ -348,6 +405,37 @@ __global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, con
   }
 }
 
+// ... with active apertures (TraceLosses): the same walk over the tiles, every one of them by the masked path.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void k_trace_particles_losses(TraceArgs a, int S, const T* __restrict__ steps,
+                                                                const T* __restrict__ ref, const T* __restrict__ p_in,
+                                                                T* __restrict__ p_out, double* __restrict__ slabs,
+                                                                TraceLosses loss) {
+  const int wgs = a.waves / 4;
+  const int64_t b = blockIdx.x / wgs;
+  const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int P = S + 1;
+  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const T* sample_ref = ref + b * (int64_t)P * kTraceRef;
+  const T* src = p_in + b * a.in_stride;
+  T* dst = p_out + b * a.n_particles * 7;
+  double* slab = slabs + (b * a.waves + w) * (int64_t)P * kTraceSlab;
+  const T* limits = static_cast<const T*>(loss.limits) + b * loss.limit_stride;
+  int32_t* lost_at = loss.lost_at ? loss.lost_at + b * a.n_particles : nullptr;
+  constexpr int64_t kTile = 64 * U;
+  const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
+  if (begin >= a.n_particles) {
+    for (int64_t i = lane; i < (int64_t)P * kTraceSlab; i += 64) slab[i] = 0.0;
+    return;
+  }
+  for (int t = 0; t < a.tiles_per_wave; ++t) {
+    const int64_t base = begin + t * kTile;
+    if (base >= a.n_particles) break;
+    trace_tile<T, U, true, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at);
+  }
+}
+
 // ---------------------------------------------------------------------------------------
 // k_trace_finalize: grid.x = B * P, THREADS = 32 G threads.  The slabs of the sample's waves at this point: group g
 // adds the g-th of G contiguous ranges of waves in wave order (one thread per cell), the G sums are added in group
@@ -356,10 +444,9 @@ __global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, con
 // (One group alone: 2608 dependent additions per cell for one sample of 10^6 particles, 577 us -- more than the
 // streaming kernel's 122.)
 // ---------------------------------------------------------------------------------------
-template <typename T, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __restrict__ slabs, const T* __restrict__ ref,
-                                                            int waves, int P, int64_t n_particles,
-                                                            double* __restrict__ out) {
+template <typename T, int THREADS, bool COUNTED>
+__device__ __forceinline__ void trace_finalize_body(const double* __restrict__ slabs, const T* __restrict__ ref, int waves,
+                                                    int P, int64_t n_particles, double* __restrict__ out) {
   constexpr int G = THREADS / kTraceSlab;
   __shared__ double s_part[G][kTraceSlab];
   __shared__ double s[kPartialStride];
@@ -385,6 +472,9 @@ __global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __rest
       v = (double)ref[(b * P + k) * kTraceRef + (tid - 28)];
     } else if (tid == 34) {
       v = 1.0;
+    } else if (COUNTED) {  // the point's own count: the sum of the 7th coordinate, exact (integers in float64)
+#pragma unroll
+      for (int q = 0; q < G; ++q) v += s_part[q][6];
     } else {
       v = (double)n_particles;
     }
@@ -392,6 +482,22 @@ __global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __rest
   }
   __syncthreads();
   if (tid < kPartialStride) write_moment_record(s, out + (b * P + k) * kPartialStride, tid);
+}
+
+template <typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __restrict__ slabs, const T* __restrict__ ref,
+                                                            int waves, int P, int64_t n_particles,
+                                                            double* __restrict__ out) {
+  trace_finalize_body<T, THREADS, false>(slabs, ref, waves, P, n_particles, out);
+}
+
+// ... of a trace with losses: slot 35 of every record is the number of particles alive at that point (a point nobody
+// reaches: count 0 and, by write_moment_record's divisions, NaN moments).
+template <typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_trace_finalize_counted(const double* __restrict__ slabs,
+                                                                    const T* __restrict__ ref, int waves, int P,
+                                                                    double* __restrict__ out) {
+  trace_finalize_body<T, THREADS, true>(slabs, ref, waves, P, 0, out);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -63,6 +63,7 @@ class Program:
     steps: list = field(default_factory=list)   # (kind, first, last) over `leaves`
     raw: bool = False  # runs take their first map as is (Element.track), see LYNX_STEP_FLAG_RAW
     observers: list = field(default_factory=list)  # (step index, element): active BPMs read inside the pass
+    apertures: list = field(default_factory=list)  # (step index, element, elliptical): active apertures of a trace with losses
 
     def add_run_element(self, element, new_run: bool):
         idx = len(self.leaves)
@@ -475,12 +476,15 @@ def track(owner, elements, incoming, raw: bool = False):
 # -------------------------------------------------------------------------------------------
 
 
-def trace_program(leaves) -> Program:
+def trace_program(leaves, losses: bool = False) -> Program:
     """
     The lattice with every leaf element a step of its own, as the loop of the reference's `plot_twiss` tracks it
     (`element.track(beam)`: the element's OWN map, taken as it is -- LYNX_STEP_FLAG_RAW; an active cavity by
     `Cavity._track_beam`).  An active BPM is an identity element whose reading comes from the trace, so the observer
-    limit of `Segment.track` does not apply; an active Screen or Aperture has no place inside one streaming pass.
+    limit of `Segment.track` does not apply; an active Screen has no place inside one streaming pass, and neither has
+    an active Aperture unless the trace carries particle losses: with `losses` it is an identity step of its own, like an
+    inactive one, and `program.apertures` remembers its step index and its shape (the kernel clears the particles
+    outside it from every later point, `lynx_track_particles_along_losses`).
     """
     program = Program(raw=True)
     for el in leaves:
@@ -488,37 +492,70 @@ def trace_program(leaves) -> Program:
             program.add_run_element(el, True)
         elif el._kind == _ffi.KIND_CAVITY:
             program.add_cavity(el)
+        elif losses and hasattr(el, "_transform"):  # active Aperture
+            assert el.shape in ["rectangular", "elliptical"], f"Unknown aperture shape {el.shape}"
+            program.apertures.append((len(program.steps), el, el.shape == "elliptical"))
+            program.add_run_element(el, True)
         else:
+            hint = " (pass losses=True to have the trace carry the particle losses)" if hasattr(el, "_transform") else ""
             raise NotImplementedError(
                 f"track_along: active {type(el).__name__} {el.name!r} -- a lattice with an active Screen or Aperture is "
-                "not traced in one pass; trace the stretches on either side of it")
+                f"not traced in one pass; trace the stretches on either side of it{hint}")
     return program
 
 
-def _trace_plan(owner, leaves) -> Program:
-    """`trace_program` remembered on `owner` like `plan` remembers the partition of `track`."""
+def _trace_plan(owner, leaves, losses: bool = False) -> Program:
+    """`trace_program` remembered on `owner` like `plan` remembers the partition of `track`, per mode."""
     token = (_late().STRUCTURE[0], tuple(map(id, leaves)))
-    remembered = owner.__dict__.get("_trace_plan")
+    remembered = owner.__dict__.setdefault("_trace_plan", {}).get(bool(losses))
     if remembered is not None and remembered[0] == token:
         return remembered[1]
-    program = trace_program(leaves)
-    owner.__dict__["_trace_plan"] = (token, program)
+    program = trace_program(leaves, bool(losses))
+    owner.__dict__["_trace_plan"][bool(losses)] = (token, program)
     return program
 
 
-def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False):
+def _aperture_limits(owner, program: Program, batch_shape, dtype, rt):
+    """
+    x_max, y_max of the program's active apertures on the device: ([B or 1][A][2] array, scalars between two samples --
+    0 when every limit is shared by the batch).  Remembered on `owner` until a limit is written.
+    """
+    elements = [el for _, el, _ in program.apertures]
+    key = (id(program), tuple(batch_shape), np.dtype(dtype).str, tuple(el._version for el in elements))
+    remembered = owner.__dict__.get("_trace_limits")
+    if remembered is not None and remembered[0] == key:
+        return remembered[1], remembered[2]
+    B = int(np.prod(batch_shape, dtype=np.int64))
+    values = []
+    for el in elements:
+        assert np.all(el.x_max >= 0) and np.all(el.y_max >= 0)  # aperture.py:74-76
+        values += [np.asarray(el.x_max, dtype=dtype), np.asarray(el.y_max, dtype=dtype)]
+    shared = all(v.size == 1 for v in values)
+    rows = [v.reshape(1) if shared else _broadcast_param(v, batch_shape, dtype, "Aperture").reshape(B) for v in values]
+    host = np.ascontiguousarray(np.stack(rows, axis=1).reshape(-1, len(elements), 2)) if rows else np.zeros((1, 1, 2), dtype=dtype)
+    limits = rt.to_device(host)
+    stride = 0 if shared else 2 * len(elements)
+    owner.__dict__["_trace_limits"] = (key, limits, stride)
+    return limits, stride
+
+
+def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False):
     """
     `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
     `lynx_track_moments_along`).  The packed "every element its own step" lattice is cached on `owner` (its own
     LatticeCache: a parameter write between two calls rewrites that element's block only).  `keep_device`: the trace
     keeps the device arrays the kernels wrote (`trace._device`) -- what the reverse pass of `grad.track_along_vjp` reads.
+    `losses` (True or "particles"): active apertures are part of the trace (`lynx_track_particles_along_losses`).
     """
     from .trace import BeamTrace
 
     late = _late()
     ParameterBeam, ParticleBeam = late.ParameterBeam, late.ParticleBeam
     leaves = list(leaves)
-    program = _trace_plan(owner, leaves)  # (raises for an active Screen or Aperture before anything touches the GPU)
+    if not (losses is False or losses is True or losses == "particles"):
+        raise ValueError(f"track_along: losses is False, True or 'particles', not {losses!r}")
+    # (raises for an active Screen -- without `losses` for an active Aperture too -- before anything touches the GPU)
+    program = _trace_plan(owner, leaves, bool(losses))
     if not isinstance(incoming, (ParameterBeam, ParticleBeam)):
         raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
     rt = get_runtime()
@@ -535,15 +572,32 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
         p_in = incoming._particles.device(rt)
         p_out = rt.empty((*batch_shape, n, 7), dtype) if keep_outgoing else None
         records = rt.empty_result((lat.B, P, _ffi.MOMENT_STRIDE), _F64)
-        rt.check(rt.lib.lynx_track_particles_along(
-            rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records),
-            _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0))
+        flags = _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0
+        lost_at = None
+        if losses:
+            A = len(program.apertures)
+            limits, stride = _aperture_limits(owner, program, batch_shape, dtype, rt)
+            pairs = (C.c_int32 * max(2 * A, 1))(*[v for step, _, elliptical in program.apertures for v in (step, int(elliptical))])
+            if losses == "particles":
+                lost_at = rt.empty((lat.B, n), np.int32)  # (4 B N bytes: device memory, read back once)
+            rt.check(rt.lib.lynx_track_particles_along_losses(
+                rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records), flags,
+                A, pairs, _ptr(limits), stride, _ptr(lost_at)))
+        else:
+            rt.check(rt.lib.lynx_track_particles_along(
+                rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records), flags))
         rec = records.numpy().reshape(*batch_shape, P, _ffi.MOMENT_STRIDE)
         energy = e_trace.numpy().reshape(*batch_shape, P)
-        trace = BeamTrace.from_records(rec, energy, lengths, names, dtype)
+        trace = BeamTrace.from_records(rec, energy, lengths, names, dtype,
+                                       apertures=[step for step, _, _ in program.apertures])
         trace.num_particles = n
-        centre = rec[..., :, (0, 2)].astype(dtype)  # mean x, y at every point
+        if lost_at is not None:
+            trace.lost_at = lost_at.numpy().reshape(*batch_shape, n)
+        centre = rec[..., :, (0, 2)].astype(dtype)  # mean x, y at every point (of the particles alive there)
         device = {"records": records}
+        # a beam object has one particle count for all samples: with losses there is none to hand out
+        if keep_outgoing and losses and not np.all(rec[..., -1, 35] == n):
+            keep_outgoing = False
         if keep_outgoing:
             out = ParticleBeam.__new__(ParticleBeam)
             charges = incoming._charges

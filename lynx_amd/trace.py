@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from . import config
 from .particles.beam import Beam
 from .particles.parameter_beam import ParameterBeam
 from .particles.particle_beam import ParticleBeam, _tri
@@ -45,11 +46,19 @@ class BeamTrace(Beam):
     :ivar names: the P - 1 element names; point k lies behind `names[k - 1]`.
     :ivar mu: (*batch, P, 6), :ivar cov: (*batch, P, 6, 6), :ivar energy: (*batch, P).
     :ivar outgoing: the tracked beam (None if it was not kept); its moments are the last point's.
+
+    A particle trace made with `losses` (active apertures inside the trace) also says who is left: `num_survivors`,
+    `transmission`, `apertures`, `lost_in`, `lost_at` (see `ParticleBeamTrace`); they are None for a ParameterBeam.
     """
 
     outgoing = None
     num_particles = None
     total_charge = None
+    num_survivors = None
+    transmission = None
+    apertures = None
+    lost_in = None
+    lost_at = None
 
     def _set_common(self, energy, lengths, names, dtype, batch_shape):
         self.dtype = np.dtype(dtype)
@@ -61,18 +70,22 @@ class BeamTrace(Beam):
         assert len(self.names) == len(self._lengths) == self.num_points - 1
 
     @staticmethod
-    def from_records(records, energy, lengths, names, dtype=np.float32) -> "BeamTrace":
+    def from_records(records, energy, lengths, names, dtype=np.float32, apertures=()) -> "BeamTrace":
         """
         A particle trace from host arrays: `records` (*batch, P, 36) float64 moment records (layout of
         LYNX_MOMENT_STRIDE, include/lynx_hip.h; whole covariance triangle), `energy` (*batch, P), `lengths` the P - 1
-        element lengths (each broadcastable to the batch), `names` the P - 1 element names.
+        element lengths (each broadcastable to the batch), `names` the P - 1 element names.  Slot 35 of a record is the
+        number of particles ITS moments were taken over: it may differ from point to point and from sample to sample
+        (a trace with losses); `apertures`: the indices (into `names`) of the elements that removed particles.
         """
         trace = ParticleBeamTrace.__new__(ParticleBeamTrace)
         trace.records = np.asarray(records, dtype=np.float64)
         assert trace.records.ndim >= 2 and trace.records.shape[-1] == 36, trace.records.shape
         trace._set_common(energy, lengths, names, dtype, trace.records.shape[:-2])
-        n = trace.records[..., 35]
-        trace.num_particles = int(n.flat[0]) if n.size else 0
+        entering = trace.records[..., 0, 35]  # nobody is lost in front of point 0
+        trace.num_particles = int(entering.max()) if entering.size else 0
+        trace._aperture_elements = [int(k) for k in apertures]
+        assert all(0 <= k < trace.num_points - 1 for k in trace._aperture_elements), trace._aperture_elements
         return trace
 
     @staticmethod
@@ -127,13 +140,59 @@ class BeamTrace(Beam):
 
 
 class ParticleBeamTrace(BeamTrace):
-    """Trace of a `ParticleBeam`: one float64 moment record per sample and point (`records`, (*batch, P, 36))."""
+    """
+    Trace of a `ParticleBeam`: one float64 moment record per sample and point (`records`, (*batch, P, 36)).  Every
+    moment of a point is taken over the particles alive there (slot 35 of its record); a point nobody reaches has count
+    0 and NaN moments.
+
+    :ivar num_particles: the incoming N.
+    :ivar lost_at: (*batch, N) int32, the ordinal in `apertures` of the aperture that removed each particle, -1 for a
+        survivor (`losses="particles"`; else None).
+    """
+
+    _aperture_elements = ()
 
     def moment_record(self, covariance: bool = False) -> np.ndarray:
         return self.records
 
-    # the ParticleBeam's own read-out of a record (LYNX_STD_DDOF and all), on (*batch, P) records
-    _mean, _std, _cov = ParticleBeam._mean, ParticleBeam._std, ParticleBeam._cov
+    @property
+    def num_survivors(self) -> np.ndarray:
+        """(*batch, P) int64: the particles alive at every point."""
+        return self.records[..., 35].astype(np.int64)
+
+    @property
+    def transmission(self) -> np.ndarray:
+        """(*batch, P): `num_survivors / num_particles`."""
+        return self.num_survivors / self.num_particles
+
+    @property
+    def apertures(self) -> list:
+        """Names of the active apertures of the trace, in lattice order."""
+        return [self.names[k] for k in self._aperture_elements]
+
+    @property
+    def lost_in(self) -> np.ndarray:
+        """(*batch, A) int64: the particles each aperture removed -- the drop of `num_survivors` across its point."""
+        alive = self.num_survivors
+        k = np.asarray(self._aperture_elements, dtype=np.int64)
+        return alive[..., k] - alive[..., k + 1]
+
+    # the ParticleBeam's own read-out of a record (LYNX_STD_DDOF and all), on (*batch, P) records -- with each record's
+    # own count, and a single particle having no spread: where one particle is left of many, the difference of sums the
+    # record holds is rounding noise of either sign instead of the 0 it stands for (sigma: NaN unbiased, 0 biased)
+    _mean = ParticleBeam._mean
+
+    def _central(self, i: int, j: int) -> np.ndarray:
+        value = self.records[..., _tri(i, j)]
+        return np.where((self.records[..., 35] == 1) & np.isfinite(value), 0.0, value)  # (a NaN stays one)
+
+    def _std(self, c: int) -> np.ndarray:
+        n = self.records[..., 35]
+        with np.errstate(all="ignore"):
+            return np.sqrt(self._central(c, c) * (n / (n - config.std_ddof))).astype(self.dtype)
+
+    def _cov(self, i: int, j: int) -> np.ndarray:
+        return self._central(i, j).astype(self.dtype)
 
     @property
     def mu(self) -> np.ndarray:
@@ -145,7 +204,7 @@ class ParticleBeamTrace(BeamTrace):
         out = np.empty((*self.records.shape[:-1], 6, 6), dtype=self.dtype)
         for i in range(6):
             for j in range(i, 6):
-                out[..., i, j] = out[..., j, i] = self.records[..., _tri(i, j)]
+                out[..., i, j] = out[..., j, i] = self._central(i, j)
         return out
 
 
