@@ -261,6 +261,27 @@ int lynx_track_particles_along_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t 
                                       int32_t n_apertures, const int32_t* apertures, const void* d_limits,
                                       int64_t limit_stride, int32_t* d_lost_at);
 
+/* ... with screens: steps that are ACTIVE screens (reference: screen.py:126-141, 196-213, where the screen swallows the
+ * beam and histograms the stored particles on read) count the particles that ENTER them into an image and let them
+ * through.  Arguments as above -- n_apertures may be 0: the records are then lynx_track_particles_along's and d_lost_at,
+ * if given, is -1 everywhere -- and
+ *   screens          host [n_screens][3]: step index (increasing, no aperture's step; the step itself is an identity step
+ *                    of the program), nx, ny >= 1 (the image is ny rows of nx pixels)
+ *   d_edges          per screen the nx + 1 x edges, then the ny + 1 y edges, in the lattice's dtype (increasing)
+ *   d_misalignment   [B][n_screens][2] (misalignment_stride = 2 n_screens) or [n_screens][2] shared by the batch
+ *                    (misalignment_stride = 0), lattice dtype; x - misalignment[0] is binned (the reference takes the
+ *                    second component off x', screen.py:134-135: no image sees it)
+ *   d_images         [B][sum of ny nx] int32, screen after screen: flipud(histogramdd((x, y), edges).T) of the particles
+ *                    alive at point `step` -- numpy's bin rule on the very edge values (the last edge belongs to the last
+ *                    bin, values outside are dropped), exact integer counts: the same call returns the same bits
+ * A particle an aperture has removed is in no later image, whatever its coordinates have become.                      */
+int lynx_track_particles_along_screens(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                       const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                       int32_t n_apertures, const int32_t* apertures, const void* d_limits,
+                                       int64_t limit_stride, int32_t* d_lost_at, int32_t n_screens, const int32_t* screens,
+                                       const void* d_edges, const void* d_misalignment, int64_t misalignment_stride,
+                                       int32_t* d_images);
+
 /* ... of a ParameterBeam (reference: the same loop; element.py:71-82 mu' = T mu, cov' = T cov T^T per element,
  * cavity.py:134-140,202-218): d_mu_trace [B][P][7], d_cov_trace [B][P][7][7], d_energy_trace [B][P].              */
 int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
@@ -351,6 +372,17 @@ int lynx_histogram2d(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particle
  * d_cov [B][7][7]; d_image [B][nx][ny] with the x axis flipped, as the reference returns it. */
 int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_mu, const void* d_cov,
                         const void* d_xs, const void* d_ys, int32_t nx, int32_t ny, void* d_image);
+
+/* ... of a ParameterBeam at screens inside a trace: lynx_gaussian_image's formula on mu, cov of point `point` of
+ * lynx_track_moments_along's d_mu_trace [B][n_points][7], d_cov_trace [B][n_points][7][7], with mu_x - misalignment[0],
+ * mu_y - misalignment[1] (formed in `dtype`).
+ *   screens          host [n_screens][3]: point, nx, ny >= 1
+ *   d_grid           per screen the nx pixel centres xs, then the ny centres ys
+ *   d_misalignment   [B][n_screens][2] (misalignment_stride = 2 n_screens) or [n_screens][2] (misalignment_stride = 0)
+ *   d_images         [B][sum of nx ny], screen after screen, each [nx][ny] in lynx_gaussian_image's layout           */
+int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
+                               const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
+                               const void* d_misalignment, int64_t misalignment_stride, void* d_images);
 
 /* Test hook: the float32 sine / cosine the cavity kick uses on the device (cavity.py:141-161
  * calls cos per particle), scalar (packed = 0) or two-per-lane (packed = 1) code path.        */

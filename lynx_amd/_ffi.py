@@ -93,6 +93,9 @@ SIGNATURES = {
     "lynx_track_particles_along": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i]),
     "lynx_track_particles_along_losses": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, C.c_int32,
                                                C.POINTER(C.c_int32), _vp, _i64, _vp]),
+    "lynx_track_particles_along_screens": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, C.c_int32,
+                                                C.POINTER(C.c_int32), _vp, _i64, _vp, C.c_int32, C.POINTER(C.c_int32),
+                                                _vp, _vp, _i64, _vp]),
     "lynx_track_moments_along": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_track_moments_along_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_track_particles_along_backward": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -101,6 +104,8 @@ SIGNATURES = {
     "lynx_moments": (_i, [_vp, _i, _i64, _i64, _vp, _vp, C.c_int32]),
     "lynx_histogram2d": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "lynx_gaussian_image": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
+    "lynx_gaussian_images_along": (_i, [_vp, _i, _i64, C.c_int32, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), _vp, _vp,
+                                        _i64, _vp]),
     "lynx_diag_phase_trig": (_i, [_vp, _i64, _vp, C.c_int32, _vp, _vp]),
     "lynx_aperture_mask": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "lynx_aperture_compact": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),

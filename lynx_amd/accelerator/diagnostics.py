@@ -306,6 +306,11 @@ class Screen(Element):
         self._read_beam = value
         self._cached_reading = None
 
+    def _reading_from_trace(self, image) -> None:
+        """`Segment.track_along(..., screens=True)`: the image was made inside the trace; there is no read beam."""
+        self._read_beam = None
+        self._cached_reading = image
+
     # -- read-out (screen.py:143-216) ----------------------------------------------------------
     @property
     def reading(self) -> np.ndarray:

@@ -199,7 +199,7 @@ class Segment(Element):
         """segment.py:340-356."""
         return engine.track(self, self.elements, incoming)
 
-    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True, losses=False):
+    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True, losses=False, screens: bool = False):
         """
         The beam ALONG the lattice: its moments and energy at the entrance and behind every leaf element (nested
         segments opened up), for every batch sample, from one pass over the particles -- the data behind the reference's
@@ -215,11 +215,21 @@ class Segment(Element):
         there (count 0: NaN); `outgoing` is the tracked beam if no sample lost a particle and None otherwise.
         `losses="particles"` also brings back `lost_at` (*batch, N): which aperture removed each particle, -1 for a
         survivor.  A `ParameterBeam` passes active apertures unchanged (aperture.py:70-72) and has no loss attributes.
+
+        An active `Screen` is refused unless `screens=True`.  Then screen k makes its image of the beam that enters it
+        (point k) and lets the beam through -- inside the trace a screen is a diagnostic, like an active BPM, and there
+        may be several; `Segment.track` keeps the reference's semantics, where an active screen swallows the beam and
+        everything behind it sees `Beam.empty`.  A `ParticleBeam`'s image is the reference's histogram (screen.py:196-213,
+        `x - misalignment_x` binned by numpy's rule on `pixel_bin_edges`) of the particles ALIVE at point k, so with
+        `losses` a screen behind a collimator shows the collimated beam; a `ParameterBeam`'s is the bivariate normal
+        density of `mu`, `cov` at point k less the misalignment, which apertures do not touch.  The trace has `screens`,
+        `screen_images`, `image_at(name_or_index)`; every active screen's `reading` returns its image afterwards (the same
+        array; `get_read_beam()` is None).  Inactive screens make no image.
         """
         if resolution is not None:
             return Segment(self.split(resolution), name=self.name).track_along(incoming, keep_outgoing=keep_outgoing,
-                                                                               losses=losses)
-        return engine.track_along(self, self._leaves(), incoming, keep_outgoing, losses=losses)
+                                                                               losses=losses, screens=screens)
+        return engine.track_along(self, self._leaves(), incoming, keep_outgoing, losses=losses, screens=screens)
 
     def forward(self, incoming):
         return self.track(incoming)

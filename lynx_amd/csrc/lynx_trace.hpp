@@ -24,6 +24,11 @@
 // aperture is an identity step that clears the `live` bit of the particles outside it: nothing is compacted, a lost
 // particle stays in its lane and is kept out of every later sum by a select, and the number of particles a record
 // stands for is the point's own sum of the 7th coordinate (slot 6 of the slab row) instead of N.
+//
+// With screens (lynx_track_particles_along_screens; k_trace_particles_screens) an active screen is an identity step too:
+// the particles alive where it stands are binned by numpy's rule on the screen's own edge arrays (bin_of's result, from
+// an arithmetic guess corrected against the neighbouring edges) and counted into the screen's image with integer
+// atomics -- there, because the particles of an interior point exist in registers only.
 #pragma once
 
 #include "lynx_device.hpp"
@@ -51,6 +56,19 @@ struct TraceLosses {
   int32_t* lost_at;      // [B][N], -1 everywhere before the launch: a particle's cell is written when (and if) an aperture
                          // removes it, with the aperture's ordinal (keeping the ordinals in registers until the end of
                          // the tile costs the float32 kernel its third wave per SIMD); or null
+};
+
+// The screens of a trace.  `plan`: [S] step codes, then [K][4] per screen.  A step's code is -1, (ordinal of the aperture
+// << 2) | (elliptical << 1) for an active aperture, (ordinal of the screen << 2) | 1 for an active screen; a screen's row
+// is nx, ny, the first scalar of its edges in `edges` (x edges, nx + 1 of them, then y edges), the first cell of its
+// image in a sample's row of `images`.
+struct TraceScreens {
+  const int64_t* plan;
+  const void* edges;          // lattice dtype
+  const void* misalignment;   // [B or 1][K][2], lattice dtype
+  int64_t misalignment_stride;  // scalars between the samples of `misalignment`: 2 K, or 0
+  int32_t* images;            // [B][cells] int32, zero before the launch
+  int64_t cells;              // sum over the screens of ny nx
 };
 
 // ---------------------------------------------------------------------------------------
@@ -249,10 +267,8 @@ __device__ __forceinline__ void trace_point(const double (&z)[U][7], const doubl
 // load), the particles whose coordinates ENTERING it lie outside are dead from the next point on.  The comparison is
 // k_aperture_mask's own (aperture_survives<T>, aperture.py:78-86).
 template <typename T, int U, typename X>
-__device__ __forceinline__ void trace_aperture(const TraceLosses& loss, const T* __restrict__ limits /* of this sample */,
-                                               int s, X&& xy, bool (&live)[U], int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
-  const int code = __builtin_amdgcn_readfirstlane(loss.codes[s]);
-  if (code < 0) return;
+__device__ __forceinline__ void trace_aperture_coded(int code /* uniform, >= 0 */, const T* __restrict__ limits /* of this sample */,
+                                                     X&& xy, bool (&live)[U], int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
   const int ordinal = code >> 1;
   const T xm = uniform_value(limits[ordinal * 2]), ym = uniform_value(limits[ordinal * 2 + 1]);
 #pragma unroll
@@ -264,15 +280,71 @@ __device__ __forceinline__ void trace_aperture(const TraceLosses& loss, const T*
     live[u] = live[u] && !out;
   }
 }
+template <typename T, int U, typename X>
+__device__ __forceinline__ void trace_aperture(const TraceLosses& loss, const T* __restrict__ limits /* of this sample */,
+                                               int s, X&& xy, bool (&live)[U], int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
+  const int code = __builtin_amdgcn_readfirstlane(loss.codes[s]);
+  if (code < 0) return;
+  trace_aperture_coded<T, U>(code, limits, xy, live, tile_lost_at, lane);
+}
+
+// The bin of v among n bins with the edges `edges` [n + 1], by numpy.histogramdd's rule: the number of edges <= v, minus
+// one; the last edge belongs to the last bin; -1 outside (and for NaN).  bin_of's result without its bisection: the
+// edges of a screen are evenly spaced, so (v - first edge) * bins / extent is the bin or one of its neighbours, and the
+// comparisons with the very edge values decide -- two loads per axis where the guess holds, any number where it does not.
+template <typename T>
+__device__ __forceinline__ int screen_bin(const T* __restrict__ edges, int n, T first, T last, T per_unit, T v) {
+  if (!(v >= first) || !(v <= last)) return -1;
+  int i = (int)((v - first) * per_unit);
+  i = min(max(i, 0), n - 1);
+  while (i > 0 && v < edges[i]) --i;
+  while (i < n - 1 && v >= edges[i + 1]) ++i;
+  return i;
+}
+
+// Step s of a trace with screens, after point s has been deposited, if the step is screen `ordinal` (wave-uniform): the
+// particles alive ENTERING it are counted into its image, flipud(histogramdd((x - misalignment_x, y)).T) of
+// screen.py:196-213 (Screen._observe takes the y misalignment off x', which no image sees).  A dead particle is left out
+// because it is dead, whatever its coordinates have become.
+template <typename T, int U, typename X>
+__device__ __forceinline__ void trace_screen(const TraceScreens& scr, int S, int ordinal, int64_t b, X&& xy, const bool (&live)[U]) {
+  const int64_t* row = scr.plan + S + 4 * (int64_t)ordinal;
+  const int nx = __builtin_amdgcn_readfirstlane((int)row[0]), ny = __builtin_amdgcn_readfirstlane((int)row[1]);
+  const T* xe = static_cast<const T*>(scr.edges) + row[2];
+  const T* ye = xe + nx + 1;
+  int32_t* img = scr.images + b * scr.cells + row[3];
+  const T shift = uniform_value(static_cast<const T*>(scr.misalignment)[b * scr.misalignment_stride + 2 * ordinal]);
+  const T x_first = uniform_value(xe[0]), x_last = uniform_value(xe[nx]), y_first = uniform_value(ye[0]), y_last = uniform_value(ye[ny]);
+  const T x_per_unit = T(nx) / (x_last - x_first), y_per_unit = T(ny) / (y_last - y_first);
+  T px[U], py[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) xy(u, px[u], py[u]);
+  // one particle at a time, picked by a uniform index: unrolled U times, the searches of all U particles were live
+  // at once and took the float32 kernel its third wave per SIMD
+#pragma nounroll
+  for (int u = 0; u < U; ++u) {
+    T x = px[0], y = py[0];
+    bool alive = live[0];
+#pragma unroll
+    for (int q = 1; q < U; ++q)
+      if (u == q) x = px[q], y = py[q], alive = live[q];
+    if (!alive) continue;
+    const int ix = screen_bin<T>(xe, nx, x_first, x_last, x_per_unit, x - shift);
+    const int iy = screen_bin<T>(ye, ny, y_first, y_last, y_per_unit, y);
+    if (ix >= 0 && iy >= 0) atomicAdd(img + (int64_t)(ny - 1 - iy) * nx + ix, 1);  // (no return value: one global_atomic_add)
+  }
+}
 
 // one tile of a wave through the whole lattice
-template <typename T, int U, bool MASKED, bool LOSSES = false>
+template <typename T, int U, bool MASKED, bool LOSSES = false, bool SCREENS = false>
 __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* __restrict__ steps /* of this sample */,
                                            const T* __restrict__ ref /* of this sample */, const T* __restrict__ src,
                                            T* __restrict__ dst, int64_t base, int lane, bool first,
                                            double* __restrict__ slab /* of this wave */, const TraceLosses& loss = TraceLosses{},
-                                           const T* __restrict__ limits = nullptr, int32_t* __restrict__ lost_at = nullptr) {
+                                           const T* __restrict__ limits = nullptr, int32_t* __restrict__ lost_at = nullptr,
+                                           const TraceScreens& scr = TraceScreens{}, int64_t b = 0) {
   static_assert(MASKED || !LOSSES, "a trace with losses always takes the masked path");
+  static_assert(LOSSES || !SCREENS, "a trace with screens takes the path of the losses (its apertures may be none)");
   bool live[U];
   T z[U][7];
 #pragma unroll
@@ -294,7 +366,17 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
     for (int s = 0; s <= S; ++s) {
       trace_point<U, MASKED>(zp, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
       if (s == S) break;
-      if constexpr (LOSSES)
+      if constexpr (SCREENS) {  // one code per step says aperture or screen (wave-uniform)
+        auto xy = [&](int u, T& x, T& y) {
+          x = (u & 1) ? zp[u / 2][0].y : zp[u / 2][0].x;
+          y = (u & 1) ? zp[u / 2][2].y : zp[u / 2][2].x;
+        };
+        const int code = __builtin_amdgcn_readfirstlane((int)scr.plan[s]);
+        if (code >= 0) {
+          if (code & 1) trace_screen<T, U>(scr, S, code >> 2, b, xy, live);
+          else trace_aperture_coded<T, U>(code >> 1, limits, xy, live, lost_at ? lost_at + base : nullptr, lane);
+        }
+      } else if constexpr (LOSSES)
         trace_aperture<T, U>(loss, limits, s, [&](int u, T& x, T& y) {
           x = (u & 1) ? zp[u / 2][0].y : zp[u / 2][0].x;
           y = (u & 1) ? zp[u / 2][2].y : zp[u / 2][2].x;
@@ -342,7 +424,17 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
     for (int s = 0; s <= S; ++s) {
       trace_point<U, MASKED>(z, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
       if (s == S) break;
-      if constexpr (LOSSES)
+      if constexpr (SCREENS) {
+        auto xy = [&](int u, T& x, T& y) {
+          x = z[u][0];
+          y = z[u][2];
+        };
+        const int code = __builtin_amdgcn_readfirstlane((int)scr.plan[s]);
+        if (code >= 0) {
+          if (code & 1) trace_screen<T, U>(scr, S, code >> 2, b, xy, live);
+          else trace_aperture_coded<T, U>(code >> 1, limits, xy, live, lost_at ? lost_at + base : nullptr, lane);
+        }
+      } else if constexpr (LOSSES)
         trace_aperture<T, U>(loss, limits, s, [&](int u, T& x, T& y) {
           x = z[u][0];
           y = z[u][2];
@@ -433,6 +525,39 @@ __global__ __launch_bounds__(256) void k_trace_particles_losses(TraceArgs a, int
     const int64_t base = begin + t * kTile;
     if (base >= a.n_particles) break;
     trace_tile<T, U, true, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at);
+  }
+}
+
+// ... with active screens (TraceScreens), and with the apertures of `loss` if there are any (their codes are in the
+// screens' plan; loss.codes is not read): the walk of k_trace_particles_losses.
+template <typename T, int U>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : 4))) void k_trace_particles_screens(TraceArgs a, int S, const T* __restrict__ steps,
+                                                                 const T* __restrict__ ref, const T* __restrict__ p_in,
+                                                                 T* __restrict__ p_out, double* __restrict__ slabs,
+                                                                 TraceLosses loss, TraceScreens scr) {
+  const int wgs = a.waves / 4;
+  const int64_t b = blockIdx.x / wgs;
+  const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int P = S + 1;
+  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const T* sample_ref = ref + b * (int64_t)P * kTraceRef;
+  const T* src = p_in + b * a.in_stride;
+  T* dst = p_out + b * a.n_particles * 7;
+  double* slab = slabs + (b * a.waves + w) * (int64_t)P * kTraceSlab;
+  const T* limits = static_cast<const T*>(loss.limits) + b * loss.limit_stride;
+  int32_t* lost_at = loss.lost_at ? loss.lost_at + b * a.n_particles : nullptr;
+  constexpr int64_t kTile = 64 * U;
+  const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
+  if (begin >= a.n_particles) {
+    for (int64_t i = lane; i < (int64_t)P * kTraceSlab; i += 64) slab[i] = 0.0;
+    return;
+  }
+  for (int t = 0; t < a.tiles_per_wave; ++t) {
+    const int64_t base = begin + t * kTile;
+    if (base >= a.n_particles) break;
+    trace_tile<T, U, true, true, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at,
+                                       scr, b);
   }
 }
 
@@ -657,6 +782,31 @@ __global__ __launch_bounds__(64) void k_trace_moments_lanes(LatticeDev lat, cons
       C[5 * 7 + 4] = v;
     }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_gaussian_image_along: the image of a ParameterBeam on a screen inside the trace -- k_gaussian_image's formula
+// (screen.py:160-195) on mu, cov of ONE point of the moment trace, mu_x and mu_y less the screen's misalignment
+// (Screen._observe, formed in the lattice's dtype), one thread per pixel; the image is [nx][ny] at `image` + b * cells.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void k_gaussian_image_along(const T* __restrict__ mu_trace, const T* __restrict__ cov_trace,
+                                                              int P, int point, const T* __restrict__ xs, const T* __restrict__ ys,
+                                                              int nx, int ny, const T* __restrict__ misalignment /* of this screen */,
+                                                              int64_t misalignment_stride, T* __restrict__ image, int64_t cells) {
+  const int64_t b = blockIdx.y;
+  const int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pix >= (int64_t)nx * ny) return;
+  const int i = (int)(pix / ny), j = (int)(pix % ny);
+  const T* mu = mu_trace + (b * P + point) * 7;
+  const T* cov = cov_trace + (b * P + point) * 49;
+  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
+  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
+  const T det = a * c - bb * bb;
+  const T dx = xs[i] - mx, dy = ys[j] - my;
+  const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
+  const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
+  image[b * cells + (int64_t)(nx - 1 - i) * ny + j] = (T)exp((double)logp);
 }
 
 }  // namespace lynx

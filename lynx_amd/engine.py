@@ -64,6 +64,7 @@ class Program:
     raw: bool = False  # runs take their first map as is (Element.track), see LYNX_STEP_FLAG_RAW
     observers: list = field(default_factory=list)  # (step index, element): active BPMs read inside the pass
     apertures: list = field(default_factory=list)  # (step index, element, elliptical): active apertures of a trace with losses
+    screens: list = field(default_factory=list)  # (step index, element): active screens of a trace with screens
 
     def add_run_element(self, element, new_run: bool):
         idx = len(self.leaves)
@@ -476,7 +477,7 @@ def track(owner, elements, incoming, raw: bool = False):
 # -------------------------------------------------------------------------------------------
 
 
-def trace_program(leaves, losses: bool = False) -> Program:
+def trace_program(leaves, losses: bool = False, screens: bool = False) -> Program:
     """
     The lattice with every leaf element a step of its own, as the loop of the reference's `plot_twiss` tracks it
     (`element.track(beam)`: the element's OWN map, taken as it is -- LYNX_STEP_FLAG_RAW; an active cavity by
@@ -484,7 +485,9 @@ def trace_program(leaves, losses: bool = False) -> Program:
     limit of `Segment.track` does not apply; an active Screen has no place inside one streaming pass, and neither has
     an active Aperture unless the trace carries particle losses: with `losses` it is an identity step of its own, like an
     inactive one, and `program.apertures` remembers its step index and its shape (the kernel clears the particles
-    outside it from every later point, `lynx_track_particles_along_losses`).
+    outside it from every later point, `lynx_track_particles_along_losses`).  With `screens` an active Screen is an
+    identity step of its own as well, `program.screens` remembers its step index, and the pass makes its image of the beam
+    entering it (`lynx_track_particles_along_screens`, `lynx_gaussian_images_along`).
     """
     program = Program(raw=True)
     for el in leaves:
@@ -496,22 +499,27 @@ def trace_program(leaves, losses: bool = False) -> Program:
             assert el.shape in ["rectangular", "elliptical"], f"Unknown aperture shape {el.shape}"
             program.apertures.append((len(program.steps), el, el.shape == "elliptical"))
             program.add_run_element(el, True)
+        elif screens and getattr(el, "_swallows_beam", False):  # active Screen
+            program.screens.append((len(program.steps), el))
+            program.add_run_element(el, True)
         else:
-            hint = " (pass losses=True to have the trace carry the particle losses)" if hasattr(el, "_transform") else ""
+            hint = (" (pass losses=True to have the trace carry the particle losses)" if hasattr(el, "_transform")
+                    else " (pass screens=True to have the trace make the screen images)" if getattr(el, "_swallows_beam", False) else "")
             raise NotImplementedError(
                 f"track_along: active {type(el).__name__} {el.name!r} -- a lattice with an active Screen or Aperture is "
                 f"not traced in one pass; trace the stretches on either side of it{hint}")
     return program
 
 
-def _trace_plan(owner, leaves, losses: bool = False) -> Program:
-    """`trace_program` remembered on `owner` like `plan` remembers the partition of `track`, per mode."""
+def _trace_plan(owner, leaves, losses: bool = False, screens: bool = False) -> Program:
+    """`trace_program` remembered on `owner` like `plan` remembers the partition of `track`, per (losses, screens) mode."""
     token = (_late().STRUCTURE[0], tuple(map(id, leaves)))
-    remembered = owner.__dict__.setdefault("_trace_plan", {}).get(bool(losses))
+    mode = (bool(losses), bool(screens))
+    remembered = owner.__dict__.setdefault("_trace_plan", {}).get(mode)
     if remembered is not None and remembered[0] == token:
         return remembered[1]
-    program = trace_program(leaves, bool(losses))
-    owner.__dict__["_trace_plan"][bool(losses)] = (token, program)
+    program = trace_program(leaves, *mode)
+    owner.__dict__["_trace_plan"][mode] = (token, program)
     return program
 
 
@@ -539,13 +547,71 @@ def _aperture_limits(owner, program: Program, batch_shape, dtype, rt):
     return limits, stride
 
 
-def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False):
+def _screen_geometry(owner, program: Program, batch_shape, dtype, rt, particles: bool):
+    """
+    What the device needs to know about the program's active screens, remembered on `owner` until a screen setting or a
+    misalignment is written: the host rows [K][3] (step -- which is the point the screen observes --, then the image's
+    two sizes), the pixel grid on the device, the misalignments [B or 1][K][2] and the scalars between two samples of
+    them (0: shared by the batch), the image shapes and the cells of one sample's images.  For a ParticleBeam the grid is
+    every screen's `pixel_bin_edges` in the lattice's dtype (x edges, then y edges) and an image is (ny, nx); for a
+    ParameterBeam it is the pixel positions `Screen.reading` evaluates the density at (xs, then ys), an image (len(xs),
+    len(ys)).
+    """
+    elements = [el for _, el in program.screens]
+    key = (tuple((step, id(el), el._version) for step, el in program.screens), tuple(batch_shape), np.dtype(dtype).str, bool(particles))
+    remembered = owner.__dict__.get("_trace_screens")
+    if remembered is not None and remembered[0] == key:
+        return remembered[1]
+    B = int(np.prod(batch_shape, dtype=np.int64))
+    rows, grid, shapes, shifts = [], [], [], []
+    for (step, el) in program.screens:
+        if particles:
+            xe, ye = (np.ascontiguousarray(e.astype(dtype)) for e in el.pixel_bin_edges)
+            nx, ny = len(xe) - 1, len(ye) - 1
+            shapes.append((ny, nx))
+            grid += [xe, ye]
+        else:  # (the very expressions of `Screen.reading`)
+            e = el.extent.astype(dtype)
+            pitch = (el.pixel_size * el.binning).astype(dtype)
+            xs, ys = np.arange(e[0], e[1], pitch[0], dtype=dtype), np.arange(e[2], e[3], pitch[1], dtype=dtype)
+            nx, ny = len(xs), len(ys)
+            shapes.append((nx, ny))
+            grid += [xs, ys]
+        assert nx >= 1 and ny >= 1, f"Screen {el.name!r} has no pixels"
+        rows += [step, nx, ny]
+        shifts.append(np.asarray(el.misalignment, dtype=dtype))
+    shared = all(v.size == 2 for v in shifts)
+    shifts = [v.reshape(1, 2) if shared else _broadcast_param(v, (*batch_shape, 2), dtype, "Screen").reshape(B, 2) for v in shifts]
+    geometry = {
+        "rows": (C.c_int32 * len(rows))(*rows), "count": len(elements), "shapes": shapes,
+        "cells": int(sum(a * b for a, b in shapes)),
+        "grid": rt.to_device(np.ascontiguousarray(np.concatenate(grid))),
+        "misalignment": rt.to_device(np.ascontiguousarray(np.stack(shifts, axis=1))),
+        "stride": 0 if shared else 2 * len(elements),
+    }
+    owner.__dict__["_trace_screens"] = (key, geometry)
+    return geometry
+
+
+def _screen_images(flat, geometry, batch_shape, dtype):
+    """One array per screen out of the [B][cells] the device wrote, in the dtype `Screen.reading` returns."""
+    images, first = [], 0
+    for shape in geometry["shapes"]:
+        cells = shape[0] * shape[1]
+        images.append(np.ascontiguousarray(flat[:, first:first + cells]).reshape(*batch_shape, *shape).astype(dtype, copy=False))
+        first += cells
+    return images
+
+
+def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False, screens: bool = False):
     """
     `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
     `lynx_track_moments_along`).  The packed "every element its own step" lattice is cached on `owner` (its own
     LatticeCache: a parameter write between two calls rewrites that element's block only).  `keep_device`: the trace
     keeps the device arrays the kernels wrote (`trace._device`) -- what the reverse pass of `grad.track_along_vjp` reads.
     `losses` (True or "particles"): active apertures are part of the trace (`lynx_track_particles_along_losses`).
+    `screens`: active screens are part of the trace and make their images inside it (`lynx_track_particles_along_screens`,
+    with the apertures if `losses`; `lynx_gaussian_images_along` on the moment trace of a ParameterBeam).
     """
     from .trace import BeamTrace
 
@@ -554,8 +620,8 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     leaves = list(leaves)
     if not (losses is False or losses is True or losses == "particles"):
         raise ValueError(f"track_along: losses is False, True or 'particles', not {losses!r}")
-    # (raises for an active Screen -- without `losses` for an active Aperture too -- before anything touches the GPU)
-    program = _trace_plan(owner, leaves, bool(losses))
+    # (raises for an active Screen without `screens`, for an active Aperture without `losses`, before anything touches the GPU)
+    program = _trace_plan(owner, leaves, bool(losses), bool(screens))
     if not isinstance(incoming, (ParameterBeam, ParticleBeam)):
         raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
     rt = get_runtime()
@@ -574,7 +640,20 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
         records = rt.empty_result((lat.B, P, _ffi.MOMENT_STRIDE), _F64)
         flags = _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0
         lost_at = None
-        if losses:
+        shots, images = (_screen_geometry(owner, program, batch_shape, dtype, rt, True) if program.screens else None), []
+        if shots is not None:
+            A = len(program.apertures) if losses else 0
+            limits, stride = _aperture_limits(owner, program, batch_shape, dtype, rt) if A else (None, 0)
+            pairs = (C.c_int32 * max(2 * A, 1))(*[v for step, _, elliptical in program.apertures for v in (step, int(elliptical))])
+            if losses == "particles":
+                lost_at = rt.empty((lat.B, n), np.int32)
+            counts = rt.empty((lat.B, shots["cells"]), np.int32)  # (zeroed by the call, on its stream)
+            rt.check(rt.lib.lynx_track_particles_along_screens(
+                rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records), flags,
+                A, pairs, _ptr(limits), stride, _ptr(lost_at), shots["count"], shots["rows"], _ptr(shots["grid"]),
+                _ptr(shots["misalignment"]), shots["stride"], _ptr(counts)))
+            images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
+        elif losses:
             A = len(program.apertures)
             limits, stride = _aperture_limits(owner, program, batch_shape, dtype, rt)
             pairs = (C.c_int32 * max(2 * A, 1))(*[v for step, _, elliptical in program.apertures for v in (step, int(elliptical))])
@@ -589,7 +668,8 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
         rec = records.numpy().reshape(*batch_shape, P, _ffi.MOMENT_STRIDE)
         energy = e_trace.numpy().reshape(*batch_shape, P)
         trace = BeamTrace.from_records(rec, energy, lengths, names, dtype,
-                                       apertures=[step for step, _, _ in program.apertures])
+                                       apertures=[step for step, _, _ in program.apertures],
+                                       screens=[step for step, _ in program.screens], screen_images=images)
         trace.num_particles = n
         if lost_at is not None:
             trace.lost_at = lost_at.numpy().reshape(*batch_shape, n)
@@ -612,10 +692,19 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
         rt.check(rt.lib.lynx_track_moments_along(
             rt.ctx, lat.handle, _ptr(e_in), _ptr(incoming._mu_d.device(rt)), _ptr(incoming._cov_d.device(rt)),
             _ptr(mu_t), _ptr(cov_t), _ptr(e_trace)))
+        images = []
+        if program.screens:  # from the trace arrays where the kernels wrote them, before they are read back
+            shots = _screen_geometry(owner, program, batch_shape, dtype, rt, False)
+            density = rt.empty((lat.B, shots["cells"]), dtype)
+            rt.check(rt.lib.lynx_gaussian_images_along(
+                rt.ctx, dtype_code(dtype), lat.B, P, _ptr(mu_t), _ptr(cov_t), shots["count"], shots["rows"], _ptr(shots["grid"]),
+                _ptr(shots["misalignment"]), shots["stride"], _ptr(density)))
+            images = _screen_images(density.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
         mu = mu_t.numpy().reshape(*batch_shape, P, 7)
         cov = cov_t.numpy().reshape(*batch_shape, P, 7, 7)
         energy = e_trace.numpy().reshape(*batch_shape, P)
-        trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype)
+        trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype,
+                                       screens=[step for step, _ in program.screens], screen_images=images)
         centre = mu[..., :, (0, 2)]
         device = {"mu": mu_t, "cov": cov_t}
         if keep_outgoing:
@@ -630,6 +719,8 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     for k, el in enumerate(leaves):  # an active BPM reads the beam that ENTERS it: point k (bpm.py:48-54)
         if getattr(el, "_fusable_observer", False):
             el.reading = np.stack([centre[..., k, 0], centre[..., k, 1]]).astype(dtype)
+    for (_, el), image in zip(program.screens, trace.screen_images):  # ... and so does an active screen
+        el._reading_from_trace(image)
     return trace
 
 

@@ -49,6 +49,11 @@ class BeamTrace(Beam):
 
     A particle trace made with `losses` (active apertures inside the trace) also says who is left: `num_survivors`,
     `transmission`, `apertures`, `lost_in`, `lost_at` (see `ParticleBeamTrace`); they are None for a ParameterBeam.
+
+    A trace made with `screens` (active screens inside the trace) holds their images: `screens`, the points the screens
+    observe in lattice order -- a screen sees the beam that ENTERS it, so screen element k (`names[k]`) observes point k --
+    and `screen_images`, one array per screen in the layout and dtype of `Screen.reading` (a list: resolutions differ);
+    `image_at` finds one of them.  Both lists are empty for a trace without screens.
     """
 
     outgoing = None
@@ -59,6 +64,14 @@ class BeamTrace(Beam):
     apertures = None
     lost_in = None
     lost_at = None
+    screens = ()
+    screen_images = ()
+
+    def _set_screens(self, screens, screen_images):
+        self.screens = [int(k) for k in screens]
+        self.screen_images = list(screen_images)
+        assert len(self.screens) == len(self.screen_images), (self.screens, len(self.screen_images))
+        assert all(0 <= k < self.num_points - 1 for k in self.screens), self.screens  # (a screen is an element: never the last point)
 
     def _set_common(self, energy, lengths, names, dtype, batch_shape):
         self.dtype = np.dtype(dtype)
@@ -70,13 +83,15 @@ class BeamTrace(Beam):
         assert len(self.names) == len(self._lengths) == self.num_points - 1
 
     @staticmethod
-    def from_records(records, energy, lengths, names, dtype=np.float32, apertures=()) -> "BeamTrace":
+    def from_records(records, energy, lengths, names, dtype=np.float32, apertures=(), screens=(), screen_images=()) -> "BeamTrace":
         """
         A particle trace from host arrays: `records` (*batch, P, 36) float64 moment records (layout of
         LYNX_MOMENT_STRIDE, include/lynx_hip.h; whole covariance triangle), `energy` (*batch, P), `lengths` the P - 1
         element lengths (each broadcastable to the batch), `names` the P - 1 element names.  Slot 35 of a record is the
         number of particles ITS moments were taken over: it may differ from point to point and from sample to sample
         (a trace with losses); `apertures`: the indices (into `names`) of the elements that removed particles.
+        `screens`: the indices (into `names`) of the active screens, which are the points they observe; `screen_images`:
+        their images, (*batch, ny, nx) each.
         """
         trace = ParticleBeamTrace.__new__(ParticleBeamTrace)
         trace.records = np.asarray(records, dtype=np.float64)
@@ -86,15 +101,18 @@ class BeamTrace(Beam):
         trace.num_particles = int(entering.max()) if entering.size else 0
         trace._aperture_elements = [int(k) for k in apertures]
         assert all(0 <= k < trace.num_points - 1 for k in trace._aperture_elements), trace._aperture_elements
+        trace._set_screens(screens, screen_images)
         return trace
 
     @staticmethod
-    def from_moments(mu, cov, energy, lengths, names, dtype=np.float32) -> "BeamTrace":
-        """A ParameterBeam trace: `mu` (*batch, P, 7), `cov` (*batch, P, 7, 7), the rest as for `from_records`."""
+    def from_moments(mu, cov, energy, lengths, names, dtype=np.float32, screens=(), screen_images=()) -> "BeamTrace":
+        """A ParameterBeam trace: `mu` (*batch, P, 7), `cov` (*batch, P, 7, 7), the rest as for `from_records` (a
+        ParameterBeam's screen image is (*batch, len(xs), len(ys)), as `Screen.reading` returns it)."""
         trace = ParameterBeamTrace.__new__(ParameterBeamTrace)
         trace._mu = np.asarray(mu, dtype=dtype)
         trace._cov = np.asarray(cov, dtype=dtype)
         trace._set_common(energy, lengths, names, dtype, trace._mu.shape[:-2])
+        trace._set_screens(screens, screen_images)
         return trace
 
     @property
@@ -125,6 +143,22 @@ class BeamTrace(Beam):
         if not -self.num_points <= k < self.num_points:
             raise IndexError(f"point {k} of a trace of {self.num_points}")
         return k % self.num_points
+
+    def image_at(self, name_or_index) -> np.ndarray:
+        """
+        The image of one active screen: by the screen's name, or by the index of the point it observes (an int as
+        `index_of` takes it, negative from the end).  A name resolves to the element so named and an index to a point;
+        KeyError if no active screen of this trace stands there.
+        """
+        if isinstance(name_or_index, str):
+            if name_or_index not in self.names:
+                raise KeyError(f"no element named {name_or_index!r} in this trace")
+            k = self.names.index(name_or_index)
+        else:
+            k = self.index_of(name_or_index)
+        if k not in self.screens:
+            raise KeyError(f"{name_or_index!r}: no active screen of this trace observes point {k} (screens at {list(self.screens)})")
+        return self.screen_images[list(self.screens).index(k)]
 
     def at(self, name_or_index) -> dict:
         """Everything known about one point: `s`, `name` (None for point 0), `energy`, `mu`, `cov` and every moment."""
