@@ -239,7 +239,10 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
  *   d_energy_trace   [B][P]     beam energy at every point, particle dtype
  *   d_trace_out      [B][P][36] float64 moment records, layout of LYNX_MOMENT_STRIDE, slot 34 = 1 (whole triangle)
  * The sums are taken about a reference point that travels with the beam (the sample's first particle, taken through
- * the same maps) and added in a fixed order: the same call returns the same bits.                                  */
+ * the same maps) and added in a fixed order: the same call returns the same bits.
+ * This entry point and the two below are one call with or without a list of apertures and of screens: they refuse
+ * the same bad arguments (LYNX_ERR_INVALID, before anything is launched; lynx_last_error starts with "beam trace: ",
+ * "beam trace with losses: " or "beam trace with screens: "), and n_apertures and n_screens are at most 0x1fffffff. */
 int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags);
 

@@ -173,12 +173,9 @@ struct lynx_ctx {
   size_t scratch_steps_bytes[kTableSlots + 3] = {};
   void* scratch_trace[2] = {nullptr, nullptr};  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
   size_t scratch_trace_bytes[2] = {0, 0};
-  void* scratch_trace_codes = nullptr;  // ... with losses: which steps are apertures (TraceLosses.codes), and what was uploaded last
-  size_t scratch_trace_codes_bytes = 0;
-  std::vector<int32_t> trace_codes;
-  void* scratch_trace_screens = nullptr;  // ... with screens: step codes and screen rows (TraceScreens.plan), and what was uploaded last
-  size_t scratch_trace_screens_bytes = 0;
-  std::vector<int64_t> trace_screens;
+  void* scratch_trace_plan = nullptr;  // ... with losses or screens: step codes and screen rows (TraceLosses.plan), and what was uploaded last
+  size_t scratch_trace_plan_bytes = 0;
+  std::vector<int64_t> trace_plan;
   void* scratch_units_bwd[2] = {nullptr, nullptr};  // ... and of the reverse pass's own table
   size_t scratch_units_bwd_bytes[2] = {0, 0};
   void* scratch_units[2 * kTableSlots] = {};  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
@@ -632,8 +629,7 @@ int lynx_ctx_destroy(lynx_ctx* ctx) {
     if (ctx->scratch_steps[i]) (void)hipFree(ctx->scratch_steps[i]);
   for (int i = 0; i < 2; ++i)
     if (ctx->scratch_trace[i]) (void)hipFree(ctx->scratch_trace[i]);
-  if (ctx->scratch_trace_codes) (void)hipFree(ctx->scratch_trace_codes);
-  if (ctx->scratch_trace_screens) (void)hipFree(ctx->scratch_trace_screens);
+  if (ctx->scratch_trace_plan) (void)hipFree(ctx->scratch_trace_plan);
   for (int i = 0; i < 2 * lynx_ctx::kTableSlots; ++i)
     if (ctx->scratch_units[i]) (void)hipFree(ctx->scratch_units[i]);
   for (int i = 0; i < 2; ++i)
@@ -2436,24 +2432,6 @@ struct TraceApertures {
   int32_t* d_lost_at;
 };
 
-// TraceLosses.codes of this call on the device.  The list is uploaded when it differs from the one that is there (a scan
-// calls with the same lattice over and over); the wait that upload needs is paid once per lattice structure.
-static int trace_codes(lynx_ctx* ctx, int32_t S, const TraceApertures& ap) {
-  std::vector<int32_t> codes(std::max<int32_t>(1, S), -1);
-  for (int32_t k = 0; k < ap.count; ++k) codes[ap.pairs[2 * k]] = (k << 1) | (ap.pairs[2 * k + 1] ? 1 : 0);
-  const size_t need = codes.size() * sizeof(int32_t);
-  const bool fresh = ctx->scratch_trace_codes_bytes < need;
-  int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace_codes, &ctx->scratch_trace_codes_bytes, need))) return rc;
-  if (fresh || codes != ctx->trace_codes) {
-    ctx->trace_codes.clear();
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_trace_codes, codes.data(), need, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, sync_main(ctx));  // (kernels of earlier calls have read the old list; the host vector is ours again)
-    ctx->trace_codes.swap(codes);
-  }
-  return LYNX_OK;
-}
-
 // The screens of a trace as the host hands them over.
 struct TraceScreenList {
   int32_t count;
@@ -2462,39 +2440,57 @@ struct TraceScreenList {
   const void* d_misalignment;
   int64_t misalignment_stride;
   int32_t* d_images;
-  int64_t cells;  // sum of ny nx
+  int64_t cells;  // sum of ny nx (track_particles_along fills it in)
 };
 
-// TraceScreens.plan of this call on the device, uploaded when it differs from the one that is there (see trace_codes).
-static int trace_screen_plan(lynx_ctx* ctx, int32_t S, const TraceApertures* ap, const TraceScreenList& sc) {
-  std::vector<int64_t> plan((size_t)S + 4 * (size_t)sc.count, -1);
+// TraceLosses.plan of this call on the device (either list may be null).  The plan is uploaded when it differs from the
+// one that is there (a scan calls with the same lattice over and over); the wait that upload needs is paid once per
+// lattice structure.
+static int trace_plan(lynx_ctx* ctx, int32_t S, const TraceApertures* ap, const TraceScreenList* sc) {
+  std::vector<int64_t> plan(std::max<size_t>(1, (size_t)S + 4 * (size_t)(sc ? sc->count : 0)), -1);
   for (int32_t k = 0; ap && k < ap->count; ++k) plan[ap->pairs[2 * k]] = ((int64_t)k << 2) | (ap->pairs[2 * k + 1] ? 2 : 0);
   int64_t edge = 0, cell = 0;
-  for (int32_t k = 0; k < sc.count; ++k) {
-    const int64_t nx = sc.rows[3 * k + 1], ny = sc.rows[3 * k + 2];
-    plan[sc.rows[3 * k]] = ((int64_t)k << 2) | 1;
+  for (int32_t k = 0; sc && k < sc->count; ++k) {
+    const int64_t nx = sc->rows[3 * k + 1], ny = sc->rows[3 * k + 2];
+    plan[sc->rows[3 * k]] = ((int64_t)k << 2) | 1;
     int64_t* row = plan.data() + S + 4 * (size_t)k;
     row[0] = nx, row[1] = ny, row[2] = edge, row[3] = cell;
     edge += nx + ny + 2;
     cell += nx * ny;
   }
   const size_t need = plan.size() * sizeof(int64_t);
-  const bool fresh = ctx->scratch_trace_screens_bytes < need;
+  const bool fresh = ctx->scratch_trace_plan_bytes < need;
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace_screens, &ctx->scratch_trace_screens_bytes, need))) return rc;
-  if (fresh || plan != ctx->trace_screens) {
-    ctx->trace_screens.clear();
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_trace_screens, plan.data(), need, hipMemcpyHostToDevice, ctx->stream));
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace_plan, &ctx->scratch_trace_plan_bytes, need))) return rc;
+  if (fresh || plan != ctx->trace_plan) {
+    ctx->trace_plan.clear();
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_trace_plan, plan.data(), need, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, sync_main(ctx));  // (kernels of earlier calls have read the old plan; the host vector is ours again)
-    ctx->trace_screens.swap(plan);
+    ctx->trace_plan.swap(plan);
   }
   return LYNX_OK;
 }
 
+// `count`: N, or negative for the point's own count (k_trace_finalize).
+template <typename T>
+static int launch_trace_finalize(lynx_ctx* ctx, int64_t B, int32_t P, int64_t waves, int64_t count, double* d_trace_out) {
+  // (few waves per sample: 8 groups of them; hundreds to thousands -- few samples of many particles: 32)
+  if (waves > 256)
+    hipLaunchKernelGGL((k_trace_finalize<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
+                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, count, d_trace_out);
+  else
+    hipLaunchKernelGGL((k_trace_finalize<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
+                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, count, d_trace_out);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+// `ap`: the apertures of a trace with losses (null: none, and the records stand for N particles each); `sc`: the
+// screens (null: none).
 template <typename T>
 static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in, const void* d_p_in,
                                    void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
-                                   const TraceApertures* ap = nullptr, const TraceScreenList* sc = nullptr) {
+                                   const TraceApertures* ap, const TraceScreenList* sc) {
   constexpr int U = sizeof(T) == 4 ? 4 : 2;  // particles per lane (float32: two packed pairs)
   const int64_t B = lat->batch;
   const int32_t S = lat->n_steps, P = S + 1;
@@ -2524,86 +2520,76 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   a.store = d_p_out ? 1 : 0;
   a.points = P;
   const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
-  if (sc) {
-    if ((rc = trace_screen_plan(ctx, S, ap, *sc))) return rc;
-  } else if (ap && (rc = trace_codes(ctx, S, *ap))) {
-    return rc;
-  }
+  const T* ref = (const T*)ctx->scratch_trace[1];
+  double* slabs = (double*)ctx->scratch_trace[0];
+  if ((ap || sc) && (rc = trace_plan(ctx, S, ap, sc))) return rc;
   hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
                      (const T*)d_energy_in, (const T*)d_p_in, a.in_stride, (T*)ctx->scratch_trace[1], (T*)d_energy_trace);
   HIP_TRY(ctx, hipGetLastError());
+  // (on the context's stream: a null-stream memset does not wait for what this stream still runs)
+  if (sc) HIP_TRY(ctx, hipMemsetAsync(sc->d_images, 0, (size_t)B * sc->cells * sizeof(int32_t), ctx->stream));
+  if (ap && ap->d_lost_at)  // every byte 0xff: -1, "survivor"; the kernel writes the cells of the lost
+    HIP_TRY(ctx, hipMemsetAsync(ap->d_lost_at, 0xff, (size_t)B * N * sizeof(int32_t), ctx->stream));
+  // a trace with screens and without an aperture loses nobody: its records are the plain trace's (slot 35 = N)
+  const bool counted = ap && (!sc || ap->count > 0);
+  const TraceLosses loss{(const int64_t*)ctx->scratch_trace_plan, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0,
+                         ap ? ap->d_lost_at : nullptr};
+  const dim3 grid((unsigned)(B * (waves / 4)));
   if (sc) {
-    // (on the context's stream, like `lost_at`: a null-stream memset does not wait for what this stream still runs)
-    HIP_TRY(ctx, hipMemsetAsync(sc->d_images, 0, (size_t)B * sc->cells * sizeof(int32_t), ctx->stream));
-    const bool counted = ap && ap->count > 0;
-    if (ap && ap->d_lost_at)
-      HIP_TRY(ctx, hipMemsetAsync(ap->d_lost_at, 0xff, (size_t)B * N * sizeof(int32_t), ctx->stream));
-    const TraceLosses loss{nullptr, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0, ap ? ap->d_lost_at : nullptr};
-    const TraceScreens scr{(const int64_t*)ctx->scratch_trace_screens, sc->d_edges, sc->d_misalignment, sc->misalignment_stride,
-                           sc->d_images, sc->cells};
-    hipLaunchKernelGGL((k_trace_particles_screens<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, S,
-                       table, (const T*)ctx->scratch_trace[1], (const T*)d_p_in, (T*)d_p_out, (double*)ctx->scratch_trace[0],
-                       loss, scr);
-    HIP_TRY(ctx, hipGetLastError());
-    // without an aperture nobody is lost: the records are the plain trace's (slot 35 = N)
-    if (counted) {
-      if (waves > 256)
-        hipLaunchKernelGGL((k_trace_finalize_counted<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
-                           (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, d_trace_out);
-      else
-        hipLaunchKernelGGL((k_trace_finalize_counted<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
-                           (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, d_trace_out);
-    } else if (waves > 256) {
-      hipLaunchKernelGGL((k_trace_finalize<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
-                         (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, N, d_trace_out);
-    } else {
-      hipLaunchKernelGGL((k_trace_finalize<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
-                         (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, N, d_trace_out);
-    }
-    HIP_TRY(ctx, hipGetLastError());
-    return LYNX_OK;
+    const TraceScreens scr{sc->d_edges, sc->d_misalignment, sc->misalignment_stride, sc->d_images, sc->cells};
+    hipLaunchKernelGGL((k_trace_particles_screens<T, U>), grid, dim3(256), 0, ctx->stream, a, S, table, ref, (const T*)d_p_in,
+                       (T*)d_p_out, slabs, loss, scr);
+  } else if (ap) {
+    hipLaunchKernelGGL((k_trace_particles_losses<T, U>), grid, dim3(256), 0, ctx->stream, a, S, table, ref, (const T*)d_p_in,
+                       (T*)d_p_out, slabs, loss);
+  } else {
+    hipLaunchKernelGGL((k_trace_particles<T, U>), grid, dim3(256), 0, ctx->stream, a, S, table, ref, (const T*)d_p_in,
+                       (T*)d_p_out, slabs);
   }
-  if (ap) {
-    if (ap->d_lost_at)  // every byte 0xff: -1, "survivor"; the kernel writes the cells of the lost
-      HIP_TRY(ctx, hipMemsetAsync(ap->d_lost_at, 0xff, (size_t)B * N * sizeof(int32_t), ctx->stream));
-    const TraceLosses loss{(const int32_t*)ctx->scratch_trace_codes, ap->d_limits, ap->limit_stride, ap->d_lost_at};
-    hipLaunchKernelGGL((k_trace_particles_losses<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, S,
-                       table, (const T*)ctx->scratch_trace[1], (const T*)d_p_in, (T*)d_p_out, (double*)ctx->scratch_trace[0],
-                       loss);
-    HIP_TRY(ctx, hipGetLastError());
-    if (waves > 256)
-      hipLaunchKernelGGL((k_trace_finalize_counted<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
-                         (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, d_trace_out);
-    else
-      hipLaunchKernelGGL((k_trace_finalize_counted<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
-                         (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, d_trace_out);
-    HIP_TRY(ctx, hipGetLastError());
-    return LYNX_OK;
-  }
-  hipLaunchKernelGGL((k_trace_particles<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, S, table,
-                     (const T*)ctx->scratch_trace[1], (const T*)d_p_in, (T*)d_p_out, (double*)ctx->scratch_trace[0]);
   HIP_TRY(ctx, hipGetLastError());
-  // (few waves per sample: 8 groups of them; hundreds to thousands -- few samples of many particles: 32)
-  if (waves > 256)
-    hipLaunchKernelGGL((k_trace_finalize<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
-                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, N, d_trace_out);
-  else
-    hipLaunchKernelGGL((k_trace_finalize<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
-                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, N, d_trace_out);
-  HIP_TRY(ctx, hipGetLastError());
-  return LYNX_OK;
+  return launch_trace_finalize<T>(ctx, B, P, waves, counted ? -1 : N, d_trace_out);
 }
 
-int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
-                               const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags) {
+// The three entry points of the particle trace: the checks, the bookkeeping and the dtype dispatch.  `ap` / `sc` are the
+// lists of a trace with losses / with screens, null where the entry point has none.
+static int track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                 const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                 const TraceApertures* ap, TraceScreenList* sc) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
-  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
-  if (flags & ~LYNX_TRACK_SHARED_INPUT) return fail(ctx, LYNX_ERR_INVALID, "beam trace: LYNX_TRACK_SHARED_INPUT is the only flag");
-  if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out)
-    return fail(ctx, LYNX_ERR_INVALID, "a shared incoming beam cannot be tracked in place");
-  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
+  const char* mode = sc ? "beam trace with screens: " : ap ? "beam trace with losses: " : "beam trace: ";
+  const auto refuse = [&](const char* what) { return fail(ctx, LYNX_ERR_INVALID, std::string(mode) + what); };
+  if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return refuse("null argument");
+  if (n_particles <= 0) return refuse("n_particles must be > 0");
+  if (flags & ~LYNX_TRACK_SHARED_INPUT) return refuse("LYNX_TRACK_SHARED_INPUT is the only flag");
+  if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out) return refuse("a shared incoming beam cannot be tracked in place");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return refuse("bad batch");
+  if (ap) {
+    // (0x1fffffff: a step's code keeps two bits for its flags)
+    if (ap->count < 0 || ap->count > 0x1fffffff || (ap->count > 0 && (!ap->pairs || !ap->d_limits))) return refuse("bad aperture list");
+    if (ap->limit_stride != 0 && ap->limit_stride != 2 * (int64_t)ap->count)
+      return refuse("the limits' sample stride is 0 or 2 * n_apertures");
+  }
+  if (sc) {
+    if (sc->count <= 0 || sc->count > 0x1fffffff || !sc->rows || !sc->d_edges || !sc->d_misalignment || !sc->d_images)
+      return refuse("bad screen list");
+    if (sc->misalignment_stride != 0 && sc->misalignment_stride != 2 * (int64_t)sc->count)
+      return refuse("the misalignments' sample stride is 0 or 2 * n_screens");
+  }
+  for (int32_t k = 0; ap && k < ap->count; ++k) {  // lattice order, every step at most once
+    const int32_t step = ap->pairs[2 * k];
+    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= ap->pairs[2 * k - 2]))
+      return refuse("aperture steps must be increasing and inside the program");
+  }
+  for (int32_t k = 0, a = 0; sc && k < sc->count; ++k) {
+    const int32_t step = sc->rows[3 * k], nx = sc->rows[3 * k + 1], ny = sc->rows[3 * k + 2];
+    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= sc->rows[3 * k - 3]))
+      return refuse("screen steps must be increasing and inside the program");
+    while (ap && a < ap->count && ap->pairs[2 * a] < step) ++a;
+    if (ap && a < ap->count && ap->pairs[2 * a] == step) return refuse("a step is an aperture or a screen, not both");
+    if (nx < 1 || ny < 1) return refuse("a screen has at least one pixel each way");
+    sc->cells += (int64_t)nx * ny;
+  }
   HIP_TRY(ctx, use_device(ctx));
   ctx->main_dirty = true;
   const size_t es = dtype_size(lat->dtype);
@@ -2611,44 +2597,24 @@ int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_parti
   ctx->wrote(d_p_out, (size_t)lat->batch * n_particles * 7 * es);
   ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
   ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
+  if (ap) ctx->wrote(ap->d_lost_at, (size_t)lat->batch * n_particles * sizeof(int32_t));
+  if (sc) ctx->wrote(sc->d_images, (size_t)lat->batch * sc->cells * sizeof(int32_t));
   return lat->dtype == LYNX_F64
-             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags)
-             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags);
+             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc)
+             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc);
+}
+
+int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                               const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags) {
+  return track_particles_along(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, nullptr, nullptr);
 }
 
 int lynx_track_particles_along_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                       const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
                                       int32_t n_apertures, const int32_t* apertures, const void* d_limits,
                                       int64_t limit_stride, int32_t* d_lost_at) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
-  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
-  if (flags & ~LYNX_TRACK_SHARED_INPUT) return fail(ctx, LYNX_ERR_INVALID, "beam trace: LYNX_TRACK_SHARED_INPUT is the only flag");
-  if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out)
-    return fail(ctx, LYNX_ERR_INVALID, "a shared incoming beam cannot be tracked in place");
-  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
-  if (n_apertures < 0 || n_apertures > 0x3fffffff || (n_apertures > 0 && (!apertures || !d_limits)))
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace with losses: bad aperture list");
-  if (limit_stride != 0 && limit_stride != 2 * (int64_t)n_apertures)
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace with losses: the limits' sample stride is 0 or 2 * n_apertures");
-  for (int32_t k = 0; k < n_apertures; ++k) {  // lattice order, every step at most once
-    const int32_t step = apertures[2 * k];
-    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= apertures[2 * k - 2]))
-      return fail(ctx, LYNX_ERR_INVALID, "beam trace with losses: aperture steps must be increasing and inside the program");
-  }
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
-  const size_t es = dtype_size(lat->dtype);
-  const size_t points = (size_t)lat->n_steps + 1;
-  ctx->wrote(d_p_out, (size_t)lat->batch * n_particles * 7 * es);
-  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
-  ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
-  ctx->wrote(d_lost_at, (size_t)lat->batch * n_particles * sizeof(int32_t));
   const TraceApertures ap{n_apertures, apertures, d_limits, limit_stride, d_lost_at};
-  return lat->dtype == LYNX_F64
-             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap)
-             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap);
+  return track_particles_along(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap, nullptr);
 }
 
 int lynx_track_particles_along_screens(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
@@ -2657,52 +2623,9 @@ int lynx_track_particles_along_screens(lynx_ctx* ctx, lynx_lattice* lat, int64_t
                                        int64_t limit_stride, int32_t* d_lost_at, int32_t n_screens, const int32_t* screens,
                                        const void* d_edges, const void* d_misalignment, int64_t misalignment_stride,
                                        int32_t* d_images) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
-  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
-  if (flags & ~LYNX_TRACK_SHARED_INPUT) return fail(ctx, LYNX_ERR_INVALID, "beam trace: LYNX_TRACK_SHARED_INPUT is the only flag");
-  if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out)
-    return fail(ctx, LYNX_ERR_INVALID, "a shared incoming beam cannot be tracked in place");
-  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
-  if (n_apertures < 0 || n_apertures > 0x1fffffff || (n_apertures > 0 && (!apertures || !d_limits)))
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: bad aperture list");
-  if (limit_stride != 0 && limit_stride != 2 * (int64_t)n_apertures)
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: the limits' sample stride is 0 or 2 * n_apertures");
-  if (n_screens <= 0 || n_screens > 0x1fffffff || !screens || !d_edges || !d_misalignment || !d_images)
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: bad screen list");
-  if (misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: the misalignments' sample stride is 0 or 2 * n_screens");
-  for (int32_t k = 0; k < n_apertures; ++k) {  // lattice order, every step at most once
-    const int32_t step = apertures[2 * k];
-    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= apertures[2 * k - 2]))
-      return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: aperture steps must be increasing and inside the program");
-  }
-  int64_t cells = 0;
-  for (int32_t k = 0, a = 0; k < n_screens; ++k) {
-    const int32_t step = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= screens[3 * k - 3]))
-      return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: screen steps must be increasing and inside the program");
-    while (a < n_apertures && apertures[2 * a] < step) ++a;
-    if (a < n_apertures && apertures[2 * a] == step)
-      return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: a step is an aperture or a screen, not both");
-    if (nx < 1 || ny < 1) return fail(ctx, LYNX_ERR_INVALID, "beam trace with screens: a screen has at least one pixel each way");
-    cells += (int64_t)nx * ny;
-  }
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
-  const size_t es = dtype_size(lat->dtype);
-  const size_t points = (size_t)lat->n_steps + 1;
-  ctx->wrote(d_p_out, (size_t)lat->batch * n_particles * 7 * es);
-  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
-  ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
-  ctx->wrote(d_lost_at, (size_t)lat->batch * n_particles * sizeof(int32_t));
-  ctx->wrote(d_images, (size_t)lat->batch * cells * sizeof(int32_t));
   const TraceApertures ap{n_apertures, apertures, d_limits, limit_stride, d_lost_at};
-  const TraceScreenList sc{n_screens, screens, d_edges, d_misalignment, misalignment_stride, d_images, cells};
-  return lat->dtype == LYNX_F64
-             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap, &sc)
-             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap, &sc);
+  TraceScreenList sc{n_screens, screens, d_edges, d_misalignment, misalignment_stride, d_images, 0};
+  return track_particles_along(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap, &sc);
 }
 
 template <typename T>

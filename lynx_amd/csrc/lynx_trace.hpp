@@ -20,10 +20,14 @@
 //   k_trace_finalize        adds the waves' slabs of a (sample, point) in a fixed order and writes the moment record
 //                           [B][P][36] (layout of LYNX_MOMENT_STRIDE, slot 34 = 1).
 //
-// With particle losses (lynx_track_particles_along_losses; k_trace_particles_losses, k_trace_finalize_counted) an active
-// aperture is an identity step that clears the `live` bit of the particles outside it: nothing is compacted, a lost
-// particle stays in its lane and is kept out of every later sum by a select, and the number of particles a record
-// stands for is the point's own sum of the 7th coordinate (slot 6 of the slab row) instead of N.
+// The three particle kernels are one wave body (trace_wave) instantiated three times -- the flags decide the register
+// pressure -- and a lattice with active apertures or screens comes with ONE step plan (TraceLosses.plan): a code per
+// step that says "nothing", "aperture k" or "screen k", read by one hook behind every point (trace_step_hook).
+//
+// With particle losses (lynx_track_particles_along_losses; k_trace_particles_losses) an active aperture is an identity
+// step that clears the `live` bit of the particles outside it: nothing is compacted, a lost particle stays in its lane
+// and is kept out of every later sum by a select, and the number of particles a record stands for is the point's own
+// sum of the 7th coordinate (slot 6 of the slab row) instead of N (k_trace_finalize with a negative count).
 //
 // With screens (lynx_track_particles_along_screens; k_trace_particles_screens) an active screen is an identity step too:
 // the particles alive where it stands are binned by numpy's rule on the screen's own edge arrays (bin_of's result, from
@@ -47,10 +51,13 @@ struct TraceArgs {
   int32_t points;         // P = E + 1
 };
 
-// The apertures of a trace with losses.  `codes` [S]: -1, or (ordinal of the aperture << 1) | elliptical for a step that
-// is an active aperture; `limits` [B or 1][A][2]: x_max, y_max in the lattice's dtype.
+// The step plan of a trace with apertures and / or screens, and its apertures.  `plan`: [S] step codes, then [K][4] per
+// screen (K may be 0).  A step's code is -1, (ordinal of the aperture << 2) | (elliptical << 1) for an active aperture,
+// (ordinal of the screen << 2) | 1 for an active screen; a screen's row is nx, ny, the first scalar of its edges in
+// TraceScreens.edges (x edges, nx + 1 of them, then y edges), the first cell of its image in a sample's row of
+// TraceScreens.images.  `limits` [B or 1][A][2]: x_max, y_max in the lattice's dtype (not read without apertures).
 struct TraceLosses {
-  const int32_t* codes;
+  const int64_t* plan;
   const void* limits;
   int64_t limit_stride;  // scalars between the samples of `limits`: 2 A, or 0 for limits the batch shares
   int32_t* lost_at;      // [B][N], -1 everywhere before the launch: a particle's cell is written when (and if) an aperture
@@ -58,12 +65,8 @@ struct TraceLosses {
                          // the tile costs the float32 kernel its third wave per SIMD); or null
 };
 
-// The screens of a trace.  `plan`: [S] step codes, then [K][4] per screen.  A step's code is -1, (ordinal of the aperture
-// << 2) | (elliptical << 1) for an active aperture, (ordinal of the screen << 2) | 1 for an active screen; a screen's row
-// is nx, ny, the first scalar of its edges in `edges` (x edges, nx + 1 of them, then y edges), the first cell of its
-// image in a sample's row of `images`.
+// The screens of a trace (which steps they are, and their rows: TraceLosses.plan).
 struct TraceScreens {
-  const int64_t* plan;
   const void* edges;          // lattice dtype
   const void* misalignment;   // [B or 1][K][2], lattice dtype
   int64_t misalignment_stride;  // scalars between the samples of `misalignment`: 2 K, or 0
@@ -263,9 +266,9 @@ __device__ __forceinline__ void trace_point(const double (&z)[U][7], const doubl
   trace_deposit<double>(v, lane, first, row);
 }
 
-// Step s of a trace with losses, after point s has been deposited: if the step is an aperture (wave-uniform: a scalar
-// load), the particles whose coordinates ENTERING it lie outside are dead from the next point on.  The comparison is
-// k_aperture_mask's own (aperture_survives<T>, aperture.py:78-86).
+// Step s of a trace with losses, after point s has been deposited, if the step is the aperture `code` >> 1 (elliptical:
+// `code` & 1; wave-uniform): the particles whose coordinates ENTERING it lie outside are dead from the next point on.
+// The comparison is k_aperture_mask's own (aperture_survives<T>, aperture.py:78-86).
 template <typename T, int U, typename X>
 __device__ __forceinline__ void trace_aperture_coded(int code /* uniform, >= 0 */, const T* __restrict__ limits /* of this sample */,
                                                      X&& xy, bool (&live)[U], int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
@@ -279,13 +282,6 @@ __device__ __forceinline__ void trace_aperture_coded(int code /* uniform, >= 0 *
     if (out && tile_lost_at) tile_lost_at[lane + 64 * u] = ordinal;  // (once: the particle is dead from here on)
     live[u] = live[u] && !out;
   }
-}
-template <typename T, int U, typename X>
-__device__ __forceinline__ void trace_aperture(const TraceLosses& loss, const T* __restrict__ limits /* of this sample */,
-                                               int s, X&& xy, bool (&live)[U], int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
-  const int code = __builtin_amdgcn_readfirstlane(loss.codes[s]);
-  if (code < 0) return;
-  trace_aperture_coded<T, U>(code, limits, xy, live, tile_lost_at, lane);
 }
 
 // The bin of v among n bins with the edges `edges` [n + 1], by numpy.histogramdd's rule: the number of edges <= v, minus
@@ -307,8 +303,9 @@ __device__ __forceinline__ int screen_bin(const T* __restrict__ edges, int n, T 
 // screen.py:196-213 (Screen._observe takes the y misalignment off x', which no image sees).  A dead particle is left out
 // because it is dead, whatever its coordinates have become.
 template <typename T, int U, typename X>
-__device__ __forceinline__ void trace_screen(const TraceScreens& scr, int S, int ordinal, int64_t b, X&& xy, const bool (&live)[U]) {
-  const int64_t* row = scr.plan + S + 4 * (int64_t)ordinal;
+__device__ __forceinline__ void trace_screen(const TraceScreens& scr, const int64_t* __restrict__ rows /* of the plan */, int ordinal,
+                                             int64_t b, X&& xy, const bool (&live)[U]) {
+  const int64_t* row = rows + 4 * (int64_t)ordinal;
   const int nx = __builtin_amdgcn_readfirstlane((int)row[0]), ny = __builtin_amdgcn_readfirstlane((int)row[1]);
   const T* xe = static_cast<const T*>(scr.edges) + row[2];
   const T* ye = xe + nx + 1;
@@ -335,14 +332,27 @@ __device__ __forceinline__ void trace_screen(const TraceScreens& scr, int S, int
   }
 }
 
+// Step s of a trace with apertures and / or screens, after point s has been deposited: one code of the plan says what
+// the step is (wave-uniform: a scalar load).
+template <typename T, int U, bool SCREENS, typename X>
+__device__ __forceinline__ void trace_step_hook(const TraceLosses& loss, const TraceScreens& scr, const T* __restrict__ limits /* of this sample */,
+                                                int S, int s, int64_t b, X&& xy, bool (&live)[U],
+                                                int32_t* __restrict__ tile_lost_at /* uniform */, int lane) {
+  const int code = __builtin_amdgcn_readfirstlane((int)loss.plan[s]);
+  if (code < 0) return;
+  if constexpr (SCREENS)
+    if (code & 1) return trace_screen<T, U>(scr, loss.plan + S, code >> 2, b, xy, live);
+  trace_aperture_coded<T, U>(code >> 1, limits, xy, live, tile_lost_at, lane);
+}
+
 // one tile of a wave through the whole lattice
-template <typename T, int U, bool MASKED, bool LOSSES = false, bool SCREENS = false>
+template <typename T, int U, bool MASKED, bool LOSSES, bool SCREENS>
 __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* __restrict__ steps /* of this sample */,
                                            const T* __restrict__ ref /* of this sample */, const T* __restrict__ src,
                                            T* __restrict__ dst, int64_t base, int lane, bool first,
-                                           double* __restrict__ slab /* of this wave */, const TraceLosses& loss = TraceLosses{},
-                                           const T* __restrict__ limits = nullptr, int32_t* __restrict__ lost_at = nullptr,
-                                           const TraceScreens& scr = TraceScreens{}, int64_t b = 0) {
+                                           double* __restrict__ slab /* of this wave */, const TraceLosses& loss,
+                                           const T* __restrict__ limits, int32_t* __restrict__ lost_at,
+                                           const TraceScreens& scr, int64_t b) {
   static_assert(MASKED || !LOSSES, "a trace with losses always takes the masked path");
   static_assert(LOSSES || !SCREENS, "a trace with screens takes the path of the losses (its apertures may be none)");
   bool live[U];
@@ -366,18 +376,8 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
     for (int s = 0; s <= S; ++s) {
       trace_point<U, MASKED>(zp, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
       if (s == S) break;
-      if constexpr (SCREENS) {  // one code per step says aperture or screen (wave-uniform)
-        auto xy = [&](int u, T& x, T& y) {
-          x = (u & 1) ? zp[u / 2][0].y : zp[u / 2][0].x;
-          y = (u & 1) ? zp[u / 2][2].y : zp[u / 2][2].x;
-        };
-        const int code = __builtin_amdgcn_readfirstlane((int)scr.plan[s]);
-        if (code >= 0) {
-          if (code & 1) trace_screen<T, U>(scr, S, code >> 2, b, xy, live);
-          else trace_aperture_coded<T, U>(code >> 1, limits, xy, live, lost_at ? lost_at + base : nullptr, lane);
-        }
-      } else if constexpr (LOSSES)
-        trace_aperture<T, U>(loss, limits, s, [&](int u, T& x, T& y) {
+      if constexpr (LOSSES)
+        trace_step_hook<T, U, SCREENS>(loss, scr, limits, S, s, b, [&](int u, T& x, T& y) {
           x = (u & 1) ? zp[u / 2][0].y : zp[u / 2][0].x;
           y = (u & 1) ? zp[u / 2][2].y : zp[u / 2][2].x;
         }, live, lost_at ? lost_at + base : nullptr, lane);
@@ -424,18 +424,8 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
     for (int s = 0; s <= S; ++s) {
       trace_point<U, MASKED>(z, ref + s * kTraceRef, live, lane, first, slab + (int64_t)s * kTraceSlab);
       if (s == S) break;
-      if constexpr (SCREENS) {
-        auto xy = [&](int u, T& x, T& y) {
-          x = z[u][0];
-          y = z[u][2];
-        };
-        const int code = __builtin_amdgcn_readfirstlane((int)scr.plan[s]);
-        if (code >= 0) {
-          if (code & 1) trace_screen<T, U>(scr, S, code >> 2, b, xy, live);
-          else trace_aperture_coded<T, U>(code >> 1, limits, xy, live, lost_at ? lost_at + base : nullptr, lane);
-        }
-      } else if constexpr (LOSSES)
-        trace_aperture<T, U>(loss, limits, s, [&](int u, T& x, T& y) {
+      if constexpr (LOSSES)
+        trace_step_hook<T, U, SCREENS>(loss, scr, limits, S, s, b, [&](int u, T& x, T& y) {
           x = z[u][0];
           y = z[u][2];
         }, live, lost_at ? lost_at + base : nullptr, lane);
@@ -463,14 +453,18 @@ __device__ __forceinline__ void trace_tile(const TraceArgs& a, int S, const T* _
 }
 
 // ---------------------------------------------------------------------------------------
-// k_trace_particles: grid.x = B * waves / 4, 256 threads; wave w of a sample owns the particles
+// The particle kernels: grid.x = B * waves / 4, 256 threads; wave w of a sample owns the particles
 // [w * tiles_per_wave * 64 U, (w + 1) * tiles_per_wave * 64 U).  No LDS, no barrier.  A wave whose range lies
 // beyond the end of the sample writes a slab of zeros (the finalizer adds every wave's slab).
+//
+// trace_wave is the body of all three.  Without apertures a full tile takes the unmasked path and only the last one
+// the masked path; with them (LOSSES) every tile is masked.  The order of the branches in the tile loop is the one the
+// plain kernels' register allocation was measured with: keep it.
 // ---------------------------------------------------------------------------------------
-template <typename T, int U>
-__global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, const T* __restrict__ steps,
-                                                         const T* __restrict__ ref, const T* __restrict__ p_in,
-                                                         T* __restrict__ p_out, double* __restrict__ slabs) {
+template <typename T, int U, bool LOSSES, bool SCREENS>
+__device__ __forceinline__ void trace_wave(const TraceArgs& a, int S, const T* __restrict__ steps, const T* __restrict__ ref,
+                                           const T* __restrict__ p_in, T* __restrict__ p_out, double* __restrict__ slabs,
+                                           const TraceLosses& loss, const TraceScreens& scr) {
   const int wgs = a.waves / 4;
   const int64_t b = blockIdx.x / wgs;
   const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
@@ -481,6 +475,8 @@ __global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, con
   const T* src = p_in + b * a.in_stride;
   T* dst = p_out + b * a.n_particles * 7;
   double* slab = slabs + (b * a.waves + w) * (int64_t)P * kTraceSlab;
+  const T* limits = LOSSES ? static_cast<const T*>(loss.limits) + b * loss.limit_stride : nullptr;
+  int32_t* lost_at = LOSSES && loss.lost_at ? loss.lost_at + b * a.n_particles : nullptr;
   constexpr int64_t kTile = 64 * U;
   const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
   if (begin >= a.n_particles) {
@@ -490,75 +486,38 @@ __global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, con
   for (int t = 0; t < a.tiles_per_wave; ++t) {
     const int64_t base = begin + t * kTile;
     if (base >= a.n_particles) break;
-    if (base + kTile <= a.n_particles)
-      trace_tile<T, U, false>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab);
+    if constexpr (LOSSES)
+      trace_tile<T, U, true, true, SCREENS>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at, scr, b);
+    else if (base + kTile <= a.n_particles)
+      trace_tile<T, U, false, false, false>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at, scr, b);
     else
-      trace_tile<T, U, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab);
+      trace_tile<T, U, true, false, false>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at, scr, b);
   }
 }
 
-// ... with active apertures (TraceLosses): the same walk over the tiles, every one of them by the masked path.
+template <typename T, int U>
+__global__ __launch_bounds__(256) void k_trace_particles(TraceArgs a, int S, const T* __restrict__ steps,
+                                                         const T* __restrict__ ref, const T* __restrict__ p_in,
+                                                         T* __restrict__ p_out, double* __restrict__ slabs) {
+  trace_wave<T, U, false, false>(a, S, steps, ref, p_in, p_out, slabs, TraceLosses{}, TraceScreens{});
+}
+
+// ... with active apertures (TraceLosses)
 template <typename T, int U>
 __global__ __launch_bounds__(256) void k_trace_particles_losses(TraceArgs a, int S, const T* __restrict__ steps,
                                                                 const T* __restrict__ ref, const T* __restrict__ p_in,
                                                                 T* __restrict__ p_out, double* __restrict__ slabs,
                                                                 TraceLosses loss) {
-  const int wgs = a.waves / 4;
-  const int64_t b = blockIdx.x / wgs;
-  const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int P = S + 1;
-  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
-  const T* sample_ref = ref + b * (int64_t)P * kTraceRef;
-  const T* src = p_in + b * a.in_stride;
-  T* dst = p_out + b * a.n_particles * 7;
-  double* slab = slabs + (b * a.waves + w) * (int64_t)P * kTraceSlab;
-  const T* limits = static_cast<const T*>(loss.limits) + b * loss.limit_stride;
-  int32_t* lost_at = loss.lost_at ? loss.lost_at + b * a.n_particles : nullptr;
-  constexpr int64_t kTile = 64 * U;
-  const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
-  if (begin >= a.n_particles) {
-    for (int64_t i = lane; i < (int64_t)P * kTraceSlab; i += 64) slab[i] = 0.0;
-    return;
-  }
-  for (int t = 0; t < a.tiles_per_wave; ++t) {
-    const int64_t base = begin + t * kTile;
-    if (base >= a.n_particles) break;
-    trace_tile<T, U, true, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at);
-  }
+  trace_wave<T, U, true, false>(a, S, steps, ref, p_in, p_out, slabs, loss, TraceScreens{});
 }
 
-// ... with active screens (TraceScreens), and with the apertures of `loss` if there are any (their codes are in the
-// screens' plan; loss.codes is not read): the walk of k_trace_particles_losses.
+// ... with active screens (TraceScreens), and with the apertures of `loss` if there are any
 template <typename T, int U>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 3 : 4))) void k_trace_particles_screens(TraceArgs a, int S, const T* __restrict__ steps,
                                                                  const T* __restrict__ ref, const T* __restrict__ p_in,
                                                                  T* __restrict__ p_out, double* __restrict__ slabs,
                                                                  TraceLosses loss, TraceScreens scr) {
-  const int wgs = a.waves / 4;
-  const int64_t b = blockIdx.x / wgs;
-  const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
-  const int lane = threadIdx.x & 63;
-  const int P = S + 1;
-  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
-  const T* sample_ref = ref + b * (int64_t)P * kTraceRef;
-  const T* src = p_in + b * a.in_stride;
-  T* dst = p_out + b * a.n_particles * 7;
-  double* slab = slabs + (b * a.waves + w) * (int64_t)P * kTraceSlab;
-  const T* limits = static_cast<const T*>(loss.limits) + b * loss.limit_stride;
-  int32_t* lost_at = loss.lost_at ? loss.lost_at + b * a.n_particles : nullptr;
-  constexpr int64_t kTile = 64 * U;
-  const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
-  if (begin >= a.n_particles) {
-    for (int64_t i = lane; i < (int64_t)P * kTraceSlab; i += 64) slab[i] = 0.0;
-    return;
-  }
-  for (int t = 0; t < a.tiles_per_wave; ++t) {
-    const int64_t base = begin + t * kTile;
-    if (base >= a.n_particles) break;
-    trace_tile<T, U, true, true, true>(a, S, sample_steps, sample_ref, src, dst, base, lane, t == 0, slab, loss, limits, lost_at,
-                                       scr, b);
-  }
+  trace_wave<T, U, true, true>(a, S, steps, ref, p_in, p_out, slabs, loss, scr);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -568,10 +527,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(T) =
 // it: every slab was taken about the same reference point, so there is nothing to move.
 // (One group alone: 2608 dependent additions per cell for one sample of 10^6 particles, 577 us -- more than the
 // streaming kernel's 122.)
+// `count`: the number of particles a record stands for (slot 35), N -- or negative, for a trace with losses: the number
+// of particles alive at that point (a point nobody reaches: count 0 and, by write_moment_record's divisions, NaN
+// moments).
 // ---------------------------------------------------------------------------------------
-template <typename T, int THREADS, bool COUNTED>
-__device__ __forceinline__ void trace_finalize_body(const double* __restrict__ slabs, const T* __restrict__ ref, int waves,
-                                                    int P, int64_t n_particles, double* __restrict__ out) {
+template <typename T, int THREADS>
+__global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __restrict__ slabs, const T* __restrict__ ref,
+                                                            int waves, int P, int64_t count, double* __restrict__ out) {
   constexpr int G = THREADS / kTraceSlab;
   __shared__ double s_part[G][kTraceSlab];
   __shared__ double s[kPartialStride];
@@ -597,32 +559,16 @@ __device__ __forceinline__ void trace_finalize_body(const double* __restrict__ s
       v = (double)ref[(b * P + k) * kTraceRef + (tid - 28)];
     } else if (tid == 34) {
       v = 1.0;
-    } else if (COUNTED) {  // the point's own count: the sum of the 7th coordinate, exact (integers in float64)
+    } else if (count < 0) {  // the point's own count: the sum of the 7th coordinate, exact (integers in float64)
 #pragma unroll
       for (int q = 0; q < G; ++q) v += s_part[q][6];
     } else {
-      v = (double)n_particles;
+      v = (double)count;
     }
     s[tid] = v;
   }
   __syncthreads();
   if (tid < kPartialStride) write_moment_record(s, out + (b * P + k) * kPartialStride, tid);
-}
-
-template <typename T, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __restrict__ slabs, const T* __restrict__ ref,
-                                                            int waves, int P, int64_t n_particles,
-                                                            double* __restrict__ out) {
-  trace_finalize_body<T, THREADS, false>(slabs, ref, waves, P, n_particles, out);
-}
-
-// ... of a trace with losses: slot 35 of every record is the number of particles alive at that point (a point nobody
-// reaches: count 0 and, by write_moment_record's divisions, NaN moments).
-template <typename T, int THREADS>
-__global__ __launch_bounds__(THREADS) void k_trace_finalize_counted(const double* __restrict__ slabs,
-                                                                    const T* __restrict__ ref, int waves, int P,
-                                                                    double* __restrict__ out) {
-  trace_finalize_body<T, THREADS, true>(slabs, ref, waves, P, 0, out);
 }
 
 // ---------------------------------------------------------------------------------------

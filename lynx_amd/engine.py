@@ -43,8 +43,9 @@ def _late():
         from .particles.particle_beam import ParticleBeam
 
         from .accelerator.segment import ElementList
+        from .trace import BeamTrace
 
-        _LATE = SimpleNamespace(EPOCH=EPOCH, STRUCTURE=STRUCTURE, Segment=Segment, Beam=Beam,
+        _LATE = SimpleNamespace(EPOCH=EPOCH, STRUCTURE=STRUCTURE, Segment=Segment, Beam=Beam, BeamTrace=BeamTrace,
                                 ParameterBeam=ParameterBeam, ParticleBeam=ParticleBeam, ElementList=ElementList)
     return _LATE
 
@@ -547,6 +548,14 @@ def _aperture_limits(owner, program: Program, batch_shape, dtype, rt):
     return limits, stride
 
 
+def _aperture_arguments(owner, program: Program, batch_shape, dtype, rt):
+    """The program's active apertures as both entry points take them: number, host pairs (step, elliptical), limits, stride."""
+    A = len(program.apertures)
+    limits, stride = _aperture_limits(owner, program, batch_shape, dtype, rt) if A else (None, 0)
+    pairs = (C.c_int32 * max(2 * A, 1))(*[v for step, _, elliptical in program.apertures for v in (step, int(elliptical))])
+    return A, pairs, _ptr(limits), stride
+
+
 def _screen_geometry(owner, program: Program, batch_shape, dtype, rt, particles: bool):
     """
     What the device needs to know about the program's active screens, remembered on `owner` until a screen setting or a
@@ -603,6 +612,77 @@ def _screen_images(flat, geometry, batch_shape, dtype):
     return images
 
 
+def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, losses, rt):
+    """The ParticleBeam's trace: (trace, x and y of the centroid at every point, the device arrays a reverse pass reads)."""
+    late = _late()
+    dtype, batch_shape, P = incoming.dtype, incoming.batch_shape, lat.S + 1
+    n, p_in = incoming.num_particles, incoming._particles.device(rt)
+    p_out = rt.empty((*batch_shape, n, 7), dtype) if keep_outgoing else None
+    records = rt.empty_result((lat.B, P, _ffi.MOMENT_STRIDE), _F64)
+    common = (rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records),
+              _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0)
+    lost_at = rt.empty((lat.B, n), np.int32) if losses == "particles" else None  # (4 B N bytes: device memory, read back once)
+    images = []
+    if program.screens:
+        shots = _screen_geometry(owner, program, batch_shape, dtype, rt, True)
+        counts = rt.empty((lat.B, shots["cells"]), np.int32)  # (zeroed by the call, on its stream)
+        rt.check(rt.lib.lynx_track_particles_along_screens(
+            *common, *_aperture_arguments(owner, program, batch_shape, dtype, rt), _ptr(lost_at), shots["count"], shots["rows"],
+            _ptr(shots["grid"]), _ptr(shots["misalignment"]), shots["stride"], _ptr(counts)))
+        images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
+    elif losses:
+        rt.check(rt.lib.lynx_track_particles_along_losses(
+            *common, *_aperture_arguments(owner, program, batch_shape, dtype, rt), _ptr(lost_at)))
+    else:
+        rt.check(rt.lib.lynx_track_particles_along(*common))
+    rec = records.numpy().reshape(*batch_shape, P, _ffi.MOMENT_STRIDE)
+    energy = e_trace.numpy().reshape(*batch_shape, P)
+    trace = late.BeamTrace.from_records(rec, energy, lengths, names, dtype,
+                                        apertures=[step for step, _, _ in program.apertures],
+                                        screens=[step for step, _ in program.screens], screen_images=images)
+    trace.num_particles = n
+    if lost_at is not None:
+        trace.lost_at = lost_at.numpy().reshape(*batch_shape, n)
+    # a beam object has one particle count for all samples: with losses there is none to hand out
+    if keep_outgoing and not (losses and not np.all(rec[..., -1, 35] == n)):
+        out = late.ParticleBeam.__new__(late.ParticleBeam)
+        own_charges = incoming._charges is not None and incoming.is_shared
+        out._init_raw(Dual(dev=p_out), Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
+                      np.ascontiguousarray(incoming.particle_charges) if own_charges else incoming._charges, dtype,
+                      moments=Dual(np.ascontiguousarray(rec[..., -1, :])))
+        trace.outgoing = out
+    return trace, rec[..., :, (0, 2)].astype(dtype), {"records": records}  # (mean x, y of the particles alive at every point)
+
+
+def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt):
+    """The ParameterBeam's trace: (trace, x and y of mu at every point, the device arrays a reverse pass reads)."""
+    late = _late()
+    dtype, batch_shape, P = incoming.dtype, incoming.batch_shape, lat.S + 1
+    mu_t, cov_t = rt.empty((lat.B, P, 7), dtype), rt.empty((lat.B, P, 7, 7), dtype)
+    rt.check(rt.lib.lynx_track_moments_along(
+        rt.ctx, lat.handle, _ptr(e_in), _ptr(incoming._mu_d.device(rt)), _ptr(incoming._cov_d.device(rt)),
+        _ptr(mu_t), _ptr(cov_t), _ptr(e_trace)))
+    images = []
+    if program.screens:  # from the trace arrays where the kernels wrote them, before they are read back
+        shots = _screen_geometry(owner, program, batch_shape, dtype, rt, False)
+        density = rt.empty((lat.B, shots["cells"]), dtype)
+        rt.check(rt.lib.lynx_gaussian_images_along(
+            rt.ctx, dtype_code(dtype), lat.B, P, _ptr(mu_t), _ptr(cov_t), shots["count"], shots["rows"], _ptr(shots["grid"]),
+            _ptr(shots["misalignment"]), shots["stride"], _ptr(density)))
+        images = _screen_images(density.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
+    mu, cov = mu_t.numpy().reshape(*batch_shape, P, 7), cov_t.numpy().reshape(*batch_shape, P, 7, 7)
+    energy = e_trace.numpy().reshape(*batch_shape, P)
+    trace = late.BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype,
+                                        screens=[step for step, _ in program.screens], screen_images=images)
+    if keep_outgoing:
+        out = late.ParameterBeam.__new__(late.ParameterBeam)
+        out._init_raw(Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
+                      Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
+                      incoming.total_charge, dtype)
+        trace.outgoing = out
+    return trace, mu[..., :, (0, 2)], {"mu": mu_t, "cov": cov_t}
+
+
 def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False, screens: bool = False):
     """
     `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
@@ -613,106 +693,25 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     `screens`: active screens are part of the trace and make their images inside it (`lynx_track_particles_along_screens`,
     with the apertures if `losses`; `lynx_gaussian_images_along` on the moment trace of a ParameterBeam).
     """
-    from .trace import BeamTrace
-
     late = _late()
-    ParameterBeam, ParticleBeam = late.ParameterBeam, late.ParticleBeam
     leaves = list(leaves)
     if not (losses is False or losses is True or losses == "particles"):
         raise ValueError(f"track_along: losses is False, True or 'particles', not {losses!r}")
     # (raises for an active Screen without `screens`, for an active Aperture without `losses`, before anything touches the GPU)
     program = _trace_plan(owner, leaves, bool(losses), bool(screens))
-    if not isinstance(incoming, (ParameterBeam, ParticleBeam)):
+    if not isinstance(incoming, (late.ParameterBeam, late.ParticleBeam)):
         raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
     rt = get_runtime()
     cache = owner.__dict__.setdefault("_trace_cache", LatticeCache())
     dtype, batch_shape = incoming.dtype, incoming.batch_shape
     lat = _ready(cache, program, batch_shape, dtype, incoming._energy._host)
-    P = lat.S + 1
     e_in = incoming._energy.broadcast_device(rt, batch_shape)
-    e_trace = rt.empty_result((lat.B, P), dtype)
-    lengths = [getattr(el, "length", None) for el in leaves]
-    names = [el.name for el in leaves]
-    if isinstance(incoming, ParticleBeam):
-        n = incoming.num_particles
-        p_in = incoming._particles.device(rt)
-        p_out = rt.empty((*batch_shape, n, 7), dtype) if keep_outgoing else None
-        records = rt.empty_result((lat.B, P, _ffi.MOMENT_STRIDE), _F64)
-        flags = _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0
-        lost_at = None
-        shots, images = (_screen_geometry(owner, program, batch_shape, dtype, rt, True) if program.screens else None), []
-        if shots is not None:
-            A = len(program.apertures) if losses else 0
-            limits, stride = _aperture_limits(owner, program, batch_shape, dtype, rt) if A else (None, 0)
-            pairs = (C.c_int32 * max(2 * A, 1))(*[v for step, _, elliptical in program.apertures for v in (step, int(elliptical))])
-            if losses == "particles":
-                lost_at = rt.empty((lat.B, n), np.int32)
-            counts = rt.empty((lat.B, shots["cells"]), np.int32)  # (zeroed by the call, on its stream)
-            rt.check(rt.lib.lynx_track_particles_along_screens(
-                rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records), flags,
-                A, pairs, _ptr(limits), stride, _ptr(lost_at), shots["count"], shots["rows"], _ptr(shots["grid"]),
-                _ptr(shots["misalignment"]), shots["stride"], _ptr(counts)))
-            images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
-        elif losses:
-            A = len(program.apertures)
-            limits, stride = _aperture_limits(owner, program, batch_shape, dtype, rt)
-            pairs = (C.c_int32 * max(2 * A, 1))(*[v for step, _, elliptical in program.apertures for v in (step, int(elliptical))])
-            if losses == "particles":
-                lost_at = rt.empty((lat.B, n), np.int32)  # (4 B N bytes: device memory, read back once)
-            rt.check(rt.lib.lynx_track_particles_along_losses(
-                rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records), flags,
-                A, pairs, _ptr(limits), stride, _ptr(lost_at)))
-        else:
-            rt.check(rt.lib.lynx_track_particles_along(
-                rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records), flags))
-        rec = records.numpy().reshape(*batch_shape, P, _ffi.MOMENT_STRIDE)
-        energy = e_trace.numpy().reshape(*batch_shape, P)
-        trace = BeamTrace.from_records(rec, energy, lengths, names, dtype,
-                                       apertures=[step for step, _, _ in program.apertures],
-                                       screens=[step for step, _ in program.screens], screen_images=images)
-        trace.num_particles = n
-        if lost_at is not None:
-            trace.lost_at = lost_at.numpy().reshape(*batch_shape, n)
-        centre = rec[..., :, (0, 2)].astype(dtype)  # mean x, y at every point (of the particles alive there)
-        device = {"records": records}
-        # a beam object has one particle count for all samples: with losses there is none to hand out
-        if keep_outgoing and losses and not np.all(rec[..., -1, 35] == n):
-            keep_outgoing = False
-        if keep_outgoing:
-            out = ParticleBeam.__new__(ParticleBeam)
-            charges = incoming._charges
-            if charges is not None and incoming.is_shared:
-                charges = np.ascontiguousarray(incoming.particle_charges)
-            out._init_raw(Dual(dev=p_out), Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
-                          charges, dtype, moments=Dual(np.ascontiguousarray(rec[..., -1, :])))
-            trace.outgoing = out
+    e_trace = rt.empty_result((lat.B, lat.S + 1), dtype)
+    shared = (owner, program, lat, incoming, e_in, e_trace, [getattr(el, "length", None) for el in leaves], [el.name for el in leaves])
+    if isinstance(incoming, late.ParticleBeam):
+        trace, centre, device = _trace_particles(*shared, keep_outgoing, losses, rt)
     else:
-        mu_t = rt.empty((lat.B, P, 7), dtype)
-        cov_t = rt.empty((lat.B, P, 7, 7), dtype)
-        rt.check(rt.lib.lynx_track_moments_along(
-            rt.ctx, lat.handle, _ptr(e_in), _ptr(incoming._mu_d.device(rt)), _ptr(incoming._cov_d.device(rt)),
-            _ptr(mu_t), _ptr(cov_t), _ptr(e_trace)))
-        images = []
-        if program.screens:  # from the trace arrays where the kernels wrote them, before they are read back
-            shots = _screen_geometry(owner, program, batch_shape, dtype, rt, False)
-            density = rt.empty((lat.B, shots["cells"]), dtype)
-            rt.check(rt.lib.lynx_gaussian_images_along(
-                rt.ctx, dtype_code(dtype), lat.B, P, _ptr(mu_t), _ptr(cov_t), shots["count"], shots["rows"], _ptr(shots["grid"]),
-                _ptr(shots["misalignment"]), shots["stride"], _ptr(density)))
-            images = _screen_images(density.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
-        mu = mu_t.numpy().reshape(*batch_shape, P, 7)
-        cov = cov_t.numpy().reshape(*batch_shape, P, 7, 7)
-        energy = e_trace.numpy().reshape(*batch_shape, P)
-        trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype,
-                                       screens=[step for step, _ in program.screens], screen_images=images)
-        centre = mu[..., :, (0, 2)]
-        device = {"mu": mu_t, "cov": cov_t}
-        if keep_outgoing:
-            out = ParameterBeam.__new__(ParameterBeam)
-            out._init_raw(Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
-                          Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
-                          incoming.total_charge, dtype)
-            trace.outgoing = out
+        trace, centre, device = _trace_parameters(*shared, keep_outgoing, rt)
     trace.total_charge = incoming.total_charge
     if keep_device:
         trace._device = device

@@ -22,6 +22,8 @@ from oracle import lynx_oracle as o
 from .helpers import make_lattice
 from .test_gpu_parity import TOL_P
 from .test_gpu_trace import SIGMA, chain, upcast
+from .test_gpu_trace_losses import EDGE as LOSSES_EDGE
+from .test_gpu_trace_losses import criterion
 
 pytestmark = pytest.mark.gpu
 
@@ -389,3 +391,110 @@ def test_the_screens_read_their_images_from_the_trace(lx, dtype):
     # `Segment.track` keeps the reference's semantics: an active screen swallows the beam
     a.is_active = True
     assert segment.track(beam) is lx.Beam.empty
+
+
+# ---------------------------------------------------------------------------------------------
+# 8. the modes alternating on one context
+# ---------------------------------------------------------------------------------------------
+
+
+def expected_losses(lx, elements, beam, dtype):
+    """
+    `lost_at` of a lattice's active apertures and the particles on an edge, both (*batch, N), from `criterion` of
+    tests/test_gpu_trace_losses.py on the particles that enter each aperture: the outgoing particles of the plain trace of
+    what stands in front of it, apertures and screens switched off (the product's own numbers, as in test 3 above).
+    """
+    steps = [k for k, el in enumerate(elements) if isinstance(el, lx.Aperture) and el.is_active]
+    limits = [(np.asarray(elements[k].x_max, dtype=dtype), np.asarray(elements[k].y_max, dtype=dtype), elements[k].shape) for k in steps]
+    switchable = [el for el in elements if isinstance(el, (lx.Aperture, lx.Screen))]
+    active = [el.is_active for el in switchable]
+    for el in switchable:
+        el.is_active = False
+    entering = [np.asarray(lx.Segment(elements[:k]).track_along(beam).outgoing.particles) for k in steps]
+    for el, was in zip(switchable, active):
+        el.is_active = was
+    alive = np.ones(entering[0].shape[:-1], dtype=bool)
+    lost_at = np.full(alive.shape, -1, dtype=np.int32)
+    on_edge = np.zeros(alive.shape, dtype=bool)
+    for ordinal, (P, (x_max, y_max, shape)) in enumerate(zip(entering, limits)):
+        crit = criterion(P.astype(np.float64), x_max, y_max, shape)
+        with np.errstate(all="ignore"):
+            keep = np.all(crit <= 1.0, axis=0)
+            on_edge |= alive & np.any(np.abs(crit - 1.0) <= LOSSES_EDGE[np.dtype(dtype).type], axis=0)
+        lost_at[alive & ~keep] = ordinal
+        alive &= keep
+    return steps, lost_at, on_edge
+
+
+def assert_survivors(lx, trace, elements, beam, dtype):
+    """The trace's `lost_at` and its counts at every point against `expected_losses`."""
+    steps, lost_at, on_edge = expected_losses(lx, elements, beam, dtype)
+    differ = (trace.lost_at != lost_at) & ~on_edge
+    assert not differ.any(), (int(differ.sum()), np.argwhere(differ)[:5])
+    where = np.array(steps + [len(elements)])  # the element that removed the particle (-1: beyond the end)
+    # the trace's own survivor set: exactly; the criterion's: but for the particles on an edge
+    for killer, slack in ((where[trace.lost_at], 0), (where[lost_at], on_edge.sum(axis=-1))):
+        for k in range(len(elements) + 1):
+            count = (killer >= k).sum(axis=-1)  # aperture j clears its particles from point j + 1 on
+            assert np.all(np.abs(trace.num_survivors[..., k] - count) <= slack), (k, trace.num_survivors[..., k], count, slack)
+
+
+def same_trace(got, want):
+    assert np.array_equal(got.records, want.records, equal_nan=True) and np.array_equal(got.energy, want.energy)
+    assert (got.lost_at is None) == (want.lost_at is None) and (got.outgoing is None) == (want.outgoing is None)
+    if want.lost_at is not None:
+        assert np.array_equal(got.lost_at, want.lost_at) and np.array_equal(got.num_survivors, want.num_survivors)
+    if want.outgoing is not None:
+        assert np.array_equal(np.asarray(got.outgoing.particles), np.asarray(want.outgoing.particles))
+    assert got.screens == want.screens and len(got.screen_images) == len(want.screen_images)
+    for a, b in zip(got.screen_images, want.screen_images):
+        assert np.array_equal(a, b)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_the_modes_alternate_on_one_context(lx, dtype):
+    """
+    losses, losses + screens, screens, plain, losses again, losses on a second lattice of the same length, then every mode
+    once more, on ONE context: the step plan of a call is uploaded when it differs from the one on the device, and every
+    mode reads the same buffer.  n = 257: a full float32 tile and a masked one; two full float64 tiles and a masked one.
+    """
+    shape, n = (2,), 257
+    P, beam = beam_of(lx, shape, n, dtype)
+    elements = collimated_lattice(lx, shape, dtype)
+    segment = lx.Segment(elements)
+
+    def switch(elements, apertures, screens):
+        for el in elements:
+            if isinstance(el, lx.Aperture):
+                el.is_active = apertures
+            if isinstance(el, lx.Screen):
+                el.is_active = screens
+
+    def run(mode):
+        switch(elements, "losses" in mode, "screens" in mode)
+        return segment.track_along(beam, losses="particles" if "losses" in mode else False, screens="screens" in mode)
+
+    modes = [("losses",), ("losses", "screens"), ("screens",), ()]
+    first = {mode: run(mode) for mode in modes}
+    same_trace(run(("losses",)), first["losses",])
+    # a second lattice with as many elements and the collimators elsewhere (steps 2 and 6, not 1 and 5), its screens idle
+    d1, rect, q, d2, a, ell, h, b = collimated_lattice(lx, shape, dtype)
+    moved = [d1, q, rect, a, d2, h, ell, b]
+    switch(moved, True, False)
+    other = lx.Segment(moved).track_along(beam, losses="particles")
+    assert other.apertures == ["AP_RECT", "AP_ELL"] and other.num_points == first["losses",].num_points
+    # every mode once more: the bits of its first call
+    for mode in modes[1:] + modes[:1]:
+        same_trace(run(mode), first[mode])
+    # what the modes owe each other
+    assert np.array_equal(first["losses", "screens"].records, first["losses",].records, equal_nan=True)
+    assert np.array_equal(first["losses", "screens"].lost_at, first["losses",].lost_at)
+    assert np.array_equal(first["screens",].records, first[()].records) and np.all(first[()].records[..., 35] == n)
+    assert first["screens",].image_at("SCREEN_B").sum() > first["losses", "screens"].image_at("SCREEN_B").sum() > 0
+    # the survivors of both lattices are their own: nobody is lost in front of point 3 of the second lattice, and both
+    # agree with the criterion on the particles entering their own apertures
+    assert np.all(first["losses",].num_survivors[..., 2] < n) and np.all(other.num_survivors[..., :3] == n)
+    assert np.all(other.num_survivors[..., 3] < n)
+    switch(elements, True, False)
+    assert_survivors(lx, first["losses",], elements, beam, dtype)
+    assert_survivors(lx, other, moved, beam, dtype)
