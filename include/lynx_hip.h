@@ -240,9 +240,10 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
  *   d_trace_out      [B][P][36] float64 moment records, layout of LYNX_MOMENT_STRIDE, slot 34 = 1 (whole triangle)
  * The sums are taken about a reference point that travels with the beam (the sample's first particle, taken through
  * the same maps) and added in a fixed order: the same call returns the same bits.
- * This entry point and the two below are one call with or without a list of apertures and of screens: they refuse
- * the same bad arguments (LYNX_ERR_INVALID, before anything is launched; lynx_last_error starts with "beam trace: ",
- * "beam trace with losses: " or "beam trace with screens: "), and n_apertures and n_screens are at most 0x1fffffff. */
+ * This entry point and the three below are one call with or without a list of apertures, of screens and of chosen
+ * particles: they refuse the same bad arguments (LYNX_ERR_INVALID, before anything is launched; lynx_last_error starts
+ * with "beam trace: ", "beam trace with losses: ", "beam trace with screens: " or "beam trace with trajectories: "),
+ * and n_apertures and n_screens are at most 0x1fffffff.                                                               */
 int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags);
 
@@ -284,6 +285,29 @@ int lynx_track_particles_along_screens(lynx_ctx* ctx, lynx_lattice* lat, int64_t
                                        int64_t limit_stride, int32_t* d_lost_at, int32_t n_screens, const int32_t* screens,
                                        const void* d_edges, const void* d_misalignment, int64_t misalignment_stride,
                                        int32_t* d_images);
+
+/* ... with trajectories: the coordinates of n_chosen CHOSEN particles at every point (reference: the loop of
+ * plot_reference_particle_traces, segment.py:387-459 -- `xs[particle]`, `ys[particle]` behind every split element).  A
+ * superset of the entry point above: arguments as there, except that n_apertures < 0 and n_screens < 0 mean "no such
+ * list" (the call then runs the particle kernel the entry point without that list runs; their pointers are not read), and
+ *   n_chosen                >= 1
+ *   d_indices               [n_chosen] int64 on the device: 0 <= index < n_particles, any order, repeats allowed, shared
+ *                           by the batch.  The caller checks them; the kernel relies on them.
+ *   d_trajectories          [B][P][n_chosen][7], lattice dtype: chosen particle j at point k (point 0: as it came in).
+ *                           The last point has the bits of d_p_out.  A particle removed by the aperture at step k has its
+ *                           coordinates at points <= k and NaN in all seven columns from point k + 1 on.
+ *   d_trajectory_lost_in    [B][n_chosen] int32 or NULL: d_lost_at of the chosen particles (ordinal of the aperture
+ *                           that removed it, -1 for a survivor)
+ * The trajectories are read from d_p_in behind the particle kernel: d_p_out must not alias it.  One more small kernel
+ * on the same stream, through the same table and step plan; nothing else of the call changes.  lynx_last_error starts
+ * with "beam trace with trajectories: ".                                                                              */
+int lynx_track_particles_along_trajectories(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                            const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                            int32_t n_apertures, const int32_t* apertures, const void* d_limits,
+                                            int64_t limit_stride, int32_t* d_lost_at, int32_t n_screens, const int32_t* screens,
+                                            const void* d_edges, const void* d_misalignment, int64_t misalignment_stride,
+                                            int32_t* d_images, int64_t n_chosen, const int64_t* d_indices, void* d_trajectories,
+                                            int32_t* d_trajectory_lost_in);
 
 /* ... of a ParameterBeam (reference: the same loop; element.py:71-82 mu' = T mu, cov' = T cov T^T per element,
  * cavity.py:134-140,202-218): d_mu_trace [B][P][7], d_cov_trace [B][P][7][7], d_energy_trace [B][P].              */

@@ -199,12 +199,14 @@ class Segment(Element):
         """segment.py:340-356."""
         return engine.track(self, self.elements, incoming)
 
-    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True, losses=False, screens: bool = False):
+    def track_along(self, incoming, resolution=None, keep_outgoing: bool = True, losses=False, screens: bool = False,
+                    trajectories=None):
         """
         The beam ALONG the lattice: its moments and energy at the entrance and behind every leaf element (nested
         segments opened up), for every batch sample, from one pass over the particles -- the data behind the reference's
-        `plot_twiss` / `plot_twiss_over_lattice` (segment.py: `element.track` element by element) and, with
-        `resolution`, `plot_reference_particle_traces` (the lattice is `split(resolution)` first).  Returns a
+        `plot_twiss` / `plot_twiss_over_lattice` (segment.py: `element.track` element by element).  With `resolution` the
+        lattice is `split(resolution)` first, as `plot_reference_particle_traces` does; the lines of that plot are single
+        particles, which the moments do not hold: pass `trajectories` for them (below).  Returns a
         `lynx_amd.trace.BeamTrace`; `keep_outgoing=False` does not store the tracked particles (moments only).
         Unlike `plot_twiss`, zero-length elements are tracked and have a point (`BeamTrace.where_length_changes()`).
 
@@ -225,11 +227,24 @@ class Segment(Element):
         density of `mu`, `cov` at point k less the misalignment, which apertures do not touch.  The trace has `screens`,
         `screen_images`, `image_at(name_or_index)`; every active screen's `reading` returns its image afterwards (the same
         array; `get_read_beam()` is None).  Inactive screens make no image.
+
+        `trajectories` (ParticleBeam only): an int K >= 1 for particles 0 .. K - 1, or a 1-D integer array of particle
+        indices (0 <= i < N, any order, repeats allowed, shared by the batch).  The trace then has `trajectories`
+        (*batch, P, K, 7), the coordinates of chosen particle j at point k (point 0: as it came in; the last point has the
+        bits of `outgoing`), `trajectory_indices` (K,) and `at(point)["trajectories"]` -- the data of the reference's
+        `plot_reference_particle_traces` (`xs[particle]`, `ys[particle]` behind every split element), for which one
+        passes `ParticleBeam.make_linspaced(num_particles=K, ...)` and `resolution`.  With `losses` a particle removed by
+        aperture k keeps its coordinates at point k and is NaN from point k + 1 on, and `trajectory_lost_in`
+        (*batch, K) says which aperture removed it (-1: none) without the (*batch, N) array of `losses="particles"`.
+        A bool, an empty selection, non-integer indices, K > N or an index outside the beam raise ValueError, a
+        `ParameterBeam` TypeError, before anything is launched.  Without `trajectories` the call is the one it was.
         """
         if resolution is not None:
             return Segment(self.split(resolution), name=self.name).track_along(incoming, keep_outgoing=keep_outgoing,
-                                                                               losses=losses, screens=screens)
-        return engine.track_along(self, self._leaves(), incoming, keep_outgoing, losses=losses, screens=screens)
+                                                                               losses=losses, screens=screens,
+                                                                               trajectories=trajectories)
+        return engine.track_along(self, self._leaves(), incoming, keep_outgoing, losses=losses, screens=screens,
+                                  trajectories=trajectories)
 
     def forward(self, incoming):
         return self.track(incoming)

@@ -2443,6 +2443,14 @@ struct TraceScreenList {
   int64_t cells;  // sum of ny nx (track_particles_along fills it in)
 };
 
+// The chosen particles of a trace with trajectories as the host hands them over.
+struct TraceChosen {
+  int64_t count;
+  const int64_t* d_indices;  // [count]
+  void* d_trajectories;      // [B][P][count][7]
+  int32_t* d_lost_in;        // [B][count] or null
+};
+
 // TraceLosses.plan of this call on the device (either list may be null).  The plan is uploaded when it differs from the
 // one that is there (a scan calls with the same lattice over and over); the wait that upload needs is paid once per
 // lattice structure.
@@ -2486,11 +2494,12 @@ static int launch_trace_finalize(lynx_ctx* ctx, int64_t B, int32_t P, int64_t wa
 }
 
 // `ap`: the apertures of a trace with losses (null: none, and the records stand for N particles each); `sc`: the
-// screens (null: none).
+// screens (null: none); `tj`: the chosen particles of a trace with trajectories (null: none -- the launches are then
+// the very ones they were before there was such a list).
 template <typename T>
 static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in, const void* d_p_in,
                                    void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
-                                   const TraceApertures* ap, const TraceScreenList* sc) {
+                                   const TraceApertures* ap, const TraceScreenList* sc, const TraceChosen* tj) {
   constexpr int U = sizeof(T) == 4 ? 4 : 2;  // particles per lane (float32: two packed pairs)
   const int64_t B = lat->batch;
   const int32_t S = lat->n_steps, P = S + 1;
@@ -2530,6 +2539,8 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   if (sc) HIP_TRY(ctx, hipMemsetAsync(sc->d_images, 0, (size_t)B * sc->cells * sizeof(int32_t), ctx->stream));
   if (ap && ap->d_lost_at)  // every byte 0xff: -1, "survivor"; the kernel writes the cells of the lost
     HIP_TRY(ctx, hipMemsetAsync(ap->d_lost_at, 0xff, (size_t)B * N * sizeof(int32_t), ctx->stream));
+  if (tj && tj->d_lost_in)
+    HIP_TRY(ctx, hipMemsetAsync(tj->d_lost_in, 0xff, (size_t)B * tj->count * sizeof(int32_t), ctx->stream));
   // a trace with screens and without an aperture loses nobody: its records are the plain trace's (slot 35 = N)
   const bool counted = ap && (!sc || ap->count > 0);
   const TraceLosses loss{(const int64_t*)ctx->scratch_trace_plan, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0,
@@ -2547,17 +2558,26 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
                        (T*)d_p_out, slabs);
   }
   HIP_TRY(ctx, hipGetLastError());
+  if (tj) {  // behind the particle kernel, on its stream: the same table, the same plan, p_in alone
+    constexpr int64_t kChosenTile = sizeof(T) == 4 ? 128 : 64;
+    const TraceTrajectories chosen{tj->d_indices, tj->count, tj->d_trajectories, tj->d_lost_in};
+    hipLaunchKernelGGL(k_trace_trajectories<T>, dim3((unsigned)(B * ((tj->count + kChosenTile - 1) / kChosenTile))), dim3(64), 0,
+                       ctx->stream, chosen, S, table, (const T*)d_p_in, a.in_stride,
+                       (ap || sc) ? (const int64_t*)ctx->scratch_trace_plan : nullptr, (const T*)(ap ? ap->d_limits : nullptr),
+                       ap ? ap->limit_stride : (int64_t)0);
+    HIP_TRY(ctx, hipGetLastError());
+  }
   return launch_trace_finalize<T>(ctx, B, P, waves, counted ? -1 : N, d_trace_out);
 }
 
-// The three entry points of the particle trace: the checks, the bookkeeping and the dtype dispatch.  `ap` / `sc` are the
-// lists of a trace with losses / with screens, null where the entry point has none.
+// The four entry points of the particle trace: the checks, the bookkeeping and the dtype dispatch.  `ap` / `sc` / `tj`
+// are the lists of a trace with losses / with screens / with trajectories, null where the entry point has none.
 static int track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                  const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
-                                 const TraceApertures* ap, TraceScreenList* sc) {
+                                 const TraceApertures* ap, TraceScreenList* sc, const TraceChosen* tj = nullptr) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  const char* mode = sc ? "beam trace with screens: " : ap ? "beam trace with losses: " : "beam trace: ";
+  const char* mode = tj ? "beam trace with trajectories: " : sc ? "beam trace with screens: " : ap ? "beam trace with losses: " : "beam trace: ";
   const auto refuse = [&](const char* what) { return fail(ctx, LYNX_ERR_INVALID, std::string(mode) + what); };
   if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return refuse("null argument");
   if (n_particles <= 0) return refuse("n_particles must be > 0");
@@ -2575,6 +2595,15 @@ static int track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_par
       return refuse("bad screen list");
     if (sc->misalignment_stride != 0 && sc->misalignment_stride != 2 * (int64_t)sc->count)
       return refuse("the misalignments' sample stride is 0 or 2 * n_screens");
+  }
+  if (tj) {
+    if (!tj->d_indices || !tj->d_trajectories) return refuse("null argument");
+    if (tj->count < 1) return refuse("n_chosen must be >= 1");
+    if (d_p_in == d_p_out) return refuse("the trajectories are read from d_p_in: it cannot be tracked in place");
+    // one launch: a workgroup per (sample, 64 chosen particles at the least), the output indexed in int64 bytes
+    const int64_t points = (int64_t)lat->n_steps + 1, most = INT64_MAX / (7 * 8);
+    if (tj->count > most / lat->batch || tj->count * lat->batch > most / points || lat->batch * ((tj->count + 63) / 64) > 0x7fffffffLL)
+      return refuse("batch x points x n_chosen x 7 too large for one launch");
   }
   for (int32_t k = 0; ap && k < ap->count; ++k) {  // lattice order, every step at most once
     const int32_t step = ap->pairs[2 * k];
@@ -2599,9 +2628,13 @@ static int track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_par
   ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
   if (ap) ctx->wrote(ap->d_lost_at, (size_t)lat->batch * n_particles * sizeof(int32_t));
   if (sc) ctx->wrote(sc->d_images, (size_t)lat->batch * sc->cells * sizeof(int32_t));
+  if (tj) {
+    ctx->wrote(tj->d_trajectories, (size_t)lat->batch * points * tj->count * 7 * es);
+    ctx->wrote(tj->d_lost_in, (size_t)lat->batch * tj->count * sizeof(int32_t));
+  }
   return lat->dtype == LYNX_F64
-             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc)
-             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc);
+             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc, tj)
+             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc, tj);
 }
 
 int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
@@ -2626,6 +2659,21 @@ int lynx_track_particles_along_screens(lynx_ctx* ctx, lynx_lattice* lat, int64_t
   const TraceApertures ap{n_apertures, apertures, d_limits, limit_stride, d_lost_at};
   TraceScreenList sc{n_screens, screens, d_edges, d_misalignment, misalignment_stride, d_images, 0};
   return track_particles_along(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, &ap, &sc);
+}
+
+int lynx_track_particles_along_trajectories(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                            const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
+                                            int32_t n_apertures, const int32_t* apertures, const void* d_limits,
+                                            int64_t limit_stride, int32_t* d_lost_at, int32_t n_screens, const int32_t* screens,
+                                            const void* d_edges, const void* d_misalignment, int64_t misalignment_stride,
+                                            int32_t* d_images, int64_t n_chosen, const int64_t* d_indices, void* d_trajectories,
+                                            int32_t* d_trajectory_lost_in) {
+  // (a negative count: no such list -- the particle kernel is the one the call without trajectories runs)
+  const TraceApertures ap{n_apertures, apertures, d_limits, limit_stride, d_lost_at};
+  TraceScreenList sc{n_screens, screens, d_edges, d_misalignment, misalignment_stride, d_images, 0};
+  const TraceChosen tj{n_chosen, d_indices, d_trajectories, d_trajectory_lost_in};
+  return track_particles_along(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags,
+                               n_apertures < 0 ? nullptr : &ap, n_screens < 0 ? nullptr : &sc, &tj);
 }
 
 template <typename T>

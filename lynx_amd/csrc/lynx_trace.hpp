@@ -33,6 +33,12 @@
 // the particles alive where it stands are binned by numpy's rule on the screen's own edge arrays (bin_of's result, from
 // an arithmetic guess corrected against the neighbouring edges) and counted into the screen's image with integer
 // atomics -- there, because the particles of an interior point exist in registers only.
+//
+// With trajectories (lynx_track_particles_along_trajectories; k_trace_trajectories) a second, small kernel behind the
+// particle kernel of the same call takes K CHOSEN particles through the same table and the same plan and writes their
+// coordinates at every point, [B][P][K][7] -- the data of the reference's plot_reference_particle_traces (segment.py:
+// `xs[particle]`, `ys[particle]` behind every split element), which the moment records do not hold.  The particle
+// kernels above do not know about it.
 #pragma once
 
 #include "lynx_device.hpp"
@@ -569,6 +575,106 @@ __global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __rest
   }
   __syncthreads();
   if (tid < kPartialStride) write_moment_record(s, out + (b * P + k) * kPartialStride, tid);
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_trajectories: the coordinates of K chosen particles at every point.  grid.x = B * ceil(K / (64 U)), 64
+// threads: one wave serves one sample and 64 U consecutive CHOSEN particles (float32: U = 2, one packed pair per lane;
+// float64: U = 1); chosen particle j of the tile sits in lane j % 64, slot j / 64, like a particle of trace_tile.  No
+// LDS, no barrier.  The wave belongs to one sample, so a step's row comes through scalar loads as in trace_tile, and the
+// arithmetic is the streaming trace's: apply_step_pair / apply_step<double>, so the last point of a trajectory has the
+// bits of the particle kernel's p_out.  At every point the lanes of a slot store 7 scalars each, 28 / 56 bytes apart:
+// one contiguous run per wave.
+// `plan`: TraceLosses.plan of the call, or null (no apertures, no screens); a screen's code is passed over.  An
+// aperture clears `live` by trace_aperture_coded -- the particle kernel's own test -- and writes the chosen particle's
+// cell of `lost_in`; a particle that is not alive is stored as NaN in all seven columns: it has its coordinates at the
+// point it entered the aperture and none behind it.
+// The indices are the host's to check (0 <= index < N); a lane beyond K carries chosen particle K - 1 and stores nothing.
+// ---------------------------------------------------------------------------------------
+struct TraceTrajectories {
+  const int64_t* indices;  // [K]
+  int64_t count;           // K >= 1
+  void* out;               // [B][P][K][7], lattice dtype
+  int32_t* lost_in;        // [B][K], -1 everywhere before the launch; or null
+};
+
+template <typename T>
+__device__ __forceinline__ void trace_store_chosen(T* __restrict__ dst, const T (&z)[7], bool live) {
+  T v[7];
+#pragma unroll
+  for (int c = 0; c < 7; ++c) v[c] = live ? z[c] : T(__builtin_nanf(""));
+  store_particle(dst, v);
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_trajectories(TraceTrajectories t, int S, const T* __restrict__ steps,
+                                                           const T* __restrict__ p_in, int64_t in_stride,
+                                                           const int64_t* __restrict__ plan, const T* __restrict__ limits_all,
+                                                           int64_t limit_stride) {
+  constexpr int U = sizeof(T) == 4 ? 2 : 1;
+  constexpr int64_t kTile = 64 * U;
+  const int64_t K = t.count, tiles = (K + kTile - 1) / kTile;
+  const int64_t b = blockIdx.x / tiles;
+  const int64_t base = ((int64_t)blockIdx.x - b * tiles) * kTile;
+  const int lane = threadIdx.x, P = S + 1;
+  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const T* limits = limits_all ? limits_all + b * limit_stride : nullptr;
+  int32_t* lost_in = t.lost_in ? t.lost_in + b * K + base : nullptr;
+  T* out = static_cast<T*>(t.out) + (b * P * K + base + lane) * 7;  // this lane's first slot at point 0
+  bool chosen[U], live[U];
+  T z[U][7];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t j = base + lane + 64 * u;
+    chosen[u] = live[u] = j < K;
+    const int64_t idx = t.indices[chosen[u] ? j : K - 1];
+    load_particle(p_in + b * in_stride + idx * 7, z[u]);
+  }
+  if constexpr (sizeof(T) == 4) {
+    lynx_f32x2 zp[7];
+#pragma unroll
+    for (int c = 0; c < 7; ++c) zp[c] = lynx_f32x2{z[0][c], z[1][c]};
+    for (int s = 0; s <= S; ++s) {
+#pragma unroll
+      for (int c = 0; c < 7; ++c) z[0][c] = zp[c].x, z[1][c] = zp[c].y;
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+        if (chosen[u]) trace_store_chosen<T>(out + ((int64_t)s * K + 64 * u) * 7, z[u], live[u]);
+      if (s == S) break;
+      if (plan) {
+        const int code = __builtin_amdgcn_readfirstlane((int)plan[s]);
+        if (code >= 0 && !(code & 1))
+          trace_aperture_coded<T, U>(code >> 1, limits, [&](int u, T& x, T& y) {
+            x = u ? zp[0].y : zp[0].x;
+            y = u ? zp[2].y : zp[2].x;
+          }, live, lost_in, lane);
+      }
+      const T* tab = sample_steps + s * LYNX_STEP_STRIDE;  // global, wave-uniform: scalar loads
+      const int desc = (int)uniform_value(tab[LYNX_FLAGS_OFFSET]);
+      const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
+      T m[LYNX_STEP_SCALARS];
+#pragma unroll
+      for (int q = 0; q < LYNX_STEP_SCALARS; ++q) m[q] = uniform_value(tab[q]);
+      apply_step_pair(m, skind, sflags, zp);
+    }
+  } else {
+    for (int s = 0; s <= S; ++s) {
+      if (chosen[0]) trace_store_chosen<T>(out + (int64_t)s * K * 7, z[0], live[0]);
+      if (s == S) break;
+      if (plan) {
+        const int code = __builtin_amdgcn_readfirstlane((int)plan[s]);
+        if (code >= 0 && !(code & 1))
+          trace_aperture_coded<T, U>(code >> 1, limits, [&](int, T& x, T& y) {
+            x = z[0][0];
+            y = z[0][2];
+          }, live, lost_in, lane);
+      }
+      const T* tab = sample_steps + s * LYNX_STEP_STRIDE;
+      const int desc = (int)tab[LYNX_FLAGS_OFFSET];
+      const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
+      apply_step<T>(tab, skind, sflags, z[0]);
+    }
+  }
 }
 
 // ---------------------------------------------------------------------------------------

@@ -612,7 +612,42 @@ def _screen_images(flat, geometry, batch_shape, dtype):
     return images
 
 
-def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, losses, rt):
+def chosen_particles(trajectories, incoming) -> np.ndarray:
+    """
+    `trajectories` of `track_along` as the (K,) int64 indices of the chosen particles: an int K is particles 0 .. K - 1,
+    a 1-D integer array is taken as it is (any order, repeats allowed).  Everything else is refused here, on the host,
+    by value -- the kernel relies on the indices.
+    """
+    late = _late()
+    if isinstance(incoming, late.ParameterBeam):
+        raise TypeError(
+            "track_along: trajectories need particles and a ParameterBeam has none -- trace a ParticleBeam with its moments "
+            "instead (ParticleBeam.make_linspaced or ParticleBeam.from_parameters), as the reference's "
+            "plot_reference_particle_traces does")
+    n = int(incoming.num_particles)
+    what = f"track_along: trajectories={trajectories!r}"
+    if isinstance(trajectories, (bool, np.bool_)):
+        raise ValueError(f"{what}: a number of particles or an array of particle indices, not a bool")
+    if isinstance(trajectories, (int, np.integer)):
+        if trajectories < 1:
+            raise ValueError(f"{what}: at least one particle")
+        if trajectories > n:
+            raise ValueError(f"{what}: the beam has {n} particles")
+        return np.arange(int(trajectories), dtype=np.int64)
+    chosen = np.asarray(trajectories)
+    if chosen.ndim != 1:
+        raise ValueError(f"{what}: a 1-D array of particle indices, not one of shape {chosen.shape}")
+    if chosen.size == 0:
+        raise ValueError(f"{what}: an empty selection")
+    if chosen.dtype.kind not in "iu":
+        raise ValueError(f"{what}: particle indices are integers, not {chosen.dtype.name}")
+    outside = chosen[(chosen < 0) | (chosen >= n)]
+    if outside.size:
+        raise ValueError(f"{what}: index {int(outside[0])} is not a particle of a beam of {n} (0 <= index < {n})")
+    return np.ascontiguousarray(chosen, dtype=np.int64)
+
+
+def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, losses, rt, chosen=None):
     """The ParticleBeam's trace: (trace, x and y of the centroid at every point, the device arrays a reverse pass reads)."""
     late = _late()
     dtype, batch_shape, P = incoming.dtype, incoming.batch_shape, lat.S + 1
@@ -623,7 +658,24 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
               _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0)
     lost_at = rt.empty((lat.B, n), np.int32) if losses == "particles" else None  # (4 B N bytes: device memory, read back once)
     images = []
-    if program.screens:
+    paths = path_lost_in = None
+    if chosen is not None:
+        # the superset entry point; -1 for a list the same call without trajectories would not hand over either
+        K = len(chosen)
+        d_chosen = rt.to_device(chosen)  # (referenced until the call is enqueued)
+        paths = rt.empty((lat.B, P, K, 7), dtype)
+        path_lost_in = rt.empty((lat.B, K), np.int32) if losses else None
+        apertures = (_aperture_arguments(owner, program, batch_shape, dtype, rt) if losses or program.screens
+                     else (-1, None, None, 0))
+        shots = _screen_geometry(owner, program, batch_shape, dtype, rt, True) if program.screens else None
+        counts = rt.empty((lat.B, shots["cells"]), np.int32) if shots else None
+        screens = ((shots["count"], shots["rows"], _ptr(shots["grid"]), _ptr(shots["misalignment"]), shots["stride"], _ptr(counts))
+                   if shots else (-1, None, None, None, 0, None))
+        rt.check(rt.lib.lynx_track_particles_along_trajectories(
+            *common, *apertures, _ptr(lost_at), *screens, K, _ptr(d_chosen), _ptr(paths), _ptr(path_lost_in)))
+        if shots:
+            images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
+    elif program.screens:
         shots = _screen_geometry(owner, program, batch_shape, dtype, rt, True)
         counts = rt.empty((lat.B, shots["cells"]), np.int32)  # (zeroed by the call, on its stream)
         rt.check(rt.lib.lynx_track_particles_along_screens(
@@ -639,7 +691,10 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
     energy = e_trace.numpy().reshape(*batch_shape, P)
     trace = late.BeamTrace.from_records(rec, energy, lengths, names, dtype,
                                         apertures=[step for step, _, _ in program.apertures],
-                                        screens=[step for step, _ in program.screens], screen_images=images)
+                                        screens=[step for step, _ in program.screens], screen_images=images,
+                                        trajectories=None if paths is None else paths.numpy().reshape(*batch_shape, P, len(chosen), 7),
+                                        trajectory_indices=chosen,
+                                        trajectory_lost_in=None if path_lost_in is None else path_lost_in.numpy().reshape(*batch_shape, len(chosen)))
     trace.num_particles = n
     if lost_at is not None:
         trace.lost_at = lost_at.numpy().reshape(*batch_shape, n)
@@ -683,7 +738,8 @@ def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, len
     return trace, mu[..., :, (0, 2)], {"mu": mu_t, "cov": cov_t}
 
 
-def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False, screens: bool = False):
+def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False, screens: bool = False,
+                trajectories=None):
     """
     `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
     `lynx_track_moments_along`).  The packed "every element its own step" lattice is cached on `owner` (its own
@@ -692,6 +748,9 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     `losses` (True or "particles"): active apertures are part of the trace (`lynx_track_particles_along_losses`).
     `screens`: active screens are part of the trace and make their images inside it (`lynx_track_particles_along_screens`,
     with the apertures if `losses`; `lynx_gaussian_images_along` on the moment trace of a ParameterBeam).
+    `trajectories` (a number K of particles or a 1-D array of particle indices): the trace also holds the coordinates of
+    those particles at every point (`lynx_track_particles_along_trajectories`: one more small kernel behind the same
+    call's particle kernel); None: the call is the one it was.
     """
     late = _late()
     leaves = list(leaves)
@@ -701,6 +760,7 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     program = _trace_plan(owner, leaves, bool(losses), bool(screens))
     if not isinstance(incoming, (late.ParameterBeam, late.ParticleBeam)):
         raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
+    chosen = None if trajectories is None else chosen_particles(trajectories, incoming)
     rt = get_runtime()
     cache = owner.__dict__.setdefault("_trace_cache", LatticeCache())
     dtype, batch_shape = incoming.dtype, incoming.batch_shape
@@ -709,7 +769,7 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     e_trace = rt.empty_result((lat.B, lat.S + 1), dtype)
     shared = (owner, program, lat, incoming, e_in, e_trace, [getattr(el, "length", None) for el in leaves], [el.name for el in leaves])
     if isinstance(incoming, late.ParticleBeam):
-        trace, centre, device = _trace_particles(*shared, keep_outgoing, losses, rt)
+        trace, centre, device = _trace_particles(*shared, keep_outgoing, losses, rt, chosen)
     else:
         trace, centre, device = _trace_parameters(*shared, keep_outgoing, rt)
     trace.total_charge = incoming.total_charge

@@ -4,7 +4,9 @@
 
 The reference holds this data in the loop of `Segment.plot_twiss` / `plot_twiss_over_lattice` (lynx/accelerator/
 segment.py: `element.track(beam)` element by element, `beta_x`, `beta_y` of every intermediate beam) and in
-`plot_reference_particle_traces`; the plots themselves are out of scope.  One deliberate departure: `plot_twiss` skips
+`plot_reference_particle_traces` -- whose lines are the coordinates of single particles at every point, which no moment
+holds: `track_along(..., trajectories=...)` brings those along (`ParticleBeamTrace.trajectories`); the plots themselves
+are out of scope.  One deliberate departure: `plot_twiss` skips
 elements of zero length altogether (it does not track through them); here every element is tracked and has a point,
 and `where_length_changes()` gives the reference's subset.
 
@@ -64,6 +66,9 @@ class BeamTrace(Beam):
     apertures = None
     lost_in = None
     lost_at = None
+    trajectories = None
+    trajectory_indices = None
+    trajectory_lost_in = None
     screens = ()
     screen_images = ()
 
@@ -83,7 +88,8 @@ class BeamTrace(Beam):
         assert len(self.names) == len(self._lengths) == self.num_points - 1
 
     @staticmethod
-    def from_records(records, energy, lengths, names, dtype=np.float32, apertures=(), screens=(), screen_images=()) -> "BeamTrace":
+    def from_records(records, energy, lengths, names, dtype=np.float32, apertures=(), screens=(), screen_images=(),
+                     trajectories=None, trajectory_indices=None, trajectory_lost_in=None) -> "BeamTrace":
         """
         A particle trace from host arrays: `records` (*batch, P, 36) float64 moment records (layout of
         LYNX_MOMENT_STRIDE, include/lynx_hip.h; whole covariance triangle), `energy` (*batch, P), `lengths` the P - 1
@@ -91,7 +97,8 @@ class BeamTrace(Beam):
         number of particles ITS moments were taken over: it may differ from point to point and from sample to sample
         (a trace with losses); `apertures`: the indices (into `names`) of the elements that removed particles.
         `screens`: the indices (into `names`) of the active screens, which are the points they observe; `screen_images`:
-        their images, (*batch, ny, nx) each.
+        their images, (*batch, ny, nx) each.  `trajectories`: (*batch, P, K, 7), the coordinates of K chosen particles
+        at every point, with `trajectory_indices` (K,) and, for a trace with losses, `trajectory_lost_in` (*batch, K).
         """
         trace = ParticleBeamTrace.__new__(ParticleBeamTrace)
         trace.records = np.asarray(records, dtype=np.float64)
@@ -102,6 +109,16 @@ class BeamTrace(Beam):
         trace._aperture_elements = [int(k) for k in apertures]
         assert all(0 <= k < trace.num_points - 1 for k in trace._aperture_elements), trace._aperture_elements
         trace._set_screens(screens, screen_images)
+        if trajectories is not None:
+            trace.trajectories = np.asarray(trajectories, dtype=trace.dtype)
+            K = trace.trajectories.shape[-2]
+            assert trace.trajectories.shape == (*trace.batch_shape, trace.num_points, K, 7), trace.trajectories.shape
+            trace.trajectory_indices = (np.arange(K, dtype=np.int64) if trajectory_indices is None
+                                        else np.asarray(trajectory_indices, dtype=np.int64))
+            assert trace.trajectory_indices.shape == (K,), trace.trajectory_indices.shape
+            if trajectory_lost_in is not None:
+                trace.trajectory_lost_in = np.asarray(trajectory_lost_in, dtype=np.int32)
+                assert trace.trajectory_lost_in.shape == (*trace.batch_shape, K), trace.trajectory_lost_in.shape
         return trace
 
     @staticmethod
@@ -161,12 +178,15 @@ class BeamTrace(Beam):
         return self.screen_images[list(self.screens).index(k)]
 
     def at(self, name_or_index) -> dict:
-        """Everything known about one point: `s`, `name` (None for point 0), `energy`, `mu`, `cov` and every moment."""
+        """Everything known about one point: `s`, `name` (None for point 0), `energy`, `mu`, `cov` and every moment --
+        and, for a trace with trajectories, `trajectories`: the chosen particles there, (*batch, K, 7)."""
         k = self.index_of(name_or_index)
         out = {"index": k, "name": self.names[k - 1] if k else None, "s": self.s[k], "energy": self.energy[..., k],
                "mu": self.mu[..., k, :], "cov": self.cov[..., k, :, :]}
         for key in _MOMENTS + _DERIVED:
             out[key] = getattr(self, key)[..., k]
+        if self.trajectories is not None:
+            out["trajectories"] = self.trajectories[..., k, :, :]
         return out
 
     def __repr__(self) -> str:
@@ -182,6 +202,13 @@ class ParticleBeamTrace(BeamTrace):
     :ivar num_particles: the incoming N.
     :ivar lost_at: (*batch, N) int32, the ordinal in `apertures` of the aperture that removed each particle, -1 for a
         survivor (`losses="particles"`; else None).
+    :ivar trajectories: (*batch, P, K, 7) in the beam's dtype, the coordinates of chosen particle j at point k -- point 0
+        is the incoming particle (`trajectories=`; else None).  With `losses` a particle removed by the aperture that is
+        element k still has its coordinates at point k (it entered the aperture there) and is NaN in all seven columns
+        from point k + 1 on.
+    :ivar trajectory_indices: (K,) int64, which particles those are.
+    :ivar trajectory_lost_in: (*batch, K) int32, `lost_at[..., trajectory_indices]` -- with `losses=True` as well, without
+        the (*batch, N) array of `losses="particles"` (None without `losses`).
     """
 
     _aperture_elements = ()
