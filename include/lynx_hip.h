@@ -346,6 +346,29 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                         void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
                                         void* d_grad_cov_in);
 
+/* ... and of the trajectories of chosen particles (lynx_track_particles_along_trajectories): gradient of a scalar function of
+ * the COORDINATES of n_chosen particles at every point -- the clearance of halo particles to an aperture, a single trace of
+ * the reference's plot_reference_particle_traces -- together with, or without, the moment cotangents above.  Per chosen
+ * particle the reverse recursion of the mean, through a gaining cavity's kick as well: a single trajectory is differentiable
+ * where the moments are not.  Arguments as above, and
+ *   n_chosen             >= 1
+ *   d_trajectories       [B][P][n_chosen][7], lattice dtype: what lynx_track_particles_along_trajectories wrote (every
+ *                        particle alive at every point: no active apertures)
+ *   d_trajectories_bar   [B][P][n_chosen][7] float64: dL/d(coordinates of chosen particle j at point k)
+ *   d_grad_chosen_in     [B][n_chosen][7], lattice dtype: dL/d(incoming coordinates of chosen particle j), every row of a
+ *                        repeated index on its own
+ * d_trace_fwd, d_grad_trace, d_grad_mean_in and d_grad_cov_in may be NULL, all four: the call then carries no moment
+ * cotangent, and only then may the program hold cavity steps.  One more kernel, one wave per sample, that adds into the
+ * T_bar of the moment sweep on the same stream; sums in float64 in a fixed order, no atomics: the same call returns the
+ * same bits.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "beam trace gradients with
+ * trajectories: ") for a null required argument, n_chosen <= 0, moment arguments given in part, more than 256 elements.   */
+int lynx_track_particles_along_backward_trajectories(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles,
+                                                     const void* d_energy_in, const double* d_trace_fwd,
+                                                     const double* d_grad_trace, const void* d_energy_bar, void* d_grad_params,
+                                                     void* d_grad_energy_in, void* d_grad_mean_in, void* d_grad_cov_in,
+                                                     int64_t n_chosen, const void* d_trajectories,
+                                                     const double* d_trajectories_bar, void* d_grad_chosen_in);
+
 /* Reverse pass of lynx_track_particles: gradient of a scalar function L of the outgoing
  * beam's moment record with respect to every element parameter and the incoming energy
  * (the reference only claims differentiability, setup.py:14-17,

@@ -2721,12 +2721,11 @@ int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ene
 
 constexpr int32_t kTraceBwdMaxSteps = 256;  // k_build_bwd deals the steps of a program to its 256 threads (`if (tid < S)`)
 
-// What both entry points share: the trace table, the reverse sweep of the moment recursion with a cotangent at every
-// point (k_trace_moments_bwd), k_build_bwd on the "every element a step of its own" program, the energy cotangents.
-template <typename T, typename ST = T>
-static int trace_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
-                            const void* d_cov_trace, const void* d_mu_bar, const void* d_cov_bar, const void* d_energy_bar,
-                            void* d_grad_params, void* d_grad_energy_in, void* d_grad_mu_in, void* d_grad_cov_in) {
+// What the entry points share.  trace_backward_begin: the trace table and the scratch of T_bar and of k_build_bwd;
+// trace_backward_finish: k_build_bwd on the "every element a step of its own" program over the T_bar a sweep left in
+// scratch_grad[1], then the energy cotangents.
+template <typename T>
+static int trace_backward_begin(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in) {
   const int64_t B = lat->batch;
   const int32_t S = lat->n_steps, E = lat->n_elems;
   int rc;
@@ -2735,15 +2734,17 @@ static int trace_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ener
   ctx->main_dirty = true;
   if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], (size_t)B * S * kGradStride * sizeof(T))))
     return rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2],
-                           (size_t)B * (2 * E + S + 1) * 49 * sizeof(T))))
-    return rc;
+  return ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2], (size_t)B * (2 * E + S + 1) * 49 * sizeof(T));
+}
+
+template <typename T>
+static int trace_backward_finish(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_energy_bar,
+                                 void* d_grad_params, void* d_grad_energy_in) {
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps, E = lat->n_elems;
+  int rc;
   const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
   LatticeDev lv = dev_view(lat);
-  hipLaunchKernelGGL((k_trace_moments_bwd<T, ST>), dim3((unsigned)B), dim3(64), 0, ctx->stream, (int)S, table,
-                     (const ST*)d_mu_trace, (const ST*)d_cov_trace, (const ST*)d_mu_bar, (const ST*)d_cov_bar,
-                     (T*)ctx->scratch_grad[1], (T*)d_grad_mu_in, (T*)d_grad_cov_in);
-  HIP_TRY(ctx, hipGetLastError());
   size_t lds2 = build_bwd_lds_fixed<T>(S, E);
   const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
   if ((rc = ensure_bwd_tasks(ctx, lat))) return rc;
@@ -2761,6 +2762,28 @@ static int trace_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ener
     HIP_TRY(ctx, hipGetLastError());
   }
   return LYNX_OK;
+}
+
+// the reverse sweep of the moment recursion with a cotangent at every point (k_trace_moments_bwd) -> T_bar
+template <typename T, typename ST>
+static int trace_backward_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_mu_trace, const void* d_cov_trace,
+                                  const void* d_mu_bar, const void* d_cov_bar, void* d_grad_mu_in, void* d_grad_cov_in) {
+  hipLaunchKernelGGL((k_trace_moments_bwd<T, ST>), dim3((unsigned)lat->batch), dim3(64), 0, ctx->stream, (int)lat->n_steps,
+                     (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const ST*)d_mu_trace, (const ST*)d_cov_trace,
+                     (const ST*)d_mu_bar, (const ST*)d_cov_bar, (T*)ctx->scratch_grad[1], (T*)d_grad_mu_in, (T*)d_grad_cov_in);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+template <typename T, typename ST = T>
+static int trace_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                            const void* d_cov_trace, const void* d_mu_bar, const void* d_cov_bar, const void* d_energy_bar,
+                            void* d_grad_params, void* d_grad_energy_in, void* d_grad_mu_in, void* d_grad_cov_in) {
+  int rc;
+  if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
+  if ((rc = trace_backward_moments<T, ST>(ctx, lat, d_mu_trace, d_cov_trace, d_mu_bar, d_cov_bar, d_grad_mu_in, d_grad_cov_in)))
+    return rc;
+  return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
 }
 
 static int trace_backward_check(lynx_ctx* ctx, lynx_lattice* lat) {
@@ -2852,6 +2875,92 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                                   d_grad_energy_in, d_grad_mean_in, d_grad_cov_in)
              : particles_along_backward_t<float>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
                                                  d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+}
+
+// ... with the trajectories of chosen particles: k_trace_trajectories_bwd behind the moment sweep (or alone), then the
+// same k_build_bwd.  scratch_grad[0]: the states of the moment sweep (if there is one), then the float64 row sums a
+// sample's wave carries from tile to tile (if the chosen particles span several tiles).
+template <typename T>
+static int particles_along_backward_trajectories_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in,
+                                                   const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
+                                                   void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
+                                                   void* d_grad_cov_in, int64_t n_chosen, const void* d_trajectories,
+                                                   const double* d_trajectories_bar, void* d_grad_chosen_in) {
+  const int64_t B = lat->batch, S = lat->n_steps;
+  const int64_t points = B * (S + 1);
+  const bool moments = d_trace_fwd != nullptr;
+  const bool tiled = n_chosen > 64 * kChosenBwdSlots;
+  const size_t state_scalars = moments ? (size_t)points * 112 : 0;
+  const size_t partial_scalars = tiled ? (size_t)B * S * kGradStride : 0;
+  int rc;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0],
+                           std::max<size_t>(state_scalars + partial_scalars, 1) * sizeof(double))))
+    return rc;
+  double* mu = (double*)ctx->scratch_grad[0];
+  double* cov = mu + points * 7;
+  double* mu_bar = cov + points * 49;
+  double* cov_bar = mu_bar + points * 7;
+  double* partial = tiled ? (double*)ctx->scratch_grad[0] + state_scalars : nullptr;
+  if (moments) {
+    hipLaunchKernelGGL(k_trace_records_to_states, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, d_grad_trace,
+                       mu, cov, mu_bar, cov_bar);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
+  if (moments && (rc = trace_backward_moments<T, double>(ctx, lat, mu, cov, mu_bar, cov_bar, d_grad_mean_in, d_grad_cov_in)))
+    return rc;
+  hipLaunchKernelGGL(k_trace_trajectories_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, (int)S, n_chosen,
+                     (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)d_trajectories, d_trajectories_bar,
+                     (T*)ctx->scratch_grad[1], partial, moments ? 1 : 0, (T*)d_grad_chosen_in);
+  HIP_TRY(ctx, hipGetLastError());
+  return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
+}
+
+int lynx_track_particles_along_backward_trajectories(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles,
+                                                     const void* d_energy_in, const double* d_trace_fwd,
+                                                     const double* d_grad_trace, const void* d_energy_bar, void* d_grad_params,
+                                                     void* d_grad_energy_in, void* d_grad_mean_in, void* d_grad_cov_in,
+                                                     int64_t n_chosen, const void* d_trajectories,
+                                                     const double* d_trajectories_bar, void* d_grad_chosen_in) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  const std::string what = "beam trace gradients with trajectories: ";
+  if (!lat || !d_energy_in || !d_grad_params || !d_grad_energy_in || !d_trajectories || !d_trajectories_bar || !d_grad_chosen_in)
+    return fail(ctx, LYNX_ERR_INVALID, what + "null argument");
+  const int given = (d_trace_fwd != nullptr) + (d_grad_trace != nullptr) + (d_grad_mean_in != nullptr) + (d_grad_cov_in != nullptr);
+  if (given != 0 && given != 4)
+    return fail(ctx, LYNX_ERR_INVALID,
+                what + "d_trace_fwd, d_grad_trace, d_grad_mean_in and d_grad_cov_in are given together or not at all");
+  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "n_particles must be > 0");
+  if (n_chosen <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "n_chosen must be > 0");
+  if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "empty program");
+  if (lat->n_steps > kTraceBwdMaxSteps || lat->n_elems > kTraceBwdMaxSteps)
+    return fail(ctx, LYNX_ERR_INVALID, what + "more than 256 elements");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, what + "bad batch");
+  if ((int64_t)lat->batch * (lat->n_steps + 1) > 0x7fffffffLL)
+    return fail(ctx, LYNX_ERR_INVALID, what + "batch x points too large for one launch");
+  if (given)  // (a single trajectory is differentiable through the kick; the moments are not closed under it)
+    for (int32_t s = 0; s < lat->n_steps; ++s)
+      if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
+        return fail(ctx, LYNX_ERR_INVALID,
+                    "beam trace gradients of a ParticleBeam: step " + std::to_string(s) +
+                        " is a cavity step (the particles' moments are not closed under its kick)");
+  HIP_TRY(ctx, use_device(ctx));
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
+  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+  if (given) {
+    ctx->wrote(d_grad_mean_in, (size_t)lat->batch * 7 * es);
+    ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
+  }
+  ctx->wrote(d_grad_chosen_in, (size_t)lat->batch * n_chosen * 7 * es);
+  return lat->dtype == LYNX_F64
+             ? particles_along_backward_trajectories_t<double>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar,
+                                                               d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,
+                                                               n_chosen, d_trajectories, d_trajectories_bar, d_grad_chosen_in)
+             : particles_along_backward_trajectories_t<float>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar,
+                                                              d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,
+                                                              n_chosen, d_trajectories, d_trajectories_bar, d_grad_chosen_in);
 }
 
 // ---- screen read-out -------------------------------------------------------------------------

@@ -29,10 +29,13 @@
 //   k_trace_moments_bwd         the sweep, one wave per sample
 //   k_trace_energy_bwd          the cotangents of the beam energy at every point -> incoming energy and the gaining
 //                               cavities' voltage and phase (adds into what k_build_bwd wrote)
+//   k_trace_trajectories_bwd    the reverse sweep of CHOSEN particles' trajectories (lynx_track_particles_along_backward_
+//                               trajectories): a cotangent on single coordinates at every point, through the kick as well
 #pragma once
 
 #include "lynx_device.hpp"
 #include "lynx_grad.hpp"
+#include "lynx_trace.hpp"
 
 namespace lynx {
 
@@ -228,6 +231,183 @@ __global__ __launch_bounds__(64) void k_trace_energy_bwd(LatticeDev lat, const T
     }
   }
   grad_energy[b] += carry + energy_bar[b * P];
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_trajectories_bwd: grid = B, one wave per sample.  The gradient of a function of the coordinates of K chosen
+// particles at every point (what k_trace_trajectories wrote, [B][P][K][7]) is, per particle, the treatment
+// k_trace_moments_bwd gives mu -- a single trajectory is differentiable through a cavity's kick, so this sweep has no
+// "moments are not closed" case:
+//
+//   lambda_j = w[S][j]
+//   for s = S - 1 .. 0:                     (z = trajectories[s][j], the state that ENTERS step s)
+//     gaining cavity: kick_cotangents(z[4], z[5], lambda[4], lambda[5]) -> cc[8], dir4, dir5;  lambda[5] = 0
+//     T_bar[s] += lambda (x) z,  coef_bar[s] += cc          (summed over the chosen particles)
+//     lambda <- M^T lambda;  lambda[4] += dir4, lambda[5] += dir5;  lambda += w[s][j]
+//   grad_chosen_in[j] = lambda
+//
+// A tile is 64 x kChosenBwdSlots chosen particles: chosen particle j of the tile sits in lane j % 64, slot j / 64 -- the
+// layout k_trace_trajectories stored, so a slot's loads of z and of w are one contiguous run per wave.  lambda (7 per
+// slot) stays in registers; the step's row is wave-uniform and comes through scalar loads; the row, z and w of step
+// s - 1 are fetched while step s is worked on.  Per step a lane forms its 49 + 8 products, summed over its slots, and
+// the wave adds them with the trace's halving butterflies, two slabs of 32 = one kGradStride row: afterwards lanes 2 c and
+// 2 c + 1 hold the sum of cell c of the slab, the even lane writes the first slab's cell, the odd lane the second's.  K
+// beyond one tile: the same wave takes the tiles in order and carries the row sums in float64 (`partial`, [B][S][64]);
+// the last tile adds what k_trace_moments_bwd left in tbar (`add_to_tbar`; otherwise tbar is written, not added to) and
+// rounds once.  One lane owns every cell it reads and writes, the order is fixed, no atomics: the same call returns the
+// same bits, and a particle's lambda depends on nothing but its own z and w -- two rows of a repeated index are equal.
+// Arithmetic and sums are float64 for both lattice dtypes (the head of this file); z is read in the lattice's dtype.
+// A lane beyond K carries chosen particle K - 1 with lambda = 0 and w = 0: finite work, zeros into every sum.
+// ---------------------------------------------------------------------------------------
+constexpr int kChosenBwdSlots = 2;
+
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_trajectories_bwd(int S, int64_t K, const T* __restrict__ steps,
+                                                               const T* __restrict__ trajectories,
+                                                               const double* __restrict__ trajectories_bar,
+                                                               T* __restrict__ tbar, double* __restrict__ partial /* null: one tile */,
+                                                               int add_to_tbar, T* __restrict__ grad_chosen_in) {
+  using A = double;
+  constexpr int U = kChosenBwdSlots;
+  constexpr int64_t kTile = 64 * U;
+  constexpr int kRow = LYNX_COEF_OFFSET + 8;  // what the sweep reads of a step's row: the map and the kick's coefficients
+  static_assert(2 * kTraceSlab == kGradStride, "two slabs of the butterfly are one row of tbar");
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x, P = S + 1;
+  const int64_t tiles = (K + kTile - 1) / kTile;
+  const T* g_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const T* g_z = trajectories + b * (int64_t)P * K * 7;
+  const double* g_w = trajectories_bar + b * (int64_t)P * K * 7;
+  T* g_tbar = tbar + b * (int64_t)S * kGradStride;
+  double* g_part = tiles > 1 ? partial + b * (int64_t)S * kGradStride : nullptr;
+  const int cell = (lane & 1) ? kTraceSlab + (lane >> 1) : (lane >> 1);
+
+  for (int64_t tile = 0; tile < tiles; ++tile) {
+    const bool first = tile == 0, last = tile == tiles - 1;
+    bool chosen[U];
+    int64_t at[U];  // this slot's particle inside a point's [K][7]
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t j = tile * kTile + lane + 64 * u;
+      chosen[u] = j < K;
+      at[u] = (chosen[u] ? j : K - 1) * 7;
+    }
+    A lam[U][7];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        const A w = g_w[(int64_t)S * K * 7 + at[u] + c];
+        lam[u][c] = chosen[u] ? w : A(0);
+      }
+    // what step s needs from memory, fetched one step ahead
+    T n_z[U][7], n_m[kRow];
+    A n_w[U][7];
+    int n_desc;
+    auto fetch = [&](int s) {
+      const T* tab = g_steps + (int64_t)s * LYNX_STEP_STRIDE;  // wave-uniform: scalar loads
+      n_desc = (int)uniform_value(tab[LYNX_FLAGS_OFFSET]);
+#pragma unroll
+      for (int q = 0; q < kRow; ++q) n_m[q] = uniform_value(tab[q]);
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 7; ++c) {
+          n_z[u][c] = g_z[(int64_t)s * K * 7 + at[u] + c];
+          n_w[u][c] = g_w[(int64_t)s * K * 7 + at[u] + c];
+        }
+    };
+    fetch(S - 1);
+    for (int s = S - 1; s >= 0; --s) {
+      A z[U][7], w[U][7], m[kRow];
+#pragma unroll
+      for (int u = 0; u < U; ++u)
+#pragma unroll
+        for (int c = 0; c < 7; ++c) {
+          z[u][c] = (A)n_z[u][c];
+          w[u][c] = chosen[u] ? n_w[u][c] : A(0);
+        }
+#pragma unroll
+      for (int q = 0; q < kRow; ++q) m[q] = (A)n_m[q];
+      const int desc = n_desc;
+      if (s > 0) fetch(s - 1);
+
+      const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);  // uniform
+      A cc[8], dir4[U], dir5[U];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) cc[q] = A(0);
+#pragma unroll
+      for (int u = 0; u < U; ++u) dir4[u] = dir5[u] = A(0);
+      if (kick) {
+        const A* cf = m + LYNX_COEF_OFFSET;
+        A sphi, cphi;
+        phase_sincos(cf[LYNX_C_PHI], sphi, cphi);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          A kc[8];
+          kick_cotangents<A, A>(cf, sphi, cphi, z[u][4], z[u][5], lam[u][4], lam[u][5], kc, dir4[u], dir5[u]);
+#pragma unroll
+          for (int q = 0; q < 8; ++q) cc[q] += kc[q];
+          lam[u][5] = A(0);  // the linear delta was overwritten by the kick
+        }
+      }
+      // cells 0..31 and 32..63 of the row: 49 entries of lambda (x) z, the 8 coefficient cotangents, padding
+      A total[2];
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        A v[kTraceSlab];
+#pragma unroll
+        for (int q = 0; q < kTraceSlab; ++q) {
+          const int c = half * kTraceSlab + q;
+          if (c < 49) {
+            A acc = lam[0][c / 7] * z[0][c % 7];
+#pragma unroll
+            for (int u = 1; u < U; ++u) acc = fma(lam[u][c / 7], z[u][c % 7], acc);
+            v[q] = acc;
+          } else if (c < 57) {
+            v[q] = cc[c - 49];
+          } else {
+            v[q] = A(0);
+          }
+        }
+        total[half] = trace_wave_sums<A>(v, lane);
+      }
+      {
+        A sum = (lane & 1) ? total[1] : total[0];
+        const int64_t o = (int64_t)s * kGradStride + cell;
+        if (!first) sum += g_part[o];
+        if (last) {
+          if (add_to_tbar) sum += (A)g_tbar[o];
+          g_tbar[o] = (T)sum;
+        } else {
+          g_part[o] = sum;
+        }
+      }
+      // lambda <- M^T lambda, the kick's direct terms, the cotangent of point s
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        A o[7];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+          A acc = m[i] * lam[u][0];
+#pragma unroll
+          for (int k = 1; k < 7; ++k) acc = fma(m[k * 7 + i], lam[u][k], acc);
+          o[i] = acc;
+        }
+        o[4] += dir4[u];
+        o[5] += dir5[u];
+#pragma unroll
+        for (int i = 0; i < 7; ++i) lam[u][i] = o[i] + w[u][i];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      if (chosen[u]) {
+        T* out = grad_chosen_in + b * K * 7 + at[u];
+#pragma unroll
+        for (int c = 0; c < 7; ++c) out[c] = (T)lam[u][c];
+      }
+  }
 }
 
 }  // namespace lynx

@@ -706,7 +706,8 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
                       np.ascontiguousarray(incoming.particle_charges) if own_charges else incoming._charges, dtype,
                       moments=Dual(np.ascontiguousarray(rec[..., -1, :])))
         trace.outgoing = out
-    return trace, rec[..., :, (0, 2)].astype(dtype), {"records": records}  # (mean x, y of the particles alive at every point)
+    device = {"records": records} if paths is None else {"records": records, "trajectories": paths}
+    return trace, rec[..., :, (0, 2)].astype(dtype), device  # (mean x, y of the particles alive at every point)
 
 
 def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt):

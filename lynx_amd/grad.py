@@ -50,10 +50,11 @@ class Gradients:
     """
 
     def __init__(self, program, raw_dev, energy_dev, batch_shape, energy_shape, particles_dev=None,
-                 mu_dev=None, cov_dev=None):
+                 mu_dev=None, cov_dev=None, chosen_dev=None):
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
         self._particles_dev = particles_dev
         self._mu_dev, self._cov_dev = mu_dev, cov_dev
+        self._chosen_dev = chosen_dev
         self._batch_shape, self._energy_shape = tuple(batch_shape), tuple(energy_shape)
         self._raw = None
         self._cache = {}
@@ -88,6 +89,16 @@ class Gradients:
         if self._cov_dev is None:
             raise KeyError("the gradient w.r.t. cov exists for ParameterBeam VJPs only")
         return self._cov_dev.numpy()
+
+    @property
+    def chosen_particles(self) -> np.ndarray:
+        """
+        dL/d(incoming coordinates of the chosen particles), (*batch, K, 7), row j for `trajectory_indices[j]` (a repeated
+        index has a row per repeat) -- `track_along_vjp(..., trajectories=)` only.
+        """
+        if self._chosen_dev is None:
+            raise KeyError("the gradient w.r.t. chosen particles exists for track_along_vjp(..., trajectories=) only")
+        return self._chosen_dev.numpy()
 
     def __contains__(self, element) -> bool:
         return any(el is element and el._kind in DIFFERENTIABLE_KINDS for el in self._program.leaves)
@@ -487,13 +498,21 @@ class TrackAlongVJP:
     kicking cavity every element is an affine map, so a ParticleBeam's mean and covariance obey the ParameterBeam's
     recursion: one reverse sweep of that recursion over the forward trace serves both beam classes, and no particle is
     tracked a second time.
+
+    With `trajectories=` (the selection rules of `track_along`) the forward trace also keeps the coordinates of the chosen
+    particles at every point, and the call takes `trajectories_bar`: cotangents of those coordinates
+    (lynx_track_particles_along_backward_trajectories).  A single trajectory is differentiable through a cavity's kick, so
+    a ParticleBeam on a lattice with an active cavity is accepted then -- for `trajectories_bar` and `energy_bar`; a
+    moment cotangent is still refused, by the call.
     """
 
-    def __init__(self, segment, beam):
+    def __init__(self, segment, beam, trajectories=None):
         from .particles.parameter_beam import ParameterBeam
 
         if not isinstance(beam, (ParameterBeam, ParticleBeam)):
             raise TypeError(f"track_along_vjp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
+        # (by value, before anything touches the GPU; a ParameterBeam has no particles to choose: TypeError)
+        self.chosen = None if trajectories is None else engine.chosen_particles(trajectories, beam)
         leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
         # (raises for an active Screen or Aperture, naming it, before anything touches the GPU)
         self.program = engine._trace_plan(segment, leaves)
@@ -501,14 +520,47 @@ class TrackAlongVJP:
             raise NotImplementedError(
                 f"track_along_vjp: {len(leaves)} leaf elements, more than {MAX_TRACE_LEAVES} (the first one beyond is "
                 f"{leaves[MAX_TRACE_LEAVES].name!r}) -- differentiate the lattice in stretches")
+        self._cavity = None  # the first active cavity in front of a ParticleBeam: no moment cotangent passes it
         if isinstance(beam, ParticleBeam):
             for kind, first, _ in self.program.steps:
                 if kind == _ffi.STEP_CAVITY:
-                    raise NotImplementedError(
-                        f"track_along_vjp: active Cavity {leaves[first].name!r} -- the moments of a ParticleBeam are not "
-                        "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated")
+                    self._cavity = leaves[first].name
+                    break
+        if self._cavity is not None and self.chosen is None:
+            self._refuse_moments()
         self.segment, self.beam, self.leaves = segment, beam, leaves
-        self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True)
+        if self.chosen is None:
+            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True)
+        else:
+            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, trajectories=self.chosen)
+
+    def _refuse_moments(self):
+        raise NotImplementedError(
+            f"track_along_vjp: active Cavity {self._cavity!r} -- the moments of a ParticleBeam are not "
+            "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated")
+
+    def _trajectory_cotangents(self, trajectories_bar) -> np.ndarray:
+        """`trajectories_bar` as (B, P, K, 7) float64, refused by value."""
+        if self.chosen is None:
+            raise ValueError("track_along_vjp: trajectories_bar needs the trajectories of the forward trace -- pass "
+                             "trajectories= (a number of particles or an array of particle indices) to track_along_vjp")
+        batch_shape, P, K = self.beam.batch_shape, len(self.leaves) + 1, len(self.chosen)
+        w = np.asarray(trajectories_bar, dtype=np.float64)
+        want = (*batch_shape, P, K)
+        k = w.shape[-1] if w.ndim else 0
+        full = None
+        if k in (6, 7):
+            try:
+                full = np.broadcast_to(w, (*want, k))
+            except ValueError:
+                pass
+        if full is None:
+            raise ValueError(f"track_along_vjp: trajectories_bar of shape {w.shape} does not broadcast to {(*want, 6)} "
+                             f"or {(*want, 7)} (*batch, points, chosen particles, coordinates)")
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        out = np.zeros((B, P, K, 7))
+        out[..., :k] = full.reshape(B, P, K, k)
+        return out
 
     def _cotangents(self, mu_bar, cov_bar, energy_bar, readings, properties):
         batch_shape = self.beam.batch_shape
@@ -540,12 +592,25 @@ class TrackAlongVJP:
                 mb[:, k, 2] += bar[1].reshape(B)
         return mb, cb, eb
 
-    def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, **properties) -> Gradients:
+    def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, trajectories_bar=None,
+                 **properties) -> Gradients:
         """
         `mu_bar` (*batch, P, 6|7), `cov_bar` (*batch, P, 6|7, 6|7) entry by entry, `energy_bar` (*batch, P): cotangents at
         every point; `properties`: cotangents (*batch, P) of any moment property of the trace and of `energy`;
-        `readings={bpm: bar}`: of the readings of active BPMs, shaped like `bpm.reading` -- (2, *batch).
+        `readings={bpm: bar}`: of the readings of active BPMs, shaped like `bpm.reading` -- (2, *batch);
+        `trajectories_bar` (broadcastable to (*batch, P, K, 6|7)): of the coordinates of the chosen particles at every point
+        (`trajectories=` of `track_along_vjp`).  All of them in one reverse call; `Gradients.chosen_particles` is then the
+        gradient w.r.t. the chosen incoming particles, and `mu`, `cov` exist if a moment cotangent was given.
         """
+        wb = None
+        if trajectories_bar is not None:
+            wb = self._trajectory_cotangents(trajectories_bar)
+        elif self.chosen is not None:  # (the trace has trajectories: the same entry point, with no cotangent on them)
+            wb = self._trajectory_cotangents(np.zeros(7))
+        with_moments = (mu_bar is not None or cov_bar is not None or bool(readings)
+                        or any(name != "energy" for name in properties))
+        if with_moments and self._cavity is not None:
+            self._refuse_moments()
         mb, cb, eb = self._cotangents(mu_bar, cov_bar, energy_bar, readings, properties)
         rt = get_runtime()
         beam, program = self.beam, self.program
@@ -562,6 +627,24 @@ class TrackAlongVJP:
         # named, so that the uploads stay allocated until the call has been enqueued
         eb_dev = rt.to_device(eb.astype(dtype)) if np.any(eb) else None
         states = self.trace._device
+        if wb is not None:
+            K = len(self.chosen)
+            rec_dev = None
+            if with_moments:
+                rec = np.zeros((B, P, _ffi.MOMENT_STRIDE), dtype=np.float64)
+                rec[..., :7] = mb
+                rows, cols = np.triu_indices(6)
+                rec[..., 7:28] = (cb[..., rows, cols] + cb[..., cols, rows]) * np.where(rows == cols, 0.5, 1.0)
+                rec_dev = rt.to_device(rec)
+            else:
+                g_mu = g_cov = None
+            wb_dev = rt.to_device(wb)
+            g_chosen = rt.empty((*batch_shape, K, 7), dtype)
+            rt.check(rt.lib.lynx_track_particles_along_backward_trajectories(
+                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]) if with_moments else None, p(rec_dev),
+                p(eb_dev), p(g_par), p(g_en), p(g_mu), p(g_cov), K, p(states["trajectories"]), p(wb_dev), p(g_chosen)))
+            return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov,
+                             chosen_dev=g_chosen)
         if isinstance(beam, ParticleBeam):
             rec = np.zeros((B, P, _ffi.MOMENT_STRIDE), dtype=np.float64)
             rec[..., :7] = mb
@@ -579,7 +662,7 @@ class TrackAlongVJP:
         return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
 
 
-def track_along_vjp(segment, beam):
+def track_along_vjp(segment, beam, trajectories=None):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
     callable vector-Jacobian product of the moments and energies at every point:
@@ -588,8 +671,18 @@ def track_along_vjp(segment, beam):
         g = vjp(beta_x=w_x, beta_y=w_y)          # cotangents (*batch, P) of any property of the trace, or
         g = vjp(mu_bar=..., cov_bar=..., energy_bar=..., readings={bpm: ...})
         g[segment.Q1]["k1"], g.energy, g.mu, g.cov
+
+    `trajectories` (a ParticleBeam; `track_along`'s selection rules): the coordinates of the chosen particles at every point
+    are differentiated as well --
+
+        vjp = lynx_amd.grad.track_along_vjp(segment, beam, trajectories=[0, 17, 4])
+        x = vjp.trace.trajectories[..., 0]       # (*batch, P, K)
+        g = vjp(trajectories_bar=w)              # (*batch, P, K, 6|7), together with any cotangent above
+        g[segment.HCOR1]["angle"], g.chosen_particles
+
+    and an active cavity in front of a ParticleBeam is no obstacle to `trajectories_bar` and `energy_bar`.
     """
-    return TrackAlongVJP(segment, beam)
+    return TrackAlongVJP(segment, beam, trajectories)
 
 
 def track_vjp(segment, beam):
