@@ -101,7 +101,7 @@ typedef struct lynx_step {
 
 /* flags of lynx_track_particles */
 #define LYNX_TRACK_MOMENTS 1     /* also accumulate the output-beam moments (fused epilogue) */
-#define LYNX_TRACK_TWO_KERNEL 2  /* build+compose in its own launch instead of the fused prologue */
+#define LYNX_TRACK_TWO_KERNEL 2  /* accepted, no effect: build+compose is always a launch of its own */
 /* d_p_in is [N][7]: one incoming beam shared by every sample of the lattice batch.  The
  * reference's `ParticleBeam.broadcast` repeats the particles physically
  * (particle_beam.py:838-843) before a parameter scan; a beam broadcast lazily is read once

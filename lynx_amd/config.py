@@ -12,9 +12,6 @@ fused_moments = os.environ.get("LYNX_FUSED_MOMENTS", "1") != "0"
 # any beam with one extra pass when it was not accumulated.
 fused_covariance = os.environ.get("LYNX_FUSED_COVARIANCE", "0") == "1"
 
-# Build+compose in its own launch instead of the fused prologue (A/B switch).
-two_kernel = os.environ.get("LYNX_TWO_KERNEL", "0") == "1"
-
 # Delta degrees of freedom of ParticleBeam.sigma_*.  The reference spells it
 # `xs.std(dim=-1)` (lynx/particles/particle_beam.py:742), i.e. the torch default: unbiased.
 std_ddof = int(os.environ.get("LYNX_STD_DDOF", "1"))

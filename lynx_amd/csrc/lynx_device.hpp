@@ -9,8 +9,7 @@
 //               coefficients (8), a merged pair's entry inverse (4), the step's descriptor (slot 62)
 //               and, in the last step, the outgoing energy (slot 63); lynx_maps.hpp.  Written by the
 //               builders (k_build, or k_build_pieces / k_pair_products / k_emit_steps for large
-//               batches), read with scalar loads by the streaming kernel (in the optional fused
-//               variant it only ever lives in LDS).
+//               batches), read with scalar loads by the streaming kernel.
 //   partials    [B][chunks][36] double: per-workgroup moment records, each around a reference
 //               point of its own (deterministic reduction in k_reduce_moments; no float atomics).
 //
@@ -1311,10 +1310,8 @@ struct TrackArgs {
   int64_t n_particles;
   int32_t chunks;        // workgroups per sample
   int32_t tiles_per_wg;
-  int32_t fused_build;   // 1: build+compose in the prologue, 0: read steps_in
   int32_t store;         // 1: write p_out
-  int32_t lds_scratch_bytes;  // build scratch / moment-reduction slab in front of the step table
-  int32_t build_chunk;   // fused prologue: elements per compose round
+  int32_t lds_scratch_bytes;  // wave tiles / moment-reduction slab in front of the step table
   int64_t in_stride;     // scalars between the samples of p_in: N*7, or 0 for one shared incoming beam
   int32_t merged_pairs;  // the step table holds [run, cavity] pairs in merged form (the builder marks them: LYNX_DESC_PAIR)
   int32_t n_observers;   // LYNX_STEP_FLAG_OBSERVE steps of the program (their sums live behind the step table in LDS)
@@ -1824,24 +1821,24 @@ __device__ __forceinline__ void apply_program_lane(const LatticeDev& lat, int S,
 // section 7); the packed-pair form of multi-step float32 programs 5 (96 VGPRs, 32 bytes of scratch outside the step
 // loop): those wait on scalar fetches of the step table, and a fifth wave hides more of that (BASELINE config 5:
 // 0.985 -> 0.961 ms; 6 waves spill into the loop: 1.07).
-template <typename T, int MOM, bool FULL, int UNROLL, bool FUSED, bool XPOSE> constexpr int track_waves_per_simd() {
+template <typename T, int MOM, bool FULL, int UNROLL, bool XPOSE> constexpr int track_waves_per_simd() {
   if (XPOSE) return 3;
-  if (sizeof(T) == 4 && UNROLL == 2 && !FUSED && !FULL && (MOM == 0 || MOM == 3)) return 5;
+  if (sizeof(T) == 4 && UNROLL == 2 && !FULL && (MOM == 0 || MOM == 3)) return 5;
   return 1;
 }
 
-template <typename T, int MOM, bool FULL, int UNROLL, bool FUSED, bool XPOSE>
-__global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, UNROLL, FUSED, XPOSE>())) void k_track_direct(
-    LatticeDev lat, TrackArgs a, const T* __restrict__ energy_in, const T* p_in, T* p_out,
+template <typename T, int MOM, bool FULL, int UNROLL, bool XPOSE>
+__global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, UNROLL, XPOSE>())) void k_track_direct(
+    LatticeDev lat, TrackArgs a, const T* __restrict__ /* energy_in: the builders read it */, const T* p_in, T* p_out,
     T* __restrict__ energy_out, const T* __restrict__ steps_in, double* __restrict__ partials,
     double* __restrict__ obs_partials) {
-  static_assert(!XPOSE || (UNROLL * 7 * sizeof(T) == 112 && !FUSED), "XPOSE: a lane owns 112 bytes");
+  static_assert(!XPOSE || (UNROLL * 7 * sizeof(T) == 112), "XPOSE: a lane owns 112 bytes");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   announce_tail(a);
-  unsigned char* s_scratch = smem_raw;                                 // build scratch / wave tiles / reduction
+  unsigned char* s_scratch = smem_raw;                                 // wave tiles / reduction
   T* s_steps = reinterpret_cast<T*>(smem_raw + a.lds_scratch_bytes);    // [S][64]
   float* stash = reinterpret_cast<float*>(smem_raw + a.stash_offset) + threadIdx.x * 4;  // used with merged tables only
-  T* s_energy = s_steps + (size_t)lat.n_steps * LYNX_STEP_STRIDE;       // [S+1]
+  // (S + 1 scalars behind the table are left free: the launch's LDS size is what it always was)
   // observers (active BPMs): every lane's float64 sums of x and y at each of them, [2 * n_observers][256]
   double* s_obs = reinterpret_cast<double*>(smem_raw + ((a.lds_scratch_bytes + ((size_t)lat.n_steps * (LYNX_STEP_STRIDE + 1) + 1) * sizeof(T) + 7) / 8 * 8)) + threadIdx.x;
 
@@ -1886,34 +1883,21 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
 
   const bool one_run = (S == 1) && (lat.steps[0].kind == LYNX_STEP_RUN) && a.n_observers == 0;
   for (int k = 0; k < 2 * a.n_observers; ++k) s_obs[k * 256] = 0.0;
+  // float32 programs: the maps come straight from the step table with wave-uniform (scalar) loads -- no LDS
+  // staging, no barrier; float64 ones keep the table in LDS
   constexpr bool kMapInRegs = sizeof(T) == 4;
-  // Pre-built single-run fp32 program: the map comes straight from the step table with
-  // wave-uniform (scalar) loads -- no LDS staging, no barrier.
-  constexpr bool kScalarTable = !FUSED && kMapInRegs;  // address space known at compile time
-  const bool scalar_table = kScalarTable && S > 0;
   const T* g_steps = steps_in + b * (int64_t)S * LYNX_STEP_STRIDE;
 
-  if (FUSED) {
-    build_compose_sample<T>(lat, b, energy_in[b], s_steps, s_energy, s_scratch, a.build_chunk);
-    table_sinphi<T>(lat, s_steps);
-    for (int s = tid; s < S; s += kTrackThreads) s_steps[s * LYNX_STEP_STRIDE + LYNX_FLAGS_OFFSET] = (T)step_descriptor(lat, s, 0);
-    __syncthreads();
-    if (energy_out && chunk == 0 && tid == 0) energy_out[b] = s_energy[S];
-  } else if (S > 0) {
-    if (!scalar_table) load_steps_sample<T>(g_steps, S, s_steps);
+  if (S > 0) {
+    if (!kMapInRegs) load_steps_sample<T>(g_steps, S, s_steps);
     // the beam energy behind the last step was parked in the table by k_build
     if (energy_out && chunk == 0 && tid == 0) energy_out[b] = g_steps[(S - 1) * LYNX_STEP_STRIDE + LYNX_ENERGY_OFFSET];
   }
 
   T m0[kMapInRegs ? 49 : 1];
   if (one_run && kMapInRegs) {
-    if (scalar_table) {
 #pragma unroll
-      for (int i = 0; i < 49; ++i) m0[i] = uniform_value(g_steps[i]);
-    } else {
-#pragma unroll
-      for (int i = 0; i < 49; ++i) m0[i] = uniform_value(s_steps[i]);
-    }
+    for (int i = 0; i < 49; ++i) m0[i] = uniform_value(g_steps[i]);
   }
 
   LaneSums<T, MOM, FULL> sums;
@@ -2018,8 +2002,8 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
         bool alive[UNROLL];
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u) alive[u] = i0 + (int64_t)u * kLaneStep < end;
-        apply_program_lane<T, UNROLL, kScalarTable>(lat, S, g_steps, s_steps, z,
-                                                    a.n_observers ? s_obs : nullptr, &alive, stash);
+        apply_program_lane<T, UNROLL, kMapInRegs>(lat, S, g_steps, s_steps, z,
+                                                  a.n_observers ? s_obs : nullptr, &alive, stash);
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
@@ -2079,7 +2063,6 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
 //   FINAL = true : writes the moment record of the sample (include/lynx_hip.h); groups must be 1.
 // ---------------------------------------------------------------------------------------
 constexpr int kReduceStage = 70;        // rows staged per pass by the 256-thread shape: 10 per set
-constexpr int kReduceStageWide = 448;   // ... by the 1024-thread shape: 16 per set
 template <int THREADS, int STAGE> constexpr size_t reduce_lds_bytes() {
   return (size_t)(STAGE + THREADS / kPartialStride + 1) * kPartialStride * sizeof(double);
 }
@@ -2106,11 +2089,8 @@ __device__ __forceinline__ void write_moment_record(const double* s, double* dst
   }
 }
 
-// THREADS / 36 sets of 36 threads; STAGE rows staged per pass (STAGE / sets per set).  Two shapes are used:
-//   <FINAL, 256, 70>    7 sets, 22 KB of LDS: many samples, or the groups of a level;
-//   <true, 1024, 448>   28 sets, 137 KB: ONE workgroup per sample walks a few hundred rows in one pass -- beams of
-//                       few samples (BASELINE configs 2 and 3: 391 and 977 rows), where a level in between costs a
-//                       launch and a kernel boundary (~10 us) and there are no other samples to fill the CUs with.
+// THREADS / 36 sets of 36 threads; STAGE rows staged per pass (STAGE / sets per set).  One shape is used:
+//   <FINAL, 256, 70>    7 sets, 22 KB of LDS: the samples' records, or the groups of a level.
 template <bool FINAL, int THREADS, int STAGE>
 __global__ __launch_bounds__(THREADS) void k_reduce_moments(const double* __restrict__ in, int rows, int rows_per_group,
                                                              int groups, double* __restrict__ out) {

@@ -38,15 +38,13 @@ struct Knobs {
   int min_tiles_per_wg = -1;  // LYNX_MIN_TILES_PER_WG
   int async_build = -1;       // LYNX_ASYNC_BUILD       build on the second stream (1) / in line (0)
   int side_reduce = -1;       // LYNX_SIDE_REDUCE       moment reduction on the side stream (1) / in line (0)
-  int build_host_wait = -1;   // LYNX_BUILD_HOST_WAIT   the host (1) / the main stream (0) waits for an asynchronous build
+  int build_host_wait = -1;   // LYNX_BUILD_HOST_WAIT   the host (1) / the main stream (0) waits for an asynchronous build (kept: the host's wait is live from 128 MB per call; tests reach it at a small shape)
   int gather_overlap = -1;    // LYNX_GATHER_OVERLAP    RCCL gather on the side stream (1) / in line (0)
   int lanes_build_min_batch = 256;  // LYNX_LANES_BUILD_MIN_BATCH  lanes = samples build from this batch on
-  int piece = 8;              // LYNX_PIECE             elements per piece of the lanes build (tests: 1 and 3 make short lattices grow a pair tree)
-  int pair_levels_fused = 1;  // LYNX_PAIR_LEVELS_FUSED narrow pair trees in one launch (wide ones always take one per level)
-  int fuse_max_chunks = 0;    // LYNX_FUSE_MAX_CHUNKS   fused build prologue for samples of <= n workgroups (0: never)
+  int piece = 8;              // LYNX_PIECE             elements per piece of the lanes build (kept: 1 and 3 make short lattices grow the pair tree that long ones have; tests)
+  int pair_levels_fused = 1;  // LYNX_PAIR_LEVELS_FUSED narrow pair trees in one launch (wide ones always take one per level; kept: 0 is the per-level path deep trees take, reached by tests at a small shape)
   int merge_steps = 1;        // LYNX_MERGE_STEPS       [run, cavity] pairs as one unit
-  int reduce_wide = 0;        // LYNX_REDUCE_WIDE       1: one 1024-thread workgroup per sample for beams of few samples with a few hundred records each
-  int reduce_ticket = 1;      // LYNX_REDUCE_TICKET     samples with more records than one workgroup walks: both levels in one launch (0: two launches)
+  int reduce_ticket = 1;      // LYNX_REDUCE_TICKET     samples with more records than one workgroup walks: both levels in one launch (0: two launches; kept: the only independent association the ticket kernel is cross-checked against)
   int one_round = -1;         // LYNX_ONE_ROUND         at most this many workgroups per CU in a launch (0: no cap; default: 3 for single-map launches of a few rounds)
   int track_units = 1;        // LYNX_TRACK_UNITS       structured step loop (2: insist)
   int unit_pairs = 1;         // LYNX_UNIT_PAIRS        lattices of merged [run, cavity] pairs of class U: the kernel written for that form (0: the general one, 2: insist)
@@ -69,8 +67,8 @@ static void load_knobs(Knobs* k) {
       {"LYNX_SIDE_REDUCE", &k->side_reduce}, {"LYNX_BUILD_HOST_WAIT", &k->build_host_wait},
       {"LYNX_GATHER_OVERLAP", &k->gather_overlap}, {"LYNX_LANES_BUILD_MIN_BATCH", &k->lanes_build_min_batch},
       {"LYNX_PIECE", &k->piece}, {"LYNX_PAIR_LEVELS_FUSED", &k->pair_levels_fused},
-      {"LYNX_FUSE_MAX_CHUNKS", &k->fuse_max_chunks}, {"LYNX_MERGE_STEPS", &k->merge_steps},
-      {"LYNX_REDUCE_WIDE", &k->reduce_wide}, {"LYNX_REDUCE_TICKET", &k->reduce_ticket}, {"LYNX_TRACK_UNITS", &k->track_units}, {"LYNX_ONE_ROUND", &k->one_round}, {"LYNX_UNIT_PAIRS", &k->unit_pairs}, {"LYNX_BWD_UNITS", &k->bwd_units},
+      {"LYNX_MERGE_STEPS", &k->merge_steps},
+      {"LYNX_REDUCE_TICKET", &k->reduce_ticket}, {"LYNX_TRACK_UNITS", &k->track_units}, {"LYNX_ONE_ROUND", &k->one_round}, {"LYNX_UNIT_PAIRS", &k->unit_pairs}, {"LYNX_BWD_UNITS", &k->bwd_units},
       {"LYNX_BWD_MERGE", &k->bwd_merge}, {"LYNX_BWD_PAIRS", &k->bwd_pairs}, {"LYNX_BUILD_IN_TAIL", &k->build_in_tail},
       {"LYNX_SMALL_INLINE", &k->small_inline}, {"LYNX_INLINE_POOL", &k->inline_pool}, {"LYNX_ALTERNATE_ORDER", &k->alternate_order}, {"LYNX_HOST_VISIBLE_RECORDS", &k->host_visible_records}, {"LYNX_BWD_REUSE_TABLE", &k->bwd_reuse_table}};
   for (const auto& t : table) {
@@ -110,8 +108,9 @@ struct lynx_ctx {
   unsigned long_calls = 0;    // streaming launches of 256 MB and more so far (TrackArgs::reversed)
   // The step table (and unit records) the latest forward call built, for a reverse pass that follows it directly on the
   // same lattice, incoming energy and merge form: it reads them instead of building its own (BASELINE config 5: 80 us
-  // of 2.27 ms).  Good while no later call has taken a table slot (`seq`), the lattice has not been written to
-  // (`version`) and no entry point that writes device memory on the caller's behalf has run since.
+  // of 2.27 ms).  Every forward call with steps takes a slot of the ring and leaves its table here (track_table): there
+  // is no forward form without one.  Good while no later call has taken a table slot (`seq`), the lattice has not been
+  // written to (`version`) and no entry point that writes device memory on the caller's behalf has run since.
   struct FwdTable {
     const lynx_lattice* lat = nullptr;
     uint64_t version = 0;
@@ -1391,8 +1390,8 @@ struct TrackPlan {
 };
 
 template <typename T>
-static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, int64_t N, int32_t S, bool fused,
-                            bool moments, bool full_cov) {
+static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, int64_t N, int32_t S, bool moments,
+                            bool full_cov) {
   TrackPlan p;
   p.full_cov = full_cov;
   constexpr int P = 16 / (int)sizeof(T);  // particles per lane of a wave tile
@@ -1402,9 +1401,7 @@ static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, i
   p.mom_mode = knob(kn.mom, sizeof(T) == 4 ? 2 : 1);
   if (sizeof(T) == 8 || p.mom_mode < 2 || p.mom_mode > 3) p.mom_mode = sizeof(T) == 4 ? 2 : 1;
   p.a.n_particles = N;
-  p.a.fused_build = (fused && S > 0) ? 1 : 0;
   p.a.store = 0;
-  p.a.build_chunk = 1;
   p.a.tail_flag = nullptr;
   p.a.tail_seq = 0;
   p.a.tail_wg = 0;
@@ -1418,8 +1415,7 @@ static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, i
                           !(lat->h_steps[0].flags & LYNX_STEP_FLAG_OBSERVE);
   // (with the whole covariance in float32 lane sums the tile form runs out of registers: 1.23 vs 1.13 ms on C4)
   // (and short samples leave most wave tiles cut: 700 particles per sample 0.79 vs 0.72 ms per 20 M particles)
-  p.xpose = !p.a.fused_build &&
-            knob(kn.xpose, ((sizeof(T) == 8 || (single_map && !full_cov)) && N >= 8 * 64 * P) ? 1 : 0) != 0;
+  p.xpose = knob(kn.xpose, ((sizeof(T) == 8 || (single_map && !full_cov)) && N >= 8 * 64 * P) ? 1 : 0) != 0;
   int u = knob(kn.unroll, p.xpose ? P : (sizeof(T) == 4 ? (S > 1 ? 2 : 4) : 1));
   if (u != 1 && u != 2 && u != 4) u = 2;
   if (sizeof(T) == 8 && u > 2) u = 2;
@@ -1459,10 +1455,6 @@ static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, i
   if (moments)
     scratch = std::max<size_t>(scratch, (size_t)(full_cov ? kMomSlabScalars : kMomSlabScalarsCompact) * (p.mom_mode >= 2 ? 4 : 8));
   if (p.xpose) scratch = std::max<size_t>(scratch, (size_t)(kTrackThreads / 64) * kWaveTileBytes);
-  if (p.a.fused_build) {
-    p.a.build_chunk = build_chunk(lat->n_elems, sizeof(T) == 4 ? 32 : 64);
-    scratch = std::max<size_t>(scratch, build_scratch_bytes(p.a.build_chunk, sizeof(T)));
-  }
   scratch = (scratch + 15) / 16 * 16;
   p.a.lds_scratch_bytes = (int32_t)scratch;
   p.a.n_observers = lat ? lat->n_observers : 0;
@@ -1471,11 +1463,10 @@ static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, i
   return p;
 }
 
-template <typename T, int MOM, bool FULL, int UNROLL, bool FUSED, bool XPOSE>
-static int launch_direct_inst(lynx_ctx* ctx, const TrackPlan& p, const LatticeDev& lv, const void* d_energy_in,
-                              const void* d_p_in, void* d_p_out, void* d_energy_out, const void* d_steps,
-                              double* d_partials, double* d_obs) {
-  int rc = allow_lds(ctx, k_track_direct<T, MOM, FULL, UNROLL, FUSED, XPOSE>, p.lds);
+// The launch of a streaming kernel, whichever it is: p.grid workgroups with `lds` bytes on the main stream.
+template <typename K, typename... Args>
+static int launch_streaming(lynx_ctx* ctx, const TrackPlan& p, K kernel, size_t lds, const Args&... args) {
+  int rc = allow_lds(ctx, kernel, lds);
   if (rc) return rc;
   // Events ride on the dispatch itself (hipExtLaunchKernelGGL: start / stop timestamps of this kernel)
   // instead of separate marker packets in front of and behind it: `done` is what the build stream waits
@@ -1486,13 +1477,19 @@ static int launch_direct_inst(lynx_ctx* ctx, const TrackPlan& p, const LatticeDe
     HIP_TRY(ctx, hipEventCreateWithFlags(&e0, timing_event_flags(ctx)));
     HIP_TRY(ctx, hipEventCreateWithFlags(&e1, timing_event_flags(ctx)));
   }
-  hipExtLaunchKernelGGL((k_track_direct<T, MOM, FULL, UNROLL, FUSED, XPOSE>), dim3(p.grid), dim3(kTrackThreads),
-                        (std::uint32_t)p.lds, ctx->stream, e0, e1, 0u, lv, p.a, (const T*)d_energy_in, (const T*)d_p_in,
-                        (T*)d_p_out, (T*)d_energy_out, (const T*)d_steps, d_partials, d_obs);
+  hipExtLaunchKernelGGL(kernel, dim3(p.grid), dim3(kTrackThreads), (std::uint32_t)lds, ctx->stream, e0, e1, 0u, args...);
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->profiling) ctx->prof_events.emplace_back(e0, e1);
   ctx->last_stream_stop = e1;  // what "this streaming kernel has finished" is, for the build stream
   return LYNX_OK;
+}
+
+template <typename T, int MOM, bool FULL, int UNROLL, bool XPOSE>
+static int launch_direct_inst(lynx_ctx* ctx, const TrackPlan& p, const LatticeDev& lv, const void* d_energy_in,
+                              const void* d_p_in, void* d_p_out, void* d_energy_out, const void* d_steps,
+                              double* d_partials, double* d_obs) {
+  return launch_streaming(ctx, p, k_track_direct<T, MOM, FULL, UNROLL, XPOSE>, p.lds, lv, p.a, (const T*)d_energy_in,
+                          (const T*)d_p_in, (T*)d_p_out, (T*)d_energy_out, (const T*)d_steps, d_partials, d_obs);
 }
 
 #define LYNX_LAUNCH_ARGS ctx, p, lv, d_energy_in, d_p_in, d_p_out, d_energy_out, d_steps, d_partials, d_obs
@@ -1502,15 +1499,10 @@ static int launch_direct_inst(lynx_ctx* ctx, const TrackPlan& p, const LatticeDe
 
 template <typename T, int MOM, bool FULL, int U>
 static int launch_direct_mu(LYNX_LAUNCH_PARAMS) {
-  if (p.a.fused_build) {
-    // the fused prologue is an option for jobs of a few workgroups: one particle per lane only
-    if constexpr (U == 1) return launch_direct_inst<T, MOM, FULL, 1, true, false>(LYNX_LAUNCH_ARGS);
-    else return fail(ctx, LYNX_ERR_INVALID, "fused build: one particle per lane");
-  }
   if constexpr (U * 7 * sizeof(T) == 112) {
-    if (p.xpose) return launch_direct_inst<T, MOM, FULL, U, false, true>(LYNX_LAUNCH_ARGS);
+    if (p.xpose) return launch_direct_inst<T, MOM, FULL, U, true>(LYNX_LAUNCH_ARGS);
   }
-  return launch_direct_inst<T, MOM, FULL, U, false, false>(LYNX_LAUNCH_ARGS);
+  return launch_direct_inst<T, MOM, FULL, U, false>(LYNX_LAUNCH_ARGS);
 }
 
 template <typename T, int MOM, bool FULL>
@@ -1607,20 +1599,8 @@ static int launch_units_inst(lynx_ctx* ctx, const TrackPlan& p, int32_t U, int32
   const size_t lds = units_lds_bytes((size_t)p.a.lds_scratch_bytes, U);
   auto kernel = k_track_units<MOM, FULL, PAIRS>;
   if constexpr (PAIR_FORM) kernel = k_track_unit_pairs<MOM, FULL>;
-  int rc = allow_lds(ctx, kernel, lds);
-  if (rc) return rc;
-  hipEvent_t e0 = nullptr, e1 = p.done;
-  if (ctx->profiling) {  // every profiled launch needs time stamps of its own
-    HIP_TRY(ctx, hipEventCreateWithFlags(&e0, timing_event_flags(ctx)));
-    HIP_TRY(ctx, hipEventCreateWithFlags(&e1, timing_event_flags(ctx)));
-  }
-  hipExtLaunchKernelGGL(kernel, dim3(p.grid), dim3(kTrackThreads), (std::uint32_t)lds, ctx->stream, e0, e1,
-                        0u, p.a, U, S, (const float*)d_p_in, (float*)d_p_out, (float*)d_energy_out, (const float*)d_steps,
-                        (const float*)d_units, (const float*)d_extras, d_partials);
-  HIP_TRY(ctx, hipGetLastError());
-  if (ctx->profiling) ctx->prof_events.emplace_back(e0, e1);
-  ctx->last_stream_stop = e1;
-  return LYNX_OK;
+  return launch_streaming(ctx, p, kernel, lds, p.a, U, S, (const float*)d_p_in, (float*)d_p_out, (float*)d_energy_out,
+                          (const float*)d_steps, (const float*)d_units, (const float*)d_extras, d_partials);
 }
 
 static int launch_units(lynx_ctx* ctx, const TrackPlan& p, int32_t U, int32_t S, const void* d_p_in, void* d_p_out,
@@ -1641,153 +1621,223 @@ static int launch_units(lynx_ctx* ctx, const TrackPlan& p, int32_t U, int32_t S,
 #undef LYNX_UNITS_ARGS
 }
 
+// The step table of one track call (S > 0): the slot of the ring it took, how it was built, and what the streaming kernel
+// reads of it.
+struct TrackTable {
+  int slot = -1;            // of the ring of tables (-1: S = 0, no table)
+  bool async = false;       // built on the second stream
+  bool tail = false;        // ... behind the tail of an earlier streaming kernel: this call's kernel announces its own
+  bool short_call = false;  // from half a million particles up to 128 MB of them, no cavity
+  const void* d_steps = nullptr;
+  const void* d_units = nullptr;  // use_units: the slot's compact unit records and their class-D extras
+  const void* d_extras = nullptr;
+  int n_units = 0;
+  bool use_units = false;   // the structured step loop (k_track_units / k_track_unit_pairs) walks this call
+};
+
+// Builds the step table of this call: takes the next slot of the ring, decides the merged form (p.a.merged_pairs and,
+// with it, the LDS stash behind the table), where the build runs and who waits for it, launches it, and leaves the table
+// to a reverse pass that may follow (lynx_ctx::fwd_table).
+template <typename T>
+static int track_table(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, int32_t S, const void* d_energy_in,
+                       const void* d_energy_out, int flags, TrackPlan& p, TrackTable* t) {
+  int rc;
+  const int slot = t->slot = (int)(ctx->seq++ % (unsigned)lynx_ctx::kTableSlots);
+  const size_t need = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[slot], &ctx->scratch_steps_bytes[slot], need))) return rc;
+  // [run, cavity] pairs in merged form for the packed float32 step loop (one 7x7 application
+  // per pair); LYNX_TRACK_SEQUENTIAL_STEPS keeps every step on its own
+  bool has_pair = false;
+  for (int32_t s = 1; s < S; ++s)
+    has_pair |= lat->h_steps[s].kind == LYNX_STEP_CAVITY && lat->h_steps[s - 1].kind == LYNX_STEP_RUN &&
+                !(lat->h_steps[s - 1].flags & LYNX_STEP_FLAG_OBSERVE);
+  p.a.merged_pairs = has_pair && sizeof(T) == 4 && p.unroll == 2 &&
+                     !(flags & LYNX_TRACK_SEQUENTIAL_STEPS) && ctx->knobs.merge_steps;
+  if (p.a.merged_pairs) {  // four floats of LDS per lane for pairs that take the rows form (kEntryStash)
+    p.lds = (p.lds + 15) / 16 * 16;
+    p.a.stash_offset = (int32_t)p.lds;
+    p.lds += (size_t)kTrackThreads * 4 * sizeof(float);
+  }
+  // The second stream pays once the streaming kernel is long enough to hide a build under; below half a
+  // million particles per call the extra event traffic costs more host time than the overlap returns
+  // (BASELINE config 2: 31 -> 46 us per call with it).
+  // SHORT calls in between (from half a million particles up to 128 MB of them: BASELINE config 3, 1 M particles,
+  // 29 us of kernel) take what the queue says: kernels of one queue follow each other without a gap, a hop to
+  // another queue costs 10-20 us of latency (kernel timeline, profiles/r04_*_timeline.txt).  If the main stream is
+  // IDLE -- the caller waits for every result -- there is nothing to hide the build under and the hops are pure
+  // loss: build, stream and reduce back to back on the main stream, no event at all.  If it is BUSY -- calls are
+  // pipelined -- the build goes to the second stream, where it runs underneath the previous call's kernels, and only
+  // the reduction stays in line (the side stream's hop is worth it for long kernels only).
+  const bool half_million = B * N >= (int64_t)512 << 10;
+  t->short_call = half_million && (size_t)B * N * 7 * sizeof(T) < ((size_t)128 << 20) && !lat->has_cavity;
+  bool inline_all = false;
+  if (t->short_call && ctx->knobs.async_build < 0)
+    inline_all = knob(ctx->knobs.small_inline, ctx->main_idle ? 1 : 0) != 0;
+  const bool async = t->async = knob(ctx->knobs.async_build, half_million && !inline_all ? 1 : 0) != 0;
+  hipStream_t bs = async ? ctx->s_build : ctx->stream;
+  if (async) {
+    // the table slot was last read by the streaming kernel kTableSlots calls ago
+    if (ctx->streamed_valid[slot]) HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_streamed[slot], 0));
+    // ... and the build starts in the TAIL of the streaming kernel before the one enqueued last (which has the GPU
+    // to itself when it gets there), not at that kernel's head
+    t->tail = ctx->can_wait_value && ctx->knobs.build_in_tail && !t->short_call;  // (a short kernel has no tail worth waiting for)
+    if (t->tail && ctx->tail_seq >= 2)
+      HIP_TRY(ctx, hipStreamWaitValue32(bs, ctx->d_tail_flag, ctx->tail_seq - 1, hipStreamWaitValueGte, 0xffffffffu));
+    // what the build reads (energy, lattice pool) may have been written on the main stream
+    if (ctx->main_dirty || (ctx->main_wrote && ctx->main_wrote == d_energy_in)) {
+      HIP_TRY(ctx, hipEventRecord(ctx->ev_mark, ctx->stream));
+      HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_mark, 0));
+      ctx->main_dirty = false;
+      ctx->main_wrote = nullptr;
+    }
+  }
+  float* d_units_w = nullptr;
+  float* d_extras_w = nullptr;
+  if constexpr (sizeof(T) == 4) {
+    // multi-step programs: walked as units with structured maps (lynx_units.hpp); LYNX_TRACK_UNITS=0 keeps the
+    // dense step loop of k_track_direct
+    // (LYNX_TRACK_UNITS=2: insist -- an error if this call cannot take the structured loop; for tests)
+    const int want_units = ctx->knobs.track_units;
+    // (k_track_units addresses a sample's particles with 32-bit byte offsets: samples below 4 GiB)
+    if (S > 1 && (p.unroll == 2 || p.unroll == 4) && !p.xpose && p.a.n_observers == 0 && want_units &&
+        (uint64_t)N * 28u + ((uint64_t)1 << 20) < ((uint64_t)1 << 32)) {
+      if ((rc = ensure_units_plan(ctx, lat, p.a.merged_pairs != 0))) return rc;
+      t->use_units = lat->units_ok[p.a.merged_pairs ? 1 : 0];
+    }
+    if (want_units == 2 && !t->use_units)
+      return fail(ctx, LYNX_ERR_INVALID, "LYNX_TRACK_UNITS=2: this call does not take the structured step loop");
+    if (t->use_units) {
+      const int64_t n = B * lat->units[p.a.merged_pairs ? 1 : 0].n_units;
+      const int xs = lynx_ctx::kTableSlots + slot;
+      if ((rc = ensure_scratch(ctx, &ctx->scratch_units[slot], &ctx->scratch_units_bytes[slot], (size_t)n * kUnitStride * sizeof(float))) ||
+          (rc = ensure_scratch(ctx, &ctx->scratch_units[xs], &ctx->scratch_units_bytes[xs], (size_t)n * kUnitExtraStride * sizeof(float))))
+        return rc;
+      t->d_units = d_units_w = (float*)ctx->scratch_units[slot];
+      t->d_extras = d_extras_w = (float*)ctx->scratch_units[xs];
+      t->n_units = lat->units[p.a.merged_pairs ? 1 : 0].n_units;
+    }
+  }
+  if ((rc = launch_build<T>(ctx, lat, bs, d_energy_in, ctx->scratch_steps[slot], nullptr, p.a.merged_pairs, async, d_units_w, d_extras_w)))
+    return rc;
+  if (async) {
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_built[slot], bs));
+    // The HOST waits for the build instead of the main stream: no barrier packet with a foreign signal in front of
+    // the streaming kernel (measured on the 128-sample shard of BASELINE config 4: step - kernel 18.8 -> 8.5-10 us,
+    // c3big 17.9 -> 8-14, config 4 itself 20 -> 14).  The build of this call started when the streaming kernel of
+    // call n - kTableSlots + 1 began, so by now the GPU still has about two calls queued.  Not for lattices with
+    // cavities: their build (k_cavity_flags + the lanes kernels) takes most of a streaming kernel's time next to a
+    // VALU-bound kernel, and the host's wake-up would sit on the critical path (BASELINE config 5: 0.932 -> 0.947
+    // ms/step with it).  LYNX_BUILD_HOST_WAIT=0 / 1 forces the main-stream / host wait.
+    // Nor for short streaming kernels (BASELINE config 3, 1 M particles: 29 us of kernel, 22 us of build -- the
+    // host would be the pacemaker: 48 -> 75 us/step): from 128 MB of particles per call.
+    const bool long_kernel = (size_t)B * N * 7 * sizeof(T) >= ((size_t)128 << 20);
+    if (knob(ctx->knobs.build_host_wait, (lat->has_cavity || !long_kernel) ? 0 : 1)) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_built[slot]));
+    else HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_built[slot], 0));
+  }
+  t->d_steps = ctx->scratch_steps[slot];
+  std::lock_guard<std::mutex> lock(ctx->mu);
+  ctx->fwd_table.lat = lat;
+  ctx->fwd_table.version = lat->version;
+  ctx->fwd_table.energy = d_energy_in;
+  ctx->fwd_table.energy_bytes = (size_t)B * sizeof(T);
+  ctx->fwd_table.slot = slot;
+  ctx->fwd_table.merged = p.a.merged_pairs;
+  ctx->fwd_table.units = t->use_units;
+  ctx->fwd_table.seq = ctx->seq;
+  ctx->fwd_table.valid = d_energy_out != d_energy_in;  // (a call that overwrites its own incoming energy leaves nothing to come back to)
+  return LYNX_OK;
+}
+
+// Records of the workgroups (`rows` per sample, in the ring slot's buffer) -> record of the sample, on the side stream
+// behind the streaming kernel's stop event (`side`) or in line on the main stream.  One 256-thread workgroup per sample
+// walks up to 70 rows; more rows go through a level of <= 64 groups first (rows_per_group grows with the beam).
+static int reduce_moment_records(lynx_ctx* ctx, int64_t B, int rows, bool side, lynx_ctx::PartialSlot* ring,
+                                 const double* d_partials, double* d_moments_out) {
+  int rc;
+  hipStream_t rs = ctx->stream;
+  if (side) {
+    rs = ctx->s_side;
+    HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->last_stream_stop, 0));
+  } else {
+    // in line: the side stream may still be reducing into a block the allocator has not seen freed; the main
+    // stream's own order covers everything else
+    ctx->side_wrote = nullptr;
+  }
+  const double* level_in = d_partials;
+  constexpr size_t lds = reduce_lds_bytes<256, kReduceStage>();
+  if (rows > kReduceStage) {
+    const int rpg = std::max((rows + 63) / 64, B <= 4 ? 32 : 1);  // (few samples: no point in groups of a handful of rows)
+    const int groups = (rows + rpg - 1) / rpg;
+    const size_t need = (size_t)B * groups * kPartialStride * sizeof(double);
+    // one buffer: its users follow each other on one stream (side or main), and a change of stream joins first
+    if ((rc = ensure_scratch(ctx, &ctx->scratch_level, &ctx->scratch_level_bytes, need))) return rc;
+    if (ctx->level_on_side != side) {
+      if (side) {  // earlier in-line levels ran on the main stream: the side stream waits for them
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_main_mark, ctx->stream));
+        HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_side, ctx->ev_main_mark, 0));
+      } else if ((rc = join_side(ctx))) {
+        return rc;
+      }
+      ctx->level_on_side = side;
+    }
+    if (ctx->knobs.reduce_ticket) {
+      // both levels in one launch: the workgroup that draws a sample's last ticket adds its group records up
+      if ((rc = ensure_tickets(ctx, (size_t)B))) return rc;
+      hipLaunchKernelGGL((k_reduce_moments_ticket<256, kReduceStage>), dim3((unsigned)(B * groups)), dim3(256), lds, rs,
+                         level_in, rows, rpg, groups, (double*)ctx->scratch_level, ctx->scratch_tickets, d_moments_out);
+      HIP_TRY(ctx, hipGetLastError());
+      rows = 0;
+    } else {
+      hipLaunchKernelGGL((k_reduce_moments<false, 256, kReduceStage>), dim3((unsigned)(B * groups)), dim3(256), lds, rs,
+                         level_in, rows, rpg, groups, (double*)ctx->scratch_level);
+      HIP_TRY(ctx, hipGetLastError());
+      level_in = (const double*)ctx->scratch_level;
+      rows = groups;
+    }
+  }
+  if (rows > 0) {
+    hipLaunchKernelGGL((k_reduce_moments<true, 256, kReduceStage>), dim3((unsigned)B), dim3(256), lds, rs, level_in,
+                       rows, rows, 1, d_moments_out);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  if (side) {
+    // one event: the ring slot's.  The host has seen its previous recording complete before this call took the
+    // slot, so whatever side operation still carries it has finished and retires on the next look.
+    {
+      std::lock_guard<std::mutex> lock(ctx->mu);
+      retire_side_ops(ctx, false);
+    }
+    HIP_TRY(ctx, hipEventRecord(ring->reduced, rs));
+    ring->pending = true;
+    side_op_issued(ctx, ring->reduced, d_moments_out, nullptr, false);
+    ctx->side_wrote = d_moments_out;
+  }
+  return LYNX_OK;
+}
+
+// One track call: plan, step table, record buffers, streaming launch, moment reduction.
 template <typename T>
 static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev& lv, int64_t B, int64_t N,
                              const void* d_energy_in, const void* d_p_in, void* d_p_out, void* d_energy_out,
                              double* d_moments_out, int flags, double* d_observations = nullptr) {
   const int32_t S = lv.n_steps;
   const bool moments = (flags & (LYNX_TRACK_MOMENTS | LYNX_TRACK_COVARIANCE)) != 0;
-  // Fused prologue vs separate build launch.  Default: separate launch (LYNX_FUSE_MAX_CHUNKS
-  // = 0).  In the fused variant every workgroup of a sample rebuilds that sample's maps in
-  // its prologue; that only pays with few, long-lived workgroups per sample, which stream
-  // ~15 % slower than many small ones, and it forces the step table
-  // through LDS instead of scalar loads.  Set LYNX_FUSE_MAX_CHUNKS=<n> to fuse whenever a
-  // sample is covered by <= n workgroups.
   const bool full_cov = (flags & LYNX_TRACK_COVARIANCE) != 0;
-  TrackPlan p = plan_track<T>(ctx, lat, B, N, S, true, moments, full_cov);
-  bool fused = S > 0 && !(flags & LYNX_TRACK_TWO_KERNEL) && p.a.chunks <= ctx->knobs.fuse_max_chunks && p.unroll == 1;
-  if (!fused) p = plan_track<T>(ctx, lat, B, N, S, false, moments, full_cov);
+  TrackPlan p = plan_track<T>(ctx, lat, B, N, S, moments, full_cov);
   p.a.store = d_p_out ? 1 : 0;
   const bool shared_in = (flags & LYNX_TRACK_SHARED_INPUT) != 0;
   p.a.in_stride = shared_in ? 0 : N * 7;
   p.a.merged_pairs = 0;
-  const void* d_steps = nullptr;
-  const void* d_units = nullptr;
-  const void* d_extras = nullptr;
-  int n_units = 0;
-  bool use_units = false;
-  bool tail = false;
   int rc;
-  int slot = -1;
-  bool async_build = false;
-  bool short_call = false;
-  // what this call writes for the caller may hold the incoming energy of the table kept for a reverse pass (a fused
-  // call takes no table slot and keeps no table: nothing else would notice)
+  // what this call writes for the caller may hold the incoming energy of the table kept for a reverse pass
   ctx->wrote(d_p_out, (size_t)B * N * 7 * sizeof(T));
   ctx->wrote(d_energy_out, (size_t)B * sizeof(T));
   ctx->wrote(d_moments_out, (size_t)B * LYNX_MOMENT_STRIDE * sizeof(double));
   ctx->wrote(d_observations, lat ? (size_t)B * lat->n_observers * 2 * sizeof(double) : 0);
-  if (S > 0 && !fused) {
-    slot = (int)(ctx->seq++ % (unsigned)lynx_ctx::kTableSlots);
-    const size_t need = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
-    if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[slot], &ctx->scratch_steps_bytes[slot], need))) return rc;
-    // [run, cavity] pairs in merged form for the packed float32 step loop (one 7x7 application
-    // per pair); LYNX_TRACK_SEQUENTIAL_STEPS keeps every step on its own
-    bool has_pair = false;
-    for (int32_t s = 1; s < S; ++s)
-      has_pair |= lat->h_steps[s].kind == LYNX_STEP_CAVITY && lat->h_steps[s - 1].kind == LYNX_STEP_RUN &&
-                  !(lat->h_steps[s - 1].flags & LYNX_STEP_FLAG_OBSERVE);
-    p.a.merged_pairs = has_pair && sizeof(T) == 4 && p.unroll == 2 &&
-                       !(flags & LYNX_TRACK_SEQUENTIAL_STEPS) && ctx->knobs.merge_steps;
-    if (p.a.merged_pairs) {  // four floats of LDS per lane for pairs that take the rows form (kEntryStash)
-      p.lds = (p.lds + 15) / 16 * 16;
-      p.a.stash_offset = (int32_t)p.lds;
-      p.lds += (size_t)kTrackThreads * 4 * sizeof(float);
-    }
-    // The second stream pays once the streaming kernel is long enough to hide a build under; below half a
-    // million particles per call the extra event traffic costs more host time than the overlap returns
-    // (BASELINE config 2: 31 -> 46 us per call with it).
-    // SHORT calls in between (from half a million particles up to 128 MB of them: BASELINE config 3, 1 M particles,
-    // 29 us of kernel) take what the queue says: kernels of one queue follow each other without a gap, a hop to
-    // another queue costs 10-20 us of latency (kernel timeline, profiles/r04_*_timeline.txt).  If the main stream is
-    // IDLE -- the caller waits for every result -- there is nothing to hide the build under and the hops are pure
-    // loss: build, stream and reduce back to back on the main stream, no event at all.  If it is BUSY -- calls are
-    // pipelined -- the build goes to the second stream, where it runs underneath the previous call's kernels, and only
-    // the reduction stays in line (the side stream's hop is worth it for long kernels only).
-    const bool half_million = B * N >= (int64_t)512 << 10;
-    short_call = half_million && (size_t)B * N * 7 * sizeof(T) < ((size_t)128 << 20) && !lat->has_cavity;
-    bool inline_all = false;
-    if (short_call && ctx->knobs.async_build < 0)
-      inline_all = knob(ctx->knobs.small_inline, ctx->main_idle ? 1 : 0) != 0;
-    const bool async = knob(ctx->knobs.async_build, half_million && !inline_all ? 1 : 0) != 0;
-    async_build = async;
-    hipStream_t bs = async ? ctx->s_build : ctx->stream;
-    if (async) {
-      // the table slot was last read by the streaming kernel kTableSlots calls ago
-      if (ctx->streamed_valid[slot]) HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_streamed[slot], 0));
-      // ... and the build starts in the TAIL of the streaming kernel before the one enqueued last (which has the GPU
-      // to itself when it gets there), not at that kernel's head
-      tail = ctx->can_wait_value && ctx->knobs.build_in_tail && !short_call;  // (a short kernel has no tail worth waiting for)
-      if (tail && ctx->tail_seq >= 2)
-        HIP_TRY(ctx, hipStreamWaitValue32(bs, ctx->d_tail_flag, ctx->tail_seq - 1, hipStreamWaitValueGte, 0xffffffffu));
-      // what the build reads (energy, lattice pool) may have been written on the main stream
-      if (ctx->main_dirty || (ctx->main_wrote && ctx->main_wrote == d_energy_in)) {
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_mark, ctx->stream));
-        HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_mark, 0));
-        ctx->main_dirty = false;
-        ctx->main_wrote = nullptr;
-      }
-    }
-    float* d_units_w = nullptr;
-    float* d_extras_w = nullptr;
-    if constexpr (sizeof(T) == 4) {
-      // multi-step programs: walked as units with structured maps (lynx_units.hpp); LYNX_TRACK_UNITS=0 keeps the
-      // dense step loop of k_track_direct
-      // (LYNX_TRACK_UNITS=2: insist -- an error if this call cannot take the structured loop; for tests)
-      const int want_units = ctx->knobs.track_units;
-      // (k_track_units addresses a sample's particles with 32-bit byte offsets: samples below 4 GiB)
-      if (S > 1 && (p.unroll == 2 || p.unroll == 4) && !p.xpose && p.a.n_observers == 0 && want_units &&
-          (uint64_t)N * 28u + ((uint64_t)1 << 20) < ((uint64_t)1 << 32)) {
-        if ((rc = ensure_units_plan(ctx, lat, p.a.merged_pairs != 0))) return rc;
-        use_units = lat->units_ok[p.a.merged_pairs ? 1 : 0];
-      }
-      if (want_units == 2 && !use_units)
-        return fail(ctx, LYNX_ERR_INVALID, "LYNX_TRACK_UNITS=2: this call does not take the structured step loop");
-      if (use_units) {
-        const int64_t n = B * lat->units[p.a.merged_pairs ? 1 : 0].n_units;
-        const int xs = lynx_ctx::kTableSlots + slot;
-        if ((rc = ensure_scratch(ctx, &ctx->scratch_units[slot], &ctx->scratch_units_bytes[slot], (size_t)n * kUnitStride * sizeof(float))) ||
-            (rc = ensure_scratch(ctx, &ctx->scratch_units[xs], &ctx->scratch_units_bytes[xs], (size_t)n * kUnitExtraStride * sizeof(float))))
-          return rc;
-        d_units = d_units_w = (float*)ctx->scratch_units[slot];
-        d_extras = d_extras_w = (float*)ctx->scratch_units[xs];
-        n_units = lat->units[p.a.merged_pairs ? 1 : 0].n_units;
-      }
-    }
-    if ((rc = launch_build<T>(ctx, lat, bs, d_energy_in, ctx->scratch_steps[slot], nullptr, p.a.merged_pairs, async, d_units_w, d_extras_w)))
-      return rc;
-    if (async) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_built[slot], bs));
-      // The HOST waits for the build instead of the main stream: no barrier packet with a foreign signal in front of
-      // the streaming kernel (measured on the 128-sample shard of BASELINE config 4: step - kernel 18.8 -> 8.5-10 us,
-      // c3big 17.9 -> 8-14, config 4 itself 20 -> 14).  The build of this call started when the streaming kernel of
-      // call n - kTableSlots + 1 began, so by now the GPU still has about two calls queued.  Not for lattices with
-      // cavities: their build (k_cavity_flags + the lanes kernels) takes most of a streaming kernel's time next to a
-      // VALU-bound kernel, and the host's wake-up would sit on the critical path (BASELINE config 5: 0.932 -> 0.947
-      // ms/step with it).  LYNX_BUILD_HOST_WAIT=0 / 1 forces the main-stream / host wait.
-      // Nor for short streaming kernels (BASELINE config 3, 1 M particles: 29 us of kernel, 22 us of build -- the
-      // host would be the pacemaker: 48 -> 75 us/step): from 128 MB of particles per call.
-      const bool long_kernel = (size_t)B * N * 7 * sizeof(T) >= ((size_t)128 << 20);
-      if (knob(ctx->knobs.build_host_wait, (lat->has_cavity || !long_kernel) ? 0 : 1)) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_built[slot]));
-      else HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_built[slot], 0));
-    }
-    d_steps = ctx->scratch_steps[slot];
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    ctx->fwd_table.lat = lat;
-    ctx->fwd_table.version = lat->version;
-    ctx->fwd_table.energy = d_energy_in;
-    ctx->fwd_table.energy_bytes = (size_t)B * sizeof(T);
-    ctx->fwd_table.slot = slot;
-    ctx->fwd_table.merged = p.a.merged_pairs;
-    ctx->fwd_table.units = use_units;
-    ctx->fwd_table.seq = ctx->seq;
-    ctx->fwd_table.valid = d_energy_out != d_energy_in;  // (a call that overwrites its own incoming energy leaves nothing to come back to)
-  }
-  if (fused && lat) {
-    if ((rc = sync_pool(ctx, lat))) return rc;  // (the prologue reads the parameters from memory)
-    if ((rc = launch_cavity_flags<T>(ctx, lat, ctx->stream, d_energy_in))) return rc;
-    ctx->main_dirty = true;  // it rewrote the lattice's flags on the main stream: a later build on s_build waits
-  }
+  // The build is always a launch of its own (in the streaming kernel's prologue it measured the same twice: NOTES.md,
+  // "Tried and dropped in round 4"), so a call with steps always takes a slot of the ring and leaves a FwdTable.
+  TrackTable t;
+  if (S > 0 && (rc = track_table<T>(ctx, lat, B, N, S, d_energy_in, d_energy_out, flags, p, &t))) return rc;
   if ((int64_t)B * p.a.chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
   // Workgroup records: a ring of buffers, so that the reduction of call n (side stream) can still read its records
   // while the streaming kernels of calls n+1.. write theirs.  The host makes sure the slot's previous reduction is done.
@@ -1795,7 +1845,7 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   lynx_ctx::PartialSlot* ring = nullptr;
   // The reduction leaves the main stream once the streaming kernel is long enough to hide it under (same threshold
   // as the build's second stream: below it the extra event traffic costs more host time than it returns).
-  const bool side = moments && knob(ctx->knobs.side_reduce, (B * N >= (int64_t)512 << 10 && !short_call) ? 1 : 0) != 0;
+  const bool side = moments && knob(ctx->knobs.side_reduce, (B * N >= (int64_t)512 << 10 && !t.short_call) ? 1 : 0) != 0;
   if (moments) {
     ring = &ctx->partial_ring[ctx->partial_seq++ % lynx_ctx::kPartialRing];
     if (ring->pending) {
@@ -1817,7 +1867,7 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   // table slot; a call whose build ran on the main stream leaves it out (it costs host time: BASELINE config 2 is
   // bound by the host's enqueue rate) and marks the main stream dirty instead, which makes the next asynchronous
   // build wait for everything enqueued here
-  if (tail) {  // this kernel announces its tail: one of the workgroups of its last round of dispatches
+  if (t.tail) {  // this kernel announces its tail: one of the workgroups of its last round of dispatches
     const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     p.a.tail_flag = ctx->d_tail_flag;
     p.a.tail_seq = ++ctx->tail_seq;
@@ -1827,12 +1877,12 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   // end of its incoming beam -- is then what this one reads first, if it is the same beam again (the optimisation loop:
   // one incoming beam, new settings every step).  BASELINE config 3 at 8 M particles (448 MB in): 171 -> 161.5 us/step;
   // config 4 (2.87 GB in): 980.6 -> 972.  Same workgroups, same records, another order of dispatch.
-  if (!use_units && ctx->knobs.alternate_order &&
+  if (!t.use_units && ctx->knobs.alternate_order &&
       (ctx->knobs.alternate_order == 2 || (size_t)B * N * 7 * sizeof(T) >= ((size_t)256 << 20)))
     p.a.reversed = ctx->knobs.alternate_order == 2 ? 1 : (int32_t)(ctx->long_calls++ & 1u);
-  p.done = (slot >= 0 && async_build) ? ctx->ev_streamed_own[slot] : nullptr;
+  p.done = (t.slot >= 0 && t.async) ? ctx->ev_streamed_own[t.slot] : nullptr;
   if (side && !p.done) p.done = ring->track_done;  // the side stream's reduction starts behind it
-  if (use_units) {
+  if (t.use_units) {
     const UnitPlan& up = lat->units[p.a.merged_pairs ? 1 : 0];
     bool pair_form = ctx->knobs.unit_pairs != 0;
     for (int u = 0; u < up.n_units && pair_form; ++u) pair_form = up.cls[u] == kClassU && up.pair[u];
@@ -1840,12 +1890,12 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
     if (ctx->knobs.unit_pairs == 2 && !pair_form)
       rc = fail(ctx, LYNX_ERR_INVALID, "LYNX_UNIT_PAIRS=2: this call does not take the kernel for lattices of [run, cavity] pairs");
     else
-      rc = launch_units(ctx, p, n_units, S, d_p_in, d_p_out, d_energy_out, d_steps, d_units, d_extras, d_partials, moments, pair_form);
+      rc = launch_units(ctx, p, t.n_units, S, d_p_in, d_p_out, d_energy_out, t.d_steps, t.d_units, t.d_extras, d_partials, moments, pair_form);
   } else {
-    rc = launch_direct<T>(ctx, p, lv, d_energy_in, d_p_in, d_p_out, d_energy_out, d_steps, d_partials, d_obs, moments);
+    rc = launch_direct<T>(ctx, p, lv, d_energy_in, d_p_in, d_p_out, d_energy_out, t.d_steps, d_partials, d_obs, moments);
   }
   if (rc) {
-    if (tail) --ctx->tail_seq;  // nothing will announce this number: a later build must not wait for it
+    if (t.tail) --ctx->tail_seq;  // nothing will announce this number: a later build must not wait for it
     return rc;
   }
   if (p.a.n_observers) {
@@ -1853,86 +1903,13 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
                        p.a.n_observers, (double)N, d_observations);
     HIP_TRY(ctx, hipGetLastError());
   }
-  if (slot >= 0) {
-    ctx->ev_streamed[slot] = ctx->last_stream_stop;
-    ctx->streamed_valid[slot] = async_build && ctx->last_stream_stop != nullptr;
-    if (!async_build) ctx->main_dirty = true;
+  if (t.slot >= 0) {
+    ctx->ev_streamed[t.slot] = ctx->last_stream_stop;
+    ctx->streamed_valid[t.slot] = t.async && ctx->last_stream_stop != nullptr;
+    if (!t.async) ctx->main_dirty = true;
   }
   if (d_energy_out) ctx->main_wrote = d_energy_out;  // a later build that reads it must wait for this kernel
-  if (moments) {
-    // records of the workgroups -> record of the sample.  Many samples: one 256-thread workgroup per sample
-    // walks up to 70 rows, more rows go through a level of <= 64 groups first (rows_per_group grows with the
-    // beam).  Few samples with a few hundred rows each (BASELINE configs 2 and 3): one 1024-thread workgroup
-    // per sample stages 448 rows per pass -- one launch instead of two (LYNX_REDUCE_WIDE=0: the level form).
-    hipStream_t rs = ctx->stream;
-    if (side) {
-      rs = ctx->s_side;
-      HIP_TRY(ctx, hipStreamWaitEvent(rs, ctx->last_stream_stop, 0));
-    } else {
-      // in line: the side stream may still be reducing into a block the allocator has not seen freed; the main
-      // stream's own order covers everything else
-      ctx->side_wrote = nullptr;
-    }
-    int rows = p.a.chunks;
-    const double* level_in = d_partials;
-    const bool wide = B <= 4 && rows > kReduceStage && rows <= 3 * kReduceStageWide && ctx->knobs.reduce_wide == 1;
-    if (wide) {
-      constexpr size_t lds = reduce_lds_bytes<1024, kReduceStageWide>();
-      if ((rc = allow_lds(ctx, k_reduce_moments<true, 1024, kReduceStageWide>, lds))) return rc;
-      hipLaunchKernelGGL((k_reduce_moments<true, 1024, kReduceStageWide>), dim3((unsigned)B), dim3(1024), lds, rs,
-                         level_in, rows, rows, 1, d_moments_out);
-      HIP_TRY(ctx, hipGetLastError());
-    } else {
-      constexpr size_t lds = reduce_lds_bytes<256, kReduceStage>();
-      if (rows > kReduceStage) {
-        const int rpg = std::max((rows + 63) / 64, B <= 4 ? 32 : 1);  // (few samples: no point in groups of a handful of rows)
-        const int groups = (rows + rpg - 1) / rpg;
-        const size_t need = (size_t)B * groups * kPartialStride * sizeof(double);
-        // one buffer: its users follow each other on one stream (side or main), and a change of stream joins first
-        if ((rc = ensure_scratch(ctx, &ctx->scratch_level, &ctx->scratch_level_bytes, need))) return rc;
-        if (ctx->level_on_side != side) {
-          if (side) {  // earlier in-line levels ran on the main stream: the side stream waits for them
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_main_mark, ctx->stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->s_side, ctx->ev_main_mark, 0));
-          } else if ((rc = join_side(ctx))) {
-            return rc;
-          }
-          ctx->level_on_side = side;
-        }
-        if (ctx->knobs.reduce_ticket) {
-          // both levels in one launch: the workgroup that draws a sample's last ticket adds its group records up
-          if ((rc = ensure_tickets(ctx, (size_t)B))) return rc;
-          hipLaunchKernelGGL((k_reduce_moments_ticket<256, kReduceStage>), dim3((unsigned)(B * groups)), dim3(256), lds, rs,
-                             level_in, rows, rpg, groups, (double*)ctx->scratch_level, ctx->scratch_tickets, d_moments_out);
-          HIP_TRY(ctx, hipGetLastError());
-          rows = 0;
-        } else {
-          hipLaunchKernelGGL((k_reduce_moments<false, 256, kReduceStage>), dim3((unsigned)(B * groups)), dim3(256), lds, rs,
-                             level_in, rows, rpg, groups, (double*)ctx->scratch_level);
-          HIP_TRY(ctx, hipGetLastError());
-          level_in = (const double*)ctx->scratch_level;
-          rows = groups;
-        }
-      }
-      if (rows > 0) {
-        hipLaunchKernelGGL((k_reduce_moments<true, 256, kReduceStage>), dim3((unsigned)B), dim3(256), lds, rs, level_in,
-                           rows, rows, 1, d_moments_out);
-        HIP_TRY(ctx, hipGetLastError());
-      }
-    }
-    if (side) {
-      // one event: the ring slot's.  The host has seen its previous recording complete before this call took the
-      // slot, so whatever side operation still carries it has finished and retires on the next look.
-      {
-        std::lock_guard<std::mutex> lock(ctx->mu);
-        retire_side_ops(ctx, false);
-      }
-      HIP_TRY(ctx, hipEventRecord(ring->reduced, rs));
-      ring->pending = true;
-      side_op_issued(ctx, ring->reduced, d_moments_out, nullptr, false);
-      ctx->side_wrote = d_moments_out;
-    }
-  }
+  if (moments) return reduce_moment_records(ctx, B, p.a.chunks, side, ring, d_partials, d_moments_out);
   return LYNX_OK;
 }
 

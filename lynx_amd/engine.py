@@ -386,7 +386,6 @@ def run_program_particles(cache, program: Program, beam, moments: bool | None = 
     e_in = beam._energy.broadcast_device(rt, batch_shape)
     want_moments = config.fused_moments if moments is None else moments
     flags = ((0 if not want_moments else _ffi.TRACK_COVARIANCE if config.fused_covariance else _ffi.TRACK_MOMENTS)
-             | (_ffi.TRACK_TWO_KERNEL if config.two_kernel else 0)
              | (_ffi.TRACK_SHARED_INPUT if beam.is_shared else 0)
              | (0 if config.merge_steps else _ffi.TRACK_SEQUENTIAL_STEPS))
     n = beam.num_particles

@@ -34,7 +34,10 @@ SHAPES = [(1,), (3,), (64,), (255,), (256,), (300,), (2, 3), (4, 16)]
 COUNTS = [1, 63, 64, 255, 257, 1000, 2047, 2049, 4097, 70_001]
 KINDS = ["drift", "quadrupole", "dipole", "rbend", "hcor", "vcor", "cavity", "custom", "bpm", "marker", "solenoid",
          "undulator"]
-KNOBS = VARIANTS + [{"LYNX_TRACK_UNITS": "0"}, {"LYNX_INLINE_POOL": "0"}, {"LYNX_LANES_BUILD_MIN_BATCH": "1"}]
+# (entry 13 was the pair of the fused build prologue's switch and LYNX_UNROLL=1 while that form existed: the half that is
+# left keeps the place, so that every case draws the knob it always drew)
+KNOBS = VARIANTS[:13] + [{"LYNX_UNROLL": "1"}] + VARIANTS[13:] + [{"LYNX_TRACK_UNITS": "0"}, {"LYNX_INLINE_POOL": "0"},
+                                                                 {"LYNX_LANES_BUILD_MIN_BATCH": "1"}]
 STEP_BUDGET = 6_000_000  # particle-element steps of the oracle per case (48 cases: < 3e8 in all)
 TOL_PB = TOL_MOM  # a ParameterBeam's mu and cov are its moments
 CONDITION_F32 = 5e-5  # float32 draws: the oracle's own float32 chain within this of float64 (see _float32_conditioned)

@@ -745,14 +745,24 @@ def test_gradients_through_active_bpms(lx, beam_type):
         vjp(mu_bar=w_mu, readings={elements[0]: r_a})  # an inactive BPM reads nothing
 
 
+def _two_quadrupole_cavity_cells(rng, B):
+    f = lambda v: np.full(B, v)  # noqa: E731
+    desc = []
+    for _ in range(2):
+        desc += [("drift", dict(length=f(0.3))), ("quadrupole", dict(length=f(0.1), k1=rng.uniform(-5, 5, B))),
+                 ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, B), phase=rng.uniform(-10, 10, B),
+                                 frequency=f(1.3e9)))]
+    return desc
+
+
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("writer", ["build_compose", "fused_forward"])
+@pytest.mark.parametrize("writer", ["build_compose", "forward_energy_out"])
 def test_a_reverse_pass_does_not_read_a_table_whose_energy_was_overwritten(lx, monkeypatch, writer, dtype):
     """
     The reverse pass reuses the forward call's step table when the energy POINTER, the table sequence and the lattice
     version match (lynx_ctx::FwdTable).  Through the C ABI: a forward call on energy buffer E; then something else
-    writes new energies into E on the caller's behalf -- lynx_build_compose with d_energy_out = E, or a forward call in
-    the fused form (LYNX_FUSE_MAX_CHUNKS), which takes no table slot -- and then the reverse pass on E.  Its gradients
+    writes new energies into E on the caller's behalf -- lynx_build_compose with d_energy_out = E, or a forward call on
+    other energies whose d_energy_out is E -- and then the reverse pass on E.  Its gradients
     must be those of a reverse pass that builds its own table from what E holds now (LYNX_BWD_REUSE_TABLE=0), bit for
     bit; and they must differ from the gradients at E's old contents (otherwise the test would prove nothing).
     Both passes walk the steps one by one (LYNX_TRACK_SEQUENTIAL_STEPS, LYNX_BWD_MERGE=0), so that their merge forms
@@ -768,13 +778,7 @@ def test_a_reverse_pass_does_not_read_a_table_whose_energy_was_overwritten(lx, m
     dtype = np.dtype(dtype)
     B, N = 3, 4000
     rng = np.random.default_rng(61)
-    f = lambda v: np.full(B, v)  # noqa: E731
-    desc = []
-    for _ in range(2):
-        desc += [("drift", dict(length=f(0.3))), ("quadrupole", dict(length=f(0.1), k1=rng.uniform(-5, 5, B))),
-                 ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, B), phase=rng.uniform(-10, 10, B),
-                                 frequency=f(1.3e9)))]
-    elements, _ = make_lattice(desc, dtype.type, lx)
+    elements, _ = make_lattice(_two_quadrupole_cavity_cells(rng, B), dtype.type, lx)
     seg = lx.Segment(elements)
     P = o.gaussian_particles((B,), N, seed=9, dtype=dtype, sigma=[1e-3, 1e-4, 1e-3, 1e-4, 1e-3, 1e-3])
     e1 = rng.uniform(6e6, 8e6, B).astype(dtype)
@@ -799,16 +803,12 @@ def test_a_reverse_pass_does_not_read_a_table_whose_energy_was_overwritten(lx, m
     p = lambda a: C.c_void_p(a.ptr)  # noqa: E731
     one_by_one = _ffi.TRACK_MOMENTS | _ffi.TRACK_SEQUENTIAL_STEPS
     monkeypatch.setenv("LYNX_BWD_MERGE", "0")
-    if writer == "fused_forward":
-        monkeypatch.setenv("LYNX_FUSE_MAX_CHUNKS", "64")
-        monkeypatch.setenv("LYNX_UNROLL", "1")
 
     def run(reuse, overwrite=True):
         monkeypatch.setenv("LYNX_BWD_REUSE_TABLE", reuse)
         rt.check(rt.lib.lynx_buf_h2d(rt.ctx, p(E), e1.ctypes.data, e1.nbytes))
-        # (the fused knobs let a call without LYNX_TRACK_TWO_KERNEL take the fused form: this one keeps its slot)
         rt.check(rt.lib.lynx_track_particles(rt.ctx, lat.handle, N, p(E), p(p_in), p(p_out), p(e_out), p(mom),
-                                             one_by_one | _ffi.TRACK_TWO_KERNEL, None))
+                                             one_by_one, None))
         if overwrite and writer == "build_compose":
             rt.check(rt.lib.lynx_build_compose(rt.ctx, lat.handle, p(other), p(steps), p(E)))
         elif overwrite:
@@ -824,3 +824,42 @@ def test_a_reverse_pass_does_not_read_a_table_whose_energy_was_overwritten(lx, m
     assert not np.array_equal(fresh[2], e1) and np.array_equal(reused[2], fresh[2])  # E was overwritten, the same way
     assert not np.array_equal(fresh[0], stale[0])  # the energy matters to the gradients
     assert np.array_equal(reused[0], fresh[0], equal_nan=True) and np.array_equal(reused[1], fresh[1], equal_nan=True)
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_the_TRACK_TWO_KERNEL_flag_is_accepted_and_changes_nothing(lx, dtype):
+    """
+    LYNX_TRACK_TWO_KERNEL stays in the C ABI for callers compiled against the header; the build is always a launch of
+    its own, so lynx_track_particles gives the same particles, energy and moment record with and without it, bit for bit.
+    """
+    import ctypes as C
+
+    from lynx_amd import _ffi, engine
+    from lynx_amd.device import get_runtime
+
+    rt = get_runtime()
+    dtype = np.dtype(dtype)
+    B, N = 3, 4000
+    rng = np.random.default_rng(61)
+    elements, _ = make_lattice(_two_quadrupole_cavity_cells(rng, B), dtype.type, lx)
+    seg = lx.Segment(elements)
+    P = o.gaussian_particles((B,), N, seed=9, dtype=dtype, sigma=[1e-3, 1e-4, 1e-3, 1e-4, 1e-3, 1e-3])
+    e1 = rng.uniform(6e6, 8e6, B).astype(dtype)
+    program, = engine.plan(seg, seg.elements, False, fuse_observers=True)
+    lat = engine._ready(seg.__dict__.setdefault("_lattice_cache", engine.LatticeCache()), program, (B,), dtype, e1)
+    E = rt.to_device(e1)
+    p_in = rt.to_device(P)
+    p = lambda a: C.c_void_p(a.ptr)  # noqa: E731
+
+    def run(flags):
+        p_out = rt.empty((B, N, 7), dtype)
+        e_out = rt.empty((B,), dtype)
+        mom = rt.empty((B, _ffi.MOMENT_STRIDE), np.float64)
+        rt.check(rt.lib.lynx_track_particles(rt.ctx, lat.handle, N, p(E), p(p_in), p(p_out), p(e_out), p(mom), flags, None))
+        return p_out.numpy().copy(), e_out.numpy().copy(), mom.numpy().copy()
+
+    plain = run(_ffi.TRACK_MOMENTS)
+    flagged = run(_ffi.TRACK_MOMENTS | _ffi.TRACK_TWO_KERNEL)
+    assert not np.array_equal(plain[0], P) and not np.array_equal(plain[1], e1)  # the call did track and accelerate
+    for a, b in zip(plain, flagged):
+        assert np.array_equal(a, b, equal_nan=True)

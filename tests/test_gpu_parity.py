@@ -203,14 +203,14 @@ def test_c2_ares_segment_particles(lx, n):
 
 
 @pytest.mark.parametrize("dtype,n", [(np.float32, 100_000), (np.float64, 300_001), (np.float64, 1_000_000)])
-def test_the_three_forms_of_the_moment_reduction_agree(lx, dtype, n, monkeypatch):
+def test_the_two_forms_of_the_moment_reduction_agree(lx, dtype, n, monkeypatch):
     """
     Beams of few samples with hundreds to thousands of workgroup records (BASELINE configs 2 and 3): by default ONE
     launch adds them up in two levels -- groups of rows, then the workgroup that draws the sample's last ticket adds the
     group records in group order (k_reduce_moments_ticket).  The same records through two launches (a level, then the
-    final one: LYNX_REDUCE_TICKET=0) and through one 1024-thread workgroup per sample (LYNX_REDUCE_WIDE=1): a different
-    association of the same float64 sums -- the records agree to rounding, and with the oracle; and the default form
-    gives the same bits every time it runs (the last arrival decides who adds, not in which order).
+    final one: LYNX_REDUCE_TICKET=0): a different association of the same float64 sums -- the records agree to rounding,
+    and with the oracle; and the default form gives the same bits every time it runs (the last arrival decides who adds,
+    not in which order).
     """
     sigma = [175e-9, 2e-7, 175e-9, 2e-7, 1e-6, 1e-6]
     out, ref = _particle_case(lx, ARES, dtype, (1,), n, seed=5, sigma=sigma)
@@ -220,7 +220,7 @@ def test_the_three_forms_of_the_moment_reduction_agree(lx, dtype, n, monkeypatch
         again, _ = _particle_case(lx, ARES, dtype, (1,), n, seed=5, sigma=sigma)
         assert np.array_equal(again.moment_record(), ticket, equal_nan=True)
     have = ~np.isnan(ticket)
-    for knob in ({"LYNX_REDUCE_TICKET": "0"}, {"LYNX_REDUCE_WIDE": "1"}):
+    for knob in ({"LYNX_REDUCE_TICKET": "0"},):
         for key, value in knob.items():
             monkeypatch.setenv(key, value)
         other, _ = _particle_case(lx, ARES, dtype, (1,), n, seed=5, sigma=sigma)
@@ -1241,7 +1241,7 @@ VARIANTS = [
     {"LYNX_LANES_BUILD_MIN_BATCH": "1", "LYNX_PIECE": "1"},  # two levels of pair products, in one launch (k_pair_levels)
     {"LYNX_LANES_BUILD_MIN_BATCH": "1", "LYNX_PIECE": "1", "LYNX_PAIR_LEVELS_FUSED": "0"},  # ... one launch per level
     {"LYNX_UNROLL": "1"}, {"LYNX_UNROLL": "2"}, {"LYNX_UNROLL": "4"}, {"LYNX_MOM": "2"}, {"LYNX_MOM": "3"},
-    {"LYNX_FUSE_MAX_CHUNKS": "64", "LYNX_UNROLL": "1"}, {"LYNX_MIN_TILES_PER_WG": "1"}, {"LYNX_MERGE_STEPS": "0"},
+    {"LYNX_MIN_TILES_PER_WG": "1"}, {"LYNX_MERGE_STEPS": "0"},
     {"LYNX_SIDE_REDUCE": "1"}, {"LYNX_ASYNC_BUILD": "1", "LYNX_BUILD_HOST_WAIT": "1"}, {"LYNX_BUILD_IN_TAIL": "0", "LYNX_ASYNC_BUILD": "1"},
     {"LYNX_SMALL_INLINE": "0"}, {"LYNX_SMALL_INLINE": "1"},
     {"LYNX_ALTERNATE_ORDER": "2", "LYNX_UNROLL": "1"}, {"LYNX_ALTERNATE_ORDER": "2", "LYNX_TRACK_UNITS": "0"}, {"LYNX_UNIT_PAIRS": "0"},
@@ -1254,7 +1254,7 @@ def test_every_kernel_variant_gives_the_default_answer(lx, dtype, monkeypatch):
     """
     The launch plan picks one of several forms of the same computation (wave tiles or per-particle
     accesses, particles per lane, moment accumulation mode, build on the second stream or in line,
-    lanes or workgroup build, fused prologue, tile order ...).  Every knob, on a lattice with cavities
+    lanes or workgroup build, tile order ...).  Every knob, on a lattice with cavities
     and an active BPM, a ragged particle count and a batch: particles agree with the default plan to
     rounding (the forms differ in the association of the map products only), moments and the BPM
     reading to the moment tolerance.
@@ -1300,27 +1300,21 @@ def test_every_kernel_variant_gives_the_default_answer(lx, dtype, monkeypatch):
     assert len(tree) == 2 and np.array_equal(tree[0], tree[1])
 
 
-def test_two_kernel_path_is_bit_identical_to_fused(lx):
+def test_merged_pairs_agree_with_the_step_by_step_form_and_the_oracle(lx):
     desc = [("drift", dict(length=[0.6] * 3)), ("quadrupole", dict(length=[0.2] * 3, k1=[4.2, -1.0, 0.0])),
             ("cavity", dict(length=[1.0] * 3, voltage=[1e7] * 3, phase=[5.0] * 3, frequency=[1.3e9] * 3)),
             ("drift", dict(length=[0.4] * 3))]
     # 200 000 particles per sample: large enough for the two-particles-per-lane plan, the one that merges
-    lx.config.two_kernel = False
-    lx.config.merge_steps = False  # step by step on both sides
+    lx.config.merge_steps = False  # step by step
     try:
         a, _ = _particle_case(lx, desc, np.float32, (3,), 200_000, seed=8, energy=6e6)
-        lx.config.two_kernel = True
-        b, _ = _particle_case(lx, desc, np.float32, (3,), 200_000, seed=8, energy=6e6)
         # default: the run in front of the cavity is applied together with it -- same algebra,
         # one rounding of the 7x7 product more in the build and one application less per particle
         lx.config.merge_steps = True
         c, ref = _particle_case(lx, desc, np.float32, (3,), 200_000, seed=8, energy=6e6)
     finally:
-        lx.config.two_kernel = False
         lx.config.merge_steps = True
-    assert np.array_equal(np.asarray(a.particles), np.asarray(b.particles))
-    assert np.array_equal(a.energy, b.energy)
-    got, seq = np.asarray(c.particles), np.asarray(b.particles)
+    got, seq = np.asarray(c.particles), np.asarray(a.particles)
     assert not np.array_equal(got, seq)
     for k in range(6):
         scale = np.max(np.abs(ref["particles"][..., k]))
