@@ -346,6 +346,40 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                         void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
                                         void* d_grad_cov_in);
 
+/* The moment records of an INCOMING beam over the nested survivor sets of a trace with losses: set j holds the particles
+ * alive behind the first j apertures (d_lost_at == -1 or >= j; set 0 is everyone).  What the reverse pass below starts
+ * its per-set recursions from -- one more streaming pass over the incoming particles.
+ *   d_p            [B][N][7], or [N][7] with LYNX_TRACK_SHARED_INPUT (the only flag), in `dtype`
+ *   d_lost_at      [B][N] int32, as lynx_track_particles_along_losses wrote it
+ *   d_records_out  [B][n_apertures + 1][36] float64, layout of LYNX_MOMENT_STRIDE: mean, biased covariance triangle,
+ *                  slot 34 = 1, slot 35 = the set's count (exact); a set without particles has count 0 and NaN moments
+ * The sums are taken about the sample's first particle and added in a fixed order, no atomics: the same call returns the
+ * same bits.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "moments by loss: ") for a null
+ * pointer, n_particles < 1, or n_apertures outside 1 .. 15.                                                           */
+int lynx_moments_by_loss(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p, int flags,
+                         int32_t n_apertures, const int32_t* d_lost_at, double* d_records_out);
+
+/* ... of lynx_track_particles_along_losses: gradient of a scalar function of the moments of the SURVIVING beam at every
+ * point (and of the energy).  The set of survivors is locally constant in the parameters and held fixed (the limits of
+ * the apertures get no gradient); on a fixed set the recursion above holds from point 0 on, an aperture step being the
+ * identity.  With Z_j the particles alive behind the first j apertures, the record of point p stands for Z_j, j = the
+ * number of apertures at steps < p; per set the call propagates the set's incoming mean and covariance through the
+ * step table in float64, takes the cotangents of the set's own points (zero elsewhere) and runs the sweep above; the
+ * sets' T_bar are added in set order.  Arguments as for lynx_track_particles_along_backward, and
+ *   d_trace_fwd    [B][P][36] float64   what lynx_track_particles_along_losses wrote
+ *   n_apertures, apertures              host [n_apertures]: the step indices of the active apertures, increasing
+ *   d_set_records  [B][n_apertures + 1][36] float64   what lynx_moments_by_loss wrote for the incoming beam and d_lost_at
+ * A set without particles (count 0) is skipped: a cotangent on a point nobody reaches counts for nothing.  There is no
+ * gradient with respect to the incoming mean and covariance: no single set of particles came in.  One wave per (sample,
+ * set), sums in float64 in a fixed order, no atomics: the same call returns the same bits.  LYNX_ERR_INVALID before
+ * anything is launched (lynx_last_error starts with "beam trace gradients with losses: ") for a null argument, a cavity
+ * step, more than 256 elements, n_apertures outside 1 .. 15, aperture steps that do not increase or are not identity
+ * steps of the program.                                                                                               */
+int lynx_track_particles_along_backward_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                               const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
+                                               int32_t n_apertures, const int32_t* apertures, const double* d_set_records,
+                                               void* d_grad_params, void* d_grad_energy_in);
+
 /* ... and of the trajectories of chosen particles (lynx_track_particles_along_trajectories): gradient of a scalar function of
  * the COORDINATES of n_chosen particles at every point -- the clearance of halo particles to an aperture, a single trace of
  * the reference's plot_reference_particle_traces -- together with, or without, the moment cotangents above.  Per chosen

@@ -2653,6 +2653,58 @@ int lynx_track_particles_along_trajectories(lynx_ctx* ctx, lynx_lattice* lat, in
                                n_apertures < 0 ? nullptr : &ap, n_screens < 0 ? nullptr : &sc, &tj);
 }
 
+// The moment records of the incoming beam over the nested survivor sets of a trace with losses: the particle trace's
+// wave plan with the sets for points, in the trace's own scratch (slabs, reference points), on the main stream.
+constexpr int32_t kTraceMaxLossApertures = kMaxLossSets - 1;
+
+template <typename T>
+static int moments_by_loss_t(lynx_ctx* ctx, int64_t B, int64_t N, const void* d_p, int flags, int32_t A,
+                             const int32_t* d_lost_at, double* d_records_out) {
+  constexpr int U = sizeof(T) == 4 ? 4 : 2;
+  const int32_t J = A + 1;
+  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t tiles = (N + 64 * U - 1) / (64 * U);
+  int64_t waves = std::min(std::max<int64_t>(1, (cus * 12 + B - 1) / B), tiles);
+  const int64_t tiles_per_wave = (tiles + waves - 1) / waves;
+  waves = ((tiles + tiles_per_wave - 1) / tiles_per_wave + 3) / 4 * 4;
+  if (B * (waves / 4) > 0x7fffffffLL || B * J > 0x7fffffffLL || tiles_per_wave > 0x7fffffffLL)
+    return fail(ctx, LYNX_ERR_INVALID, "moments by loss: batch too large for one launch");
+  int rc;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace[0], &ctx->scratch_trace_bytes[0],
+                           (size_t)B * waves * J * kTraceSlab * sizeof(double))) ||
+      (rc = ensure_scratch(ctx, &ctx->scratch_trace[1], &ctx->scratch_trace_bytes[1], (size_t)B * J * kTraceRef * sizeof(T))))
+    return rc;
+  LossSetArgs a{};
+  a.n_particles = N;
+  a.in_stride = (flags & LYNX_TRACK_SHARED_INPUT) ? 0 : N * 7;
+  a.waves = (int32_t)waves;
+  a.tiles_per_wave = (int32_t)tiles_per_wave;
+  a.sets = J;
+  hipLaunchKernelGGL((k_moments_by_loss<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, (const T*)d_p,
+                     d_lost_at, (double*)ctx->scratch_trace[0], (T*)ctx->scratch_trace[1]);
+  HIP_TRY(ctx, hipGetLastError());
+  return launch_trace_finalize<T>(ctx, B, J, waves, -1, d_records_out);
+}
+
+int lynx_moments_by_loss(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p, int flags,
+                         int32_t n_apertures, const int32_t* d_lost_at, double* d_records_out) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  const auto refuse = [&](const std::string& what) { return fail(ctx, LYNX_ERR_INVALID, "moments by loss: " + what); };
+  if (!d_p || !d_lost_at || !d_records_out) return refuse("null argument");
+  if (dtype != LYNX_F32 && dtype != LYNX_F64) return refuse("dtype is LYNX_F32 or LYNX_F64");
+  if (n_particles < 1) return refuse("n_particles must be >= 1");
+  if (batch <= 0 || batch > 0x7fffffffLL) return refuse("bad batch");
+  if (flags & ~LYNX_TRACK_SHARED_INPUT) return refuse("LYNX_TRACK_SHARED_INPUT is the only flag");
+  if (n_apertures < 1 || n_apertures > kTraceMaxLossApertures)
+    return refuse("n_apertures = " + std::to_string(n_apertures) + ", not 1 .. " + std::to_string(kTraceMaxLossApertures));
+  HIP_TRY(ctx, use_device(ctx));
+  ctx->main_dirty = true;
+  ctx->wrote(d_records_out, (size_t)batch * (n_apertures + 1) * LYNX_MOMENT_STRIDE * sizeof(double));
+  return dtype == LYNX_F64 ? moments_by_loss_t<double>(ctx, batch, n_particles, d_p, flags, n_apertures, d_lost_at, d_records_out)
+                           : moments_by_loss_t<float>(ctx, batch, n_particles, d_p, flags, n_apertures, d_lost_at, d_records_out);
+}
+
 template <typename T>
 static int track_moments_along_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                                  const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace) {
@@ -2852,6 +2904,77 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                                   d_grad_energy_in, d_grad_mean_in, d_grad_cov_in)
              : particles_along_backward_t<float>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
                                                  d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+}
+
+// ... of a trace with losses: one wave per (sample, survivor set) propagates the set's incoming moments and sweeps back
+// over the set's live points (k_trace_moments_bwd_sets), the sets' T_bar are added in set order (k_trace_sum_sets), then
+// the same k_build_bwd.  scratch_grad[0]: the states [B][A + 1][S][56], then the sets' T_bar [A + 1][B][S][64], float64.
+template <typename T>
+static int particles_along_backward_losses_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const double* d_grad_trace,
+                                             const void* d_energy_bar, const TraceLossSets& sets, const double* d_set_records,
+                                             void* d_grad_params, void* d_grad_energy_in) {
+  const int64_t B = lat->batch, S = lat->n_steps, J = sets.sets;
+  const size_t state_scalars = (size_t)B * J * S * kSetState, tbar_scalars = (size_t)J * B * S * kGradStride;
+  int rc;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (state_scalars + tbar_scalars) * sizeof(double))))
+    return rc;
+  double* states = (double*)ctx->scratch_grad[0];
+  double* tbar_sets = states + state_scalars;
+  if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
+  hipLaunchKernelGGL(k_trace_moments_bwd_sets<T>, dim3((unsigned)(B * J)), dim3(64), 0, ctx->stream, (int)S, B, sets,
+                     (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], d_set_records, d_grad_trace, states, tbar_sets);
+  HIP_TRY(ctx, hipGetLastError());
+  const int64_t cells = B * S * kGradStride;
+  hipLaunchKernelGGL(k_trace_sum_sets<T>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)tbar_sets,
+                     (int)J, cells, (T*)ctx->scratch_grad[1]);
+  HIP_TRY(ctx, hipGetLastError());
+  return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
+}
+
+int lynx_track_particles_along_backward_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                               const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
+                                               int32_t n_apertures, const int32_t* apertures, const double* d_set_records,
+                                               void* d_grad_params, void* d_grad_energy_in) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  const auto refuse = [&](const std::string& what) {
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients with losses: " + what);
+  };
+  if (!lat || !d_energy_in || !d_trace_fwd || !d_grad_trace || !apertures || !d_set_records || !d_grad_params || !d_grad_energy_in)
+    return refuse("null argument");
+  if (n_particles <= 0) return refuse("n_particles must be > 0");
+  if (lat->n_steps <= 0) return refuse("empty program");
+  if (lat->n_steps > kTraceBwdMaxSteps || lat->n_elems > kTraceBwdMaxSteps) return refuse("more than 256 elements");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return refuse("bad batch");
+  if (n_apertures < 1 || n_apertures > kTraceMaxLossApertures)
+    return refuse("n_apertures = " + std::to_string(n_apertures) + ", not 1 .. " + std::to_string(kTraceMaxLossApertures));
+  if ((int64_t)lat->batch * (lat->n_steps + 1) * (n_apertures + 1) > 0x7fffffffLL)
+    return refuse("batch x points x sets too large for one launch");
+  // the moments of a fixed set of particles are closed under affine maps only
+  for (int32_t s = 0; s < lat->n_steps; ++s)
+    if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
+      return refuse("step " + std::to_string(s) + " is a cavity step (the particles' moments are not closed under its kick)");
+  TraceLossSets sets{};
+  sets.sets = n_apertures + 1;
+  for (int32_t k = 0; k < n_apertures; ++k) {
+    const int32_t step = apertures[k];
+    if (step < 0 || step >= lat->n_steps || (k > 0 && step <= apertures[k - 1]))
+      return refuse("aperture steps must be increasing and inside the program");
+    const lynx_step& st = lat->h_steps[step];
+    if (st.kind != LYNX_STEP_RUN || st.last != st.first + 1 || lat->h_elems[st.first].kind != LYNX_KIND_IDENTITY)
+      return refuse("step " + std::to_string(step) + " is not an identity step: an aperture leaves the particles it passes alone");
+    sets.last[k] = step;
+  }
+  sets.last[n_apertures] = lat->n_steps;
+  HIP_TRY(ctx, use_device(ctx));
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
+  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+  return lat->dtype == LYNX_F64
+             ? particles_along_backward_losses_t<double>(ctx, lat, d_energy_in, d_grad_trace, d_energy_bar, sets, d_set_records,
+                                                         d_grad_params, d_grad_energy_in)
+             : particles_along_backward_losses_t<float>(ctx, lat, d_energy_in, d_grad_trace, d_energy_bar, sets, d_set_records,
+                                                        d_grad_params, d_grad_energy_in);
 }
 
 // ... with the trajectories of chosen particles: k_trace_trajectories_bwd behind the moment sweep (or alone), then the

@@ -29,6 +29,9 @@
 // and is kept out of every later sum by a select, and the number of particles a record stands for is the point's own
 // sum of the 7th coordinate (slot 6 of the slab row) instead of N (k_trace_finalize with a negative count).
 //
+// The reverse pass of such a trace wants the moments of the INCOMING beam over every nested survivor set
+// (lynx_moments_by_loss; k_moments_by_loss): the same wave body's pieces with identity steps, the sets for points.
+//
 // With screens (lynx_track_particles_along_screens; k_trace_particles_screens) an active screen is an identity step too:
 // the particles alive where it stands are binned by numpy's rule on the screen's own edge arrays (bin_of's result, from
 // an arithmetic guess corrected against the neighbouring edges) and counted into the screen's image with integer
@@ -575,6 +578,92 @@ __global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __rest
   }
   __syncthreads();
   if (tid < kPartialStride) write_moment_record(s, out + (b * P + k) * kPartialStride, tid);
+}
+
+// ---------------------------------------------------------------------------------------
+// k_moments_by_loss: the moment records of the INCOMING beam over the nested survivor sets of a trace with losses
+// (lynx_moments_by_loss).  Set j holds the particles alive behind the first j apertures: lost_at == -1 or lost_at >= j;
+// set 0 is everyone.  The kernel is the particle kernel with identity steps whose "points" are the sets: the same grid
+// and wave plan, a tile of 64 U particles in registers with their `lost_at`, per set the 28 shifted sums with a select
+// on `lost_at` (trace_point's masked form), the transposing butterfly, the wave's own float64 slab [A + 1][32]; then
+// k_trace_finalize in its per-point-count mode.  The reference point of every sum is the sample's first particle; wave 0
+// of a sample writes it where the finalizer looks for it, `ref_out` [B][A + 1][kTraceRef].  No atomics, one fixed order.
+// ---------------------------------------------------------------------------------------
+struct LossSetArgs {
+  int64_t n_particles;
+  int64_t in_stride;  // scalars between the samples of p_in: N * 7, or 0 for one shared incoming beam
+  int32_t waves;      // waves per sample (a multiple of 4)
+  int32_t tiles_per_wave;
+  int32_t sets;       // A + 1
+};
+
+template <typename T, int U>
+__device__ __forceinline__ void loss_sets_tile(const LossSetArgs& a, const T* __restrict__ src, const int32_t* __restrict__ lost_at,
+                                               int64_t base, int lane, bool first, double* __restrict__ slab /* of this wave */) {
+  bool inside[U];
+  int32_t gone[U];
+  T z[U][7];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t i = base + lane + 64 * u;
+    inside[u] = i < a.n_particles;
+    // (a lane beyond the end of the sample carries the sample's last particle: finite work, no part in any sum)
+    const int64_t at = inside[u] ? i : a.n_particles - 1;
+    load_particle(src + at * 7, z[u]);
+    gone[u] = lost_at[at];
+  }
+  if constexpr (sizeof(T) == 4) {
+    lynx_f32x2 zp[U / 2][7];
+#pragma unroll
+    for (int u = 0; u < U; u += 2)
+#pragma unroll
+      for (int c = 0; c < 7; ++c) {
+        zp[u / 2][c].x = z[u][c];
+        zp[u / 2][c].y = z[u + 1][c];
+      }
+#pragma nounroll
+    for (int j = 0; j < a.sets; ++j) {
+      bool live[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) live[u] = inside[u] && (gone[u] < 0 || gone[u] >= j);
+      trace_point<U, true>(zp, src, live, lane, first, slab + (int64_t)j * kTraceSlab);
+    }
+  } else {
+#pragma nounroll
+    for (int j = 0; j < a.sets; ++j) {
+      bool live[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) live[u] = inside[u] && (gone[u] < 0 || gone[u] >= j);
+      trace_point<U, true>(z, src, live, lane, first, slab + (int64_t)j * kTraceSlab);
+    }
+  }
+}
+
+template <typename T, int U>
+__global__ __launch_bounds__(256) void k_moments_by_loss(LossSetArgs a, const T* __restrict__ p_in,
+                                                         const int32_t* __restrict__ lost_at, double* __restrict__ slabs,
+                                                         T* __restrict__ ref_out) {
+  const int wgs = a.waves / 4;
+  const int64_t b = blockIdx.x / wgs;
+  const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int J = a.sets;
+  const T* src = p_in + b * a.in_stride;  // (its first six scalars: the reference point)
+  const int32_t* gone = lost_at + b * a.n_particles;
+  double* slab = slabs + (b * a.waves + w) * (int64_t)J * kTraceSlab;
+  if (w == 0)
+    for (int i = lane; i < J * kTraceRef; i += 64) ref_out[b * J * kTraceRef + i] = (i & (kTraceRef - 1)) < 6 ? src[i & (kTraceRef - 1)] : T(0);
+  constexpr int64_t kTile = 64 * U;
+  const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
+  if (begin >= a.n_particles) {
+    for (int64_t i = lane; i < (int64_t)J * kTraceSlab; i += 64) slab[i] = 0.0;
+    return;
+  }
+  for (int t = 0; t < a.tiles_per_wave; ++t) {
+    const int64_t base = begin + t * kTile;
+    if (base >= a.n_particles) break;
+    loss_sets_tile<T, U>(a, src, gone, base, lane, t == 0, slab);
+  }
 }
 
 // ---------------------------------------------------------------------------------------

@@ -31,6 +31,9 @@
 //                               cavities' voltage and phase (adds into what k_build_bwd wrote)
 //   k_trace_trajectories_bwd    the reverse sweep of CHOSEN particles' trajectories (lynx_track_particles_along_backward_
 //                               trajectories): a cotangent on single coordinates at every point, through the kick as well
+//   k_trace_moments_bwd_sets    a trace with losses (lynx_track_particles_along_backward_losses): per nested survivor
+//                               set the recursion from the set's incoming moments and the sweep over its own points;
+//                               k_trace_sum_sets adds the sets' T_bar in set order
 #pragma once
 
 #include "lynx_device.hpp"
@@ -408,6 +411,165 @@ __global__ __launch_bounds__(64) void k_trace_trajectories_bwd(int S, int64_t K,
         for (int c = 0; c < 7; ++c) out[c] = (T)lam[u][c];
       }
   }
+}
+
+// ---------------------------------------------------------------------------------------
+// The reverse pass of a trace WITH LOSSES (lynx_track_particles_along_backward_losses).  The record of point p is taken
+// over the particles alive there, and that set changes behind every active aperture -- but the sets are nested and
+// locally constant in the parameters, and for a FIXED set of particles the mean and the biased covariance obey the
+// recursion above from point 0 on (an aperture step is the identity).  With the apertures at the steps
+// a_0 < ... < a_{A-1} and Z_j the incoming particles alive behind the first j of them, the record of point p stands for
+// Z_j with j = #{a < p}: Z_j's live points are a_{j-1} + 1 .. a_j (a_{-1} = -1, a_A = S).  So L = sum_j L_j, and L_j is
+// the no-loss problem on the moment trace of Z_j with the cotangents zeroed outside its live points.
+//
+// k_trace_moments_bwd_sets: grid = B * (A + 1), one wave per (sample, set), 49 lanes busy.
+//   states      mean and C of set j's incoming particles (lynx_moments_by_loss) taken through the step table from point 0
+//               to the set's last live point -- k_trace_moments' recursion in float64 whatever the lattice's dtype (the
+//               head of this file) -- every state that ENTERS a step parked in `states` [B][A + 1][S][56];
+//   cotangents  read from the record cotangents under k_trace_records_to_states' conventions, zero outside the live points;
+//   sweep       k_trace_moments_bwd's, from the last live point down to step 0 (no cavity: refused by the host), T_bar
+//               in float64 into the set's own slab `tbar_sets` [A + 1][B][S][64]; rows behind the last live point are 0.
+// A set nobody is in (count 0, NaN moments) writes zeros.  k_trace_sum_sets then adds the sets' slabs in set order and
+// rounds once into the T_bar k_build_bwd consumes.  One lane owns every cell, fixed order: the same call, the same bits.
+// ---------------------------------------------------------------------------------------
+constexpr int kMaxLossSets = 16;  // 15 apertures
+constexpr int kSetState = 56;     // mu [7] | C [49]
+
+struct TraceLossSets {
+  int32_t sets;                // A + 1
+  int32_t last[kMaxLossSets];  // last live point of set j: the step of aperture j; S for the last set
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_moments_bwd_sets(int S, int64_t B, TraceLossSets sets, const T* __restrict__ steps,
+                                                               const double* __restrict__ set_records,
+                                                               const double* __restrict__ grad_trace,
+                                                               double* __restrict__ states, double* __restrict__ tbar_sets) {
+  using A = double;
+  __shared__ A s_mu[8], s_c[49], s_x[49], s_y[49], s_g[49], s_mb[8], s_m[64];
+  const int J = sets.sets;
+  const int64_t b = blockIdx.x / J;
+  const int set = (int)(blockIdx.x - b * J);
+  const int lane = threadIdx.x;
+  const int cl = lane < 49 ? lane : 48, l7 = lane < 7 ? lane : 6;
+  const int i = cl / 7, j = cl % 7;
+  const int L = sets.last[set], lo = set == 0 ? 0 : sets.last[set - 1] + 1;  // live points lo .. L
+  const T* g_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const double* rec = set_records + (b * J + set) * (int64_t)LYNX_MOMENT_STRIDE;
+  const double* g = grad_trace + b * (int64_t)(S + 1) * LYNX_MOMENT_STRIDE;
+  double* st = states + (b * J + set) * (int64_t)S * kSetState;
+  double* out = tbar_sets + ((int64_t)set * B + b) * (int64_t)S * kGradStride;
+  const bool empty = rec[35] == 0.0;  // uniform
+  for (int s = empty ? 0 : L; s < S; ++s) out[(int64_t)s * kGradStride + lane] = 0.0;
+  if (empty) return;
+  // this lane's entry in a record's triangle (k_trace_records_to_states)
+  const bool inner = i < 6 && j < 6;
+  const int r = i < j ? i : j, q = i < j ? j : i;
+  const int tri = inner ? 7 + r * 6 - (r * (r - 1)) / 2 + (q - r) : 7;
+  const A weight = !inner ? 0.0 : (i == j ? 1.0 : 0.5);
+
+  // forward: k_trace_moments' recursion, the state entering step s parked at st[s]
+  if (lane < 7) s_mu[lane] = lane < 6 ? rec[lane] : 1.0;
+  if (lane < 49) s_c[lane] = inner ? rec[tri] : 0.0;
+  __syncthreads();
+  for (int s = 0; s < L; ++s) {
+    if (lane < 7) st[(int64_t)s * kSetState + lane] = s_mu[lane];
+    if (lane < 49) st[(int64_t)s * kSetState + 7 + lane] = s_c[lane];
+    s_m[lane] = (A)g_steps[(int64_t)s * LYNX_STEP_STRIDE + lane];
+    __syncthreads();
+    A mu_new = 0.0;
+    if (lane < 7) {
+      mu_new = s_m[lane * 7] * s_mu[0];
+#pragma unroll
+      for (int k = 1; k < 7; ++k) mu_new = fma(s_m[lane * 7 + k], s_mu[k], mu_new);
+    }
+    A x = s_c[i * 7] * s_m[j * 7];  // X = C M^T
+#pragma unroll
+    for (int k = 1; k < 7; ++k) x = fma(s_c[i * 7 + k], s_m[j * 7 + k], x);
+    __syncthreads();
+    if (lane < 49) s_x[lane] = x;
+    if (lane < 7) s_mu[lane] = mu_new;
+    __syncthreads();
+    A c = s_m[i * 7] * s_x[j];  // C' = M X
+#pragma unroll
+    for (int k = 1; k < 7; ++k) c = fma(s_m[i * 7 + k], s_x[k * 7 + j], c);
+    if (lane < 49) s_c[lane] = c;
+    __syncthreads();
+  }
+  __threadfence_block();
+  __syncthreads();
+
+  // reverse: k_trace_moments_bwd's sweep; the cotangent of point p counts for lo <= p <= L (point 0's reaches no parameter)
+  if (lane < 7) s_mb[lane] = A(0);
+  if (lane < 49) s_g[lane] = A(0);
+  A n_mu = A(0), n_c = A(0), n_m = A(0), n_mb = A(0), n_cb = A(0);
+  if (L > 0) {
+    n_mb = L >= lo ? g[(int64_t)L * LYNX_MOMENT_STRIDE + l7] : A(0);
+    n_cb = L >= lo ? weight * g[(int64_t)L * LYNX_MOMENT_STRIDE + tri] : A(0);
+    n_mu = st[(int64_t)(L - 1) * kSetState + l7];
+    n_c = st[(int64_t)(L - 1) * kSetState + 7 + cl];
+    n_m = (A)g_steps[(int64_t)(L - 1) * LYNX_STEP_STRIDE + lane];
+  }
+  __syncthreads();
+  for (int s = L - 1; s >= 0; --s) {
+    if (lane < 7) {
+      s_mb[lane] += n_mb;  // cotangent of point s + 1
+      s_mu[lane] = n_mu;   // state at point s
+    }
+    if (lane < 49) {
+      s_g[lane] += n_cb;
+      s_c[lane] = n_c;
+    }
+    s_m[lane] = n_m;
+    if (s > 0) {
+      const bool counts = s >= lo;  // uniform
+      n_mb = counts ? g[(int64_t)s * LYNX_MOMENT_STRIDE + l7] : A(0);
+      n_cb = counts ? weight * g[(int64_t)s * LYNX_MOMENT_STRIDE + tri] : A(0);
+      n_mu = st[(int64_t)(s - 1) * kSetState + l7];
+      n_c = st[(int64_t)(s - 1) * kSetState + 7 + cl];
+      n_m = (A)g_steps[(int64_t)(s - 1) * LYNX_STEP_STRIDE + lane];
+    }
+    __syncthreads();
+    // P = G M, Q = G^T M
+    A pv = s_g[i * 7] * s_m[j], qv = s_g[i] * s_m[j];
+#pragma unroll
+    for (int k = 1; k < 7; ++k) {
+      pv = t_fma(s_g[i * 7 + k], s_m[k * 7 + j], pv);
+      qv = t_fma(s_g[k * 7 + i], s_m[k * 7 + j], qv);
+    }
+    if (lane < 49) {
+      s_x[lane] = pv;
+      s_y[lane] = qv;
+    }
+    __syncthreads();
+    A tb = s_mb[i] * s_mu[j], cb = A(0), mbn = A(0);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+      tb = t_fma(s_x[i * 7 + k], s_c[j * 7 + k], tb);
+      tb = t_fma(s_y[i * 7 + k], s_c[k * 7 + j], tb);
+      cb = t_fma(s_m[k * 7 + i], s_x[k * 7 + j], cb);
+    }
+    if (lane < 7) {
+#pragma unroll
+      for (int k = 0; k < 7; ++k) mbn = t_fma(s_m[k * 7 + lane], s_mb[k], mbn);
+    }
+    out[(int64_t)s * kGradStride + lane] = lane < 49 ? tb : A(0);
+    __syncthreads();
+    if (lane < 49) s_g[lane] = cb;
+    if (lane < 7) s_mb[lane] = mbn;
+    __syncthreads();
+  }
+}
+
+// grid = ceil(cells / 256): cell c of T_bar [B][S][64] is the sum over the sets of cell c of their slabs, in set order
+template <typename T>
+__global__ __launch_bounds__(256) void k_trace_sum_sets(const double* __restrict__ tbar_sets, int sets, int64_t cells,
+                                                        T* __restrict__ tbar) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= cells) return;
+  double v = 0.0;
+  for (int j = 0; j < sets; ++j) v += tbar_sets[(int64_t)j * cells + c];
+  tbar[c] = (T)v;
 }
 
 }  // namespace lynx

@@ -706,6 +706,8 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
                       moments=Dual(np.ascontiguousarray(rec[..., -1, :])))
         trace.outgoing = out
     device = {"records": records} if paths is None else {"records": records, "trajectories": paths}
+    if lost_at is not None:  # (what the reverse pass of a trace with losses makes its survivor sets from)
+        device["lost_at"] = lost_at
     return trace, rec[..., :, (0, 2)].astype(dtype), device  # (mean x, y of the particles alive at every point)
 
 

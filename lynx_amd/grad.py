@@ -50,8 +50,9 @@ class Gradients:
     """
 
     def __init__(self, program, raw_dev, energy_dev, batch_shape, energy_shape, particles_dev=None,
-                 mu_dev=None, cov_dev=None, chosen_dev=None):
+                 mu_dev=None, cov_dev=None, chosen_dev=None, survivors: bool = False):
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
+        self._survivors = survivors  # of `track_along_vjp(..., losses=True)`: no single incoming set of particles
         self._particles_dev = particles_dev
         self._mu_dev, self._cov_dev = mu_dev, cov_dev
         self._chosen_dev = chosen_dev
@@ -78,14 +79,18 @@ class Gradients:
 
     @property
     def mu(self) -> np.ndarray:
-        """dL/d(incoming mu), (*batch, 7) -- ParameterBeam VJPs only."""
+        """dL/d(incoming mu), (*batch, 7) -- ParameterBeam VJPs only; None for the survivors of a trace with losses."""
+        if self._survivors:
+            return None
         if self._mu_dev is None:
             raise KeyError("the gradient w.r.t. mu exists for ParameterBeam VJPs only")
         return self._mu_dev.numpy()
 
     @property
     def cov(self) -> np.ndarray:
-        """dL/d(incoming cov), (*batch, 7, 7), entry by entry -- ParameterBeam VJPs only."""
+        """dL/d(incoming cov), (*batch, 7, 7), entry by entry -- ParameterBeam VJPs only; None like `mu`."""
+        if self._survivors:
+            return None
         if self._cov_dev is None:
             raise KeyError("the gradient w.r.t. cov exists for ParameterBeam VJPs only")
         return self._cov_dev.numpy()
@@ -101,6 +106,8 @@ class Gradients:
         return self._chosen_dev.numpy()
 
     def __contains__(self, element) -> bool:
+        if self._survivors and any(el is element for _, el, _ in self._program.apertures):
+            return True
         return any(el is element and el._kind in DIFFERENTIABLE_KINDS for el in self._program.leaves)
 
     def __getitem__(self, element) -> dict:
@@ -108,6 +115,9 @@ class Gradients:
             return self._cache[id(element)]
         from .accelerator.magnets import RBend
 
+        if self._survivors and any(el is element for _, el, _ in self._program.apertures):
+            # the survivor set is held fixed: the limits that made it get gradient 0
+            return {n: np.zeros(np.asarray(getattr(element, n)).shape) for n in ("x_max", "y_max")}
         raw, total = self._host(), None
         for e, el in enumerate(self._program.leaves):
             if el is not element or el._kind not in DIFFERENTIABLE_KINDS:
@@ -385,6 +395,7 @@ class MomentsVJP:
 # -------------------------------------------------------------------------------------------
 
 MAX_TRACE_LEAVES = 256  # lynx_track_*_along_backward: k_build_bwd deals the steps of a program to its 256 threads
+MAX_TRACE_LOSS_APERTURES = 15  # lynx_track_particles_along_backward_losses: 16 survivor sets
 
 
 def trace_property_cotangents(trace, named: dict):
@@ -491,6 +502,18 @@ def trace_property_cotangents(trace, named: dict):
     return mu_bar, cov_bar, energy_bar
 
 
+def _record_cotangents(mb: np.ndarray, cb: np.ndarray) -> np.ndarray:
+    """
+    Cotangents of mean (B, P, 7) and covariance (B, P, 7, 7), entry by entry, as record cotangents (B, P, 36): [0..6] the
+    mean's, [7..27] the upper triangle in the record's order (`_tri`), an off-diagonal entry counted once.
+    """
+    rec = np.zeros((*mb.shape[:2], _ffi.MOMENT_STRIDE), dtype=np.float64)
+    rec[..., :7] = mb
+    rows, cols = np.triu_indices(6)
+    rec[..., 7:28] = (cb[..., rows, cols] + cb[..., cols, rows]) * np.where(rows == cols, 0.5, 1.0)
+    return rec
+
+
 class TrackAlongVJP:
     """
     Vector-Jacobian product of `Segment.track_along`: gradients of any function of the beam moments and the energy at
@@ -506,16 +529,34 @@ class TrackAlongVJP:
     moment cotangent is still refused, by the call.
     """
 
-    def __init__(self, segment, beam, trajectories=None):
+    def __init__(self, segment, beam, trajectories=None, losses=False):
         from .particles.parameter_beam import ParameterBeam
 
         if not isinstance(beam, (ParameterBeam, ParticleBeam)):
             raise TypeError(f"track_along_vjp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
+        if not isinstance(losses, (bool, np.bool_)):
+            raise ValueError(f"track_along_vjp: losses is True or False, not {losses!r}")
+        if losses and trajectories is not None:
+            raise NotImplementedError(
+                "track_along_vjp: losses=True together with trajectories= -- the trajectories of a trace with losses are "
+                "not differentiated; ask for one of the two")
         # (by value, before anything touches the GPU; a ParameterBeam has no particles to choose: TypeError)
         self.chosen = None if trajectories is None else engine.chosen_particles(trajectories, beam)
         leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
-        # (raises for an active Screen or Aperture, naming it, before anything touches the GPU)
-        self.program = engine._trace_plan(segment, leaves)
+        # (raises for an active Screen -- and, without `losses`, for an active Aperture --, naming it, before anything
+        # touches the GPU)
+        self.program = engine._trace_plan(segment, leaves, bool(losses))
+        # the survivors' reverse pass: a ParticleBeam and at least one active aperture; anything else with `losses` is the
+        # plain problem (apertures pass a ParameterBeam unchanged)
+        self._sets = bool(losses) and isinstance(beam, ParticleBeam) and len(self.program.apertures) > 0
+        if isinstance(beam, ParticleBeam) and not self._sets:
+            losses = False  # (no active aperture: nobody is lost, the call is the plain one)
+            self.program = engine._trace_plan(segment, leaves)
+        if self._sets and len(self.program.apertures) > MAX_TRACE_LOSS_APERTURES:
+            raise NotImplementedError(
+                f"track_along_vjp: {len(self.program.apertures)} active apertures, more than {MAX_TRACE_LOSS_APERTURES} (the "
+                f"first one beyond is {self.program.apertures[MAX_TRACE_LOSS_APERTURES][1].name!r}) -- differentiate the "
+                "lattice in stretches")
         if len(leaves) > MAX_TRACE_LEAVES:
             raise NotImplementedError(
                 f"track_along_vjp: {len(leaves)} leaf elements, more than {MAX_TRACE_LEAVES} (the first one beyond is "
@@ -529,10 +570,32 @@ class TrackAlongVJP:
         if self._cavity is not None and self.chosen is None:
             self._refuse_moments()
         self.segment, self.beam, self.leaves = segment, beam, leaves
-        if self.chosen is None:
+        self._set_records = None
+        if self._sets:
+            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses="particles")
+            self._set_records = self._survivor_set_records()
+        elif losses:  # (a ParameterBeam: active apertures are identity steps of its trace)
+            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses=True)
+        elif self.chosen is None:
             self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True)
         else:
             self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, trajectories=self.chosen)
+
+    def _survivor_set_records(self):
+        """
+        The moment records of the INCOMING beam over the nested survivor sets, [B][A + 1][36] on the device
+        (lynx_moments_by_loss): set j holds the particles alive behind the first j active apertures, by the `lost_at` the
+        forward trace left on the device.  One more streaming pass over the incoming particles.
+        """
+        rt = get_runtime()
+        beam, A = self.beam, len(self.program.apertures)
+        B = int(np.prod(beam.batch_shape, dtype=np.int64))
+        records = rt.empty((B, A + 1, _ffi.MOMENT_STRIDE), np.float64)
+        rt.check(rt.lib.lynx_moments_by_loss(
+            rt.ctx, engine.dtype_code(beam.dtype), B, beam.num_particles, C.c_void_p(beam._particles.device(rt).ptr),
+            _ffi.TRACK_SHARED_INPUT if beam.is_shared else 0, A, C.c_void_p(self.trace._device["lost_at"].ptr),
+            C.c_void_p(records.ptr)))
+        return records
 
     def _refuse_moments(self):
         raise NotImplementedError(
@@ -567,7 +630,23 @@ class TrackAlongVJP:
         P = self.trace.num_points
         B = int(np.prod(batch_shape, dtype=np.int64))
         mb, cb, eb = np.zeros((B, P, 7)), np.zeros((B, P, 7, 7)), np.zeros((B, P))
-        if properties:
+        # a trace with losses: the points no particle of a sample reaches have no moments (NaN) and take no cotangent
+        dead = np.asarray(self.trace.num_survivors).reshape(B, P) == 0 if self._sets else np.zeros((B, P), dtype=bool)
+        if properties and dead.any():
+            for name, bar in properties.items():
+                if name != "energy":
+                    self._refuse_cotangent_on_nobody(np.broadcast_to(np.asarray(bar, dtype=np.float64), (*batch_shape, P)).reshape(B, P),
+                                                     dead, repr(name))
+            with np.errstate(all="ignore"):
+                pm, pc, pe = trace_property_cotangents(self.trace, {n: v for n, v in properties.items() if n != "energy"})
+            pm, pc, pe = pm.reshape(B, P, 7), pc.reshape(B, P, 7, 7), pe.reshape(B, P)
+            pm[dead], pc[dead], pe[dead] = 0.0, 0.0, 0.0  # (0 x NaN of the rules above)
+            mb += pm
+            cb += pc
+            eb += pe
+            if "energy" in properties:
+                eb += np.broadcast_to(np.asarray(properties["energy"], dtype=np.float64), (*batch_shape, P)).reshape(B, P)
+        elif properties:
             pm, pc, pe = trace_property_cotangents(self.trace, properties)
             mb += pm.reshape(B, P, 7)
             cb += pc.reshape(B, P, 7, 7)
@@ -590,7 +669,19 @@ class TrackAlongVJP:
             for k in points:  # an active BPM reads (mu_x, mu_y) of the beam that ENTERS it: point k (bpm.py:48-54)
                 mb[:, k, 0] += bar[0].reshape(B)
                 mb[:, k, 2] += bar[1].reshape(B)
+        if dead.any():
+            self._refuse_cotangent_on_nobody(np.abs(mb).sum(axis=-1) + np.abs(cb).sum(axis=(-1, -2)), dead, "the moments")
         return mb, cb, eb
+
+    def _refuse_cotangent_on_nobody(self, bar, dead, what):
+        """`bar` (B, P) must be zero where `dead`: the first offender is named by sample and point."""
+        wrong = np.argwhere(dead & (bar != 0))
+        if len(wrong):
+            b, k = (int(v) for v in wrong[0])
+            sample = tuple(int(v) for v in np.unravel_index(b, self.beam.batch_shape)) if self.beam.batch_shape else ()
+            raise ValueError(
+                f"track_along_vjp: a non-zero cotangent of {what} on sample {sample}, point {k}, which no particle reaches "
+                f"(transmission 0 there): the moments of nobody have no gradient")
 
     def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, trajectories_bar=None,
                  **properties) -> Gradients:
@@ -631,11 +722,7 @@ class TrackAlongVJP:
             K = len(self.chosen)
             rec_dev = None
             if with_moments:
-                rec = np.zeros((B, P, _ffi.MOMENT_STRIDE), dtype=np.float64)
-                rec[..., :7] = mb
-                rows, cols = np.triu_indices(6)
-                rec[..., 7:28] = (cb[..., rows, cols] + cb[..., cols, rows]) * np.where(rows == cols, 0.5, 1.0)
-                rec_dev = rt.to_device(rec)
+                rec_dev = rt.to_device(_record_cotangents(mb, cb))
             else:
                 g_mu = g_cov = None
             wb_dev = rt.to_device(wb)
@@ -645,12 +732,16 @@ class TrackAlongVJP:
                 p(eb_dev), p(g_par), p(g_en), p(g_mu), p(g_cov), K, p(states["trajectories"]), p(wb_dev), p(g_chosen)))
             return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov,
                              chosen_dev=g_chosen)
+        if self._sets:
+            rec_dev = rt.to_device(_record_cotangents(mb, cb))
+            A = len(program.apertures)
+            at = (C.c_int32 * A)(*[step for step, _, _ in program.apertures])
+            rt.check(rt.lib.lynx_track_particles_along_backward_losses(
+                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]), p(rec_dev), p(eb_dev), A, at,
+                p(self._set_records), p(g_par), p(g_en)))
+            return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, survivors=True)
         if isinstance(beam, ParticleBeam):
-            rec = np.zeros((B, P, _ffi.MOMENT_STRIDE), dtype=np.float64)
-            rec[..., :7] = mb
-            rows, cols = np.triu_indices(6)  # (the order of the record's triangle, `_tri`)
-            rec[..., 7:28] = (cb[..., rows, cols] + cb[..., cols, rows]) * np.where(rows == cols, 0.5, 1.0)
-            rec_dev = rt.to_device(rec)
+            rec_dev = rt.to_device(_record_cotangents(mb, cb))
             rt.check(rt.lib.lynx_track_particles_along_backward(
                 rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]), p(rec_dev), p(eb_dev),
                 p(g_par), p(g_en), p(g_mu), p(g_cov)))
@@ -662,7 +753,7 @@ class TrackAlongVJP:
         return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
 
 
-def track_along_vjp(segment, beam, trajectories=None):
+def track_along_vjp(segment, beam, trajectories=None, losses=False):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
     callable vector-Jacobian product of the moments and energies at every point:
@@ -681,8 +772,25 @@ def track_along_vjp(segment, beam, trajectories=None):
         g[segment.HCOR1]["angle"], g.chosen_particles
 
     and an active cavity in front of a ParticleBeam is no obstacle to `trajectories_bar` and `energy_bar`.
+
+    `losses=True` (a ParticleBeam): the forward pass is `segment.track_along(beam, losses=True)` -- active `Aperture`s remove
+    particles, `vjp.trace` has `num_survivors`, `transmission`, `lost_in`, `lost_at` -- and every cotangent above is one of
+    the SURVIVING beam at that point (a property's own count; a BPM reads the centroid of the particles alive in front of it):
+
+        vjp = lynx_amd.grad.track_along_vjp(segment, beam, losses=True)
+        k = vjp.trace.index_of("SCREEN")
+        g = vjp(sigma_x=w, sigma_y=w)            # w (*batch, P), non-zero at point k: sizes of the collimated beam there
+        g[segment.Q1]["k1"], g.energy
+
+    The set of survivors is locally constant in the magnet settings and is HELD FIXED: the transmission is a step function
+    and has no gradient, the moments over the survivors have one almost everywhere, and that is what is returned
+    (lynx_moments_by_loss, lynx_track_particles_along_backward_losses).  An `Aperture`'s own `x_max` and `y_max`
+    therefore get gradient 0, and `g.mu`, `g.cov` are None: no single set of particles came in.  A non-zero cotangent on a
+    point no particle of a sample reaches is a ValueError.  At most 15 active apertures; not together with
+    `trajectories=`.  Without an active aperture, or with a ParameterBeam (apertures pass it unchanged), `losses=True` is
+    the plain call.
     """
-    return TrackAlongVJP(segment, beam, trajectories)
+    return TrackAlongVJP(segment, beam, trajectories, losses)
 
 
 def track_vjp(segment, beam):
