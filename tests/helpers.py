@@ -132,6 +132,71 @@ MOMENT_KEYS = ("mu_x", "mu_xp", "mu_y", "mu_yp", "mu_s", "mu_p", "sigma_x", "sig
                "sigma_p", "sigma_xxp", "sigma_yyp")
 
 
+def tri_slot(i, j):
+    """Slot of cov[i, j] = cov[j, i] in a moment record (include/lynx_hip.h: 6 means, 1, the 21 entries of the triangle)."""
+    i, j = min(i, j), max(i, j)
+    return 7 + i * 6 - (i * (i - 1)) // 2 + (j - i)
+
+
+def biased_covariance(particles, alive=None):
+    """
+    (*batch, 6, 6) float64: the biased covariance of (*batch, N, 7) particles, by numpy in float64 from the stored values.
+    `alive` (*batch, N) bool: over each sample's survivors alone (their number differs from sample to sample); a sample
+    nobody is left in is NaN everywhere.
+    """
+    P = np.asarray(particles)
+    batch = P.shape[:-2]
+    out = np.full((*batch, 6, 6), np.nan)
+    with np.errstate(all="ignore"):
+        for b in np.ndindex(*batch):  # (sample by sample: a sample's float64 copy stays in the cache)
+            q = (P[b] if alive is None else P[b][alive[b]])[:, :6].astype(np.float64)
+            if len(q):
+                q -= q.mean(axis=0)
+                out[b] = q.T @ q / len(q)
+    return out
+
+
+OFF_DIAGONAL = [(i, j) for i in range(6) for j in range(i + 1, 6)]
+
+
+def correlations(particles, alive=None):
+    """(*batch, 15): |correlation| of the 15 off-diagonal slots of the particles' covariance (a slot that is NaN counts as 0)."""
+    cov = biased_covariance(particles, alive)
+    with np.errstate(all="ignore"):
+        sig = np.sqrt(np.einsum("...ii->...i", cov))
+        rho = np.abs(cov / (sig[..., :, None] * sig[..., None, :]))
+    return np.nan_to_num(np.stack([rho[..., i, j] for i, j in OFF_DIAGONAL], axis=-1))
+
+
+def covariance_distances(got_cov, ref_particles_or_cov, alive=None):
+    """
+    EVERY entry (i, j) of a (*batch, 6, 6) covariance against the reference's: |got - ref| / (sigma_i sigma_j), the sigmas
+    the reference's own -- the scale `moment_distances` measures sigma_xxp in.  The reference is a (*batch, 6, 6) covariance,
+    or (*batch, N, 7) particles, whose biased float64 covariance `biased_covariance` takes (over `alive`, if given).  The
+    NaN patterns must be equal.  Where the reference has no spread at all (one particle: sigma = 0) the covariance must be
+    0 exactly.  Returns (worst distance, (i, j, sample)) -- `sample` the batch index of the worst entry -- so that a
+    failure names the slot.
+    """
+    got = np.asarray(got_cov, dtype=np.float64)
+    ref = np.asarray(ref_particles_or_cov)
+    ref = biased_covariance(ref, alive) if ref.shape[-1] == 7 else np.asarray(ref, dtype=np.float64)
+    assert got.shape == ref.shape and got.shape[-2:] == (6, 6), (got.shape, ref.shape)
+    nan_g, nan_r = np.isnan(got), np.isnan(ref)
+    if not np.array_equal(nan_g, nan_r):
+        *sample, i, j = (int(v) for v in np.argwhere(nan_g != nan_r)[0])
+        raise AssertionError(f"NaN pattern differs: first at cov[{i}, {j}] of sample {tuple(sample)}: got {got[(*sample, i, j)]}, "
+                             f"reference {ref[(*sample, i, j)]}")
+    with np.errstate(all="ignore"):
+        sig = np.sqrt(np.einsum("...ii->...i", ref))
+        scale = np.nan_to_num(sig[..., :, None] * sig[..., None, :]) + 1e-300
+        d = np.where(nan_r, 0.0, np.abs(got - ref) / scale)
+    d = np.where(np.isnan(d), np.inf, d)  # (an inf on one side only)
+    if d.size == 0:
+        return 0.0, (0, 0, ())
+    *sample, i, j = (int(v) for v in np.unravel_index(np.argmax(d), d.shape))
+    return float(d[(*sample, i, j)]), (i, j, tuple(sample))
+
+
 def moment_distances(got, ref, scale=None):
     """
     Per beam moment, the largest distance over the samples between `got` and `ref` (dicts key -> array, or objects with

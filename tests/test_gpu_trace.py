@@ -10,7 +10,7 @@ import pytest
 
 from oracle import lynx_oracle as o
 
-from .helpers import MOMENT_KEYS, assert_parameter_beam, make_lattice, moment_distances, rel_err
+from .helpers import MOMENT_KEYS, assert_parameter_beam, covariance_distances, make_lattice, moment_distances, rel_err
 from .test_gpu_parity import KICK_MOMENTS, TOL_KICK_F64, TOL_MOM, TOL_P
 
 pytestmark = pytest.mark.gpu
@@ -75,11 +75,18 @@ def assert_trace(trace, beams, dtype, beams64=None, first_kick=None, n=None, nan
     """Every moment at every point within TOL_MOM of the chain; float32 behind an active cavity: the moments the kick
     decides also within TOL_KICK_F64 of the float64 chain.  Where the reference itself returns NaN (N = 1: the unbiased
     sigma; `nan_points`: behind a cavity without voltage, whose map has NaN entries) the NaN patterns must be equal and
-    every other moment is held to the same tolerance."""
+    every other moment is held to the same tolerance.  And ALL 36 entries of the biased covariance at every point
+    (`trace.cov`, `at(k)["cov"]`) within TOL_MOM of the float64 numpy covariance of the chain's particles there, in units of
+    sigma_i sigma_j (`covariance_distances`: NaN patterns equal; one particle: 0 exactly)."""
     dtype = np.dtype(dtype).type
     assert trace.num_points == len(beams)
-    worst = 0.0
+    worst, worst_cov, cov = 0.0, (0.0, None), trace.cov
+    assert cov.shape == (*trace.batch_shape, len(beams), 6, 6)
     for k, beam in enumerate(beams):
+        d_cov, where = covariance_distances(cov[..., k, :, :], beam["particles"])
+        worst_cov = max(worst_cov, (d_cov, (k, *where)), key=lambda v: v[0])
+        assert d_cov <= TOL_MOM[dtype], ("cov", k, d_cov, where)
+        assert np.array_equal(trace.at(k)["cov"], cov[..., k, :, :], equal_nan=True), k
         ref = o.beam_moments(beam, ddof=1)
         d = nan_aware_distances(point(trace, k), ref) if (n == 1 or k in nan_points) else moment_distances(point(trace, k), ref)
         worst = max(worst, max(d.values()))
@@ -88,7 +95,8 @@ def assert_trace(trace, beams, dtype, beams64=None, first_kick=None, n=None, nan
         if beams64 is not None and first_kick is not None and k > first_kick and n != 1:
             d64 = moment_distances(point(trace, k), o.beam_moments(beams64[k], ddof=1))
             assert max(d64[key] for key in KICK_MOMENTS) <= TOL_KICK_F64, (k, d64)
-    print(f"trace: worst moment distance over {len(beams)} points {worst:.2e}")
+    print(f"trace {np.dtype(dtype).name}: worst moment distance over {len(beams)} points {worst:.2e}; worst covariance distance {worst_cov[0]:.2e} "
+          f"at (point, i, j, sample) {worst_cov[1]}")
     return worst
 
 
@@ -125,14 +133,119 @@ def mixed_desc(shape, rng, dead_cavity=False):
     ] + ([("cavity", dict(length=f(1.0), voltage=f(0.0), phase=f(1.0), frequency=f(1.3e9)))] if dead_cavity else [])
 
 
+def correlated_particles(shape, n, seed, dtype):
+    """
+    `o.gaussian_particles` of SIGMA with every pair of coordinates correlated on the way in: correlation matrix
+    0.5 I + 0.5 v v^T, v = (+, -, +, +, -, +) -- |rho| = 0.5 in all 15 off-diagonal slots, signs mixed -- and the SIGMA
+    of the plain beam.  A covariance check downstream then sees no slot that is sampling noise alone.
+    """
+    v = np.array([1.0, -1.0, 1.0, 1.0, -1.0, 1.0])
+    L = np.linalg.cholesky(0.5 * np.eye(6) + 0.5 * np.outer(v, v))
+    P = o.gaussian_particles(shape, n, seed=seed, dtype=np.float64, sigma=[1.0] * 6)
+    P[..., :6] = (P[..., :6] @ L.T) * np.array(SIGMA)
+    return P.astype(dtype)
+
+
+def coupled_desc(shape, rng):
+    """
+    Six elements that couple every pair of coordinates in every sample: drift, tilted misaligned quadrupole (x-y), tilted
+    dipole (dispersion in both planes, the s row), solenoid (x-y once more), gaining cavity (s-delta), drift.  The
+    strengths keep away from 0, so that no sample of a large batch is an uncoupled one; tests/test_covariance_check_host.py
+    asserts the correlations from the oracle alone.  No BPM: a float32 `Segment.track` walks it as units.
+    """
+    f = lambda v: np.full(shape, v)  # noqa: E731
+    away = lambda lo, hi: rng.uniform(lo, hi, shape) * rng.choice([-1.0, 1.0], shape)  # noqa: E731
+    return [
+        ("drift", dict(length=f(0.6))),
+        ("quadrupole", dict(length=f(0.2), k1=away(2, 5), tilt=away(0.3, 1.0), misalignment=rng.normal(0, 1e-4, (*shape, 2)))),
+        ("dipole", dict(length=f(0.5), angle=rng.uniform(0.1, 0.2, shape), e1=f(0.05), e2=f(0.02), fringe_integral=f(0.4),
+                        gap=f(0.02), tilt=f(0.3))),
+        ("solenoid", dict(length=f(0.3), k=away(0.8, 2.0))),
+        ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, shape), phase=rng.uniform(-10, 10, shape),
+                        frequency=f(1.3e9))),
+        ("drift", dict(length=f(0.4))),
+    ]
+
+
+TWISS_KEYS = ("emittance", "beta", "alpha", "normalized_emittance")
+
+
+def assert_twiss(trace, beams, beams64, dtype):
+    """
+    emittance, beta, alpha and the normalised emittance of both planes at every point against `o.beam_moments(ddof=1)` of
+    the FLOAT64 chain.  The emittance is sqrt(sigma^2 sigma'^2 (1 - rho^2)) and cancels as |rho| -> 1, so the bounds follow
+    from the record's own tolerance d on sigma, sigma' (relative) and the covariance (in sigma sigma'), to first order:
+    eps^2 = sigma^2 sigma'^2 - c^2 moves by <= (4 + 2 |rho|) d sigma^2 sigma'^2, so eps by <= 3 d / (1 - rho^2)
+    relative; beta = sigma^2 / eps by <= 2 d + 3 d / (1 - rho^2); alpha = -c / eps by <= d / sqrt(1 - rho^2) +
+    3 |alpha| d / (1 - rho^2).  Asserted: relative error of eps, eps_n and beta <= 5 d / (1 - rho^2), absolute error of
+    alpha <= 5 d (1 + |alpha|) / (1 - rho^2), rho the reference's own correlation at the point.  float64: d = TOL_MOM;
+    float32: d = TOL_MOM plus the distance, in those three moments, of the oracle's float32 chain from its float64 chain
+    at the point.  Points where the reference is NaN (one particle; behind the dead cavity) are left out, no others.
+    """
+    dtype = np.dtype(dtype).type
+    worst = {key: 0.0 for key in TWISS_KEYS}
+    compared = 0
+    for k, beam64 in enumerate(beams64):
+        with np.errstate(all="ignore"):
+            ref = o.beam_moments(beam64, ddof=1)
+            own = o.beam_moments(beams[k], ddof=1)
+        for plane, cross in (("x", "sigma_xxp"), ("y", "sigma_yyp")):
+            sa, sb, c = (np.asarray(ref[key], dtype=np.float64) for key in ("sigma_" + plane, "sigma_" + plane + "p", cross))
+            delta = np.full(sa.shape, TOL_MOM[dtype])
+            if dtype == np.float32:
+                with np.errstate(all="ignore"):
+                    delta = delta + np.maximum.reduce([np.abs(own["sigma_" + plane] - sa) / sa, np.abs(own["sigma_" + plane + "p"] - sb) / sb,
+                                                       np.abs(own[cross] - c) / (sa * sb)])
+            with np.errstate(all="ignore"):
+                one_minus_rho2 = 1.0 - (c / (sa * sb)) ** 2
+            for key in TWISS_KEYS:
+                want = np.asarray(ref[f"{key}_{plane}"], dtype=np.float64)
+                got = np.asarray(getattr(trace, f"{key}_{plane}")[..., k], dtype=np.float64)
+                use = ~np.isnan(want)
+                assert not np.isnan(got[use]).any(), (key, plane, k, got, want)
+                if not use.any():
+                    continue
+                compared += int(use.sum())
+                bound = 5 * delta / one_minus_rho2 * ((1 + np.abs(want)) if key == "alpha" else np.abs(want))
+                err = np.abs(got - want)
+                worst[key] = max(worst[key], float(np.max(err[use] / bound[use])))
+                assert np.all(err[use] <= bound[use]), (key, plane, k, got, want, bound)
+    print(f"twiss: worst error in units of its bound {({key: round(v, 4) for key, v in worst.items()})}; {compared} values compared")
+    return compared
+
+
+# `mixed_desc` per batch shape: with these seeds every off-diagonal slot of the covariance has |correlation| >= 0.1 at some
+# point in every sample, for every n below (asserted from the oracle alone in tests/test_covariance_check_host.py)
+LATTICE_SEED = {(3,): 21, (2, 2): 23}
+
+
+def every_element_kind_case(dtype, shape, n):
+    desc = mixed_desc(shape, np.random.default_rng(LATTICE_SEED[shape]), dead_cavity=True)
+    P = o.gaussian_particles(shape, n, seed=3 + n, dtype=dtype, sigma=SIGMA)
+    return desc, P, np.full(shape, 1e8, dtype=dtype)
+
+
 @pytest.mark.parametrize("n", [1, 63, 64, 1000, 70_001])
 @pytest.mark.parametrize("shape", [(3,), (2, 2)])
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_every_element_kind_at_every_point(lx, dtype, shape, n):
-    desc = mixed_desc(shape, np.random.default_rng(21), dead_cavity=True)
+    """n = 70 001 is 274 tiles (float32) / 547 (float64); a batch of 3 or 4 caps the waves per sample at 1024 / 768, so
+    there are as many waves as tiles (rounded up to 276 / 548), more than 256: those cases, of both shapes, take
+    `k_trace_finalize<T, 1024>`; every other one takes `k_trace_finalize<T, 256>`."""
+    every_element_kind(lx, dtype, shape, n)
+
+
+@pytest.mark.parametrize("dtype,n", [(np.float32, 255), (np.float32, 256), (np.float32, 257),
+                                     (np.float64, 127), (np.float64, 128), (np.float64, 129)])
+def test_every_element_kind_at_the_tile_edges_of_the_plain_trace(lx, dtype, n):
+    """A tile of `track_particles_along_t` is 64 U particles, U = 4 (float32) / 2 (float64): one particle short of a full
+    tile, a full tile, and a second tile (a second wave) of one particle."""
+    every_element_kind(lx, dtype, (3,), n)
+
+
+def every_element_kind(lx, dtype, shape, n):
+    desc, P, energy = every_element_kind_case(dtype, shape, n)
     elements, specs = make_lattice(desc, dtype, lx)
-    P = o.gaussian_particles(shape, n, seed=3 + n, dtype=dtype, sigma=SIGMA)
-    energy = np.full(shape, 1e8, dtype=dtype)
     segment = lx.Segment(elements)
     trace = segment.track_along(lx.ParticleBeam(P, energy, dtype=dtype))
     beams, readings = chain(specs, o.particle_beam(P, energy, dtype), dtype)
@@ -142,6 +255,8 @@ def test_every_element_kind_at_every_point(lx, dtype, shape, n):
         beams64, _ = chain(specs64, o.particle_beam(P.astype(np.float64), energy.astype(np.float64), np.float64), np.float64)
     first_kick = [k for k, (kind, kw) in enumerate(desc) if kind == "cavity" and np.any(kw["voltage"] != 0)][0]
     assert_trace(trace, beams, dtype, beams64, first_kick, n, nan_points=(len(desc),))
+    compared = assert_twiss(trace, beams, beams if beams64 is None else beams64, dtype)
+    assert compared == (0 if n == 1 else 8 * len(desc) * int(np.prod(shape)))  # (every point but the one behind the dead cavity)
     assert np.isnan(trace.mu_x[..., -1]).all() and not np.isnan(trace.records[..., :-1, :]).any()
     assert trace.s.shape == (len(desc) + 1, *shape) and trace.mu.shape == (*shape, len(desc) + 1, 6)
     assert trace.beta_x.shape == (*shape, len(desc) + 1) and trace.num_particles == n
@@ -159,6 +274,43 @@ def test_every_element_kind_at_every_point(lx, dtype, shape, n):
         assert have.shape == (2, *shape) and have.dtype == np.dtype(dtype)
         assert np.all(np.abs(have - want) <= TOL_MOM[dtype] * (np.abs(want) + 3 * sig_x)), (k, have, want)
     assert elements[0].reading is None
+
+
+def two_tiles_per_wave_case(dtype, shared):
+    shape, n = (300,), {np.float32: 4097, np.float64: 2049}[np.dtype(dtype).type]
+    desc = coupled_desc(shape, np.random.default_rng(22))
+    P = correlated_particles((1,) if shared else shape, n, seed=3 + n, dtype=dtype)
+    return desc, P, np.full(shape, 1e8, dtype=dtype)
+
+
+@pytest.mark.parametrize("dtype,shared", [(np.float32, False), (np.float64, False), (np.float32, True)])
+def test_two_tiles_per_wave_and_waves_without_a_tile(lx, dtype, shared):
+    """
+    `track_particles_along_t` with 256 CUs and a batch of 300: the cap is ceil(256 * 12 / 300) = 11 waves per sample; n =
+    4097 (float32, tiles of 256) / 2049 (float64, tiles of 128) is 17 tiles, so tiles_per_wave = ceil(17 / 11) = 2, nine
+    waves own tiles -- the ninth one tile, of one particle -- and the launch is rounded up to 12 waves: three own none.
+    That is the `first ? 0 : *cell` accumulation of `trace_deposit` over a wave's second tile, and the empty slabs in
+    front of `k_trace_finalize<T, 256>`.  (Another CU count changes the cap: ceil(12 cus / 300) must stay in 9 .. 16 for
+    two tiles per wave.)  The lattice couples every pair of coordinates; `shared`: one incoming beam for the batch.
+    """
+    desc, P, energy = two_tiles_per_wave_case(dtype, shared)
+    shape, n = energy.shape, P.shape[-2]
+    assert -(-n // (64 * (4 if dtype == np.float32 else 2))) == 17
+    elements, specs = make_lattice(desc, dtype, lx)
+    if shared:
+        beam = lx.ParticleBeam(P, energy[:1], dtype=dtype).broadcast(shape)
+        assert beam.is_shared
+        P = np.ascontiguousarray(np.broadcast_to(P, (*shape, n, 7)))
+    else:
+        beam = lx.ParticleBeam(P, energy, dtype=dtype)
+    trace = lx.Segment(elements).track_along(beam)
+    beams, _ = chain(specs, o.particle_beam(P, energy, dtype), dtype)
+    assert trace.num_points == 7 and trace.num_particles == n
+    assert_trace(trace, beams, dtype)
+    got = np.asarray(trace.outgoing.particles)
+    for c in range(7):
+        assert rel_err(got[..., c], beams[-1]["particles"][..., c]) < TOL_P[dtype], c
+    assert np.array_equal(trace.outgoing.moment_record(covariance=True), trace.records[..., -1, :])
 
 
 def test_a_centroid_that_moves_keeps_float32_variances(lx):

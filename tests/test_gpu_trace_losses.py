@@ -11,7 +11,8 @@ Mask parity: a particle is ON THE EDGE of an aperture if the float64 chain puts 
 is on no edge.  The inputs are held to: no edge particle at all for n <= 1000 and for float64, at most 1e-3 n per sample
 and aperture above that -- asserted from the oracle alone, before the GPU result is looked at (the seeds of SEEDS were
 picked so).  The moments are then compared with the oracle's moments over the survivor set `lost_at` gives, at the
-tolerances of the plain trace (TOL_MOM, TOL_KICK_F64), and `num_survivors` with that set's counts, exactly.
+tolerances of the plain trace (TOL_MOM, TOL_KICK_F64), and `num_survivors` with that set's counts, exactly; so are all
+36 entries of the biased covariance at every point, with the float64 numpy covariance of that survivor set.
 """
 
 import warnings
@@ -21,9 +22,9 @@ import pytest
 
 from oracle import lynx_oracle as o
 
-from .helpers import MOMENT_KEYS, make_lattice, moment_distances, rel_err
+from .helpers import MOMENT_KEYS, biased_covariance, covariance_distances, make_lattice, moment_distances, rel_err
 from .test_gpu_parity import KICK_MOMENTS, TOL_KICK_F64, TOL_MOM
-from .test_gpu_trace import SIGMA, chain, point, upcast
+from .test_gpu_trace import SIGMA, chain, correlated_particles, point, upcast
 
 pytestmark = pytest.mark.gpu
 
@@ -31,6 +32,7 @@ EDGE = {np.float32: 1e-4, np.float64: 1e-9}
 # gaussian_particles seeds per n for which the float32 cases with n <= 1000 have no particle on an edge (searched on the
 # host with `expectation` alone: the condition is asserted in every case before the GPU result is looked at)
 SEEDS = {1: 0, 63: 0, 64: 0, 127: 0, 128: 0, 129: 0, 255: 0, 256: 0, 257: 2, 1000: 5, 70_001: 0}
+SEEDS_COUPLED = {129: 0, 257: 0, 1000: 0}  # `correlated_particles` seeds of variant "c", searched the same way
 
 
 @pytest.fixture(scope="module")
@@ -170,12 +172,23 @@ def assert_losses(trace, desc, P, energy, dtype, expected=None, overflows=()):
     # the survivor set the trace itself reports: counts exactly, moments at the plain trace's tolerances
     first_kick = next((k for k, (kind, kw) in enumerate(desc) if kind == "cavity" and np.any(kw["voltage"] != 0)), None)
     killer = np.array(apertures + [len(desc)])[trace.lost_at]  # element that removed the particle (-1 -> beyond the end)
-    worst = 0.0
-    assert trace.num_points == len(beams)
+    worst, worst_cov, cov = 0.0, (0.0, None), trace.cov
+    assert trace.num_points == len(beams) and cov.shape == (*batch, len(beams), 6, 6)
     for k, beam in enumerate(beams):
         alive = killer >= k  # aperture j clears its particles from point j + 1 on
         count = alive.sum(axis=-1)
         assert np.array_equal(trace.num_survivors[..., k], count), (k, trace.num_survivors[..., k], count)
+        # all 36 entries of the biased covariance of each sample's survivors (nobody left: NaN; one left: 0 exactly)
+        got_cov, ref_cov = np.array(cov[..., k, :, :], dtype=np.float64), biased_covariance(beam["particles"], alive)
+        for kk, key, b in overflows:  # (the variance of the same coordinate: the same rule as for the sigma below)
+            if kk == k:
+                c = ["x", "xp", "y", "yp", "s", "p"].index(key[len("sigma_"):])
+                assert not np.isfinite(got_cov[b, c, c]), (k, key, b, got_cov[b, c, c])
+                got_cov[b, c, c] = ref_cov[b, c, c]
+        d_cov, where = covariance_distances(got_cov, ref_cov)
+        worst_cov = max(worst_cov, (d_cov, (k, *where)), key=lambda v: v[0])
+        assert d_cov <= TOL_MOM[dtype], ("cov", k, d_cov, where)
+        assert np.array_equal(trace.at(k)["cov"], cov[..., k, :, :], equal_nan=True), k
         ref = survivor_moments(beam, alive)
         got = point(trace, k)
         for kk, key, b in overflows:
@@ -198,7 +211,8 @@ def assert_losses(trace, desc, P, energy, dtype, expected=None, overflows=()):
         assert np.array_equal(trace.lost_in[..., ordinal], (trace.lost_at == ordinal).sum(axis=-1))
     lost_any = bool((trace.lost_at >= 0).any())
     assert (trace.outgoing is None) == lost_any
-    print(f"losses: worst moment distance over {len(beams)} points {worst:.2e}; lost {(trace.lost_at >= 0).sum(axis=-1).tolist()} of {n}")
+    print(f"losses {np.dtype(dtype).name}: worst moment distance over {len(beams)} points {worst:.2e}; worst covariance distance {worst_cov[0]:.2e} at "
+          f"(point, i, j, sample) {worst_cov[1]}; lost {(trace.lost_at >= 0).sum(axis=-1).tolist()} of {n}")
     return worst
 
 
@@ -213,16 +227,26 @@ def mixed_desc(shape, energy, dtype, variant):
     either side, quadrupole, drift, an aperture as last leaf.  The apertures are sigma-sized where they stand (x_max =
     1 sigma_x, y_max = 1.5 sigma_y of the unclipped float64 chain there; per-sample limits 0.8 .. 1.2 of that).  Variant
     "a": rectangular shared, elliptical per sample, rectangular per sample; variant "b": elliptical per sample,
-    rectangular shared, elliptical shared.
+    rectangular shared, elliptical shared.  Variant "c": the apertures of "a" in optics that couple the planes (the
+    quadrupole tilted, a tilted dipole behind the corrector), for a beam that comes in correlated (`mixed_case`): every
+    off-diagonal slot of the survivors' covariance is then far from 0 somewhere (tests/test_covariance_check_host.py).
     """
     rng = np.random.default_rng(17)
     f = lambda v: np.full(shape, v)  # noqa: E731
+    coupled = variant == "c"
+    if coupled:  # the planes and the dispersion coupled in front of the second aperture: a tilted quadrupole and dipole
+        variant, away = "a", lambda lo, hi: rng.uniform(lo, hi, shape) * rng.choice([-1.0, 1.0], shape)  # noqa: E731
+        first = dict(length=f(0.2), k1=away(2, 5), tilt=away(0.3, 1.0), misalignment=rng.normal(0, 2e-5, (*shape, 2)))
+    else:
+        first = dict(length=f(0.2), k1=rng.uniform(-5, 5, shape), misalignment=rng.normal(0, 2e-5, (*shape, 2)))
     optics = [
         ("aperture", None),
         ("drift", dict(length=f(0.6))),
-        ("quadrupole", dict(length=f(0.2), k1=rng.uniform(-5, 5, shape), misalignment=rng.normal(0, 2e-5, (*shape, 2)))),
+        ("quadrupole", first),
         ("bpm", dict(is_active=True)),
         ("hcor", dict(length=f(0.1), angle=rng.uniform(1e-5, 5e-5, shape))),
+    ] + ([("dipole", dict(length=f(0.5), angle=rng.uniform(0.1, 0.2, shape), e1=f(0.05), e2=f(0.02), fringe_integral=f(0.4),
+                          gap=f(0.02), tilt=f(0.3)))] if coupled else []) + [
         ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, shape), phase=rng.uniform(-10, 10, shape), frequency=f(1.3e9))),
         ("aperture", None),
         ("quadrupole", dict(length=f(0.2), k1=rng.uniform(-5, 5, shape))),
@@ -251,7 +275,10 @@ def mixed_desc(shape, energy, dtype, variant):
 
 
 def mixed_case(dtype, shape, n, variant):
-    P = o.gaussian_particles(shape, n, seed=SEEDS[n], dtype=dtype, sigma=SIGMA)
+    if variant == "c":
+        P = correlated_particles(shape, n, seed=SEEDS_COUPLED[n], dtype=dtype)
+    else:
+        P = o.gaussian_particles(shape, n, seed=SEEDS[n], dtype=dtype, sigma=SIGMA)
     energy = np.full(shape, 1e8, dtype=dtype)
     desc = mixed_desc(shape, energy, dtype, variant)
     return desc, P, energy
@@ -294,6 +321,15 @@ def test_losses_in_a_mixed_lattice_at_every_tile_boundary(lx, dtype, shape, n):
 @pytest.mark.parametrize("dtype", [np.float32, np.float64])
 def test_the_other_shapes_and_sharing_of_the_limits(lx, dtype, shape, n):
     run_mixed(lx, dtype, shape, n, "b")
+
+
+@pytest.mark.parametrize("n", [129, 257, 1000])
+@pytest.mark.parametrize("shape", [(3,), (2, 2)])
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_losses_in_optics_that_couple_every_pair_of_coordinates(lx, dtype, shape, n):
+    """The survivors' x-y, dispersion and s-row covariances where they are far from 0: one particle past a tile edge of
+    either dtype (129, 257), and several tiles."""
+    run_mixed(lx, dtype, shape, n, "c")
 
 
 # ---------------------------------------------------------------------------------------------
