@@ -2308,6 +2308,63 @@ __global__ __launch_bounds__(64) void k_reduce_observers(const double* __restric
 }
 
 // ---------------------------------------------------------------------------------------
+// One step of the ParameterBeam's recursion, mu' = M mu, C' = M C M^T (element.py:71-82), then the cavity branch.  Every
+// kernel that walks mu and C through a step table calls one of the two forms below: the same operations in the same
+// order, so they agree bit for bit on the same table row.
+//
+// moment_cavity_branch: what an active cavity does to the moments BEHIND the linear step (cavity.py:134-140, 202-218):
+// the kick on the incoming s, delta, C55 restored, and T566 c55^2 + T556 c45 c55 + T555 c44^2 in C44, C45, C54 -- with
+// s, delta, c44, c45, c55 of the INCOMING beam.  `coef` is the step's own row behind the map (the kick reads sin(phi)
+// behind the coefficients).
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ void moment_cavity_branch(const T* coef, T s_in, T d_in, T c44, T c45, T c55, T* mu, T* C) {
+  T s_o = mu[4], d_o;
+  device_cavity_kick<T>(coef, s_in, d_in, s_o, d_o);  // cavity.py:134-140, 202-206
+  mu[4] = s_o;
+  mu[5] = d_o;
+  C[5 * 7 + 5] = c55;  // cavity.py:140
+  const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
+  C[4 * 7 + 4] = v;
+  C[4 * 7 + 5] = v;
+  C[5 * 7 + 4] = v;
+}
+
+// The wave form: one wave per sample, mu [7] and C [49] in LDS, lane = entry i * 7 + j of C (lanes 49 .. 63 clamped to
+// entry 48, lanes 0 .. 6 also own mu), X = C M^T through `s_x` [49].  M: the step's row, in LDS or in memory.  `kick`
+// (uniform): the step is an active cavity.  Called by every thread of the workgroup, with mu and C visible to all of
+// them; they are again when it returns.  The barriers, by the accesses they separate:
+//   1  every read of the incoming mu, C (the products, lane 0's cavity inputs) | mu' over mu; the last step's reads of X | X
+//   2  X and mu' written | the reads of X for C', lane 0's read of mu'[4]
+//      (C' goes over C without a barrier: C was last read in front of barrier 1, C' reads X and M only)
+//   3  C' written | lane 0's cavity entries over it
+//   4  the cavity branch | whatever reads mu, C next
+template <typename T>
+__device__ __forceinline__ void moment_step_wave(const T* M, T* s_mu, T* s_cov, T* s_x, int lane, int i, int j, bool kick) {
+  const T s_in = s_mu[4], d_in = s_mu[5], c44 = s_cov[4 * 7 + 4], c45 = s_cov[4 * 7 + 5], c55 = s_cov[5 * 7 + 5];
+  T mu_new = T(0);
+  if (lane < 7) {
+    mu_new = M[lane * 7] * s_mu[0];
+#pragma unroll
+    for (int k = 1; k < 7; ++k) mu_new = t_fma(M[lane * 7 + k], s_mu[k], mu_new);
+  }
+  T x = s_cov[i * 7] * M[j * 7];  // X = C M^T
+#pragma unroll
+  for (int k = 1; k < 7; ++k) x = t_fma(s_cov[i * 7 + k], M[j * 7 + k], x);
+  __syncthreads();
+  if (lane < 49) s_x[lane] = x;
+  if (lane < 7) s_mu[lane] = mu_new;
+  __syncthreads();
+  T c = M[i * 7] * s_x[j];  // C' = M X
+#pragma unroll
+  for (int k = 1; k < 7; ++k) c = t_fma(M[i * 7 + k], s_x[k * 7 + j], c);
+  if (lane < 49) s_cov[lane] = c;
+  __syncthreads();
+  if (kick && lane == 0) moment_cavity_branch<T>(M + LYNX_COEF_OFFSET, s_in, d_in, c44, c45, c55, s_mu, s_cov);
+  __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------
 // k_track_moments: ParameterBeam path, one workgroup per sample (element.py:71-82,
 // cavity.py:134-140, 202-218): one wave when the batch is large (hundreds of thousands of
 // settings), four when it is small, where the build of a long lattice is the whole cost and
@@ -2322,8 +2379,7 @@ __device__ __forceinline__ void track_moments_sample(const LatticeDev& lat, cons
   T* s_energy = s_steps + (size_t)lat.n_steps * LYNX_STEP_STRIDE;
   T* s_mu = s_energy + lat.n_steps + 1;  // 8
   T* s_cov = s_mu + 8;                   // 49
-  T* s_x = s_cov + 49;                   // 49
-  T* s_in = s_x + 49;                    // mu_in(7) + cov_in 44,45,55 for the cavity branch
+  T* s_x = s_cov + 49;                   // 49 (the launch still provides 10 scalars behind it, unused)
 
   const int64_t b = blockIdx.x;
   const int lane = threadIdx.x;
@@ -2339,48 +2395,7 @@ __device__ __forceinline__ void track_moments_sample(const LatticeDev& lat, cons
   for (int s = 0; s < lat.n_steps; ++s) {
     lynx_step st = lat.steps[s];
     const T* M = s_steps + s * LYNX_STEP_STRIDE;
-    // keep what the cavity branch needs from the incoming beam
-    if (lane < 7) s_in[lane] = s_mu[lane];
-    if (lane == 7) s_in[7] = s_cov[4 * 7 + 4];
-    if (lane == 8) s_in[8] = s_cov[4 * 7 + 5];
-    if (lane == 9) s_in[9] = s_cov[5 * 7 + 5];
-    // mu' = T mu
-    T mu_new = T(0);
-    if (lane < 7) {
-      mu_new = M[lane * 7 + 0] * s_mu[0];
-#pragma unroll
-      for (int k = 1; k < 7; ++k) mu_new = t_fma(M[lane * 7 + k], s_mu[k], mu_new);
-    }
-    // X = cov . T^T
-    T x = s_cov[i * 7 + 0] * M[j * 7 + 0];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) x = t_fma(s_cov[i * 7 + k], M[j * 7 + k], x);
-    __syncthreads();
-    if (lane < 49) s_x[lane] = x;
-    if (lane < 7) s_mu[lane] = mu_new;
-    __syncthreads();
-    // cov' = T . X
-    T c = M[i * 7 + 0] * s_x[0 * 7 + j];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) c = t_fma(M[i * 7 + k], s_x[k * 7 + j], c);
-    __syncthreads();
-    if (lane < 49) s_cov[lane] = c;
-    __syncthreads();
-    if (st.kind == LYNX_STEP_CAVITY && (st.flags & LYNX_FLAG_CAV_GAIN) && lane == 0) {
-      const T* coef = M + LYNX_COEF_OFFSET;
-      T s_o = s_mu[4], d_o;
-      device_cavity_kick<T>(coef, s_in[4], s_in[5], s_o, d_o);  // cavity.py:134-140, 202-206
-      s_mu[4] = s_o;
-      s_mu[5] = d_o;
-      const T c44 = s_in[7], c45 = s_in[8], c55 = s_in[9];
-      s_cov[5 * 7 + 5] = c55;  // cavity.py:140
-      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 +
-                  coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
-      s_cov[4 * 7 + 4] = v;
-      s_cov[4 * 7 + 5] = v;
-      s_cov[5 * 7 + 4] = v;
-    }
-    __syncthreads();
+    moment_step_wave<T>(M, s_mu, s_cov, s_x, lane, i, j, st.kind == LYNX_STEP_CAVITY && (st.flags & LYNX_FLAG_CAV_GAIN));
   }
   if (lane < 7) mu_out[b * 7 + lane] = s_mu[lane];
   if (lane < 49) cov_out[b * 49 + lane] = s_cov[lane];
@@ -2404,17 +2419,64 @@ __global__ __launch_bounds__(256) void k_track_moments_inline(InlinePool<BYTES> 
 }
 
 // ---------------------------------------------------------------------------------------
-// k_apply_moments_lanes: ParameterBeam path for LARGE batches (hundreds of thousands of settings in one
-// call, tests/test_vectorized.py:298-321), lanes = samples: the step table comes from the lanes build,
-// a wave stages the 64 table rows of a step in LDS with coalesced loads, every lane takes its own row
-// and propagates ITS sample's moments in registers -- mu' = T mu, cov' = T cov T^T as X = cov T^T (row by
-// row in place) and cov' = T X (column by column in place), then the cavity branch (cavity.py:134-140,
-// 202-218).  Same operations in the same order per sample as k_track_moments, which keeps one
-// workgroup per sample and spends most of its lanes waiting (3 x 100 000 settings of the ARES lattice:
-// 1.56 ms there).
+// The lanes form: lanes = samples, for LARGE batches (hundreds of thousands of settings in one call,
+// tests/test_vectorized.py:298-321).  The step table comes from the lanes build, a wave stages the 64 table rows of a
+// step in LDS with coalesced loads, every lane takes its own row and propagates ITS sample's moments in registers
+// (moment_step_lanes): the operations of moment_step_wave in the same order per sample.  (The staging loop stays in the
+// two kernels: as a function it compiled, in k_trace_moments_lanes, to one load waited for at a time -- 674 against
+// 562 us for 300 000 x 11 steps.)
 // ---------------------------------------------------------------------------------------
 template <typename T> constexpr size_t apply_moments_lds() { return 64 * 68 * sizeof(T); }
 
+// mu' = M mu, X = C M^T row by row in place, C' = M X column by column in place, then the cavity branch; M: the lane's row
+template <typename T>
+__device__ __forceinline__ void moment_step_lanes(const T* M, T (&mu)[7], T (&C)[49]) {
+  const int desc = (int)M[LYNX_FLAGS_OFFSET];
+  const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
+  const T s_in = mu[4], d_in = mu[5], c44 = C[4 * 7 + 4], c45 = C[4 * 7 + 5], c55 = C[5 * 7 + 5];
+  {
+    T out[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      T acc = M[i * 7] * mu[0];
+#pragma unroll
+      for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], mu[k], acc);
+      out[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) mu[i] = out[i];
+  }
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {  // row i of X from row i of C
+    T out[7];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      T acc = C[i * 7] * M[j * 7];
+#pragma unroll
+      for (int k = 1; k < 7; ++k) acc = t_fma(C[i * 7 + k], M[j * 7 + k], acc);
+      out[j] = acc;
+    }
+#pragma unroll
+    for (int j = 0; j < 7; ++j) C[i * 7 + j] = out[j];
+  }
+#pragma unroll
+  for (int j = 0; j < 7; ++j) {  // column j of C' from column j of X
+    T out[7];
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+      T acc = M[i * 7] * C[j];
+#pragma unroll
+      for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], C[k * 7 + j], acc);
+      out[i] = acc;
+    }
+#pragma unroll
+    for (int i = 0; i < 7; ++i) C[i * 7 + j] = out[i];
+  }
+  if (kick) moment_cavity_branch<T>(M + LYNX_COEF_OFFSET, s_in, d_in, c44, c45, c55, mu, C);
+}
+
+// k_apply_moments_lanes: `Segment.track` of a ParameterBeam in the lanes form.  (k_track_moments keeps one workgroup per
+// sample and spends most of its lanes waiting: 3 x 100 000 settings of the ARES lattice took 1.56 ms there.)
 template <typename T>
 __global__ __launch_bounds__(64) void k_apply_moments_lanes(LatticeDev lat, const T* __restrict__ steps,
                                                             const T* __restrict__ mu_in, const T* __restrict__ cov_in,
@@ -2445,62 +2507,7 @@ __global__ __launch_bounds__(64) void k_apply_moments_lanes(LatticeDev lat, cons
     }
     wave_fence();
     const T* M = rows + lane * 68;
-    const int desc = (int)M[LYNX_FLAGS_OFFSET];
-    const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
-    const T s_in = mu[4], d_in = mu[5], c44 = C[4 * 7 + 4], c45 = C[4 * 7 + 5], c55 = C[5 * 7 + 5];
-    // mu' = T mu
-    {
-      T out[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        T acc = M[i * 7] * mu[0];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], mu[k], acc);
-        out[i] = acc;
-      }
-#pragma unroll
-      for (int i = 0; i < 7; ++i) mu[i] = out[i];
-    }
-    // X = cov . T^T, row i of X from row i of cov
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {
-      T out[7];
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        T acc = C[i * 7] * M[j * 7];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) acc = t_fma(C[i * 7 + k], M[j * 7 + k], acc);
-        out[j] = acc;
-      }
-#pragma unroll
-      for (int j = 0; j < 7; ++j) C[i * 7 + j] = out[j];
-    }
-    // cov' = T . X, column j of cov' from column j of X
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {
-      T out[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        T acc = M[i * 7] * C[j];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], C[k * 7 + j], acc);
-        out[i] = acc;
-      }
-#pragma unroll
-      for (int i = 0; i < 7; ++i) C[i * 7 + j] = out[i];
-    }
-    if (kick) {
-      const T* coef = M + LYNX_COEF_OFFSET;  // (the row itself: the kick reads sin(phi) behind the coefficients)
-      T s_o = mu[4], d_o;
-      device_cavity_kick<T>(coef, s_in, d_in, s_o, d_o);  // cavity.py:134-140, 202-206
-      mu[4] = s_o;
-      mu[5] = d_o;
-      C[5 * 7 + 5] = c55;  // cavity.py:140
-      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
-      C[4 * 7 + 4] = v;
-      C[4 * 7 + 5] = v;
-      C[5 * 7 + 4] = v;
-    }
+    moment_step_lanes<T>(M, mu, C);
     if (s == S - 1 && energy_out && live) energy_out[b] = M[LYNX_ENERGY_OFFSET];
   }
   if (live) {

@@ -648,14 +648,79 @@ __global__ __launch_bounds__(kTrackThreads) void k_track_bwd(
 }
 
 // ---------------------------------------------------------------------------------------
+// One step of the reverse sweep of the moment recursion (forward: moment_step_wave), one wave per sample, lane = entry
+// i * 7 + j, the state that ENTERED the step in s_mu, s_c, its row in s_m, the cotangents of what LEFT it in s_mb, s_g:
+//   G = C'_bar without the entries an active cavity overwrites, m = mu'_bar without [5]      (sweep_kick)
+//   T_bar = m (x) mu + (G M) C^T + (G^T M) C,   mu_bar = M^T m,   C_bar = M^T G M            (sweep_products)
+// in the arithmetic type A of the caller (k_moments_bwd: the lattice's; k_trace_moments_bwd, k_trace_moments_bwd_sets:
+// double).  The gradient tolerances of all three rest on these being the same operations in the same order.
+//
+// sweep_kick, lane 0 of a step that is an active cavity, in front of a barrier: the kick's 8 coefficient cotangents in
+// s_k[0..7], its direct terms d/d (mu_in[4], mu_in[5], c44, c45, c55) in s_k[8..12] (the caller adds them to mu_bar and
+// C_bar behind sweep_products), and zeros over the cotangents of the outputs the kick overwrote.
+// ---------------------------------------------------------------------------------------
+template <typename A>
+__device__ __forceinline__ void sweep_kick(const A* s_m, const A* s_mu, const A* s_c, A* s_g, A* s_mb, A* s_k) {
+  const A* cf = s_m + LYNX_COEF_OFFSET;
+  const A z4 = s_mu[4], z5 = s_mu[5], c44 = s_c[32], c45 = s_c[33], c55 = s_c[40];
+  const A m4 = s_mb[4], m5 = s_mb[5];
+  const A vb = s_g[32] + s_g[33] + s_g[39];
+  A sphi, cphi, kc[8], d4, d5;
+  phase_sincos(cf[LYNX_C_PHI], sphi, cphi);
+  kick_cotangents<A, A>(cf, sphi, cphi, z4, z5, m4, m5, kc, d4, d5);
+#pragma unroll
+  for (int q = 0; q < 8; ++q) s_k[q] = kc[q];
+  s_k[LYNX_C_T566] += vb * (c55 * c55);
+  s_k[LYNX_C_T556] += vb * (c45 * c55);
+  s_k[LYNX_C_T555] += vb * (c44 * c44);
+  s_k[8] = d4;  // d/d mu_in[4]
+  s_k[9] = d5;  // d/d mu_in[5]
+  s_k[10] = vb * A(2) * cf[LYNX_C_T555] * c44;                                                   // d/d c44
+  s_k[11] = vb * cf[LYNX_C_T556] * c55;                                                          // d/d c45
+  s_k[12] = s_g[40] + vb * (A(2) * cf[LYNX_C_T566] * c55 + cf[LYNX_C_T556] * c45);               // d/d c55
+  s_mb[5] = A(0);  // these outputs were overwritten by the kick
+  s_g[32] = A(0);
+  s_g[33] = A(0);
+  s_g[39] = A(0);
+  s_g[40] = A(0);
+}
+
+// sweep_products, every lane: tb = the lane's entry of T_bar, cb = of C_bar, mbn = of mu_bar (lanes 0 .. 6).  P = G M and
+// Q = G^T M go through s_x, s_y; the barrier between separates their writes from the reads of other lanes' entries.
+template <typename A>
+__device__ __forceinline__ void sweep_products(const A* s_m, const A* s_mu, const A* s_c, const A* s_g, const A* s_mb,
+                                               A* s_x, A* s_y, int lane, int i, int j, A& tb, A& cb, A& mbn) {
+  A pv = s_g[i * 7] * s_m[j], qv = s_g[i] * s_m[j];
+#pragma unroll
+  for (int k = 1; k < 7; ++k) {
+    pv = t_fma(s_g[i * 7 + k], s_m[k * 7 + j], pv);
+    qv = t_fma(s_g[k * 7 + i], s_m[k * 7 + j], qv);
+  }
+  if (lane < 49) {
+    s_x[lane] = pv;
+    s_y[lane] = qv;
+  }
+  __syncthreads();
+  tb = s_mb[i] * s_mu[j], cb = A(0), mbn = A(0);
+#pragma unroll
+  for (int k = 0; k < 7; ++k) {
+    tb = t_fma(s_x[i * 7 + k], s_c[j * 7 + k], tb);
+    tb = t_fma(s_y[i * 7 + k], s_c[k * 7 + j], tb);
+    cb = t_fma(s_m[k * 7 + i], s_x[k * 7 + j], cb);
+  }
+  if (lane < 7) {
+#pragma unroll
+    for (int k = 0; k < 7; ++k) mbn = t_fma(s_m[k * 7 + lane], s_mb[k], mbn);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
 // k_moments_bwd: reverse pass of k_track_moments (ParameterBeam), one wave per sample.
-//   forward per step:  mu' = M mu,  C' = M C M^T,  then for an active cavity
+//   forward per step:  moment_step_wave (lynx_device.hpp): mu' = M mu,  C' = M C M^T,  then for an active cavity
 //                      mu'[4] += T566 d^2 + T556 s d + T555 s^2,  mu'[5] = d c0 + c1 (cos a - c4),
 //                      C'[5][5] = c55,  C'[4][4] = C'[4][5] = C'[5][4] = T566 c55^2 + T556 c45 c55 + T555 c44^2
 //                      with s, d, c44, c45, c55 of the INCOMING beam (cavity.py:134-140, 202-218)
-//   reverse per step:  G = C'_bar without the overwritten entries, m = mu'_bar without [5]
-//                      T_bar = m (x) mu + (G M) C^T + (G^T M) C,   mu_bar = M^T m,   C_bar = M^T G M
-//                      plus the cavity's direct terms and its 8 coefficient cotangents.
+//   reverse per step:  sweep_kick and sweep_products above, in the lattice's dtype.
 // The states entering every step are parked in HBM by the forward sweep ([B][S+1][56]).
 // T_bar and the coefficient cotangents leave in the layout k_build_bwd consumes.
 // ---------------------------------------------------------------------------------------
@@ -683,38 +748,7 @@ __global__ __launch_bounds__(64) void k_moments_bwd(LatticeDev lat, const T* __r
     if (lane < 49) st[s * 56 + 7 + lane] = s_c[lane];
     s_m[lane] = g_steps[s * LYNX_STEP_STRIDE + lane];
     __syncthreads();
-    T mu_new = T(0);
-    if (lane < 7) {
-      mu_new = s_m[lane * 7] * s_mu[0];
-#pragma unroll
-      for (int k = 1; k < 7; ++k) mu_new = t_fma(s_m[lane * 7 + k], s_mu[k], mu_new);
-    }
-    T x = s_c[i * 7] * s_m[j * 7];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) x = t_fma(s_c[i * 7 + k], s_m[j * 7 + k], x);
-    const T s_i = s_mu[4], d_i = s_mu[5], c44 = s_c[32], c45 = s_c[33], c55 = s_c[40];
-    __syncthreads();
-    if (lane < 49) s_x[lane] = x;
-    if (lane < 7) s_mu[lane] = mu_new;
-    __syncthreads();
-    T c = s_m[i * 7] * s_x[j];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) c = t_fma(s_m[i * 7 + k], s_x[k * 7 + j], c);
-    if (lane < 49) s_c[lane] = c;
-    __syncthreads();
-    if (stp.kind == LYNX_STEP_CAVITY && (stp.flags & LYNX_FLAG_CAV_GAIN) && lane == 0) {
-      const T* coef = s_m + LYNX_COEF_OFFSET;
-      T s_o = s_mu[4], d_o;
-      device_cavity_kick<T>(coef, s_i, d_i, s_o, d_o);
-      s_mu[4] = s_o;
-      s_mu[5] = d_o;
-      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);
-      s_c[40] = c55;
-      s_c[32] = v;
-      s_c[33] = v;
-      s_c[39] = v;
-    }
-    __syncthreads();
+    moment_step_wave<T>(s_m, s_mu, s_c, s_x, lane, i, j, stp.kind == LYNX_STEP_CAVITY && (stp.flags & LYNX_FLAG_CAV_GAIN));
   }
 
   if (lane < 7) s_mb[lane] = mu_bar_out[b * 7 + lane];
@@ -728,54 +762,10 @@ __global__ __launch_bounds__(64) void k_moments_bwd(LatticeDev lat, const T* __r
     if (lane < 16) s_k[lane] = T(0);
     __syncthreads();
     const bool kick = stp.kind == LYNX_STEP_CAVITY && (stp.flags & LYNX_FLAG_CAV_GAIN);
-    if (kick && lane == 0) {
-      const T* cf = s_m + LYNX_COEF_OFFSET;
-      const T z4 = s_mu[4], z5 = s_mu[5], c44 = s_c[32], c45 = s_c[33], c55 = s_c[40];
-      const T m4 = s_mb[4], m5 = s_mb[5];
-      const T vb = s_g[32] + s_g[33] + s_g[39];
-      T sphi, cphi, kc[8], d4, d5;
-      phase_sincos(cf[LYNX_C_PHI], sphi, cphi);
-      kick_cotangents<T, T>(cf, sphi, cphi, z4, z5, m4, m5, kc, d4, d5);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s_k[q] = kc[q];
-      s_k[LYNX_C_T566] += vb * (c55 * c55);
-      s_k[LYNX_C_T556] += vb * (c45 * c55);
-      s_k[LYNX_C_T555] += vb * (c44 * c44);
-      s_k[8] = d4;  // d/d mu_in[4]
-      s_k[9] = d5;  // d/d mu_in[5]
-      s_k[10] = vb * T(2) * cf[LYNX_C_T555] * c44;                                                   // d/d c44
-      s_k[11] = vb * cf[LYNX_C_T556] * c55;                                                          // d/d c45
-      s_k[12] = s_g[40] + vb * (T(2) * cf[LYNX_C_T566] * c55 + cf[LYNX_C_T556] * c45);               // d/d c55
-      s_mb[5] = T(0);  // these outputs were overwritten by the kick
-      s_g[32] = T(0);
-      s_g[33] = T(0);
-      s_g[39] = T(0);
-      s_g[40] = T(0);
-    }
+    if (kick && lane == 0) sweep_kick<T>(s_m, s_mu, s_c, s_g, s_mb, s_k);
     __syncthreads();
-    // P = G M, Q = G^T M
-    T pv = s_g[i * 7] * s_m[j], qv = s_g[i] * s_m[j];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) {
-      pv = t_fma(s_g[i * 7 + k], s_m[k * 7 + j], pv);
-      qv = t_fma(s_g[k * 7 + i], s_m[k * 7 + j], qv);
-    }
-    if (lane < 49) {
-      s_x[lane] = pv;
-      s_y[lane] = qv;
-    }
-    __syncthreads();
-    T tb = s_mb[i] * s_mu[j], cb = T(0), mbn = T(0);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      tb = t_fma(s_x[i * 7 + k], s_c[j * 7 + k], tb);
-      tb = t_fma(s_y[i * 7 + k], s_c[k * 7 + j], tb);
-      cb = t_fma(s_m[k * 7 + i], s_x[k * 7 + j], cb);
-    }
-    if (lane < 7) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) mbn = t_fma(s_m[k * 7 + lane], s_mb[k], mbn);
-    }
+    T tb, cb, mbn;
+    sweep_products<T>(s_m, s_mu, s_c, s_g, s_mb, s_x, s_y, lane, i, j, tb, cb, mbn);
     T* tb_out = tbar + (b * S + s) * (int64_t)kGradStride;
     if (lane < 49) tb_out[lane] = tb;
     else if (lane < 57) tb_out[lane] = s_k[lane - 49];

@@ -2470,6 +2470,26 @@ static int launch_trace_finalize(lynx_ctx* ctx, int64_t B, int32_t P, int64_t wa
   return LYNX_OK;
 }
 
+// Waves per sample of a streaming pass over N particles that leaves `points` records per sample and wave: enough of them
+// to fill the GPU three waves per SIMD deep over the whole batch, whole workgroups of four, never more than there are
+// tiles -- and few enough for the slabs (256 bytes per wave and point) to stay below 1 GiB.  The plan depends on the
+// shapes alone: the same call adds the same numbers in the same order.  (The survivor sets of lynx_moments_by_loss, at
+// most 16 "points", never meet the cap, which they were planned without: more than one wave per sample means B < 12 CUs,
+// the cap is then at least 2^22 / (16 B) = 262144 / B waves, and the first bound asks for fewer than 24 CUs / B -- less
+// on any GPU of fewer than 10 000 CUs.)
+struct TraceWavePlan {
+  int64_t waves, tiles_per_wave;
+};
+static TraceWavePlan trace_wave_plan(const lynx_ctx* ctx, int64_t B, int64_t N, int U /* particles per lane */, int64_t points) {
+  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t tiles = (N + 64 * U - 1) / (64 * U);
+  int64_t waves = std::max<int64_t>(1, (cus * 12 + B - 1) / B);
+  const int64_t slab_cap = std::max<int64_t>(1, ((int64_t)1 << 30) / (B * points * kTraceSlab * (int64_t)sizeof(double)));
+  waves = std::min(std::min(waves, tiles), slab_cap);
+  const int64_t tiles_per_wave = (tiles + waves - 1) / waves;
+  return {((tiles + tiles_per_wave - 1) / tiles_per_wave + 3) / 4 * 4, tiles_per_wave};
+}
+
 // `ap`: the apertures of a trace with losses (null: none, and the records stand for N particles each); `sc`: the
 // screens (null: none); `tj`: the chosen particles of a trace with trajectories (null: none -- the launches are then
 // the very ones they were before there was such a list).
@@ -2482,16 +2502,7 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   const int32_t S = lat->n_steps, P = S + 1;
   int rc;
   if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
-  // Waves per sample: enough of them to fill the GPU three waves per SIMD deep over the whole batch, whole workgroups
-  // of four, never more than there are tiles -- and few enough for the slabs (256 bytes per wave and point) to stay
-  // below 1 GiB.  The plan depends on the shapes alone: the same call adds the same numbers in the same order.
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  const int64_t tiles = (N + 64 * U - 1) / (64 * U);
-  int64_t waves = std::max<int64_t>(1, (cus * 12 + B - 1) / B);
-  const int64_t slab_cap = std::max<int64_t>(1, ((int64_t)1 << 30) / (B * P * kTraceSlab * (int64_t)sizeof(double)));
-  waves = std::min(std::min(waves, tiles), slab_cap);
-  const int64_t tiles_per_wave = (tiles + waves - 1) / waves;
-  waves = ((tiles + tiles_per_wave - 1) / tiles_per_wave + 3) / 4 * 4;
+  const auto [waves, tiles_per_wave] = trace_wave_plan(ctx, B, N, U, P);
   if (B * (waves / 4) > 0x7fffffffLL || B * P > 0x7fffffffLL || tiles_per_wave > 0x7fffffffLL)
     return fail(ctx, LYNX_ERR_INVALID, "beam trace: batch x points too large for one launch");
   if ((rc = ensure_scratch(ctx, &ctx->scratch_trace[0], &ctx->scratch_trace_bytes[0],
@@ -2662,11 +2673,7 @@ static int moments_by_loss_t(lynx_ctx* ctx, int64_t B, int64_t N, const void* d_
                              const int32_t* d_lost_at, double* d_records_out) {
   constexpr int U = sizeof(T) == 4 ? 4 : 2;
   const int32_t J = A + 1;
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  const int64_t tiles = (N + 64 * U - 1) / (64 * U);
-  int64_t waves = std::min(std::max<int64_t>(1, (cus * 12 + B - 1) / B), tiles);
-  const int64_t tiles_per_wave = (tiles + waves - 1) / waves;
-  waves = ((tiles + tiles_per_wave - 1) / tiles_per_wave + 3) / 4 * 4;
+  const auto [waves, tiles_per_wave] = trace_wave_plan(ctx, B, N, U, J);
   if (B * (waves / 4) > 0x7fffffffLL || B * J > 0x7fffffffLL || tiles_per_wave > 0x7fffffffLL)
     return fail(ctx, LYNX_ERR_INVALID, "moments by loss: batch too large for one launch");
   int rc;
@@ -2815,16 +2822,28 @@ static int trace_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ener
   return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
 }
 
-static int trace_backward_check(lynx_ctx* ctx, lynx_lattice* lat) {
-  if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program");
+// what every reverse entry point of the trace refuses about the lattice; `what`: the entry point's message prefix
+static int trace_backward_check(lynx_ctx* ctx, lynx_lattice* lat, const std::string& what) {
+  if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "empty program");
   if (lat->n_steps > kTraceBwdMaxSteps || lat->n_elems > kTraceBwdMaxSteps)
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients: more than 256 elements");
-  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
+    return fail(ctx, LYNX_ERR_INVALID, what + "more than 256 elements");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, what + "bad batch");
   if ((int64_t)lat->batch * (lat->n_steps + 1) > 0x7fffffffLL)
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace: batch x points too large for one launch");
+    return fail(ctx, LYNX_ERR_INVALID, what + "batch x points too large for one launch");
   return LYNX_OK;
 }
 
+// The moments of a fixed set of particles are closed under affine maps only: behind a cavity's kick they are not a
+// function of the moments in front of it.
+static int trace_backward_no_cavity(lynx_ctx* ctx, lynx_lattice* lat, const std::string& what) {
+  for (int32_t s = 0; s < lat->n_steps; ++s)
+    if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
+      return fail(ctx, LYNX_ERR_INVALID,
+                  what + "step " + std::to_string(s) + " is a cavity step (the particles' moments are not closed under its kick)");
+  return LYNX_OK;
+}
+
+// (`ctx->wrote` ignores null: the entry points without gradients of the incoming moments pass none)
 static void trace_backward_wrote(lynx_ctx* ctx, lynx_lattice* lat, void* d_grad_params, void* d_grad_energy_in,
                                  void* d_grad_mu_in, void* d_grad_cov_in) {
   const size_t es = dtype_size(lat->dtype);
@@ -2843,10 +2862,7 @@ int lynx_track_moments_along_backward(lynx_ctx* ctx, lynx_lattice* lat, const vo
   if (!lat || !d_energy_in || !d_mu_trace || !d_cov_trace || !d_mu_bar || !d_cov_bar || !d_grad_params ||
       !d_grad_energy_in || !d_grad_mu_in || !d_grad_cov_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
-  {
-    const int rc = trace_backward_check(ctx, lat);
-    if (rc) return rc;
-  }
+  if (const int rc = trace_backward_check(ctx, lat, "beam trace gradients: ")) return rc;
   HIP_TRY(ctx, use_device(ctx));
   trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
   return lat->dtype == LYNX_F64
@@ -2856,24 +2872,40 @@ int lynx_track_moments_along_backward(lynx_ctx* ctx, lynx_lattice* lat, const vo
                                        d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
 }
 
+// A ParticleBeam's states and cotangents of the sweep in scratch_grad[0]: mu [7] | cov [49] | mu_bar [7] | cov_bar [49] per
+// (sample, point), block by block, in the float64 of the records (k_trace_records_to_states), and `behind` more scalars
+// behind them for the caller.  Null records: no moment sweep -- no blocks, no launch, `behind` starts the scratch.
+struct TraceSweepStates {
+  double *mu, *cov, *mu_bar, *cov_bar, *behind;
+};
+static int trace_sweep_states(lynx_ctx* ctx, lynx_lattice* lat, const double* d_trace_fwd, const double* d_grad_trace,
+                              size_t behind, TraceSweepStates* st) {
+  const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
+  const size_t state_scalars = d_trace_fwd ? (size_t)points * 112 : 0;
+  int rc;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0],
+                           std::max<size_t>(state_scalars + behind, 1) * sizeof(double))))
+    return rc;
+  st->mu = (double*)ctx->scratch_grad[0];
+  st->cov = st->mu + points * 7;
+  st->mu_bar = st->cov + points * 49;
+  st->cov_bar = st->mu_bar + points * 7;
+  st->behind = st->mu + state_scalars;
+  if (!d_trace_fwd) return LYNX_OK;
+  hipLaunchKernelGGL(k_trace_records_to_states, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, d_grad_trace,
+                     st->mu, st->cov, st->mu_bar, st->cov_bar);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
 template <typename T>
 static int particles_along_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const double* d_trace_fwd,
                                       const double* d_grad_trace, const void* d_energy_bar, void* d_grad_params,
                                       void* d_grad_energy_in, void* d_grad_mean_in, void* d_grad_cov_in) {
-  const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
-  int rc;
-  // states and cotangents of the sweep: mu [7] | cov [49] | mu_bar [7] | cov_bar [49] per (sample, point), block by block,
-  // in the float64 of the records
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (size_t)points * 112 * sizeof(double)))) return rc;
-  double* mu = (double*)ctx->scratch_grad[0];
-  double* cov = mu + points * 7;
-  double* mu_bar = cov + points * 49;
-  double* cov_bar = mu_bar + points * 7;
-  hipLaunchKernelGGL(k_trace_records_to_states, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, d_grad_trace,
-                     mu, cov, mu_bar, cov_bar);
-  HIP_TRY(ctx, hipGetLastError());
-  return trace_backward_t<T, double>(ctx, lat, d_energy_in, mu, cov, mu_bar, cov_bar, d_energy_bar, d_grad_params, d_grad_energy_in,
-                             d_grad_mean_in, d_grad_cov_in);
+  TraceSweepStates st;
+  if (const int rc = trace_sweep_states(ctx, lat, d_trace_fwd, d_grad_trace, 0, &st)) return rc;
+  return trace_backward_t<T, double>(ctx, lat, d_energy_in, st.mu, st.cov, st.mu_bar, st.cov_bar, d_energy_bar, d_grad_params,
+                                     d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
 }
 
 int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
@@ -2886,17 +2918,8 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
       !d_grad_cov_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
-  {
-    const int rc = trace_backward_check(ctx, lat);
-    if (rc) return rc;
-  }
-  // the moments of the particles are closed under affine maps only: behind a cavity's kick they are not a function of
-  // the moments in front of it
-  for (int32_t s = 0; s < lat->n_steps; ++s)
-    if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
-      return fail(ctx, LYNX_ERR_INVALID,
-                  "beam trace gradients of a ParticleBeam: step " + std::to_string(s) +
-                      " is a cavity step (the particles' moments are not closed under its kick)");
+  if (const int rc = trace_backward_check(ctx, lat, "beam trace gradients: ")) return rc;
+  if (const int rc = trace_backward_no_cavity(ctx, lat, "beam trace gradients of a ParticleBeam: ")) return rc;
   HIP_TRY(ctx, use_device(ctx));
   trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
   return lat->dtype == LYNX_F64
@@ -2937,23 +2960,17 @@ int lynx_track_particles_along_backward_losses(lynx_ctx* ctx, lynx_lattice* lat,
                                                void* d_grad_params, void* d_grad_energy_in) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  const auto refuse = [&](const std::string& what) {
-    return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients with losses: " + what);
-  };
+  const std::string prefix = "beam trace gradients with losses: ";
+  const auto refuse = [&](const std::string& what) { return fail(ctx, LYNX_ERR_INVALID, prefix + what); };
   if (!lat || !d_energy_in || !d_trace_fwd || !d_grad_trace || !apertures || !d_set_records || !d_grad_params || !d_grad_energy_in)
     return refuse("null argument");
   if (n_particles <= 0) return refuse("n_particles must be > 0");
-  if (lat->n_steps <= 0) return refuse("empty program");
-  if (lat->n_steps > kTraceBwdMaxSteps || lat->n_elems > kTraceBwdMaxSteps) return refuse("more than 256 elements");
-  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return refuse("bad batch");
+  if (const int rc = trace_backward_check(ctx, lat, prefix)) return rc;
   if (n_apertures < 1 || n_apertures > kTraceMaxLossApertures)
     return refuse("n_apertures = " + std::to_string(n_apertures) + ", not 1 .. " + std::to_string(kTraceMaxLossApertures));
   if ((int64_t)lat->batch * (lat->n_steps + 1) * (n_apertures + 1) > 0x7fffffffLL)
     return refuse("batch x points x sets too large for one launch");
-  // the moments of a fixed set of particles are closed under affine maps only
-  for (int32_t s = 0; s < lat->n_steps; ++s)
-    if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
-      return refuse("step " + std::to_string(s) + " is a cavity step (the particles' moments are not closed under its kick)");
+  if (const int rc = trace_backward_no_cavity(ctx, lat, prefix)) return rc;
   TraceLossSets sets{};
   sets.sets = n_apertures + 1;
   for (int32_t k = 0; k < n_apertures; ++k) {
@@ -2967,9 +2984,7 @@ int lynx_track_particles_along_backward_losses(lynx_ctx* ctx, lynx_lattice* lat,
   }
   sets.last[n_apertures] = lat->n_steps;
   HIP_TRY(ctx, use_device(ctx));
-  const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
-  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
   return lat->dtype == LYNX_F64
              ? particles_along_backward_losses_t<double>(ctx, lat, d_energy_in, d_grad_trace, d_energy_bar, sets, d_set_records,
                                                          d_grad_params, d_grad_energy_in)
@@ -2987,27 +3002,15 @@ static int particles_along_backward_trajectories_t(lynx_ctx* ctx, lynx_lattice* 
                                                    void* d_grad_cov_in, int64_t n_chosen, const void* d_trajectories,
                                                    const double* d_trajectories_bar, void* d_grad_chosen_in) {
   const int64_t B = lat->batch, S = lat->n_steps;
-  const int64_t points = B * (S + 1);
   const bool moments = d_trace_fwd != nullptr;
   const bool tiled = n_chosen > 64 * kChosenBwdSlots;
-  const size_t state_scalars = moments ? (size_t)points * 112 : 0;
-  const size_t partial_scalars = tiled ? (size_t)B * S * kGradStride : 0;
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0],
-                           std::max<size_t>(state_scalars + partial_scalars, 1) * sizeof(double))))
-    return rc;
-  double* mu = (double*)ctx->scratch_grad[0];
-  double* cov = mu + points * 7;
-  double* mu_bar = cov + points * 49;
-  double* cov_bar = mu_bar + points * 7;
-  double* partial = tiled ? (double*)ctx->scratch_grad[0] + state_scalars : nullptr;
-  if (moments) {
-    hipLaunchKernelGGL(k_trace_records_to_states, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, d_grad_trace,
-                       mu, cov, mu_bar, cov_bar);
-    HIP_TRY(ctx, hipGetLastError());
-  }
+  TraceSweepStates st;
+  if ((rc = trace_sweep_states(ctx, lat, d_trace_fwd, d_grad_trace, tiled ? (size_t)B * S * kGradStride : 0, &st))) return rc;
+  double* partial = tiled ? st.behind : nullptr;
   if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
-  if (moments && (rc = trace_backward_moments<T, double>(ctx, lat, mu, cov, mu_bar, cov_bar, d_grad_mean_in, d_grad_cov_in)))
+  if (moments &&
+      (rc = trace_backward_moments<T, double>(ctx, lat, st.mu, st.cov, st.mu_bar, st.cov_bar, d_grad_mean_in, d_grad_cov_in)))
     return rc;
   hipLaunchKernelGGL(k_trace_trajectories_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, (int)S, n_chosen,
                      (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)d_trajectories, d_trajectories_bar,
@@ -3033,27 +3036,13 @@ int lynx_track_particles_along_backward_trajectories(lynx_ctx* ctx, lynx_lattice
                 what + "d_trace_fwd, d_grad_trace, d_grad_mean_in and d_grad_cov_in are given together or not at all");
   if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "n_particles must be > 0");
   if (n_chosen <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "n_chosen must be > 0");
-  if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "empty program");
-  if (lat->n_steps > kTraceBwdMaxSteps || lat->n_elems > kTraceBwdMaxSteps)
-    return fail(ctx, LYNX_ERR_INVALID, what + "more than 256 elements");
-  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, what + "bad batch");
-  if ((int64_t)lat->batch * (lat->n_steps + 1) > 0x7fffffffLL)
-    return fail(ctx, LYNX_ERR_INVALID, what + "batch x points too large for one launch");
-  if (given)  // (a single trajectory is differentiable through the kick; the moments are not closed under it)
-    for (int32_t s = 0; s < lat->n_steps; ++s)
-      if (lat->h_steps[s].kind == LYNX_STEP_CAVITY)
-        return fail(ctx, LYNX_ERR_INVALID,
-                    "beam trace gradients of a ParticleBeam: step " + std::to_string(s) +
-                        " is a cavity step (the particles' moments are not closed under its kick)");
+  if (const int rc = trace_backward_check(ctx, lat, what)) return rc;
+  // (a single trajectory is differentiable through the kick; a moment cotangent does not pass it)
+  if (given)
+    if (const int rc = trace_backward_no_cavity(ctx, lat, what)) return rc;
   HIP_TRY(ctx, use_device(ctx));
-  const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
-  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
-  if (given) {
-    ctx->wrote(d_grad_mean_in, (size_t)lat->batch * 7 * es);
-    ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
-  }
-  ctx->wrote(d_grad_chosen_in, (size_t)lat->batch * n_chosen * 7 * es);
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+  ctx->wrote(d_grad_chosen_in, (size_t)lat->batch * n_chosen * 7 * dtype_size(lat->dtype));
   return lat->dtype == LYNX_F64
              ? particles_along_backward_trajectories_t<double>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar,
                                                                d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,

@@ -768,16 +768,17 @@ __global__ __launch_bounds__(64) void k_trace_trajectories(TraceTrajectories t, 
 
 // ---------------------------------------------------------------------------------------
 // ParameterBeam: mu_k = M_k mu_{k-1}, cov_k = M_k cov_{k-1} M_k^T (element.py:71-82), the cavity branch of
-// cavity.py:134-140, 202-218 -- the operations of k_track_moments / k_apply_moments_lanes in the same order, every
-// intermediate written: mu [B][P][7], cov [B][P][7][7].  (The energies come from k_trace_reference.)
+// cavity.py:134-140, 202-218 -- the step functions of k_track_moments / k_apply_moments_lanes (moment_step_wave,
+// moment_step_lanes in lynx_device.hpp), every intermediate written: mu [B][P][7], cov [B][P][7][7].  (The energies
+// come from k_trace_reference.)
 //
-// k_trace_moments: one wave per sample, 49 lanes busy; the table is read from memory.
+// k_trace_moments: one wave per sample, 49 lanes busy (moment_step_wave); the table is read from memory.
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(64) void k_trace_moments(LatticeDev lat, const T* __restrict__ steps,
                                                       const T* __restrict__ mu_in, const T* __restrict__ cov_in,
                                                       T* __restrict__ mu_trace, T* __restrict__ cov_trace) {
-  __shared__ T s_mu[8], s_cov[49], s_x[49], s_in[10];
+  __shared__ T s_mu[8], s_cov[49], s_x[49];
   const int64_t b = blockIdx.x;
   const int lane = threadIdx.x, S = lat.n_steps, P = S + 1;
   if (lane < 7) s_mu[lane] = mu_in[b * 7 + lane];
@@ -792,47 +793,11 @@ __global__ __launch_bounds__(64) void k_trace_moments(LatticeDev lat, const T* _
     const T* M = steps + (b * S + s) * LYNX_STEP_STRIDE;
     const int desc = (int)M[LYNX_FLAGS_OFFSET];
     const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
-    if (lane < 7) s_in[lane] = s_mu[lane];
-    if (lane == 7) s_in[7] = s_cov[4 * 7 + 4];
-    if (lane == 8) s_in[8] = s_cov[4 * 7 + 5];
-    if (lane == 9) s_in[9] = s_cov[5 * 7 + 5];
-    T mu_new = T(0);
-    if (lane < 7) {
-      mu_new = M[lane * 7 + 0] * s_mu[0];
-#pragma unroll
-      for (int k = 1; k < 7; ++k) mu_new = t_fma(M[lane * 7 + k], s_mu[k], mu_new);
-    }
-    T x = s_cov[i * 7 + 0] * M[j * 7 + 0];  // X = cov . T^T
-#pragma unroll
-    for (int k = 1; k < 7; ++k) x = t_fma(s_cov[i * 7 + k], M[j * 7 + k], x);
-    __syncthreads();
-    if (lane < 49) s_x[lane] = x;
-    if (lane < 7) s_mu[lane] = mu_new;
-    __syncthreads();
-    T c = M[i * 7 + 0] * s_x[0 * 7 + j];  // cov' = T . X
-#pragma unroll
-    for (int k = 1; k < 7; ++k) c = t_fma(M[i * 7 + k], s_x[k * 7 + j], c);
-    __syncthreads();
-    if (lane < 49) s_cov[lane] = c;
-    __syncthreads();
-    if (kick && lane == 0) {
-      const T* coef = M + LYNX_COEF_OFFSET;
-      T s_o = s_mu[4], d_o;
-      device_cavity_kick<T>(coef, s_in[4], s_in[5], s_o, d_o);  // cavity.py:134-140, 202-206
-      s_mu[4] = s_o;
-      s_mu[5] = d_o;
-      const T c44 = s_in[7], c45 = s_in[8], c55 = s_in[9];
-      s_cov[5 * 7 + 5] = c55;  // cavity.py:140
-      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
-      s_cov[4 * 7 + 4] = v;
-      s_cov[4 * 7 + 5] = v;
-      s_cov[5 * 7 + 4] = v;
-    }
-    __syncthreads();
+    moment_step_wave<T>(M, s_mu, s_cov, s_x, lane, i, j, kick);
   }
 }
 
-// k_trace_moments_lanes: large float32 batches, lanes = samples (the form of k_apply_moments_lanes: a wave stages the
+// k_trace_moments_lanes: large float32 batches, lanes = samples (moment_step_lanes: a wave stages the
 // 64 table rows of a step in LDS with coalesced loads, every lane propagates its own sample's moments in registers).
 template <typename T>
 __global__ __launch_bounds__(64) void k_trace_moments_lanes(LatticeDev lat, const T* __restrict__ steps,
@@ -869,59 +834,7 @@ __global__ __launch_bounds__(64) void k_trace_moments_lanes(LatticeDev lat, cons
     }
     wave_fence();
     const T* M = rows + lane * 68;
-    const int desc = (int)M[LYNX_FLAGS_OFFSET];
-    const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
-    const T s_in = mu[4], d_in = mu[5], c44 = C[4 * 7 + 4], c45 = C[4 * 7 + 5], c55 = C[5 * 7 + 5];
-    {
-      T out[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        T acc = M[i * 7] * mu[0];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], mu[k], acc);
-        out[i] = acc;
-      }
-#pragma unroll
-      for (int i = 0; i < 7; ++i) mu[i] = out[i];
-    }
-#pragma unroll
-    for (int i = 0; i < 7; ++i) {  // X = cov . T^T, row i of X from row i of cov
-      T out[7];
-#pragma unroll
-      for (int j = 0; j < 7; ++j) {
-        T acc = C[i * 7] * M[j * 7];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) acc = t_fma(C[i * 7 + k], M[j * 7 + k], acc);
-        out[j] = acc;
-      }
-#pragma unroll
-      for (int j = 0; j < 7; ++j) C[i * 7 + j] = out[j];
-    }
-#pragma unroll
-    for (int j = 0; j < 7; ++j) {  // cov' = T . X, column j of cov' from column j of X
-      T out[7];
-#pragma unroll
-      for (int i = 0; i < 7; ++i) {
-        T acc = M[i * 7] * C[j];
-#pragma unroll
-        for (int k = 1; k < 7; ++k) acc = t_fma(M[i * 7 + k], C[k * 7 + j], acc);
-        out[i] = acc;
-      }
-#pragma unroll
-      for (int i = 0; i < 7; ++i) C[i * 7 + j] = out[i];
-    }
-    if (kick) {
-      const T* coef = M + LYNX_COEF_OFFSET;
-      T s_o = mu[4], d_o;
-      device_cavity_kick<T>(coef, s_in, d_in, s_o, d_o);  // cavity.py:134-140, 202-206
-      mu[4] = s_o;
-      mu[5] = d_o;
-      C[5 * 7 + 5] = c55;  // cavity.py:140
-      const T v = coef[LYNX_C_T566] * (c55 * c55) + coef[LYNX_C_T556] * c45 * c55 + coef[LYNX_C_T555] * (c44 * c44);  // cavity.py:207-218
-      C[4 * 7 + 4] = v;
-      C[4 * 7 + 5] = v;
-      C[5 * 7 + 4] = v;
-    }
+    moment_step_lanes<T>(M, mu, C);
   }
 }
 

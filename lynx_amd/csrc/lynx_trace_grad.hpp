@@ -10,12 +10,14 @@
 //   m = 0, G = 0
 //   for k = S .. 1:                      (point k lies behind step k - 1)
 //     m += mu_bar[k], G += cov_bar[k]
-//     (active cavity: the direct terms and coefficient cotangents of k_moments_bwd)
+//     (active cavity: the direct terms and coefficient cotangents, sweep_kick)
 //     T_bar[k-1] = m (x) mu[k-1] + (G M) C[k-1]^T + (G^T M) C[k-1]
 //     m <- M^T m,  G <- M^T G M
 //   grad_mu_in = m + mu_bar[0],  grad_cov_in = G + cov_bar[0]
 //
-// with mu[k], C[k] read from the forward trace.  T_bar leaves in the layout k_build_bwd consumes.
+// with mu[k], C[k] read from the forward trace.  T_bar leaves in the layout k_build_bwd consumes.  One step of the loop
+// is sweep_kick and sweep_products of lynx_grad.hpp, the functions k_moments_bwd runs in the lattice's dtype; the
+// recursion itself, where a kernel here needs it, is moment_step_wave of lynx_device.hpp.
 //
 // The sweep's own arithmetic is float64 for every lattice dtype.  The cotangent of a Twiss value carries
 // -(beta / 2 eps) C^-1, and (G M) C^T then forms C^-1 C = 1 as gamma beta - alpha^2: a sum that cancels (1 + alpha^2)-fold
@@ -26,13 +28,14 @@
 //
 //   k_trace_records_to_states   ParticleBeam: moment records and record cotangents [B][P][36] float64 -> mu, C, mu_bar,
 //                               cov_bar of the sweep
-//   k_trace_moments_bwd         the sweep, one wave per sample
+//   k_trace_moments_bwd         the sweep, one wave per sample (sweep_kick, sweep_products in float64)
 //   k_trace_energy_bwd          the cotangents of the beam energy at every point -> incoming energy and the gaining
 //                               cavities' voltage and phase (adds into what k_build_bwd wrote)
 //   k_trace_trajectories_bwd    the reverse sweep of CHOSEN particles' trajectories (lynx_track_particles_along_backward_
 //                               trajectories): a cotangent on single coordinates at every point, through the kick as well
 //   k_trace_moments_bwd_sets    a trace with losses (lynx_track_particles_along_backward_losses): per nested survivor
-//                               set the recursion from the set's incoming moments and the sweep over its own points;
+//                               set the recursion from the set's incoming moments (moment_step_wave) and the sweep over
+//                               its own points (sweep_products), both in float64;
 //                               k_trace_sum_sets adds the sets' T_bar in set order
 #pragma once
 
@@ -75,8 +78,8 @@ __global__ __launch_bounds__(64) void k_trace_records_to_states(const double* __
 }
 
 // ---------------------------------------------------------------------------------------
-// k_trace_moments_bwd: grid = B, one wave per sample, 49 lanes busy (lane = entry i * 7 + j), the formulas of
-// k_moments_bwd's reverse sweep.  Nothing is recomputed and nothing parked: the state that ENTERS step s is point s of
+// k_trace_moments_bwd: grid = B, one wave per sample, 49 lanes busy (lane = entry i * 7 + j), every step by sweep_kick
+// and sweep_products.  Nothing is recomputed and nothing parked: the state that ENTERS step s is point s of
 // the forward trace.  The cotangent of point s + 1 is added BEFORE step s is reversed, so a cotangent on the entries an
 // active cavity overwrites (mu[5], cov[4,4], cov[4,5], cov[5,4], cov[5,5]) goes through the kick's formulas, not
 // through M.  What step s - 1 needs from memory (state, table row, cotangents: independent of the sweep) is fetched
@@ -134,54 +137,10 @@ __global__ __launch_bounds__(64) void k_trace_moments_bwd(int S, const T* __rest
     __syncthreads();
     const int desc = (int)s_m[LYNX_FLAGS_OFFSET];
     const bool kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
-    if (kick && lane == 0) {
-      const A* cf = s_m + LYNX_COEF_OFFSET;
-      const A z4 = s_mu[4], z5 = s_mu[5], c44 = s_c[32], c45 = s_c[33], c55 = s_c[40];
-      const A m4 = s_mb[4], m5 = s_mb[5];
-      const A vb = s_g[32] + s_g[33] + s_g[39];
-      A sphi, cphi, kc[8], d4, d5;
-      phase_sincos(cf[LYNX_C_PHI], sphi, cphi);
-      kick_cotangents<A, A>(cf, sphi, cphi, z4, z5, m4, m5, kc, d4, d5);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s_k[q] = kc[q];
-      s_k[LYNX_C_T566] += vb * (c55 * c55);
-      s_k[LYNX_C_T556] += vb * (c45 * c55);
-      s_k[LYNX_C_T555] += vb * (c44 * c44);
-      s_k[8] = d4;  // d/d mu_in[4]
-      s_k[9] = d5;  // d/d mu_in[5]
-      s_k[10] = vb * A(2) * cf[LYNX_C_T555] * c44;                                                   // d/d c44
-      s_k[11] = vb * cf[LYNX_C_T556] * c55;                                                          // d/d c45
-      s_k[12] = s_g[40] + vb * (A(2) * cf[LYNX_C_T566] * c55 + cf[LYNX_C_T556] * c45);               // d/d c55
-      s_mb[5] = A(0);  // these outputs were overwritten by the kick
-      s_g[32] = A(0);
-      s_g[33] = A(0);
-      s_g[39] = A(0);
-      s_g[40] = A(0);
-    }
+    if (kick && lane == 0) sweep_kick<A>(s_m, s_mu, s_c, s_g, s_mb, s_k);
     __syncthreads();
-    // P = G M, Q = G^T M
-    A pv = s_g[i * 7] * s_m[j], qv = s_g[i] * s_m[j];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) {
-      pv = t_fma(s_g[i * 7 + k], s_m[k * 7 + j], pv);
-      qv = t_fma(s_g[k * 7 + i], s_m[k * 7 + j], qv);
-    }
-    if (lane < 49) {
-      s_x[lane] = pv;
-      s_y[lane] = qv;
-    }
-    __syncthreads();
-    A tb = s_mb[i] * s_mu[j], cb = A(0), mbn = A(0);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      tb = t_fma(s_x[i * 7 + k], s_c[j * 7 + k], tb);
-      tb = t_fma(s_y[i * 7 + k], s_c[k * 7 + j], tb);
-      cb = t_fma(s_m[k * 7 + i], s_x[k * 7 + j], cb);
-    }
-    if (lane < 7) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) mbn = t_fma(s_m[k * 7 + lane], s_mb[k], mbn);
-    }
+    A tb, cb, mbn;
+    sweep_products<A>(s_m, s_mu, s_c, s_g, s_mb, s_x, s_y, lane, i, j, tb, cb, mbn);
     T* tb_out = tbar + (b * S + s) * (int64_t)kGradStride;
     if (lane < 49) tb_out[lane] = tb;
     else if (lane < 57) tb_out[lane] = s_k[lane - 49];
@@ -424,10 +383,10 @@ __global__ __launch_bounds__(64) void k_trace_trajectories_bwd(int S, int64_t K,
 //
 // k_trace_moments_bwd_sets: grid = B * (A + 1), one wave per (sample, set), 49 lanes busy.
 //   states      mean and C of set j's incoming particles (lynx_moments_by_loss) taken through the step table from point 0
-//               to the set's last live point -- k_trace_moments' recursion in float64 whatever the lattice's dtype (the
+//               to the set's last live point -- moment_step_wave in float64 whatever the lattice's dtype (the
 //               head of this file) -- every state that ENTERS a step parked in `states` [B][A + 1][S][56];
 //   cotangents  read from the record cotangents under k_trace_records_to_states' conventions, zero outside the live points;
-//   sweep       k_trace_moments_bwd's, from the last live point down to step 0 (no cavity: refused by the host), T_bar
+//   sweep       sweep_products from the last live point down to step 0 (no cavity: refused by the host), T_bar
 //               in float64 into the set's own slab `tbar_sets` [A + 1][B][S][64]; rows behind the last live point are 0.
 // A set nobody is in (count 0, NaN moments) writes zeros.  k_trace_sum_sets then adds the sets' slabs in set order and
 // rounds once into the T_bar k_build_bwd consumes.  One lane owns every cell, fixed order: the same call, the same bits.
@@ -468,7 +427,7 @@ __global__ __launch_bounds__(64) void k_trace_moments_bwd_sets(int S, int64_t B,
   const int tri = inner ? 7 + r * 6 - (r * (r - 1)) / 2 + (q - r) : 7;
   const A weight = !inner ? 0.0 : (i == j ? 1.0 : 0.5);
 
-  // forward: k_trace_moments' recursion, the state entering step s parked at st[s]
+  // forward: the state entering step s parked at st[s]
   if (lane < 7) s_mu[lane] = lane < 6 ? rec[lane] : 1.0;
   if (lane < 49) s_c[lane] = inner ? rec[tri] : 0.0;
   __syncthreads();
@@ -477,29 +436,12 @@ __global__ __launch_bounds__(64) void k_trace_moments_bwd_sets(int S, int64_t B,
     if (lane < 49) st[(int64_t)s * kSetState + 7 + lane] = s_c[lane];
     s_m[lane] = (A)g_steps[(int64_t)s * LYNX_STEP_STRIDE + lane];
     __syncthreads();
-    A mu_new = 0.0;
-    if (lane < 7) {
-      mu_new = s_m[lane * 7] * s_mu[0];
-#pragma unroll
-      for (int k = 1; k < 7; ++k) mu_new = fma(s_m[lane * 7 + k], s_mu[k], mu_new);
-    }
-    A x = s_c[i * 7] * s_m[j * 7];  // X = C M^T
-#pragma unroll
-    for (int k = 1; k < 7; ++k) x = fma(s_c[i * 7 + k], s_m[j * 7 + k], x);
-    __syncthreads();
-    if (lane < 49) s_x[lane] = x;
-    if (lane < 7) s_mu[lane] = mu_new;
-    __syncthreads();
-    A c = s_m[i * 7] * s_x[j];  // C' = M X
-#pragma unroll
-    for (int k = 1; k < 7; ++k) c = fma(s_m[i * 7 + k], s_x[k * 7 + j], c);
-    if (lane < 49) s_c[lane] = c;
-    __syncthreads();
+    moment_step_wave<A>(s_m, s_mu, s_c, s_x, lane, i, j, false);  // (no cavity: refused by the host)
   }
   __threadfence_block();
   __syncthreads();
 
-  // reverse: k_trace_moments_bwd's sweep; the cotangent of point p counts for lo <= p <= L (point 0's reaches no parameter)
+  // reverse, with k_trace_moments_bwd's prefetching: the cotangent of point p counts for lo <= p <= L (point 0's reaches no parameter)
   if (lane < 7) s_mb[lane] = A(0);
   if (lane < 49) s_g[lane] = A(0);
   A n_mu = A(0), n_c = A(0), n_m = A(0), n_mb = A(0), n_cb = A(0);
@@ -530,29 +472,8 @@ __global__ __launch_bounds__(64) void k_trace_moments_bwd_sets(int S, int64_t B,
       n_m = (A)g_steps[(int64_t)(s - 1) * LYNX_STEP_STRIDE + lane];
     }
     __syncthreads();
-    // P = G M, Q = G^T M
-    A pv = s_g[i * 7] * s_m[j], qv = s_g[i] * s_m[j];
-#pragma unroll
-    for (int k = 1; k < 7; ++k) {
-      pv = t_fma(s_g[i * 7 + k], s_m[k * 7 + j], pv);
-      qv = t_fma(s_g[k * 7 + i], s_m[k * 7 + j], qv);
-    }
-    if (lane < 49) {
-      s_x[lane] = pv;
-      s_y[lane] = qv;
-    }
-    __syncthreads();
-    A tb = s_mb[i] * s_mu[j], cb = A(0), mbn = A(0);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) {
-      tb = t_fma(s_x[i * 7 + k], s_c[j * 7 + k], tb);
-      tb = t_fma(s_y[i * 7 + k], s_c[k * 7 + j], tb);
-      cb = t_fma(s_m[k * 7 + i], s_x[k * 7 + j], cb);
-    }
-    if (lane < 7) {
-#pragma unroll
-      for (int k = 0; k < 7; ++k) mbn = t_fma(s_m[k * 7 + lane], s_mb[k], mbn);
-    }
+    A tb, cb, mbn;
+    sweep_products<A>(s_m, s_mu, s_c, s_g, s_mb, s_x, s_y, lane, i, j, tb, cb, mbn);
     out[(int64_t)s * kGradStride + lane] = lane < 49 ? tb : A(0);
     __syncthreads();
     if (lane < 49) s_g[lane] = cb;

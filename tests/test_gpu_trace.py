@@ -424,6 +424,50 @@ def test_parameter_beam_trace_through_cavities(lx, dtype):
     assert trace.sigma_x.shape == (B, len(beams)) and trace.beta_y.shape == (B, len(beams))
 
 
+@pytest.mark.parametrize("B", [1, 64, 65])
+def test_parameter_beam_trace_through_cavities_lanes_form(lx, B, monkeypatch):
+    """
+    The lattice and beam of `test_parameter_beam_trace_through_cavities`, float32, lanes = samples at any batch
+    (LYNX_LANES_BUILD_MIN_BATCH=1: k_trace_moments_lanes, cavity branch included): one live lane, a full wave, a second
+    wave of one live lane and 63 clamped ones.  Every point against the oracle chain, and the last point against
+    `Segment.track` under the same knob (k_apply_moments_lanes: the same step function, moment_step_lanes).  The two are
+    not the same bits, before the step function was shared or after: `track` composes [drift, quadrupole] and
+    [drift, corrector] into one table row each, the trace keeps a row per element.  On the commit before the shared
+    function, on an MI355X: mean 3.6e-12 / 1.5e-11 / 7.3e-12, covariance 5.2e-6 / 1.5e-5 / 6.7e-6 of sigma_i sigma_j at
+    batch 1 / 64 / 65 -- so the limits are those of `test_parameter_beam_lanes_path_agrees_with_the_workgroup_path`.
+    """
+    monkeypatch.setenv("LYNX_LANES_BUILD_MIN_BATCH", "1")
+    dtype = np.float32
+    rng = np.random.default_rng(9)
+    f = lambda v: np.full(B, v)  # noqa: E731
+    desc = [("drift", dict(length=f(0.6))), ("quadrupole", dict(length=f(0.2), k1=rng.uniform(-5, 5, B))),
+            ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, B), phase=rng.uniform(-10, 10, B),
+                            frequency=f(1.3e9))),
+            ("bpm", dict(is_active=True)),
+            ("drift", dict(length=f(0.4))), ("hcor", dict(length=f(0.1), angle=f(1e-4))),
+            ("cavity", dict(length=f(1.0377), voltage=rng.uniform(5e6, 2e7, B), phase=f(0.0), frequency=f(1.3e9))),
+            ("dipole", dict(length=f(0.5), angle=f(0.1)))]
+    elements, specs = make_lattice(desc, dtype, lx)
+    kw = dict(sigma_x=f(1e-4), sigma_xp=f(1e-5), sigma_y=f(1e-4), sigma_yp=f(1e-5), sigma_s=f(1e-5),
+              sigma_p=f(1e-3), mu_x=rng.normal(0, 1e-4, B), energy=f(6e6))
+    kw = {k: np.asarray(v, dtype=dtype) for k, v in kw.items()}
+    segment = lx.Segment(elements)
+    trace = segment.track_along(lx.ParameterBeam.from_parameters(**kw, dtype=dtype))
+    beams, _ = chain(specs, o.parameter_beam_from_parameters(dtype=dtype, **kw), dtype)
+    assert trace.num_points == len(beams) and trace.mu.shape == (B, len(beams), 6)
+    for k, ref in enumerate(beams):
+        assert_parameter_beam((trace._mu[..., k, :], trace._cov[..., k, :, :]), ref, 1e-4, f"point {k}")
+        assert rel_err(trace.energy[..., k], ref["energy"]) < 1e-6, k
+    out = segment.track(lx.ParameterBeam.from_parameters(**kw, dtype=dtype))
+    mu, cov = np.array(out._mu), np.array(out._cov)
+    last_mu, last_cov = np.asarray(trace._mu[..., -1, :]), np.asarray(trace._cov[..., -1, :, :])
+    sc = np.sqrt(np.abs(np.einsum("bii,bjj->bij", cov[..., :6, :6], cov[..., :6, :6]))) + 1e-300
+    d_mu, d_cov = rel_err(last_mu, mu), float(np.max(np.abs(last_cov[..., :6, :6] - cov[..., :6, :6]) / sc))
+    print(f"lanes trace, batch {B}: last point against Segment.track: equal bits {np.array_equal(last_mu, mu)} (mu) "
+          f"{np.array_equal(last_cov, cov)} (cov), distances {d_mu:.2e} (mu) {d_cov:.2e} (cov)")
+    assert d_mu < 1e-5 and d_cov < 1e-4
+
+
 @pytest.mark.parametrize("B", [3, 100_000])
 def test_parameter_beam_trace_on_the_ares_segment(lx, B):
     """Batch 3: one wave per sample; batch 100 000: lanes = samples."""
