@@ -417,8 +417,11 @@ int lynx_track_particles_along_backward_trajectories(lynx_ctx* ctx, lynx_lattice
  *                                   tests/test_differentiable.py:75-91 differentiates through those)
  *   d_grad_observations [B][n_observers][2] float64 or NULL: dL/d(reading) of the program's observer steps (active
  *                                   BPMs, bpm.py:48-58: the reading is the mean x, y of the beam that enters the BPM)
- * Limit of this version: n_steps <= 64 (every 4th per-particle state is parked in a
- * fixed-size private array during the forward sweep).                                       */
+ * Limits of this version: at most 64 units -- a unit is a step, or in float32 a [run, cavity]
+ * pair of steps (every 4th per-particle state is parked in a fixed-size private array during
+ * the forward sweep).  Beyond that the call returns LYNX_ERR_INVALID and launches nothing.
+ * (Float64 beyond 58 steps: the workgroup keeps its per-step sums at a stride of the 57
+ * entries in use instead of 64, so that 64 steps fit 160 KiB of LDS; the sums are the same.) */
 int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles,
                                   const void* d_energy_in, const void* d_p_in,
                                   const double* d_moments_fwd, const double* d_grad_moments,
@@ -431,7 +434,12 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
  * leaves).
  *   d_mu_bar [B][7], d_cov_bar [B][7][7]   dL/d(outgoing mu), dL/d(outgoing cov), entry by entry
  *   d_grad_params [B][E][8], d_grad_energy_in [B]   as for lynx_track_particles_backward
- *   d_grad_mu_in [B][7], d_grad_cov_in [B][7][7]    dL/d(incoming mu), dL/d(incoming cov)      */
+ *   d_grad_mu_in [B][7], d_grad_cov_in [B][7][7]    dL/d(incoming mu), dL/d(incoming cov)
+ * No limit on n_steps: k_build_bwd deals the steps of the program to its 256 threads in strided
+ * loops (several steps per thread beyond 256; it used to serve the first 256 steps only, and
+ * the step energies and the energy cotangent of a longer program came out wrong, without an
+ * error).  The build of a long program takes shorter chunks of elements so that its step table
+ * fits the LDS next to them.  At most 4095 elements per program.                             */
 int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in,
                                 const void* d_mu_in, const void* d_cov_in, const void* d_mu_bar,
                                 const void* d_cov_bar, void* d_grad_params, void* d_grad_energy_in,

@@ -328,6 +328,13 @@ template <typename T, int W> struct ExGeom {
   static constexpr int kPieces = kRow / (8 * kVW);         // accesses per lane and row
 };
 
+// Entries per step of k_track_bwd's per-wave sums in LDS: the partial sums' stride, 64 -- or, where a float64 workgroup's
+// 4 . 21 . 66 exchange entries and 4 . S . 64 sums no longer fit 160 KiB (from 59 steps on), the 57 entries in use (49 of
+// T_bar, 8 of coef_bar): 64 steps then take 161 088 bytes.  Same sums in the same order either way.
+template <typename T> __host__ __device__ inline int bwd_acc_stride(int S) {
+  return (sizeof(T) == 8 && S > 58) ? 57 : 64;
+}
+
 // what one workgroup of k_track_bwd does: chunk `work % a.chunks` of sample `work / a.chunks`
 template <typename T, typename Z>
 __device__ __forceinline__ void track_bwd_workgroup(
@@ -358,7 +365,8 @@ __device__ __forceinline__ void track_bwd_workgroup(
   constexpr int kExRows = ExRows<W>::value;
   constexpr bool kCoefRows = kExRows == 21;
   T* s_ex = reinterpret_cast<T*>(smem_raw);                  // [4][kExRows][P]
-  T* s_acc = s_ex + 4 * kExRows * P;                         // [4][S][64]
+  T* s_acc = s_ex + 4 * kExRows * P;                         // [4][S][AS]
+  const int AS = bwd_acc_stride<T>(S);                       // (64, or float64 beyond 58 steps the 57 entries in use)
   Z stack[kBwdMaxGroups * 7];                                // private: state entering step g*K
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -367,9 +375,10 @@ __device__ __forceinline__ void track_bwd_workgroup(
   const int64_t N = a.n_particles;
   const T* g_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
   T* ex = s_ex + wave * (kExRows * P);
-  T* acc = s_acc + wave * (S * 64);
+  T* acc = s_acc + wave * (S * AS);
 
-  for (int s = 0; s < S; ++s) acc[s * 64 + lane] = T(0);
+  for (int s = 0; s < S; ++s)
+    if (lane < AS) acc[s * AS + lane] = T(0);
 
   const double* rec = moments_fwd + b * LYNX_MOMENT_STRIDE;
   const double* gm = grad_moments + b * LYNX_MOMENT_STRIDE;
@@ -540,12 +549,12 @@ __device__ __forceinline__ void track_bwd_workgroup(
           }
           if (kb < 7) {
             if (coef_lane) {
-              if (kick) acc[s * 64 + 49 + kb] += mine;
+              if (kick) acc[s * AS + 49 + kb] += mine;
             } else if (entry_lane) {
-              acc[(s - 1) * 64 + kb] += mine;      // run slot, row of s
+              acc[(s - 1) * AS + kb] += mine;      // run slot, row of s
             } else if (oi < 7) {
-              if (entry_rows && oi == 5) acc[(s - 1) * 64 + 7 + kb] += mine;  // run slot, row of delta
-              else acc[s * 64 + oi * 7 + kb] += mine;
+              if (entry_rows && oi == 5) acc[(s - 1) * AS + 7 + kb] += mine;  // run slot, row of delta
+              else acc[s * AS + oi * 7 + kb] += mine;
             }
           }
           if (kick) {
@@ -563,7 +572,7 @@ __device__ __forceinline__ void track_bwd_workgroup(
                 rest = (lane == c) ? total : rest;
               }
             }
-            if (lane >= (kCoefRows ? 7 : 0) && lane < 8) acc[s * 64 + 49 + lane] += rest;
+            if (lane >= (kCoefRows ? 7 : 0) && lane < 8) acc[s * AS + 49 + lane] += rest;
           }
         }
         wave_lds_sync();
@@ -621,7 +630,8 @@ __device__ __forceinline__ void track_bwd_workgroup(
   const int rows = a.out_chunks > 0 ? a.out_chunks : a.chunks;
   T* out = partials + (((int64_t)b * rows + chunk) * S) * kGradStride;
   for (int idx = tid; idx < S * 64; idx += kTrackThreads) {
-    out[idx] = ((s_acc[idx] + s_acc[S * 64 + idx]) + s_acc[2 * S * 64 + idx]) + s_acc[3 * S * 64 + idx];
+    const int entry = idx & 63, at = (idx >> 6) * AS + entry;  // (AS = 64: at = idx)
+    out[idx] = entry < AS ? ((s_acc[at] + s_acc[S * AS + at]) + s_acc[2 * S * AS + at]) + s_acc[3 * S * AS + at] : T(0);
   }
   if (a.out_chunks > a.chunks) {  // (one workgroup for the whole sample: the rows of the workgroups that are not there)
     for (int64_t idx = tid; idx < (int64_t)(rows - a.chunks) * S * kGradStride; idx += kTrackThreads)
@@ -894,18 +904,19 @@ __device__ __forceinline__ void build_bwd_sample(const LatticeDev& lat, const T*
   // with M_bar_e.  (The +s keeps neighbouring steps from sharing a slot.)
   T* g_pref = g_maps + (int64_t)E * 49;
 
-  // energies (same walk as the forward build).  The steps' energy gains are fetched by one thread per step --
+  // energies (same walk as the forward build).  The steps' energy gains are fetched by one thread per step (a lattice of
+  // more than 256 steps: several steps per thread, here and in part 4) --
   // lattice tables and parameters sit behind two dependent loads from memory, which the serial walk used to pay
   // step after step -- and the walk itself only adds them up.
-  if (tid < S) {
-    const lynx_step st = lat.steps[tid];
+  for (int s = tid; s < S; s += blockDim.x) {
+    const lynx_step st = lat.steps[s];
     T gain = T(0);
     if (st.kind == LYNX_STEP_CAVITY && (st.flags & LYNX_FLAG_CAV_GAIN)) {
       const lynx_elem el = lat.elems[st.first];
       const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
       gain = p[1] * t_cos(p[2] * T(LYNX_PI / 180.0));
     }
-    s_ebar[tid] = gain;  // parked here until the walk has used it
+    s_ebar[s] = gain;  // parked here until the walk has used it
   }
   __syncthreads();
   if (tid == 0) {
@@ -1087,11 +1098,11 @@ __device__ __forceinline__ void build_bwd_sample(const LatticeDev& lat, const T*
 
   // 4. energy cotangent: sum per step (one thread per step over its elements, in element order), the carries by a
   //    serial walk over the S sums, then back through the cavities' energy gains (one thread per step again)
-  if (tid < S) {
-    const lynx_step st = lat.steps[tid];
+  for (int s = tid; s < S; s += blockDim.x) {
+    const lynx_step st = lat.steps[s];
     T sum = T(0);
     for (int e = st.first; e < st.last; ++e) sum += s_econ[e];
-    s_ebar[tid] = sum;
+    s_ebar[s] = sum;
   }
   __syncthreads();
   if (tid == 0) {
@@ -1104,10 +1115,10 @@ __device__ __forceinline__ void build_bwd_sample(const LatticeDev& lat, const T*
     grad_energy[b] = carry;
   }
   __syncthreads();
-  if (tid < S) {
-    const lynx_step st = lat.steps[tid];
+  for (int s = tid; s < S; s += blockDim.x) {
+    const lynx_step st = lat.steps[s];
     if (st.kind == LYNX_STEP_CAVITY && (st.flags & LYNX_FLAG_CAV_GAIN)) {
-      const T carry = s_ebar[tid];
+      const T carry = s_ebar[s];
       const lynx_elem el = lat.elems[st.first];
       const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
       const T phi = p[2] * T(LYNX_PI / 180.0);

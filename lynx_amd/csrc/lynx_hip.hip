@@ -1329,8 +1329,12 @@ static int launch_build(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stream, co
   }
   int threads, chunk;
   build_shape<T>(ctx, lat, underneath, &threads, &chunk);
-  const size_t lds = build_scratch_bytes(chunk, sizeof(T)) +
-                     ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1) * sizeof(T);
+  const auto lds_at = [&](int c) {
+    return build_scratch_bytes(c, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1) * sizeof(T);
+  };
+  // (a program of many steps: its table takes most of the LDS, and shorter chunks -- more compose rounds -- leave it room)
+  while (lds_at(chunk) > (size_t)160 * 1024 && chunk > 8) chunk = (chunk + 1) / 2;
+  const size_t lds = lds_at(chunk);
   int rc;
   if (lat->prog_pool && ctx->knobs.inline_pool) {
     if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall) {
@@ -2034,6 +2038,12 @@ static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const v
     a.unit_slot[a.n_units++] = (unsigned char)s;
   }
   for (int u = a.n_units; u < kBwdGroup * kBwdMaxGroups; ++u) a.unit_slot[u] = a.unit_observer[u] = 0;
+  // k_track_bwd's exchange buffer and per-step sums (refused here, before anything is launched)
+  const size_t lds = ((size_t)4 * ExRows<W>::value * ExGeom<T, W>::kPitch + (size_t)4 * S * bwd_acc_stride<T>(S)) * sizeof(T);
+  if (lds > 160 * 1024)  // (the 64 units fit: 64 float64 steps at the narrow stride take 161088 bytes, 128 float32 steps 162752)
+    return fail(ctx, LYNX_ERR_INVALID,
+                "lynx_track_particles_backward: LDS budget exceeded: " + std::to_string(S) + " steps need " +
+                    std::to_string(lds) + " bytes of the 163840 per workgroup (split the lattice)");
   const size_t steps_bytes = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
   if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableBwd], &ctx->scratch_steps_bytes[lynx_ctx::kTableBwd], steps_bytes))) return rc;
   // float32 packed pairs: samples whose units all have class U take the structured reverse kernel (lynx_grad_units.hpp)
@@ -2098,8 +2108,6 @@ static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const v
   a.n_particles = N;
   a.chunks = (int32_t)chunks;
   a.tiles_per_wg = (int32_t)tpw;
-  const size_t lds = ((size_t)4 * ExRows<W>::value * Geo::kPitch + (size_t)4 * S * 64) * sizeof(T);
-  if (lds > 160 * 1024) return fail(ctx, LYNX_ERR_INVALID, "lynx_track_particles_backward: LDS budget exceeded");
   if ((rc = allow_lds(ctx, k_track_bwd<T, Z>, lds))) return rc;
   if ((int64_t)B * chunks > 0x7fffffffLL || (int64_t)B * S > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
   if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0],
@@ -2336,9 +2344,13 @@ static int launch_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
   const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
   const bool deep = lat->batch * 2 <= cus;
   const unsigned threads = lat->batch <= 4096 ? 256u : 64u;
-  const int chunk = build_chunk(lat->n_elems, deep ? 128 : 64);
-  const size_t lds = build_scratch_bytes(chunk, sizeof(T)) +
-                     ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1 + 8 + 49 + 49 + 16) * sizeof(T);
+  int chunk = build_chunk(lat->n_elems, deep ? 128 : 64);
+  const auto lds_at = [&](int c) {
+    return build_scratch_bytes(c, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1 + 8 + 49 + 49 + 16) * sizeof(T);
+  };
+  // (a program of many steps: its table takes most of the LDS, and shorter chunks -- more compose rounds -- leave it room)
+  while (lds_at(chunk) > (size_t)160 * 1024 && chunk > 8) chunk = (chunk + 1) / 2;
+  const size_t lds = lds_at(chunk);
   if (lat->prog_pool && ctx->knobs.inline_pool) {  // (no cavities: no flags to evaluate)
     if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall) {
       if ((rc = allow_lds(ctx, k_track_moments_inline<T, kInlinePoolSmall>, lds))) return rc;
