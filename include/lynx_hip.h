@@ -476,6 +476,34 @@ int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t 
                                const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
                                const void* d_misalignment, int64_t misalignment_stride, void* d_images);
 
+/* The adjoint of lynx_gaussian_images_along: cotangents of the images, reduced over all pixels of every screen of every
+ * sample to cotangents of mu and cov at the points the screens observe.  Arguments up to misalignment_stride exactly as for
+ * lynx_gaussian_images_along, and
+ *   d_images_bar         [B][sum of nx ny] dL/d(image), in that function's image layout (x flipped), lattice dtype
+ *   d_mu_bar             [B][n_points][7], read and written: at each screen's point, entries 0 and 2 are added to
+ *   d_cov_bar            [B][n_points][7][7], read and written: entries [0][0], [2][2], [0][2] and [2][0] are added to (the
+ *                        xy cotangent in two equal halves: their sum is the derivative by the covariance of x and y)
+ *   d_grad_misalignment  [B][n_screens][2] or NULL: dL/d(misalignment) per sample, the negative of the mu_bar entries
+ * -- what lynx_track_moments_along_backward takes as d_mu_bar, d_cov_bar on the same stream.  With mx = mu_x -
+ * misalignment[0], my = mu_y - misalignment[1], a, b, c = cov_xx, cov_xy, cov_yy, det = a c - b^2 and, per pixel, dx = xs[i]
+ * - mx, dy = ys[j] - my, I the image (formed anew from mu and cov by the forward kernel's expression; no image is read), W
+ * its cotangent, ux = (c dx - b dy) / det, uy = (a dy - b dx) / det:
+ *   S0, Sx, Sy, Sxx, Sxy, Syy = sum over the pixels of W I {1, ux, uy, ux^2, ux uy, uy^2}
+ *   mu_bar[0] += Sx, mu_bar[2] += Sy, cov_bar[0][0] += (Sxx - c/det S0) / 2, cov_bar[2][2] += (Syy - a/det S0) / 2,
+ *   cov_bar[0][2], cov_bar[2][0] += (Sxy + b/det S0) / 2.
+ * One pass over d_images_bar: a workgroup sums LYNX_IMAGE_GRAD_CELLS consecutive cells in float64 (both dtypes) and writes
+ * its six partial sums to a slab in the context's scratch; a second small kernel adds a sample's slab in a fixed order.  No
+ * atomics: the same call returns the same bits.  det <= 0 gives NaN, as it does in the image; an image that has
+ * underflowed to 0 gives 0.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "image gradients
+ * along the trace: ") for a null required argument, a batch beyond 65535, a bad stride, a screen outside the trace or
+ * without pixels, or one of 2^31 - 2048 pixels or more.                                                              */
+#define LYNX_IMAGE_GRAD_CELLS 2048
+int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
+                                        const void* d_cov_trace, int32_t n_screens, const int32_t* screens,
+                                        const void* d_grid, const void* d_misalignment, int64_t misalignment_stride,
+                                        const void* d_images_bar, void* d_mu_bar, void* d_cov_bar,
+                                        void* d_grad_misalignment);
+
 /* Test hook: the float32 sine / cosine the cavity kick uses on the device (cavity.py:141-161
  * calls cos per particle), scalar (packed = 0) or two-per-lane (packed = 1) code path.        */
 int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t packed, float* d_sin,

@@ -31,6 +31,8 @@ STEP_RUN, STEP_CAVITY = 0, 1
 STEP_FLAG_RAW = 64
 STEP_FLAG_OBSERVE = 128
 MAX_OBSERVERS = 8
+IMAGE_GRAD_CELLS = 2048  # LYNX_IMAGE_GRAD_CELLS: the cells one workgroup of lynx_gaussian_images_along_backward sums
+MAX_IMAGE_BATCH = 65535  # lynx_gaussian_images_along and its adjoint: a sample is a row of the launch grid
 
 TRACK_MOMENTS, TRACK_TWO_KERNEL, TRACK_SHARED_INPUT, TRACK_SEQUENTIAL_STEPS, TRACK_COVARIANCE = 1, 2, 4, 8, 16
 
@@ -114,6 +116,8 @@ SIGNATURES = {
     "lynx_gaussian_image": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp]),
     "lynx_gaussian_images_along": (_i, [_vp, _i, _i64, C.c_int32, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), _vp, _vp,
                                         _i64, _vp]),
+    "lynx_gaussian_images_along_backward": (_i, [_vp, _i, _i64, C.c_int32, _vp, _vp, C.c_int32, C.POINTER(C.c_int32), _vp,
+                                                 _vp, _i64, _vp, _vp, _vp, _vp]),
     "lynx_diag_phase_trig": (_i, [_vp, _i64, _vp, C.c_int32, _vp, _vp]),
     "lynx_aperture_mask": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "lynx_aperture_compact": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),

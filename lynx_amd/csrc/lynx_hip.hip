@@ -175,6 +175,8 @@ struct lynx_ctx {
   void* scratch_trace_plan = nullptr;  // ... with losses or screens: step codes and screen rows (TraceLosses.plan), and what was uploaded last
   size_t scratch_trace_plan_bytes = 0;
   std::vector<int64_t> trace_plan;
+  void* scratch_image_grad = nullptr;  // lynx_gaussian_images_along_backward: the workgroups' partial sums [B][chunks][6] float64, screen after screen
+  size_t scratch_image_grad_bytes = 0;
   void* scratch_units_bwd[2] = {nullptr, nullptr};  // ... and of the reverse pass's own table
   size_t scratch_units_bwd_bytes[2] = {0, 0};
   void* scratch_units[2 * kTableSlots] = {};  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
@@ -629,6 +631,7 @@ int lynx_ctx_destroy(lynx_ctx* ctx) {
   for (int i = 0; i < 2; ++i)
     if (ctx->scratch_trace[i]) (void)hipFree(ctx->scratch_trace[i]);
   if (ctx->scratch_trace_plan) (void)hipFree(ctx->scratch_trace_plan);
+  if (ctx->scratch_image_grad) (void)hipFree(ctx->scratch_image_grad);
   for (int i = 0; i < 2 * lynx_ctx::kTableSlots; ++i)
     if (ctx->scratch_units[i]) (void)hipFree(ctx->scratch_units[i]);
   for (int i = 0; i < 2; ++i)
@@ -3220,6 +3223,73 @@ int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t 
     cell += (int64_t)nx * ny;
   }
   return LYNX_OK;
+}
+
+template <typename T>
+static int images_along_backward_t(lynx_ctx* ctx, int64_t batch, int32_t n_points, const void* d_mu_trace, const void* d_cov_trace,
+                                   int32_t n_screens, const int32_t* screens, const void* d_grid, const void* d_misalignment,
+                                   int64_t misalignment_stride, const void* d_images_bar, int64_t cells, void* d_mu_bar,
+                                   void* d_cov_bar, void* d_grad_misalignment) {
+  int64_t grid = 0, cell = 0, slab = 0;
+  for (int32_t k = 0; k < n_screens; ++k) {
+    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
+    const int64_t chunks = ((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells;
+    double* d_slab = (double*)ctx->scratch_image_grad + slab;
+    hipLaunchKernelGGL(k_gaussian_image_along_bwd<T>, dim3((unsigned)chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
+                       ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)point,
+                       (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx, (int)ny, (const T*)d_misalignment + 2 * k,
+                       misalignment_stride, (const T*)d_images_bar + cell, cells, d_slab);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_gaussian_image_along_bwd_finish<T>, dim3((unsigned)batch), dim3(64), 0, ctx->stream,
+                       (const T*)d_cov_trace, (int)n_points, (int)point, (const double*)d_slab, (int)chunks, (T*)d_mu_bar,
+                       (T*)d_cov_bar, d_grad_misalignment ? (T*)d_grad_misalignment + 2 * k : (T*)nullptr,
+                       (int64_t)2 * n_screens);
+    HIP_TRY(ctx, hipGetLastError());
+    grid += (int64_t)nx + ny;
+    cell += (int64_t)nx * ny;
+    slab += batch * chunks * 6;
+  }
+  return LYNX_OK;
+}
+
+int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
+                                        const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
+                                        const void* d_misalignment, int64_t misalignment_stride, const void* d_images_bar,
+                                        void* d_mu_bar, void* d_cov_bar, void* d_grad_misalignment) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !d_images_bar || !d_mu_bar || !d_cov_bar ||
+      batch <= 0 || batch > 65535 || n_points <= 0 || n_screens <= 0)
+    return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: bad argument");
+  if (dtype != LYNX_F32 && dtype != LYNX_F64)
+    return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: the dtype is float32 or float64");
+  if (misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
+    return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: the misalignments' sample stride is 0 or 2 * n_screens");
+  int64_t cells = 0, slab = 0;
+  for (int32_t k = 0; k < n_screens; ++k) {
+    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
+    if (point < 0 || point >= n_points || nx < 1 || ny < 1)
+      return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: a screen's point lies inside the trace, and it has pixels");
+    if ((int64_t)nx * ny > 0x7fffffffLL - kImageGradCells)  // (the kernel counts a screen's cells in 32 bits)
+      return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: a screen has fewer than 2^31 - 2048 pixels");
+    cells += (int64_t)nx * ny;
+    slab += batch * (((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells) * 6;
+  }
+  HIP_TRY(ctx, use_device(ctx));
+  if (const int rc = ensure_scratch(ctx, &ctx->scratch_image_grad, &ctx->scratch_image_grad_bytes, (size_t)slab * sizeof(double)))
+    return rc;
+  ctx->main_dirty = true;
+  const size_t es = dtype_size(dtype);
+  ctx->wrote(d_mu_bar, (size_t)batch * n_points * 7 * es);
+  ctx->wrote(d_cov_bar, (size_t)batch * n_points * 49 * es);
+  ctx->wrote(d_grad_misalignment, (size_t)batch * n_screens * 2 * es);
+  return dtype == LYNX_F64
+             ? images_along_backward_t<double>(ctx, batch, n_points, d_mu_trace, d_cov_trace, n_screens, screens, d_grid,
+                                               d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
+                                               d_grad_misalignment)
+             : images_along_backward_t<float>(ctx, batch, n_points, d_mu_trace, d_cov_trace, n_screens, screens, d_grid,
+                                              d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
+                                              d_grad_misalignment);
 }
 
 // ---- synthetic beams -------------------------------------------------------------------

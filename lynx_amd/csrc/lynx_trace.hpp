@@ -863,4 +863,116 @@ __global__ __launch_bounds__(256) void k_gaussian_image_along(const T* __restric
   image[b * cells + (int64_t)(nx - 1 - i) * ny + j] = (T)exp((double)logp);
 }
 
+// ---------------------------------------------------------------------------------------
+// k_gaussian_image_along_bwd: the adjoint of k_gaussian_image_along -- W = dL/d(image) of one screen, [nx][ny] in the
+// image's own (x-flipped) layout, reduced to six sums per sample:
+//   S0 = sum W I, Sx = sum W I ux, Sy = sum W I uy, Sxx = sum W I ux^2, Sxy = sum W I ux uy, Syy = sum W I uy^2,
+//   ux = (c dx - b dy) / det, uy = (a dy - b dx) / det  (d log I / d mx, d log I / d my).
+// I is formed anew from mu, cov with the very expression of the forward kernel: the gradient is that of the image the
+// caller saw, and no image is read back.  A workgroup sums kImageGradCells consecutive cells (flat index: coalesced loads
+// of W; i, j come from the cell index), float64 sums for both dtypes, across the wave with cross-lane adds, across the
+// four waves through LDS, and writes its six partial sums to slab[b][chunk][6].  No atomics:
+// k_gaussian_image_along_bwd_finish adds a sample's chunks in a fixed order.
+// ---------------------------------------------------------------------------------------
+constexpr int kImageGradThreads = 256;
+constexpr int kImageGradCells = LYNX_IMAGE_GRAD_CELLS;  // cells one workgroup sums
+static_assert(kImageGradCells % kImageGradThreads == 0, "every thread of a workgroup takes as many cells");
+
+__device__ __forceinline__ double image_grad_wave_sum(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kImageGradThreads) void k_gaussian_image_along_bwd(
+    const T* __restrict__ mu_trace, const T* __restrict__ cov_trace, int P, int point, const T* __restrict__ xs,
+    const T* __restrict__ ys, int nx, int ny, const T* __restrict__ misalignment /* of this screen */,
+    int64_t misalignment_stride, const T* __restrict__ image_bar /* of this screen */, int64_t cells,
+    double* __restrict__ slab /* of this screen: [B][chunks][6] */) {
+  __shared__ double s_part[kImageGradThreads / 64][6];
+  const int64_t b = blockIdx.y;
+  const int chunks = gridDim.x, chunk = blockIdx.x, tid = threadIdx.x;
+  const int n = nx * ny;
+  const T* mu = mu_trace + (b * P + point) * 7;
+  const T* cov = cov_trace + (b * P + point) * 49;
+  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
+  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
+  const T det = a * c - bb * bb;
+  const T* w = image_bar + b * cells;
+  double s[6] = {0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < kImageGradCells / kImageGradThreads; ++k) {
+    const int cell = chunk * kImageGradCells + k * kImageGradThreads + tid;
+    if (cell < n) {
+      const int row = cell / ny, j = cell - row * ny, i = nx - 1 - row;
+      const T dx = xs[i] - mx, dy = ys[j] - my;
+      const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
+      const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
+      const T density = (T)exp((double)logp);
+      const double wi = (double)w[cell] * (double)density;
+      const double ux = (double)((c * dx - bb * dy) / det), uy = (double)((a * dy - bb * dx) / det);
+      const double wx = wi * ux, wy = wi * uy;
+      s[0] += wi;
+      s[1] += wx;
+      s[2] += wy;
+      s[3] += wx * ux;
+      s[4] += wx * uy;
+      s[5] += wy * uy;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) s[q] = image_grad_wave_sum(s[q]);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) s_part[tid >> 6][q] = s[q];
+  }
+  __syncthreads();
+  if (tid < 6) {
+    double total = s_part[0][tid];
+#pragma unroll
+    for (int v = 1; v < kImageGradThreads / 64; ++v) total += s_part[v][tid];
+    slab[(b * chunks + chunk) * 6 + tid] = total;
+  }
+}
+
+// ... and its finishing step, one wave per sample: lane l adds the chunks l, l + 64, ... in that order, the lanes are added
+// across the wave, and lane 0 forms the five entries
+//   mu_bar[0] += Sx, mu_bar[2] += Sy, cov_bar[0][0] += (Sxx - c/det S0) / 2, cov_bar[2][2] += (Syy - a/det S0) / 2,
+//   cov_bar[0][2] and cov_bar[2][0] += (Sxy + b/det S0) / 2 each (their sum is the derivative by the covariance b)
+// at the screen's point, and grad_misalignment = (-Sx, -Sy).  a, b, c and det in float64 here.
+template <typename T>
+__global__ __launch_bounds__(64) void k_gaussian_image_along_bwd_finish(const T* __restrict__ cov_trace, int P, int point,
+                                                                        const double* __restrict__ slab, int chunks,
+                                                                        T* __restrict__ mu_bar, T* __restrict__ cov_bar,
+                                                                        T* __restrict__ grad_misalignment /* of this screen, or null */,
+                                                                        int64_t grad_misalignment_stride) {
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  double s[6] = {0, 0, 0, 0, 0, 0};
+  for (int chunk = lane; chunk < chunks; chunk += 64) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) s[q] += slab[(b * chunks + chunk) * 6 + q];
+  }
+#pragma unroll
+  for (int q = 0; q < 6; ++q) s[q] = image_grad_wave_sum(s[q]);
+  if (lane != 0) return;
+  const T* cov = cov_trace + (b * P + point) * 49;
+  const double a = (double)cov[0], bb = (double)cov[2], c = (double)cov[2 * 7 + 2];
+  const double det = a * c - bb * bb;
+  T* mb = mu_bar + (b * P + point) * 7;
+  T* cb = cov_bar + (b * P + point) * 49;
+  mb[0] += (T)s[1];
+  mb[2] += (T)s[2];
+  cb[0] += (T)(0.5 * (s[3] - c / det * s[0]));
+  cb[2 * 7 + 2] += (T)(0.5 * (s[5] - a / det * s[0]));
+  const T cross = (T)(0.5 * (s[4] + bb / det * s[0]));
+  cb[2] += cross;
+  cb[2 * 7] += cross;
+  if (grad_misalignment) {
+    grad_misalignment[b * grad_misalignment_stride] = (T)(-s[1]);
+    grad_misalignment[b * grad_misalignment_stride + 1] = (T)(-s[2]);
+  }
+}
+
 }  // namespace lynx

@@ -50,12 +50,15 @@ class Gradients:
     """
 
     def __init__(self, program, raw_dev, energy_dev, batch_shape, energy_shape, particles_dev=None,
-                 mu_dev=None, cov_dev=None, chosen_dev=None, survivors: bool = False):
+                 mu_dev=None, cov_dev=None, chosen_dev=None, survivors: bool = False, screens=(), screen_shifts_dev=None):
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
         self._survivors = survivors  # of `track_along_vjp(..., losses=True)`: no single incoming set of particles
         self._particles_dev = particles_dev
         self._mu_dev, self._cov_dev = mu_dev, cov_dev
         self._chosen_dev = chosen_dev
+        # of `track_along_vjp(..., screens=True)`: the trace's active screens and dL/d(misalignment) [B][screens][2] on the
+        # device (None: no image took a cotangent)
+        self._screens, self._screen_shifts_dev = list(screens), screen_shifts_dev
         self._batch_shape, self._energy_shape = tuple(batch_shape), tuple(energy_shape)
         self._raw = None
         self._cache = {}
@@ -108,6 +111,8 @@ class Gradients:
     def __contains__(self, element) -> bool:
         if self._survivors and any(el is element for _, el, _ in self._program.apertures):
             return True
+        if any(el is element for el in self._screens):
+            return True
         return any(el is element and el._kind in DIFFERENTIABLE_KINDS for el in self._program.leaves)
 
     def __getitem__(self, element) -> dict:
@@ -118,6 +123,14 @@ class Gradients:
         if self._survivors and any(el is element for _, el, _ in self._program.apertures):
             # the survivor set is held fixed: the limits that made it get gradient 0
             return {n: np.zeros(np.asarray(getattr(element, n)).shape) for n in ("x_max", "y_max")}
+        for k, el in enumerate(self._screens):
+            if el is element:  # the image sees mu_x - misalignment[0], mu_y - misalignment[1]: minus the mu cotangent there
+                shape = np.asarray(el.misalignment).shape
+                if self._screen_shifts_dev is None:
+                    return {"misalignment": np.zeros(shape)}
+                shifts = self._screen_shifts_dev.numpy().reshape(*self._batch_shape, len(self._screens), 2)
+                self._cache[id(element)] = {"misalignment": _unbroadcast(np.ascontiguousarray(shifts[..., k, :]), shape)}
+                return self._cache[id(element)]
         raw, total = self._host(), None
         for e, el in enumerate(self._program.leaves):
             if el is not element or el._kind not in DIFFERENTIABLE_KINDS:
@@ -529,13 +542,21 @@ class TrackAlongVJP:
     moment cotangent is still refused, by the call.
     """
 
-    def __init__(self, segment, beam, trajectories=None, losses=False):
+    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False):
         from .particles.parameter_beam import ParameterBeam
 
         if not isinstance(beam, (ParameterBeam, ParticleBeam)):
             raise TypeError(f"track_along_vjp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
         if not isinstance(losses, (bool, np.bool_)):
             raise ValueError(f"track_along_vjp: losses is True or False, not {losses!r}")
+        if not isinstance(screens, (bool, np.bool_)):
+            raise ValueError(f"track_along_vjp: screens is True or False, not {screens!r}")
+        if screens and isinstance(beam, ParticleBeam):
+            raise TypeError(
+                "track_along_vjp: screens=True with a ParticleBeam -- its screen image is a histogram of counts, a step "
+                "function of the magnets whose gradient is zero almost everywhere; a ParameterBeam of the same moments "
+                "(its image is a smooth density) is differentiated")
+        self._screens = bool(screens)
         if losses and trajectories is not None:
             raise NotImplementedError(
                 "track_along_vjp: losses=True together with trajectories= -- the trajectories of a trace with losses are "
@@ -545,7 +566,12 @@ class TrackAlongVJP:
         leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
         # (raises for an active Screen -- and, without `losses`, for an active Aperture --, naming it, before anything
         # touches the GPU)
-        self.program = engine._trace_plan(segment, leaves, bool(losses))
+        self.program = engine._trace_plan(segment, leaves, bool(losses), True) if screens else engine._trace_plan(segment, leaves, bool(losses))
+        B = int(np.prod(beam.batch_shape, dtype=np.int64))
+        if screens and self.program.screens and B > _ffi.MAX_IMAGE_BATCH:  # (as lynx_gaussian_images_along refuses it)
+            raise _ffi.LynxError(
+                f"track_along_vjp: screens=True with a batch of {B} samples, more than {_ffi.MAX_IMAGE_BATCH} -- "
+                "lynx_gaussian_images_along takes a sample per row of its launch grid (bad argument); trace the batch in parts")
         # the survivors' reverse pass: a ParticleBeam and at least one active aperture; anything else with `losses` is the
         # plain problem (apertures pass a ParameterBeam unchanged)
         self._sets = bool(losses) and isinstance(beam, ParticleBeam) and len(self.program.apertures) > 0
@@ -571,13 +597,14 @@ class TrackAlongVJP:
             self._refuse_moments()
         self.segment, self.beam, self.leaves = segment, beam, leaves
         self._set_records = None
+        with_screens = {"screens": True} if screens else {}  # (a ParameterBeam's then; without it the call is the one it was)
         if self._sets:
             self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses="particles")
             self._set_records = self._survivor_set_records()
         elif losses:  # (a ParameterBeam: active apertures are identity steps of its trace)
-            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses=True)
+            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses=True, **with_screens)
         elif self.chosen is None:
-            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True)
+            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, **with_screens)
         else:
             self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, trajectories=self.chosen)
 
@@ -683,8 +710,48 @@ class TrackAlongVJP:
                 f"track_along_vjp: a non-zero cotangent of {what} on sample {sample}, point {k}, which no particle reaches "
                 f"(transmission 0 there): the moments of nobody have no gradient")
 
+    def _image_cotangents(self, screen_images_bar):
+        """
+        `screen_images_bar` as one (B, cells) array of the beam's dtype in the layout of lynx_gaussian_images_along (screen
+        after screen, zeros for a screen that is not named), refused by value; None for an empty dict.
+        """
+        if not getattr(self, "_screens", False):
+            raise ValueError("track_along_vjp: screen_images_bar needs the screen images of the forward trace -- pass "
+                             "screens=True to track_along_vjp")
+        if not isinstance(screen_images_bar, dict):
+            raise TypeError(f"track_along_vjp: screen_images_bar is a dict {{screen: cotangent of its image}}, not {type(screen_images_bar)}")
+        trace, elements = self.trace, [el for _, el in self.program.screens]
+        named = []  # (screen, cotangent broadcast to its image), checked before anything is allocated
+        for key, bar in screen_images_bar.items():
+            if getattr(key, "_swallows_beam", False):  # the Screen element itself
+                found = [k for k, el in enumerate(elements) if el is key]
+                if not found:
+                    raise KeyError(f"{key!r} is not an active screen of this trace (screens at {list(trace.screens)})")
+                k = found[0]
+            else:
+                image = trace.image_at(key)  # (KeyError for anything but an active screen of the trace)
+                k = next(n for n, own in enumerate(trace.screen_images) if own is image)
+            shape = trace.screen_images[k].shape
+            w = np.asarray(bar)
+            try:
+                w = np.broadcast_to(w, shape)
+            except ValueError:
+                raise ValueError(f"track_along_vjp: screen_images_bar of screen {elements[k].name!r} has shape {w.shape}, which "
+                                 f"does not broadcast to its image's {shape} (*batch, nx, ny)") from None
+            named.append((k, w))
+        if not named:
+            return None
+        B = int(np.prod(self.beam.batch_shape, dtype=np.int64))
+        cells = [int(np.prod(image.shape[-2:])) for image in trace.screen_images]
+        first = np.concatenate([[0], np.cumsum(cells)])
+        # one pass per named screen, straight into what is uploaded: an ARES screen has 5e6 pixels per sample
+        flat = np.zeros((B, int(first[-1])), dtype=self.beam.dtype)
+        for k, w in named:
+            flat[:, first[k]:first[k + 1]] += w.reshape(B, cells[k])
+        return flat
+
     def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, trajectories_bar=None,
-                 **properties) -> Gradients:
+                 screen_images_bar: dict | None = None, **properties) -> Gradients:
         """
         `mu_bar` (*batch, P, 6|7), `cov_bar` (*batch, P, 6|7, 6|7) entry by entry, `energy_bar` (*batch, P): cotangents at
         every point; `properties`: cotangents (*batch, P) of any moment property of the trace and of `energy`;
@@ -692,7 +759,12 @@ class TrackAlongVJP:
         `trajectories_bar` (broadcastable to (*batch, P, K, 6|7)): of the coordinates of the chosen particles at every point
         (`trajectories=` of `track_along_vjp`).  All of them in one reverse call; `Gradients.chosen_particles` is then the
         gradient w.r.t. the chosen incoming particles, and `mu`, `cov` exist if a moment cotangent was given.
+        `screen_images_bar={screen: bar}` (`screens=True` of `track_along_vjp`): cotangents of the images of active screens,
+        a key whatever `trace.image_at` takes or the `Screen` itself, a value broadcastable to that image (*batch, nx, ny);
+        lynx_gaussian_images_along_backward reduces them on the device into the mu and cov cotangents at the screens' points,
+        where the sweep picks them up, and `g[screen]["misalignment"]` is the gradient w.r.t. the screen's misalignment.
         """
+        wi = None if screen_images_bar is None else self._image_cotangents(screen_images_bar)
         wb = None
         if trajectories_bar is not None:
             wb = self._trajectory_cotangents(trajectories_bar)
@@ -747,13 +819,24 @@ class TrackAlongVJP:
                 p(g_par), p(g_en), p(g_mu), p(g_cov)))
         else:
             mb_dev, cb_dev = rt.to_device(mb.astype(dtype)), rt.to_device(cb.astype(dtype))
+            shifts = None
+            if wi is not None:  # the images' cotangents go into mb_dev, cb_dev at the screens' points, on the same stream
+                shots = engine._screen_geometry(self.segment, program, batch_shape, dtype, rt, False)
+                wi_dev = rt.to_device(np.ascontiguousarray(wi, dtype=dtype))
+                shifts = rt.empty((B, shots["count"], 2), dtype)
+                rt.check(rt.lib.lynx_gaussian_images_along_backward(
+                    rt.ctx, engine.dtype_code(dtype), B, P, p(states["mu"]), p(states["cov"]), shots["count"], shots["rows"],
+                    p(shots["grid"]), p(shots["misalignment"]), shots["stride"], p(wi_dev), p(mb_dev), p(cb_dev), p(shifts)))
             rt.check(rt.lib.lynx_track_moments_along_backward(
                 rt.ctx, lat.handle, p(e_in), p(states["mu"]), p(states["cov"]), p(mb_dev), p(cb_dev), p(eb_dev),
                 p(g_par), p(g_en), p(g_mu), p(g_cov)))
+            if getattr(self, "_screens", False):
+                return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov,
+                                 screens=[el for _, el in program.screens], screen_shifts_dev=shifts)
         return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
 
 
-def track_along_vjp(segment, beam, trajectories=None, losses=False):
+def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
     callable vector-Jacobian product of the moments and energies at every point:
@@ -789,8 +872,25 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False):
     point no particle of a sample reaches is a ValueError.  At most 15 active apertures; not together with
     `trajectories=`.  Without an active aperture, or with a ParameterBeam (apertures pass it unchanged), `losses=True` is
     the plain call.
+
+    `screens=True` (a ParameterBeam): the forward pass is `segment.track_along(beam, screens=True)` -- every active `Screen`
+    makes its image inside the trace (`vjp.trace.screens`, `screen_images`, `image_at`; the screen's `reading` is that image)
+    -- and the call takes cotangents of the images, together with any cotangent above:
+
+        vjp = lynx_amd.grad.track_along_vjp(segment, parameter_beam, screens=True)
+        img = vjp.trace.image_at("SCREEN")                        # (*batch, nx, ny)
+        g = vjp(screen_images_bar={"SCREEN": 2 * (img - target)})
+        g[segment.Q1]["k1"], g.energy, g.mu, g.cov, g[segment.SCREEN]["misalignment"]
+
+    The image is the bivariate-normal density of (mu_x - misalignment[0], mu_y - misalignment[1]) and cov_xx, cov_xy, cov_yy at
+    the point the screen observes; its adjoint is a weighted sum over all pixels (lynx_gaussian_images_along_backward, on the
+    device, into the cotangents of mu and cov there), and the gradient with respect to the screen's `misalignment` -- summed
+    over the batch where it is shared -- comes with it (zero for a screen that got no cotangent).  Nothing is special-cased:
+    a covariance with cov_xx cov_yy - cov_xy^2 <= 0 gives NaN images and NaN gradients, a beam so far off the screen that the
+    image has underflowed to 0 gives gradient 0.  A ParticleBeam is a TypeError (its image is a histogram of counts);
+    `losses=True` may be combined (apertures pass a ParameterBeam unchanged); at most 65535 samples.
     """
-    return TrackAlongVJP(segment, beam, trajectories, losses)
+    return TrackAlongVJP(segment, beam, trajectories, losses, screens)
 
 
 def track_vjp(segment, beam):
