@@ -346,6 +346,28 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                         void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
                                         void* d_grad_cov_in);
 
+/* ... of lynx_track_particles_along on a program WITH cavity steps: behind a kick the moments are no function of the
+ * moments in front of it, so the gradient takes a second pass over the particles -- the reverse sweep of
+ * lynx_track_particles_backward (forward sweep, every 4th state parked, walk back through the kicks), in which the moment
+ * cotangent of EVERY point p gives every particle the cotangent
+ *   inj_p(z)[k] = (mu_bar_p[k] + sum_j G_hat_p[k][j] (z[j] - mean_p[j])) / n  (k < 6),   inj_p(z)[6] = mu_bar_p[6] / n,
+ * G_hat the symmetric matrix of the triangle cotangent with the diagonal doubled, at the point where the particle has the
+ * state the record was taken from.  The records and cotangents are converted once into a table in the lattice's dtype.
+ *   d_p_in        [B][N][7], or [N][7] with LYNX_TRACK_SHARED_INPUT (the only flag): the incoming particles of the trace
+ *   d_trace_fwd, d_grad_trace [B][P][36] float64, d_energy_bar [B][P] or NULL, d_grad_params [B][E][8],
+ *   d_grad_energy_in [B]                        as for lynx_track_particles_along_backward
+ *   d_grad_p_in   [B][N][7] or NULL             dL/d(incoming particles), lattice dtype (a shared beam: per sample)
+ * There is no gradient with respect to the incoming mean and covariance.  A program without a cavity step is accepted
+ * (a second way to the answer of lynx_track_particles_along_backward).  Fixed summation order, no atomics: the same call
+ * returns the same bits.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "beam trace gradients
+ * with cavities: ") for a null required argument, n_particles < 1, any other flag, an empty program, more than 64 steps
+ * (the parked states of the sweep), a program whose sums do not fit the LDS of a workgroup, d_grad_p_in == d_p_in.   */
+int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles,
+                                                 const void* d_energy_in, const void* d_p_in, int flags,
+                                                 const double* d_trace_fwd, const double* d_grad_trace,
+                                                 const void* d_energy_bar, void* d_grad_params, void* d_grad_energy_in,
+                                                 void* d_grad_p_in);
+
 /* The moment records of an INCOMING beam over the nested survivor sets of a trace with losses: set j holds the particles
  * alive behind the first j apertures (d_lost_at == -1 or >= j; set 0 is everyone).  What the reverse pass below starts
  * its per-set recursions from -- one more streaming pass over the incoming particles.

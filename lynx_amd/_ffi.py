@@ -104,6 +104,7 @@ SIGNATURES = {
     "lynx_track_moments_along": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_track_moments_along_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_track_particles_along_backward": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lynx_track_particles_along_backward_cavities": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_moments_by_loss": (_i, [_vp, _i, _i64, _i64, _vp, _i, C.c_int32, _vp, _vp]),
     "lynx_track_particles_along_backward_losses": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, C.c_int32, C.POINTER(C.c_int32),
                                                         _vp, _vp, _vp]),

@@ -335,18 +335,85 @@ template <typename T> __host__ __device__ inline int bwd_acc_stride(int S) {
   return (sizeof(T) == 8 && S > 58) ? 57 : 64;
 }
 
-// what one workgroup of k_track_bwd does: chunk `work % a.chunks` of sample `work / a.chunks`
-template <typename T, typename Z>
+// ---- a moment cotangent at EVERY point of the program (the beam trace's reverse pass through cavities) ----------------
+// Row (sample, point p) of the injection table, in the lattice's dtype (k_trace_inject_table converts the trace's float64
+// records and their cotangents once; the streaming kernel reads a row through wave-uniform scalar loads):
+//   [0..5] mean m_p | [6..12] mu_bar_p | [13..33] G_hat_p, upper triangle in the record's order, the diagonal doubled |
+//   [34] 1 / n | [35] non-zero where any of the 28 cotangents is (a point without a cotangent costs one scalar load)
+// A particle at z takes  inj_p(z)[k] = (mu_bar[k] + sum_j G_hat[k][j] (z[j] - m[j])) / n,  inj_p(z)[6] = mu_bar[6] / n --
+// the expression k_track_bwd starts its sweep from, in the (z - m) form (folding G_hat m into a constant loses two digits
+// of a float32 beam 1 mm off axis with sigma = 10 um).
+constexpr int kInjectStride = 36;
+constexpr int kInjectMuBar = 6, kInjectG = 13, kInjectInvN = 34, kInjectAny = 35;
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_trace_inject_table(const double* __restrict__ trace_fwd /* [B][P][36] */,
+                                                            const double* __restrict__ grad_trace /* [B][P][36] */,
+                                                            int64_t cells /* B * P * kInjectStride */, T* __restrict__ table) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= cells) return;
+  const int64_t point = idx / kInjectStride;
+  const int q = (int)(idx % kInjectStride);
+  const double* rec = trace_fwd + point * LYNX_MOMENT_STRIDE;
+  const double* gm = grad_trace + point * LYNX_MOMENT_STRIDE;
+  T v;
+  if (q < kInjectMuBar) {
+    v = (T)rec[q];
+  } else if (q < kInjectG) {
+    v = (T)gm[q - kInjectMuBar];
+  } else if (q < kInjectInvN) {
+    const int t = q - kInjectG;  // diagonal entries of the triangle: 0, 6, 11, 15, 18, 20
+    const T g = (T)gm[7 + t];
+    v = (t == 0 || t == 6 || t == 11 || t == 15 || t == 18 || t == 20) ? g + g : g;
+  } else if (q == kInjectInvN) {
+    v = (T)(1.0 / rec[35]);
+  } else {
+    bool any = false;
+    for (int k = 0; k < 28; ++k) any = any || gm[k] != 0.0;
+    v = any ? T(1) : T(0);
+  }
+  table[idx] = v;
+}
+
+// inj_p(z) of the live lanes (zeros elsewhere, and everywhere at a point without a cotangent); `row` is wave-uniform
+template <typename T, typename Z, int W>
+__device__ __forceinline__ void inject_cotangent(const T* __restrict__ row, const Z (&z)[7], const bool (&live)[W], Z (&out)[7]) {
+  const T inv_n = row[kInjectInvN];
+  Z d[6];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) d[k] = z[k] - row[k];
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    Z accv = Z(row[kInjectMuBar + k]);
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const int r = k < j ? k : j, c = k < j ? j : k;
+      accv = zfma(d[j], row[kInjectG + r * 6 - (r * (r - 1)) / 2 + (c - r)], accv);
+    }
+    out[k] = accv * inv_n;
+  }
+  out[6] = Z(row[kInjectMuBar + 6] * inv_n);
+#pragma unroll
+  for (int w = 0; w < W; ++w)
+#pragma unroll
+    for (int c = 0; c < 7; ++c) zset(out[c], w, live[w] ? zget(out[c], w) : T(0));
+}
+
+// what one workgroup of k_track_bwd does: chunk `work % a.chunks` of sample `work / a.chunks`.  INJECT (k_track_bwd_inject):
+// the cotangents come from the injection table, one row per point, `in_stride` scalars lie between two samples' incoming
+// particles (0: shared), and moments_fwd, grad_moments, units_skip and grad_observations are not looked at.
+template <typename T, typename Z, bool INJECT = false>
 __device__ __forceinline__ void track_bwd_workgroup(
     const LatticeDev& lat, const BwdArgs& a, uint32_t work, const T* __restrict__ p_in, const T* __restrict__ steps,
     const double* __restrict__ moments_fwd, const double* __restrict__ grad_moments,
     T* __restrict__ partials /* [B][chunks][S][64] */, T* __restrict__ grad_p /* [B][N][7] or null */,
     const float* __restrict__ units_skip, int units_stride, int units_class_shift, int units_class_u,
-    const double* __restrict__ grad_observations) {
+    const double* __restrict__ grad_observations, const T* __restrict__ inject = nullptr /* [B][S + 1][kInjectStride] */,
+    int64_t in_stride = 0) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   constexpr int K = kBwdGroup;
   constexpr int W = LaneOf<Z>::W;
-  if (units_skip) {  // uniform
+  if (!INJECT && units_skip) {  // uniform
     const float* rec = units_skip + (work / a.chunks) * (int64_t)a.n_units * units_stride;
     bool other = false;  // (one descriptor per lane, 64 at a time: one round trip where a loop over the units takes n_units)
     for (int u0 = 0; u0 < a.n_units; u0 += 64) {
@@ -382,7 +449,8 @@ __device__ __forceinline__ void track_bwd_workgroup(
 
   const double* rec = moments_fwd + b * LYNX_MOMENT_STRIDE;
   const double* gm = grad_moments + b * LYNX_MOMENT_STRIDE;
-  const T* src = p_in + b * N * 7;
+  const T* src = p_in + (INJECT ? b * in_stride : b * N * 7);
+  const T* inj = INJECT ? inject + b * (int64_t)(S + 1) * kInjectStride : nullptr;  // (raw program: point u enters unit u)
   constexpr int64_t kTile = (int64_t)kTrackThreads * W;
   for (int it = 0; it < a.tiles_per_wg; ++it) {
     const int64_t base = ((int64_t)chunk * a.tiles_per_wg + it) * kTile;
@@ -412,7 +480,14 @@ __device__ __forceinline__ void track_bwd_workgroup(
     // the upper-triangle cotangent (diagonal counted twice); the per-sample constants are
     // fetched here, per tile, so that they do not stay live across the sweeps
     Z zb[7];
-    {
+    if constexpr (INJECT) {  // lambda_S = inj_S(z_S)
+      if (uniform_value(inj[U * kInjectStride + kInjectAny]) != T(0)) {  // uniform
+        inject_cotangent<T, Z, W>(inj + U * kInjectStride, z, live, zb);
+      } else {
+#pragma unroll
+        for (int c = 0; c < 7; ++c) zb[c] = Z(T(0));
+      }
+    } else {
       const T inv_n = (T)(1.0 / rec[35]);
       Z d[6];
 #pragma unroll
@@ -585,7 +660,15 @@ __device__ __forceinline__ void track_bwd_workgroup(
           for (int r = 1; r < 7; ++r) v = zfma(olin[r], m[r * 7 + jj], v);
           zb[jj] = v;
         }
-        if (grad_observations != nullptr && a.unit_observer[u] != 0) {  // uniform: an active BPM read the beam entering this unit
+        if constexpr (INJECT) {  // the moment cotangent of the point that enters this unit: lambda_u += inj_u(z_u)
+          const T* row = inj + u * kInjectStride;
+          if (uniform_value(row[kInjectAny]) != T(0)) {  // uniform
+            Z add[7];
+            inject_cotangent<T, Z, W>(row, zin, live, add);
+#pragma unroll
+            for (int c = 0; c < 7; ++c) zb[c] += add[c];
+          }
+        } else if (grad_observations != nullptr && a.unit_observer[u] != 0) {  // uniform: an active BPM read the beam entering this unit
           const double* ob = grad_observations + (b * a.n_observers + (a.unit_observer[u] - 1)) * 2;
           const T inv_n = (T)(1.0 / rec[35]), gx = (T)ob[0] * inv_n, gy = (T)ob[1] * inv_n;
 #pragma unroll
@@ -654,6 +737,20 @@ __global__ __launch_bounds__(kTrackThreads) void k_track_bwd(
     track_bwd_workgroup<T, Z>(lat, a, work, p_in, steps, moments_fwd, grad_moments, partials, grad_p, units_skip, units_stride,
                               units_class_shift, units_class_u, grad_observations);
     __syncthreads();  // (the LDS sums of this piece have been read by everybody before the next one clears them)
+  }
+}
+
+// k_track_bwd with a moment cotangent at every point (lynx_track_particles_along_backward_cavities): the same sweep, parking
+// scheme, LDS geometry and partial sums; every sample is walked here (no structured kernel next to it).
+template <typename T, typename Z>
+__global__ __launch_bounds__(kTrackThreads) void k_track_bwd_inject(
+    LatticeDev lat, BwdArgs a, const T* __restrict__ p_in, int64_t in_stride, const T* __restrict__ steps,
+    const T* __restrict__ inject /* [B][S + 1][kInjectStride] */, T* __restrict__ partials /* [B][chunks][S][64] */,
+    T* __restrict__ grad_p /* [B][N][7] or null */) {
+  for (uint32_t work = blockIdx.x; work < (uint32_t)a.n_work; work += gridDim.x) {
+    track_bwd_workgroup<T, Z, true>(lat, a, work, p_in, steps, nullptr, nullptr, partials, grad_p, nullptr, 0, 0, 0, nullptr, inject,
+                                    in_stride);
+    __syncthreads();
   }
 }
 

@@ -2944,6 +2944,113 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                                  d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
 }
 
+// ... through cavity steps: k_track_bwd's sweep over the particles with a moment cotangent injected at every point
+// (k_track_bwd_inject), on the trace's program -- every step a unit of its own --, its partial sums reduced into
+// scratch_grad[1] as track_backward_t reduces them, then the same k_build_bwd.  scratch_grad[0]: the partial sums
+// [B][chunks][S][64], then the injection table [B][P][kInjectStride], both in the lattice's dtype.
+template <typename T, int W>
+static size_t bwd_inject_lds_bytes(int32_t S) {
+  return ((size_t)4 * ExRows<W>::value * ExGeom<T, W>::kPitch + (size_t)4 * S * bwd_acc_stride<T>(S)) * sizeof(T);
+}
+
+template <typename T, typename Z>
+static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in,
+                                               const void* d_p_in, int flags, const double* d_trace_fwd,
+                                               const double* d_grad_trace, const void* d_energy_bar, void* d_grad_params,
+                                               void* d_grad_energy_in, void* d_grad_p_in) {
+  constexpr int W = LaneOf<Z>::W;
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps, P = S + 1;
+  int rc;
+  BwdArgs a;
+  a.n_units = S;
+  a.n_observers = 0;
+  a.out_chunks = 0;
+  a.leave_odd = 0;
+  for (int u = 0; u < kBwdGroup * kBwdMaxGroups; ++u) {
+    a.unit_slot[u] = (unsigned char)(u < S ? u : 0);
+    a.unit_observer[u] = 0;
+  }
+  const size_t lds = bwd_inject_lds_bytes<T, W>(S);
+  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t ntiles = (N + kTrackThreads * W - 1) / (kTrackThreads * W);
+  int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(ntiles, ((int64_t)kBwdWgsPerCu * cus + B - 1) / B));
+  const int64_t tpw = (ntiles + chunks - 1) / chunks;
+  chunks = (ntiles + tpw - 1) / tpw;
+  a.n_particles = N;
+  a.chunks = (int32_t)chunks;
+  a.tiles_per_wg = (int32_t)tpw;
+  a.n_work = (int32_t)(B * chunks);
+  if ((int64_t)B * chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients with cavities: grid too large");
+  if ((rc = allow_lds(ctx, k_track_bwd_inject<T, Z>, lds))) return rc;
+  const size_t partial_scalars = (size_t)B * chunks * S * kGradStride, table_scalars = (size_t)B * P * kInjectStride;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (partial_scalars + table_scalars) * sizeof(T))))
+    return rc;
+  T* partials = (T*)ctx->scratch_grad[0];
+  T* inject = partials + partial_scalars;
+  if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
+  hipLaunchKernelGGL(k_trace_inject_table<T>, dim3((unsigned)((table_scalars + 255) / 256)), dim3(256), 0, ctx->stream, d_trace_fwd,
+                     d_grad_trace, (int64_t)table_scalars, inject);
+  HIP_TRY(ctx, hipGetLastError());
+  // (between lynx_profile_begin and _end the sweep's own duration is one more entry of lynx_profile_launches)
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (ctx->profiling) {
+    HIP_TRY(ctx, hipEventCreateWithFlags(&e0, timing_event_flags(ctx)));
+    HIP_TRY(ctx, hipEventCreateWithFlags(&e1, timing_event_flags(ctx)));
+  }
+  hipExtLaunchKernelGGL((k_track_bwd_inject<T, Z>), dim3((unsigned)(B * chunks)), dim3(kTrackThreads), (std::uint32_t)lds, ctx->stream,
+                        e0, e1, 0u, dev_view(lat), a, (const T*)d_p_in, (flags & LYNX_TRACK_SHARED_INPUT) ? (int64_t)0 : N * 7,
+                        (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)inject, partials, (T*)d_grad_p_in);
+  HIP_TRY(ctx, hipGetLastError());
+  if (ctx->profiling) ctx->prof_events.emplace_back(e0, e1);
+  if (chunks >= 16) {
+    hipLaunchKernelGGL(k_reduce_tbar<T>, dim3((unsigned)(B * S)), dim3(256), 0, ctx->stream, (const T*)partials, (int)chunks, (int)S,
+                       (T*)ctx->scratch_grad[1]);
+  } else {  // four rows (sample, step) per wave
+    const int64_t rows = B * S;
+    hipLaunchKernelGGL((k_reduce_tbar_rows<T, 4>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const T*)partials,
+                       (int)chunks, (int)S, rows, (T*)ctx->scratch_grad[1]);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
+}
+
+int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles,
+                                                 const void* d_energy_in, const void* d_p_in, int flags,
+                                                 const double* d_trace_fwd, const double* d_grad_trace,
+                                                 const void* d_energy_bar, void* d_grad_params, void* d_grad_energy_in,
+                                                 void* d_grad_p_in) {
+  LYNX_NEED(ctx);
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  const std::string prefix = "beam trace gradients with cavities: ";
+  const auto refuse = [&](const std::string& what) { return fail(ctx, LYNX_ERR_INVALID, prefix + what); };
+  if (!lat || !d_energy_in || !d_p_in || !d_trace_fwd || !d_grad_trace || !d_grad_params || !d_grad_energy_in)
+    return refuse("null argument");
+  if (n_particles < 1) return refuse("n_particles must be > 0");
+  if (flags & ~LYNX_TRACK_SHARED_INPUT) return refuse("LYNX_TRACK_SHARED_INPUT is the only flag");
+  if (const int rc = trace_backward_check(ctx, lat, prefix)) return rc;
+  if (lat->n_steps > kBwdGroup * kBwdMaxGroups)
+    return refuse(std::to_string(lat->n_steps) + " steps; the sweep over the particles parks at most " +
+                  std::to_string(kBwdGroup * kBwdMaxGroups) + " (split the lattice)");
+  {
+    const size_t lds = lat->dtype == LYNX_F64 ? bwd_inject_lds_bytes<double, 1>(lat->n_steps) : bwd_inject_lds_bytes<float, 2>(lat->n_steps);
+    if (lds > 160 * 1024)
+      return refuse("LDS budget exceeded: " + std::to_string(lat->n_steps) + " steps need " + std::to_string(lds) +
+                    " bytes of the 163840 per workgroup (split the lattice)");
+  }
+  if (d_grad_p_in && d_grad_p_in == d_p_in) return refuse("d_grad_p_in aliases d_p_in: the sweep reads the incoming particles tile by tile");
+  HIP_TRY(ctx, use_device(ctx));
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
+  ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype));
+  return lat->dtype == LYNX_F64
+             ? particles_along_backward_cavities_t<double, double>(ctx, lat, n_particles, d_energy_in, d_p_in, flags, d_trace_fwd,
+                                                                   d_grad_trace, d_energy_bar, d_grad_params, d_grad_energy_in,
+                                                                   d_grad_p_in)
+             : particles_along_backward_cavities_t<float, lynx_f32x2>(ctx, lat, n_particles, d_energy_in, d_p_in, flags, d_trace_fwd,
+                                                                      d_grad_trace, d_energy_bar, d_grad_params, d_grad_energy_in,
+                                                                      d_grad_p_in);
+}
+
 // ... of a trace with losses: one wave per (sample, survivor set) propagates the set's incoming moments and sweeps back
 // over the set's live points (k_trace_moments_bwd_sets), the sets' T_bar are added in set order (k_trace_sum_sets), then
 // the same k_build_bwd.  scratch_grad[0]: the states [B][A + 1][S][56], then the sets' T_bar [A + 1][B][S][64], float64.

@@ -50,9 +50,13 @@ class Gradients:
     """
 
     def __init__(self, program, raw_dev, energy_dev, batch_shape, energy_shape, particles_dev=None,
-                 mu_dev=None, cov_dev=None, chosen_dev=None, survivors: bool = False, screens=(), screen_shifts_dev=None):
+                 mu_dev=None, cov_dev=None, chosen_dev=None, survivors: bool = False, screens=(), screen_shifts_dev=None,
+                 through_kicks: bool = False):
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
         self._survivors = survivors  # of `track_along_vjp(..., losses=True)`: no single incoming set of particles
+        # of `track_along_vjp(..., cavities=True)` on a ParticleBeam: behind a kick the gradient is no function of the
+        # incoming moments -- `mu`, `cov` are None, `particles` (if asked for) is what there is
+        self._through_kicks = through_kicks
         self._particles_dev = particles_dev
         self._mu_dev, self._cov_dev = mu_dev, cov_dev
         self._chosen_dev = chosen_dev
@@ -82,8 +86,11 @@ class Gradients:
 
     @property
     def mu(self) -> np.ndarray:
-        """dL/d(incoming mu), (*batch, 7) -- ParameterBeam VJPs only; None for the survivors of a trace with losses."""
-        if self._survivors:
+        """
+        dL/d(incoming mu), (*batch, 7) -- ParameterBeam VJPs only; None for the survivors of a trace with losses and for a
+        ParticleBeam differentiated through cavities.
+        """
+        if self._survivors or self._through_kicks:
             return None
         if self._mu_dev is None:
             raise KeyError("the gradient w.r.t. mu exists for ParameterBeam VJPs only")
@@ -92,7 +99,7 @@ class Gradients:
     @property
     def cov(self) -> np.ndarray:
         """dL/d(incoming cov), (*batch, 7, 7), entry by entry -- ParameterBeam VJPs only; None like `mu`."""
-        if self._survivors:
+        if self._survivors or self._through_kicks:
             return None
         if self._cov_dev is None:
             raise KeyError("the gradient w.r.t. cov exists for ParameterBeam VJPs only")
@@ -409,6 +416,7 @@ class MomentsVJP:
 
 MAX_TRACE_LEAVES = 256  # lynx_track_*_along_backward: k_build_bwd deals the steps of a program to its 256 threads
 MAX_TRACE_LOSS_APERTURES = 15  # lynx_track_particles_along_backward_losses: 16 survivor sets
+MAX_TRACE_CAVITY_LEAVES = 64  # lynx_track_particles_along_backward_cavities: k_track_bwd parks the states of 16 groups of 4 steps
 
 
 def trace_property_cotangents(trace, named: dict):
@@ -540,9 +548,13 @@ class TrackAlongVJP:
     (lynx_track_particles_along_backward_trajectories).  A single trajectory is differentiable through a cavity's kick, so
     a ParticleBeam on a lattice with an active cavity is accepted then -- for `trajectories_bar` and `energy_bar`; a
     moment cotangent is still refused, by the call.
+
+    With `cavities=True` a ParticleBeam's moment cotangents pass active cavities: the reverse call is a second pass over the
+    particles (lynx_track_particles_along_backward_cavities), the sweep of `track_vjp` with the moment cotangent of every
+    point given to every particle at that point; at most 64 leaf elements, `wrt_particles=True` in the call.
     """
 
-    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False):
+    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False, cavities=False):
         from .particles.parameter_beam import ParameterBeam
 
         if not isinstance(beam, (ParameterBeam, ParticleBeam)):
@@ -551,6 +563,15 @@ class TrackAlongVJP:
             raise ValueError(f"track_along_vjp: losses is True or False, not {losses!r}")
         if not isinstance(screens, (bool, np.bool_)):
             raise ValueError(f"track_along_vjp: screens is True or False, not {screens!r}")
+        if not isinstance(cavities, (bool, np.bool_)):
+            raise ValueError(f"track_along_vjp: cavities is True or False, not {cavities!r}")
+        if cavities and (trajectories is not None or losses):
+            raise NotImplementedError(
+                "track_along_vjp: cavities=True together with " + ("trajectories=" if trajectories is not None else "losses=True")
+                + " -- the second pass over the particles differentiates the moments of the whole beam alone; ask for one of "
+                "the two")
+        # the pass through the kicks: a ParticleBeam's (a ParameterBeam's recursion handles cavities as it is)
+        self._through_kicks = bool(cavities) and isinstance(beam, ParticleBeam)
         if screens and isinstance(beam, ParticleBeam):
             raise TypeError(
                 "track_along_vjp: screens=True with a ParticleBeam -- its screen image is a histogram of counts, a step "
@@ -587,8 +608,12 @@ class TrackAlongVJP:
             raise NotImplementedError(
                 f"track_along_vjp: {len(leaves)} leaf elements, more than {MAX_TRACE_LEAVES} (the first one beyond is "
                 f"{leaves[MAX_TRACE_LEAVES].name!r}) -- differentiate the lattice in stretches")
+        if self._through_kicks and len(leaves) > MAX_TRACE_CAVITY_LEAVES:
+            raise NotImplementedError(
+                f"track_along_vjp: cavities=True with {len(leaves)} leaf elements, more than {MAX_TRACE_CAVITY_LEAVES} (the first "
+                f"one beyond is {leaves[MAX_TRACE_CAVITY_LEAVES].name!r}) -- differentiate the lattice in stretches")
         self._cavity = None  # the first active cavity in front of a ParticleBeam: no moment cotangent passes it
-        if isinstance(beam, ParticleBeam):
+        if isinstance(beam, ParticleBeam) and not self._through_kicks:
             for kind, first, _ in self.program.steps:
                 if kind == _ffi.STEP_CAVITY:
                     self._cavity = leaves[first].name
@@ -627,7 +652,8 @@ class TrackAlongVJP:
     def _refuse_moments(self):
         raise NotImplementedError(
             f"track_along_vjp: active Cavity {self._cavity!r} -- the moments of a ParticleBeam are not "
-            "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated")
+            "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated, and so is this beam by a "
+            "second pass over its particles: track_along_vjp(..., cavities=True)")
 
     def _trajectory_cotangents(self, trajectories_bar) -> np.ndarray:
         """`trajectories_bar` as (B, P, K, 7) float64, refused by value."""
@@ -751,7 +777,7 @@ class TrackAlongVJP:
         return flat
 
     def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, trajectories_bar=None,
-                 screen_images_bar: dict | None = None, **properties) -> Gradients:
+                 screen_images_bar: dict | None = None, wrt_particles: bool = False, **properties) -> Gradients:
         """
         `mu_bar` (*batch, P, 6|7), `cov_bar` (*batch, P, 6|7, 6|7) entry by entry, `energy_bar` (*batch, P): cotangents at
         every point; `properties`: cotangents (*batch, P) of any moment property of the trace and of `energy`;
@@ -763,7 +789,12 @@ class TrackAlongVJP:
         a key whatever `trace.image_at` takes or the `Screen` itself, a value broadcastable to that image (*batch, nx, ny);
         lynx_gaussian_images_along_backward reduces them on the device into the mu and cov cotangents at the screens' points,
         where the sweep picks them up, and `g[screen]["misalignment"]` is the gradient w.r.t. the screen's misalignment.
+        `wrt_particles=True` (`cavities=True` of `track_along_vjp`, a ParticleBeam): `Gradients.particles` (*batch, N, 7), the
+        gradient w.r.t. every incoming particle, device-resident.
         """
+        if wrt_particles and not getattr(self, "_through_kicks", False):
+            raise ValueError("track_along_vjp: wrt_particles=True needs the pass over the particles -- a ParticleBeam and "
+                             "cavities=True of track_along_vjp (without a cavity g.mu and g.cov say the same)")
         wi = None if screen_images_bar is None else self._image_cotangents(screen_images_bar)
         wb = None
         if trajectories_bar is not None:
@@ -804,6 +835,15 @@ class TrackAlongVJP:
                 p(eb_dev), p(g_par), p(g_en), p(g_mu), p(g_cov), K, p(states["trajectories"]), p(wb_dev), p(g_chosen)))
             return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov,
                              chosen_dev=g_chosen)
+        if getattr(self, "_through_kicks", False):
+            rec_dev = rt.to_device(_record_cotangents(mb, cb))
+            g_p = rt.empty((*batch_shape, beam.num_particles, 7), dtype) if wrt_particles else None
+            rt.check(rt.lib.lynx_track_particles_along_backward_cavities(
+                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(beam._particles.device(rt)),
+                _ffi.TRACK_SHARED_INPUT if beam.is_shared else 0, p(states["records"]), p(rec_dev), p(eb_dev), p(g_par), p(g_en),
+                p(g_p)))
+            return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, particles_dev=g_p,
+                             through_kicks=True)
         if self._sets:
             rec_dev = rt.to_device(_record_cotangents(mb, cb))
             A = len(program.apertures)
@@ -836,7 +876,7 @@ class TrackAlongVJP:
         return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
 
 
-def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False):
+def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False, cavities=False):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
     callable vector-Jacobian product of the moments and energies at every point:
@@ -889,8 +929,23 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
     a covariance with cov_xx cov_yy - cov_xy^2 <= 0 gives NaN images and NaN gradients, a beam so far off the screen that the
     image has underflowed to 0 gives gradient 0.  A ParticleBeam is a TypeError (its image is a histogram of counts);
     `losses=True` may be combined (apertures pass a ParameterBeam unchanged); at most 65535 samples.
+
+    `cavities=True` (a ParticleBeam): active cavities are no obstacle to the moment cotangents.  Behind a cavity's kick the
+    moments are not a function of the moments in front of it, so the reverse call takes a second pass over the particles
+    (lynx_track_particles_along_backward_cavities: the sweep of `track_vjp`, which parks every 4th state and walks back
+    through the kicks, with the moment cotangent of every point given to every particle at that point):
+
+        vjp = lynx_amd.grad.track_along_vjp(segment, beam, cavities=True)
+        g = vjp(sigma_x=w, sigma_y=w)            # or mu_bar, cov_bar, energy_bar, readings=, any property of the trace
+        g[segment.Q1]["k1"], g[segment.CAV]["voltage"], g.energy
+        g = vjp(sigma_x=w, wrt_particles=True)   # g.particles (*batch, N, 7), device-resident
+
+    `g.mu` and `g.cov` are None (the gradient is no function of the incoming moments).  One call instead of one
+    `track_vjp` per point on a prefix of the lattice.  At most 64 leaf elements; not together with `trajectories=` or
+    `losses=True`.  A lattice without a cavity is accepted (the same gradients by another way), and with a ParameterBeam
+    `cavities=True` is the plain call.
     """
-    return TrackAlongVJP(segment, beam, trajectories, losses, screens)
+    return TrackAlongVJP(segment, beam, trajectories, losses, screens, cavities)
 
 
 def track_vjp(segment, beam):
