@@ -238,8 +238,12 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
  *   d_p_out          [B][N][7] or NULL: moments only, half the traffic (may alias d_p_in unless that is shared)
  *   d_energy_trace   [B][P]     beam energy at every point, particle dtype
  *   d_trace_out      [B][P][36] float64 moment records, layout of LYNX_MOMENT_STRIDE, slot 34 = 1 (whole triangle)
- * The sums are taken about a reference point that travels with the beam (the sample's first particle, taken through
- * the same maps) and added in a fixed order: the same call returns the same bits.
+ * The sums are taken about a reference point that travels with the beam and added in a fixed order: the same call
+ * returns the same bits.  The point is chosen from 64 candidates per sample -- particle 0 and 63 more at equal strides,
+ * particle floor(l N / 64) for l = 0 .. 63 --: the component-wise median, at the entrance, of the candidates that are
+ * finite there, taken through the same maps.  It is no particle of the beam as a rule.  A record keeps its accuracy
+ * wherever the first particle is stored and however far out a minority of the candidates lies; if no candidate is finite
+ * at the entrance the point is the origin.
  * This entry point and the three below are one call with or without a list of apertures, of screens and of chosen
  * particles: they refuse the same bad arguments (LYNX_ERR_INVALID, before anything is launched; lynx_last_error starts
  * with "beam trace: ", "beam trace with losses: ", "beam trace with screens: " or "beam trace with trajectories: "),
@@ -259,7 +263,11 @@ int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_parti
  * Aperture k tests the particles that ENTER its step (point `step`), by lynx_aperture_mask's comparison; a particle
  * that fails takes no part in the sums of any later point.  Slot 35 of a record is the number of particles alive at
  * that point; a point with none has count 0 and NaN moments.  d_p_out holds every particle, a lost one as far as the
- * maps took it (possibly inf or NaN).  The reference point stays the sample's first particle, lost or not.           */
+ * maps took it (possibly inf or NaN).  The reference point is chosen as above from the candidates that stay ALIVE and
+ * finite to the last point (each is taken through the steps and the apertures of the call): whether a record is
+ * accurate does not depend on the coordinates of particles that are lost before its point.  If no candidate survives
+ * to the end, the median of those that live longest is used; the points behind the one where the last of them is lost
+ * then have a reference point outside the beam, and float32 records there lose digits as its distance in sigmas grows. */
 int lynx_track_particles_along_losses(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                       const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
                                       int32_t n_apertures, const int32_t* apertures, const void* d_limits,
@@ -375,8 +383,10 @@ int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* la
  *   d_lost_at      [B][N] int32, as lynx_track_particles_along_losses wrote it
  *   d_records_out  [B][n_apertures + 1][36] float64, layout of LYNX_MOMENT_STRIDE: mean, biased covariance triangle,
  *                  slot 34 = 1, slot 35 = the set's count (exact); a set without particles has count 0 and NaN moments
- * The sums are taken about the sample's first particle and added in a fixed order, no atomics: the same call returns the
- * same bits.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "moments by loss: ") for a null
+ * The sums are taken about one reference point per sample -- the component-wise median of those of the 64 candidates of
+ * lynx_track_particles_along (particle floor(l N / 64)) that are finite and members of the innermost set any of them is a
+ * member of -- and added in a fixed order, no atomics: the same call returns the same bits.  No finite candidate: the
+ * origin.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "moments by loss: ") for a null
  * pointer, n_particles < 1, or n_apertures outside 1 .. 15.                                                           */
 int lynx_moments_by_loss(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p, int flags,
                          int32_t n_apertures, const int32_t* d_lost_at, double* d_records_out);

@@ -2078,7 +2078,10 @@ __device__ __forceinline__ void write_moment_record(const double* s, double* dst
     while (k >= row) { k -= row; --row; ++i; }
     const int j = i + k;
     // a property-set record (s[34] == 0) carries the variances, cov(x, x') and cov(y, y') only
-    const bool have = s[34] != 0.0 || i == j || (i == 0 && j == 1) || (i == 2 && j == 3);
+    // ... and about a mean that is not finite (a particle at infinity that is still in the beam) a covariance is NaN, as
+    // the centred products of its definition are: the difference below would be NaN or an infinity, by the signs
+    const bool have = (s[34] != 0.0 || i == j || (i == 0 && j == 1) || (i == 2 && j == 3)) &&
+                      __builtin_isfinite(s[i]) && __builtin_isfinite(s[j]);
     dst[tid] = have ? (s[tid] - s[i] * s[j] / n) / n : __longlong_as_double(0x7ff8000000000000ll);
   } else if (tid < 34) {
     dst[tid] = 0.0;

@@ -2535,8 +2535,13 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   const T* ref = (const T*)ctx->scratch_trace[1];
   double* slabs = (double*)ctx->scratch_trace[0];
   if ((ap || sc) && (rc = trace_plan(ctx, S, ap, sc))) return rc;
-  hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
-                     (const T*)d_energy_in, (const T*)d_p_in, a.in_stride, (T*)ctx->scratch_trace[1], (T*)d_energy_trace);
+  // a trace with screens and without an aperture loses nobody: its records are the plain trace's (slot 35 = N)
+  const bool counted = ap && (!sc || ap->count > 0);
+  const TraceLosses loss{(const int64_t*)ctx->scratch_trace_plan, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0,
+                         ap ? ap->d_lost_at : nullptr};
+  hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, dev_view(lat), table, (const T*)d_energy_in,
+                     (const T*)d_p_in, a.in_stride, N, counted ? loss.plan : nullptr, (const T*)loss.limits, loss.limit_stride,
+                     (T*)ctx->scratch_trace[1], (T*)d_energy_trace);
   HIP_TRY(ctx, hipGetLastError());
   // (on the context's stream: a null-stream memset does not wait for what this stream still runs)
   if (sc) HIP_TRY(ctx, hipMemsetAsync(sc->d_images, 0, (size_t)B * sc->cells * sizeof(int32_t), ctx->stream));
@@ -2544,10 +2549,6 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
     HIP_TRY(ctx, hipMemsetAsync(ap->d_lost_at, 0xff, (size_t)B * N * sizeof(int32_t), ctx->stream));
   if (tj && tj->d_lost_in)
     HIP_TRY(ctx, hipMemsetAsync(tj->d_lost_in, 0xff, (size_t)B * tj->count * sizeof(int32_t), ctx->stream));
-  // a trace with screens and without an aperture loses nobody: its records are the plain trace's (slot 35 = N)
-  const bool counted = ap && (!sc || ap->count > 0);
-  const TraceLosses loss{(const int64_t*)ctx->scratch_trace_plan, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0,
-                         ap ? ap->d_lost_at : nullptr};
   const dim3 grid((unsigned)(B * (waves / 4)));
   if (sc) {
     const TraceScreens scr{sc->d_edges, sc->d_misalignment, sc->misalignment_stride, sc->d_images, sc->cells};
@@ -2734,8 +2735,8 @@ static int track_moments_along_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d
   if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
   const int64_t B = lat->batch;
   const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
-  hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
-                     (const T*)d_energy_in, (const T*)nullptr, (int64_t)0, (T*)nullptr, (T*)d_energy_trace);
+  hipLaunchKernelGGL(k_trace_energies<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
+                     (const T*)d_energy_in, (T*)d_energy_trace);
   HIP_TRY(ctx, hipGetLastError());
   // large float32 batches: lanes = samples (float64: 98 registers of covariance per lane, see launch_track_moments)
   if (sizeof(T) == 4 && B >= ctx->knobs.lanes_build_min_batch) {

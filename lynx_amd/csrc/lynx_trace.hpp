@@ -6,11 +6,16 @@
 // element, `beta_x`, `beta_y` of every intermediate beam): 2 E passes over the particle array.  Here:
 //
 //   table      [B][E][64]   every element a step of its own (the existing builders; LYNX_STEP_FLAG_RAW)
-//   k_trace_reference       one lane per sample takes the sample's FIRST particle through the E steps and writes its
-//                           coordinates at every point, [B][P][8], next to the beam energy there, [B][P].  That
-//                           trajectory is the reference point the sums of every point are taken about: it moves with the
-//                           centroid (correctors, misaligned quadrupoles, a cavity's delta), so float32 products do
-//                           not cancel; it is the same for every wave of a sample, so the records add up as they are.
+//   k_trace_reference       one wave per sample takes 64 CANDIDATES (particle 0 and 63 more at equal strides) through the
+//                           E steps and the apertures of the call (none: no walk, every finite candidate counts),
+//                           takes the component-wise median -- at the entrance -- of those that stay alive and finite
+//                           to the end (none does: of those that do longest) through the steps and writes its
+//                           coordinates at every point, [B][P][8], next to
+//                           the beam energy there, [B][P].  That trajectory is the reference point the sums of every
+//                           point are taken about: it moves with the centroid (correctors, misaligned quadrupoles, a
+//                           cavity's delta), so float32 products do not cancel; it lies inside the beam at every point
+//                           whichever particle is stored first and whatever becomes of the lost ones; it is the same
+//                           for every wave of a sample, so the records add up as they are.
 //   k_trace_particles       a wave loads a tile of 64 U particles ONCE, keeps them in registers and takes them through
 //                           the E steps; at every point each lane forms the 28 shifted sums of its U particles
 //                           (6 first moments, the 7th column, 21 products), the wave folds them with a transposing
@@ -84,35 +89,159 @@ struct TraceScreens {
 };
 
 // ---------------------------------------------------------------------------------------
-// k_trace_reference: reference trajectory and energies, one lane per sample.
+// The reference point of a sample's sums.  64 CANDIDATES, one per lane: particle 0 and 63 more at equal strides over the
+// sample (lane l: particle floor(l N / 64); N < 64: some particles more than once).  Every candidate has a score, the
+// number of points (of sets, in k_moments_by_loss) it is a finite, living member of; the candidates of the highest score
+// are the ones that stay in the beam longest, and the reference point is their component-wise median (the lower one of an
+// even number): no particle of the beam as a rule, and none is needed -- k_trace_finalize only adds the point back.  A
+// candidate that is lost, far out or not finite does not move the median of the others; the guarantee ends where fewer
+// than half of the best candidates lie inside the set a record is about.  No candidate finite at the entrance: the origin.
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ int64_t trace_candidate(int lane, int64_t n) { return (n / 64) * lane + (n % 64) * lane / 64; }
+
+template <typename T>
+__device__ __forceinline__ bool trace_finite(const T (&z)[7]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) ok = ok && __builtin_isfinite(z[k]);
+  return ok;
+}
+
+// `v` of the 64 lanes in ascending order, lane by lane: a bitonic network, 21 exchanges (no NaN among them).
+template <typename T>
+__device__ __forceinline__ T trace_wave_sorted(T v, int lane) {
+#pragma unroll
+  for (int k = 2; k <= 64; k <<= 1)
+#pragma unroll
+    for (int j = k >> 1; j >= 1; j >>= 1) {
+      const T other = __shfl_xor(v, j, 64);
+      const bool smaller = ((lane & j) == 0) == ((lane & k) == 0);  // this lane keeps the smaller one of the pair
+      v = smaller ? (other < v ? other : v) : (other > v ? other : v);
+    }
+  return v;
+}
+
+template <typename T>
+__device__ __forceinline__ void trace_reference_median(const T (&z)[7], int score, int lane, T (&c)[6]) {
+  int best = score;
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) best = max(best, __shfl_xor(best, m, 64));
+  const bool mine = best > 0 && score == best;
+  const int members = __popcll(__ballot(mine));
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {  // the others sort behind the set: +inf
+    const T sorted = trace_wave_sorted<T>(mine ? z[k] : T(__builtin_huge_valf()), lane);
+    c[k] = members > 0 ? __shfl(sorted, (members - 1) / 2, 64) : T(0);
+  }
+}
+
+// The rows of the steps s0 .. s0 + kTraceRefChunk - 1 of a sample (as many as there are) into LDS, by one wave: every
+// lane's loads are in flight at once, so a chunk costs one memory latency -- read from memory step by step, the walk
+// below paid one per step (1.2 us each: 0.15 ms for 128 elements).
+constexpr int kTraceRefChunk = 32;
+
+template <typename T>
+__device__ __forceinline__ void trace_stage_steps(const T* __restrict__ sample_steps, int S, int s0, T* __restrict__ rows, int lane) {
+  const int count = min(kTraceRefChunk, S - s0) * LYNX_STEP_STRIDE;
+  const T* src = sample_steps + (int64_t)s0 * LYNX_STEP_STRIDE;
+  __syncthreads();  // (one wave: what it still reads of the chunk before)
+#pragma unroll
+  for (int q = 0; q < kTraceRefChunk; ++q) {
+    const int i = q * 64 + lane;
+    if (i < count) rows[i] = src[i];
+  }
+  __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_reference: reference trajectory and energies, one wave per sample.  With apertures (`plan`, `limits_all`:
+// TraceLosses' of the call) the lanes take the 64 candidates through the S steps and the apertures -- a candidate's score
+// is the number of points it reaches alive and finite --; without them (null) nobody is lost, and the candidates finite
+// at the entrance are the best.  The median of the best AT THE ENTRANCE is taken through the steps, and its coordinates
+// at every point are the reference points, [B][P][8].  Both walks read the steps' rows from LDS, kTraceRefChunk of them
+// staged at a time (trace_stage_steps).
 // Energy behind an active cavity: E + V cos(phi), the expression of energy_before_step (cavity.py:130).
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(64) void k_trace_reference(LatticeDev lat, const T* __restrict__ steps,
                                                         const T* __restrict__ energy_in, const T* __restrict__ p_in,
-                                                        int64_t in_stride, T* __restrict__ ref_out /* null: energies only */,
+                                                        int64_t in_stride, int64_t n_particles,
+                                                        const int64_t* __restrict__ plan, const T* __restrict__ limits_all,
+                                                        int64_t limit_stride, T* __restrict__ ref_out,
                                                         T* __restrict__ energy_trace) {
-  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
-  if (b >= lat.batch) return;
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
   const int S = lat.n_steps, P = S + 1;
   const T* pool = static_cast<const T*>(lat.pool);
-  T z[7] = {T(0), T(0), T(0), T(0), T(0), T(0), T(1)};
-  if (ref_out) load_particle(p_in + b * in_stride, z);
+  const T* sample_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
+  const T* limits = (plan && limits_all) ? limits_all + b * limit_stride : nullptr;
+  T first[7], z[7];
+  load_particle(p_in + b * in_stride + trace_candidate(lane, n_particles) * 7, first);
+#pragma unroll
+  for (int k = 0; k < 7; ++k) z[k] = first[k];
+  __shared__ T s_rows[kTraceRefChunk * LYNX_STEP_STRIDE];
+  __shared__ int s_plan[kTraceRefChunk];
+  // without apertures nobody is lost, and a candidate is as good as it is at the entrance: no walk
+  int score = trace_finite<T>(first) ? 1 : 0;
+  bool alive = true;
+  for (int s = 0; limits && s <= S; ++s) {
+    alive = alive && trace_finite<T>(z);
+    if (alive) score = s + 1;
+    if (s == S) break;
+    if (s % kTraceRefChunk == 0) {  // (the chunk's codes of the plan with its rows)
+      if (lane < min(kTraceRefChunk, S - s)) s_plan[lane] = (int)plan[s + lane];
+      trace_stage_steps<T>(sample_steps, S, s, s_rows, lane);
+    }
+    const int code = __builtin_amdgcn_readfirstlane(s_plan[s % kTraceRefChunk]);
+    if (code >= 0 && !(code & 1))  // an active aperture (TraceLosses.plan)
+      alive = alive && aperture_survives<T>(z[0], z[2], limits[(code >> 2) * 2], limits[(code >> 2) * 2 + 1], (code >> 1) & 1);
+    const T* M = s_rows + (s % kTraceRefChunk) * LYNX_STEP_STRIDE;
+    const int desc = (int)M[LYNX_FLAGS_OFFSET];
+    apply_step<T>(M, (desc >> LYNX_DESC_KIND_SHIFT) & 3, desc & 0xffff, z);
+  }
+  T c[6];
+  trace_reference_median<T>(first, score, lane, c);
+#pragma unroll
+  for (int k = 0; k < 6; ++k) z[k] = c[k];
+  z[6] = T(1);
   T e = energy_in[b];
-  for (int s = 0; s <= S; ++s) {
-    if (ref_out) {
+  for (int s = 0; s <= S; ++s) {  // (every lane the same point; lane 0 writes)
+    if (lane == 0) {
       T* r = ref_out + (b * P + s) * kTraceRef;
 #pragma unroll
       for (int k = 0; k < 7; ++k) r[k] = z[k];
       r[7] = T(0);
+      energy_trace[b * P + s] = e;
     }
-    energy_trace[b * P + s] = e;
     if (s == S) break;
-    const T* M = steps + (b * S + s) * LYNX_STEP_STRIDE;
+    // (a lattice of one chunk is still there from the candidates' walk)
+    if (s % kTraceRefChunk == 0 && (S > kTraceRefChunk || !limits)) trace_stage_steps<T>(sample_steps, S, s, s_rows, lane);
+    const T* M = s_rows + (s % kTraceRefChunk) * LYNX_STEP_STRIDE;
     const int desc = (int)M[LYNX_FLAGS_OFFSET];
     const int skind = (desc >> LYNX_DESC_KIND_SHIFT) & 3, sflags = desc & 0xffff;
-    if (ref_out) apply_step<T>(M, skind, sflags, z);
+    apply_step<T>(M, skind, sflags, z);
     if (skind == LYNX_STEP_CAVITY && (sflags & LYNX_FLAG_CAV_GAIN)) {
+      const lynx_elem el = lat.elems[lat.steps[s].first];
+      const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
+      e = e + p[1] * t_cos(p[2] * T(LYNX_PI / 180.0));
+    }
+  }
+}
+
+// k_trace_energies: the energies alone (a ParameterBeam's trace), one lane per sample.
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_energies(LatticeDev lat, const T* __restrict__ steps,
+                                                       const T* __restrict__ energy_in, T* __restrict__ energy_trace) {
+  const int64_t b = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (b >= lat.batch) return;
+  const int S = lat.n_steps, P = S + 1;
+  const T* pool = static_cast<const T*>(lat.pool);
+  T e = energy_in[b];
+  for (int s = 0; s <= S; ++s) {
+    energy_trace[b * P + s] = e;
+    if (s == S) break;
+    const int desc = (int)steps[(b * S + s) * LYNX_STEP_STRIDE + LYNX_FLAGS_OFFSET];
+    if (((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN)) {
       const lynx_elem el = lat.elems[lat.steps[s].first];
       const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
       e = e + p[1] * t_cos(p[2] * T(LYNX_PI / 180.0));
@@ -586,8 +715,11 @@ __global__ __launch_bounds__(THREADS) void k_trace_finalize(const double* __rest
 // set 0 is everyone.  The kernel is the particle kernel with identity steps whose "points" are the sets: the same grid
 // and wave plan, a tile of 64 U particles in registers with their `lost_at`, per set the 28 shifted sums with a select
 // on `lost_at` (trace_point's masked form), the transposing butterfly, the wave's own float64 slab [A + 1][32]; then
-// k_trace_finalize in its per-point-count mode.  The reference point of every sum is the sample's first particle; wave 0
-// of a sample writes it where the finalizer looks for it, `ref_out` [B][A + 1][kTraceRef].  No atomics, one fixed order.
+// k_trace_finalize in its per-point-count mode.  The reference point of every sum of a sample is the median of the
+// candidates (trace_reference_median) that are finite and members of the innermost set any candidate is a member of -- a
+// point inside every non-empty set that holds a candidate, wherever the lost particles are.  Every wave works it out for
+// itself from `lost_at` (64 loads, the same bits in every wave); wave 0 of a sample writes it where the finalizer looks for
+// it, `ref_out` [B][A + 1][kTraceRef].  No atomics, one fixed order.
 // ---------------------------------------------------------------------------------------
 struct LossSetArgs {
   int64_t n_particles;
@@ -598,8 +730,9 @@ struct LossSetArgs {
 };
 
 template <typename T, int U>
-__device__ __forceinline__ void loss_sets_tile(const LossSetArgs& a, const T* __restrict__ src, const int32_t* __restrict__ lost_at,
-                                               int64_t base, int lane, bool first, double* __restrict__ slab /* of this wave */) {
+__device__ __forceinline__ void loss_sets_tile(const LossSetArgs& a, const T* __restrict__ src, const T* __restrict__ ref /* six scalars */,
+                                               const int32_t* __restrict__ lost_at, int64_t base, int lane, bool first,
+                                               double* __restrict__ slab /* of this wave */) {
   bool inside[U];
   int32_t gone[U];
   T z[U][7];
@@ -626,7 +759,7 @@ __device__ __forceinline__ void loss_sets_tile(const LossSetArgs& a, const T* __
       bool live[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) live[u] = inside[u] && (gone[u] < 0 || gone[u] >= j);
-      trace_point<U, true>(zp, src, live, lane, first, slab + (int64_t)j * kTraceSlab);
+      trace_point<U, true>(zp, ref, live, lane, first, slab + (int64_t)j * kTraceSlab);
     }
   } else {
 #pragma nounroll
@@ -634,7 +767,7 @@ __device__ __forceinline__ void loss_sets_tile(const LossSetArgs& a, const T* __
       bool live[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) live[u] = inside[u] && (gone[u] < 0 || gone[u] >= j);
-      trace_point<U, true>(z, src, live, lane, first, slab + (int64_t)j * kTraceSlab);
+      trace_point<U, true>(z, ref, live, lane, first, slab + (int64_t)j * kTraceSlab);
     }
   }
 }
@@ -648,21 +781,33 @@ __global__ __launch_bounds__(256) void k_moments_by_loss(LossSetArgs a, const T*
   const int w = (int)(blockIdx.x - b * wgs) * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   const int J = a.sets;
-  const T* src = p_in + b * a.in_stride;  // (its first six scalars: the reference point)
+  const T* src = p_in + b * a.in_stride;
   const int32_t* gone = lost_at + b * a.n_particles;
   double* slab = slabs + (b * a.waves + w) * (int64_t)J * kTraceSlab;
-  if (w == 0)
-    for (int i = lane; i < J * kTraceRef; i += 64) ref_out[b * J * kTraceRef + i] = (i & (kTraceRef - 1)) < 6 ? src[i & (kTraceRef - 1)] : T(0);
   constexpr int64_t kTile = 64 * U;
   const int64_t begin = (int64_t)w * a.tiles_per_wave * kTile;
   if (begin >= a.n_particles) {
     for (int64_t i = lane; i < (int64_t)J * kTraceSlab; i += 64) slab[i] = 0.0;
     return;
   }
+  T c[6];
+  {
+    const int64_t at = trace_candidate(lane, a.n_particles);
+    T z[7];
+    load_particle(src + at * 7, z);
+    const int32_t g = gone[at];  // a candidate lost at aperture g is a member of the sets 0 .. g, a survivor of all J
+    trace_reference_median<T>(z, trace_finite<T>(z) ? (g < 0 || g >= J ? J : g + 1) : 0, lane, c);
+  }
+  if (w == 0) {
+    T mine = T(0);
+#pragma unroll
+    for (int k = 0; k < 6; ++k) mine = (lane & (kTraceRef - 1)) == k ? c[k] : mine;
+    for (int i = lane; i < J * kTraceRef; i += 64) ref_out[b * J * kTraceRef + i] = mine;  // (64 is a multiple of kTraceRef)
+  }
   for (int t = 0; t < a.tiles_per_wave; ++t) {
     const int64_t base = begin + t * kTile;
     if (base >= a.n_particles) break;
-    loss_sets_tile<T, U>(a, src, gone, base, lane, t == 0, slab);
+    loss_sets_tile<T, U>(a, src, c, gone, base, lane, t == 0, slab);
   }
 }
 

@@ -100,7 +100,6 @@ def test_the_records_of_the_nested_survivor_sets_against_numpy(lx, dtype, shared
         # a set without particles: NaN moments; the others: finite
         nobody = counts == 0
         assert np.isnan(rec[nobody][:, :28]).all() and np.isfinite(rec[~nobody][:, :28]).all()
-        first = np.broadcast_to(np.asarray(p, dtype=np.float64), (B, n, 7))[:, 0, :6]  # the reference point of the sums
         for b in range(B):
             for j in range(A + 1):
                 if counts[b, j] == 0:
@@ -109,11 +108,13 @@ def test_the_records_of_the_nested_survivor_sets_against_numpy(lx, dtype, shared
                 got_cov = np.array([[rec[b, j, _tri(min(r, c), max(r, c))] for c in range(6)] for r in range(6)])
                 assert rec[b, j, 6] == 1.0
                 if counts[b, j] == 1:
-                    # one particle: what the kernel rounds are its coordinates relative to the reference point and their
-                    # products (the scales of test_gpu_trace_losses.sparse_distances)
-                    e = np.abs(mean[b, j] - first[b])
-                    assert np.all(np.abs(got_mean - mean[b, j]) <= TOL_MOM[dtype] * (np.abs(mean[b, j]) + e)), (n, b, j)
-                    assert np.all(np.abs(got_cov) <= TOL_MOM[dtype] * np.outer(e, e)), (n, b, j)
+                    # one particle, and (a condition on the inputs) one of the 64 reference candidates of include/lynx_hip.h,
+                    # particle floor(l n / 64): the only candidate in the innermost set, hence the reference point of its
+                    # own sums -- its coordinates are the means, and the covariance is 0 exactly, as the oracle's is
+                    member = int(np.flatnonzero((lost_at[b] == -1) | (lost_at[b] >= j))[0])
+                    assert member in {(l * n) // 64 for l in range(64)}, (n, b, j, member)
+                    assert np.all(np.abs(got_mean - mean[b, j]) <= TOL_MOM[dtype] * np.abs(mean[b, j])), (n, b, j)
+                    assert np.all(got_cov == 0), (n, b, j)
                     continue
                 sigma = np.sqrt(np.diag(cov[b, j]))
                 d_mean = np.abs(got_mean - mean[b, j]) / (np.abs(mean[b, j]) + sigma)
