@@ -1372,7 +1372,7 @@ int lynx_build_compose(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
                        void* d_energy_out) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !lat || !d_energy_in || !d_steps_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  if (!lat || !d_energy_in || !d_steps_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
   HIP_TRY(ctx, use_device(ctx));
   ctx->main_dirty = true;
@@ -2004,139 +2004,214 @@ static int ensure_bwd_tasks(lynx_ctx* ctx, lynx_lattice* lat) {
 constexpr int kBwdWgsPerCu = 24;                     // workgroups per CU of the reverse streaming kernels
 constexpr size_t kBwdMapsLdsBytes = (size_t)40 << 10;  // k_build_bwd keeps maps and prefix products in LDS up to this
 
-template <typename T, typename Z = T>
-static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in, const void* d_p_in,
-                            const double* d_moments_fwd, const double* d_grad_moments, void* d_grad_params,
-                            void* d_grad_energy_in, void* d_grad_p_in, const double* d_grad_observations) {
+// What every reverse pass ends with.  A sweep leaves T_bar [B][S][kGradStride] in scratch_grad[1]; k_build_bwd, with its
+// maps and prefix products in scratch_grad[2], turns it into the gradients [B][E][kGradParams] and [B].
+template <typename T>
+static int ensure_tbar_scratch(lynx_ctx* ctx, const lynx_lattice* lat) {
+  const size_t B = (size_t)lat->batch, S = (size_t)lat->n_steps, E = (size_t)lat->n_elems;
+  if (const int rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], B * S * kGradStride * sizeof(T))) return rc;
+  return ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2], B * (2 * E + S + 1) * 49 * sizeof(T));
+}
+
+// `merged`: the sweep walked [run, cavity] pairs as one unit each, k_build_bwd takes their cotangents apart again.
+// `pool_in_args`: the parameters travel in the kernel's arguments (the caller has not brought d_pool up to date).
+template <typename T>
+static int launch_build_bwd(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, void* d_grad_params, void* d_grad_energy_in,
+                            int merged, bool pool_in_args) {
   const int64_t B = lat->batch;
   const int32_t S = lat->n_steps, E = lat->n_elems;
   int rc;
-  // (k_build_bwd reads the parameters: from its arguments if the lattice's pool travels there, from memory otherwise)
-  const bool pool_in_args = lat->prog_pool && ctx->knobs.inline_pool != 0;
-  if (!pool_in_args && (rc = sync_pool(ctx, lat))) return rc;
-  // forward step tables; packed float32 pairs walk [run, cavity] pairs in the merged form of the forward
-  // kernel (LYNX_BWD_MERGE=0: every step on its own), k_build_bwd takes the cotangents apart again
-  constexpr int W = LaneOf<Z>::W;
-  BwdArgs a;
+  if ((rc = ensure_bwd_tasks(ctx, lat))) return rc;
+  // the kind-sorted task list and the elements' kinds, then -- while they fit -- the maps and prefix products
+  size_t lds = build_bwd_lds_fixed<T>(S, E);
+  const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
+  const int maps_in_lds = lds + maps_bytes <= kBwdMapsLdsBytes;
+  if (maps_in_lds) lds += maps_bytes;
+  const auto launch = [&](auto kernel, const auto&... pool) -> int {
+    if (const int refused = allow_lds(ctx, kernel, lds)) return refused;
+    HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(256), lds, ctx->stream, pool..., dev_view(lat), (const T*)d_energy_in,
+                       (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, merged,
+                       maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
+    HIP_TRY(ctx, hipGetLastError());
+    return LYNX_OK;
+  };
+  if (!pool_in_args) return launch(k_build_bwd<T>);
+  if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall)
+    return launch(k_build_bwd_inline<T, kInlinePoolSmall>, *reinterpret_cast<const InlinePool<kInlinePoolSmall>*>(&lat->h_pool));
+  return launch(k_build_bwd_inline<T, kInlinePoolLarge>, lat->h_pool);
+}
+
+// The sweep over the particles (k_track_bwd, k_track_bwd_units, k_track_bwd_inject): a workgroup walks `tiles_per_wg`
+// tiles of kTrackThreads lanes, W particles per lane, `chunks` workgroups per sample; its LDS holds the exchange buffer
+// and the waves' per-step sums.
+template <typename T, int W>
+static size_t bwd_stream_lds_bytes(int32_t S) {
+  return ((size_t)4 * ExRows<W>::value * ExGeom<T, W>::kPitch + (size_t)4 * S * bwd_acc_stride<T>(S)) * sizeof(T);
+}
+
+// (the 64 units fit: 64 float64 steps at the narrow stride take 161088 bytes, 128 float32 steps 162752)
+static int refuse_bwd_stream_lds(lynx_ctx* ctx, const char* what, int32_t S, size_t lds) {
+  if (lds <= 160 * 1024) return LYNX_OK;
+  return fail(ctx, LYNX_ERR_INVALID,
+              std::string(what) + "LDS budget exceeded: " + std::to_string(S) + " steps need " + std::to_string(lds) +
+                  " bytes of the 163840 per workgroup (split the lattice)");
+}
+
+struct BwdSweepPlan {
+  int64_t ntiles, chunks, tiles_per_wg;
+  size_t lds;
+};
+
+template <typename T, int W>
+static BwdSweepPlan plan_bwd_sweep(const lynx_ctx* ctx, int64_t B, int64_t N, int32_t S, BwdArgs* a) {
+  BwdSweepPlan p;
+  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  p.ntiles = (N + kTrackThreads * W - 1) / (kTrackThreads * W);
+  p.chunks = std::max<int64_t>(1, std::min<int64_t>(p.ntiles, ((int64_t)kBwdWgsPerCu * cus + B - 1) / B));
+  p.tiles_per_wg = (p.ntiles + p.chunks - 1) / p.chunks;
+  p.chunks = (p.ntiles + p.tiles_per_wg - 1) / p.tiles_per_wg;
+  p.lds = bwd_stream_lds_bytes<T, W>(S);
+  a->n_particles = N;
+  a->chunks = (int32_t)p.chunks;
+  a->tiles_per_wg = (int32_t)p.tiles_per_wg;
+  return p;
+}
+
+// The units the sweep parks the (s, delta) of: every step one, or (`merge`) a run and the cavity behind it together, at
+// the cavity's slot, in the merged form of the forward kernel; `observers`: the observer steps are numbered.  Returns
+// whether there is a pair -- the `merged` of the step table and of k_build_bwd --, or -1: more units than the kernels park.
+static int plan_bwd_units(const lynx_lattice* lat, bool merge, bool observers, BwdArgs* a) {
+  const int32_t S = lat->n_steps;
   int merged = 0;
-  if (W == 2 && ctx->knobs.bwd_merge)
-    for (int32_t s = 1; s < S; ++s)
-      merged |= lat->h_steps[s].kind == LYNX_STEP_CAVITY && lat->h_steps[s - 1].kind == LYNX_STEP_RUN &&
-                !(lat->h_steps[s - 1].flags & LYNX_STEP_FLAG_OBSERVE);
-  a.n_units = 0;
-  a.n_observers = 0;
-  a.out_chunks = 0;
-  a.n_work = 0;
-  a.leave_odd = ctx->knobs.bwd_units == 2 ? 1 : 0;
+  a->n_units = a->n_observers = a->out_chunks = a->n_work = a->leave_odd = 0;
   for (int32_t s = 0; s < S; ++s) {
-    const bool pair = merged && s + 1 < S && lat->h_steps[s].kind == LYNX_STEP_RUN &&
+    const bool pair = merge && s + 1 < S && lat->h_steps[s].kind == LYNX_STEP_RUN &&
                       lat->h_steps[s + 1].kind == LYNX_STEP_CAVITY && !(lat->h_steps[s].flags & LYNX_STEP_FLAG_OBSERVE);
-    if (pair) ++s;
-    if (a.n_units >= kBwdGroup * kBwdMaxGroups || s > 255)
-      return fail(ctx, LYNX_ERR_INVALID,
-                  "lynx_track_particles_backward: " + std::to_string(S) + " steps; this version parks at most " +
-                      std::to_string(kBwdGroup * kBwdMaxGroups) + " (merge skippable elements or split the lattice)");
-    a.unit_observer[a.n_units] = 0;
-    if (lat->h_steps[s].flags & LYNX_STEP_FLAG_OBSERVE) a.unit_observer[a.n_units] = (unsigned char)(++a.n_observers);
-    a.unit_slot[a.n_units++] = (unsigned char)s;
+    if (pair) merged = 1, ++s;
+    if (a->n_units >= kBwdGroup * kBwdMaxGroups || s > 255) return -1;
+    const bool observed = observers && (lat->h_steps[s].flags & LYNX_STEP_FLAG_OBSERVE);
+    a->unit_observer[a->n_units] = observed ? (unsigned char)(++a->n_observers) : 0;
+    a->unit_slot[a->n_units++] = (unsigned char)s;
   }
-  for (int u = a.n_units; u < kBwdGroup * kBwdMaxGroups; ++u) a.unit_slot[u] = a.unit_observer[u] = 0;
-  // k_track_bwd's exchange buffer and per-step sums (refused here, before anything is launched)
-  const size_t lds = ((size_t)4 * ExRows<W>::value * ExGeom<T, W>::kPitch + (size_t)4 * S * bwd_acc_stride<T>(S)) * sizeof(T);
-  if (lds > 160 * 1024)  // (the 64 units fit: 64 float64 steps at the narrow stride take 161088 bytes, 128 float32 steps 162752)
-    return fail(ctx, LYNX_ERR_INVALID,
-                "lynx_track_particles_backward: LDS budget exceeded: " + std::to_string(S) + " steps need " +
-                    std::to_string(lds) + " bytes of the 163840 per workgroup (split the lattice)");
-  const size_t steps_bytes = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableBwd], &ctx->scratch_steps_bytes[lynx_ctx::kTableBwd], steps_bytes))) return rc;
-  // float32 packed pairs: samples whose units all have class U take the structured reverse kernel (lynx_grad_units.hpp)
-  float* d_units = nullptr;
+  for (int u = a->n_units; u < kBwdGroup * kBwdMaxGroups; ++u) a->unit_slot[u] = a->unit_observer[u] = 0;
+  return merged;
+}
+
+// the workgroups' partial sums [B][chunks][S][kGradStride] -> T_bar in scratch_grad[1]
+template <typename T>
+static int reduce_tbar(lynx_ctx* ctx, const T* partials, int64_t B, int32_t S, int64_t chunks) {
+  if (chunks >= 16) {
+    hipLaunchKernelGGL(k_reduce_tbar<T>, dim3((unsigned)(B * S)), dim3(256), 0, ctx->stream, partials, (int)chunks, (int)S,
+                       (T*)ctx->scratch_grad[1]);
+  } else {  // four rows (sample, step) per wave
+    const int64_t rows = B * S;
+    hipLaunchKernelGGL((k_reduce_tbar_rows<T, 4>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, partials,
+                       (int)chunks, (int)S, rows, (T*)ctx->scratch_grad[1]);
+  }
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+// What a reverse entry point writes for the caller: the gradients of the parameters, of the incoming energy and (if it
+// has them: `ctx->wrote` ignores null) of the incoming moments.
+static void trace_backward_wrote(lynx_ctx* ctx, lynx_lattice* lat, void* d_grad_params, void* d_grad_energy_in,
+                                 void* d_grad_mu_in, void* d_grad_cov_in) {
+  const size_t es = dtype_size(lat->dtype);
+  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
+  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
+  ctx->wrote(d_grad_mu_in, (size_t)lat->batch * 7 * es);
+  ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
+}
+
+// -- the stages of track_backward_t --
+
+// The step table and, for the structured kernel, the unit records the sweep reads.
+struct BwdTable {
+  const void* d_steps = nullptr;
+  float* d_units = nullptr;  // null: no sample takes k_track_bwd_units
   float* d_extras = nullptr;
   bool all_proposed_u = false;  // the plan proposes class U for every unit: only a sample with a non-finite map is left to k_track_bwd
-  if constexpr (W == 2) {
-    if (ctx->knobs.bwd_units) {
-      if ((rc = ensure_units_plan(ctx, lat, merged != 0))) return rc;
-      const UnitPlan& up = lat->units[merged ? 1 : 0];
-      // (the structured kernel parks the (s, delta) entering every unit in registers: up to kBwdUnitsMax units)
-      bool same = lat->units_ok[merged ? 1 : 0] && up.n_units == a.n_units && a.n_units <= kBwdUnitsMax;
-      for (int u = 0; same && u < a.n_units; ++u) same = up.slot[u] == a.unit_slot[u];
-      if (same) {
-        const int64_t n = B * a.n_units;
-        if ((rc = ensure_scratch(ctx, &ctx->scratch_units_bwd[0], &ctx->scratch_units_bwd_bytes[0], (size_t)n * kUnitStride * sizeof(float))) ||
-            (rc = ensure_scratch(ctx, &ctx->scratch_units_bwd[1], &ctx->scratch_units_bwd_bytes[1], (size_t)n * kUnitExtraStride * sizeof(float))))
-          return rc;
-        d_units = (float*)ctx->scratch_units_bwd[0];
-        d_extras = (float*)ctx->scratch_units_bwd[1];
-        all_proposed_u = true;
-        for (int u = 0; u < up.n_units; ++u) all_proposed_u = all_proposed_u && up.cls[u] == kClassU;
-      }
-    }
-  }
-  // the forward call this reverse pass belongs to has built exactly this table (and these unit records) a moment ago:
-  // read them where they are -- and make the slot's next build wait for this reverse pass too
+  int reused_slot = -1;         // the slot of the forward call's table, if that is the one read
+};
+
+// float32 packed pairs: samples whose units all have class U take the structured reverse kernel (lynx_grad_units.hpp),
+// if the lattice's units plan is the sweep's (LYNX_BWD_UNITS=0: never).  Its records go to the reverse pass's own scratch.
+static int bwd_units_records(lynx_ctx* ctx, lynx_lattice* lat, int merged, const BwdArgs& a, BwdTable* t) {
+  int rc;
+  if (!ctx->knobs.bwd_units) return LYNX_OK;
+  if ((rc = ensure_units_plan(ctx, lat, merged != 0))) return rc;
+  const UnitPlan& up = lat->units[merged ? 1 : 0];
+  // (the structured kernel parks the (s, delta) entering every unit in registers: up to kBwdUnitsMax units)
+  bool same = lat->units_ok[merged ? 1 : 0] && up.n_units == a.n_units && a.n_units <= kBwdUnitsMax;
+  for (int u = 0; same && u < a.n_units; ++u) same = up.slot[u] == a.unit_slot[u];
+  if (!same) return LYNX_OK;
+  const int64_t n = lat->batch * a.n_units;
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_units_bwd[0], &ctx->scratch_units_bwd_bytes[0], (size_t)n * kUnitStride * sizeof(float))) ||
+      (rc = ensure_scratch(ctx, &ctx->scratch_units_bwd[1], &ctx->scratch_units_bwd_bytes[1], (size_t)n * kUnitExtraStride * sizeof(float))))
+    return rc;
+  t->d_units = (float*)ctx->scratch_units_bwd[0];
+  t->d_extras = (float*)ctx->scratch_units_bwd[1];
+  t->all_proposed_u = true;
+  for (int u = 0; u < up.n_units; ++u) t->all_proposed_u = t->all_proposed_u && up.cls[u] == kClassU;
+  return LYNX_OK;
+}
+
+// The forward call this reverse pass belongs to has built exactly this table (and these unit records) a moment ago: read
+// them where they are (LYNX_BWD_REUSE_TABLE=0: never).  Otherwise build them into the reverse pass's own.
+template <typename T>
+static int bwd_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, int merged, size_t steps_bytes, BwdTable* t) {
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps;
   std::unique_lock<std::mutex> table_lock(ctx->mu);
   const lynx_ctx::FwdTable ft = ctx->fwd_table;
   table_lock.unlock();
   const bool reuse = ctx->knobs.bwd_reuse_table && ft.valid && ft.lat == lat && ft.version == lat->version &&
                      ft.energy == d_energy_in && ft.seq == ctx->seq && ft.merged == merged &&
                      ctx->scratch_steps_bytes[ft.slot] >= steps_bytes;
-  const void* d_table = ctx->scratch_steps[lynx_ctx::kTableBwd];
-  if (reuse) {
-    d_table = ctx->scratch_steps[ft.slot];
-    if (d_units && ft.units) {
-      d_units = (float*)ctx->scratch_units[ft.slot];
-      d_extras = (float*)ctx->scratch_units[lynx_ctx::kTableSlots + ft.slot];
-    } else if (d_units) {  // the forward call walked the table itself (a single-map program): the records from its rows
-      if constexpr (sizeof(T) == 4) {
-        const UnitPlan& up = lat->units[merged ? 1 : 0];
-        const int64_t n = B * up.n_units;
-        hipLaunchKernelGGL(k_pack_units, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, up, B, S,
-                           (const float*)d_table, d_units, d_extras);
-        HIP_TRY(ctx, hipGetLastError());
-      }
-    }
-  } else if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableBwd], nullptr, merged, false,
-                                   d_units, d_extras))) {
-    return rc;
+  if (!reuse) {
+    t->d_steps = ctx->scratch_steps[lynx_ctx::kTableBwd];
+    return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableBwd], nullptr, merged, false,
+                           t->d_units, t->d_extras);
   }
-  ctx->main_dirty = true;
-
-  // Z: what a lane carries -- one particle, or (float32) two as a packed pair
-  using Geo = ExGeom<T, W>;
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  const int64_t ntiles = (N + kTrackThreads * W - 1) / (kTrackThreads * W);
-  int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(ntiles, ((int64_t)kBwdWgsPerCu * cus + B - 1) / B));
-  const int64_t tpw = (ntiles + chunks - 1) / chunks;
-  chunks = (ntiles + tpw - 1) / tpw;
-  a.n_particles = N;
-  a.chunks = (int32_t)chunks;
-  a.tiles_per_wg = (int32_t)tpw;
-  if ((rc = allow_lds(ctx, k_track_bwd<T, Z>, lds))) return rc;
-  if ((int64_t)B * chunks > 0x7fffffffLL || (int64_t)B * S > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0],
-                           (size_t)B * chunks * S * kGradStride * sizeof(T))))
-    return rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], (size_t)B * S * kGradStride * sizeof(T))))
-    return rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2],
-                           (size_t)B * (2 * E + S + 1) * 49 * sizeof(T))))
-    return rc;
-  LatticeDev lv = dev_view(lat);
-  if constexpr (W == 2) {
-    if (d_units) {
-      const size_t lds_u = bwd_units_lds_bytes(S);
-      if (a.n_units <= 8) {
-        if ((rc = allow_lds(ctx, k_track_bwd_units<8>, lds_u))) return rc;
-        hipLaunchKernelGGL(k_track_bwd_units<8>, dim3((unsigned)(B * chunks)), dim3(kTrackThreads), lds_u, ctx->stream, a, S,
-                           (const float*)d_p_in, (const float*)d_units, (const float*)d_extras, d_moments_fwd, d_grad_moments,
-                           (float*)ctx->scratch_grad[0], (float*)d_grad_p_in);
-      } else {
-        if ((rc = allow_lds(ctx, k_track_bwd_units<kBwdUnitsMax>, lds_u))) return rc;
-        hipLaunchKernelGGL(k_track_bwd_units<kBwdUnitsMax>, dim3((unsigned)(B * chunks)), dim3(kTrackThreads), lds_u, ctx->stream,
-                           a, S, (const float*)d_p_in, (const float*)d_units, (const float*)d_extras, d_moments_fwd,
-                           d_grad_moments, (float*)ctx->scratch_grad[0], (float*)d_grad_p_in);
-      }
+  t->reused_slot = ft.slot;
+  t->d_steps = ctx->scratch_steps[ft.slot];
+  if (t->d_units && ft.units) {
+    t->d_units = (float*)ctx->scratch_units[ft.slot];
+    t->d_extras = (float*)ctx->scratch_units[lynx_ctx::kTableSlots + ft.slot];
+  } else if (t->d_units) {  // the forward call walked the table itself (a single-map program): the records from its rows
+    if constexpr (sizeof(T) == 4) {
+      const UnitPlan& up = lat->units[merged ? 1 : 0];
+      const int64_t n = B * up.n_units;
+      hipLaunchKernelGGL(k_pack_units, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, up, B, S,
+                         (const float*)t->d_steps, t->d_units, t->d_extras);
       HIP_TRY(ctx, hipGetLastError());
+    }
+  }
+  return LYNX_OK;
+}
+
+// The streaming launches: the structured kernel for the samples whose units all have class U, then the dense one.
+template <typename T, typename Z>
+static int launch_bwd_sweep(lynx_ctx* ctx, lynx_lattice* lat, const BwdArgs& a, const BwdSweepPlan& p, const BwdTable& t,
+                            const void* d_p_in, const double* d_moments_fwd, const double* d_grad_moments, void* d_grad_p_in,
+                            const double* d_grad_observations) {
+  constexpr int W = LaneOf<Z>::W;
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps;
+  int rc;
+  if constexpr (W == 2) {
+    if (t.d_units) {
+      const size_t lds_u = bwd_units_lds_bytes(S);
+      const auto launch = [&](auto kernel) -> int {
+        if (const int refused = allow_lds(ctx, kernel, lds_u)) return refused;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(B * p.chunks)), dim3(kTrackThreads), lds_u, ctx->stream, a, S, (const float*)d_p_in,
+                           (const float*)t.d_units, (const float*)t.d_extras, d_moments_fwd, d_grad_moments,
+                           (float*)ctx->scratch_grad[0], (float*)d_grad_p_in);
+        HIP_TRY(ctx, hipGetLastError());
+        return LYNX_OK;
+      };
+      if ((rc = a.n_units <= 8 ? launch(k_track_bwd_units<8>) : launch(k_track_bwd_units<kBwdUnitsMax>))) return rc;
     }
   }
   // Next to k_track_bwd_units this kernel is there for the samples that one left: workgroups of the others return at once --
@@ -2144,69 +2219,77 @@ static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const v
   // U for EVERY unit, only a sample with a non-finite map can be left: ONE workgroup per sample then (it walks all of
   // the sample's tiles, writes row 0 of the sample's partial sums and clears the rest).
   BwdArgs a_dense = a;
-  a_dense.n_work = (int32_t)(B * chunks);
-  int64_t dense_grid = B * chunks;
-  if (d_units && all_proposed_u) {
-    if (chunks > 1) {
-      a_dense.out_chunks = (int32_t)chunks;
+  a_dense.n_work = (int32_t)(B * p.chunks);
+  int64_t dense_grid = B * p.chunks;
+  if (t.d_units && t.all_proposed_u) {
+    if (p.chunks > 1) {
+      a_dense.out_chunks = (int32_t)p.chunks;
       a_dense.chunks = 1;
-      a_dense.tiles_per_wg = (int32_t)ntiles;
+      a_dense.tiles_per_wg = (int32_t)p.ntiles;
     }
     a_dense.n_work = (int32_t)B;
+    const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     dense_grid = std::min<int64_t>(B, 2 * cus);  // (and as many workgroups as are resident at once: they look at B / grid samples each)
   }
-  hipLaunchKernelGGL((k_track_bwd<T, Z>), dim3((unsigned)dense_grid), dim3(kTrackThreads), lds, ctx->stream, lv, a_dense,
-                     (const T*)d_p_in, (const T*)d_table, d_moments_fwd, d_grad_moments,
-                     (T*)ctx->scratch_grad[0], (T*)d_grad_p_in, (const float*)d_units, kUnitStride, kUnitClassShift, (int)kClassU,
-                     d_grad_observations);
+  hipLaunchKernelGGL((k_track_bwd<T, Z>), dim3((unsigned)dense_grid), dim3(kTrackThreads), p.lds, ctx->stream, dev_view(lat), a_dense,
+                     (const T*)d_p_in, (const T*)t.d_steps, d_moments_fwd, d_grad_moments, (T*)ctx->scratch_grad[0],
+                     (T*)d_grad_p_in, (const float*)t.d_units, kUnitStride, kUnitClassShift, (int)kClassU, d_grad_observations);
   HIP_TRY(ctx, hipGetLastError());
-  if (chunks >= 16) {
-    hipLaunchKernelGGL(k_reduce_tbar<T>, dim3((unsigned)(B * S)), dim3(256), 0, ctx->stream, (const T*)ctx->scratch_grad[0],
-                       (int)chunks, (int)S, (T*)ctx->scratch_grad[1]);
-  } else {  // four rows (sample, step) per wave
-    const int64_t rows = B * S;
-    hipLaunchKernelGGL((k_reduce_tbar_rows<T, 4>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream,
-                       (const T*)ctx->scratch_grad[0], (int)chunks, (int)S, rows, (T*)ctx->scratch_grad[1]);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+// The reverse pass of one track call.  Z: what a lane carries -- one particle, or (float32) two as a packed pair.
+template <typename T, typename Z = T>
+static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in, const void* d_p_in,
+                            const double* d_moments_fwd, const double* d_grad_moments, void* d_grad_params,
+                            void* d_grad_energy_in, void* d_grad_p_in, const double* d_grad_observations) {
+  constexpr int W = LaneOf<Z>::W;
+  const int64_t B = lat->batch;
+  const int32_t S = lat->n_steps;
+  int rc;
+  // (k_build_bwd reads the parameters: from its arguments if the lattice's pool travels there, from memory otherwise)
+  const bool pool_in_args = lat->prog_pool && ctx->knobs.inline_pool != 0;
+  if (!pool_in_args && (rc = sync_pool(ctx, lat))) return rc;
+  // the units of the program, and what is refused about them -- here, before anything is built or launched
+  // (packed float32 pairs walk [run, cavity] pairs as one unit; LYNX_BWD_MERGE=0: every step on its own)
+  BwdArgs a;
+  const int merged = plan_bwd_units(lat, W == 2 && ctx->knobs.bwd_merge, true, &a);
+  if (merged < 0)
+    return fail(ctx, LYNX_ERR_INVALID,
+                "lynx_track_particles_backward: " + std::to_string(S) + " steps; this version parks at most " +
+                    std::to_string(kBwdGroup * kBwdMaxGroups) + " (merge skippable elements or split the lattice)");
+  a.leave_odd = ctx->knobs.bwd_units == 2 ? 1 : 0;
+  const BwdSweepPlan p = plan_bwd_sweep<T, W>(ctx, B, N, S, &a);
+  if ((rc = refuse_bwd_stream_lds(ctx, "lynx_track_particles_backward: ", S, p.lds))) return rc;
+  // the units plan for the structured kernel, then the table: the forward call's, or one built here
+  BwdTable t;
+  const size_t steps_bytes = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableBwd], &ctx->scratch_steps_bytes[lynx_ctx::kTableBwd], steps_bytes))) return rc;
+  if constexpr (W == 2)
+    if ((rc = bwd_units_records(ctx, lat, merged, a, &t))) return rc;
+  if ((rc = bwd_table<T>(ctx, lat, d_energy_in, merged, steps_bytes, &t))) return rc;
+  ctx->main_dirty = true;
+  // the sweep over the particles -> partial sums [B][chunks][S][kGradStride] in scratch_grad[0] -> T_bar
+  if ((rc = allow_lds(ctx, k_track_bwd<T, Z>, p.lds))) return rc;
+  if ((int64_t)B * p.chunks > 0x7fffffffLL || (int64_t)B * S > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
+  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (size_t)B * p.chunks * S * kGradStride * sizeof(T))))
+    return rc;
+  if ((rc = ensure_tbar_scratch<T>(ctx, lat))) return rc;
+  if ((rc = launch_bwd_sweep<T, Z>(ctx, lat, a, p, t, d_p_in, d_moments_fwd, d_grad_moments, d_grad_p_in, d_grad_observations))) return rc;
+  if ((rc = reduce_tbar<T>(ctx, (const T*)ctx->scratch_grad[0], B, S, p.chunks))) return rc;
   if constexpr (W == 2) {
-    if (d_units) {  // class-U samples: the units' transverse blocks from the sample's S_x, S_y (lynx_grad_units.hpp)
-      hipLaunchKernelGGL(k_finish_tbar_units, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, S, (const float*)d_units,
+    if (t.d_units) {  // class-U samples: the units' transverse blocks from the sample's S_x, S_y (lynx_grad_units.hpp)
+      hipLaunchKernelGGL(k_finish_tbar_units, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, S, (const float*)t.d_units,
                          (float*)ctx->scratch_grad[1]);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
-  if (reuse) {  // the forward call's table slot has been read up to here: its next build waits for this, too
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_streamed_own[ft.slot], ctx->stream));
-    ctx->ev_streamed[ft.slot] = ctx->ev_streamed_own[ft.slot];
-    ctx->streamed_valid[ft.slot] = true;
+  if (t.reused_slot >= 0) {  // the forward call's table slot has been read up to here: its next build waits for this, too
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_streamed_own[t.reused_slot], ctx->stream));
+    ctx->ev_streamed[t.reused_slot] = ctx->ev_streamed_own[t.reused_slot];
+    ctx->streamed_valid[t.reused_slot] = true;
   }
-  size_t lds2 = build_bwd_lds_fixed<T>(S, E);
-  // maps + prefix products, then the kind-sorted task list and the elements' kinds (unsigned short each)
-  const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
-  if ((rc = ensure_bwd_tasks(ctx, lat))) return rc;
-  const int maps_in_lds = lds2 + maps_bytes <= kBwdMapsLdsBytes;
-  if (maps_in_lds) lds2 += maps_bytes;
-  HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
-  if (pool_in_args && (size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall) {
-    if ((rc = allow_lds(ctx, k_build_bwd_inline<T, kInlinePoolSmall>, lds2))) return rc;
-    hipLaunchKernelGGL((k_build_bwd_inline<T, kInlinePoolSmall>), dim3((unsigned)B), dim3(256), lds2, ctx->stream,
-                       *reinterpret_cast<const InlinePool<kInlinePoolSmall>*>(&lat->h_pool), lv, (const T*)d_energy_in,
-                       (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, merged,
-                       maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
-  } else if (pool_in_args) {
-    if ((rc = allow_lds(ctx, k_build_bwd_inline<T, kInlinePoolLarge>, lds2))) return rc;
-    hipLaunchKernelGGL((k_build_bwd_inline<T, kInlinePoolLarge>), dim3((unsigned)B), dim3(256), lds2, ctx->stream, lat->h_pool, lv,
-                       (const T*)d_energy_in, (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params,
-                       (T*)d_grad_energy_in, merged, maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
-  } else {
-    if ((rc = allow_lds(ctx, k_build_bwd<T>, lds2))) return rc;
-    hipLaunchKernelGGL(k_build_bwd<T>, dim3((unsigned)B), dim3(256), lds2, ctx->stream, lv, (const T*)d_energy_in,
-                       (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, merged,
-                       maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  return LYNX_OK;
+  return launch_build_bwd<T>(ctx, lat, d_energy_in, d_grad_params, d_grad_energy_in, merged, pool_in_args);
 }
 
 int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
@@ -2215,30 +2298,23 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
                                   const double* d_grad_observations) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !lat || !d_energy_in || !d_p_in || !d_moments_fwd || !d_grad_moments || !d_grad_params || !d_grad_energy_in)
+  if (!lat || !d_energy_in || !d_p_in || !d_moments_fwd || !d_grad_moments || !d_grad_params || !d_grad_energy_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (n_particles <= 0 || lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program or beam");
   if (d_grad_observations && lat->n_observers == 0)
     return fail(ctx, LYNX_ERR_INVALID, "d_grad_observations given, but the program has no observer step");
   HIP_TRY(ctx, use_device(ctx));
-  {
-    const int rc = join_side(ctx);  // d_moments_fwd is what a reduction on the side stream writes
-    if (rc) return rc;
-  }
-  const int rc = lat->dtype == LYNX_F64
-             ? track_backward_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_moments_fwd, d_grad_moments,
-                                        d_grad_params, d_grad_energy_in, d_grad_p_in, d_grad_observations)
-         : ctx->knobs.bwd_pairs
-             ? track_backward_t<float, lynx_f32x2>(ctx, lat, n_particles, d_energy_in, d_p_in, d_moments_fwd,
-                                                   d_grad_moments, d_grad_params, d_grad_energy_in, d_grad_p_in,
-                                                   d_grad_observations)
-             : track_backward_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_moments_fwd, d_grad_moments,
-                                       d_grad_params, d_grad_energy_in, d_grad_p_in, d_grad_observations);
-  // the gradients it wrote for the caller (after the reverse pass has read the forward call's table)
-  const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
-  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
-  ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * es);
+  if (const int rc = join_side(ctx)) return rc;  // d_moments_fwd is what a reduction on the side stream writes
+  const auto pass = lat->dtype == LYNX_F64   ? track_backward_t<double, double>
+                    : ctx->knobs.bwd_pairs ? track_backward_t<float, lynx_f32x2>
+                                           : track_backward_t<float, float>;
+  const int rc = pass(ctx, lat, n_particles, d_energy_in, d_p_in, d_moments_fwd, d_grad_moments, d_grad_params, d_grad_energy_in,
+                      d_grad_p_in, d_grad_observations);
+  // The gradients it wrote for the caller, said AFTER the pass: `wrote` invalidates the FwdTable if a block overlaps the
+  // forward call's incoming energy, and the pass reads that table -- said up front, it would build its own instead
+  // (the other reverse passes read no FwdTable: they say it up front).
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
+  ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype));
   return rc;
 }
 
@@ -2247,38 +2323,21 @@ static int moments_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_en
                               const void* d_cov_in, const void* d_mu_bar, const void* d_cov_bar, void* d_grad_params,
                               void* d_grad_energy_in, void* d_grad_mu_in, void* d_grad_cov_in) {
   const int64_t B = lat->batch;
-  const int32_t S = lat->n_steps, E = lat->n_elems;
+  const int32_t S = lat->n_steps;
   int rc;
-  if ((rc = sync_pool(ctx, lat))) return rc;  // (k_moments_bwd reads the parameters from memory)
+  if ((rc = sync_pool(ctx, lat))) return rc;  // (k_moments_bwd and k_build_bwd read the parameters from memory)
   if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableBwd], &ctx->scratch_steps_bytes[lynx_ctx::kTableBwd], (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T))))
     return rc;
   if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableBwd], nullptr))) return rc;
   ctx->main_dirty = true;
   if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (size_t)B * (S + 1) * 56 * sizeof(T))))
     return rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], (size_t)B * S * kGradStride * sizeof(T))))
-    return rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2],
-                           (size_t)B * (2 * E + S + 1) * 49 * sizeof(T))))
-    return rc;
-  LatticeDev lv = dev_view(lat);
-  hipLaunchKernelGGL(k_moments_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, lv, (const T*)ctx->scratch_steps[lynx_ctx::kTableBwd],
+  if ((rc = ensure_tbar_scratch<T>(ctx, lat))) return rc;
+  hipLaunchKernelGGL(k_moments_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, dev_view(lat), (const T*)ctx->scratch_steps[lynx_ctx::kTableBwd],
                      (const T*)d_mu_in, (const T*)d_cov_in, (const T*)d_mu_bar, (const T*)d_cov_bar,
                      (T*)ctx->scratch_grad[0], (T*)ctx->scratch_grad[1], (T*)d_grad_mu_in, (T*)d_grad_cov_in);
   HIP_TRY(ctx, hipGetLastError());
-  size_t lds2 = build_bwd_lds_fixed<T>(S, E);
-  // maps + prefix products, then the kind-sorted task list and the elements' kinds (unsigned short each)
-  const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
-  if ((rc = ensure_bwd_tasks(ctx, lat))) return rc;
-  const int maps_in_lds = lds2 + maps_bytes <= kBwdMapsLdsBytes;
-  if (maps_in_lds) lds2 += maps_bytes;
-  if ((rc = allow_lds(ctx, k_build_bwd<T>, lds2))) return rc;
-  HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
-  hipLaunchKernelGGL(k_build_bwd<T>, dim3((unsigned)B), dim3(256), lds2, ctx->stream, lv, (const T*)d_energy_in,
-                     (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, 0,
-                     maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
-  HIP_TRY(ctx, hipGetLastError());
-  return LYNX_OK;
+  return launch_build_bwd<T>(ctx, lat, d_energy_in, d_grad_params, d_grad_energy_in, 0, false);
 }
 
 int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
@@ -2287,31 +2346,22 @@ int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
                                 void* d_grad_cov_in) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_bar || !d_cov_bar || !d_grad_params ||
+  if (!lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_bar || !d_cov_bar || !d_grad_params ||
       !d_grad_energy_in || !d_grad_mu_in || !d_grad_cov_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program");
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
   HIP_TRY(ctx, use_device(ctx));
-  {
-    const size_t es = dtype_size(lat->dtype);
-    ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
-    ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
-    ctx->wrote(d_grad_mu_in, (size_t)lat->batch * 7 * es);
-    ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
-  }
-  return lat->dtype == LYNX_F64
-             ? moments_backward_t<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_bar, d_cov_bar, d_grad_params,
-                                          d_grad_energy_in, d_grad_mu_in, d_grad_cov_in)
-             : moments_backward_t<float>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_bar, d_cov_bar, d_grad_params,
-                                         d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  const auto pass = lat->dtype == LYNX_F64 ? moments_backward_t<double> : moments_backward_t<float>;
+  return pass(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_bar, d_cov_bar, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
 }
 
 int lynx_moments(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                  double* d_moments_out, int32_t covariance) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_p || !d_moments_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
+  if (!d_p || !d_moments_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (batch <= 0 || n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad shape");
   HIP_TRY(ctx, use_device(ctx));
   LatticeDev lv;
@@ -2382,7 +2432,7 @@ int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
                        const void* d_cov_in, void* d_mu_out, void* d_cov_out, void* d_energy_out) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_out || !d_cov_out)
+  if (!lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_out || !d_cov_out)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   const size_t es = dtype_size(lat->dtype);
   ctx->wrote(d_energy_out, (size_t)lat->batch * es);
@@ -2771,46 +2821,31 @@ int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ene
 
 // ---- reverse pass of the beam trace: gradients of the moments at every point -----------------
 
-constexpr int32_t kTraceBwdMaxSteps = 256;  // k_build_bwd deals the steps of a program to its 256 threads (`if (tid < S)`)
+// The trace's reverse passes refuse longer programs.  k_build_bwd once dealt a program's steps one to each of its 256
+// threads; it walks them in strided loops now, but no sweep of the trace has run beyond 256 points and the header states
+// the refusal: the limit stays.
+constexpr int32_t kTraceBwdMaxSteps = 256;
 
 // What the entry points share.  trace_backward_begin: the trace table and the scratch of T_bar and of k_build_bwd;
 // trace_backward_finish: k_build_bwd on the "every element a step of its own" program over the T_bar a sweep left in
 // scratch_grad[1], then the energy cotangents.
 template <typename T>
 static int trace_backward_begin(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in) {
-  const int64_t B = lat->batch;
-  const int32_t S = lat->n_steps, E = lat->n_elems;
   int rc;
   if ((rc = sync_pool(ctx, lat))) return rc;  // (k_build_bwd and k_trace_energy_bwd read the parameters from memory)
   if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
   ctx->main_dirty = true;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], (size_t)B * S * kGradStride * sizeof(T))))
-    return rc;
-  return ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2], (size_t)B * (2 * E + S + 1) * 49 * sizeof(T));
+  return ensure_tbar_scratch<T>(ctx, lat);
 }
 
 template <typename T>
 static int trace_backward_finish(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_energy_bar,
                                  void* d_grad_params, void* d_grad_energy_in) {
-  const int64_t B = lat->batch;
-  const int32_t S = lat->n_steps, E = lat->n_elems;
-  int rc;
-  const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
-  LatticeDev lv = dev_view(lat);
-  size_t lds2 = build_bwd_lds_fixed<T>(S, E);
-  const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
-  if ((rc = ensure_bwd_tasks(ctx, lat))) return rc;
-  const int maps_in_lds = lds2 + maps_bytes <= kBwdMapsLdsBytes;
-  if (maps_in_lds) lds2 += maps_bytes;
-  if ((rc = allow_lds(ctx, k_build_bwd<T>, lds2))) return rc;
-  HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
-  hipLaunchKernelGGL(k_build_bwd<T>, dim3((unsigned)B), dim3(256), lds2, ctx->stream, lv, (const T*)d_energy_in,
-                     (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, 0,
-                     maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
-  HIP_TRY(ctx, hipGetLastError());
+  if (const int rc = launch_build_bwd<T>(ctx, lat, d_energy_in, d_grad_params, d_grad_energy_in, 0, false)) return rc;
   if (d_energy_bar) {
-    hipLaunchKernelGGL(k_trace_energy_bwd<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, lv, table,
-                       (const T*)d_energy_bar, (T*)d_grad_params, (T*)d_grad_energy_in);
+    hipLaunchKernelGGL(k_trace_energy_bwd<T>, dim3((unsigned)((lat->batch + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat),
+                       (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)d_energy_bar, (T*)d_grad_params,
+                       (T*)d_grad_energy_in);
     HIP_TRY(ctx, hipGetLastError());
   }
   return LYNX_OK;
@@ -2857,16 +2892,6 @@ static int trace_backward_no_cavity(lynx_ctx* ctx, lynx_lattice* lat, const std:
       return fail(ctx, LYNX_ERR_INVALID,
                   what + "step " + std::to_string(s) + " is a cavity step (the particles' moments are not closed under its kick)");
   return LYNX_OK;
-}
-
-// (`ctx->wrote` ignores null: the entry points without gradients of the incoming moments pass none)
-static void trace_backward_wrote(lynx_ctx* ctx, lynx_lattice* lat, void* d_grad_params, void* d_grad_energy_in,
-                                 void* d_grad_mu_in, void* d_grad_cov_in) {
-  const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
-  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
-  ctx->wrote(d_grad_mu_in, (size_t)lat->batch * 7 * es);
-  ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
 }
 
 int lynx_track_moments_along_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
@@ -2949,11 +2974,6 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
 // (k_track_bwd_inject), on the trace's program -- every step a unit of its own --, its partial sums reduced into
 // scratch_grad[1] as track_backward_t reduces them, then the same k_build_bwd.  scratch_grad[0]: the partial sums
 // [B][chunks][S][64], then the injection table [B][P][kInjectStride], both in the lattice's dtype.
-template <typename T, int W>
-static size_t bwd_inject_lds_bytes(int32_t S) {
-  return ((size_t)4 * ExRows<W>::value * ExGeom<T, W>::kPitch + (size_t)4 * S * bwd_acc_stride<T>(S)) * sizeof(T);
-}
-
 template <typename T, typename Z>
 static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in,
                                                const void* d_p_in, int flags, const double* d_trace_fwd,
@@ -2964,27 +2984,13 @@ static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat,
   const int32_t S = lat->n_steps, P = S + 1;
   int rc;
   BwdArgs a;
-  a.n_units = S;
-  a.n_observers = 0;
-  a.out_chunks = 0;
-  a.leave_odd = 0;
-  for (int u = 0; u < kBwdGroup * kBwdMaxGroups; ++u) {
-    a.unit_slot[u] = (unsigned char)(u < S ? u : 0);
-    a.unit_observer[u] = 0;
-  }
-  const size_t lds = bwd_inject_lds_bytes<T, W>(S);
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
-  const int64_t ntiles = (N + kTrackThreads * W - 1) / (kTrackThreads * W);
-  int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(ntiles, ((int64_t)kBwdWgsPerCu * cus + B - 1) / B));
-  const int64_t tpw = (ntiles + chunks - 1) / chunks;
-  chunks = (ntiles + tpw - 1) / tpw;
-  a.n_particles = N;
-  a.chunks = (int32_t)chunks;
-  a.tiles_per_wg = (int32_t)tpw;
-  a.n_work = (int32_t)(B * chunks);
-  if ((int64_t)B * chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients with cavities: grid too large");
-  if ((rc = allow_lds(ctx, k_track_bwd_inject<T, Z>, lds))) return rc;
-  const size_t partial_scalars = (size_t)B * chunks * S * kGradStride, table_scalars = (size_t)B * P * kInjectStride;
+  (void)plan_bwd_units(lat, false, false, &a);  // (the entry point has refused more steps than the sweep parks)
+  const BwdSweepPlan p = plan_bwd_sweep<T, W>(ctx, B, N, S, &a);
+  a.n_work = (int32_t)(B * p.chunks);
+  if ((int64_t)B * p.chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "beam trace gradients with cavities: grid too large");
+  if ((rc = allow_lds(ctx, k_track_bwd_inject<T, Z>, p.lds))) return rc;
+  // (sized before trace_backward_begin, the table launched behind it: what is refused is refused before the build)
+  const size_t partial_scalars = (size_t)B * p.chunks * S * kGradStride, table_scalars = (size_t)B * P * kInjectStride;
   if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (partial_scalars + table_scalars) * sizeof(T))))
     return rc;
   T* partials = (T*)ctx->scratch_grad[0];
@@ -2999,20 +3005,12 @@ static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat,
     HIP_TRY(ctx, hipEventCreateWithFlags(&e0, timing_event_flags(ctx)));
     HIP_TRY(ctx, hipEventCreateWithFlags(&e1, timing_event_flags(ctx)));
   }
-  hipExtLaunchKernelGGL((k_track_bwd_inject<T, Z>), dim3((unsigned)(B * chunks)), dim3(kTrackThreads), (std::uint32_t)lds, ctx->stream,
+  hipExtLaunchKernelGGL((k_track_bwd_inject<T, Z>), dim3((unsigned)(B * p.chunks)), dim3(kTrackThreads), (std::uint32_t)p.lds, ctx->stream,
                         e0, e1, 0u, dev_view(lat), a, (const T*)d_p_in, (flags & LYNX_TRACK_SHARED_INPUT) ? (int64_t)0 : N * 7,
                         (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)inject, partials, (T*)d_grad_p_in);
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->profiling) ctx->prof_events.emplace_back(e0, e1);
-  if (chunks >= 16) {
-    hipLaunchKernelGGL(k_reduce_tbar<T>, dim3((unsigned)(B * S)), dim3(256), 0, ctx->stream, (const T*)partials, (int)chunks, (int)S,
-                       (T*)ctx->scratch_grad[1]);
-  } else {  // four rows (sample, step) per wave
-    const int64_t rows = B * S;
-    hipLaunchKernelGGL((k_reduce_tbar_rows<T, 4>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, (const T*)partials,
-                       (int)chunks, (int)S, rows, (T*)ctx->scratch_grad[1]);
-  }
-  HIP_TRY(ctx, hipGetLastError());
+  if ((rc = reduce_tbar<T>(ctx, partials, B, S, p.chunks))) return rc;
   return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
 }
 
@@ -3033,23 +3031,16 @@ int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* la
   if (lat->n_steps > kBwdGroup * kBwdMaxGroups)
     return refuse(std::to_string(lat->n_steps) + " steps; the sweep over the particles parks at most " +
                   std::to_string(kBwdGroup * kBwdMaxGroups) + " (split the lattice)");
-  {
-    const size_t lds = lat->dtype == LYNX_F64 ? bwd_inject_lds_bytes<double, 1>(lat->n_steps) : bwd_inject_lds_bytes<float, 2>(lat->n_steps);
-    if (lds > 160 * 1024)
-      return refuse("LDS budget exceeded: " + std::to_string(lat->n_steps) + " steps need " + std::to_string(lds) +
-                    " bytes of the 163840 per workgroup (split the lattice)");
-  }
+  const size_t lds = lat->dtype == LYNX_F64 ? bwd_stream_lds_bytes<double, 1>(lat->n_steps) : bwd_stream_lds_bytes<float, 2>(lat->n_steps);
+  if (const int rc = refuse_bwd_stream_lds(ctx, prefix.c_str(), lat->n_steps, lds)) return rc;
   if (d_grad_p_in && d_grad_p_in == d_p_in) return refuse("d_grad_p_in aliases d_p_in: the sweep reads the incoming particles tile by tile");
   HIP_TRY(ctx, use_device(ctx));
   trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
   ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype));
-  return lat->dtype == LYNX_F64
-             ? particles_along_backward_cavities_t<double, double>(ctx, lat, n_particles, d_energy_in, d_p_in, flags, d_trace_fwd,
-                                                                   d_grad_trace, d_energy_bar, d_grad_params, d_grad_energy_in,
-                                                                   d_grad_p_in)
-             : particles_along_backward_cavities_t<float, lynx_f32x2>(ctx, lat, n_particles, d_energy_in, d_p_in, flags, d_trace_fwd,
-                                                                      d_grad_trace, d_energy_bar, d_grad_params, d_grad_energy_in,
-                                                                      d_grad_p_in);
+  const auto pass = lat->dtype == LYNX_F64 ? particles_along_backward_cavities_t<double, double>
+                                           : particles_along_backward_cavities_t<float, lynx_f32x2>;
+  return pass(ctx, lat, n_particles, d_energy_in, d_p_in, flags, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
+              d_grad_energy_in, d_grad_p_in);
 }
 
 // ... of a trace with losses: one wave per (sample, survivor set) propagates the set's incoming moments and sweeps back
@@ -3181,7 +3172,7 @@ int lynx_histogram2d(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particle
                      const void* d_xedges, const void* d_yedges, int32_t nx, int32_t ny, int32_t* d_image) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_p || !d_xedges || !d_yedges || !d_image || batch <= 0 || n_particles <= 0 || nx <= 0 || ny <= 0)
+  if (!d_p || !d_xedges || !d_yedges || !d_image || batch <= 0 || n_particles <= 0 || nx <= 0 || ny <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
   ctx->wrote(d_image, (size_t)batch * nx * ny * sizeof(int32_t));
@@ -3207,7 +3198,7 @@ int lynx_histogram2d(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particle
 int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t packed, float* d_sin, float* d_cos) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_x || !d_sin || !d_cos || n <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad argument");
+  if (!d_x || !d_sin || !d_cos || n <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
   ctx->wrote(d_sin, (size_t)n * sizeof(float));
   ctx->wrote(d_cos, (size_t)n * sizeof(float));
@@ -3225,7 +3216,7 @@ int lynx_aperture_mask(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
                        unsigned char* d_mask, int32_t* d_counts, int64_t* d_offsets, int64_t* d_totals) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_p || !d_x_max || !d_y_max || !d_mask || !d_counts || !d_offsets || !d_totals || batch <= 0 ||
+  if (!d_p || !d_x_max || !d_y_max || !d_mask || !d_counts || !d_offsets || !d_totals || batch <= 0 ||
       n_particles <= 0 || (param_stride != 0 && param_stride != 1))
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
@@ -3254,7 +3245,7 @@ int lynx_aperture_compact(lynx_ctx* ctx, int dtype, int64_t n_particles, const v
                           const int64_t* d_offsets, void* d_kept, void* d_lost) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_p || !d_mask || !d_offsets || !d_kept || !d_lost || n_particles <= 0)
+  if (!d_p || !d_mask || !d_offsets || !d_kept || !d_lost || n_particles <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
   ctx->wrote(d_kept, (size_t)n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
@@ -3274,7 +3265,7 @@ int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_m
                         const void* d_xs, const void* d_ys, int32_t nx, int32_t ny, void* d_image) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_mu || !d_cov || !d_xs || !d_ys || !d_image || batch <= 0 || nx <= 0 || ny <= 0 || batch > 65535)
+  if (!d_mu || !d_cov || !d_xs || !d_ys || !d_image || batch <= 0 || nx <= 0 || ny <= 0 || batch > 65535)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
   ctx->wrote(d_image, (size_t)batch * nx * ny * (dtype == LYNX_F64 ? 8 : 4));
@@ -3406,7 +3397,7 @@ int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
                        const double* sigma, uint64_t seed, void* d_p) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !d_p || !mu || !sigma || batch <= 0 || n_particles <= 0)
+  if (!d_p || !mu || !sigma || batch <= 0 || n_particles <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
   ctx->wrote(d_p, (size_t)batch * n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
@@ -3432,7 +3423,7 @@ int lynx_diag_copy(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes, 
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
   const int per_thread = vec_per_thread >= 100 ? vec_per_thread - 100 : vec_per_thread;  // >= 100: non-temporal stores
-  if (!ctx || !d_dst || !d_src || bytes % 16 || repeats <= 0 || vec_per_thread < 0 || per_thread > 64 ||
+  if (!d_dst || !d_src || bytes % 16 || repeats <= 0 || vec_per_thread < 0 || per_thread > 64 ||
       (vec_per_thread >= 100 && per_thread == 0))
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
   HIP_TRY(ctx, use_device(ctx));
@@ -3522,7 +3513,7 @@ int lynx_comm_info(lynx_ctx* ctx, int32_t* rccl_version, int32_t* n_ranks, int32
 int lynx_gather_moments(lynx_ctx* ctx, const double* d_send, double* d_recv, int64_t count) {
   LYNX_NEED(ctx);
   ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  if (!ctx || !ctx->comm) return fail(ctx, LYNX_ERR_INVALID, "communicator not initialised");
+  if (!ctx->comm) return fail(ctx, LYNX_ERR_INVALID, "communicator not initialised");
   HIP_TRY(ctx, use_device(ctx));
   ctx->wrote(d_recv, (size_t)std::max(1, ctx->comm_ranks) * count * sizeof(double));
   // Default with more than one rank: the side stream.  With one rank (LYNX_FORCE_COMM rehearsals) the "gather" is

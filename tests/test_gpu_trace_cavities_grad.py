@@ -242,6 +242,17 @@ def test_several_tiles_per_workgroup_with_a_partial_last_tile_and_a_shared_beam(
     _compare_with_prefixes(lx, desc, N, f"B = {B}, {tiles} tiles, {per_wg} per workgroup", points=[3, 5], shared=True, B=B)
 
 
+def _seventeen_chunks(lx, N, lane_particles):
+    """B = 2: every tile a workgroup of its own, and 17 of them -- k_reduce_tbar (from 16 chunks up) with a remainder behind its unrolled loop."""
+    tiles, chunks, per_wg = rr.backward_geometry(N, 2, lx.device.get_runtime().info()["compute_units"], lane_particles)
+    assert (tiles, chunks, per_wg) == (17, 17, 1)
+
+
+def test_the_sum_of_prefix_track_vjps_at_seventeen_chunks(lx):
+    _seventeen_chunks(lx, 4097, 1)
+    _compare_with_prefixes(lx, _short(2, GROUP_LAYOUTS[5]), 4097, "N = 4097, 17 chunks, float64")
+
+
 def test_a_shared_incoming_beam(lx):
     _compare_with_prefixes(lx, _short(3, GROUP_LAYOUTS[9]), 700, "shared beam", shared=True, B=3)
 
@@ -278,25 +289,46 @@ def _assert_fp32(got, ref, w_cov, what):
         floor = 1e-4 * max(np.max(np.abs(r)), 1e-9 * np.max(np.abs(w_cov)))
         assert np.all(np.abs(g - r) <= 3e-3 * np.abs(r) + floor), (what, key, g, r)
         worst = max(worst, float(np.max(np.abs(g - r) / (3e-3 * np.abs(r) + floor))))
-    print(f"{what}: worst distance {worst:.2f} of the bound")
+    print(f"{what}: worst distance {worst:.4f} of the bound")
 
 
-@pytest.mark.parametrize("B,N", [(2, 3000), (300, 256)], ids=["workgroup-build", "lanes-build"])
-def test_float32_against_the_float64_pass(lx, B, N):
-    """The lattice, beam and energies of test_merged_pairs_reverse_pass_fp32, cotangents at all ten points."""
+def _both_dtypes(lx, B, N):
+    """
+    The lattice, beam and energies of test_merged_pairs_reverse_pass_fp32, cotangents at all ten points: the gradients of
+    the call in both dtypes, and what they were made from: {dtype: (elements, beam)}, desc, w_mu, w_cov.
+    """
     rng = np.random.default_rng(42)
     desc = _desc(B, rng)
     P = len(desc) + 1
     particles = o.gaussian_particles((B,), N, seed=9, dtype=np.float64, sigma=SIGMA, mu=MU)
     energy = rng.uniform(6e6, 8e6, B)
     w_mu, w_cov = _weights(B, P, 29)
-    out = {}
+    out, made = {}, {}
     for dtype in (np.float64, np.float32):
         elements, _ = make_lattice(desc, dtype, lx)
         beam = lx.ParticleBeam(particles.astype(dtype), energy.astype(dtype), dtype=dtype)
         out[dtype] = _collect(lx.grad.track_along_vjp(lx.Segment(elements), beam, cavities=True)(mu_bar=w_mu, cov_bar=w_cov), desc, elements)
+        made[dtype] = (elements, beam)
     assert sum(v.size for v in out[np.float64].values()) > 50
+    return out, made, desc, w_mu, w_cov
+
+
+@pytest.mark.parametrize("B,N", [(2, 3000), (300, 256)], ids=["workgroup-build", "lanes-build"])
+def test_float32_against_the_float64_pass(lx, B, N):
+    out, _, _, _, w_cov = _both_dtypes(lx, B, N)
     _assert_fp32(out[np.float32], out[np.float64], w_cov, f"float32 against float64, B = {B}, N = {N}")
+
+
+def test_float32_against_the_float64_pass_at_seventeen_chunks(lx):
+    """
+    N = 8193: 17 packed tiles.  The float32 sum of prefix `track_vjp` calls -- a float32 path that knows nothing of this
+    one -- lies within the same bound of the float64 pass: the inputs allow float32 that much.
+    """
+    _seventeen_chunks(lx, 8193, 2)
+    out, made, desc, w_mu, w_cov = _both_dtypes(lx, 2, 8193)
+    _assert_fp32(out[np.float32], out[np.float64], w_cov, "float32 against float64, B = 2, N = 8193")
+    elements, beam = made[np.float32]
+    _assert_fp32(_prefix_sum(lx, desc, elements, beam, w_mu, w_cov), out[np.float64], w_cov, "float32 prefix track_vjps against float64, B = 2, N = 8193")
 
 
 # ---- 5. the incoming particles -----------------------------------------------------------------------------------------------
