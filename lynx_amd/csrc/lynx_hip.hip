@@ -92,7 +92,7 @@ struct lynx_ctx {
   // Every build is followed at once by the main stream's wait on it, so anything enqueued on the
   // main stream later (copies, other kernels, lynx_sync) is ordered after every build so far.  The
   // build stream in turn waits for the main stream when (a) it reuses a table slot (ev_streamed) or
-  // (b) the main stream may have written what the build reads (`main_dirty`, `main_wrote`).
+  // (b) the main stream may have written what the build reads (`main_dirty`, `main_wrote`, `slot_wrote`).
   hipStream_t s_build = nullptr;
   static constexpr int kTableSlots = 3;
   hipEvent_t ev_built[kTableSlots] = {}, ev_streamed_own[kTableSlots] = {}, ev_mark = nullptr;
@@ -128,6 +128,10 @@ struct lynx_ctx {
     }
   } fwd_table;
   const void* main_wrote = nullptr;   // energy buffer the last streaming kernel published on the main stream
+  // ... and the one each table slot's streaming kernel published: a build that reads the energy of a call further back
+  // than the last one (up = U(beam); x = A(beam); y = B(up)) waits for that slot's ev_streamed.  Kernels kTableSlots
+  // calls back have been waited for with the slot itself; a wait for the whole main stream (ev_mark) clears them all.
+  const void* slot_wrote[kTableSlots] = {};
   std::mutex mu;                      // allocator maps and fwd_table: finalizers may run on other threads
   // every entry point that writes device memory on the caller's behalf says so here, under the lock
   void wrote(const void* dst, size_t bytes) {
@@ -1696,6 +1700,13 @@ static int track_table(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, i
       HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_mark, 0));
       ctx->main_dirty = false;
       ctx->main_wrote = nullptr;
+      for (const void*& w : ctx->slot_wrote) w = nullptr;
+    } else {
+      // ... by a streaming kernel further back than the last one: the tail flag says that kernel's last workgroups have
+      // been dispatched, not that they have written the energy
+      for (int i = 0; i < lynx_ctx::kTableSlots; ++i)
+        if (i != slot && ctx->slot_wrote[i] == d_energy_in && d_energy_in && ctx->streamed_valid[i])
+          HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_streamed[i], 0));
     }
   }
   float* d_units_w = nullptr;
@@ -1914,6 +1925,7 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
     ctx->ev_streamed[t.slot] = ctx->last_stream_stop;
     ctx->streamed_valid[t.slot] = t.async && ctx->last_stream_stop != nullptr;
     if (!t.async) ctx->main_dirty = true;
+    ctx->slot_wrote[t.slot] = d_energy_out;
   }
   if (d_energy_out) ctx->main_wrote = d_energy_out;  // a later build that reads it must wait for this kernel
   if (moments) return reduce_moment_records(ctx, B, p.a.chunks, side, ring, d_partials, d_moments_out);

@@ -287,9 +287,11 @@ def test_samples_the_structured_reverse_kernel_leaves_to_the_dense_one(lx, monke
     assert not np.all(np.isfinite(with_dead["particles"][dead]))
 
 
-@pytest.mark.parametrize("dtype,B,N", [(np.float32, 3, 4000), (np.float32, 300, 512), (np.float64, 2, 3000)],
-                         ids=["fp32-workgroup-build", "fp32-lanes-build", "fp64"])
-def test_the_reverse_pass_reads_the_table_of_its_forward_call(lx, monkeypatch, dtype, B, N):
+@pytest.mark.parametrize("dtype,B,N,written", [(np.float32, 3, 4000, False), (np.float32, 300, 512, False), (np.float64, 2, 3000, False),
+                                               (np.float32, 3, 4000, True), (np.float32, 300, 512, True), (np.float64, 2, 3000, True)],
+                         ids=["fp32-workgroup-build", "fp32-lanes-build", "fp64",
+                              "fp32-workgroup-build-k1-written", "fp32-lanes-build-k1-written", "fp64-k1-written"])
+def test_the_reverse_pass_reads_the_table_of_its_forward_call(lx, monkeypatch, dtype, B, N, written):
     """
     A reverse pass that directly follows its forward call (same lattice, incoming energy, merge form; nothing written
     in between) reads the step table and unit records that call built instead of building its own
@@ -297,7 +299,8 @@ def test_the_reverse_pass_reads_the_table_of_its_forward_call(lx, monkeypatch, d
     gradient bit for bit.  What must break the hand-over does: another forward call in between (the slots move on), a
     parameter written in between (the gradient is the one at the NEW value, as it always was), and -- many steps in a
     row, each of them a forward and a reverse pass -- the table slot's next build waits for the reverse pass that
-    still reads it.
+    still reads it.  `written`: the many steps in a row each write k1 of the first quadrupole first, and every step's
+    gradient is the one a reverse pass with its own table gives at that value.
     """
     rng = np.random.default_rng(47)
     f = lambda v: np.full(B, v)  # noqa: E731
@@ -350,6 +353,20 @@ def test_the_reverse_pass_reads_the_table_of_its_forward_call(lx, monkeypatch, d
     runs = [lx.grad.track_vjp(seg, beam)(cov_bar=w_cov) for _ in range(8)]
     for g in runs:
         assert same(flat(g, elements), own_table)
+    if not written:
+        return
+    # ... and with k1 written before every step: each step's gradient against a reverse pass with its own table
+    values = [(k1_old * s).astype(dtype) for s in (-1.0, 0.7, -0.4, 1.3, -1.6, 0.5, -0.9, 1.1)]
+    runs = []
+    for v in values:
+        quad.k1 = v
+        runs.append(lx.grad.track_vjp(seg, beam)(cov_bar=w_cov))
+    runs = [flat(g, elements) for g in runs]
+    monkeypatch.setenv("LYNX_BWD_REUSE_TABLE", "0")
+    for step, (v, got) in enumerate(zip(values, runs)):
+        quad.k1 = v
+        assert same(got, flat(lx.grad.track_vjp(seg, beam)(cov_bar=w_cov), elements)), step
+        assert step == 0 or not same(got, runs[step - 1])
 
 
 def test_gradient_of_linear_lattice_and_broadcast_parameters(lx):
