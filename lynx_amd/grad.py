@@ -17,6 +17,7 @@ All arithmetic runs in the HIP kernels of `lynx_amd/csrc/lynx_grad.hpp`
 from __future__ import annotations
 
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -49,23 +50,19 @@ class Gradients:
     first access.
     """
 
-    def __init__(self, program, raw_dev, energy_dev, batch_shape, energy_shape, particles_dev=None,
-                 mu_dev=None, cov_dev=None, chosen_dev=None, survivors: bool = False, screens=(), screen_shifts_dev=None,
-                 through_kicks: bool = False):
+    # `moments=` of a pass with no incoming moments to differentiate, `mu` and `cov` are None: the survivors of a trace with
+    # losses are no single set of particles, behind a cavity's kick a ParticleBeam's gradient is no function of them
+    NO_INCOMING_MOMENTS = (None, None)
+
+    def __init__(self, program, beam, raw_dev, energy_dev, particles=None, moments=None, chosen=None, screens=None, zeros=()):
+        # what a pass may have besides `[B][E][8]` and the energy's, on the device: `particles`; `moments` = (mu, cov); `chosen`;
+        # `screens` = (the trace's active screens, dL/d(misalignment) `[B][screens][2]` or None: no image took a cotangent);
+        # `zeros`: (element, parameter names) whose gradient is an exact zero
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
-        self._survivors = survivors  # of `track_along_vjp(..., losses=True)`: no single incoming set of particles
-        # of `track_along_vjp(..., cavities=True)` on a ParticleBeam: behind a kick the gradient is no function of the
-        # incoming moments -- `mu`, `cov` are None, `particles` (if asked for) is what there is
-        self._through_kicks = through_kicks
-        self._particles_dev = particles_dev
-        self._mu_dev, self._cov_dev = mu_dev, cov_dev
-        self._chosen_dev = chosen_dev
-        # of `track_along_vjp(..., screens=True)`: the trace's active screens and dL/d(misalignment) [B][screens][2] on the
-        # device (None: no image took a cotangent)
-        self._screens, self._screen_shifts_dev = list(screens), screen_shifts_dev
-        self._batch_shape, self._energy_shape = tuple(batch_shape), tuple(energy_shape)
-        self._raw = None
-        self._cache = {}
+        self._particles_dev, self._moments, self._chosen_dev = particles, moments, chosen
+        self._screens, self._screen_shifts_dev = ([], None) if screens is None else (list(screens[0]), screens[1])
+        self._batch_shape, self._energy_shape = tuple(beam.batch_shape), np.asarray(beam.energy).shape
+        self._zeros, self._raw, self._cache = list(zeros), None, {}
 
     def _host(self):
         if self._raw is None:
@@ -90,20 +87,16 @@ class Gradients:
         dL/d(incoming mu), (*batch, 7) -- ParameterBeam VJPs only; None for the survivors of a trace with losses and for a
         ParticleBeam differentiated through cavities.
         """
-        if self._survivors or self._through_kicks:
-            return None
-        if self._mu_dev is None:
+        if self._moments is None:
             raise KeyError("the gradient w.r.t. mu exists for ParameterBeam VJPs only")
-        return self._mu_dev.numpy()
+        return None if self._moments[0] is None else self._moments[0].numpy()
 
     @property
     def cov(self) -> np.ndarray:
         """dL/d(incoming cov), (*batch, 7, 7), entry by entry -- ParameterBeam VJPs only; None like `mu`."""
-        if self._survivors or self._through_kicks:
-            return None
-        if self._cov_dev is None:
+        if self._moments is None:
             raise KeyError("the gradient w.r.t. cov exists for ParameterBeam VJPs only")
-        return self._cov_dev.numpy()
+        return None if self._moments[1] is None else self._moments[1].numpy()
 
     @property
     def chosen_particles(self) -> np.ndarray:
@@ -116,9 +109,7 @@ class Gradients:
         return self._chosen_dev.numpy()
 
     def __contains__(self, element) -> bool:
-        if self._survivors and any(el is element for _, el, _ in self._program.apertures):
-            return True
-        if any(el is element for el in self._screens):
+        if any(el is element for el, _ in self._zeros) or any(el is element for el in self._screens):
             return True
         return any(el is element and el._kind in DIFFERENTIABLE_KINDS for el in self._program.leaves)
 
@@ -127,9 +118,9 @@ class Gradients:
             return self._cache[id(element)]
         from .accelerator.magnets import RBend
 
-        if self._survivors and any(el is element for _, el, _ in self._program.apertures):
-            # the survivor set is held fixed: the limits that made it get gradient 0
-            return {n: np.zeros(np.asarray(getattr(element, n)).shape) for n in ("x_max", "y_max")}
+        for el, names in self._zeros:
+            if el is element:
+                return {n: np.zeros(np.asarray(getattr(element, n)).shape) for n in names}
         for k, el in enumerate(self._screens):
             if el is element:  # the image sees mu_x - misalignment[0], mu_y - misalignment[1]: minus the mu cotangent there
                 shape = np.asarray(el.misalignment).shape
@@ -162,51 +153,142 @@ class Gradients:
 _COORDINATES = ("x", "xp", "y", "yp", "s", "p")
 
 
-def property_cotangents(outgoing: ParticleBeam, named: dict):
+def _walk_properties(named: dict, shape, what: str, per_plane=(), whole=()):
+    """
+    The one walk over `{property name: cotangent}` of the three rule functions: each cotangent broadcast to `shape` as
+    float64, as ("mu" | "sigma", coordinate, bar) for `mu_<c>` and `sigma_<c>`, ("cross", 0 | 2, bar) for `sigma_xxp` and
+    `sigma_yyp`, (name, 0 | 2, bar) for `<name>_x`, `<name>_y` of a name in `per_plane`, (name, None, bar) for one in `whole`.
+    """
+    for name, bar in named.items():
+        bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), shape)
+        kind, _, coord = name.partition("_")
+        head, _, plane = name.rpartition("_")
+        if kind in ("mu", "sigma") and coord in _COORDINATES:
+            yield kind, _COORDINATES.index(coord), bar
+        elif name in ("sigma_xxp", "sigma_yyp"):
+            yield "cross", 0 if name == "sigma_xxp" else 2, bar
+        elif head in per_plane and plane in ("x", "y"):
+            yield head, 0 if plane == "x" else 2, bar
+        elif name in whole:
+            yield name, None, bar
+        else:
+            raise KeyError(f"no cotangent rule for {what} property {name!r}")
+
+
+def property_cotangents(outgoing, named: dict):
     """
     Cotangents of named beam properties -> (mu_bar, cov_bar).  `mu_<c>`: the mean itself;
     `sigma_<c>` = sqrt(cov_cc n / (n - ddof)) (particle_beam.py:736-823, `config.std_ddof`), so
     d sigma / d cov_cc = n / (n - ddof) / (2 sigma); `sigma_xxp`, `sigma_yyp`: cov_01, cov_23.
+    Of a ParameterBeam, 7 wide: `sigma_<c>` = sqrt(max(cov_cc, 1e-20)) (parameter_beam.py:371-417), 0 where clamped.
     """
     from . import config
 
-    batch = outgoing.batch_shape
-    mu_bar, cov_bar = np.zeros((*batch, 6)), np.zeros((*batch, 6, 6))
-    n = float(outgoing.num_particles)
-    for name, bar in named.items():
-        bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), batch)
-        kind, _, coord = name.partition("_")
-        if kind == "mu" and coord in _COORDINATES:
-            mu_bar[..., _COORDINATES.index(coord)] += bar
-        elif kind == "sigma" and coord in _COORDINATES:
-            c = _COORDINATES.index(coord)
-            sigma = np.asarray(getattr(outgoing, name), dtype=np.float64)
-            cov_bar[..., c, c] += bar * (n / (n - config.std_ddof)) / (2.0 * sigma)
-        elif name in ("sigma_xxp", "sigma_yyp"):
-            c = 0 if name == "sigma_xxp" else 2
+    particles = isinstance(outgoing, ParticleBeam)
+    batch, width = outgoing.batch_shape, 6 if particles else 7
+    mu_bar, cov_bar = np.zeros((*batch, width)), np.zeros((*batch, width, width))
+    for kind, c, bar in _walk_properties(named, batch, "beam"):
+        if kind == "mu":
+            mu_bar[..., c] += bar
+        elif kind == "cross":
             cov_bar[..., c, c + 1] += bar
+        elif particles:  # (by the beam's own property, in the beam's dtype)
+            n, sigma = float(outgoing.num_particles), np.asarray(getattr(outgoing, "sigma_" + _COORDINATES[c]), dtype=np.float64)
+            cov_bar[..., c, c] += bar * (n / (n - config.std_ddof)) / (2.0 * sigma)
         else:
-            raise KeyError(f"no cotangent rule for beam property {name!r}")
+            var = np.asarray(outgoing._cov, dtype=np.float64)[..., c, c]
+            cov_bar[..., c, c] += np.where(var > 1e-20, bar / (2.0 * np.sqrt(np.maximum(var, 1e-20))), 0.0)
     return mu_bar, cov_bar
 
 
-def _reading_cotangents(program, readings: dict, batch_shape) -> np.ndarray | None:
+class _MomentCotangents:
     """
-    `{bpm: cotangent of bpm.reading}` -> [B][observers][2] float64 in the order the program reads them.  A BPM's reading
-    is `stack([mu_x, mu_y])` of the beam that enters it (bpm.py:48-54), shape (2, *batch): so is its cotangent.
+    What every reverse pass assembles first: the cotangents of mean and covariance, entry by entry, as float64 terms (*lead, k)
+    and (*lead, k, k) in the order they came -- `lead` = (B,) behind a lattice, (B, P) for a trace.  Behind a lattice a cotangent
+    is whatever `reshape` takes for the flattened batch (`cov_width`: k where the caller fixes it), for a trace whatever
+    broadcasts to (*batch, P, k): the rules of `track_vjp` and of `track_along_vjp`.
     """
-    if not readings:
-        return None
-    B = int(np.prod(batch_shape, dtype=np.int64))
-    out = np.zeros((B, len(program.observers), 2), dtype=np.float64)
-    known = {id(element): k for k, (_, element) in enumerate(program.observers)}
-    for element, bar in readings.items():
-        if id(element) not in known:
-            raise KeyError(f"{element!r} is not an active BPM of this lattice")
-        bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), (2, *batch_shape))
-        out[:, known[id(element)], 0] += bar[0].reshape(B)
-        out[:, known[id(element)], 1] += bar[1].reshape(B)
-    return out
+
+    def __init__(self, batch_shape, points: int | None = None, cov_width: int | None = None):
+        self.batch_shape, self.cov_width, self.means, self.covariances = tuple(batch_shape), cov_width, [], []
+        self.lead = (math.prod(self.batch_shape), *(() if points is None else (points,)))
+
+    def _term(self, bar: np.ndarray, *tail) -> np.ndarray:
+        if len(self.lead) == 1:
+            return bar.reshape(*self.lead, *tail)
+        return np.broadcast_to(bar, (*self.batch_shape, *self.lead[1:], *tail)).reshape(*self.lead, *tail)
+
+    def add(self, mu_bar=None, cov_bar=None):  # (`cov_bar` not necessarily symmetric; None: no such cotangent)
+        if mu_bar is not None:
+            mu_bar = np.asarray(mu_bar, dtype=np.float64)
+            self.means.append(self._term(mu_bar, -1 if len(self.lead) == 1 else mu_bar.shape[-1]))
+        if cov_bar is not None:
+            cov_bar = np.asarray(cov_bar, dtype=np.float64)
+            k = self.cov_width or cov_bar.shape[-1]
+            self.covariances.append(self._term(cov_bar, k, k))
+
+    def summed(self):
+        """(mb (*lead, 7), cb (*lead, 7, 7)), the caller's own: every term added into zeros, in the order it came."""
+        mb, cb = np.zeros((*self.lead, 7)), np.zeros((*self.lead, 7, 7))
+        for term in self.means:
+            mb[..., : term.shape[-1]] += term
+        for term in self.covariances:
+            cb[..., : term.shape[-1], : term.shape[-1]] += term
+        return mb, cb
+
+    def chained(self):  # (mean's, covariance's): one term to the next, None for none; a single one AS IT CAME -- no copy, no `-0.0` lost
+        return tuple(sum(terms[1:], terms[0]) if terms else None for terms in (self.means, self.covariances))
+
+
+def _known_bpm(element, known: bool):
+    if not known:
+        raise KeyError(f"{element!r} is not an active BPM of this lattice")
+
+
+def _reading_bar(bar, batch_shape) -> np.ndarray:  # (2, B): a BPM reads `stack([mu_x, mu_y])` of the beam entering it (bpm.py:48-54)
+    return np.broadcast_to(np.asarray(bar, dtype=np.float64), (2, *batch_shape)).reshape(2, -1)
+
+
+def _add_reading(mb: np.ndarray, bar, batch_shape, *point):  # ... into the mean's cotangent, at `point` of a trace
+    bar = _reading_bar(bar, batch_shape)
+    mb[(slice(None), *point, 0)] += bar[0]
+    mb[(slice(None), *point, 2)] += bar[1]
+
+
+_TRIANGLE = [(7 + n, int(i), int(j)) for n, (i, j) in enumerate(zip(*np.triu_indices(6)))]  # (slot of a record, i, j): `_tri`
+
+
+def _record_cotangents(lead: tuple, mb, cb) -> np.ndarray:
+    """
+    Cotangents of mean (*lead, k) and covariance (*lead, 6|7, 6|7), entry by entry (None: none), as record cotangents
+    (*lead, 36): [0..k) the mean's, [7..27] the upper triangle in `_tri`'s order, an off-diagonal entry counted once.  The only
+    place that packs records -- slot by slot: at a batch of thousands a gather of the triangle costs three times as much (it
+    wrote (G + G) * 0.5 on the diagonal: the bits of G for every finite G below half the largest float64).
+    """
+    rec = np.zeros((*lead, _ffi.MOMENT_STRIDE), dtype=np.float64)
+    if mb is not None:
+        rec[..., : mb.shape[-1]] = mb
+    if cb is not None:
+        slots, G = rec.reshape(-1, _ffi.MOMENT_STRIDE), cb.reshape(-1, *cb.shape[-2:])  # (views of two and three dimensions: indexed the fastest)
+        for slot, i, j in _TRIANGLE:
+            slots[:, slot] = G[:, i, i] if i == j else G[:, i, j] + G[:, j, i]
+    return rec
+
+
+def _p(array):  # a device array, or None, as a library call takes it
+    return None if array is None else C.c_void_p(array.ptr)
+
+
+class _Sweep:
+    """What every sweep of the moment recursion is given besides its cotangents: lattice, incoming energy, outputs in HBM."""
+
+    def __init__(self, rt, cache, program, beam):
+        batch_shape, dtype = beam.batch_shape, beam.dtype
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        self.lat = engine._ready(cache, program, batch_shape, dtype, beam._energy._host)
+        self.g_par, self.g_en = rt.empty((B, max(self.lat.E, 1), 8), dtype), rt.empty((B,), dtype)
+        self.g_mu, self.g_cov = rt.empty((*batch_shape, 7), dtype), rt.empty((*batch_shape, 7, 7), dtype)
+        self.e_in = beam._energy.broadcast_device(rt, batch_shape)
 
 
 class TrackVJP:
@@ -235,37 +317,36 @@ class TrackVJP:
         rt = get_runtime()
         beam, program = self.beam, self.program
         batch_shape, dtype = beam.batch_shape, beam.dtype
-        B = int(np.prod(batch_shape, dtype=np.int64))
-        if properties:
-            extra_mu, extra_cov = property_cotangents(self.outgoing, properties)
-            mu_bar = extra_mu if mu_bar is None else extra_mu + np.asarray(mu_bar, dtype=np.float64).reshape(extra_mu.shape)
-            cov_bar = extra_cov if cov_bar is None else extra_cov + np.asarray(cov_bar, dtype=np.float64).reshape(extra_cov.shape)
-        rec = np.zeros((B, _ffi.MOMENT_STRIDE), dtype=np.float64)
-        if mu_bar is not None:
-            mu_bar = np.asarray(mu_bar, dtype=np.float64).reshape(B, -1)
-            rec[:, : mu_bar.shape[1]] = mu_bar
-        if cov_bar is not None:
-            G = np.asarray(cov_bar, dtype=np.float64).reshape(B, 6, 6)
-            for i in range(6):
-                rec[:, _tri(i, i)] = G[:, i, i]
-                for j in range(i + 1, 6):
-                    rec[:, _tri(i, j)] = G[:, i, j] + G[:, j, i]
+        bars = _MomentCotangents(batch_shape, cov_width=6)
+        if properties:  # (beside them a cotangent has their shape; alone a mean's is as wide as it comes)
+            pm, pc = property_cotangents(self.outgoing, properties)
+            bars.add(pm, pc)
+            bars.add(None if mu_bar is None else np.asarray(mu_bar, dtype=np.float64).reshape(pm.shape),
+                     None if cov_bar is None else np.asarray(cov_bar, dtype=np.float64).reshape(pc.shape))
+        else:
+            bars.add(mu_bar, cov_bar)
+        B = bars.lead[0]
         lat = engine._ready(self.cache, program, batch_shape, dtype, beam._energy._host)
-        E = lat.E
-        # (cotangents in and gradients out: small ones live in host memory the GPU reads and writes through)
-        g_rec = rt.to_device_result(rec)
-        g_par = rt.empty_result((B, max(E, 1), 8), dtype)
+        # What differs from the sweeps of the moment recursion below, on purpose: this call is bound by the host (one per step
+        # of an optimisation), so cotangents in and gradients out live in host memory the GPU reads and writes through ...
+        g_rec = rt.to_device_result(_record_cotangents(bars.lead, *bars.chained()))
+        g_par = rt.empty_result((B, max(lat.E, 1), 8), dtype)
         g_en = rt.empty_result((B,), dtype)
         g_p = rt.empty((*batch_shape, beam.num_particles, 7), dtype) if wrt_particles else None
         fwd = self.outgoing._moments.device(rt)
         e_in = beam._energy.broadcast_device(rt, batch_shape)
-        obs_bar = _reading_cotangents(program, readings, batch_shape)
-        g_obs = None if obs_bar is None else rt.to_device_result(obs_bar)  # (named: alive until the call has been enqueued)
+        g_obs = None  # ... and the kernel reads the BPMs inside the pass: their cotangents go to its table [B][observers][2]
+        if readings:
+            obs_bar = np.zeros((B, len(program.observers), 2), dtype=np.float64)
+            known = {id(element): k for k, (_, element) in enumerate(program.observers)}
+            for element, bar in readings.items():
+                _known_bpm(element, id(element) in known)
+                obs_bar[:, known[id(element)], :] += _reading_bar(bar, batch_shape).T
+            g_obs = rt.to_device_result(obs_bar)
         rt.check(rt.lib.lynx_track_particles_backward(
-            rt.ctx, lat.handle, beam.num_particles, C.c_void_p(e_in.ptr), C.c_void_p(beam._particles.device(rt).ptr),
-            C.c_void_p(fwd.ptr), C.c_void_p(g_rec.ptr), C.c_void_p(g_par.ptr), C.c_void_p(g_en.ptr),
-            None if g_p is None else C.c_void_p(g_p.ptr), None if g_obs is None else C.c_void_p(g_obs.ptr)))
-        return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, g_p)
+            rt.ctx, lat.handle, beam.num_particles, _p(e_in), _p(beam._particles.device(rt)), _p(fwd), _p(g_rec), _p(g_par),
+            _p(g_en), _p(g_p), _p(g_obs)))
+        return Gradients(program, beam, g_par, g_en, particles=g_p)
 
 
 class ChainedGradients:
@@ -330,44 +411,15 @@ class MomentsVJP:
         self.beam = self.stretches[0][1] if self.stretches else beam
         self.outgoing = beam
 
-    def _property_cotangents(self, named: dict):
-        """`mu_<c>`: mu[c]; `sigma_<c>` = sqrt(max(cov_cc, 1e-20)) (parameter_beam.py:371-417); `sigma_xxp/yyp`: cov_01, cov_23."""
-        out = self.outgoing
-        batch = out.batch_shape
-        mu_bar, cov_bar = np.zeros((*batch, 7)), np.zeros((*batch, 7, 7))
-        for name, bar in named.items():
-            bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), batch)
-            kind, _, coord = name.partition("_")
-            if kind == "mu" and coord in _COORDINATES:
-                mu_bar[..., _COORDINATES.index(coord)] += bar
-            elif kind == "sigma" and coord in _COORDINATES:
-                c = _COORDINATES.index(coord)
-                var = np.asarray(out._cov, dtype=np.float64)[..., c, c]
-                cov_bar[..., c, c] += np.where(var > 1e-20, bar / (2.0 * np.sqrt(np.maximum(var, 1e-20))), 0.0)
-            elif name in ("sigma_xxp", "sigma_yyp"):
-                c = 0 if name == "sigma_xxp" else 2
-                cov_bar[..., c, c + 1] += bar
-            else:
-                raise KeyError(f"no cotangent rule for beam property {name!r}")
-        return mu_bar, cov_bar
-
     def _stretch(self, program, beam, mb, cb) -> Gradients:
         rt = get_runtime()
-        batch_shape, dtype = beam.batch_shape, beam.dtype
-        B = int(np.prod(batch_shape, dtype=np.int64))
-        lat = engine._ready(self.cache, program, batch_shape, dtype, beam._energy._host)
-        g_par = rt.empty((B, max(lat.E, 1), 8), dtype)
-        g_en = rt.empty((B,), dtype)
-        g_mu = rt.empty((*batch_shape, 7), dtype)
-        g_cov = rt.empty((*batch_shape, 7, 7), dtype)
-        e_in = beam._energy.broadcast_device(rt, batch_shape)
-        p = lambda a: C.c_void_p(a.ptr)  # noqa: E731
+        sweep = _Sweep(rt, self.cache, program, beam)
         # named, so that both uploads stay allocated until the call has been enqueued
-        mb_dev, cb_dev = rt.to_device(mb.astype(dtype)), rt.to_device(cb.astype(dtype))
+        mb_dev, cb_dev = rt.to_device(mb.astype(beam.dtype)), rt.to_device(cb.astype(beam.dtype))
         rt.check(rt.lib.lynx_track_moments_backward(
-            rt.ctx, lat.handle, p(e_in), p(beam._mu_d.device(rt)), p(beam._cov_d.device(rt)),
-            p(mb_dev), p(cb_dev), p(g_par), p(g_en), p(g_mu), p(g_cov)))
-        return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
+            rt.ctx, sweep.lat.handle, _p(sweep.e_in), _p(beam._mu_d.device(rt)), _p(beam._cov_d.device(rt)),
+            _p(mb_dev), _p(cb_dev), _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
+        return Gradients(program, beam, sweep.g_par, sweep.g_en, moments=(sweep.g_mu, sweep.g_cov))
 
     def __call__(self, mu_bar=None, cov_bar=None, readings: dict | None = None, **properties):
         """
@@ -375,36 +427,25 @@ class MomentsVJP:
         of the readings of active BPMs, shaped like `bpm.reading` -- (2, *batch).
         """
         batch_shape = self.outgoing.batch_shape
-        B = int(np.prod(batch_shape, dtype=np.int64))
-        mb, cb = np.zeros((B, 7)), np.zeros((B, 7, 7))
+        bars = _MomentCotangents(batch_shape)
         if properties:
-            pm, pc = self._property_cotangents(properties)
-            mb += pm.reshape(B, 7)
-            cb += pc.reshape(B, 7, 7)
-        if mu_bar is not None:
-            mu_bar = np.asarray(mu_bar, dtype=np.float64).reshape(B, -1)
-            mb[:, : mu_bar.shape[1]] += mu_bar
-        if cov_bar is not None:
-            cov_bar = np.asarray(cov_bar, dtype=np.float64)
-            k = cov_bar.shape[-1]
-            cb[:, :k, :k] += cov_bar.reshape(B, k, k)
+            bars.add(*property_cotangents(self.outgoing, properties))
+        bars.add(mu_bar, cov_bar)
+        mb, cb = bars.summed()
         readings = dict(readings or {})
-        known = {id(item): item for item, beam in self.stretches if beam is None}
         for element in readings:
-            if id(element) not in known:
-                raise KeyError(f"{element!r} is not an active BPM of this lattice")
+            _known_bpm(element, any(element is item for item, beam in self.stretches if beam is None))
         parts = []
         for item, beam in reversed(self.stretches):
-            if beam is None:  # an active BPM: its reading is (mu_x, mu_y) of the beam passing here
+            if beam is None:  # an active BPM cuts the lattice here: its reading joins what the stretch in front is given
                 for element, bar in readings.items():
                     if element is item:
-                        bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), (2, *batch_shape))
-                        mb[:, 0] += bar[0].reshape(B)
-                        mb[:, 2] += bar[1].reshape(B)
+                        _add_reading(mb, bar, batch_shape)
                 continue
             part = self._stretch(item, beam, mb, cb)
             parts.insert(0, part)
-            mb, cb = np.asarray(part.mu, dtype=np.float64).reshape(B, 7), np.asarray(part.cov, dtype=np.float64).reshape(B, 7, 7)
+            mb = np.asarray(part.mu, dtype=np.float64).reshape(*bars.lead, 7)
+            cb = np.asarray(part.cov, dtype=np.float64).reshape(*bars.lead, 7, 7)  # (what the stretch in front is given)
         if not parts:
             raise ValueError("track_vjp: the lattice has no element to differentiate")
         return parts[0] if len(parts) == 1 else ChainedGradients(parts)
@@ -479,24 +520,20 @@ def trace_property_cotangents(trace, named: dict):
         acc["p2"] += w * s2
         acc["cross"] += -2.0 * w * cross
 
-    for name, bar in named.items():
-        bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), shape)
-        kind, _, coord = name.partition("_")
-        if name == "energy":
+    for kind, a, bar in _walk_properties(named, shape, "trace", ("emittance", "normalized_emittance", "beta", "alpha"), ("energy",)):
+        if kind == "energy":
             energy_bar += bar
-        elif kind == "mu" and coord in _COORDINATES:
-            mu_bar[..., _COORDINATES.index(coord)] += bar
-        elif kind == "sigma" and coord in _COORDINATES:
-            c = _COORDINATES.index(coord)
-            s2, ds2 = sigma_squared(c)
+        elif kind == "mu":
+            mu_bar[..., a] += bar
+        elif kind == "sigma":
+            s2, ds2 = sigma_squared(a)
             with np.errstate(all="ignore"):
-                cov_bar[..., c, c] += np.where(ds2 != 0, bar * ds2 / (2.0 * np.sqrt(s2)), 0.0)
-        elif name in ("sigma_xxp", "sigma_yyp"):
-            plane(0 if name == "sigma_xxp" else 2)["cross"] += bar
-        elif name in ("emittance_x", "emittance_y"):
-            emittance_bar(0 if name.endswith("x") else 2, bar)
-        elif name in ("normalized_emittance_x", "normalized_emittance_y"):
-            a = 0 if name.endswith("x") else 2
+                cov_bar[..., a, a] += np.where(ds2 != 0, bar * ds2 / (2.0 * np.sqrt(s2)), 0.0)
+        elif kind == "cross":
+            plane(a)["cross"] += bar
+        elif kind == "emittance":
+            emittance_bar(a, bar)
+        elif kind == "normalized_emittance":
             gamma = np.asarray(trace.energy, dtype=np.float64) / engine.ELECTRON_MASS_EV
             moving = np.abs(gamma) > 0
             with np.errstate(all="ignore"):
@@ -504,18 +541,14 @@ def trace_property_cotangents(trace, named: dict):
                 dbg = np.where(moving, gamma / np.sqrt(gamma**2 - 1), 0.0) / engine.ELECTRON_MASS_EV
             emittance_bar(a, bar * bg)
             energy_bar += bar * emittance(a)[0] * dbg
-        elif name in ("beta_x", "beta_y"):
-            a = 0 if name.endswith("x") else 2
+        elif kind == "beta":
             eps, _, s2, _, _ = emittance(a)
             plane(a)["s2"] += bar / eps
             emittance_bar(a, -bar * s2 / eps**2)
-        elif name in ("alpha_x", "alpha_y"):
-            a = 0 if name.endswith("x") else 2
+        else:  # alpha
             eps, _, _, _, cross = emittance(a)
             plane(a)["cross"] += -bar / eps
             emittance_bar(a, bar * cross / eps**2)
-        else:
-            raise KeyError(f"no cotangent rule for trace property {name!r}")
     for a, acc in plane_bars.items():
         cov_bar[..., a, a] += acc["s2"] * sigma_squared(a)[1]
         cov_bar[..., a + 1, a + 1] += acc["p2"] * sigma_squared(a + 1)[1]
@@ -523,16 +556,76 @@ def trace_property_cotangents(trace, named: dict):
     return mu_bar, cov_bar, energy_bar
 
 
-def _record_cotangents(mb: np.ndarray, cb: np.ndarray) -> np.ndarray:
+def _refuse_moments(cavity: str):
+    raise NotImplementedError(
+        f"track_along_vjp: active Cavity {cavity!r} -- the moments of a ParticleBeam are not "
+        "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated, and so is this beam by a "
+        "second pass over its particles: track_along_vjp(..., cavities=True)")
+
+
+def _trace_mode(segment, beam, trajectories, losses, screens, cavities):
     """
-    Cotangents of mean (B, P, 7) and covariance (B, P, 7, 7), entry by entry, as record cotangents (B, P, 36): [0..6] the
-    mean's, [7..27] the upper triangle in the record's order (`_tri`), an off-diagonal entry counted once.
+    Every refusal of `track_along_vjp` by value, before anything touches the GPU -> (mode, the trace's program, the leaf
+    elements, the chosen particles or None, the name of the active cavity that stops this beam's moment cotangents or None).
     """
-    rec = np.zeros((*mb.shape[:2], _ffi.MOMENT_STRIDE), dtype=np.float64)
-    rec[..., :7] = mb
-    rows, cols = np.triu_indices(6)
-    rec[..., 7:28] = (cb[..., rows, cols] + cb[..., cols, rows]) * np.where(rows == cols, 0.5, 1.0)
-    return rec
+    from .particles.parameter_beam import ParameterBeam
+
+    if not isinstance(beam, (ParameterBeam, ParticleBeam)):
+        raise TypeError(f"track_along_vjp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
+    for name, flag in (("losses", losses), ("screens", screens), ("cavities", cavities)):
+        if not isinstance(flag, (bool, np.bool_)):
+            raise ValueError(f"track_along_vjp: {name} is True or False, not {flag!r}")
+    if cavities and (trajectories is not None or losses):
+        raise NotImplementedError(
+            "track_along_vjp: cavities=True together with " + ("trajectories=" if trajectories is not None else "losses=True")
+            + " -- the second pass over the particles differentiates the moments of the whole beam alone; ask for one of "
+            "the two")
+    particles = isinstance(beam, ParticleBeam)
+    if screens and particles:
+        raise TypeError(
+            "track_along_vjp: screens=True with a ParticleBeam -- its screen image is a histogram of counts, a step "
+            "function of the magnets whose gradient is zero almost everywhere; a ParameterBeam of the same moments "
+            "(its image is a smooth density) is differentiated")
+    if losses and trajectories is not None:
+        raise NotImplementedError(
+            "track_along_vjp: losses=True together with trajectories= -- the trajectories of a trace with losses are "
+            "not differentiated; ask for one of the two")
+    chosen = None if trajectories is None else engine.chosen_particles(trajectories, beam)
+    leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
+    # (raises for an active Screen -- and, without `losses`, for an active Aperture --, naming it)
+    program = engine._trace_plan(segment, leaves, bool(losses), True) if screens else engine._trace_plan(segment, leaves, bool(losses))
+    B = int(np.prod(beam.batch_shape, dtype=np.int64))
+    if screens and program.screens and B > _ffi.MAX_IMAGE_BATCH:  # (as lynx_gaussian_images_along refuses it)
+        raise _ffi.LynxError(
+            f"track_along_vjp: screens=True with a batch of {B} samples, more than {_ffi.MAX_IMAGE_BATCH} -- "
+            "lynx_gaussian_images_along takes a sample per row of its launch grid (bad argument); trace the batch in parts")
+    # survivors: a ParticleBeam and an active aperture; anything else with `losses` is the plain problem (nobody is lost)
+    if not particles:
+        mode = "moments"
+    elif losses and len(program.apertures) > 0:
+        mode = "survivors"
+    else:
+        mode = "kicks" if cavities else "particles" if chosen is None else "trajectories"
+        program = engine._trace_plan(segment, leaves)
+    if mode == "survivors" and len(program.apertures) > MAX_TRACE_LOSS_APERTURES:
+        raise NotImplementedError(
+            f"track_along_vjp: {len(program.apertures)} active apertures, more than {MAX_TRACE_LOSS_APERTURES} (the "
+            f"first one beyond is {program.apertures[MAX_TRACE_LOSS_APERTURES][1].name!r}) -- differentiate the "
+            "lattice in stretches")
+    if len(leaves) > MAX_TRACE_LEAVES:
+        raise NotImplementedError(
+            f"track_along_vjp: {len(leaves)} leaf elements, more than {MAX_TRACE_LEAVES} (the first one beyond is "
+            f"{leaves[MAX_TRACE_LEAVES].name!r}) -- differentiate the lattice in stretches")
+    if mode == "kicks" and len(leaves) > MAX_TRACE_CAVITY_LEAVES:
+        raise NotImplementedError(
+            f"track_along_vjp: cavities=True with {len(leaves)} leaf elements, more than {MAX_TRACE_CAVITY_LEAVES} (the first "
+            f"one beyond is {leaves[MAX_TRACE_CAVITY_LEAVES].name!r}) -- differentiate the lattice in stretches")
+    # the first active cavity in front of a ParticleBeam: no moment cotangent passes it but through the kicks
+    cavities_at = [first for kind, first, _ in program.steps if kind == _ffi.STEP_CAVITY] if particles and mode != "kicks" else []
+    cavity = leaves[cavities_at[0]].name if cavities_at else None
+    if cavity is not None and chosen is None:
+        _refuse_moments(cavity)
+    return mode, program, leaves, chosen, cavity
 
 
 class TrackAlongVJP:
@@ -555,83 +648,15 @@ class TrackAlongVJP:
     """
 
     def __init__(self, segment, beam, trajectories=None, losses=False, screens=False, cavities=False):
-        from .particles.parameter_beam import ParameterBeam
-
-        if not isinstance(beam, (ParameterBeam, ParticleBeam)):
-            raise TypeError(f"track_along_vjp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
-        if not isinstance(losses, (bool, np.bool_)):
-            raise ValueError(f"track_along_vjp: losses is True or False, not {losses!r}")
-        if not isinstance(screens, (bool, np.bool_)):
-            raise ValueError(f"track_along_vjp: screens is True or False, not {screens!r}")
-        if not isinstance(cavities, (bool, np.bool_)):
-            raise ValueError(f"track_along_vjp: cavities is True or False, not {cavities!r}")
-        if cavities and (trajectories is not None or losses):
-            raise NotImplementedError(
-                "track_along_vjp: cavities=True together with " + ("trajectories=" if trajectories is not None else "losses=True")
-                + " -- the second pass over the particles differentiates the moments of the whole beam alone; ask for one of "
-                "the two")
-        # the pass through the kicks: a ParticleBeam's (a ParameterBeam's recursion handles cavities as it is)
-        self._through_kicks = bool(cavities) and isinstance(beam, ParticleBeam)
-        if screens and isinstance(beam, ParticleBeam):
-            raise TypeError(
-                "track_along_vjp: screens=True with a ParticleBeam -- its screen image is a histogram of counts, a step "
-                "function of the magnets whose gradient is zero almost everywhere; a ParameterBeam of the same moments "
-                "(its image is a smooth density) is differentiated")
-        self._screens = bool(screens)
-        if losses and trajectories is not None:
-            raise NotImplementedError(
-                "track_along_vjp: losses=True together with trajectories= -- the trajectories of a trace with losses are "
-                "not differentiated; ask for one of the two")
-        # (by value, before anything touches the GPU; a ParameterBeam has no particles to choose: TypeError)
-        self.chosen = None if trajectories is None else engine.chosen_particles(trajectories, beam)
-        leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
-        # (raises for an active Screen -- and, without `losses`, for an active Aperture --, naming it, before anything
-        # touches the GPU)
-        self.program = engine._trace_plan(segment, leaves, bool(losses), True) if screens else engine._trace_plan(segment, leaves, bool(losses))
-        B = int(np.prod(beam.batch_shape, dtype=np.int64))
-        if screens and self.program.screens and B > _ffi.MAX_IMAGE_BATCH:  # (as lynx_gaussian_images_along refuses it)
-            raise _ffi.LynxError(
-                f"track_along_vjp: screens=True with a batch of {B} samples, more than {_ffi.MAX_IMAGE_BATCH} -- "
-                "lynx_gaussian_images_along takes a sample per row of its launch grid (bad argument); trace the batch in parts")
-        # the survivors' reverse pass: a ParticleBeam and at least one active aperture; anything else with `losses` is the
-        # plain problem (apertures pass a ParameterBeam unchanged)
-        self._sets = bool(losses) and isinstance(beam, ParticleBeam) and len(self.program.apertures) > 0
-        if isinstance(beam, ParticleBeam) and not self._sets:
-            losses = False  # (no active aperture: nobody is lost, the call is the plain one)
-            self.program = engine._trace_plan(segment, leaves)
-        if self._sets and len(self.program.apertures) > MAX_TRACE_LOSS_APERTURES:
-            raise NotImplementedError(
-                f"track_along_vjp: {len(self.program.apertures)} active apertures, more than {MAX_TRACE_LOSS_APERTURES} (the "
-                f"first one beyond is {self.program.apertures[MAX_TRACE_LOSS_APERTURES][1].name!r}) -- differentiate the "
-                "lattice in stretches")
-        if len(leaves) > MAX_TRACE_LEAVES:
-            raise NotImplementedError(
-                f"track_along_vjp: {len(leaves)} leaf elements, more than {MAX_TRACE_LEAVES} (the first one beyond is "
-                f"{leaves[MAX_TRACE_LEAVES].name!r}) -- differentiate the lattice in stretches")
-        if self._through_kicks and len(leaves) > MAX_TRACE_CAVITY_LEAVES:
-            raise NotImplementedError(
-                f"track_along_vjp: cavities=True with {len(leaves)} leaf elements, more than {MAX_TRACE_CAVITY_LEAVES} (the first "
-                f"one beyond is {leaves[MAX_TRACE_CAVITY_LEAVES].name!r}) -- differentiate the lattice in stretches")
-        self._cavity = None  # the first active cavity in front of a ParticleBeam: no moment cotangent passes it
-        if isinstance(beam, ParticleBeam) and not self._through_kicks:
-            for kind, first, _ in self.program.steps:
-                if kind == _ffi.STEP_CAVITY:
-                    self._cavity = leaves[first].name
-                    break
-        if self._cavity is not None and self.chosen is None:
-            self._refuse_moments()
-        self.segment, self.beam, self.leaves = segment, beam, leaves
-        self._set_records = None
-        with_screens = {"screens": True} if screens else {}  # (a ParameterBeam's then; without it the call is the one it was)
-        if self._sets:
-            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses="particles")
-            self._set_records = self._survivor_set_records()
-        elif losses:  # (a ParameterBeam: active apertures are identity steps of its trace)
-            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, losses=True, **with_screens)
-        elif self.chosen is None:
-            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, **with_screens)
-        else:
-            self.trace = engine.track_along(segment, leaves, beam, keep_outgoing=True, keep_device=True, trajectories=self.chosen)
+        # the mode, decided once: "moments" (a ParameterBeam's sweep), "particles", "trajectories", "survivors" or "kicks"
+        self.mode, self.program, self.leaves, self.chosen, self._cavity = _trace_mode(segment, beam, trajectories, losses, screens, cavities)
+        self.segment, self.beam = segment, beam
+        self._screens = bool(screens)  # (of "moments": the forward trace makes images, the call takes their cotangents)
+        # (a keyword is given only where it says something; apertures are identity steps of a ParameterBeam's trace)
+        plain = {**({"losses": True} if losses and self.mode == "moments" else {}), **({"screens": True} if screens else {})}
+        options = {"survivors": {"losses": "particles"}, "trajectories": {"trajectories": self.chosen}}.get(self.mode, plain)
+        self.trace = engine.track_along(segment, self.leaves, beam, keep_outgoing=True, keep_device=True, **options)
+        self._set_records = self._survivor_set_records() if self.mode == "survivors" else None
 
     def _survivor_set_records(self):
         """
@@ -644,16 +669,9 @@ class TrackAlongVJP:
         B = int(np.prod(beam.batch_shape, dtype=np.int64))
         records = rt.empty((B, A + 1, _ffi.MOMENT_STRIDE), np.float64)
         rt.check(rt.lib.lynx_moments_by_loss(
-            rt.ctx, engine.dtype_code(beam.dtype), B, beam.num_particles, C.c_void_p(beam._particles.device(rt).ptr),
-            _ffi.TRACK_SHARED_INPUT if beam.is_shared else 0, A, C.c_void_p(self.trace._device["lost_at"].ptr),
-            C.c_void_p(records.ptr)))
+            rt.ctx, engine.dtype_code(beam.dtype), B, beam.num_particles, _p(beam._particles.device(rt)),
+            _ffi.TRACK_SHARED_INPUT if beam.is_shared else 0, A, _p(self.trace._device["lost_at"]), _p(records)))
         return records
-
-    def _refuse_moments(self):
-        raise NotImplementedError(
-            f"track_along_vjp: active Cavity {self._cavity!r} -- the moments of a ParticleBeam are not "
-            "closed under a cavity's kick; a ParameterBeam of the same lattice is differentiated, and so is this beam by a "
-            "second pass over its particles: track_along_vjp(..., cavities=True)")
 
     def _trajectory_cotangents(self, trajectories_bar) -> np.ndarray:
         """`trajectories_bar` as (B, P, K, 7) float64, refused by value."""
@@ -679,50 +697,38 @@ class TrackAlongVJP:
         return out
 
     def _cotangents(self, mu_bar, cov_bar, energy_bar, readings, properties):
-        batch_shape = self.beam.batch_shape
-        P = self.trace.num_points
-        B = int(np.prod(batch_shape, dtype=np.int64))
-        mb, cb, eb = np.zeros((B, P, 7)), np.zeros((B, P, 7, 7)), np.zeros((B, P))
+        batch_shape, P = self.beam.batch_shape, self.trace.num_points
+        bars = _MomentCotangents(batch_shape, P)
+        eb = np.zeros(bars.lead)
+        over_points = lambda bar: np.broadcast_to(np.asarray(bar, dtype=np.float64), (*batch_shape, P)).reshape(bars.lead)  # noqa: E731
         # a trace with losses: the points no particle of a sample reaches have no moments (NaN) and take no cotangent
-        dead = np.asarray(self.trace.num_survivors).reshape(B, P) == 0 if self._sets else np.zeros((B, P), dtype=bool)
+        dead = np.asarray(self.trace.num_survivors).reshape(bars.lead) == 0 if self.mode == "survivors" else np.zeros(bars.lead, dtype=bool)
         if properties and dead.any():
-            for name, bar in properties.items():
-                if name != "energy":
-                    self._refuse_cotangent_on_nobody(np.broadcast_to(np.asarray(bar, dtype=np.float64), (*batch_shape, P)).reshape(B, P),
-                                                     dead, repr(name))
+            moments = {name: bar for name, bar in properties.items() if name != "energy"}  # (the energy is there at every point)
+            for name, bar in moments.items():
+                self._refuse_cotangent_on_nobody(over_points(bar), dead, repr(name))
             with np.errstate(all="ignore"):
-                pm, pc, pe = trace_property_cotangents(self.trace, {n: v for n, v in properties.items() if n != "energy"})
-            pm, pc, pe = pm.reshape(B, P, 7), pc.reshape(B, P, 7, 7), pe.reshape(B, P)
-            pm[dead], pc[dead], pe[dead] = 0.0, 0.0, 0.0  # (0 x NaN of the rules above)
-            mb += pm
-            cb += pc
-            eb += pe
+                pm, pc, pe = trace_property_cotangents(self.trace, moments)
+            nobody = dead.reshape(pe.shape)
+            pm[nobody], pc[nobody], pe[nobody] = 0.0, 0.0, 0.0  # (0 x NaN of the rules above)
+            bars.add(pm, pc)
+            eb += pe.reshape(bars.lead)
             if "energy" in properties:
-                eb += np.broadcast_to(np.asarray(properties["energy"], dtype=np.float64), (*batch_shape, P)).reshape(B, P)
+                eb += over_points(properties["energy"])
         elif properties:
             pm, pc, pe = trace_property_cotangents(self.trace, properties)
-            mb += pm.reshape(B, P, 7)
-            cb += pc.reshape(B, P, 7, 7)
-            eb += pe.reshape(B, P)
-        if mu_bar is not None:
-            mu_bar = np.asarray(mu_bar, dtype=np.float64)
-            k = mu_bar.shape[-1]
-            mb[..., :k] += np.broadcast_to(mu_bar, (*batch_shape, P, k)).reshape(B, P, k)
-        if cov_bar is not None:
-            cov_bar = np.asarray(cov_bar, dtype=np.float64)
-            k = cov_bar.shape[-1]
-            cb[..., :k, :k] += np.broadcast_to(cov_bar, (*batch_shape, P, k, k)).reshape(B, P, k, k)
+            bars.add(pm, pc)
+            eb += pe.reshape(bars.lead)
+        bars.add(mu_bar, cov_bar)
+        mb, cb = bars.summed()
         if energy_bar is not None:
-            eb += np.broadcast_to(np.asarray(energy_bar, dtype=np.float64), (*batch_shape, P)).reshape(B, P)
+            eb += over_points(energy_bar)
         for element, bar in (readings or {}).items():
             points = [k for k, el in enumerate(self.leaves) if el is element and getattr(el, "_fusable_observer", False)]
-            if not points:
-                raise KeyError(f"{element!r} is not an active BPM of this lattice")
-            bar = np.broadcast_to(np.asarray(bar, dtype=np.float64), (2, *batch_shape))
-            for k in points:  # an active BPM reads (mu_x, mu_y) of the beam that ENTERS it: point k (bpm.py:48-54)
-                mb[:, k, 0] += bar[0].reshape(B)
-                mb[:, k, 2] += bar[1].reshape(B)
-        if dead.any():
+            _known_bpm(element, bool(points))
+            for k in points:  # an active BPM reads the beam that ENTERS it: point k of the trace
+                _add_reading(mb, bar, batch_shape, k)
+        if dead.any():  # (what nobody reaches stays zero: anything else was a cotangent of the moments of nobody)
             self._refuse_cotangent_on_nobody(np.abs(mb).sum(axis=-1) + np.abs(cb).sum(axis=(-1, -2)), dead, "the moments")
         return mb, cb, eb
 
@@ -741,7 +747,7 @@ class TrackAlongVJP:
         `screen_images_bar` as one (B, cells) array of the beam's dtype in the layout of lynx_gaussian_images_along (screen
         after screen, zeros for a screen that is not named), refused by value; None for an empty dict.
         """
-        if not getattr(self, "_screens", False):
+        if not self._screens:
             raise ValueError("track_along_vjp: screen_images_bar needs the screen images of the forward trace -- pass "
                              "screens=True to track_along_vjp")
         if not isinstance(screen_images_bar, dict):
@@ -792,88 +798,82 @@ class TrackAlongVJP:
         `wrt_particles=True` (`cavities=True` of `track_along_vjp`, a ParticleBeam): `Gradients.particles` (*batch, N, 7), the
         gradient w.r.t. every incoming particle, device-resident.
         """
-        if wrt_particles and not getattr(self, "_through_kicks", False):
+        if wrt_particles and self.mode != "kicks":
             raise ValueError("track_along_vjp: wrt_particles=True needs the pass over the particles -- a ParticleBeam and "
                              "cavities=True of track_along_vjp (without a cavity g.mu and g.cov say the same)")
         wi = None if screen_images_bar is None else self._image_cotangents(screen_images_bar)
-        wb = None
-        if trajectories_bar is not None:
-            wb = self._trajectory_cotangents(trajectories_bar)
-        elif self.chosen is not None:  # (the trace has trajectories: the same entry point, with no cotangent on them)
-            wb = self._trajectory_cotangents(np.zeros(7))
-        with_moments = (mu_bar is not None or cov_bar is not None or bool(readings)
-                        or any(name != "energy" for name in properties))
+        wb = None  # (a trace with trajectories and no cotangent on them: zeros)
+        if trajectories_bar is not None or self.chosen is not None:
+            wb = self._trajectory_cotangents(np.zeros(7) if trajectories_bar is None else trajectories_bar)
+        with_moments = mu_bar is not None or cov_bar is not None or bool(readings) or any(name != "energy" for name in properties)
         if with_moments and self._cavity is not None:
-            self._refuse_moments()
+            _refuse_moments(self._cavity)
         mb, cb, eb = self._cotangents(mu_bar, cov_bar, energy_bar, readings, properties)
         rt = get_runtime()
-        beam, program = self.beam, self.program
-        batch_shape, dtype = beam.batch_shape, beam.dtype
+        sweep = _Sweep(rt, self.segment.__dict__.setdefault("_trace_cache", engine.LatticeCache()), self.program, self.beam)
+        # (an upload is named until its call has been enqueued, so that it stays allocated; no energy cotangent: no upload)
+        eb_dev = rt.to_device(eb.astype(self.beam.dtype)) if np.any(eb) else None
+        launch = getattr(self, "_launch_" + self.mode)  # (_launch_moments, _particles, _trajectories, _survivors, _kicks)
+        results = launch(rt, sweep, mb, cb, eb_dev, wi=wi, wb=wb, with_moments=with_moments, wrt_particles=wrt_particles)
+        return Gradients(self.program, self.beam, sweep.g_par, sweep.g_en, **results)
+
+    # one method per mode, called alike (each names what it uses): the library call or calls -> `Gradients`' optional results
+    def _launch_moments(self, rt, sweep, mb, cb, eb_dev, wi, **_):
+        beam, states = self.beam, self.trace._device
         B, P = mb.shape[:2]
-        cache = self.segment.__dict__.setdefault("_trace_cache", engine.LatticeCache())
-        lat = engine._ready(cache, program, batch_shape, dtype, beam._energy._host)
-        g_par = rt.empty((B, max(lat.E, 1), 8), dtype)
-        g_en = rt.empty((B,), dtype)
-        g_mu = rt.empty((*batch_shape, 7), dtype)
-        g_cov = rt.empty((*batch_shape, 7, 7), dtype)
-        e_in = beam._energy.broadcast_device(rt, batch_shape)
-        p = lambda a: None if a is None else C.c_void_p(a.ptr)  # noqa: E731
-        # named, so that the uploads stay allocated until the call has been enqueued
-        eb_dev = rt.to_device(eb.astype(dtype)) if np.any(eb) else None
-        states = self.trace._device
-        if wb is not None:
-            K = len(self.chosen)
-            rec_dev = None
-            if with_moments:
-                rec_dev = rt.to_device(_record_cotangents(mb, cb))
-            else:
-                g_mu = g_cov = None
-            wb_dev = rt.to_device(wb)
-            g_chosen = rt.empty((*batch_shape, K, 7), dtype)
-            rt.check(rt.lib.lynx_track_particles_along_backward_trajectories(
-                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]) if with_moments else None, p(rec_dev),
-                p(eb_dev), p(g_par), p(g_en), p(g_mu), p(g_cov), K, p(states["trajectories"]), p(wb_dev), p(g_chosen)))
-            return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov,
-                             chosen_dev=g_chosen)
-        if getattr(self, "_through_kicks", False):
-            rec_dev = rt.to_device(_record_cotangents(mb, cb))
-            g_p = rt.empty((*batch_shape, beam.num_particles, 7), dtype) if wrt_particles else None
-            rt.check(rt.lib.lynx_track_particles_along_backward_cavities(
-                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(beam._particles.device(rt)),
-                _ffi.TRACK_SHARED_INPUT if beam.is_shared else 0, p(states["records"]), p(rec_dev), p(eb_dev), p(g_par), p(g_en),
-                p(g_p)))
-            return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, particles_dev=g_p,
-                             through_kicks=True)
-        if self._sets:
-            rec_dev = rt.to_device(_record_cotangents(mb, cb))
-            A = len(program.apertures)
-            at = (C.c_int32 * A)(*[step for step, _, _ in program.apertures])
-            rt.check(rt.lib.lynx_track_particles_along_backward_losses(
-                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]), p(rec_dev), p(eb_dev), A, at,
-                p(self._set_records), p(g_par), p(g_en)))
-            return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, survivors=True)
-        if isinstance(beam, ParticleBeam):
-            rec_dev = rt.to_device(_record_cotangents(mb, cb))
-            rt.check(rt.lib.lynx_track_particles_along_backward(
-                rt.ctx, lat.handle, beam.num_particles, p(e_in), p(states["records"]), p(rec_dev), p(eb_dev),
-                p(g_par), p(g_en), p(g_mu), p(g_cov)))
-        else:
-            mb_dev, cb_dev = rt.to_device(mb.astype(dtype)), rt.to_device(cb.astype(dtype))
-            shifts = None
-            if wi is not None:  # the images' cotangents go into mb_dev, cb_dev at the screens' points, on the same stream
-                shots = engine._screen_geometry(self.segment, program, batch_shape, dtype, rt, False)
-                wi_dev = rt.to_device(np.ascontiguousarray(wi, dtype=dtype))
-                shifts = rt.empty((B, shots["count"], 2), dtype)
-                rt.check(rt.lib.lynx_gaussian_images_along_backward(
-                    rt.ctx, engine.dtype_code(dtype), B, P, p(states["mu"]), p(states["cov"]), shots["count"], shots["rows"],
-                    p(shots["grid"]), p(shots["misalignment"]), shots["stride"], p(wi_dev), p(mb_dev), p(cb_dev), p(shifts)))
-            rt.check(rt.lib.lynx_track_moments_along_backward(
-                rt.ctx, lat.handle, p(e_in), p(states["mu"]), p(states["cov"]), p(mb_dev), p(cb_dev), p(eb_dev),
-                p(g_par), p(g_en), p(g_mu), p(g_cov)))
-            if getattr(self, "_screens", False):
-                return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov,
-                                 screens=[el for _, el in program.screens], screen_shifts_dev=shifts)
-        return Gradients(program, g_par, g_en, batch_shape, np.asarray(beam.energy).shape, mu_dev=g_mu, cov_dev=g_cov)
+        mb_dev, cb_dev = rt.to_device(mb.astype(beam.dtype)), rt.to_device(cb.astype(beam.dtype))
+        shifts = None
+        if wi is not None:  # the images' cotangents go into mb_dev, cb_dev at the screens' points, on the same stream
+            shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+            wi_dev = rt.to_device(np.ascontiguousarray(wi, dtype=beam.dtype))
+            shifts = rt.empty((B, shots["count"], 2), beam.dtype)
+            rt.check(rt.lib.lynx_gaussian_images_along_backward(
+                rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), shots["count"], shots["rows"],
+                _p(shots["grid"]), _p(shots["misalignment"]), shots["stride"], _p(wi_dev), _p(mb_dev), _p(cb_dev), _p(shifts)))
+        rt.check(rt.lib.lynx_track_moments_along_backward(
+            rt.ctx, sweep.lat.handle, _p(sweep.e_in), _p(states["mu"]), _p(states["cov"]), _p(mb_dev), _p(cb_dev), _p(eb_dev),
+            _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
+        return dict(moments=(sweep.g_mu, sweep.g_cov), screens=([el for _, el in self.program.screens], shifts) if self._screens else None)
+
+    def _launch_particles(self, rt, sweep, mb, cb, eb_dev, **_):
+        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+        rt.check(rt.lib.lynx_track_particles_along_backward(
+            rt.ctx, sweep.lat.handle, self.beam.num_particles, _p(sweep.e_in), _p(self.trace._device["records"]), _p(rec_dev),
+            _p(eb_dev), _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
+        return dict(moments=(sweep.g_mu, sweep.g_cov))
+
+    def _launch_trajectories(self, rt, sweep, mb, cb, eb_dev, wb, with_moments, **_):
+        beam, states, K = self.beam, self.trace._device, len(self.chosen)
+        # without a moment cotangent the moment path does not run: no records in, no g.mu and g.cov out
+        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb)) if with_moments else None
+        g_mu, g_cov = (sweep.g_mu, sweep.g_cov) if with_moments else (None, None)
+        wb_dev = rt.to_device(wb)
+        g_chosen = rt.empty((*beam.batch_shape, K, 7), beam.dtype)
+        rt.check(rt.lib.lynx_track_particles_along_backward_trajectories(
+            rt.ctx, sweep.lat.handle, beam.num_particles, _p(sweep.e_in), _p(states["records"]) if with_moments else None,
+            _p(rec_dev), _p(eb_dev), _p(sweep.g_par), _p(sweep.g_en), _p(g_mu), _p(g_cov), K,
+            _p(states["trajectories"]), _p(wb_dev), _p(g_chosen)))
+        return dict(moments=(g_mu, g_cov) if with_moments else None, chosen=g_chosen)
+
+    def _launch_kicks(self, rt, sweep, mb, cb, eb_dev, wrt_particles, **_):
+        beam = self.beam
+        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+        g_p = rt.empty((*beam.batch_shape, beam.num_particles, 7), beam.dtype) if wrt_particles else None
+        rt.check(rt.lib.lynx_track_particles_along_backward_cavities(
+            rt.ctx, sweep.lat.handle, beam.num_particles, _p(sweep.e_in), _p(beam._particles.device(rt)),
+            _ffi.TRACK_SHARED_INPUT if beam.is_shared else 0, _p(self.trace._device["records"]), _p(rec_dev), _p(eb_dev),
+            _p(sweep.g_par), _p(sweep.g_en), _p(g_p)))
+        return dict(particles=g_p, moments=Gradients.NO_INCOMING_MOMENTS)
+
+    def _launch_survivors(self, rt, sweep, mb, cb, eb_dev, **_):
+        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+        A = len(self.program.apertures)
+        at = (C.c_int32 * A)(*[step for step, _, _ in self.program.apertures])
+        rt.check(rt.lib.lynx_track_particles_along_backward_losses(
+            rt.ctx, sweep.lat.handle, self.beam.num_particles, _p(sweep.e_in), _p(self.trace._device["records"]), _p(rec_dev),
+            _p(eb_dev), A, at, _p(self._set_records), _p(sweep.g_par), _p(sweep.g_en)))
+        # the survivor set is held fixed: the limits that made it get gradient 0
+        return dict(moments=Gradients.NO_INCOMING_MOMENTS, zeros=[(el, ("x_max", "y_max")) for _, el, _ in self.program.apertures])
 
 
 def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False, cavities=False):

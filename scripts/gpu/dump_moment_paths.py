@@ -84,7 +84,7 @@ def gradients(g, segment):
         try:
             if getattr(g, name) is not None:
                 out[name] = getattr(g, name)
-        except KeyError:
+        except (KeyError, AttributeError):  # (AttributeError: ChainedGradients has `mu` and `cov` alone)
             pass
     return out
 
@@ -227,3 +227,31 @@ for dtype in (np.float32, np.float64):
     image = np.asarray(vjp.trace.image_at("SCREEN"), dtype=np.float64)
     save(f"i_along_vjp_screens_parameter_beam_{np.dtype(dtype).name}",
          {**gradients(vjp(screen_images_bar={"SCREEN": image - 1.1 * np.roll(image, 3, axis=-2)}, sigma_x=1e3), segment), "image": image})
+
+
+# ---- what the Python layer of the reverse passes adds: named properties through each VJP class, `readings=` across two
+# ---- stretches of a ParameterBeam lattice, an RBend (e1, e2 folded into angle), a parameter of shape (1,) under the batch ----
+
+def mixed(dtype, B=3):
+    f = lambda v: np.full(B, v, dtype=dtype)  # noqa: E731
+    bpm = lx.BPM(is_active=True, name="BPM_MIXED")
+    segment = lx.Segment([lx.Drift(f(0.6), dtype=dtype), lx.Quadrupole(f(0.2), k1=np.linspace(-3.0, 4.0, B).astype(dtype), dtype=dtype),
+                          lx.RBend(f(0.5), angle=np.linspace(0.1, 0.2, B).astype(dtype), e1=f(0.01), dtype=dtype), bpm,
+                          lx.HorizontalCorrector(f(0.1), angle=np.array([2e-4], dtype=dtype), dtype=dtype), lx.Drift(f(0.4), dtype=dtype)])
+    particles = lx.ParticleBeam.synthetic((B,), 1000, sigma=SIGMA, energy=1e8, seed=6, dtype=dtype)
+    parameters = lx.ParameterBeam.from_parameters(mu_x=np.linspace(-1e-5, 2e-5, B).astype(dtype), sigma_x=f(1e-4), sigma_xp=f(1e-5), sigma_y=f(2e-4),
+                                                  sigma_yp=f(1e-5), sigma_s=f(1e-5), sigma_p=f(1e-3), energy=f(1e8), dtype=dtype)
+    return segment, bpm, particles, parameters
+
+
+for dtype in (np.float32, np.float64):
+    name, rng = np.dtype(dtype).name, np.random.default_rng(79)
+    segment, bpm, particles, parameters = mixed(dtype)
+    named = dict(sigma_x=rng.normal(size=3), sigma_p=rng.normal(size=3), mu_y=rng.normal(size=3), sigma_xxp=rng.normal(size=3) * 1e3, sigma_yyp=2e3)
+    reading = {bpm: rng.normal(size=(2, 3))}
+    save(f"j_track_vjp_particles_properties_{name}", gradients(grad.track_vjp(segment, particles)(readings=reading, **named), segment))
+    save(f"j_track_vjp_parameter_beam_two_stretches_{name}",
+         gradients(grad.track_vjp(segment, parameters)(mu_bar=rng.normal(size=(3, 6)), readings=reading, **named), segment))
+    along = dict(beta_x=rng.normal(size=(3, 7)), sigma_y=rng.normal(size=(3, 7)), normalized_emittance_y=1e6, alpha_x=0.5, energy=rng.normal(size=(3, 7)) * 1e-8)
+    save(f"j_along_vjp_particles_properties_{name}", gradients(grad.track_along_vjp(segment, particles)(readings=reading, **along), segment))
+    save(f"j_along_vjp_parameter_beam_properties_{name}", gradients(grad.track_along_vjp(segment, parameters)(readings=reading, **along), segment))

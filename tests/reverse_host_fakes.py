@@ -1,0 +1,236 @@
+"""
+What the host tests of the reverse passes (`lynx_amd/grad.py`) share: a runtime, a library and device arrays that exist
+on the host alone, and the two fixtures built on them.  The library records every call in full -- the entry point's name
+and each argument by value --, an allocated output reads back as seeded random numbers, and the forward passes
+(`engine.track_along`, `engine.run_program_particles`, `engine.run_program_parameters`) are fabricated on the host: what
+`grad.py` does between its arguments and the C boundary is then a pure function, which tests/test_reverse_calls_host.py
+holds to a transcript.
+"""
+
+import ctypes as C
+
+import numpy as np
+import pytest
+
+N = 16  # particles of a fabricated particle trace
+
+
+class FakeArray:
+    """
+    What the calls need of a device array.  `how`: `empty`, `empty_result`, `to_device`, `to_device_result`, or `forward:
+    <name>` for what a forward pass left on the device.  An upload keeps its host array; anything else reads back as
+    multiples of 1/4 drawn from a generator seeded by the allocation's ordinal in its runtime.
+    """
+
+    def __init__(self, rt, how, shape, dtype, host=None):
+        self.how, self.shape, self.dtype, self.host = how, tuple(int(n) for n in shape), np.dtype(dtype), host
+        self.ordinal = len(rt.allocations)
+        self.ptr = 4096 * (self.ordinal + 1)
+        rt.allocations.append(self)
+
+    def numpy(self):
+        if self.host is not None:
+            return self.host.copy()
+        return (np.random.default_rng(self.ordinal).integers(-8, 9, size=self.shape) / 4.0).astype(self.dtype)
+
+    def __array__(self, dtype=None, copy=None):
+        return self.numpy() if dtype is None else self.numpy().astype(dtype)
+
+    def tag(self):
+        tag = {"how": self.how, "shape": list(self.shape), "dtype": self.dtype.str}
+        if self.host is not None:
+            tag["host"] = self.host
+        return tag
+
+
+class FakeLibrary:
+    """`calls`: the names of the entry points in the order they were asked for; `records`: (name, [argument, ...])."""
+
+    def __init__(self, rt):
+        self._rt, self.calls, self.records = rt, [], []
+
+    def _argument(self, value):
+        if value is None or isinstance(value, (bool, int, np.integer)):
+            return None if value is None else int(value)
+        if isinstance(value, C.c_void_p):
+            if value.value is None:
+                return None
+            return self._rt.allocations[value.value // 4096 - 1].tag()
+        if isinstance(value, C.Array):
+            return {"ctypes": [int(v) for v in value]}
+        raise AssertionError(f"an argument of type {type(value)} crossed the C boundary")
+
+    def __getattr__(self, name):
+        def entry(*args):
+            self.calls.append(name)
+            self.records.append((name, [self._argument(a) for a in args]))
+            return 0
+        return entry
+
+
+class FakeRuntime:
+    ctx = None
+
+    def __init__(self):
+        self.allocations = []
+        self.lib = FakeLibrary(self)
+
+    def empty(self, shape, dtype):
+        return FakeArray(self, "empty", shape, dtype)
+
+    def empty_result(self, shape, dtype):
+        return FakeArray(self, "empty_result", shape, dtype)
+
+    def to_device(self, host):
+        host = np.array(host)
+        return FakeArray(self, "to_device", host.shape, host.dtype, host)
+
+    def to_device_result(self, host):
+        host = np.array(host)
+        return FakeArray(self, "to_device_result", host.shape, host.dtype, host)
+
+    def forward(self, name, shape, dtype=np.float64):
+        return FakeArray(self, "forward:" + name, shape, dtype)
+
+    def check(self, status):
+        assert status == 0
+
+
+def fabricated_records(batch, P, seed=0, nobody=()):
+    """(*batch, P, 36) moment records of N particles drawn per sample and point; `nobody`: (flat sample, point) left empty."""
+    rng = np.random.default_rng(seed)
+    B = int(np.prod(batch, dtype=np.int64))
+    rec = np.zeros((B, P, 36))
+    rows, cols = np.triu_indices(6)
+    for b in range(B):
+        for k in range(P):
+            z = rng.normal(size=(N, 6)) * [1e-4, 1e-5, 1e-4, 1e-5, 1e-5, 1e-3] + rng.normal(size=6) * 1e-5
+            z[:, 1] += 0.05 * z[:, 0]
+            z[:, 3] -= 0.03 * z[:, 2]
+            d = z - z.mean(axis=0)
+            rec[b, k, :6], rec[b, k, 6] = z.mean(axis=0), 1.0
+            rec[b, k, 7:28] = (d.T @ d / N)[rows, cols]
+            rec[b, k, 34], rec[b, k, 35] = 1.0, N
+    for b, k in nobody:
+        rec[b, k, :35], rec[b, k, 35] = np.nan, 0.0
+    return rec.reshape(*batch, P, 36)
+
+
+def fake_gpu(monkeypatch, nobody=(), clamped=()):
+    """
+    `lynx_amd` with every way to the GPU replaced until `monkeypatch` is undone: returns (runtime, forward) -- `forward` the keyword arguments of every
+    `engine.track_along`.  `nobody`: the (flat sample, point) no particle of a fabricated trace with losses reaches;
+    `clamped`: the coordinates whose variance a fabricated outgoing ParameterBeam has at 1e-20 and below.
+    """
+    import lynx_amd as lx
+    from lynx_amd import engine, grad
+    from lynx_amd.device import Dual
+    from lynx_amd.trace import BeamTrace
+
+    rt, forward = FakeRuntime(), []
+
+    def moments_of(batch, lead, dtype, seed):
+        rec = fabricated_records(batch, int(np.prod(lead, dtype=np.int64)), seed).reshape(*batch, *lead, 36)
+        mu, cov = np.zeros((*batch, *lead, 7)), np.zeros((*batch, *lead, 7, 7))
+        rows, cols = np.triu_indices(6)
+        mu[...] = rec[..., :7]
+        cov[..., rows, cols] = rec[..., 7:28]
+        cov[..., cols, rows] = rec[..., 7:28]
+        return mu.astype(dtype), cov.astype(dtype)
+
+    def track_along(owner, leaves, incoming, **kwargs):
+        forward.append(kwargs)
+        leaves, batch, dtype = list(leaves), incoming.batch_shape, incoming.dtype
+        B, P = int(np.prod(batch, dtype=np.int64)), len(leaves) + 1
+        energy = np.broadcast_to(np.asarray(incoming.energy, dtype=np.float64)[..., None], (*batch, P)) * np.linspace(1.0, 1.5, P)
+        lengths, names = [1.0] * (P - 1), [el.name for el in leaves]
+        if isinstance(incoming, lx.ParticleBeam):
+            chosen = kwargs.get("trajectories")
+            losses = kwargs.get("losses", False)
+            program = engine._trace_plan(owner, leaves, bool(losses))
+            paths = None if chosen is None else np.zeros((*batch, P, len(chosen), 7))
+            rec = fabricated_records(batch, P, 1, nobody if losses else ())
+            trace = BeamTrace.from_records(rec, energy, lengths, names, dtype, apertures=[step for step, _, _ in program.apertures],
+                                           trajectories=paths, trajectory_indices=chosen)
+            trace._device = {"records": rt.forward("records", (B, P, 36))}
+            if chosen is not None:
+                trace._device["trajectories"] = rt.forward("trajectories", (B, P, len(chosen), 7), dtype)
+            if losses == "particles":
+                trace._device["lost_at"] = rt.forward("lost_at", (B, incoming.num_particles), np.int32)
+            return trace
+        program = engine._trace_plan(owner, leaves, bool(kwargs.get("losses")), bool(kwargs.get("screens")))
+        shots = engine._screen_geometry(owner, program, batch, dtype, rt, False) if program.screens else {"shapes": []}
+        mu, cov = moments_of(batch, (P,), dtype, 2)
+        trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype, screens=[step for step, _ in program.screens],
+                                       screen_images=[np.zeros((*batch, *shape), dtype) for shape in shots["shapes"]])
+        trace._device = {"mu": rt.forward("mu", (B, P, 7), dtype), "cov": rt.forward("cov", (B, P, 7, 7), dtype)}
+        return trace
+
+    def run_program_particles(cache, program, beam, moments=None):
+        out = lx.ParticleBeam.__new__(lx.ParticleBeam)
+        batch = beam.batch_shape
+        rec = fabricated_records(batch, 1, 3).reshape(*batch, 36)
+        record = rt.forward("moments", rec.shape)
+        record.host = rec
+        out._init_raw(Dual(dev=rt.forward("particles", (*batch, beam.num_particles, 7), beam.dtype)), beam._energy, None, beam.dtype,
+                      moments=Dual(dev=record))
+        return out
+
+    stretch = [0]
+
+    def run_program_parameters(cache, program, beam):
+        stretch[0] += 1
+        mu, cov = moments_of(beam.batch_shape, (), beam.dtype, 10 + stretch[0])
+        for c in clamped:
+            cov[..., c, c] = np.resize(np.array([1e-20, 1e-21, 0.0, 4e-8], dtype=cov.dtype), cov[..., c, c].shape)
+        out = lx.ParameterBeam.__new__(lx.ParameterBeam)
+        out._init_raw(Dual(mu), Dual(cov), beam._energy, beam.total_charge, beam.dtype)
+        return out
+
+    class Lattice:
+        handle = None
+
+        def __init__(self, program):
+            self.E = len(program.leaves)
+
+    def device(self, runtime=None):
+        if self._dev is None:
+            self._dev = rt.to_device(self._host)
+        return self._dev
+
+    patch = monkeypatch  # (the caller's own: whatever a test patches on top of this is undone in the right order)
+    patch.setattr(engine, "track_along", track_along)
+    patch.setattr(engine, "run_program_particles", run_program_particles)
+    patch.setattr(engine, "run_program_parameters", run_program_parameters)
+    patch.setattr(engine, "_ready", lambda cache, program, *a, **k: Lattice(program))
+    patch.setattr(engine, "get_runtime", lambda: rt)
+    patch.setattr(grad, "get_runtime", lambda: rt)
+    patch.setattr(Dual, "device", device)
+    patch.setattr(Dual, "broadcast_device",
+                  lambda self, runtime, shape: rt.to_device(np.ascontiguousarray(np.broadcast_to(self.host(), tuple(shape)))))
+    return rt, forward
+
+
+@pytest.fixture
+def recorded(monkeypatch):
+    """
+    A vjp whose forward pass is fabricated on the host and whose reverse call goes to a library object that records it:
+    (lynx_amd, the names of the entry points called so far, the keyword arguments of every `engine.track_along`).
+    """
+    import lynx_amd as lx
+
+    rt, forward = fake_gpu(monkeypatch)
+    return lx, rt.lib.calls, forward
+
+
+@pytest.fixture
+def no_gpu(monkeypatch):
+    """Anything that asks for the GPU runtime fails the test."""
+    from lynx_amd import device, engine, grad
+
+    def refuse(*args, **kwargs):
+        raise AssertionError("track_along_vjp touched the GPU runtime")
+
+    monkeypatch.setattr(device, "get_runtime", refuse)
+    monkeypatch.setattr(engine, "get_runtime", refuse)
+    monkeypatch.setattr(grad, "get_runtime", refuse)

@@ -10,6 +10,8 @@ import pytest
 
 from oracle import lynx_oracle as o
 
+from .reverse_host_fakes import no_gpu  # noqa: F401 (fixture)
+
 ROOT = Path(__file__).resolve().parent.parent
 
 
@@ -22,18 +24,6 @@ def test_both_entry_points_are_declared():
         assert f"int {name}(" in header
     assert len(_ffi.SIGNATURES["lynx_moments_by_loss"][1]) == 9
     assert len(_ffi.SIGNATURES["lynx_track_particles_along_backward_losses"][1]) == 12
-
-
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from lynx_amd import device, engine, grad
-
-    def refuse(*args, **kwargs):
-        raise AssertionError("track_along_vjp touched the GPU runtime")
-
-    monkeypatch.setattr(device, "get_runtime", refuse)
-    monkeypatch.setattr(engine, "get_runtime", refuse)
-    monkeypatch.setattr(grad, "get_runtime", refuse)
 
 
 def _f(v):

@@ -15,7 +15,7 @@ from oracle import lynx_oracle as o
 
 from . import screen_grad_reference as ref
 from .test_gpu_trace_screens import SCREEN_A, SCREEN_B
-from .test_trace_trajectories_grad_host import _Array, _Runtime
+from .reverse_host_fakes import no_gpu, recorded  # noqa: F401 (fixtures)
 
 ROOT = Path(__file__).resolve().parent.parent
 ENTRY = "lynx_gaussian_images_along_backward"
@@ -94,18 +94,6 @@ def test_what_the_float32_operations_cost_the_restatement():
 f = lambda v: np.array([v], dtype=np.float64)  # noqa: E731
 
 
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from lynx_amd import device, engine, grad
-
-    def refuse(*args, **kwargs):
-        raise AssertionError("track_along_vjp touched the GPU runtime")
-
-    monkeypatch.setattr(device, "get_runtime", refuse)
-    monkeypatch.setattr(engine, "get_runtime", refuse)
-    monkeypatch.setattr(grad, "get_runtime", refuse)
-
-
 def _lattice(lx, shared=True, batch=(1,)):
     mis = np.array([1e-5, -2e-5]) if shared else np.zeros((*batch, 2))
     first = lx.Screen(resolution=(20, 12), pixel_size=(1e-4, 1e-4), misalignment=mis, is_active=True, name="SCR_FIRST", dtype=np.float64)
@@ -169,44 +157,6 @@ def test_a_batch_beyond_65535_is_refused_as_the_forward_entry_point_refuses_it(n
     with pytest.raises(_ffi.LynxError, match="65536") as info:
         lx.grad.track_along_vjp(segment, _parameters(lx, batch), screens=True)
     assert "lynx_gaussian_images_along" in str(info.value) and "bad argument" in str(info.value)
-
-
-@pytest.fixture
-def recorded(monkeypatch):
-    """
-    A vjp whose forward trace is fabricated on the host (`engine.track_along` replaced, its arguments recorded; images of
-    zeros) and whose reverse call goes to a library object that records the names of the entry points it is asked for.
-    """
-    import lynx_amd as lx
-    from lynx_amd import engine, grad
-    from lynx_amd.trace import BeamTrace
-
-    rt, forward = _Runtime(), []
-
-    def track_along(owner, leaves, incoming, **kwargs):
-        forward.append(kwargs)
-        leaves, batch = list(leaves), incoming.batch_shape
-        B, P = int(np.prod(batch)), len(leaves) + 1
-        program = engine._trace_plan(owner, leaves, bool(kwargs.get("losses")), bool(kwargs.get("screens")))
-        shots = engine._screen_geometry(owner, program, batch, incoming.dtype, rt, False) if program.screens else {"shapes": []}
-        mu = np.zeros((*batch, P, 7))
-        mu[..., 6] = 1
-        cov = np.broadcast_to(np.eye(7) * 1e-8, (*batch, P, 7, 7)).copy()
-        trace = BeamTrace.from_moments(mu, cov, np.full((*batch, P), 1e8), [1.0] * (P - 1), [el.name for el in leaves], np.float64,
-                                       screens=[step for step, _ in program.screens],
-                                       screen_images=[np.zeros((*batch, *shape)) for shape in shots["shapes"]])
-        trace._device = {"mu": _Array((B, P, 7)), "cov": _Array((B, P, 7, 7))}
-        return trace
-
-    class _Lattice:
-        E, handle = 6, None
-
-    monkeypatch.setattr(engine, "track_along", track_along)
-    monkeypatch.setattr(engine, "_ready", lambda *a, **k: _Lattice())
-    monkeypatch.setattr(engine, "get_runtime", lambda: rt)
-    monkeypatch.setattr(grad, "get_runtime", lambda: rt)
-    monkeypatch.setattr(lx.device.Dual, "broadcast_device", lambda self, rt, shape: _Array(shape))
-    return lx, rt.lib.calls, forward
 
 
 def test_the_forward_pass_is_track_along_with_screens_and_one_reverse_call_takes_every_cotangent(recorded):

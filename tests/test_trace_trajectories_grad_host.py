@@ -12,6 +12,8 @@ import pytest
 
 from oracle import lynx_oracle as o
 
+from .reverse_host_fakes import no_gpu, recorded  # noqa: F401 (fixtures)
+
 ROOT = Path(__file__).resolve().parent.parent
 N = 16
 ENTRY = "lynx_track_particles_along_backward_trajectories"
@@ -37,99 +39,12 @@ def test_the_entry_point_is_declared():
     assert "beam trace gradients with trajectories: " in header.replace("\n * ", " ").replace("  ", " ")
 
 
-@pytest.fixture
-def no_gpu(monkeypatch):
-    from lynx_amd import device, engine, grad
-
-    def refuse(*args, **kwargs):
-        raise AssertionError("track_along_vjp touched the GPU runtime")
-
-    monkeypatch.setattr(device, "get_runtime", refuse)
-    monkeypatch.setattr(engine, "get_runtime", refuse)
-    monkeypatch.setattr(grad, "get_runtime", refuse)
-
-
 def _line(lx):
     return lx.Segment([lx.Drift(f(1.0), dtype=np.float64), lx.Quadrupole(f(0.2), k1=f(2.0), dtype=np.float64)])
 
 
 def _beam(lx, batch=(1,)):
     return lx.ParticleBeam(o.gaussian_particles(batch, N, seed=1, dtype=np.float64), np.full(batch, 1e8), dtype=np.float64)
-
-
-class _Array:
-    """What the calls need of a device array."""
-
-    ptr = 1
-
-    def __init__(self, shape=(), dtype=np.float64):
-        self.shape, self.dtype = tuple(shape), np.dtype(dtype)
-
-    def numpy(self):
-        return np.zeros(self.shape, self.dtype)
-
-
-class _Library:
-    def __init__(self):
-        self.calls = []
-
-    def __getattr__(self, name):
-        def entry(*args):
-            self.calls.append(name)
-            return 0
-        return entry
-
-
-class _Runtime:
-    ctx = None
-
-    def __init__(self):
-        self.lib = _Library()
-
-    def empty(self, shape, dtype):
-        return _Array(shape, dtype)
-
-    def to_device(self, host):
-        return _Array(np.shape(host), np.asarray(host).dtype)
-
-    def check(self, status):
-        assert status == 0
-
-
-@pytest.fixture
-def recorded(monkeypatch):
-    """
-    A vjp whose forward trace is fabricated on the host (`engine.track_along` replaced, its arguments recorded) and whose
-    reverse call goes to a library object that records the names of the entry points it is asked for.
-    """
-    import lynx_amd as lx
-    from lynx_amd import engine, grad
-    from lynx_amd.trace import BeamTrace
-
-    rt, forward = _Runtime(), []
-
-    def track_along(owner, leaves, incoming, **kwargs):
-        forward.append(kwargs)
-        B, P = int(np.prod(incoming.batch_shape)), len(list(leaves)) + 1
-        chosen = kwargs.get("trajectories")
-        paths = None if chosen is None else np.zeros((*incoming.batch_shape, P, len(chosen), 7))
-        rec = np.zeros((*incoming.batch_shape, P, 36))
-        rec[..., 35] = N
-        trace = BeamTrace.from_records(rec, np.full((*incoming.batch_shape, P), 1e8), [1.0] * (P - 1), ["E"] * (P - 1),
-                                       np.float64, trajectories=paths, trajectory_indices=chosen)
-        trace._device = {"records": _Array((B, P, 36))}
-        if chosen is not None:
-            trace._device["trajectories"] = _Array((B, P, len(chosen), 7))
-        return trace
-
-    class _Lattice:
-        E, handle = 2, None
-
-    monkeypatch.setattr(engine, "track_along", track_along)
-    monkeypatch.setattr(engine, "_ready", lambda *a, **k: _Lattice())
-    monkeypatch.setattr(grad, "get_runtime", lambda: rt)
-    monkeypatch.setattr(lx.device.Dual, "broadcast_device", lambda self, rt, shape: _Array(shape))
-    return lx, rt.lib.calls, forward
 
 
 def test_without_trajectories_the_calls_are_the_ones_they_were(recorded):
@@ -156,17 +71,13 @@ def test_with_trajectories_every_cotangent_goes_into_one_call(recorded):
         only.mu
 
 
-def test_trajectories_bar_without_trajectories_is_a_value_error(no_gpu, monkeypatch):
-    import lynx_amd as lx
-    from lynx_amd import engine, grad
-
-    vjp = grad.TrackAlongVJP.__new__(grad.TrackAlongVJP)  # (a vjp as `track_along_vjp(segment, beam)` leaves it)
-    segment, beam = _line(lx), _beam(lx)
-    vjp.segment, vjp.beam, vjp.leaves, vjp.chosen, vjp._cavity = segment, beam, list(segment._leaves()), None, None
-    vjp.program = engine._trace_plan(segment, vjp.leaves)
+def test_trajectories_bar_without_trajectories_is_a_value_error(recorded):
+    lx, calls, _ = recorded
+    vjp = lx.grad.track_along_vjp(_line(lx), _beam(lx))
     with pytest.raises(ValueError, match="trajectories=") as info:
         vjp(trajectories_bar=np.ones((1, 3, 2, 6)))
     assert "trajectories_bar" in str(info.value)
+    assert calls == []
 
 
 @pytest.mark.parametrize("shape", [(1, 3, 4, 6), (1, 2, 3, 6), (2, 3, 3, 7), (1, 3, 3, 5), (3, 3), ()])
