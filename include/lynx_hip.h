@@ -560,6 +560,24 @@ int lynx_aperture_compact(lynx_ctx* ctx, int dtype, int64_t n_particles, const v
 int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles,
                        const double* mu, const double* sigma, uint64_t seed, void* d_p);
 
+/* Seeded correlated 6-D Gaussian beam, generated in HBM: sample b has its own mean and covariance factor.
+ *   d_rows [B][27] float64 on the device: m[0..5], then the lower triangle of the 6x6 factor L row by row
+ *          (L00, L10, L11, L20, ... L55); the sample's covariance is L L^T
+ * Column c < 6 of particle i of sample b is m[c] + sum_{j <= c} L[c][j] z_j, summed in float64 from j = 0 upwards and
+ * rounded once to the dtype; z_j is the normal lynx_fill_gaussian draws for flat scalar (b N + i) 7 + j (so a diagonal
+ * L with the same row for every sample gives lynx_fill_gaussian's bits).  Column 6 is 1.                            */
+int lynx_fill_gaussian_rows(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const double* d_rows,
+                            uint64_t seed, void* d_p);
+
+/* Per-sample affine rescale of a beam (ParticleBeam.transformed_to, particle_beam.py:580-715), device to device:
+ *   out[b][i][c] = (in[b][i][c] - old_mu[b][c]) / old_sigma[b][c] * new_sigma[b][c] + new_mu[b][c]   (c < 6; column 6 is 1)
+ * in the dtype, in this order.
+ *   d_rows [B][24] of the dtype: old_mu[6], old_sigma[6], new_sigma[6], new_mu[6]
+ *   in_sample_stride (scalars): n_particles * 7, or 0 for one stored sample that every output sample reads
+ * d_p_out may be d_p_in unless the stride is 0.                                                                     */
+int lynx_transform_particles(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p_in,
+                             int64_t in_sample_stride, const void* d_rows, void* d_p_out);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI (no reference counterpart: the
  *      reference is single-process; batch samples are independent, so only the
  *      per-sample moment records are exchanged) --------------------------------------- */

@@ -15,6 +15,8 @@ _LIB_PATH = Path(__file__).resolve().parent / "_lib" / "liblynxhip.so"
 UNIQUE_ID_BYTES = 128
 MOMENT_STRIDE = 36
 STEP_STRIDE = 64
+GAUSS_ROW = 27  # lynx_fill_gaussian_rows: mean[6] and the lower triangle of the factor
+TRANSFORM_ROW = 24  # lynx_transform_particles: old_mu, old_sigma, new_sigma, new_mu
 
 F32, F64 = 0, 1
 
@@ -124,6 +126,8 @@ SIGNATURES = {
     "lynx_aperture_compact": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),
     "lynx_fill_gaussian": (_i, [_vp, _i, _i64, _i64, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                 C.c_uint64, _vp]),
+    "lynx_fill_gaussian_rows": (_i, [_vp, _i, _i64, _i64, _vp, C.c_uint64, _vp]),
+    "lynx_transform_particles": (_i, [_vp, _i, _i64, _i64, _vp, _i64, _vp, _vp]),
     "lynx_comm_unique_id": (_i, [C.c_char_p]),
     "lynx_comm_init": (_i, [_vp, _i, _i, C.c_char_p]),
     "lynx_comm_destroy": (_i, [_vp]),

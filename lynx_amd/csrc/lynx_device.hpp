@@ -2757,4 +2757,156 @@ __global__ __launch_bounds__(256) void k_fill_gaussian(T* __restrict__ p, int64_
   }
 }
 
+// `zn` of k_fill_gaussian for flat scalar `idx`, statement for statement (the kernel above keeps its own copy: moving
+// it into this function reorders its instructions, and it is what every benchmark and parity input is made with)
+__device__ __forceinline__ double gaussian_of_scalar(uint64_t seed, uint64_t idx) {
+  const uint64_t h1 = splitmix64(seed ^ splitmix64(idx * 2 + 0));
+  const uint64_t h2 = splitmix64(seed ^ splitmix64(idx * 2 + 1));
+  const double u1 = ((double)(h1 >> 11) + 1.0) * (1.0 / 9007199254740993.0);  // (0,1)
+  const double u2 = (double)(h2 >> 11) * (1.0 / 9007199254740992.0);          // [0,1)
+  const double r = sqrt(-2.0 * log(u1));
+  return r * cos(6.283185307179586 * u2);
+}
+
+// ---------------------------------------------------------------------------------------
+// Beam factory: k_fill_gaussian_rows (correlated Gaussian, one mean and one lower-triangular
+// factor per sample) and k_transform_particles (per-sample affine rescale).  Both walk the
+// flat [B * N] particle array in wave tiles of 64 lanes x P particles (P = 16 / sizeof(T)), a
+// lane owning P whole particles, and leave through the wave's private LDS region as
+// full-width non-temporal stores; only the tile cut by the end of the array goes particle
+// by particle.  A tile inside one sample reads that sample's row through wave-uniform
+// (scalar) loads; a tile that straddles samples takes each particle's own row.
+// ---------------------------------------------------------------------------------------
+constexpr int kGaussRowScalars = 27;      // m[6], then L row by row: L00, L10, L11, L20, ... L55
+constexpr int kTransformRowScalars = 24;  // old_mu[6], old_sigma[6], new_sigma[6], new_mu[6]
+constexpr int kBeamFactoryMaxBlocks = 1024;  // 4 workgroups (16 waves, 112 KiB of LDS) per CU; more tiles: the loop goes round
+
+__device__ __forceinline__ int64_t wave_first(int64_t v) {
+  const int lo = __builtin_amdgcn_readfirstlane((int)(v & 0xffffffffll));
+  const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
+  return ((int64_t)hi << 32) | (unsigned int)lo;
+}
+
+// x = m + L z for one particle: `row` is m[6] and the factor, z its six normals; column 6 is 1.  Every term is kept in the
+// order of tests/beam_factory_reference.py (the build has -ffp-contract=off).
+template <typename T>
+__device__ __forceinline__ void gaussian_particle(const double* __restrict__ row, const double (&z)[6], T (&x)[7]) {
+#pragma unroll
+  for (int c = 0; c < 6; ++c) {
+    const double* L = row + 6 + c * (c + 1) / 2;
+    double s = L[0] * z[0];
+#pragma unroll
+    for (int j = 1; j <= c; ++j) s = s + L[j] * z[j];
+    x[c] = (T)(row[c] + s);
+  }
+  x[6] = T(1);
+}
+
+// the walk over wave tiles both kernels share: what of a tile a wave and a lane see
+template <int P>
+struct WaveTileWalk {
+  static constexpr int64_t kSpan = 64 * P;
+  int64_t n, total;             // particles of a sample and of the whole array
+  int64_t base, first, sample;  // the tile's and this lane's first particle; the sample of the tile's first particle
+  bool full, one_sample;        // wave-uniform: not cut by the end of the array; inside one sample
+
+  __device__ __forceinline__ WaveTileWalk(int64_t tile_base, int lane, int64_t n_particles, int64_t total_particles) {
+    n = n_particles;
+    total = total_particles;
+    base = tile_base;
+    first = base + lane * P;
+    sample = wave_first(sample_of(base));
+    full = base + kSpan <= total;
+    one_sample = (sample + 1) * n >= (full ? base + kSpan : total);
+  }
+  __device__ __forceinline__ int64_t sample_of(int64_t q) const { return q / n; }
+  // particle u of this lane (the last particle of the array stands in for those behind it)
+  __device__ __forceinline__ int64_t particle(int u) const { return first + u < total ? first + u : total - 1; }
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_fill_gaussian_rows(T* __restrict__ p, int64_t n_particles, int64_t total,
+                                                             const double* __restrict__ rows, uint64_t seed) {
+  constexpr int P = 16 / (int)sizeof(T);
+  using Walk = WaveTileWalk<P>;
+  __shared__ __attribute__((aligned(16))) unsigned char s_tiles[4 * kWaveTileBytes];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned char* s_wave = s_tiles + wave * kWaveTileBytes;
+  const int64_t step = (int64_t)gridDim.x * 4 * Walk::kSpan;
+  for (int64_t base = wave_first(((int64_t)blockIdx.x * 4 + wave) * Walk::kSpan); base < total; base += step) {
+    const Walk t(base, lane, n_particles, total);
+    T x[P][7];
+#pragma unroll
+    for (int u = 0; u < P; ++u) {  // one particle at a time: six normals in flight, not 6 P (registers)
+      const int64_t q = t.particle(u);
+      double z[6];
+#pragma unroll
+      for (int j = 0; j < 6; ++j) z[j] = gaussian_of_scalar(seed, (uint64_t)q * 7 + j);
+      if (t.one_sample)  // the row comes through scalar loads
+        gaussian_particle(rows + t.sample * kGaussRowScalars, z, x[u]);
+      else
+        gaussian_particle(rows + t.sample_of(q) * kGaussRowScalars, z, x[u]);
+    }
+    if (t.full) {
+      lynx_u32x4 v[7];
+      wave_tile_from_particles<T, P>(x, s_wave, lane, v);
+      wave_tile_store(p + base * 7, lane, v);
+    } else {
+#pragma unroll
+      for (int u = 0; u < P; ++u)
+        if (t.first + u < total) store_particle(p + (t.first + u) * 7, x[u]);
+    }
+  }
+}
+
+// (z - old_mu) / old_sigma * new_sigma + new_mu in T, in this order (the host path's expression); column 6 is 1
+template <typename T>
+__device__ __forceinline__ void transform_particle(const T* __restrict__ row, T (&z)[7]) {
+#pragma unroll
+  for (int c = 0; c < 6; ++c) z[c] = (z[c] - row[c]) / row[6 + c] * row[12 + c] + row[18 + c];
+  z[6] = T(1);
+}
+
+// in_stride = 0: one stored sample for every output sample.  `in` may be `out`: a lane writes only what its wave has read.
+template <typename T>
+__global__ __launch_bounds__(256) void k_transform_particles(const T* in, int64_t in_stride, T* out, int64_t n_particles,
+                                                              int64_t total, const T* __restrict__ rows) {
+  constexpr int P = 16 / (int)sizeof(T);
+  using Walk = WaveTileWalk<P>;
+  __shared__ __attribute__((aligned(16))) unsigned char s_tiles[4 * kWaveTileBytes];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  unsigned char* s_wave = s_tiles + wave * kWaveTileBytes;
+  const int64_t step = (int64_t)gridDim.x * 4 * Walk::kSpan;
+  for (int64_t base = wave_first(((int64_t)blockIdx.x * 4 + wave) * Walk::kSpan); base < total; base += step) {
+    const Walk t(base, lane, n_particles, total);
+    T z[P][7];
+    // (fetching the straddling tiles of a beam with a stride full-width too took the float32 form from 121 to 132 VGPRs,
+    // three waves per SIMD for four, for one tile in some hundred)
+    if (t.full && t.one_sample) {
+      lynx_u32x4 v[7];
+      wave_tile_fetch(in + (in_stride ? base : base - t.sample * n_particles) * 7, lane, v);
+      wave_tile_to_particles<T, P>(v, s_wave, lane, z);
+      const T* row = rows + t.sample * kTransformRowScalars;  // through scalar loads
+#pragma unroll
+      for (int u = 0; u < P; ++u) transform_particle(row, z[u]);
+    } else {
+#pragma unroll
+      for (int u = 0; u < P; ++u) {
+        const int64_t q = t.particle(u), b = t.sample_of(q);
+        load_particle(in + (in_stride ? q : q - b * n_particles) * 7, z[u]);
+        transform_particle(rows + b * kTransformRowScalars, z[u]);
+      }
+    }
+    if (t.full) {
+      lynx_u32x4 v[7];
+      wave_tile_from_particles<T, P>(z, s_wave, lane, v);
+      wave_tile_store(out + base * 7, lane, v);
+    } else {
+#pragma unroll
+      for (int u = 0; u < P; ++u)
+        if (t.first + u < total) store_particle(out + (t.first + u) * 7, z[u]);
+    }
+  }
+}
+
 }  // namespace lynx

@@ -3428,6 +3428,58 @@ int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
   return LYNX_OK;
 }
 
+// wave tiles of 64 lanes x (16 / element size) particles, four to a workgroup
+static unsigned wave_tile_grid(int dtype, int64_t total_particles, int max_blocks) {
+  const int64_t per_block = 4 * 64 * (dtype == LYNX_F64 ? 2 : 4);
+  return (unsigned)std::min<int64_t>((total_particles + per_block - 1) / per_block, max_blocks);
+}
+
+int lynx_fill_gaussian_rows(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const double* d_rows,
+                            uint64_t seed, void* d_p) {
+  LYNX_NEED(ctx);
+  if (!d_p || !d_rows || batch <= 0 || n_particles <= 0 || (dtype != LYNX_F32 && dtype != LYNX_F64) ||
+      batch > (int64_t)(0x7fffffffffffffffLL / 14) / n_particles)  // (2 * scalars is the generator's counter)
+    return fail(ctx, LYNX_ERR_INVALID, "bad argument");
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_p, (size_t)batch * n_particles * 7 * dtype_size(dtype));
+  const int64_t total = batch * n_particles;
+  const unsigned grid = wave_tile_grid(dtype, total, kBeamFactoryMaxBlocks);
+  if (dtype == LYNX_F64)
+    hipLaunchKernelGGL(k_fill_gaussian_rows<double>, dim3(grid), dim3(256), 0, ctx->stream, (double*)d_p, n_particles,
+                       total, d_rows, seed);
+  else
+    hipLaunchKernelGGL(k_fill_gaussian_rows<float>, dim3(grid), dim3(256), 0, ctx->stream, (float*)d_p, n_particles, total,
+                       d_rows, seed);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+int lynx_transform_particles(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p_in,
+                             int64_t in_sample_stride, const void* d_rows, void* d_p_out) {
+  LYNX_NEED(ctx);
+  if (!d_p_in || !d_rows || !d_p_out || batch <= 0 || n_particles <= 0 || (dtype != LYNX_F32 && dtype != LYNX_F64) ||
+      batch > (int64_t)(0x7fffffffffffffffLL / 7 / 8) / n_particles)
+    return fail(ctx, LYNX_ERR_INVALID, "bad argument");
+  if (in_sample_stride != 0 && in_sample_stride != n_particles * 7)
+    return fail(ctx, LYNX_ERR_INVALID, "transform: the incoming sample stride is 0 (one stored sample) or n_particles * 7");
+  if (in_sample_stride == 0 && d_p_in == d_p_out)
+    return fail(ctx, LYNX_ERR_INVALID, "transform: one stored sample cannot be rescaled in place");
+  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  HIP_TRY(ctx, use_device(ctx));
+  ctx->wrote(d_p_out, (size_t)batch * n_particles * 7 * dtype_size(dtype));
+  const int64_t total = batch * n_particles;
+  const unsigned grid = wave_tile_grid(dtype, total, kBeamFactoryMaxBlocks);
+  if (dtype == LYNX_F64)
+    hipLaunchKernelGGL(k_transform_particles<double>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)d_p_in,
+                       in_sample_stride, (double*)d_p_out, n_particles, total, (const double*)d_rows);
+  else
+    hipLaunchKernelGGL(k_transform_particles<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)d_p_in,
+                       in_sample_stride, (float*)d_p_out, n_particles, total, (const float*)d_rows);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
 // ---- diagnostics: practical HBM ceiling ------------------------------------------------------
 
 int lynx_diag_copy(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes, int repeats, int vec_per_thread,

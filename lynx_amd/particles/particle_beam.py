@@ -4,7 +4,9 @@
 The particle array is only copied to the host when somebody asks for it; all moment
 properties come from ONE fused reduction pass on the GPU (`lynx_moments`, or the epilogue
 of the tracking kernel), not from 14 separate reductions as in the reference.
-Samplers run on the host with NumPy (they are not on the hot path).
+Samplers run on the host with NumPy unless asked otherwise: `from_parameters`, `from_twiss` and `transformed_to`
+take `on_device=True` (and `from_parameter_beam` always does), which draws or rescales the particles in HBM with a
+mean, sizes and correlations per sample (`lynx_fill_gaussian_rows`, `lynx_transform_particles`).
 """
 
 from __future__ import annotations
@@ -21,6 +23,38 @@ from .beam import Beam, _batch_args
 def _tri(i: int, j: int) -> int:
     """Index of cov[i, j] (i <= j < 6) in a moment record (include/lynx_hip.h)."""
     return 7 + i * 6 - (i * (i - 1)) // 2 + (j - i)
+
+
+def covariance_factor(cov) -> np.ndarray:
+    """
+    Lower-triangular `L` with `L @ L.T == cov` for symmetric positive semi-definite `cov` of shape (..., 6, 6): a plain
+    Cholesky factorisation in float64 that leaves a column zero where its pivot is not positive.  A coordinate without
+    spread (`sigma_s = 0`) or a fully correlated pair (`cor_y = sigma_y * sigma_yp`, a line in phase space) therefore
+    gives a factor, not a NaN.  Returns (..., 6, 6) float64.
+    """
+    cov = np.asarray(cov, dtype=np.float64)
+    assert cov.shape[-2:] == (6, 6), "Covariance matrices must be 6 x 6."
+    L = np.zeros_like(cov)
+    for j in range(6):
+        pivot = cov[..., j, j] - np.sum(L[..., j, :j] ** 2, axis=-1)
+        ok = pivot > 0
+        root = np.sqrt(np.where(ok, pivot, 1.0))
+        L[..., j, j] = np.where(ok, root, 0.0)
+        for i in range(j + 1, 6):
+            rest = cov[..., i, j] - np.sum(L[..., i, :j] * L[..., j, :j], axis=-1)
+            L[..., i, j] = np.where(ok, rest / root, 0.0)
+    return L
+
+
+_TRIL = np.tril_indices(6)  # row by row: L00, L10, L11, L20, ... L55 (include/lynx_hip.h: lynx_fill_gaussian_rows)
+
+
+def gaussian_rows(mean, cov) -> np.ndarray:
+    """The (B, 27) float64 rows of `lynx_fill_gaussian_rows`: each sample's mean, then its `covariance_factor`."""
+    mean = np.asarray(mean, dtype=np.float64).reshape(-1, 6)
+    factor = covariance_factor(cov).reshape(-1, 6, 6)
+    assert len(mean) == len(factor) and 6 + len(_TRIL[0]) == _ffi.GAUSS_ROW
+    return np.ascontiguousarray(np.concatenate([mean, factor[:, _TRIL[0], _TRIL[1]]], axis=-1))
 
 
 class ParticleBeam(Beam):
@@ -115,31 +149,40 @@ class ParticleBeam(Beam):
     def from_parameters(cls, num_particles=None, mu_x=None, mu_y=None, mu_xp=None, mu_yp=None, sigma_x=None,
                         sigma_y=None, sigma_xp=None, sigma_yp=None, sigma_s=None, sigma_p=None, cor_x=None,
                         cor_y=None, cor_s=None, energy=None, total_charge=None, device=None,
-                        dtype=np.float32, seed=None) -> "ParticleBeam":
+                        dtype=np.float32, seed=None, on_device: bool = False) -> "ParticleBeam":
         """
         Random 6-D Gaussian beam (particle_beam.py:47-178).  `seed` makes it reproducible
         (the reference draws from torch's global RNG).
+
+        `on_device=True` generates the particles in HBM (`lynx_fill_gaussian_rows`): only each sample's mean and
+        `covariance_factor` are made on the host, in float64 from the arguments as the dtype holds them, and the beam's
+        particles are a `DeviceArray`.  The draws are those of `ParticleBeam.synthetic`, not the host path's
+        `np.random` draws for the same seed; `seed=None` draws a 64-bit seed.
         """
         dtype = np.dtype(dtype)
         g, shape = _batch_args(dict(mu_x=mu_x, mu_xp=mu_xp, mu_y=mu_y, mu_yp=mu_yp, sigma_x=sigma_x,
                                     sigma_xp=sigma_xp, sigma_y=sigma_y, sigma_yp=sigma_yp, sigma_s=sigma_s,
                                     sigma_p=sigma_p, cor_x=cor_x, cor_y=cor_y, cor_s=cor_s, energy=energy,
                                     total_charge=total_charge), dtype)
+        work = np.dtype(np.float64) if on_device else dtype  # what the mean and covariance are formed in
         d = lambda k, v: g.get(k, np.full(shape, v, dtype=dtype))  # noqa: E731
+        w = lambda k, v: d(k, v).astype(work, copy=False)  # noqa: E731
         n = int(np.asarray(num_particles).reshape(-1)[0]) if num_particles is not None else 100_000
         total_charge = d("total_charge", 0.0)
-        mean = np.stack([d("mu_x", 0.0), d("mu_xp", 0.0), d("mu_y", 0.0), d("mu_yp", 0.0),
-                         np.zeros(shape, dtype), np.zeros(shape, dtype)], axis=-1)
-        cov = np.zeros((*shape, 6, 6), dtype=dtype)
-        cov[..., 0, 0] = d("sigma_x", 175e-9) ** 2
-        cov[..., 0, 1] = cov[..., 1, 0] = d("cor_x", 0.0)
-        cov[..., 1, 1] = d("sigma_xp", 2e-7) ** 2
-        cov[..., 2, 2] = d("sigma_y", 175e-9) ** 2
-        cov[..., 2, 3] = cov[..., 3, 2] = d("cor_y", 0.0)
-        cov[..., 3, 3] = d("sigma_yp", 2e-7) ** 2
-        cov[..., 4, 4] = d("sigma_s", 1e-6) ** 2
-        cov[..., 4, 5] = cov[..., 5, 4] = d("cor_s", 0.0)
-        cov[..., 5, 5] = d("sigma_p", 1e-6) ** 2
+        mean = np.stack([w("mu_x", 0.0), w("mu_xp", 0.0), w("mu_y", 0.0), w("mu_yp", 0.0),
+                         np.zeros(shape, work), np.zeros(shape, work)], axis=-1)
+        cov = np.zeros((*shape, 6, 6), dtype=work)
+        cov[..., 0, 0] = w("sigma_x", 175e-9) ** 2
+        cov[..., 0, 1] = cov[..., 1, 0] = w("cor_x", 0.0)
+        cov[..., 1, 1] = w("sigma_xp", 2e-7) ** 2
+        cov[..., 2, 2] = w("sigma_y", 175e-9) ** 2
+        cov[..., 2, 3] = cov[..., 3, 2] = w("cor_y", 0.0)
+        cov[..., 3, 3] = w("sigma_yp", 2e-7) ** 2
+        cov[..., 4, 4] = w("sigma_s", 1e-6) ** 2
+        cov[..., 4, 5] = cov[..., 5, 4] = w("cor_s", 0.0)
+        cov[..., 5, 5] = w("sigma_p", 1e-6) ** 2
+        if on_device:
+            return cls._sampled_on_device(mean, cov, n, d("energy", 1e8), total_charge, shape, dtype, seed)
 
         rng = np.random.default_rng(seed)
         particles = np.ones((*shape, n, 7), dtype=dtype)
@@ -158,10 +201,47 @@ class ParticleBeam(Beam):
         return beam
 
     @classmethod
+    def _sampled_on_device(cls, mean, cov, n: int, energy, total_charge, shape, dtype, seed) -> "ParticleBeam":
+        """Gaussian beam of per-sample `mean` (*shape, 6) and `cov` (*shape, 6, 6), generated in HBM."""
+        rows = gaussian_rows(mean, cov)
+        seed = (int(np.random.SeedSequence().generate_state(1, np.uint64)[0]) if seed is None
+                else int(seed) % (1 << 64))
+        rt = get_runtime()
+        arr = rt.empty((*shape, n, 7), dtype)
+        d_rows = rt.to_device(rows)
+        rt.check(rt.lib.lynx_fill_gaussian_rows(rt.ctx, dtype_code(dtype), len(rows), n, C.c_void_p(d_rows.ptr),
+                                                C.c_uint64(seed), C.c_void_p(arr.ptr)))
+        total_charge = np.asarray(total_charge, dtype=dtype)
+        charges = (np.ones((*shape, n), dtype=dtype) * total_charge[..., None] / n
+                   if np.any(total_charge != 0) else None)
+        beam = cls.__new__(cls)
+        beam._init_raw(Dual(dev=arr), Dual(np.asarray(energy, dtype=dtype)), charges, dtype)
+        if charges is None:
+            beam._zero_charge_shape = shape
+        return beam
+
+    @classmethod
+    def from_parameter_beam(cls, beam, num_particles: int, seed=None) -> "ParticleBeam":
+        """
+        Particles drawn from a `ParameterBeam`'s mean and its whole 6 x 6 covariance (couplings included), generated in
+        HBM as `from_parameters(on_device=True)` generates them.  Energy, total charge and dtype are the beam's.
+        """
+        from .parameter_beam import ParameterBeam
+
+        assert isinstance(beam, ParameterBeam), "from_parameter_beam samples a ParameterBeam."
+        n = int(num_particles)
+        assert n > 0, "A beam has at least one particle."
+        mu, cov = np.asarray(beam._mu, dtype=np.float64), np.asarray(beam._cov, dtype=np.float64)
+        shape = mu.shape[:-1]
+        return cls._sampled_on_device(mu[..., :6], cov[..., :6, :6], n, np.broadcast_to(beam.energy, shape),
+                                      np.broadcast_to(beam.total_charge, shape), shape, beam.dtype, seed)
+
+    @classmethod
     def from_twiss(cls, num_particles=None, beta_x=None, alpha_x=None, emittance_x=None, beta_y=None,
                    alpha_y=None, emittance_y=None, energy=None, sigma_s=None, sigma_p=None, cor_s=None,
-                   total_charge=None, device=None, dtype=np.float32, seed=None) -> "ParticleBeam":
-        """particle_beam.py:180-264."""
+                   total_charge=None, device=None, dtype=np.float32, seed=None,
+                   on_device: bool = False) -> "ParticleBeam":
+        """particle_beam.py:180-264.  `on_device=True`: as in `from_parameters`."""
         dtype = np.dtype(dtype)
         g, shape = _batch_args(dict(beta_x=beta_x, alpha_x=alpha_x, emittance_x=emittance_x, beta_y=beta_y,
                                     alpha_y=alpha_y, emittance_y=emittance_y, energy=energy, sigma_s=sigma_s,
@@ -181,7 +261,7 @@ class ParticleBeam(Beam):
                                    sigma_s=d("sigma_s", 1e-6), sigma_p=d("sigma_p", 1e-6),
                                    energy=d("energy", 1e8), cor_s=d("cor_s", 0.0),
                                    cor_x=-emittance_x * alpha_x, cor_y=-emittance_y * alpha_y,
-                                   total_charge=d("total_charge", 0.0), dtype=dtype, seed=seed)
+                                   total_charge=d("total_charge", 0.0), dtype=dtype, seed=seed, on_device=on_device)
 
     @classmethod
     def uniform_3d_ellipsoid(cls, num_particles=None, radius_x=None, radius_y=None, radius_s=None, sigma_xp=None,
@@ -272,9 +352,22 @@ class ParticleBeam(Beam):
 
     def transformed_to(self, mu_x=None, mu_y=None, mu_xp=None, mu_yp=None, sigma_x=None, sigma_y=None,
                        sigma_xp=None, sigma_yp=None, sigma_s=None, sigma_p=None, energy=None,
-                       total_charge=None, device=None, dtype=None) -> "ParticleBeam":
-        """Affine rescale of the particles to new moments (particle_beam.py:580-715)."""
+                       total_charge=None, device=None, dtype=None, on_device: bool = False) -> "ParticleBeam":
+        """
+        Affine rescale of the particles to new moments (particle_beam.py:580-715).
+
+        `on_device=True` rescales in HBM (`lynx_transform_particles`): the same old and new moments, the same four
+        operations per coordinate in the beam's dtype, but the particles neither come down to the host nor go up
+        again, and the result's particles are a `DeviceArray`.  A shared beam is read as its one stored sample.
+        `dtype=` other than the beam's own is refused on this path.
+        """
         dtype = np.dtype(dtype) if dtype is not None else self.dtype
+        if on_device:  # (checked before the moments are asked for: a refusal needs no pass over the beam)
+            if dtype != self.dtype:
+                raise TypeError(f"transformed_to(on_device=True) keeps the beam's dtype {self.dtype}, got dtype={dtype}")
+            assert all(np.asarray(v).shape == self.batch_shape for v in (
+                mu_x, mu_xp, mu_y, mu_yp, sigma_x, sigma_xp, sigma_y, sigma_yp, sigma_s, sigma_p, energy, total_charge)
+                if v is not None), "Arguments must have the same shape."
         names = ["x", "xp", "y", "yp", "s", "p"]
         given = dict(mu_x=mu_x, mu_xp=mu_xp, mu_y=mu_y, mu_yp=mu_yp, sigma_x=sigma_x, sigma_xp=sigma_xp,
                      sigma_y=sigma_y, sigma_yp=sigma_yp, sigma_s=sigma_s, sigma_p=sigma_p, energy=energy,
@@ -288,6 +381,9 @@ class ParticleBeam(Beam):
         new_sigma = np.stack([pick("sigma_" + n) for n in names], axis=-1)
         old_mu = np.stack([self.mu_x, self.mu_xp, self.mu_y, self.mu_yp, zeros, zeros], axis=-1)
         old_sigma = np.stack([getattr(self, "sigma_" + n) for n in names], axis=-1)
+        if on_device:
+            return self._transformed_on_device(np.concatenate([old_mu, old_sigma, new_sigma, new_mu], axis=-1),
+                                               pick("energy"), total_charge)
         host = np.asarray(self.particles)
         phase_space = (host[..., :6] - old_mu[..., None, :]) / old_sigma[..., None, :] * new_sigma[..., None, :] \
             + new_mu[..., None, :]
@@ -299,6 +395,27 @@ class ParticleBeam(Beam):
             charges = (np.ones(host.shape[:-1], dtype=dtype)
                        * np.asarray(total_charge, dtype)[..., None] / host.shape[-2])
         return self.__class__(particles=particles, energy=pick("energy"), particle_charges=charges, dtype=dtype)
+
+    def _transformed_on_device(self, rows: np.ndarray, energy, total_charge) -> "ParticleBeam":
+        """`transformed_to` in HBM; `rows` (*batch, 24): old means, old sigmas, new sigmas, new means, in the dtype."""
+        rt = get_runtime()
+        batch, n = self.batch_shape, self.num_particles
+        B = int(np.prod(batch, dtype=np.int64))
+        assert rows.shape == (*batch, _ffi.TRANSFORM_ROW) and rows.dtype == self.dtype
+        p = self._particles.device(rt)
+        out = rt.empty((*batch, n, 7), self.dtype)
+        d_rows = rt.to_device(rows)
+        rt.check(rt.lib.lynx_transform_particles(rt.ctx, dtype_code(self.dtype), B, n, C.c_void_p(p.ptr),
+                                                 0 if self.is_shared else n * 7, C.c_void_p(d_rows.ptr),
+                                                 C.c_void_p(out.ptr)))
+        if total_charge is None:
+            charges = self._charges
+        else:
+            charges = np.ones((*batch, n), dtype=self.dtype) * np.asarray(total_charge, self.dtype)[..., None] / n
+        beam = self.__class__.__new__(self.__class__)
+        beam._init_raw(Dual(dev=out), Dual(np.asarray(energy, dtype=self.dtype)),
+                       None if charges is None else np.asarray(charges, dtype=self.dtype), self.dtype)
+        return beam
 
     def broadcast(self, shape: tuple) -> "ParticleBeam":
         """
