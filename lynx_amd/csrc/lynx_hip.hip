@@ -7,6 +7,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <array>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -78,12 +79,21 @@ static void load_knobs(Knobs* k) {
 }
 static inline int knob(int value, int dflt) { return value >= 0 ? value : dflt; }
 
+// A buffer of the library's own, grown on demand (ensure_scratch) and reused in stream order.
+struct Scratch {
+  void* buf = nullptr;
+  size_t bytes = 0;
+};
+
 struct lynx_ctx {
   Knobs knobs;
   int device = 0;
   hipStream_t stream = nullptr;
-  // Second stream for k_build.  The map build of a `track` call depends on the lattice and the
-  // incoming energy only, so it runs underneath the previous call's streaming kernel:
+  hipStream_t s_build = nullptr;  // second stream for k_build (BuildOrder)
+  static constexpr int kTableSlots = 3;
+  hipEvent_t ev_built[kTableSlots] = {};
+  // Who waits for whom before a build.  The map build of a `track` call depends on the lattice and the
+  // incoming energy only, so it runs on a second stream underneath the previous call's streaming kernel:
   //   s_build:  [wait: table slot free] k_build(n) -> table[n % kTableSlots]   record ev_built
   //   host   :  waits for ev_built (LYNX_BUILD_HOST_WAIT=0: the main stream does, with a barrier packet)
   //   stream :  k_track_direct(n)                                              ev_streamed rides on its dispatch
@@ -93,13 +103,83 @@ struct lynx_ctx {
   // main stream later (copies, other kernels, lynx_sync) is ordered after every build so far.  The
   // build stream in turn waits for the main stream when (a) it reuses a table slot (ev_streamed) or
   // (b) the main stream may have written what the build reads (`main_dirty`, `main_wrote`, `slot_wrote`).
-  hipStream_t s_build = nullptr;
-  static constexpr int kTableSlots = 3;
-  hipEvent_t ev_built[kTableSlots] = {}, ev_streamed_own[kTableSlots] = {}, ev_mark = nullptr;
-  hipEvent_t ev_streamed[kTableSlots] = {};  // the slot's current "streamed" event: its own, or a profiled launch's
-  bool streamed_valid[kTableSlots] = {};
+  // The methods are the only code that reads or writes the members (the context makes and destroys the events with its
+  // others: make_sync_events, lynx_ctx_destroy).
+  struct BuildOrder {
+    hipEvent_t ev_streamed_own[kTableSlots] = {}, ev_mark = nullptr;
+    hipEvent_t ev_streamed[kTableSlots] = {};  // the slot's current "streamed" event: its own, or a profiled launch's
+    bool streamed_valid[kTableSlots] = {};
+    // The main stream has enqueued a write that a later build on s_build could read as its incoming energy or its
+    // parameter pool, and nothing has waited for it (h2d copies wait themselves; a streaming kernel's outgoing energy
+    // is `main_wrote` / `slot_wrote`).  Writes no build can read -- images, masks, moment records, fresh beams -- do not
+    // count: marking them would put an ev_mark record and wait into pipelines that have none.
+    bool main_dirty = false;
+    const void* main_wrote = nullptr;   // energy buffer the last streaming kernel published on the main stream
+    // ... and the one each table slot's streaming kernel published: a build that reads the energy of a call further back
+    // than the last one (up = U(beam); x = A(beam); y = B(up)) waits for that slot's ev_streamed.  Kernels kTableSlots
+    // calls back have been waited for with the slot itself; a wait for the whole main stream (ev_mark) clears them all.
+    const void* slot_wrote[kTableSlots] = {};
+
+    // the main stream enqueued a write a build may read (main_stream_writes, kFeedsBuild)
+    void main_wrote_build_input() { main_dirty = true; }
+    // the event a streaming kernel that reads the table in `slot` carries as its stop event
+    hipEvent_t stop_event(int slot) const { return ev_streamed_own[slot]; }
+    // A streaming kernel was enqueued that read the table in `slot` (-1: none) and writes `energy_out` (may be null).
+    // `stop`: what rides on its dispatch.  A call whose build ran on the main stream (`async` false) carries none --
+    // it costs host time: BASELINE config 2 is bound by the host's enqueue rate -- and marks the main stream dirty
+    // instead, which makes the next asynchronous build wait for everything enqueued here.
+    void streamed(int slot, bool async, hipEvent_t stop, const void* energy_out) {
+      if (slot >= 0) {
+        ev_streamed[slot] = stop;
+        streamed_valid[slot] = async && stop != nullptr;
+        if (!async) main_dirty = true;
+        slot_wrote[slot] = energy_out;
+      }
+      if (energy_out) main_wrote = energy_out;  // a later build that reads it must wait for this kernel
+    }
+    // The table in `slot` has been read on `main` up to here (a reverse pass that reads the forward call's table): the
+    // slot's next build waits for this, too.
+    hipError_t read_until_here(int slot, hipStream_t main) {
+      const hipError_t e = hipEventRecord(ev_streamed_own[slot], main);
+      if (e != hipSuccess) return e;
+      ev_streamed[slot] = ev_streamed_own[slot];
+      streamed_valid[slot] = true;
+      return hipSuccess;
+    }
+    // Orders a build on `bs` into `slot` that reads the energy `energy` behind what it depends on, in this order: the
+    // streaming kernel that last read the slot; the tail of the streaming kernel before the one enqueued last
+    // (`tail_flag` reaching `tail_value`; null: no such wait); and what the main stream may have written of its inputs.
+    hipError_t order_build(hipStream_t bs, hipStream_t main, int slot, const void* energy, unsigned int* tail_flag,
+                           uint32_t tail_value) {
+      hipError_t e = hipSuccess;
+      // the table slot was last read by the streaming kernel kTableSlots calls ago
+      if (streamed_valid[slot] && (e = hipStreamWaitEvent(bs, ev_streamed[slot], 0)) != hipSuccess) return e;
+      // ... and the build starts in the TAIL of the streaming kernel before the one enqueued last (which has the GPU
+      // to itself when it gets there), not at that kernel's head
+      if (tail_flag && (e = hipStreamWaitValue32(bs, tail_flag, tail_value, hipStreamWaitValueGte, 0xffffffffu)) != hipSuccess)
+        return e;
+      // what the build reads (energy, lattice pool) may have been written on the main stream
+      if (main_dirty || (main_wrote && main_wrote == energy)) {
+        if ((e = hipEventRecord(ev_mark, main)) != hipSuccess || (e = hipStreamWaitEvent(bs, ev_mark, 0)) != hipSuccess) return e;
+        main_dirty = false;
+        main_wrote = nullptr;
+        for (const void*& w : slot_wrote) w = nullptr;
+      } else {
+        // ... by a streaming kernel further back than the last one: the tail flag says that kernel's last workgroups have
+        // been dispatched, not that they have written the energy
+        for (int i = 0; i < kTableSlots; ++i)
+          if (i != slot && slot_wrote[i] == energy && energy && streamed_valid[i] &&
+              (e = hipStreamWaitEvent(bs, ev_streamed[i], 0)) != hipSuccess)
+            return e;
+      }
+      return hipSuccess;
+    }
+    // No stop event may be waited for any more (they are about to be destroyed, or both streams are idle).
+    void forget_stop_events() {
+      for (bool& v : streamed_valid) v = false;
+    }
+  } order;
   unsigned seq = 0;
-  bool main_dirty = false;            // unsynchronised device writes on the main stream (any buffer)
   // Nothing enqueued on the main stream since the host last waited for it.  Kept by the library itself (set by
   // sync_main, cleared by every entry point that enqueues): asking the runtime -- hipStreamQuery -- puts a marker
   // packet into the queue whose release costs the next kernel ~5 us behind a kernel that left dirty lines in L2.
@@ -126,13 +206,21 @@ struct lynx_ctx {
       const char *a = (const char*)dst, *e = (const char*)energy;
       if (valid && a < e + energy_bytes && a + bytes > e) valid = false;
     }
+    // a forward call has built the table in `slot_` (call number `seq_`) from the energies [energy_in, + energy_bytes_)
+    void leave(const lynx_lattice* lat_, uint64_t version_, const void* energy_in, size_t energy_bytes_, const void* energy_out,
+               int slot_, int merged_, bool units_, unsigned seq_) {
+      lat = lat_;
+      version = version_;
+      energy = energy_in;
+      energy_bytes = energy_bytes_;
+      slot = slot_;
+      merged = merged_;
+      units = units_;
+      seq = seq_;
+      valid = energy_out != energy_in;  // (a call that overwrites its own incoming energy leaves nothing to come back to)
+    }
   } fwd_table;
-  const void* main_wrote = nullptr;   // energy buffer the last streaming kernel published on the main stream
-  // ... and the one each table slot's streaming kernel published: a build that reads the energy of a call further back
-  // than the last one (up = U(beam); x = A(beam); y = B(up)) waits for that slot's ev_streamed.  Kernels kTableSlots
-  // calls back have been waited for with the slot itself; a wait for the whole main stream (ev_mark) clears them all.
-  const void* slot_wrote[kTableSlots] = {};
-  std::mutex mu;                      // allocator maps and fwd_table: finalizers may run on other threads
+  std::mutex mu;                     // allocator maps and fwd_table: finalizers may run on other threads
   // every entry point that writes device memory on the caller's behalf says so here, under the lock
   void wrote(const void* dst, size_t bytes) {
     if (!dst || bytes == 0) return;
@@ -155,38 +243,32 @@ struct lynx_ctx {
   std::multimap<size_t, void*> free_blocks;
   std::unordered_map<void*, size_t> live;
   std::vector<std::pair<const char*, size_t>> host_ranges;  // the host-visible blocks there are (live or cached)
-  // internal scratch (grown on demand, stream-ordered reuse)
-  void* scratch_level = nullptr;  // second level of the moment reduction (long beams)
-  size_t scratch_level_bytes = 0;
-  unsigned int* scratch_tickets = nullptr;  // ... and its per-sample tickets (k_reduce_moments_ticket): zero between launches
-  size_t scratch_tickets_count = 0;
-  void* scratch_obs = nullptr;  // per-workgroup sums of x, y at the observers [B][chunks][2 * LYNX_MAX_OBSERVERS]
-  size_t scratch_obs_bytes = 0;
-  void* scratch_erun = nullptr;      // k_cavity_flags: every sample's energy on its way through the cavities
-  size_t scratch_erun_bytes = 0;
-  void* scratch_esteps = nullptr;    // k_cavity_flags_spec -> lanes build: every sample's energy behind 0, 1, ... step cavities [k][Bp]
-  size_t scratch_esteps_bytes = 0;
-  int32_t* d_spec_valid = nullptr;   // ... and whether they hold (k_cavity_flags)
-  void* scratch_products = nullptr;  // lanes = samples build: piece / pair products [slot][49][Bp] float64
-  size_t scratch_products_bytes = 0;
-  void* scratch_coefs = nullptr;     // ... and cavity coefficients [S][8][Bp]
-  size_t scratch_coefs_bytes = 0;
   static constexpr int kTableBwd = kTableSlots, kTablePb = kTableSlots + 1, kTableTrace = kTableSlots + 2;
-  void* scratch_steps[kTableSlots + 3] = {};  // the ring of step tables, the reverse pass's own, the ParameterBeam lanes path's, the beam trace's
-  size_t scratch_steps_bytes[kTableSlots + 3] = {};
-  void* scratch_trace[2] = {nullptr, nullptr};  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
-  size_t scratch_trace_bytes[2] = {0, 0};
-  void* scratch_trace_plan = nullptr;  // ... with losses or screens: step codes and screen rows (TraceLosses.plan), and what was uploaded last
-  size_t scratch_trace_plan_bytes = 0;
+  static constexpr int kPartialRing = 4;
+  // Internal scratch (grown on demand, stream-ordered reuse).  Nothing but Scratch members: lynx_ctx_destroy walks the
+  // struct as the array of them it is, so a new buffer is one line here.
+  struct ScratchSet {
+    Scratch level;     // second level of the moment reduction (long beams)
+    Scratch tickets;   // ... and its per-sample tickets (k_reduce_moments_ticket, unsigned int): zero between launches
+    Scratch obs;       // per-workgroup sums of x, y at the observers [B][chunks][2 * LYNX_MAX_OBSERVERS]
+    Scratch erun;      // k_cavity_flags: every sample's energy on its way through the cavities
+    Scratch esteps;    // k_cavity_flags_spec -> lanes build: every sample's energy behind 0, 1, ... step cavities [k][Bp]
+    Scratch products;  // lanes = samples build: piece / pair products [slot][49][Bp] float64
+    Scratch coefs;     // ... and cavity coefficients [S][8][Bp]
+    Scratch steps[kTableSlots + 3];  // the ring of step tables, the reverse pass's own, the ParameterBeam lanes path's, the beam trace's
+    Scratch trace[2];  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
+    Scratch trace_plan;  // ... with losses or screens: step codes and screen rows (TraceLosses.plan); lynx_ctx::trace_plan is what was uploaded last
+    Scratch image_grad;  // lynx_gaussian_images_along_backward: the workgroups' partial sums [B][chunks][6] float64, screen after screen
+    Scratch units[2 * kTableSlots];  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
+    Scratch units_bwd[2];  // ... and of the reverse pass's own table
+    Scratch grad[3];   // backward: partials, T_bar, build scratch
+    Scratch partials[kPartialRing];  // the workgroups' moment records, one buffer per slot of partial_ring
+    Scratch* begin() { return reinterpret_cast<Scratch*>(this); }
+    Scratch* end() { return reinterpret_cast<Scratch*>(this + 1); }
+  } scratch;
+  static_assert(std::is_standard_layout<Scratch>::value && sizeof(ScratchSet) % sizeof(Scratch) == 0, "ScratchSet: Scratch members only");
+  int32_t* d_spec_valid = nullptr;   // whether scratch.esteps holds (k_cavity_flags)
   std::vector<int64_t> trace_plan;
-  void* scratch_image_grad = nullptr;  // lynx_gaussian_images_along_backward: the workgroups' partial sums [B][chunks][6] float64, screen after screen
-  size_t scratch_image_grad_bytes = 0;
-  void* scratch_units_bwd[2] = {nullptr, nullptr};  // ... and of the reverse pass's own table
-  size_t scratch_units_bwd_bytes[2] = {0, 0};
-  void* scratch_units[2 * kTableSlots] = {};  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
-  size_t scratch_units_bytes[2 * kTableSlots] = {};
-  void* scratch_grad[3] = {nullptr, nullptr, nullptr};  // backward: partials, T_bar, build scratch
-  size_t scratch_grad_bytes[3] = {0, 0, 0};
   ncclComm_t comm = nullptr;
   int comm_ranks = 0;
   // The SIDE stream: what follows a streaming kernel without anything on this GPU waiting for it -- the reduction of
@@ -211,12 +293,9 @@ struct lynx_ctx {
   std::vector<SideOp> side_ops;         // in flight, oldest first (one stream: they finish in order)
   std::vector<hipEvent_t> side_events;  // idle "done" events
   bool side_busy = false;               // s_side may still be writing a block: readers wait for it
-  bool level_on_side = false;           // which stream the users of scratch_level ran on last
+  bool level_on_side = false;           // which stream the users of scratch.level ran on last
   const void* side_wrote = nullptr;     // moment block the last side reduction writes (a gather of it needs no marker)
-  static constexpr int kPartialRing = 4;
-  struct PartialSlot {
-    void* buf = nullptr;
-    size_t bytes = 0;
+  struct PartialSlot {  // (its buffer: scratch.partials)
     hipEvent_t track_done = nullptr;  // rides on the streaming kernel's dispatch
     hipEvent_t reduced = nullptr;     // recorded on s_side behind the reduction
     bool pending = false;             // `reduced` has been recorded and not yet seen complete
@@ -474,38 +553,89 @@ static int ctx_free(lynx_ctx* ctx, void* p) {
   return LYNX_OK;
 }
 
-static int ensure_scratch(lynx_ctx* ctx, void** buf, size_t* have, size_t need) {
-  if (*have >= need) return LYNX_OK;
-  if (*buf) {
+static int ensure_scratch(lynx_ctx* ctx, Scratch& s, size_t need) {
+  if (s.bytes >= need) return LYNX_OK;
+  if (s.buf) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->s_build));
     HIP_TRY(ctx, sync_main(ctx));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->s_side));
-    HIP_TRY(ctx, hipFree(*buf));
-    *buf = nullptr;
-    *have = 0;
+    HIP_TRY(ctx, hipFree(s.buf));
+    s = Scratch();
   }
   const size_t sz = size_class(need);
-  HIP_TRY(ctx, hipMalloc(buf, sz));
-  *have = sz;
+  HIP_TRY(ctx, hipMalloc(&s.buf, sz));
+  s.bytes = sz;
   return LYNX_OK;
 }
 
 // per-sample tickets of k_reduce_moments_ticket, zeroed when they are (re)allocated; the kernel leaves them zero
 static int ensure_tickets(lynx_ctx* ctx, size_t count) {
-  if (ctx->scratch_tickets_count >= count) return LYNX_OK;
-  void* buf = ctx->scratch_tickets;
-  size_t have = ctx->scratch_tickets_count * sizeof(unsigned int);
-  const int rc = ensure_scratch(ctx, &buf, &have, std::max<size_t>(count, 1024) * sizeof(unsigned int));
+  Scratch& tickets = ctx->scratch.tickets;
+  if (tickets.bytes >= count * sizeof(unsigned int)) return LYNX_OK;
+  const int rc = ensure_scratch(ctx, tickets, std::max<size_t>(count, 1024) * sizeof(unsigned int));
   if (rc) return rc;
-  ctx->scratch_tickets = (unsigned int*)buf;
-  ctx->scratch_tickets_count = have / sizeof(unsigned int);
   // (hipMemset runs on the null stream and need not have finished when it returns; the context's streams do not wait for
   // that stream -- a reduction launched right behind this took tickets that the fill then wiped: one moment record of
   // zeros in the first call of a process, once in about thirty processes)
-  HIP_TRY(ctx, hipMemsetAsync(buf, 0, have, ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(tickets.buf, 0, tickets.bytes, ctx->stream));
   HIP_TRY(ctx, sync_main(ctx));
   return LYNX_OK;
 }
+
+// the GPU's compute units (256 if the runtime reports none)
+static int64_t compute_units(const lynx_ctx* ctx) {
+  return ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+}
+
+// One body for both element types: `body` is a generic lambda that is handed a zero of the type -- `using T =
+// decltype(zero);`.  Whatever is not LYNX_F64 is float (entry points that are handed a dtype and care check it themselves).
+template <typename F>
+static auto with_dtype(int dtype, F&& body) {
+  return dtype == LYNX_F64 ? body(double()) : body(float());
+}
+
+// ---- the prologue of an entry point that enqueues on the main stream --------------------------
+// Every such entry point reads, in this order:
+//   LYNX_MAIN_ENTRY(ctx);                                    the context is there, and the main stream is idle no longer
+//   ... its own checks (every refusal in front of what follows) ...
+//   LYNX_MAIN_WRITES(ctx, kFeedsBuild | kFeedsNoBuild, {{pointer, bytes}, ...});
+//                                                            this thread's device; what the call writes for the caller
+// (lynx_track_particles and lynx_track_particles_backward say why they differ, where they do.)
+#define LYNX_MAIN_ENTRY(ctx)                                                                \
+  LYNX_NEED(ctx);                                                                           \
+  (ctx)->main_idle = false /* (something is about to be enqueued on the main stream) */
+
+// Device memory [p, p + bytes) that a call writes on the caller's behalf (a null pointer or no bytes: nothing).
+struct Written {
+  const void* p;
+  size_t bytes;
+};
+// Whether the call's work on the main stream may write something that a later build on s_build reads -- its incoming
+// energy or the lattice's parameter pool (BuildOrder::main_dirty has the rule).  kFeedsBuild: copies and fills between
+// the caller's blocks, lynx_build_compose, the reverse passes, the ParameterBeam calls, the traces and the screen images
+// along a trace, whose outputs a caller may hand to a track call as an energy.  kFeedsNoBuild: everything else -- an
+// image, a mask, a moment record, a fresh beam, a diagnostic is never an energy or a pool, and a track call with steps
+// says what it publishes itself (BuildOrder::streamed).
+enum FeedsBuild : bool { kFeedsNoBuild = false, kFeedsBuild = true };
+
+// what the call writes for the caller, without the device: for entry points that have never set it (lynx_buf_d2d,
+// lynx_buf_memset) and for what is said behind a pass (lynx_track_particles_backward)
+template <typename Outputs = std::initializer_list<Written>>
+static void caller_blocks_written(lynx_ctx* ctx, FeedsBuild feeds, const Outputs& outputs) {
+  for (const Written& w : outputs) ctx->wrote(w.p, w.bytes);
+  if (feeds) ctx->order.main_wrote_build_input();
+}
+
+template <typename Outputs = std::initializer_list<Written>>
+static int main_stream_writes(lynx_ctx* ctx, FeedsBuild feeds, const Outputs& outputs) {
+  HIP_TRY(ctx, use_device(ctx));
+  caller_blocks_written(ctx, feeds, outputs);
+  return LYNX_OK;
+}
+#define LYNX_MAIN_WRITES(ctx, feeds, ...)                                                   \
+  do {                                                                                      \
+    if (const int rc_ = main_stream_writes((ctx), (feeds), __VA_ARGS__)) return rc_;        \
+  } while (0)
 
 // The API functions below get C linkage from their declarations in include/lynx_hip.h.
 
@@ -536,10 +666,10 @@ static int make_sync_events(lynx_ctx* ctx) {
   }
   for (int i = 0; i < lynx_ctx::kTableSlots; ++i) {
     HIP_TRY(ctx, make(&ctx->ev_built[i]));
-    HIP_TRY(ctx, make(&ctx->ev_streamed_own[i]));
-    ctx->streamed_valid[i] = false;
+    HIP_TRY(ctx, make(&ctx->order.ev_streamed_own[i]));
   }
-  HIP_TRY(ctx, make(&ctx->ev_mark));
+  ctx->order.forget_stop_events();
+  HIP_TRY(ctx, make(&ctx->order.ev_mark));
   for (hipEvent_t e : ctx->side_events) (void)hipEventDestroy(e);  // idle "done" events: made again on demand
   ctx->side_events.clear();
   return LYNX_OK;
@@ -617,38 +747,20 @@ int lynx_ctx_destroy(lynx_ctx* ctx) {
   for (auto& slot : ctx->partial_ring) {
     (void)hipEventDestroy(slot.track_done);
     (void)hipEventDestroy(slot.reduced);
-    if (slot.buf) (void)hipFree(slot.buf);
   }
   (void)hipStreamDestroy(ctx->s_side);
   for (auto& kv : ctx->free_blocks) free_block(ctx, kv.second, kv.first);
   for (auto& kv : ctx->live) free_block(ctx, kv.first, kv.second);
-  if (ctx->scratch_level) (void)hipFree(ctx->scratch_level);
-  if (ctx->scratch_tickets) (void)hipFree(ctx->scratch_tickets);
-  if (ctx->scratch_obs) (void)hipFree(ctx->scratch_obs);
-  if (ctx->scratch_erun) (void)hipFree(ctx->scratch_erun);
-  if (ctx->scratch_esteps) (void)hipFree(ctx->scratch_esteps);
+  for (Scratch& s : ctx->scratch)
+    if (s.buf) (void)hipFree(s.buf);
   if (ctx->d_spec_valid) (void)hipFree(ctx->d_spec_valid);
-  if (ctx->scratch_products) (void)hipFree(ctx->scratch_products);
-  if (ctx->scratch_coefs) (void)hipFree(ctx->scratch_coefs);
-  for (int i = 0; i < lynx_ctx::kTableSlots + 3; ++i)
-    if (ctx->scratch_steps[i]) (void)hipFree(ctx->scratch_steps[i]);
-  for (int i = 0; i < 2; ++i)
-    if (ctx->scratch_trace[i]) (void)hipFree(ctx->scratch_trace[i]);
-  if (ctx->scratch_trace_plan) (void)hipFree(ctx->scratch_trace_plan);
-  if (ctx->scratch_image_grad) (void)hipFree(ctx->scratch_image_grad);
-  for (int i = 0; i < 2 * lynx_ctx::kTableSlots; ++i)
-    if (ctx->scratch_units[i]) (void)hipFree(ctx->scratch_units[i]);
-  for (int i = 0; i < 2; ++i)
-    if (ctx->scratch_units_bwd[i]) (void)hipFree(ctx->scratch_units_bwd[i]);
-  for (int i = 0; i < 3; ++i)
-    if (ctx->scratch_grad[i]) (void)hipFree(ctx->scratch_grad[i]);
   for (int i = 0; i < lynx_ctx::kTableSlots; ++i) {
     (void)hipEventDestroy(ctx->ev_built[i]);
-    (void)hipEventDestroy(ctx->ev_streamed_own[i]);
+    (void)hipEventDestroy(ctx->order.ev_streamed_own[i]);
   }
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->d_tail_flag) (void)hipFree(ctx->d_tail_flag);
-  (void)hipEventDestroy(ctx->ev_mark);
+  (void)hipEventDestroy(ctx->order.ev_mark);
   (void)hipEventDestroy(ctx->ev_start);
   (void)hipEventDestroy(ctx->ev_stop);
   (void)hipStreamDestroy(ctx->s_build);
@@ -744,8 +856,7 @@ int lynx_sync(lynx_ctx* ctx) {
 }
 
 int lynx_timer_start(lynx_ctx* ctx) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   HIP_TRY(ctx, hipEventRecord(ctx->ev_start, ctx->stream));
   return LYNX_OK;
 }
@@ -766,7 +877,7 @@ int lynx_profile_begin(lynx_ctx* ctx) {
   if (!ctx->prof_events.empty()) {
     HIP_TRY(ctx, hipStreamSynchronize(ctx->s_build));
     HIP_TRY(ctx, sync_main(ctx));
-    for (bool& v : ctx->streamed_valid) v = false;
+    ctx->order.forget_stop_events();
     ctx->last_stream_stop = nullptr;
   }
   for (auto& pr : ctx->prof_events) {
@@ -789,7 +900,7 @@ int lynx_profile_end(lynx_ctx* ctx, double* total_ms, int64_t* launches) {
   HIP_TRY(ctx, sync_main(ctx));
   // every build is followed by its streaming kernel on the main stream, so both streams are idle now;
   // the per-launch stop events stood in for the step-table slots' "streamed" events and go away here
-  for (bool& v : ctx->streamed_valid) v = false;
+  ctx->order.forget_stop_events();
   double total = 0.0;
   ctx->prof_ms.clear();
   for (auto& pr : ctx->prof_events) {
@@ -896,31 +1007,27 @@ int lynx_buf_d2h(lynx_ctx* ctx, void* h_dst, const void* d_src, size_t bytes) {
 }
 
 int lynx_buf_d2d(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (bytes == 0) return LYNX_OK;
   {
     const int rc = join_side(ctx);  // the source may be a moment record the side stream is still reducing
     if (rc) return rc;
   }
-  ctx->wrote(d_dst, bytes);
+  caller_blocks_written(ctx, kFeedsBuild, {{d_dst, bytes}});
   // (either side may be a host-visible block: the runtime works the direction out from the addresses)
   HIP_TRY(ctx, hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDefault, ctx->stream));
-  ctx->main_dirty = true;
   return LYNX_OK;
 }
 
 int lynx_buf_memset(lynx_ctx* ctx, void* d_dst, int value, size_t bytes) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (bytes == 0) return LYNX_OK;
   {
     const int rc = join_side(ctx);
     if (rc) return rc;
   }
-  ctx->wrote(d_dst, bytes);
+  caller_blocks_written(ctx, kFeedsBuild, {{d_dst, bytes}});
   HIP_TRY(ctx, hipMemsetAsync(d_dst, value, bytes, ctx->stream));
-  ctx->main_dirty = true;
   return LYNX_OK;
 }
 
@@ -1175,7 +1282,7 @@ static int allow_lds(lynx_ctx* ctx, K kernel, size_t bytes) {
 // the short chunk's share of the GPU under the streaming kernel).
 template <typename T>
 static void build_shape(lynx_ctx* ctx, const lynx_lattice* lat, bool underneath, int* threads, int* chunk) {
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t cus = compute_units(ctx);
   const bool deep = lat->batch * 2 <= cus && !underneath;
   *threads = 256;
   // (float32, at most one workgroup per CU: 64 again -- half the rounds; the 128-sample shard of BASELINE config 4
@@ -1191,13 +1298,13 @@ static int launch_cavity_flags(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t str
                                bool for_lanes_build = false) {
   if (!lat->has_cavity || lat->n_steps == 0) return LYNX_OK;
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_erun, &ctx->scratch_erun_bytes, (size_t)lat->batch * sizeof(T)))) return rc;
+  if ((rc = ensure_scratch(ctx, ctx->scratch.erun, (size_t)lat->batch * sizeof(T)))) return rc;
   // the lanes build reads every sample's energy in front of every step from what the first kernel computes on its way
   const int64_t Bp = (lat->batch + 63) / 64 * 64;
   T* e_steps = nullptr;
   if (for_lanes_build) {
-    if ((rc = ensure_scratch(ctx, &ctx->scratch_esteps, &ctx->scratch_esteps_bytes, (size_t)(lat->n_step_cavities + 1) * Bp * sizeof(T)))) return rc;
-    e_steps = (T*)ctx->scratch_esteps;
+    if ((rc = ensure_scratch(ctx, ctx->scratch.esteps, (size_t)(lat->n_step_cavities + 1) * Bp * sizeof(T)))) return rc;
+    e_steps = (T*)ctx->scratch.esteps.buf;
   }
   // the predicates for every cavity at once, assuming every batch gains energy (one lane per sample), then one small
   // workgroup that checks the assumption, publishes the bits and -- should it not hold -- walks the serial way
@@ -1205,7 +1312,7 @@ static int launch_cavity_flags(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t str
                      lat->d_cavs, lat->n_cavities, (const T*)d_energy_in, lat->d_cav_words, e_steps, Bp);
   HIP_TRY(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_cavity_flags<T>, dim3(1), dim3(256), 0, stream, dev_view(lat), lat->d_elems, lat->d_steps,
-                     (const T*)d_energy_in, (T*)ctx->scratch_erun, ctx->d_status, lat->d_cavs, lat->n_cavities,
+                     (const T*)d_energy_in, (T*)ctx->scratch.erun.buf, ctx->d_status, lat->d_cavs, lat->n_cavities,
                      lat->d_cav_words, e_steps ? ctx->d_spec_valid : (int32_t*)nullptr);
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
@@ -1276,15 +1383,15 @@ static int launch_build_lanes(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stre
   if ((rc = plan_lanes_build(ctx, lat, std::max(1, ctx->knobs.piece)))) return rc;
   const int64_t groups = (lat->batch + 63) / 64, Bp = groups * 64;
   if (lat->n_pieces > 65535 || lat->n_steps > 65535) return fail(ctx, LYNX_ERR_INVALID, "lattice too long for the lanes build");
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_products, &ctx->scratch_products_bytes, (size_t)lat->n_slots * 49 * Bp * sizeof(double))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.products, (size_t)lat->n_slots * 49 * Bp * sizeof(double))))
     return rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_coefs, &ctx->scratch_coefs_bytes, (size_t)std::max(1, lat->n_steps) * 8 * Bp * sizeof(T))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.coefs, (size_t)std::max(1, lat->n_steps) * 8 * Bp * sizeof(T))))
     return rc;
   const LatticeDev lv = dev_view(lat);
-  const StepEnergies<T> se{lat->has_cavity ? (const T*)ctx->scratch_esteps : (const T*)nullptr, lat->d_cav_before, ctx->d_spec_valid, Bp};
+  const StepEnergies<T> se{lat->has_cavity ? (const T*)ctx->scratch.esteps.buf : (const T*)nullptr, lat->d_cav_before, ctx->d_spec_valid, Bp};
   if ((rc = allow_lds(ctx, k_build_pieces<T>, build_pieces_lds<T>()))) return rc;
   hipLaunchKernelGGL(k_build_pieces<T>, dim3((unsigned)groups, (unsigned)lat->n_pieces), dim3(64), build_pieces_lds<T>(), stream, lv,
-                     lat->d_pieces, (const T*)d_energy_in, Bp, (double*)ctx->scratch_products, (T*)ctx->scratch_coefs, se);
+                     lat->d_pieces, (const T*)d_energy_in, Bp, (double*)ctx->scratch.products.buf, (T*)ctx->scratch.coefs.buf, se);
   HIP_TRY(ctx, hipGetLastError());
   // narrow trees (BASELINE config 4: 8, 4, 2, 1 tasks per level) in one launch: underneath a streaming kernel every
   // launch of the chain costs ~20 us, the product itself 3-6 (config 4: 0.995 -> 0.985 ms/step, same box)
@@ -1298,18 +1405,18 @@ static int launch_build_lanes(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stre
       lv.count[l] = lat->levels[l].second;
     }
     hipLaunchKernelGGL(k_pair_levels, dim3((unsigned)groups), dim3(256), 0, stream, lv, lat->d_tasks, lat->batch, Bp,
-                       (double*)ctx->scratch_products);
+                       (double*)ctx->scratch.products.buf);
     HIP_TRY(ctx, hipGetLastError());
   } else {
     for (const auto& level : lat->levels) {
       hipLaunchKernelGGL(k_pair_products, dim3((unsigned)groups, (unsigned)level.second), dim3(64), 0, stream,
-                         lat->d_tasks + level.first, lat->batch, Bp, (double*)ctx->scratch_products);
+                         lat->d_tasks + level.first, lat->batch, Bp, (double*)ctx->scratch.products.buf);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
   hipLaunchKernelGGL(k_emit_steps<T>, dim3((unsigned)groups, (unsigned)lat->n_steps), dim3(64), emit_steps_lds<T>(), stream, lv,
-                     lat->d_step_slot, (const T*)d_energy_in, Bp, (const double*)ctx->scratch_products,
-                     (const T*)ctx->scratch_coefs, merge_pairs, (T*)d_steps_out, (T*)d_energy_out,
+                     lat->d_step_slot, (const T*)d_energy_in, Bp, (const double*)ctx->scratch.products.buf,
+                     (const T*)ctx->scratch.coefs.buf, merge_pairs, (T*)d_steps_out, (T*)d_energy_out,
                      d_units ? lat->d_step_unit[merge_pairs ? 1 : 0] : (const int32_t*)nullptr,
                      lat->units[merge_pairs ? 1 : 0].n_units, d_units, d_extras, se);
   HIP_TRY(ctx, hipGetLastError());
@@ -1374,17 +1481,15 @@ static int launch_build(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stream, co
 
 int lynx_build_compose(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, void* d_steps_out,
                        void* d_energy_out) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_steps_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
   const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_steps_out, (size_t)lat->batch * lat->n_steps * LYNX_STEP_STRIDE * es);
-  ctx->wrote(d_energy_out, (size_t)lat->batch * es);
-  return lat->dtype == LYNX_F64 ? launch_build<double>(ctx, lat, ctx->stream, d_energy_in, d_steps_out, d_energy_out)
-                                : launch_build<float>(ctx, lat, ctx->stream, d_energy_in, d_steps_out, d_energy_out);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_steps_out, (size_t)lat->batch * lat->n_steps * LYNX_STEP_STRIDE * es},
+                                      {d_energy_out, (size_t)lat->batch * es}});
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return launch_build<decltype(zero)>(ctx, lat, ctx->stream, d_energy_in, d_steps_out, d_energy_out);
+  });
 }
 
 // ---- particle tracking -----------------------------------------------------------------
@@ -1406,7 +1511,7 @@ static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, i
   TrackPlan p;
   p.full_cov = full_cov;
   constexpr int P = 16 / (int)sizeof(T);  // particles per lane of a wave tile
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t cus = compute_units(ctx);
   const Knobs& kn = ctx->knobs;
   const int64_t target = 512 * cus;  // workgroups per CU over the whole launch
   p.mom_mode = knob(kn.mom, sizeof(T) == 4 ? 2 : 1);
@@ -1640,24 +1745,18 @@ struct TrackTable {
   bool tail = false;        // ... behind the tail of an earlier streaming kernel: this call's kernel announces its own
   bool short_call = false;  // from half a million particles up to 128 MB of them, no cavity
   const void* d_steps = nullptr;
-  const void* d_units = nullptr;  // use_units: the slot's compact unit records and their class-D extras
-  const void* d_extras = nullptr;
+  float* d_units = nullptr;  // use_units: the slot's compact unit records and their class-D extras
+  float* d_extras = nullptr;
   int n_units = 0;
   bool use_units = false;   // the structured step loop (k_track_units / k_track_unit_pairs) walks this call
 };
 
-// Builds the step table of this call: takes the next slot of the ring, decides the merged form (p.a.merged_pairs and,
-// with it, the LDS stash behind the table), where the build runs and who waits for it, launches it, and leaves the table
-// to a reverse pass that may follow (lynx_ctx::fwd_table).
+// -- the stages of track_table --
+
+// The merged form: [run, cavity] pairs as one unit for the packed float32 step loop (one 7x7 application per pair;
+// LYNX_TRACK_SEQUENTIAL_STEPS keeps every step on its own), and with it the LDS stash behind the table.
 template <typename T>
-static int track_table(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, int32_t S, const void* d_energy_in,
-                       const void* d_energy_out, int flags, TrackPlan& p, TrackTable* t) {
-  int rc;
-  const int slot = t->slot = (int)(ctx->seq++ % (unsigned)lynx_ctx::kTableSlots);
-  const size_t need = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[slot], &ctx->scratch_steps_bytes[slot], need))) return rc;
-  // [run, cavity] pairs in merged form for the packed float32 step loop (one 7x7 application
-  // per pair); LYNX_TRACK_SEQUENTIAL_STEPS keeps every step on its own
+static void table_merged_form(const lynx_ctx* ctx, const lynx_lattice* lat, int32_t S, int flags, TrackPlan& p) {
   bool has_pair = false;
   for (int32_t s = 1; s < S; ++s)
     has_pair |= lat->h_steps[s].kind == LYNX_STEP_CAVITY && lat->h_steps[s - 1].kind == LYNX_STEP_RUN &&
@@ -1669,100 +1768,114 @@ static int track_table(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, i
     p.a.stash_offset = (int32_t)p.lds;
     p.lds += (size_t)kTrackThreads * 4 * sizeof(float);
   }
-  // The second stream pays once the streaming kernel is long enough to hide a build under; below half a
-  // million particles per call the extra event traffic costs more host time than the overlap returns
-  // (BASELINE config 2: 31 -> 46 us per call with it).
-  // SHORT calls in between (from half a million particles up to 128 MB of them: BASELINE config 3, 1 M particles,
-  // 29 us of kernel) take what the queue says: kernels of one queue follow each other without a gap, a hop to
-  // another queue costs 10-20 us of latency (kernel timeline, profiles/r04_*_timeline.txt).  If the main stream is
-  // IDLE -- the caller waits for every result -- there is nothing to hide the build under and the hops are pure
-  // loss: build, stream and reduce back to back on the main stream, no event at all.  If it is BUSY -- calls are
-  // pipelined -- the build goes to the second stream, where it runs underneath the previous call's kernels, and only
-  // the reduction stays in line (the side stream's hop is worth it for long kernels only).
+}
+
+// Where the build runs (t->short_call, t->async).
+// The second stream pays once the streaming kernel is long enough to hide a build under; below half a
+// million particles per call the extra event traffic costs more host time than the overlap returns
+// (BASELINE config 2: 31 -> 46 us per call with it).
+// SHORT calls in between (from half a million particles up to 128 MB of them: BASELINE config 3, 1 M particles,
+// 29 us of kernel) take what the queue says: kernels of one queue follow each other without a gap, a hop to
+// another queue costs 10-20 us of latency (kernel timeline, profiles/r04_*_timeline.txt).  If the main stream is
+// IDLE -- the caller waits for every result -- there is nothing to hide the build under and the hops are pure
+// loss: build, stream and reduce back to back on the main stream, no event at all.  If it is BUSY -- calls are
+// pipelined -- the build goes to the second stream, where it runs underneath the previous call's kernels, and only
+// the reduction stays in line (the side stream's hop is worth it for long kernels only).
+template <typename T>
+static void table_build_stream(const lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, int64_t N, TrackTable* t) {
   const bool half_million = B * N >= (int64_t)512 << 10;
   t->short_call = half_million && (size_t)B * N * 7 * sizeof(T) < ((size_t)128 << 20) && !lat->has_cavity;
   bool inline_all = false;
   if (t->short_call && ctx->knobs.async_build < 0)
     inline_all = knob(ctx->knobs.small_inline, ctx->main_idle ? 1 : 0) != 0;
-  const bool async = t->async = knob(ctx->knobs.async_build, half_million && !inline_all ? 1 : 0) != 0;
-  hipStream_t bs = async ? ctx->s_build : ctx->stream;
-  if (async) {
-    // the table slot was last read by the streaming kernel kTableSlots calls ago
-    if (ctx->streamed_valid[slot]) HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_streamed[slot], 0));
-    // ... and the build starts in the TAIL of the streaming kernel before the one enqueued last (which has the GPU
-    // to itself when it gets there), not at that kernel's head
-    t->tail = ctx->can_wait_value && ctx->knobs.build_in_tail && !t->short_call;  // (a short kernel has no tail worth waiting for)
-    if (t->tail && ctx->tail_seq >= 2)
-      HIP_TRY(ctx, hipStreamWaitValue32(bs, ctx->d_tail_flag, ctx->tail_seq - 1, hipStreamWaitValueGte, 0xffffffffu));
-    // what the build reads (energy, lattice pool) may have been written on the main stream
-    if (ctx->main_dirty || (ctx->main_wrote && ctx->main_wrote == d_energy_in)) {
-      HIP_TRY(ctx, hipEventRecord(ctx->ev_mark, ctx->stream));
-      HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_mark, 0));
-      ctx->main_dirty = false;
-      ctx->main_wrote = nullptr;
-      for (const void*& w : ctx->slot_wrote) w = nullptr;
-    } else {
-      // ... by a streaming kernel further back than the last one: the tail flag says that kernel's last workgroups have
-      // been dispatched, not that they have written the energy
-      for (int i = 0; i < lynx_ctx::kTableSlots; ++i)
-        if (i != slot && ctx->slot_wrote[i] == d_energy_in && d_energy_in && ctx->streamed_valid[i])
-          HIP_TRY(ctx, hipStreamWaitEvent(bs, ctx->ev_streamed[i], 0));
-    }
-  }
-  float* d_units_w = nullptr;
-  float* d_extras_w = nullptr;
+  t->async = knob(ctx->knobs.async_build, half_million && !inline_all ? 1 : 0) != 0;
+}
+
+// An asynchronous build behind what it reads (BuildOrder::order_build), and whether it starts in a tail (t->tail).
+static int table_order_build(lynx_ctx* ctx, const void* d_energy_in, TrackTable* t) {
+  t->tail = ctx->can_wait_value && ctx->knobs.build_in_tail && !t->short_call;  // (a short kernel has no tail worth waiting for)
+  const bool wait_for_tail = t->tail && ctx->tail_seq >= 2;
+  HIP_TRY(ctx, ctx->order.order_build(ctx->s_build, ctx->stream, t->slot, d_energy_in, wait_for_tail ? ctx->d_tail_flag : nullptr,
+                                      ctx->tail_seq - 1));
+  return LYNX_OK;
+}
+
+// The structured step loop: whether this call takes it (t->use_units), and room for its records in the table's slot.
+// Multi-step float32 programs are walked as units with structured maps (lynx_units.hpp); LYNX_TRACK_UNITS=0 keeps the
+// dense step loop of k_track_direct (LYNX_TRACK_UNITS=2: insist -- an error if this call cannot take the structured
+// loop; for tests).
+template <typename T>
+static int table_unit_records(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, int32_t S, const TrackPlan& p, TrackTable* t) {
   if constexpr (sizeof(T) == 4) {
-    // multi-step programs: walked as units with structured maps (lynx_units.hpp); LYNX_TRACK_UNITS=0 keeps the
-    // dense step loop of k_track_direct
-    // (LYNX_TRACK_UNITS=2: insist -- an error if this call cannot take the structured loop; for tests)
+    int rc;
     const int want_units = ctx->knobs.track_units;
+    const int m = p.a.merged_pairs ? 1 : 0;
     // (k_track_units addresses a sample's particles with 32-bit byte offsets: samples below 4 GiB)
     if (S > 1 && (p.unroll == 2 || p.unroll == 4) && !p.xpose && p.a.n_observers == 0 && want_units &&
         (uint64_t)N * 28u + ((uint64_t)1 << 20) < ((uint64_t)1 << 32)) {
       if ((rc = ensure_units_plan(ctx, lat, p.a.merged_pairs != 0))) return rc;
-      t->use_units = lat->units_ok[p.a.merged_pairs ? 1 : 0];
+      t->use_units = lat->units_ok[m];
     }
     if (want_units == 2 && !t->use_units)
       return fail(ctx, LYNX_ERR_INVALID, "LYNX_TRACK_UNITS=2: this call does not take the structured step loop");
     if (t->use_units) {
-      const int64_t n = B * lat->units[p.a.merged_pairs ? 1 : 0].n_units;
-      const int xs = lynx_ctx::kTableSlots + slot;
-      if ((rc = ensure_scratch(ctx, &ctx->scratch_units[slot], &ctx->scratch_units_bytes[slot], (size_t)n * kUnitStride * sizeof(float))) ||
-          (rc = ensure_scratch(ctx, &ctx->scratch_units[xs], &ctx->scratch_units_bytes[xs], (size_t)n * kUnitExtraStride * sizeof(float))))
+      const int64_t n = B * lat->units[m].n_units;
+      Scratch &units = ctx->scratch.units[t->slot], &extras = ctx->scratch.units[lynx_ctx::kTableSlots + t->slot];
+      if ((rc = ensure_scratch(ctx, units, (size_t)n * kUnitStride * sizeof(float))) ||
+          (rc = ensure_scratch(ctx, extras, (size_t)n * kUnitExtraStride * sizeof(float))))
         return rc;
-      t->d_units = d_units_w = (float*)ctx->scratch_units[slot];
-      t->d_extras = d_extras_w = (float*)ctx->scratch_units[xs];
-      t->n_units = lat->units[p.a.merged_pairs ? 1 : 0].n_units;
+      t->d_units = (float*)units.buf;
+      t->d_extras = (float*)extras.buf;
+      t->n_units = lat->units[m].n_units;
     }
   }
-  if ((rc = launch_build<T>(ctx, lat, bs, d_energy_in, ctx->scratch_steps[slot], nullptr, p.a.merged_pairs, async, d_units_w, d_extras_w)))
+  return LYNX_OK;
+}
+
+// The build's launch on its stream, and who waits for an asynchronous one.
+template <typename T>
+static int table_launch_build(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, const void* d_energy_in, const TrackPlan& p,
+                              TrackTable* t) {
+  int rc;
+  hipStream_t bs = t->async ? ctx->s_build : ctx->stream;
+  if ((rc = launch_build<T>(ctx, lat, bs, d_energy_in, ctx->scratch.steps[t->slot].buf, nullptr, p.a.merged_pairs, t->async, t->d_units,
+                            t->d_extras)))
     return rc;
-  if (async) {
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_built[slot], bs));
-    // The HOST waits for the build instead of the main stream: no barrier packet with a foreign signal in front of
-    // the streaming kernel (measured on the 128-sample shard of BASELINE config 4: step - kernel 18.8 -> 8.5-10 us,
-    // c3big 17.9 -> 8-14, config 4 itself 20 -> 14).  The build of this call started when the streaming kernel of
-    // call n - kTableSlots + 1 began, so by now the GPU still has about two calls queued.  Not for lattices with
-    // cavities: their build (k_cavity_flags + the lanes kernels) takes most of a streaming kernel's time next to a
-    // VALU-bound kernel, and the host's wake-up would sit on the critical path (BASELINE config 5: 0.932 -> 0.947
-    // ms/step with it).  LYNX_BUILD_HOST_WAIT=0 / 1 forces the main-stream / host wait.
-    // Nor for short streaming kernels (BASELINE config 3, 1 M particles: 29 us of kernel, 22 us of build -- the
-    // host would be the pacemaker: 48 -> 75 us/step): from 128 MB of particles per call.
-    const bool long_kernel = (size_t)B * N * 7 * sizeof(T) >= ((size_t)128 << 20);
-    if (knob(ctx->knobs.build_host_wait, (lat->has_cavity || !long_kernel) ? 0 : 1)) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_built[slot]));
-    else HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_built[slot], 0));
-  }
-  t->d_steps = ctx->scratch_steps[slot];
+  t->d_steps = ctx->scratch.steps[t->slot].buf;
+  if (!t->async) return LYNX_OK;
+  HIP_TRY(ctx, hipEventRecord(ctx->ev_built[t->slot], bs));
+  // The HOST waits for the build instead of the main stream: no barrier packet with a foreign signal in front of
+  // the streaming kernel (measured on the 128-sample shard of BASELINE config 4: step - kernel 18.8 -> 8.5-10 us,
+  // c3big 17.9 -> 8-14, config 4 itself 20 -> 14).  The build of this call started when the streaming kernel of
+  // call n - kTableSlots + 1 began, so by now the GPU still has about two calls queued.  Not for lattices with
+  // cavities: their build (k_cavity_flags + the lanes kernels) takes most of a streaming kernel's time next to a
+  // VALU-bound kernel, and the host's wake-up would sit on the critical path (BASELINE config 5: 0.932 -> 0.947
+  // ms/step with it).  LYNX_BUILD_HOST_WAIT=0 / 1 forces the main-stream / host wait.
+  // Nor for short streaming kernels (BASELINE config 3, 1 M particles: 29 us of kernel, 22 us of build -- the
+  // host would be the pacemaker: 48 -> 75 us/step): from 128 MB of particles per call.
+  const bool long_kernel = (size_t)B * N * 7 * sizeof(T) >= ((size_t)128 << 20);
+  if (knob(ctx->knobs.build_host_wait, (lat->has_cavity || !long_kernel) ? 0 : 1)) HIP_TRY(ctx, hipEventSynchronize(ctx->ev_built[t->slot]));
+  else HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_built[t->slot], 0));
+  return LYNX_OK;
+}
+
+// Builds the step table of this call: takes the next slot of the ring, then stage by stage -- the merged form
+// (p.a.merged_pairs and the LDS stash), where the build runs, what it waits for, the structured step loop's records, the
+// launch and who waits for it -- and leaves the table to a reverse pass that may follow (lynx_ctx::fwd_table).
+template <typename T>
+static int track_table(lynx_ctx* ctx, lynx_lattice* lat, int64_t B, int64_t N, int32_t S, const void* d_energy_in,
+                       const void* d_energy_out, int flags, TrackPlan& p, TrackTable* t) {
+  int rc;
+  t->slot = (int)(ctx->seq++ % (unsigned)lynx_ctx::kTableSlots);
+  if ((rc = ensure_scratch(ctx, ctx->scratch.steps[t->slot], (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T)))) return rc;
+  table_merged_form<T>(ctx, lat, S, flags, p);
+  table_build_stream<T>(ctx, lat, B, N, t);
+  if (t->async && (rc = table_order_build(ctx, d_energy_in, t))) return rc;
+  if ((rc = table_unit_records<T>(ctx, lat, B, N, S, p, t))) return rc;
+  if ((rc = table_launch_build<T>(ctx, lat, B, N, d_energy_in, p, t))) return rc;
   std::lock_guard<std::mutex> lock(ctx->mu);
-  ctx->fwd_table.lat = lat;
-  ctx->fwd_table.version = lat->version;
-  ctx->fwd_table.energy = d_energy_in;
-  ctx->fwd_table.energy_bytes = (size_t)B * sizeof(T);
-  ctx->fwd_table.slot = slot;
-  ctx->fwd_table.merged = p.a.merged_pairs;
-  ctx->fwd_table.units = t->use_units;
-  ctx->fwd_table.seq = ctx->seq;
-  ctx->fwd_table.valid = d_energy_out != d_energy_in;  // (a call that overwrites its own incoming energy leaves nothing to come back to)
+  ctx->fwd_table.leave(lat, lat->version, d_energy_in, (size_t)B * sizeof(T), d_energy_out, t->slot, p.a.merged_pairs, t->use_units,
+                       ctx->seq);
   return LYNX_OK;
 }
 
@@ -1788,7 +1901,7 @@ static int reduce_moment_records(lynx_ctx* ctx, int64_t B, int rows, bool side, 
     const int groups = (rows + rpg - 1) / rpg;
     const size_t need = (size_t)B * groups * kPartialStride * sizeof(double);
     // one buffer: its users follow each other on one stream (side or main), and a change of stream joins first
-    if ((rc = ensure_scratch(ctx, &ctx->scratch_level, &ctx->scratch_level_bytes, need))) return rc;
+    if ((rc = ensure_scratch(ctx, ctx->scratch.level, need))) return rc;
     if (ctx->level_on_side != side) {
       if (side) {  // earlier in-line levels ran on the main stream: the side stream waits for them
         HIP_TRY(ctx, hipEventRecord(ctx->ev_main_mark, ctx->stream));
@@ -1802,14 +1915,14 @@ static int reduce_moment_records(lynx_ctx* ctx, int64_t B, int rows, bool side, 
       // both levels in one launch: the workgroup that draws a sample's last ticket adds its group records up
       if ((rc = ensure_tickets(ctx, (size_t)B))) return rc;
       hipLaunchKernelGGL((k_reduce_moments_ticket<256, kReduceStage>), dim3((unsigned)(B * groups)), dim3(256), lds, rs,
-                         level_in, rows, rpg, groups, (double*)ctx->scratch_level, ctx->scratch_tickets, d_moments_out);
+                         level_in, rows, rpg, groups, (double*)ctx->scratch.level.buf, (unsigned int*)ctx->scratch.tickets.buf, d_moments_out);
       HIP_TRY(ctx, hipGetLastError());
       rows = 0;
     } else {
       hipLaunchKernelGGL((k_reduce_moments<false, 256, kReduceStage>), dim3((unsigned)(B * groups)), dim3(256), lds, rs,
-                         level_in, rows, rpg, groups, (double*)ctx->scratch_level);
+                         level_in, rows, rpg, groups, (double*)ctx->scratch.level.buf);
       HIP_TRY(ctx, hipGetLastError());
-      level_in = (const double*)ctx->scratch_level;
+      level_in = (const double*)ctx->scratch.level.buf;
       rows = groups;
     }
   }
@@ -1848,10 +1961,11 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   p.a.merged_pairs = 0;
   int rc;
   // what this call writes for the caller may hold the incoming energy of the table kept for a reverse pass
-  ctx->wrote(d_p_out, (size_t)B * N * 7 * sizeof(T));
-  ctx->wrote(d_energy_out, (size_t)B * sizeof(T));
-  ctx->wrote(d_moments_out, (size_t)B * LYNX_MOMENT_STRIDE * sizeof(double));
-  ctx->wrote(d_observations, lat ? (size_t)B * lat->n_observers * 2 * sizeof(double) : 0);
+  // (kFeedsNoBuild: a call with steps says what it publishes behind its launch, BuildOrder::streamed)
+  caller_blocks_written(ctx, kFeedsNoBuild, {{d_p_out, (size_t)B * N * 7 * sizeof(T)},
+                                             {d_energy_out, (size_t)B * sizeof(T)},
+                                             {d_moments_out, (size_t)B * LYNX_MOMENT_STRIDE * sizeof(double)},
+                                             {d_observations, lat ? (size_t)B * lat->n_observers * 2 * sizeof(double) : 0}});
   // The build is always a launch of its own (in the streaming kernel's prologue it measured the same twice: NOTES.md,
   // "Tried and dropped in round 4"), so a call with steps always takes a slot of the ring and leaves a FwdTable.
   TrackTable t;
@@ -1865,31 +1979,27 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   // as the build's second stream: below it the extra event traffic costs more host time than it returns).
   const bool side = moments && knob(ctx->knobs.side_reduce, (B * N >= (int64_t)512 << 10 && !t.short_call) ? 1 : 0) != 0;
   if (moments) {
-    ring = &ctx->partial_ring[ctx->partial_seq++ % lynx_ctx::kPartialRing];
+    const unsigned ring_slot = ctx->partial_seq++ % lynx_ctx::kPartialRing;
+    ring = &ctx->partial_ring[ring_slot];
     if (ring->pending) {
       if (hipEventQuery(ring->reduced) != hipSuccess) HIP_TRY(ctx, hipEventSynchronize(ring->reduced));
       ring->pending = false;
     }
     const size_t need = (size_t)B * p.a.chunks * kPartialStride * sizeof(double);
-    if ((rc = ensure_scratch(ctx, &ring->buf, &ring->bytes, need))) return rc;
-    d_partials = (double*)ring->buf;
+    if ((rc = ensure_scratch(ctx, ctx->scratch.partials[ring_slot], need))) return rc;
+    d_partials = (double*)ctx->scratch.partials[ring_slot].buf;
   }
   double* d_obs = nullptr;
   if (p.a.n_observers) {
     if (!d_observations) return fail(ctx, LYNX_ERR_INVALID, "the program has observer steps: d_observations required");
     const size_t need = (size_t)B * p.a.chunks * 2 * LYNX_MAX_OBSERVERS * sizeof(double);
-    if ((rc = ensure_scratch(ctx, &ctx->scratch_obs, &ctx->scratch_obs_bytes, need))) return rc;
-    d_obs = (double*)ctx->scratch_obs;
+    if ((rc = ensure_scratch(ctx, ctx->scratch.obs, need))) return rc;
+    d_obs = (double*)ctx->scratch.obs.buf;
   }
-  // the time stamp on the dispatch is what a later build on the second stream waits for before it reuses the
-  // table slot; a call whose build ran on the main stream leaves it out (it costs host time: BASELINE config 2 is
-  // bound by the host's enqueue rate) and marks the main stream dirty instead, which makes the next asynchronous
-  // build wait for everything enqueued here
   if (t.tail) {  // this kernel announces its tail: one of the workgroups of its last round of dispatches
-    const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
     p.a.tail_flag = ctx->d_tail_flag;
     p.a.tail_seq = ++ctx->tail_seq;
-    p.a.tail_wg = (int32_t)std::max<int64_t>(0, (int64_t)p.grid - 4 * cus);
+    p.a.tail_wg = (int32_t)std::max<int64_t>(0, (int64_t)p.grid - 4 * compute_units(ctx));
   }
   // Every other LONG call walks the batch from its end: what the previous pass left in the 256 MB Infinity Cache -- the
   // end of its incoming beam -- is then what this one reads first, if it is the same beam again (the optimisation loop:
@@ -1898,7 +2008,9 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   if (!t.use_units && ctx->knobs.alternate_order &&
       (ctx->knobs.alternate_order == 2 || (size_t)B * N * 7 * sizeof(T) >= ((size_t)256 << 20)))
     p.a.reversed = ctx->knobs.alternate_order == 2 ? 1 : (int32_t)(ctx->long_calls++ & 1u);
-  p.done = (t.slot >= 0 && t.async) ? ctx->ev_streamed_own[t.slot] : nullptr;
+  // the time stamp on the dispatch is what a later build on the second stream waits for before it reuses the
+  // table slot; a call whose build ran on the main stream leaves it out (BuildOrder::streamed)
+  p.done = (t.slot >= 0 && t.async) ? ctx->order.stop_event(t.slot) : nullptr;
   if (side && !p.done) p.done = ring->track_done;  // the side stream's reduction starts behind it
   if (t.use_units) {
     const UnitPlan& up = lat->units[p.a.merged_pairs ? 1 : 0];
@@ -1921,13 +2033,7 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
                        p.a.n_observers, (double)N, d_observations);
     HIP_TRY(ctx, hipGetLastError());
   }
-  if (t.slot >= 0) {
-    ctx->ev_streamed[t.slot] = ctx->last_stream_stop;
-    ctx->streamed_valid[t.slot] = t.async && ctx->last_stream_stop != nullptr;
-    if (!t.async) ctx->main_dirty = true;
-    ctx->slot_wrote[t.slot] = d_energy_out;
-  }
-  if (d_energy_out) ctx->main_wrote = d_energy_out;  // a later build that reads it must wait for this kernel
+  ctx->order.streamed(t.slot, t.async, ctx->last_stream_stop, d_energy_out);
   if (moments) return reduce_moment_records(ctx, B, p.a.chunks, side, ring, d_partials, d_moments_out);
   return LYNX_OK;
 }
@@ -1944,11 +2050,10 @@ int lynx_track_particles(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, 
     return fail(ctx, LYNX_ERR_INVALID, "a shared incoming beam cannot be tracked in place");
   HIP_TRY(ctx, use_device(ctx));
   LatticeDev lv = dev_view(lat);
-  const int rc = lat->dtype == LYNX_F64
-                     ? track_particles_t<double>(ctx, lat, lv, lat->batch, n_particles, d_energy_in, d_p_in, d_p_out,
-                                                 d_energy_out, d_moments_out, flags, d_observations)
-                     : track_particles_t<float>(ctx, lat, lv, lat->batch, n_particles, d_energy_in, d_p_in, d_p_out,
-                                                d_energy_out, d_moments_out, flags, d_observations);
+  const int rc = with_dtype(lat->dtype, [&](auto zero) {
+    return track_particles_t<decltype(zero)>(ctx, lat, lv, lat->batch, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_out,
+                                             d_moments_out, flags, d_observations);
+  });
   ctx->main_idle = false;  // (whatever allocation inside may have waited for the stream: work follows it now)
   return rc;
 }
@@ -2016,13 +2121,13 @@ static int ensure_bwd_tasks(lynx_ctx* ctx, lynx_lattice* lat) {
 constexpr int kBwdWgsPerCu = 24;                     // workgroups per CU of the reverse streaming kernels
 constexpr size_t kBwdMapsLdsBytes = (size_t)40 << 10;  // k_build_bwd keeps maps and prefix products in LDS up to this
 
-// What every reverse pass ends with.  A sweep leaves T_bar [B][S][kGradStride] in scratch_grad[1]; k_build_bwd, with its
-// maps and prefix products in scratch_grad[2], turns it into the gradients [B][E][kGradParams] and [B].
+// What every reverse pass ends with.  A sweep leaves T_bar [B][S][kGradStride] in scratch.grad[1]; k_build_bwd, with its
+// maps and prefix products in scratch.grad[2], turns it into the gradients [B][E][kGradParams] and [B].
 template <typename T>
 static int ensure_tbar_scratch(lynx_ctx* ctx, const lynx_lattice* lat) {
   const size_t B = (size_t)lat->batch, S = (size_t)lat->n_steps, E = (size_t)lat->n_elems;
-  if (const int rc = ensure_scratch(ctx, &ctx->scratch_grad[1], &ctx->scratch_grad_bytes[1], B * S * kGradStride * sizeof(T))) return rc;
-  return ensure_scratch(ctx, &ctx->scratch_grad[2], &ctx->scratch_grad_bytes[2], B * (2 * E + S + 1) * 49 * sizeof(T));
+  if (const int rc = ensure_scratch(ctx, ctx->scratch.grad[1], B * S * kGradStride * sizeof(T))) return rc;
+  return ensure_scratch(ctx, ctx->scratch.grad[2], B * (2 * E + S + 1) * 49 * sizeof(T));
 }
 
 // `merged`: the sweep walked [run, cavity] pairs as one unit each, k_build_bwd takes their cotangents apart again.
@@ -2043,7 +2148,7 @@ static int launch_build_bwd(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ener
     if (const int refused = allow_lds(ctx, kernel, lds)) return refused;
     HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
     hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(256), lds, ctx->stream, pool..., dev_view(lat), (const T*)d_energy_in,
-                       (T*)ctx->scratch_grad[1], (T*)ctx->scratch_grad[2], (T*)d_grad_params, (T*)d_grad_energy_in, merged,
+                       (T*)ctx->scratch.grad[1].buf, (T*)ctx->scratch.grad[2].buf, (T*)d_grad_params, (T*)d_grad_energy_in, merged,
                        maps_in_lds, lat->d_bwd_tasks, lat->n_bwd_tasks);
     HIP_TRY(ctx, hipGetLastError());
     return LYNX_OK;
@@ -2078,7 +2183,7 @@ struct BwdSweepPlan {
 template <typename T, int W>
 static BwdSweepPlan plan_bwd_sweep(const lynx_ctx* ctx, int64_t B, int64_t N, int32_t S, BwdArgs* a) {
   BwdSweepPlan p;
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t cus = compute_units(ctx);
   p.ntiles = (N + kTrackThreads * W - 1) / (kTrackThreads * W);
   p.chunks = std::max<int64_t>(1, std::min<int64_t>(p.ntiles, ((int64_t)kBwdWgsPerCu * cus + B - 1) / B));
   p.tiles_per_wg = (p.ntiles + p.chunks - 1) / p.chunks;
@@ -2110,30 +2215,31 @@ static int plan_bwd_units(const lynx_lattice* lat, bool merge, bool observers, B
   return merged;
 }
 
-// the workgroups' partial sums [B][chunks][S][kGradStride] -> T_bar in scratch_grad[1]
+// the workgroups' partial sums [B][chunks][S][kGradStride] -> T_bar in scratch.grad[1]
 template <typename T>
 static int reduce_tbar(lynx_ctx* ctx, const T* partials, int64_t B, int32_t S, int64_t chunks) {
   if (chunks >= 16) {
     hipLaunchKernelGGL(k_reduce_tbar<T>, dim3((unsigned)(B * S)), dim3(256), 0, ctx->stream, partials, (int)chunks, (int)S,
-                       (T*)ctx->scratch_grad[1]);
+                       (T*)ctx->scratch.grad[1].buf);
   } else {  // four rows (sample, step) per wave
     const int64_t rows = B * S;
     hipLaunchKernelGGL((k_reduce_tbar_rows<T, 4>), dim3((unsigned)((rows + 15) / 16)), dim3(256), 0, ctx->stream, partials,
-                       (int)chunks, (int)S, rows, (T*)ctx->scratch_grad[1]);
+                       (int)chunks, (int)S, rows, (T*)ctx->scratch.grad[1].buf);
   }
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
 
 // What a reverse entry point writes for the caller: the gradients of the parameters, of the incoming energy and (if it
-// has them: `ctx->wrote` ignores null) of the incoming moments.
-static void trace_backward_wrote(lynx_ctx* ctx, lynx_lattice* lat, void* d_grad_params, void* d_grad_energy_in,
-                                 void* d_grad_mu_in, void* d_grad_cov_in) {
+// has them: a null block is nothing) of the incoming moments, and what `more` it has.
+static std::array<Written, 5> reverse_writes(const lynx_lattice* lat, void* d_grad_params, void* d_grad_energy_in, void* d_grad_mu_in,
+                                             void* d_grad_cov_in, Written more = {nullptr, 0}) {
   const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es);
-  ctx->wrote(d_grad_energy_in, (size_t)lat->batch * es);
-  ctx->wrote(d_grad_mu_in, (size_t)lat->batch * 7 * es);
-  ctx->wrote(d_grad_cov_in, (size_t)lat->batch * 49 * es);
+  return {{{d_grad_params, (size_t)lat->batch * lat->n_elems * kGradParams * es},
+           {d_grad_energy_in, (size_t)lat->batch * es},
+           {d_grad_mu_in, (size_t)lat->batch * 7 * es},
+           {d_grad_cov_in, (size_t)lat->batch * 49 * es},
+           more}};
 }
 
 // -- the stages of track_backward_t --
@@ -2159,11 +2265,11 @@ static int bwd_units_records(lynx_ctx* ctx, lynx_lattice* lat, int merged, const
   for (int u = 0; same && u < a.n_units; ++u) same = up.slot[u] == a.unit_slot[u];
   if (!same) return LYNX_OK;
   const int64_t n = lat->batch * a.n_units;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_units_bwd[0], &ctx->scratch_units_bwd_bytes[0], (size_t)n * kUnitStride * sizeof(float))) ||
-      (rc = ensure_scratch(ctx, &ctx->scratch_units_bwd[1], &ctx->scratch_units_bwd_bytes[1], (size_t)n * kUnitExtraStride * sizeof(float))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.units_bwd[0], (size_t)n * kUnitStride * sizeof(float))) ||
+      (rc = ensure_scratch(ctx, ctx->scratch.units_bwd[1], (size_t)n * kUnitExtraStride * sizeof(float))))
     return rc;
-  t->d_units = (float*)ctx->scratch_units_bwd[0];
-  t->d_extras = (float*)ctx->scratch_units_bwd[1];
+  t->d_units = (float*)ctx->scratch.units_bwd[0].buf;
+  t->d_extras = (float*)ctx->scratch.units_bwd[1].buf;
   t->all_proposed_u = true;
   for (int u = 0; u < up.n_units; ++u) t->all_proposed_u = t->all_proposed_u && up.cls[u] == kClassU;
   return LYNX_OK;
@@ -2180,17 +2286,17 @@ static int bwd_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, 
   table_lock.unlock();
   const bool reuse = ctx->knobs.bwd_reuse_table && ft.valid && ft.lat == lat && ft.version == lat->version &&
                      ft.energy == d_energy_in && ft.seq == ctx->seq && ft.merged == merged &&
-                     ctx->scratch_steps_bytes[ft.slot] >= steps_bytes;
+                     ctx->scratch.steps[ft.slot].bytes >= steps_bytes;
   if (!reuse) {
-    t->d_steps = ctx->scratch_steps[lynx_ctx::kTableBwd];
-    return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableBwd], nullptr, merged, false,
+    t->d_steps = ctx->scratch.steps[lynx_ctx::kTableBwd].buf;
+    return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch.steps[lynx_ctx::kTableBwd].buf, nullptr, merged, false,
                            t->d_units, t->d_extras);
   }
   t->reused_slot = ft.slot;
-  t->d_steps = ctx->scratch_steps[ft.slot];
+  t->d_steps = ctx->scratch.steps[ft.slot].buf;
   if (t->d_units && ft.units) {
-    t->d_units = (float*)ctx->scratch_units[ft.slot];
-    t->d_extras = (float*)ctx->scratch_units[lynx_ctx::kTableSlots + ft.slot];
+    t->d_units = (float*)ctx->scratch.units[ft.slot].buf;
+    t->d_extras = (float*)ctx->scratch.units[lynx_ctx::kTableSlots + ft.slot].buf;
   } else if (t->d_units) {  // the forward call walked the table itself (a single-map program): the records from its rows
     if constexpr (sizeof(T) == 4) {
       const UnitPlan& up = lat->units[merged ? 1 : 0];
@@ -2219,7 +2325,7 @@ static int launch_bwd_sweep(lynx_ctx* ctx, lynx_lattice* lat, const BwdArgs& a, 
         if (const int refused = allow_lds(ctx, kernel, lds_u)) return refused;
         hipLaunchKernelGGL(kernel, dim3((unsigned)(B * p.chunks)), dim3(kTrackThreads), lds_u, ctx->stream, a, S, (const float*)d_p_in,
                            (const float*)t.d_units, (const float*)t.d_extras, d_moments_fwd, d_grad_moments,
-                           (float*)ctx->scratch_grad[0], (float*)d_grad_p_in);
+                           (float*)ctx->scratch.grad[0].buf, (float*)d_grad_p_in);
         HIP_TRY(ctx, hipGetLastError());
         return LYNX_OK;
       };
@@ -2240,11 +2346,11 @@ static int launch_bwd_sweep(lynx_ctx* ctx, lynx_lattice* lat, const BwdArgs& a, 
       a_dense.tiles_per_wg = (int32_t)p.ntiles;
     }
     a_dense.n_work = (int32_t)B;
-    const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+    const int64_t cus = compute_units(ctx);
     dense_grid = std::min<int64_t>(B, 2 * cus);  // (and as many workgroups as are resident at once: they look at B / grid samples each)
   }
   hipLaunchKernelGGL((k_track_bwd<T, Z>), dim3((unsigned)dense_grid), dim3(kTrackThreads), p.lds, ctx->stream, dev_view(lat), a_dense,
-                     (const T*)d_p_in, (const T*)t.d_steps, d_moments_fwd, d_grad_moments, (T*)ctx->scratch_grad[0],
+                     (const T*)d_p_in, (const T*)t.d_steps, d_moments_fwd, d_grad_moments, (T*)ctx->scratch.grad[0].buf,
                      (T*)d_grad_p_in, (const float*)t.d_units, kUnitStride, kUnitClassShift, (int)kClassU, d_grad_observations);
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
@@ -2276,30 +2382,27 @@ static int track_backward_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const v
   // the units plan for the structured kernel, then the table: the forward call's, or one built here
   BwdTable t;
   const size_t steps_bytes = (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T);
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableBwd], &ctx->scratch_steps_bytes[lynx_ctx::kTableBwd], steps_bytes))) return rc;
+  if ((rc = ensure_scratch(ctx, ctx->scratch.steps[lynx_ctx::kTableBwd], steps_bytes))) return rc;
   if constexpr (W == 2)
     if ((rc = bwd_units_records(ctx, lat, merged, a, &t))) return rc;
   if ((rc = bwd_table<T>(ctx, lat, d_energy_in, merged, steps_bytes, &t))) return rc;
-  ctx->main_dirty = true;
-  // the sweep over the particles -> partial sums [B][chunks][S][kGradStride] in scratch_grad[0] -> T_bar
+  // the sweep over the particles -> partial sums [B][chunks][S][kGradStride] in scratch.grad[0] -> T_bar
   if ((rc = allow_lds(ctx, k_track_bwd<T, Z>, p.lds))) return rc;
   if ((int64_t)B * p.chunks > 0x7fffffffLL || (int64_t)B * S > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (size_t)B * p.chunks * S * kGradStride * sizeof(T))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.grad[0], (size_t)B * p.chunks * S * kGradStride * sizeof(T))))
     return rc;
   if ((rc = ensure_tbar_scratch<T>(ctx, lat))) return rc;
   if ((rc = launch_bwd_sweep<T, Z>(ctx, lat, a, p, t, d_p_in, d_moments_fwd, d_grad_moments, d_grad_p_in, d_grad_observations))) return rc;
-  if ((rc = reduce_tbar<T>(ctx, (const T*)ctx->scratch_grad[0], B, S, p.chunks))) return rc;
+  if ((rc = reduce_tbar<T>(ctx, (const T*)ctx->scratch.grad[0].buf, B, S, p.chunks))) return rc;
   if constexpr (W == 2) {
     if (t.d_units) {  // class-U samples: the units' transverse blocks from the sample's S_x, S_y (lynx_grad_units.hpp)
       hipLaunchKernelGGL(k_finish_tbar_units, dim3((unsigned)B), dim3(64), 0, ctx->stream, a, S, (const float*)t.d_units,
-                         (float*)ctx->scratch_grad[1]);
+                         (float*)ctx->scratch.grad[1].buf);
       HIP_TRY(ctx, hipGetLastError());
     }
   }
   if (t.reused_slot >= 0) {  // the forward call's table slot has been read up to here: its next build waits for this, too
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_streamed_own[t.reused_slot], ctx->stream));
-    ctx->ev_streamed[t.reused_slot] = ctx->ev_streamed_own[t.reused_slot];
-    ctx->streamed_valid[t.reused_slot] = true;
+    HIP_TRY(ctx, ctx->order.read_until_here(t.reused_slot, ctx->stream));
   }
   return launch_build_bwd<T>(ctx, lat, d_energy_in, d_grad_params, d_grad_energy_in, merged, pool_in_args);
 }
@@ -2308,14 +2411,13 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
                                   const void* d_p_in, const double* d_moments_fwd, const double* d_grad_moments,
                                   void* d_grad_params, void* d_grad_energy_in, void* d_grad_p_in,
                                   const double* d_grad_observations) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_p_in || !d_moments_fwd || !d_grad_moments || !d_grad_params || !d_grad_energy_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (n_particles <= 0 || lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program or beam");
   if (d_grad_observations && lat->n_observers == 0)
     return fail(ctx, LYNX_ERR_INVALID, "d_grad_observations given, but the program has no observer step");
-  HIP_TRY(ctx, use_device(ctx));
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {});  // (what it writes: behind the pass, below)
   if (const int rc = join_side(ctx)) return rc;  // d_moments_fwd is what a reduction on the side stream writes
   const auto pass = lat->dtype == LYNX_F64   ? track_backward_t<double, double>
                     : ctx->knobs.bwd_pairs ? track_backward_t<float, lynx_f32x2>
@@ -2325,8 +2427,9 @@ int lynx_track_particles_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_pa
   // The gradients it wrote for the caller, said AFTER the pass: `wrote` invalidates the FwdTable if a block overlaps the
   // forward call's incoming energy, and the pass reads that table -- said up front, it would build its own instead
   // (the other reverse passes read no FwdTable: they say it up front).
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
-  ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype));
+  caller_blocks_written(ctx, kFeedsNoBuild,
+                        reverse_writes(lat, d_grad_params, d_grad_energy_in, nullptr, nullptr,
+                                       {d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype)}));
   return rc;
 }
 
@@ -2338,16 +2441,15 @@ static int moments_backward_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_en
   const int32_t S = lat->n_steps;
   int rc;
   if ((rc = sync_pool(ctx, lat))) return rc;  // (k_moments_bwd and k_build_bwd read the parameters from memory)
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableBwd], &ctx->scratch_steps_bytes[lynx_ctx::kTableBwd], (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.steps[lynx_ctx::kTableBwd], (size_t)B * S * LYNX_STEP_STRIDE * sizeof(T))))
     return rc;
-  if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableBwd], nullptr))) return rc;
-  ctx->main_dirty = true;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (size_t)B * (S + 1) * 56 * sizeof(T))))
+  if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch.steps[lynx_ctx::kTableBwd].buf, nullptr))) return rc;
+  if ((rc = ensure_scratch(ctx, ctx->scratch.grad[0], (size_t)B * (S + 1) * 56 * sizeof(T))))
     return rc;
   if ((rc = ensure_tbar_scratch<T>(ctx, lat))) return rc;
-  hipLaunchKernelGGL(k_moments_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, dev_view(lat), (const T*)ctx->scratch_steps[lynx_ctx::kTableBwd],
+  hipLaunchKernelGGL(k_moments_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, dev_view(lat), (const T*)ctx->scratch.steps[lynx_ctx::kTableBwd].buf,
                      (const T*)d_mu_in, (const T*)d_cov_in, (const T*)d_mu_bar, (const T*)d_cov_bar,
-                     (T*)ctx->scratch_grad[0], (T*)ctx->scratch_grad[1], (T*)d_grad_mu_in, (T*)d_grad_cov_in);
+                     (T*)ctx->scratch.grad[0].buf, (T*)ctx->scratch.grad[1].buf, (T*)d_grad_mu_in, (T*)d_grad_cov_in);
   HIP_TRY(ctx, hipGetLastError());
   return launch_build_bwd<T>(ctx, lat, d_energy_in, d_grad_params, d_grad_energy_in, 0, false);
 }
@@ -2356,34 +2458,32 @@ int lynx_track_moments_backward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
                                 const void* d_cov_in, const void* d_mu_bar, const void* d_cov_bar,
                                 void* d_grad_params, void* d_grad_energy_in, void* d_grad_mu_in,
                                 void* d_grad_cov_in) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_bar || !d_cov_bar || !d_grad_params ||
       !d_grad_energy_in || !d_grad_mu_in || !d_grad_cov_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, "empty program");
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
-  HIP_TRY(ctx, use_device(ctx));
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
-  const auto pass = lat->dtype == LYNX_F64 ? moments_backward_t<double> : moments_backward_t<float>;
-  return pass(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_bar, d_cov_bar, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, reverse_writes(lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return moments_backward_t<decltype(zero)>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_bar, d_cov_bar, d_grad_params,
+                                              d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  });
 }
 
 int lynx_moments(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                  double* d_moments_out, int32_t covariance) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p || !d_moments_out) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (batch <= 0 || n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad shape");
-  HIP_TRY(ctx, use_device(ctx));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {});  // (track_particles_t says what it writes)
   LatticeDev lv;
   memset(&lv, 0, sizeof(lv));
   lv.batch = batch;
-  return dtype == LYNX_F64
-             ? track_particles_t<double>(ctx, nullptr, lv, batch, n_particles, nullptr, d_p, nullptr, nullptr,
-                                         d_moments_out, covariance ? LYNX_TRACK_COVARIANCE : LYNX_TRACK_MOMENTS)
-             : track_particles_t<float>(ctx, nullptr, lv, batch, n_particles, nullptr, d_p, nullptr, nullptr,
-                                        d_moments_out, covariance ? LYNX_TRACK_COVARIANCE : LYNX_TRACK_MOMENTS);
+  return with_dtype(dtype, [&](auto zero) {
+    return track_particles_t<decltype(zero)>(ctx, nullptr, lv, batch, n_particles, nullptr, d_p, nullptr, nullptr, d_moments_out,
+                                             covariance ? LYNX_TRACK_COVARIANCE : LYNX_TRACK_MOMENTS);
+  });
 }
 
 // ---- ParameterBeam ---------------------------------------------------------------------
@@ -2396,17 +2496,17 @@ static int launch_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
   if (lat->n_steps > 0 && lat->batch >= ctx->knobs.lanes_build_min_batch) {
     // large batches: lanes = samples all the way (step table from the lanes build, then one lane per sample)
     const size_t need = (size_t)lat->batch * lat->n_steps * LYNX_STEP_STRIDE * sizeof(T);
-    if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTablePb], &ctx->scratch_steps_bytes[lynx_ctx::kTablePb], need))) return rc;
-    if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTablePb], nullptr, 0))) return rc;
+    if ((rc = ensure_scratch(ctx, ctx->scratch.steps[lynx_ctx::kTablePb], need))) return rc;
+    if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch.steps[lynx_ctx::kTablePb].buf, nullptr, 0))) return rc;
     hipLaunchKernelGGL(k_apply_moments_lanes<T>, dim3((unsigned)((lat->batch + 63) / 64)), dim3(64), apply_moments_lds<T>(),
-                       ctx->stream, dev_view(lat), (const T*)ctx->scratch_steps[lynx_ctx::kTablePb], (const T*)d_mu_in, (const T*)d_cov_in,
+                       ctx->stream, dev_view(lat), (const T*)ctx->scratch.steps[lynx_ctx::kTablePb].buf, (const T*)d_mu_in, (const T*)d_cov_in,
                        (T*)d_mu_out, (T*)d_cov_out, (T*)d_energy_out);
     HIP_TRY(ctx, hipGetLastError());
     return LYNX_OK;
   }
   // one workgroup per sample: one wave for big batches, four otherwise -- with chunks of up to 128 elements when the
   // batch leaves most of the GPU idle and the depth of the tree is what the call waits for (build_shape)
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t cus = compute_units(ctx);
   const bool deep = lat->batch * 2 <= cus;
   const unsigned threads = lat->batch <= 4096 ? 256u : 64u;
   int chunk = build_chunk(lat->n_elems, deep ? 128 : 64);
@@ -2442,20 +2542,17 @@ static int launch_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
 
 int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                        const void* d_cov_in, void* d_mu_out, void* d_cov_out, void* d_energy_out) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_out || !d_cov_out)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
-  const size_t es = dtype_size(lat->dtype);
-  ctx->wrote(d_energy_out, (size_t)lat->batch * es);
-  ctx->wrote(d_mu_out, (size_t)lat->batch * 7 * es);
-  ctx->wrote(d_cov_out, (size_t)lat->batch * 49 * es);
   if (lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "batch too large");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
-  return lat->dtype == LYNX_F64
-             ? launch_track_moments<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_out, d_cov_out, d_energy_out)
-             : launch_track_moments<float>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_out, d_cov_out, d_energy_out);
+  const size_t es = dtype_size(lat->dtype);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_energy_out, (size_t)lat->batch * es},
+                                      {d_mu_out, (size_t)lat->batch * 7 * es},
+                                      {d_cov_out, (size_t)lat->batch * 49 * es}});
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return launch_track_moments<decltype(zero)>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_out, d_cov_out, d_energy_out);
+  });
 }
 
 // ---- beam trace: the moments at every element of the lattice ---------------------------------
@@ -2466,14 +2563,14 @@ template <typename T>
 static int trace_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in) {
   int rc;
   const size_t need = std::max<size_t>(1, (size_t)lat->batch * lat->n_steps) * LYNX_STEP_STRIDE * sizeof(T);
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_steps[lynx_ctx::kTableTrace], &ctx->scratch_steps_bytes[lynx_ctx::kTableTrace], need)))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.steps[lynx_ctx::kTableTrace], need)))
     return rc;
   if (lat->n_steps == 0) return LYNX_OK;
   // no limit on the number of elements: where the workgroup build's table would not fit its LDS, lanes = samples
   int threads, chunk;
   build_shape<T>(ctx, lat, false, &threads, &chunk);
   const size_t lds = build_scratch_bytes(chunk, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1) * sizeof(T);
-  return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch_steps[lynx_ctx::kTableTrace], nullptr, 0, false, nullptr,
+  return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch.steps[lynx_ctx::kTableTrace].buf, nullptr, 0, false, nullptr,
                          nullptr, lds > (size_t)64 * 1024);
 }
 
@@ -2521,12 +2618,12 @@ static int trace_plan(lynx_ctx* ctx, int32_t S, const TraceApertures* ap, const 
     cell += nx * ny;
   }
   const size_t need = plan.size() * sizeof(int64_t);
-  const bool fresh = ctx->scratch_trace_plan_bytes < need;
+  const bool fresh = ctx->scratch.trace_plan.bytes < need;
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace_plan, &ctx->scratch_trace_plan_bytes, need))) return rc;
+  if ((rc = ensure_scratch(ctx, ctx->scratch.trace_plan, need))) return rc;
   if (fresh || plan != ctx->trace_plan) {
     ctx->trace_plan.clear();
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch_trace_plan, plan.data(), need, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->scratch.trace_plan.buf, plan.data(), need, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(ctx, sync_main(ctx));  // (kernels of earlier calls have read the old plan; the host vector is ours again)
     ctx->trace_plan.swap(plan);
   }
@@ -2539,10 +2636,10 @@ static int launch_trace_finalize(lynx_ctx* ctx, int64_t B, int32_t P, int64_t wa
   // (few waves per sample: 8 groups of them; hundreds to thousands -- few samples of many particles: 32)
   if (waves > 256)
     hipLaunchKernelGGL((k_trace_finalize<T, 1024>), dim3((unsigned)(B * P)), dim3(1024), 0, ctx->stream,
-                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, count, d_trace_out);
+                       (const double*)ctx->scratch.trace[0].buf, (const T*)ctx->scratch.trace[1].buf, (int)waves, (int)P, count, d_trace_out);
   else
     hipLaunchKernelGGL((k_trace_finalize<T, 256>), dim3((unsigned)(B * P)), dim3(256), 0, ctx->stream,
-                       (const double*)ctx->scratch_trace[0], (const T*)ctx->scratch_trace[1], (int)waves, (int)P, count, d_trace_out);
+                       (const double*)ctx->scratch.trace[0].buf, (const T*)ctx->scratch.trace[1].buf, (int)waves, (int)P, count, d_trace_out);
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
@@ -2558,7 +2655,7 @@ struct TraceWavePlan {
   int64_t waves, tiles_per_wave;
 };
 static TraceWavePlan trace_wave_plan(const lynx_ctx* ctx, int64_t B, int64_t N, int U /* particles per lane */, int64_t points) {
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t cus = compute_units(ctx);
   const int64_t tiles = (N + 64 * U - 1) / (64 * U);
   int64_t waves = std::max<int64_t>(1, (cus * 12 + B - 1) / B);
   const int64_t slab_cap = std::max<int64_t>(1, ((int64_t)1 << 30) / (B * points * kTraceSlab * (int64_t)sizeof(double)));
@@ -2582,9 +2679,8 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   const auto [waves, tiles_per_wave] = trace_wave_plan(ctx, B, N, U, P);
   if (B * (waves / 4) > 0x7fffffffLL || B * P > 0x7fffffffLL || tiles_per_wave > 0x7fffffffLL)
     return fail(ctx, LYNX_ERR_INVALID, "beam trace: batch x points too large for one launch");
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace[0], &ctx->scratch_trace_bytes[0],
-                           (size_t)B * waves * P * kTraceSlab * sizeof(double))) ||
-      (rc = ensure_scratch(ctx, &ctx->scratch_trace[1], &ctx->scratch_trace_bytes[1], (size_t)B * P * kTraceRef * sizeof(T))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.trace[0], (size_t)B * waves * P * kTraceSlab * sizeof(double))) ||
+      (rc = ensure_scratch(ctx, ctx->scratch.trace[1], (size_t)B * P * kTraceRef * sizeof(T))))
     return rc;
   TraceArgs a{};
   a.n_particles = N;
@@ -2593,17 +2689,17 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
   a.tiles_per_wave = (int32_t)tiles_per_wave;
   a.store = d_p_out ? 1 : 0;
   a.points = P;
-  const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
-  const T* ref = (const T*)ctx->scratch_trace[1];
-  double* slabs = (double*)ctx->scratch_trace[0];
+  const T* table = (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf;
+  const T* ref = (const T*)ctx->scratch.trace[1].buf;
+  double* slabs = (double*)ctx->scratch.trace[0].buf;
   if ((ap || sc) && (rc = trace_plan(ctx, S, ap, sc))) return rc;
   // a trace with screens and without an aperture loses nobody: its records are the plain trace's (slot 35 = N)
   const bool counted = ap && (!sc || ap->count > 0);
-  const TraceLosses loss{(const int64_t*)ctx->scratch_trace_plan, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0,
+  const TraceLosses loss{(const int64_t*)ctx->scratch.trace_plan.buf, counted ? ap->d_limits : nullptr, counted ? ap->limit_stride : 0,
                          ap ? ap->d_lost_at : nullptr};
   hipLaunchKernelGGL(k_trace_reference<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, dev_view(lat), table, (const T*)d_energy_in,
                      (const T*)d_p_in, a.in_stride, N, counted ? loss.plan : nullptr, (const T*)loss.limits, loss.limit_stride,
-                     (T*)ctx->scratch_trace[1], (T*)d_energy_trace);
+                     (T*)ctx->scratch.trace[1].buf, (T*)d_energy_trace);
   HIP_TRY(ctx, hipGetLastError());
   // (on the context's stream: a null-stream memset does not wait for what this stream still runs)
   if (sc) HIP_TRY(ctx, hipMemsetAsync(sc->d_images, 0, (size_t)B * sc->cells * sizeof(int32_t), ctx->stream));
@@ -2629,7 +2725,7 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
     const TraceTrajectories chosen{tj->d_indices, tj->count, tj->d_trajectories, tj->d_lost_in};
     hipLaunchKernelGGL(k_trace_trajectories<T>, dim3((unsigned)(B * ((tj->count + kChosenTile - 1) / kChosenTile))), dim3(64), 0,
                        ctx->stream, chosen, S, table, (const T*)d_p_in, a.in_stride,
-                       (ap || sc) ? (const int64_t*)ctx->scratch_trace_plan : nullptr, (const T*)(ap ? ap->d_limits : nullptr),
+                       (ap || sc) ? (const int64_t*)ctx->scratch.trace_plan.buf : nullptr, (const T*)(ap ? ap->d_limits : nullptr),
                        ap ? ap->limit_stride : (int64_t)0);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -2641,8 +2737,7 @@ static int track_particles_along_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, 
 static int track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
                                  const void* d_p_in, void* d_p_out, void* d_energy_trace, double* d_trace_out, int flags,
                                  const TraceApertures* ap, TraceScreenList* sc, const TraceChosen* tj = nullptr) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   const char* mode = tj ? "beam trace with trajectories: " : sc ? "beam trace with screens: " : ap ? "beam trace with losses: " : "beam trace: ";
   const auto refuse = [&](const char* what) { return fail(ctx, LYNX_ERR_INVALID, std::string(mode) + what); };
   if (!lat || !d_energy_in || !d_p_in || !d_energy_trace || !d_trace_out) return refuse("null argument");
@@ -2685,22 +2780,19 @@ static int track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_par
     if (nx < 1 || ny < 1) return refuse("a screen has at least one pixel each way");
     sc->cells += (int64_t)nx * ny;
   }
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
   const size_t es = dtype_size(lat->dtype);
-  const size_t points = (size_t)lat->n_steps + 1;
-  ctx->wrote(d_p_out, (size_t)lat->batch * n_particles * 7 * es);
-  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
-  ctx->wrote(d_trace_out, (size_t)lat->batch * points * LYNX_MOMENT_STRIDE * sizeof(double));
-  if (ap) ctx->wrote(ap->d_lost_at, (size_t)lat->batch * n_particles * sizeof(int32_t));
-  if (sc) ctx->wrote(sc->d_images, (size_t)lat->batch * sc->cells * sizeof(int32_t));
-  if (tj) {
-    ctx->wrote(tj->d_trajectories, (size_t)lat->batch * points * tj->count * 7 * es);
-    ctx->wrote(tj->d_lost_in, (size_t)lat->batch * tj->count * sizeof(int32_t));
-  }
-  return lat->dtype == LYNX_F64
-             ? track_particles_along_t<double>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc, tj)
-             : track_particles_along_t<float>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out, flags, ap, sc, tj);
+  const size_t B = (size_t)lat->batch, points = (size_t)lat->n_steps + 1;
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_p_out, B * n_particles * 7 * es},
+                                      {d_energy_trace, B * points * es},
+                                      {d_trace_out, B * points * LYNX_MOMENT_STRIDE * sizeof(double)},
+                                      {ap ? ap->d_lost_at : nullptr, B * n_particles * sizeof(int32_t)},
+                                      {sc ? sc->d_images : nullptr, sc ? B * sc->cells * sizeof(int32_t) : 0},
+                                      {tj ? tj->d_trajectories : nullptr, tj ? B * points * tj->count * 7 * es : 0},
+                                      {tj ? tj->d_lost_in : nullptr, tj ? B * tj->count * sizeof(int32_t) : 0}});
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return track_particles_along_t<decltype(zero)>(ctx, lat, n_particles, d_energy_in, d_p_in, d_p_out, d_energy_trace, d_trace_out,
+                                                   flags, ap, sc, tj);
+  });
 }
 
 int lynx_track_particles_along(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
@@ -2755,9 +2847,8 @@ static int moments_by_loss_t(lynx_ctx* ctx, int64_t B, int64_t N, const void* d_
   if (B * (waves / 4) > 0x7fffffffLL || B * J > 0x7fffffffLL || tiles_per_wave > 0x7fffffffLL)
     return fail(ctx, LYNX_ERR_INVALID, "moments by loss: batch too large for one launch");
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_trace[0], &ctx->scratch_trace_bytes[0],
-                           (size_t)B * waves * J * kTraceSlab * sizeof(double))) ||
-      (rc = ensure_scratch(ctx, &ctx->scratch_trace[1], &ctx->scratch_trace_bytes[1], (size_t)B * J * kTraceRef * sizeof(T))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.trace[0], (size_t)B * waves * J * kTraceSlab * sizeof(double))) ||
+      (rc = ensure_scratch(ctx, ctx->scratch.trace[1], (size_t)B * J * kTraceRef * sizeof(T))))
     return rc;
   LossSetArgs a{};
   a.n_particles = N;
@@ -2766,15 +2857,14 @@ static int moments_by_loss_t(lynx_ctx* ctx, int64_t B, int64_t N, const void* d_
   a.tiles_per_wave = (int32_t)tiles_per_wave;
   a.sets = J;
   hipLaunchKernelGGL((k_moments_by_loss<T, U>), dim3((unsigned)(B * (waves / 4))), dim3(256), 0, ctx->stream, a, (const T*)d_p,
-                     d_lost_at, (double*)ctx->scratch_trace[0], (T*)ctx->scratch_trace[1]);
+                     d_lost_at, (double*)ctx->scratch.trace[0].buf, (T*)ctx->scratch.trace[1].buf);
   HIP_TRY(ctx, hipGetLastError());
   return launch_trace_finalize<T>(ctx, B, J, waves, -1, d_records_out);
 }
 
 int lynx_moments_by_loss(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p, int flags,
                          int32_t n_apertures, const int32_t* d_lost_at, double* d_records_out) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   const auto refuse = [&](const std::string& what) { return fail(ctx, LYNX_ERR_INVALID, "moments by loss: " + what); };
   if (!d_p || !d_lost_at || !d_records_out) return refuse("null argument");
   if (dtype != LYNX_F32 && dtype != LYNX_F64) return refuse("dtype is LYNX_F32 or LYNX_F64");
@@ -2783,11 +2873,10 @@ int lynx_moments_by_loss(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_part
   if (flags & ~LYNX_TRACK_SHARED_INPUT) return refuse("LYNX_TRACK_SHARED_INPUT is the only flag");
   if (n_apertures < 1 || n_apertures > kTraceMaxLossApertures)
     return refuse("n_apertures = " + std::to_string(n_apertures) + ", not 1 .. " + std::to_string(kTraceMaxLossApertures));
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
-  ctx->wrote(d_records_out, (size_t)batch * (n_apertures + 1) * LYNX_MOMENT_STRIDE * sizeof(double));
-  return dtype == LYNX_F64 ? moments_by_loss_t<double>(ctx, batch, n_particles, d_p, flags, n_apertures, d_lost_at, d_records_out)
-                           : moments_by_loss_t<float>(ctx, batch, n_particles, d_p, flags, n_apertures, d_lost_at, d_records_out);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_records_out, (size_t)batch * (n_apertures + 1) * LYNX_MOMENT_STRIDE * sizeof(double)}});
+  return with_dtype(dtype, [&](auto zero) {
+    return moments_by_loss_t<decltype(zero)>(ctx, batch, n_particles, d_p, flags, n_apertures, d_lost_at, d_records_out);
+  });
 }
 
 template <typename T>
@@ -2796,7 +2885,7 @@ static int track_moments_along_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d
   int rc;
   if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
   const int64_t B = lat->batch;
-  const T* table = (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace];
+  const T* table = (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf;
   hipLaunchKernelGGL(k_trace_energies<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
                      (const T*)d_energy_in, (T*)d_energy_trace);
   HIP_TRY(ctx, hipGetLastError());
@@ -2814,21 +2903,16 @@ static int track_moments_along_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d
 
 int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                              const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_mu_in || !d_cov_in || !d_mu_trace || !d_cov_trace || !d_energy_trace)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "bad batch");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
   const size_t es = dtype_size(lat->dtype);
-  const size_t points = (size_t)lat->n_steps + 1;
-  ctx->wrote(d_energy_trace, (size_t)lat->batch * points * es);
-  ctx->wrote(d_mu_trace, (size_t)lat->batch * points * 7 * es);
-  ctx->wrote(d_cov_trace, (size_t)lat->batch * points * 49 * es);
-  return lat->dtype == LYNX_F64
-             ? track_moments_along_t<double>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace)
-             : track_moments_along_t<float>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace);
+  const size_t points = (size_t)lat->batch * ((size_t)lat->n_steps + 1);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_energy_trace, points * es}, {d_mu_trace, points * 7 * es}, {d_cov_trace, points * 49 * es}});
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return track_moments_along_t<decltype(zero)>(ctx, lat, d_energy_in, d_mu_in, d_cov_in, d_mu_trace, d_cov_trace, d_energy_trace);
+  });
 }
 
 // ---- reverse pass of the beam trace: gradients of the moments at every point -----------------
@@ -2840,13 +2924,12 @@ constexpr int32_t kTraceBwdMaxSteps = 256;
 
 // What the entry points share.  trace_backward_begin: the trace table and the scratch of T_bar and of k_build_bwd;
 // trace_backward_finish: k_build_bwd on the "every element a step of its own" program over the T_bar a sweep left in
-// scratch_grad[1], then the energy cotangents.
+// scratch.grad[1], then the energy cotangents.
 template <typename T>
 static int trace_backward_begin(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in) {
   int rc;
   if ((rc = sync_pool(ctx, lat))) return rc;  // (k_build_bwd and k_trace_energy_bwd read the parameters from memory)
   if ((rc = trace_table<T>(ctx, lat, d_energy_in))) return rc;
-  ctx->main_dirty = true;
   return ensure_tbar_scratch<T>(ctx, lat);
 }
 
@@ -2856,7 +2939,7 @@ static int trace_backward_finish(lynx_ctx* ctx, lynx_lattice* lat, const void* d
   if (const int rc = launch_build_bwd<T>(ctx, lat, d_energy_in, d_grad_params, d_grad_energy_in, 0, false)) return rc;
   if (d_energy_bar) {
     hipLaunchKernelGGL(k_trace_energy_bwd<T>, dim3((unsigned)((lat->batch + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat),
-                       (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)d_energy_bar, (T*)d_grad_params,
+                       (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf, (const T*)d_energy_bar, (T*)d_grad_params,
                        (T*)d_grad_energy_in);
     HIP_TRY(ctx, hipGetLastError());
   }
@@ -2868,8 +2951,8 @@ template <typename T, typename ST>
 static int trace_backward_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_mu_trace, const void* d_cov_trace,
                                   const void* d_mu_bar, const void* d_cov_bar, void* d_grad_mu_in, void* d_grad_cov_in) {
   hipLaunchKernelGGL((k_trace_moments_bwd<T, ST>), dim3((unsigned)lat->batch), dim3(64), 0, ctx->stream, (int)lat->n_steps,
-                     (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const ST*)d_mu_trace, (const ST*)d_cov_trace,
-                     (const ST*)d_mu_bar, (const ST*)d_cov_bar, (T*)ctx->scratch_grad[1], (T*)d_grad_mu_in, (T*)d_grad_cov_in);
+                     (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf, (const ST*)d_mu_trace, (const ST*)d_cov_trace,
+                     (const ST*)d_mu_bar, (const ST*)d_cov_bar, (T*)ctx->scratch.grad[1].buf, (T*)d_grad_mu_in, (T*)d_grad_cov_in);
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
@@ -2910,22 +2993,19 @@ int lynx_track_moments_along_backward(lynx_ctx* ctx, lynx_lattice* lat, const vo
                                       const void* d_cov_trace, const void* d_mu_bar, const void* d_cov_bar,
                                       const void* d_energy_bar, void* d_grad_params, void* d_grad_energy_in,
                                       void* d_grad_mu_in, void* d_grad_cov_in) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_mu_trace || !d_cov_trace || !d_mu_bar || !d_cov_bar || !d_grad_params ||
       !d_grad_energy_in || !d_grad_mu_in || !d_grad_cov_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (const int rc = trace_backward_check(ctx, lat, "beam trace gradients: ")) return rc;
-  HIP_TRY(ctx, use_device(ctx));
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
-  return lat->dtype == LYNX_F64
-             ? trace_backward_t<double>(ctx, lat, d_energy_in, d_mu_trace, d_cov_trace, d_mu_bar, d_cov_bar, d_energy_bar,
-                                        d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in)
-             : trace_backward_t<float>(ctx, lat, d_energy_in, d_mu_trace, d_cov_trace, d_mu_bar, d_cov_bar, d_energy_bar,
-                                       d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, reverse_writes(lat, d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return trace_backward_t<decltype(zero)>(ctx, lat, d_energy_in, d_mu_trace, d_cov_trace, d_mu_bar, d_cov_bar, d_energy_bar,
+                                            d_grad_params, d_grad_energy_in, d_grad_mu_in, d_grad_cov_in);
+  });
 }
 
-// A ParticleBeam's states and cotangents of the sweep in scratch_grad[0]: mu [7] | cov [49] | mu_bar [7] | cov_bar [49] per
+// A ParticleBeam's states and cotangents of the sweep in scratch.grad[0]: mu [7] | cov [49] | mu_bar [7] | cov_bar [49] per
 // (sample, point), block by block, in the float64 of the records (k_trace_records_to_states), and `behind` more scalars
 // behind them for the caller.  Null records: no moment sweep -- no blocks, no launch, `behind` starts the scratch.
 struct TraceSweepStates {
@@ -2936,10 +3016,9 @@ static int trace_sweep_states(lynx_ctx* ctx, lynx_lattice* lat, const double* d_
   const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
   const size_t state_scalars = d_trace_fwd ? (size_t)points * 112 : 0;
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0],
-                           std::max<size_t>(state_scalars + behind, 1) * sizeof(double))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.grad[0], std::max<size_t>(state_scalars + behind, 1) * sizeof(double))))
     return rc;
-  st->mu = (double*)ctx->scratch_grad[0];
+  st->mu = (double*)ctx->scratch.grad[0].buf;
   st->cov = st->mu + points * 7;
   st->mu_bar = st->cov + points * 49;
   st->cov_bar = st->mu_bar + points * 7;
@@ -2965,26 +3044,23 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
                                         const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
                                         void* d_grad_params, void* d_grad_energy_in, void* d_grad_mean_in,
                                         void* d_grad_cov_in) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!lat || !d_energy_in || !d_trace_fwd || !d_grad_trace || !d_grad_params || !d_grad_energy_in || !d_grad_mean_in ||
       !d_grad_cov_in)
     return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
   if (const int rc = trace_backward_check(ctx, lat, "beam trace gradients: ")) return rc;
   if (const int rc = trace_backward_no_cavity(ctx, lat, "beam trace gradients of a ParticleBeam: ")) return rc;
-  HIP_TRY(ctx, use_device(ctx));
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
-  return lat->dtype == LYNX_F64
-             ? particles_along_backward_t<double>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
-                                                  d_grad_energy_in, d_grad_mean_in, d_grad_cov_in)
-             : particles_along_backward_t<float>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
-                                                 d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, reverse_writes(lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return particles_along_backward_t<decltype(zero)>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
+                                                      d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+  });
 }
 
 // ... through cavity steps: k_track_bwd's sweep over the particles with a moment cotangent injected at every point
 // (k_track_bwd_inject), on the trace's program -- every step a unit of its own --, its partial sums reduced into
-// scratch_grad[1] as track_backward_t reduces them, then the same k_build_bwd.  scratch_grad[0]: the partial sums
+// scratch.grad[1] as track_backward_t reduces them, then the same k_build_bwd.  scratch.grad[0]: the partial sums
 // [B][chunks][S][64], then the injection table [B][P][kInjectStride], both in the lattice's dtype.
 template <typename T, typename Z>
 static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat, int64_t N, const void* d_energy_in,
@@ -3003,9 +3079,9 @@ static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat,
   if ((rc = allow_lds(ctx, k_track_bwd_inject<T, Z>, p.lds))) return rc;
   // (sized before trace_backward_begin, the table launched behind it: what is refused is refused before the build)
   const size_t partial_scalars = (size_t)B * p.chunks * S * kGradStride, table_scalars = (size_t)B * P * kInjectStride;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (partial_scalars + table_scalars) * sizeof(T))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.grad[0], (partial_scalars + table_scalars) * sizeof(T))))
     return rc;
-  T* partials = (T*)ctx->scratch_grad[0];
+  T* partials = (T*)ctx->scratch.grad[0].buf;
   T* inject = partials + partial_scalars;
   if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
   hipLaunchKernelGGL(k_trace_inject_table<T>, dim3((unsigned)((table_scalars + 255) / 256)), dim3(256), 0, ctx->stream, d_trace_fwd,
@@ -3019,7 +3095,7 @@ static int particles_along_backward_cavities_t(lynx_ctx* ctx, lynx_lattice* lat,
   }
   hipExtLaunchKernelGGL((k_track_bwd_inject<T, Z>), dim3((unsigned)(B * p.chunks)), dim3(kTrackThreads), (std::uint32_t)p.lds, ctx->stream,
                         e0, e1, 0u, dev_view(lat), a, (const T*)d_p_in, (flags & LYNX_TRACK_SHARED_INPUT) ? (int64_t)0 : N * 7,
-                        (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)inject, partials, (T*)d_grad_p_in);
+                        (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf, (const T*)inject, partials, (T*)d_grad_p_in);
   HIP_TRY(ctx, hipGetLastError());
   if (ctx->profiling) ctx->prof_events.emplace_back(e0, e1);
   if ((rc = reduce_tbar<T>(ctx, partials, B, S, p.chunks))) return rc;
@@ -3031,8 +3107,7 @@ int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* la
                                                  const double* d_trace_fwd, const double* d_grad_trace,
                                                  const void* d_energy_bar, void* d_grad_params, void* d_grad_energy_in,
                                                  void* d_grad_p_in) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   const std::string prefix = "beam trace gradients with cavities: ";
   const auto refuse = [&](const std::string& what) { return fail(ctx, LYNX_ERR_INVALID, prefix + what); };
   if (!lat || !d_energy_in || !d_p_in || !d_trace_fwd || !d_grad_trace || !d_grad_params || !d_grad_energy_in)
@@ -3046,9 +3121,8 @@ int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* la
   const size_t lds = lat->dtype == LYNX_F64 ? bwd_stream_lds_bytes<double, 1>(lat->n_steps) : bwd_stream_lds_bytes<float, 2>(lat->n_steps);
   if (const int rc = refuse_bwd_stream_lds(ctx, prefix.c_str(), lat->n_steps, lds)) return rc;
   if (d_grad_p_in && d_grad_p_in == d_p_in) return refuse("d_grad_p_in aliases d_p_in: the sweep reads the incoming particles tile by tile");
-  HIP_TRY(ctx, use_device(ctx));
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
-  ctx->wrote(d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype));
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, reverse_writes(lat, d_grad_params, d_grad_energy_in, nullptr, nullptr,
+                                                    {d_grad_p_in, (size_t)lat->batch * n_particles * 7 * dtype_size(lat->dtype)}));
   const auto pass = lat->dtype == LYNX_F64 ? particles_along_backward_cavities_t<double, double>
                                            : particles_along_backward_cavities_t<float, lynx_f32x2>;
   return pass(ctx, lat, n_particles, d_energy_in, d_p_in, flags, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
@@ -3057,7 +3131,7 @@ int lynx_track_particles_along_backward_cavities(lynx_ctx* ctx, lynx_lattice* la
 
 // ... of a trace with losses: one wave per (sample, survivor set) propagates the set's incoming moments and sweeps back
 // over the set's live points (k_trace_moments_bwd_sets), the sets' T_bar are added in set order (k_trace_sum_sets), then
-// the same k_build_bwd.  scratch_grad[0]: the states [B][A + 1][S][56], then the sets' T_bar [A + 1][B][S][64], float64.
+// the same k_build_bwd.  scratch.grad[0]: the states [B][A + 1][S][56], then the sets' T_bar [A + 1][B][S][64], float64.
 template <typename T>
 static int particles_along_backward_losses_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const double* d_grad_trace,
                                              const void* d_energy_bar, const TraceLossSets& sets, const double* d_set_records,
@@ -3065,17 +3139,17 @@ static int particles_along_backward_losses_t(lynx_ctx* ctx, lynx_lattice* lat, c
   const int64_t B = lat->batch, S = lat->n_steps, J = sets.sets;
   const size_t state_scalars = (size_t)B * J * S * kSetState, tbar_scalars = (size_t)J * B * S * kGradStride;
   int rc;
-  if ((rc = ensure_scratch(ctx, &ctx->scratch_grad[0], &ctx->scratch_grad_bytes[0], (state_scalars + tbar_scalars) * sizeof(double))))
+  if ((rc = ensure_scratch(ctx, ctx->scratch.grad[0], (state_scalars + tbar_scalars) * sizeof(double))))
     return rc;
-  double* states = (double*)ctx->scratch_grad[0];
+  double* states = (double*)ctx->scratch.grad[0].buf;
   double* tbar_sets = states + state_scalars;
   if ((rc = trace_backward_begin<T>(ctx, lat, d_energy_in))) return rc;
   hipLaunchKernelGGL(k_trace_moments_bwd_sets<T>, dim3((unsigned)(B * J)), dim3(64), 0, ctx->stream, (int)S, B, sets,
-                     (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], d_set_records, d_grad_trace, states, tbar_sets);
+                     (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf, d_set_records, d_grad_trace, states, tbar_sets);
   HIP_TRY(ctx, hipGetLastError());
   const int64_t cells = B * S * kGradStride;
   hipLaunchKernelGGL(k_trace_sum_sets<T>, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, (const double*)tbar_sets,
-                     (int)J, cells, (T*)ctx->scratch_grad[1]);
+                     (int)J, cells, (T*)ctx->scratch.grad[1].buf);
   HIP_TRY(ctx, hipGetLastError());
   return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
 }
@@ -3084,8 +3158,7 @@ int lynx_track_particles_along_backward_losses(lynx_ctx* ctx, lynx_lattice* lat,
                                                const double* d_trace_fwd, const double* d_grad_trace, const void* d_energy_bar,
                                                int32_t n_apertures, const int32_t* apertures, const double* d_set_records,
                                                void* d_grad_params, void* d_grad_energy_in) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   const std::string prefix = "beam trace gradients with losses: ";
   const auto refuse = [&](const std::string& what) { return fail(ctx, LYNX_ERR_INVALID, prefix + what); };
   if (!lat || !d_energy_in || !d_trace_fwd || !d_grad_trace || !apertures || !d_set_records || !d_grad_params || !d_grad_energy_in)
@@ -3109,17 +3182,15 @@ int lynx_track_particles_along_backward_losses(lynx_ctx* ctx, lynx_lattice* lat,
     sets.last[k] = step;
   }
   sets.last[n_apertures] = lat->n_steps;
-  HIP_TRY(ctx, use_device(ctx));
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, nullptr, nullptr);
-  return lat->dtype == LYNX_F64
-             ? particles_along_backward_losses_t<double>(ctx, lat, d_energy_in, d_grad_trace, d_energy_bar, sets, d_set_records,
-                                                         d_grad_params, d_grad_energy_in)
-             : particles_along_backward_losses_t<float>(ctx, lat, d_energy_in, d_grad_trace, d_energy_bar, sets, d_set_records,
-                                                        d_grad_params, d_grad_energy_in);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, reverse_writes(lat, d_grad_params, d_grad_energy_in, nullptr, nullptr));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return particles_along_backward_losses_t<decltype(zero)>(ctx, lat, d_energy_in, d_grad_trace, d_energy_bar, sets, d_set_records,
+                                                             d_grad_params, d_grad_energy_in);
+  });
 }
 
 // ... with the trajectories of chosen particles: k_trace_trajectories_bwd behind the moment sweep (or alone), then the
-// same k_build_bwd.  scratch_grad[0]: the states of the moment sweep (if there is one), then the float64 row sums a
+// same k_build_bwd.  scratch.grad[0]: the states of the moment sweep (if there is one), then the float64 row sums a
 // sample's wave carries from tile to tile (if the chosen particles span several tiles).
 template <typename T>
 static int particles_along_backward_trajectories_t(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in,
@@ -3139,8 +3210,8 @@ static int particles_along_backward_trajectories_t(lynx_ctx* ctx, lynx_lattice* 
       (rc = trace_backward_moments<T, double>(ctx, lat, st.mu, st.cov, st.mu_bar, st.cov_bar, d_grad_mean_in, d_grad_cov_in)))
     return rc;
   hipLaunchKernelGGL(k_trace_trajectories_bwd<T>, dim3((unsigned)B), dim3(64), 0, ctx->stream, (int)S, n_chosen,
-                     (const T*)ctx->scratch_steps[lynx_ctx::kTableTrace], (const T*)d_trajectories, d_trajectories_bar,
-                     (T*)ctx->scratch_grad[1], partial, moments ? 1 : 0, (T*)d_grad_chosen_in);
+                     (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf, (const T*)d_trajectories, d_trajectories_bar,
+                     (T*)ctx->scratch.grad[1].buf, partial, moments ? 1 : 0, (T*)d_grad_chosen_in);
   HIP_TRY(ctx, hipGetLastError());
   return trace_backward_finish<T>(ctx, lat, d_energy_in, d_energy_bar, d_grad_params, d_grad_energy_in);
 }
@@ -3151,8 +3222,7 @@ int lynx_track_particles_along_backward_trajectories(lynx_ctx* ctx, lynx_lattice
                                                      void* d_grad_energy_in, void* d_grad_mean_in, void* d_grad_cov_in,
                                                      int64_t n_chosen, const void* d_trajectories,
                                                      const double* d_trajectories_bar, void* d_grad_chosen_in) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   const std::string what = "beam trace gradients with trajectories: ";
   if (!lat || !d_energy_in || !d_grad_params || !d_grad_energy_in || !d_trajectories || !d_trajectories_bar || !d_grad_chosen_in)
     return fail(ctx, LYNX_ERR_INVALID, what + "null argument");
@@ -3166,54 +3236,42 @@ int lynx_track_particles_along_backward_trajectories(lynx_ctx* ctx, lynx_lattice
   // (a single trajectory is differentiable through the kick; a moment cotangent does not pass it)
   if (given)
     if (const int rc = trace_backward_no_cavity(ctx, lat, what)) return rc;
-  HIP_TRY(ctx, use_device(ctx));
-  trace_backward_wrote(ctx, lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
-  ctx->wrote(d_grad_chosen_in, (size_t)lat->batch * n_chosen * 7 * dtype_size(lat->dtype));
-  return lat->dtype == LYNX_F64
-             ? particles_along_backward_trajectories_t<double>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar,
-                                                               d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,
-                                                               n_chosen, d_trajectories, d_trajectories_bar, d_grad_chosen_in)
-             : particles_along_backward_trajectories_t<float>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar,
-                                                              d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,
-                                                              n_chosen, d_trajectories, d_trajectories_bar, d_grad_chosen_in);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, reverse_writes(lat, d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,
+                                                    {d_grad_chosen_in, (size_t)lat->batch * n_chosen * 7 * dtype_size(lat->dtype)}));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    return particles_along_backward_trajectories_t<decltype(zero)>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar,
+                                                                   d_grad_params, d_grad_energy_in, d_grad_mean_in, d_grad_cov_in,
+                                                                   n_chosen, d_trajectories, d_trajectories_bar, d_grad_chosen_in);
+  });
 }
 
 // ---- screen read-out -------------------------------------------------------------------------
 
 int lynx_histogram2d(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                      const void* d_xedges, const void* d_yedges, int32_t nx, int32_t ny, int32_t* d_image) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p || !d_xedges || !d_yedges || !d_image || batch <= 0 || n_particles <= 0 || nx <= 0 || ny <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_image, (size_t)batch * nx * ny * sizeof(int32_t));
-  const size_t es = dtype_size(dtype);
-  const size_t lds = ((size_t)nx + ny + 2) * es;
+  const size_t lds = ((size_t)nx + ny + 2) * dtype_size(dtype);
   if (lds > 64 * 1024) return fail(ctx, LYNX_ERR_INVALID, "screen resolution too large for the edge table");
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_image, (size_t)batch * nx * ny * sizeof(int32_t)}});
   HIP_TRY(ctx, hipMemsetAsync(d_image, 0, (size_t)batch * nx * ny * sizeof(int32_t), ctx->stream));
-  const int64_t cus = ctx->prop.multiProcessorCount > 0 ? ctx->prop.multiProcessorCount : 256;
+  const int64_t cus = compute_units(ctx);
   int64_t chunks = std::max<int64_t>(1, std::min<int64_t>((n_particles + 1023) / 1024, (8 * cus + batch - 1) / batch));
   if (batch * chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_histogram2d<double>, dim3((unsigned)(batch * chunks)), dim3(256), lds, ctx->stream,
-                       (const double*)d_p, n_particles, (int)chunks, (const double*)d_xedges, (const double*)d_yedges,
-                       nx, ny, d_image);
-  else
-    hipLaunchKernelGGL(k_histogram2d<float>, dim3((unsigned)(batch * chunks)), dim3(256), lds, ctx->stream,
-                       (const float*)d_p, n_particles, (int)chunks, (const float*)d_xedges, (const float*)d_yedges, nx,
-                       ny, d_image);
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_histogram2d<T>, dim3((unsigned)(batch * chunks)), dim3(256), lds, ctx->stream, (const T*)d_p, n_particles,
+                       (int)chunks, (const T*)d_xedges, (const T*)d_yedges, nx, ny, d_image);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
 
 int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t packed, float* d_sin, float* d_cos) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_x || !d_sin || !d_cos || n <= 0) return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_sin, (size_t)n * sizeof(float));
-  ctx->wrote(d_cos, (size_t)n * sizeof(float));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_sin, (size_t)n * sizeof(float)}, {d_cos, (size_t)n * sizeof(float)}});
   const int64_t threads = (n + 1) / 2;
   hipLaunchKernelGGL(k_diag_phase_trig, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, d_x, n,
                      (int)packed, d_sin, d_cos);
@@ -3226,26 +3284,21 @@ int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t pac
 int lynx_aperture_mask(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p,
                        const void* d_x_max, const void* d_y_max, int32_t param_stride, int32_t elliptical,
                        unsigned char* d_mask, int32_t* d_counts, int64_t* d_offsets, int64_t* d_totals) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p || !d_x_max || !d_y_max || !d_mask || !d_counts || !d_offsets || !d_totals || batch <= 0 ||
       n_particles <= 0 || (param_stride != 0 && param_stride != 1))
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
   const int64_t chunks = (n_particles + kApertureChunk - 1) / kApertureChunk;
   if (batch * chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
-  ctx->wrote(d_mask, (size_t)batch * n_particles);
-  ctx->wrote(d_counts, (size_t)batch * chunks * sizeof(int32_t));
-  ctx->wrote(d_offsets, (size_t)batch * chunks * sizeof(int64_t));
-  ctx->wrote(d_totals, (size_t)batch * sizeof(int64_t));
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_aperture_mask<double>, dim3((unsigned)(batch * chunks)), dim3(256), 0, ctx->stream,
-                       (const double*)d_p, n_particles, (int)chunks, (const double*)d_x_max, (const double*)d_y_max,
-                       (int)param_stride, (int)elliptical, d_mask, d_counts);
-  else
-    hipLaunchKernelGGL(k_aperture_mask<float>, dim3((unsigned)(batch * chunks)), dim3(256), 0, ctx->stream,
-                       (const float*)d_p, n_particles, (int)chunks, (const float*)d_x_max, (const float*)d_y_max,
-                       (int)param_stride, (int)elliptical, d_mask, d_counts);
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_mask, (size_t)batch * n_particles},
+                                        {d_counts, (size_t)batch * chunks * sizeof(int32_t)},
+                                        {d_offsets, (size_t)batch * chunks * sizeof(int64_t)},
+                                        {d_totals, (size_t)batch * sizeof(int64_t)}});
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_aperture_mask<T>, dim3((unsigned)(batch * chunks)), dim3(256), 0, ctx->stream, (const T*)d_p, n_particles,
+                       (int)chunks, (const T*)d_x_max, (const T*)d_y_max, (int)param_stride, (int)elliptical, d_mask, d_counts);
+  });
   HIP_TRY(ctx, hipGetLastError());
   hipLaunchKernelGGL(k_aperture_scan, dim3((unsigned)batch), dim3(256), 0, ctx->stream, d_counts, (int)chunks, d_offsets,
                      d_totals);
@@ -3255,41 +3308,33 @@ int lynx_aperture_mask(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
 
 int lynx_aperture_compact(lynx_ctx* ctx, int dtype, int64_t n_particles, const void* d_p, const unsigned char* d_mask,
                           const int64_t* d_offsets, void* d_kept, void* d_lost) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p || !d_mask || !d_offsets || !d_kept || !d_lost || n_particles <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_kept, (size_t)n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
-  ctx->wrote(d_lost, (size_t)n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
+  const size_t bytes = (size_t)n_particles * 7 * dtype_size(dtype);
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_kept, bytes}, {d_lost, bytes}});
   const int64_t chunks = (n_particles + kApertureChunk - 1) / kApertureChunk;
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_aperture_compact<double>, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, (const double*)d_p,
-                       n_particles, d_mask, d_offsets, (double*)d_kept, (double*)d_lost);
-  else
-    hipLaunchKernelGGL(k_aperture_compact<float>, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, (const float*)d_p,
-                       n_particles, d_mask, d_offsets, (float*)d_kept, (float*)d_lost);
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_aperture_compact<T>, dim3((unsigned)chunks), dim3(256), 0, ctx->stream, (const T*)d_p, n_particles, d_mask,
+                       d_offsets, (T*)d_kept, (T*)d_lost);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
 
 int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_mu, const void* d_cov,
                         const void* d_xs, const void* d_ys, int32_t nx, int32_t ny, void* d_image) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_mu || !d_cov || !d_xs || !d_ys || !d_image || batch <= 0 || nx <= 0 || ny <= 0 || batch > 65535)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_image, (size_t)batch * nx * ny * (dtype == LYNX_F64 ? 8 : 4));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_image, (size_t)batch * nx * ny * dtype_size(dtype)}});
   const unsigned gx = (unsigned)(((int64_t)nx * ny + 255) / 256);
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_gaussian_image<double>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream,
-                       (const double*)d_mu, (const double*)d_cov, (const double*)d_xs, (const double*)d_ys, nx, ny,
-                       (double*)d_image);
-  else
-    hipLaunchKernelGGL(k_gaussian_image<float>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream,
-                       (const float*)d_mu, (const float*)d_cov, (const float*)d_xs, (const float*)d_ys, nx, ny,
-                       (float*)d_image);
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_gaussian_image<T>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream, (const T*)d_mu, (const T*)d_cov,
+                       (const T*)d_xs, (const T*)d_ys, nx, ny, (T*)d_image);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
@@ -3297,8 +3342,7 @@ int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_m
 int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
                                const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
                                const void* d_misalignment, int64_t misalignment_stride, void* d_images) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !d_images || batch <= 0 || batch > 65535 ||
       n_points <= 0 || n_screens <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
@@ -3311,24 +3355,17 @@ int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t 
       return fail(ctx, LYNX_ERR_INVALID, "images along the trace: a screen's point lies inside the trace, and it has pixels");
     cells += (int64_t)nx * ny;
   }
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->main_dirty = true;
-  const size_t es = dtype_size(dtype);
-  ctx->wrote(d_images, (size_t)batch * cells * es);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_images, (size_t)batch * cells * dtype_size(dtype)}});
   int64_t grid = 0, cell = 0;
   for (int32_t k = 0; k < n_screens; ++k) {
     const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
     const unsigned gx = (unsigned)(((int64_t)nx * ny + 255) / 256);
-    if (dtype == LYNX_F64)
-      hipLaunchKernelGGL(k_gaussian_image_along<double>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream,
-                         (const double*)d_mu_trace, (const double*)d_cov_trace, (int)n_points, (int)point, (const double*)d_grid + grid,
-                         (const double*)d_grid + grid + nx, (int)nx, (int)ny, (const double*)d_misalignment + 2 * k,
-                         misalignment_stride, (double*)d_images + cell, cells);
-    else
-      hipLaunchKernelGGL(k_gaussian_image_along<float>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream,
-                         (const float*)d_mu_trace, (const float*)d_cov_trace, (int)n_points, (int)point, (const float*)d_grid + grid,
-                         (const float*)d_grid + grid + nx, (int)nx, (int)ny, (const float*)d_misalignment + 2 * k,
-                         misalignment_stride, (float*)d_images + cell, cells);
+    with_dtype(dtype, [&](auto zero) {
+      using T = decltype(zero);
+      hipLaunchKernelGGL(k_gaussian_image_along<T>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream, (const T*)d_mu_trace,
+                         (const T*)d_cov_trace, (int)n_points, (int)point, (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx,
+                         (int)ny, (const T*)d_misalignment + 2 * k, misalignment_stride, (T*)d_images + cell, cells);
+    });
     HIP_TRY(ctx, hipGetLastError());
     grid += (int64_t)nx + ny;
     cell += (int64_t)nx * ny;
@@ -3345,7 +3382,7 @@ static int images_along_backward_t(lynx_ctx* ctx, int64_t batch, int32_t n_point
   for (int32_t k = 0; k < n_screens; ++k) {
     const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
     const int64_t chunks = ((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells;
-    double* d_slab = (double*)ctx->scratch_image_grad + slab;
+    double* d_slab = (double*)ctx->scratch.image_grad.buf + slab;
     hipLaunchKernelGGL(k_gaussian_image_along_bwd<T>, dim3((unsigned)chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
                        ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)point,
                        (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx, (int)ny, (const T*)d_misalignment + 2 * k,
@@ -3367,8 +3404,7 @@ int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch,
                                         const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
                                         const void* d_misalignment, int64_t misalignment_stride, const void* d_images_bar,
                                         void* d_mu_bar, void* d_cov_bar, void* d_grad_misalignment) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !d_images_bar || !d_mu_bar || !d_cov_bar ||
       batch <= 0 || batch > 65535 || n_points <= 0 || n_screens <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: bad argument");
@@ -3386,33 +3422,26 @@ int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch,
     cells += (int64_t)nx * ny;
     slab += batch * (((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells) * 6;
   }
-  HIP_TRY(ctx, use_device(ctx));
-  if (const int rc = ensure_scratch(ctx, &ctx->scratch_image_grad, &ctx->scratch_image_grad_bytes, (size_t)slab * sizeof(double)))
-    return rc;
-  ctx->main_dirty = true;
   const size_t es = dtype_size(dtype);
-  ctx->wrote(d_mu_bar, (size_t)batch * n_points * 7 * es);
-  ctx->wrote(d_cov_bar, (size_t)batch * n_points * 49 * es);
-  ctx->wrote(d_grad_misalignment, (size_t)batch * n_screens * 2 * es);
-  return dtype == LYNX_F64
-             ? images_along_backward_t<double>(ctx, batch, n_points, d_mu_trace, d_cov_trace, n_screens, screens, d_grid,
-                                               d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
-                                               d_grad_misalignment)
-             : images_along_backward_t<float>(ctx, batch, n_points, d_mu_trace, d_cov_trace, n_screens, screens, d_grid,
-                                              d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
-                                              d_grad_misalignment);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_mu_bar, (size_t)batch * n_points * 7 * es},
+                                      {d_cov_bar, (size_t)batch * n_points * 49 * es},
+                                      {d_grad_misalignment, (size_t)batch * n_screens * 2 * es}});
+  if (const int rc = ensure_scratch(ctx, ctx->scratch.image_grad, (size_t)slab * sizeof(double))) return rc;
+  return with_dtype(dtype, [&](auto zero) {
+    return images_along_backward_t<decltype(zero)>(ctx, batch, n_points, d_mu_trace, d_cov_trace, n_screens, screens, d_grid,
+                                                   d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
+                                                   d_grad_misalignment);
+  });
 }
 
 // ---- synthetic beams -------------------------------------------------------------------
 
 int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const double* mu,
                        const double* sigma, uint64_t seed, void* d_p) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p || !mu || !sigma || batch <= 0 || n_particles <= 0)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_p, (size_t)batch * n_particles * 7 * (dtype == LYNX_F64 ? 8 : 4));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_p, (size_t)batch * n_particles * 7 * dtype_size(dtype)}});
   GaussArgs g;
   for (int i = 0; i < 6; ++i) {
     g.mu[i] = mu[i];
@@ -3420,44 +3449,40 @@ int lynx_fill_gaussian(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_partic
   }
   const int64_t total = batch * n_particles * 7;
   const unsigned grid = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 32);
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_fill_gaussian<double>, dim3(grid), dim3(256), 0, ctx->stream, (double*)d_p, total, seed, g);
-  else
-    hipLaunchKernelGGL(k_fill_gaussian<float>, dim3(grid), dim3(256), 0, ctx->stream, (float*)d_p, total, seed, g);
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_fill_gaussian<T>, dim3(grid), dim3(256), 0, ctx->stream, (T*)d_p, total, seed, g);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
 
 // wave tiles of 64 lanes x (16 / element size) particles, four to a workgroup
 static unsigned wave_tile_grid(int dtype, int64_t total_particles, int max_blocks) {
-  const int64_t per_block = 4 * 64 * (dtype == LYNX_F64 ? 2 : 4);
+  const int64_t per_block = 4 * 64 * (16 / (int64_t)dtype_size(dtype));
   return (unsigned)std::min<int64_t>((total_particles + per_block - 1) / per_block, max_blocks);
 }
 
 int lynx_fill_gaussian_rows(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const double* d_rows,
                             uint64_t seed, void* d_p) {
-  LYNX_NEED(ctx);
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p || !d_rows || batch <= 0 || n_particles <= 0 || (dtype != LYNX_F32 && dtype != LYNX_F64) ||
       batch > (int64_t)(0x7fffffffffffffffLL / 14) / n_particles)  // (2 * scalars is the generator's counter)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_p, (size_t)batch * n_particles * 7 * dtype_size(dtype));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_p, (size_t)batch * n_particles * 7 * dtype_size(dtype)}});
   const int64_t total = batch * n_particles;
   const unsigned grid = wave_tile_grid(dtype, total, kBeamFactoryMaxBlocks);
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_fill_gaussian_rows<double>, dim3(grid), dim3(256), 0, ctx->stream, (double*)d_p, n_particles,
-                       total, d_rows, seed);
-  else
-    hipLaunchKernelGGL(k_fill_gaussian_rows<float>, dim3(grid), dim3(256), 0, ctx->stream, (float*)d_p, n_particles, total,
-                       d_rows, seed);
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_fill_gaussian_rows<T>, dim3(grid), dim3(256), 0, ctx->stream, (T*)d_p, n_particles, total, d_rows, seed);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
 
 int lynx_transform_particles(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, const void* d_p_in,
                              int64_t in_sample_stride, const void* d_rows, void* d_p_out) {
-  LYNX_NEED(ctx);
+  LYNX_MAIN_ENTRY(ctx);
   if (!d_p_in || !d_rows || !d_p_out || batch <= 0 || n_particles <= 0 || (dtype != LYNX_F32 && dtype != LYNX_F64) ||
       batch > (int64_t)(0x7fffffffffffffffLL / 7 / 8) / n_particles)
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
@@ -3465,17 +3490,14 @@ int lynx_transform_particles(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_
     return fail(ctx, LYNX_ERR_INVALID, "transform: the incoming sample stride is 0 (one stored sample) or n_particles * 7");
   if (in_sample_stride == 0 && d_p_in == d_p_out)
     return fail(ctx, LYNX_ERR_INVALID, "transform: one stored sample cannot be rescaled in place");
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_p_out, (size_t)batch * n_particles * 7 * dtype_size(dtype));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_p_out, (size_t)batch * n_particles * 7 * dtype_size(dtype)}});
   const int64_t total = batch * n_particles;
   const unsigned grid = wave_tile_grid(dtype, total, kBeamFactoryMaxBlocks);
-  if (dtype == LYNX_F64)
-    hipLaunchKernelGGL(k_transform_particles<double>, dim3(grid), dim3(256), 0, ctx->stream, (const double*)d_p_in,
-                       in_sample_stride, (double*)d_p_out, n_particles, total, (const double*)d_rows);
-  else
-    hipLaunchKernelGGL(k_transform_particles<float>, dim3(grid), dim3(256), 0, ctx->stream, (const float*)d_p_in,
-                       in_sample_stride, (float*)d_p_out, n_particles, total, (const float*)d_rows);
+  with_dtype(dtype, [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL(k_transform_particles<T>, dim3(grid), dim3(256), 0, ctx->stream, (const T*)d_p_in, in_sample_stride,
+                       (T*)d_p_out, n_particles, total, (const T*)d_rows);
+  });
   HIP_TRY(ctx, hipGetLastError());
   return LYNX_OK;
 }
@@ -3484,14 +3506,12 @@ int lynx_transform_particles(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_
 
 int lynx_diag_copy(lynx_ctx* ctx, void* d_dst, const void* d_src, size_t bytes, int repeats, int vec_per_thread,
                    float* avg_ms) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   const int per_thread = vec_per_thread >= 100 ? vec_per_thread - 100 : vec_per_thread;  // >= 100: non-temporal stores
   if (!d_dst || !d_src || bytes % 16 || repeats <= 0 || vec_per_thread < 0 || per_thread > 64 ||
       (vec_per_thread >= 100 && per_thread == 0))
     return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_dst, bytes);
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_dst, bytes}});
   const int64_t n_vec = (int64_t)(bytes / 16);
   const int vpt = vec_per_thread;  // 0 = grid-stride
   const unsigned grid = per_thread > 0 ? (unsigned)((n_vec + 256LL * per_thread - 1) / (256LL * per_thread))
@@ -3575,11 +3595,9 @@ int lynx_comm_info(lynx_ctx* ctx, int32_t* rccl_version, int32_t* n_ranks, int32
 }
 
 int lynx_gather_moments(lynx_ctx* ctx, const double* d_send, double* d_recv, int64_t count) {
-  LYNX_NEED(ctx);
-  ctx->main_idle = false;  // (something is about to be enqueued on the main stream)
+  LYNX_MAIN_ENTRY(ctx);
   if (!ctx->comm) return fail(ctx, LYNX_ERR_INVALID, "communicator not initialised");
-  HIP_TRY(ctx, use_device(ctx));
-  ctx->wrote(d_recv, (size_t)std::max(1, ctx->comm_ranks) * count * sizeof(double));
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_recv, (size_t)std::max(1, ctx->comm_ranks) * count * sizeof(double)}});
   // Default with more than one rank: the side stream.  With one rank (LYNX_FORCE_COMM rehearsals) the "gather" is
   // a copy; it follows the reduction wherever that ran.
   const bool produced_on_side = ctx->side_wrote && ctx->side_wrote == (const void*)d_send;
