@@ -536,6 +536,40 @@ int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch,
                                         const void* d_images_bar, void* d_mu_bar, void* d_cov_bar,
                                         void* d_grad_misalignment);
 
+/* The mean squared difference of the images of lynx_gaussian_images_along to target images, evaluated on the device: no
+ * image and no cotangent of one is made or moved.  Arguments up to misalignment_stride exactly as for
+ * lynx_gaussian_images_along, and
+ *   target_offsets  host [n_screens]: where this screen's target starts in a sample's row of d_targets, -1: no target
+ *   d_targets       [B][target_cells] (target_stride = target_cells) or [target_cells] (target_stride = 0: one row shared by
+ *                   the batch), lattice dtype, every target [nx][ny] in lynx_gaussian_image's layout (x flipped)
+ *   d_loss          [B][n_screens] float64: mean over the screen's pixels of (I - target)^2; 0 for a screen without a target
+ *   d_sums          [B][n_screens][6] float64: S0, Sx, Sy, Sxx, Sxy, Syy of lynx_gaussian_images_along_backward for the
+ *                   cotangent W = 2 (I - target) / (nx ny) of that loss; 0 for a screen without a target
+ * I is formed per pixel by the forward kernel's expression (the loss is that of the image lynx_gaussian_images_along writes,
+ * bit for bit), I - target and W in float64.  One pass over the target: a workgroup sums LYNX_IMAGE_GRAD_CELLS consecutive
+ * cells in float64 (both dtypes) and writes seven partial sums to a slab in the context's scratch; a second small kernel adds
+ * a sample's slab in a fixed order.  No atomics: the same call returns the same bits.  det <= 0 gives a NaN loss and NaN
+ * sums; an image that has underflowed to 0 gives the mean of target^2 and sums of 0.  LYNX_ERR_INVALID before anything is
+ * launched (lynx_last_error starts with "image loss along the trace: ") for a null required argument, a batch beyond 65535, a
+ * misalignment stride that is neither 0 nor 2 n_screens, a target stride that is neither 0 nor at least the cells the
+ * offsets name, a screen outside the trace or without pixels, one of 2^31 - 2048 pixels or more, or an offset that is
+ * negative and not -1.                                                                                                  */
+int lynx_gaussian_images_along_mse(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
+                                   const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
+                                   const void* d_misalignment, int64_t misalignment_stride, const int64_t* target_offsets,
+                                   const void* d_targets, int64_t target_stride, double* d_loss, double* d_sums);
+
+/* ... and its reverse half: d_loss_bar [B][n_screens] (lattice dtype), the cotangents of d_loss, times the five entries
+ * that lynx_gaussian_images_along_backward forms from d_sums [B][n_screens][6] and d_cov_trace, ADDED into d_mu_bar
+ * [B][n_points][7] and d_cov_bar [B][n_points][7][7] at the screens' points (screen after screen per sample: two screens on
+ * one point do not race) -- what lynx_track_moments_along_backward takes on the same stream.  d_grad_misalignment
+ * [B][n_screens][2] or NULL: -d_loss_bar (Sx, Sy), written; a screen without a target has sums of 0 and gets (0, 0).  The
+ * refusals and the message's beginning are those of lynx_gaussian_images_along_mse.                                    */
+int lynx_gaussian_images_along_mse_backward(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points,
+                                            const void* d_cov_trace, int32_t n_screens, const int32_t* screens,
+                                            const double* d_sums, const void* d_loss_bar, void* d_mu_bar, void* d_cov_bar,
+                                            void* d_grad_misalignment);
+
 /* Test hook: the float32 sine / cosine the cavity kick uses on the device (cavity.py:141-161
  * calls cos per particle), scalar (packed = 0) or two-per-lane (packed = 1) code path.        */
 int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t packed, float* d_sin,

@@ -259,6 +259,7 @@ struct lynx_ctx {
     Scratch trace[2];  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
     Scratch trace_plan;  // ... with losses or screens: step codes and screen rows (TraceLosses.plan); lynx_ctx::trace_plan is what was uploaded last
     Scratch image_grad;  // lynx_gaussian_images_along_backward: the workgroups' partial sums [B][chunks][6] float64, screen after screen
+    Scratch image_loss;  // lynx_gaussian_images_along_mse: the workgroups' partial sums [B][chunks][7] float64 of one screen, reused screen after screen
     Scratch units[2 * kTableSlots];  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
     Scratch units_bwd[2];  // ... and of the reverse pass's own table
     Scratch grad[3];   // backward: partials, T_bar, build scratch
@@ -3432,6 +3433,101 @@ int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch,
                                                    d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
                                                    d_grad_misalignment);
   });
+}
+
+// The screens of the two image loss entries, checked alike: every refusal in front of anything else.
+static int image_loss_screens(lynx_ctx* ctx, int32_t n_points, int32_t n_screens, const int32_t* screens) {
+  for (int32_t k = 0; k < n_screens; ++k) {
+    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
+    if (point < 0 || point >= n_points || nx < 1 || ny < 1)
+      return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: a screen's point lies inside the trace, and it has pixels");
+    if ((int64_t)nx * ny > 0x7fffffffLL - kImageGradCells)  // (the kernel counts a screen's cells in 32 bits)
+      return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: a screen has fewer than 2^31 - 2048 pixels");
+  }
+  return LYNX_OK;
+}
+
+int lynx_gaussian_images_along_mse(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
+                                   const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
+                                   const void* d_misalignment, int64_t misalignment_stride, const int64_t* target_offsets,
+                                   const void* d_targets, int64_t target_stride, double* d_loss, double* d_sums) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !target_offsets || !d_targets || !d_loss ||
+      !d_sums || batch <= 0 || batch > 65535 || n_points <= 0 || n_screens <= 0)
+    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: bad argument");
+  if (dtype != LYNX_F32 && dtype != LYNX_F64)
+    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the dtype is float32 or float64");
+  if (misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
+    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the misalignments' sample stride is 0 or 2 * n_screens");
+  if (const int rc = image_loss_screens(ctx, n_points, n_screens, screens)) return rc;
+  int64_t target_cells = 0, slab = 0;  // the cells the offsets name; the largest slab of one screen (screens reuse it in stream order)
+  for (int32_t k = 0; k < n_screens; ++k) {
+    const int64_t cells = (int64_t)screens[3 * k + 1] * screens[3 * k + 2];
+    if (target_offsets[k] == -1) continue;
+    if (target_offsets[k] < 0)
+      return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: a target's offset is -1 (no target) or not negative");
+    target_cells = std::max(target_cells, target_offsets[k] + cells);
+    slab = std::max(slab, batch * ((cells + kImageGradCells - 1) / kImageGradCells) * 7);
+  }
+  if (target_stride != 0 && target_stride < target_cells)
+    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the targets' sample stride is 0 or at least the cells the offsets name");
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_loss, (size_t)batch * n_screens * sizeof(double)},
+                                        {d_sums, (size_t)batch * n_screens * 6 * sizeof(double)}});
+  if (const int rc = ensure_scratch(ctx, ctx->scratch.image_loss, (size_t)slab * sizeof(double))) return rc;
+  // (a screen without a target: loss 0 and sums 0)
+  HIP_TRY(ctx, hipMemsetAsync(d_loss, 0, (size_t)batch * n_screens * sizeof(double), ctx->stream));
+  HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, (size_t)batch * n_screens * 6 * sizeof(double), ctx->stream));
+  double* d_slab = (double*)ctx->scratch.image_loss.buf;
+  int64_t grid = 0;
+  for (int32_t k = 0; k < n_screens; ++k) {
+    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
+    if (target_offsets[k] >= 0) {
+      const int64_t chunks = ((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells;
+      with_dtype(dtype, [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL(k_gaussian_image_along_mse<T>, dim3((unsigned)chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
+                           ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)point,
+                           (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx, (int)ny,
+                           (const T*)d_misalignment + 2 * k, misalignment_stride, (const T*)d_targets + target_offsets[k],
+                           target_stride, d_slab);
+      });
+      HIP_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_gaussian_image_along_mse_finish, dim3((unsigned)batch), dim3(64), 0, ctx->stream,
+                         (const double*)d_slab, (int)chunks, (int)(nx * ny), d_loss + k, d_sums + 6 * k, (int)n_screens);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    grid += (int64_t)nx + ny;
+  }
+  return LYNX_OK;
+}
+
+int lynx_gaussian_images_along_mse_backward(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_cov_trace,
+                                            int32_t n_screens, const int32_t* screens, const double* d_sums,
+                                            const void* d_loss_bar, void* d_mu_bar, void* d_cov_bar, void* d_grad_misalignment) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!d_cov_trace || !screens || !d_sums || !d_loss_bar || !d_mu_bar || !d_cov_bar || batch <= 0 || batch > 65535 ||
+      n_points <= 0 || n_screens <= 0)
+    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: bad argument");
+  if (dtype != LYNX_F32 && dtype != LYNX_F64)
+    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the dtype is float32 or float64");
+  if (const int rc = image_loss_screens(ctx, n_points, n_screens, screens)) return rc;
+  const size_t es = dtype_size(dtype);
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_mu_bar, (size_t)batch * n_points * 7 * es},
+                                        {d_cov_bar, (size_t)batch * n_points * 49 * es},
+                                        {d_grad_misalignment, (size_t)batch * n_screens * 2 * es}});
+  for (int32_t first = 0; first < n_screens; first += kImageLossScreens) {
+    const int count = std::min<int32_t>(kImageLossScreens, n_screens - first);
+    ImageLossScreens rows;
+    for (int q = 0; q < kImageLossScreens; ++q) rows.point[q] = q < count ? screens[3 * (first + q)] : 0;
+    with_dtype(dtype, [&](auto zero) {
+      using T = decltype(zero);
+      hipLaunchKernelGGL(k_gaussian_image_along_mse_apply<T>, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream,
+                         (const T*)d_cov_trace, batch, (int)n_points, rows, (int)first, count, (int)n_screens, d_sums,
+                         (const T*)d_loss_bar, (T*)d_mu_bar, (T*)d_cov_bar, (T*)d_grad_misalignment);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  return LYNX_OK;
 }
 
 // ---- synthetic beams -------------------------------------------------------------------

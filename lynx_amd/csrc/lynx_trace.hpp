@@ -1120,4 +1120,137 @@ __global__ __launch_bounds__(64) void k_gaussian_image_along_bwd_finish(const T*
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// k_gaussian_image_along_mse: the mean squared difference of a screen's image to a target, and the six adjoint sums of that
+// loss, in ONE pass over the target -- neither the image nor its cotangent exists in memory.  Per cell the density I is
+// formed with the very expression of k_gaussian_image_along (the loss is that of the image the forward kernel would have
+// written, bit for bit), r = I - target, w = 2 r / cells in double, and seven float64 sums are kept:
+//   L = sum r^2,  S0, Sx, Sy, Sxx, Sxy, Syy = sum w I {1, ux, uy, ux^2, ux uy, uy^2}   (ux, uy as in k_gaussian_image_along_bwd)
+// The work split, the reduction and the slab are those of k_gaussian_image_along_bwd with seven values for six:
+// slab[b][chunk][7], no atomics.  `target` is this screen's part of sample 0's row; sample b's is target_stride further
+// (0: one target for the whole batch, which then stays in cache while every sample reads it).
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(kImageGradThreads) void k_gaussian_image_along_mse(
+    const T* __restrict__ mu_trace, const T* __restrict__ cov_trace, int P, int point, const T* __restrict__ xs,
+    const T* __restrict__ ys, int nx, int ny, const T* __restrict__ misalignment /* of this screen */,
+    int64_t misalignment_stride, const T* __restrict__ target /* of this screen */, int64_t target_stride,
+    double* __restrict__ slab /* of this screen: [B][chunks][7] */) {
+  __shared__ double s_part[kImageGradThreads / 64][7];
+  const int64_t b = blockIdx.y;
+  const int chunks = gridDim.x, chunk = blockIdx.x, tid = threadIdx.x;
+  const int n = nx * ny;
+  const T* mu = mu_trace + (b * P + point) * 7;
+  const T* cov = cov_trace + (b * P + point) * 49;
+  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
+  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
+  const T det = a * c - bb * bb;
+  const T* t = target + b * target_stride;
+  const double scale = 2.0 / (double)n;
+  double s[7] = {0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < kImageGradCells / kImageGradThreads; ++k) {
+    const int cell = chunk * kImageGradCells + k * kImageGradThreads + tid;
+    if (cell < n) {
+      const int row = cell / ny, j = cell - row * ny, i = nx - 1 - row;
+      const T dx = xs[i] - mx, dy = ys[j] - my;
+      const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
+      const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
+      const T density = (T)exp((double)logp);
+      const double r = (double)density - (double)t[cell];
+      const double wi = scale * r * (double)density;
+      const double ux = (double)((c * dx - bb * dy) / det), uy = (double)((a * dy - bb * dx) / det);
+      const double wx = wi * ux, wy = wi * uy;
+      s[0] += wi;
+      s[1] += wx;
+      s[2] += wy;
+      s[3] += wx * ux;
+      s[4] += wx * uy;
+      s[5] += wy * uy;
+      s[6] += r * r;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 7; ++q) s[q] = image_grad_wave_sum(s[q]);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q) s_part[tid >> 6][q] = s[q];
+  }
+  __syncthreads();
+  if (tid < 7) {
+    double total = s_part[0][tid];
+#pragma unroll
+    for (int v = 1; v < kImageGradThreads / 64; ++v) total += s_part[v][tid];
+    slab[(b * chunks + chunk) * 7 + tid] = total;
+  }
+}
+
+// ... its finishing step, one wave per sample: lane l adds the chunks l, l + 64, ... in that order and the lanes are added
+// across the wave, as in k_gaussian_image_along_bwd_finish; lanes 0 .. 5 write sums[b][screen][6] and lane 6 writes
+// loss[b][screen] = L / cells.
+__global__ __launch_bounds__(64) void k_gaussian_image_along_mse_finish(const double* __restrict__ slab, int chunks, int cells,
+                                                                        double* __restrict__ loss /* of this screen */,
+                                                                        double* __restrict__ sums /* of this screen */,
+                                                                        int n_screens) {
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  double s[7] = {0, 0, 0, 0, 0, 0, 0};
+  for (int chunk = lane; chunk < chunks; chunk += 64) {
+#pragma unroll
+    for (int q = 0; q < 7; ++q) s[q] += slab[(b * chunks + chunk) * 7 + q];
+  }
+#pragma unroll
+  for (int q = 0; q < 7; ++q) s[q] = image_grad_wave_sum(s[q]);
+  if (lane == 0) {
+#pragma unroll
+    for (int q = 0; q < 6; ++q) sums[b * n_screens * 6 + q] = s[q];
+    loss[b * n_screens] = s[6] / (double)cells;
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_gaussian_image_along_mse_apply: the reverse half.  One thread per sample walks the screens in order (two screens never
+// race on one point): the five entries of k_gaussian_image_along_bwd_finish from sums[b][k] and a, b, c, det in float64,
+// scaled by loss_bar[b][k], ADDED into mu_bar, cov_bar at the screen's point; grad_misalignment[b][k] = -loss_bar (Sx, Sy).
+// A screen without a target has sums of 0: it adds 0 and gets (0, 0), by the same arithmetic.  The screens' points come by
+// value, kImageLossScreens of them per launch (screens `first` .. `first + count - 1`); launches follow each other on one
+// stream.
+// ---------------------------------------------------------------------------------------
+constexpr int kImageLossScreens = 64;
+struct ImageLossScreens {
+  int point[kImageLossScreens];
+};
+
+template <typename T>
+__global__ __launch_bounds__(64) void k_gaussian_image_along_mse_apply(const T* __restrict__ cov_trace, int64_t B, int P,
+                                                                       ImageLossScreens screens, int first, int count,
+                                                                       int n_screens, const double* __restrict__ sums,
+                                                                       const T* __restrict__ loss_bar, T* __restrict__ mu_bar,
+                                                                       T* __restrict__ cov_bar,
+                                                                       T* __restrict__ grad_misalignment /* or null */) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  for (int q = 0; q < count; ++q) {
+    const int k = first + q, point = screens.point[q];
+    const double* s = sums + (b * n_screens + k) * 6;
+    const double bar = (double)loss_bar[b * n_screens + k];
+    const T* cov = cov_trace + (b * P + point) * 49;
+    const double a = (double)cov[0], bb = (double)cov[2], c = (double)cov[2 * 7 + 2];
+    const double det = a * c - bb * bb;
+    T* mb = mu_bar + (b * P + point) * 7;
+    T* cb = cov_bar + (b * P + point) * 49;
+    mb[0] += (T)(bar * s[1]);
+    mb[2] += (T)(bar * s[2]);
+    cb[0] += (T)(bar * (0.5 * (s[3] - c / det * s[0])));
+    cb[2 * 7 + 2] += (T)(bar * (0.5 * (s[5] - a / det * s[0])));
+    const T cross = (T)(bar * (0.5 * (s[4] + bb / det * s[0])));
+    cb[2] += cross;
+    cb[2 * 7] += cross;
+    if (grad_misalignment) {
+      grad_misalignment[(b * n_screens + k) * 2] = (T)(-(bar * s[1]));
+      grad_misalignment[(b * n_screens + k) * 2 + 1] = (T)(-(bar * s[2]));
+    }
+  }
+}
+
 }  // namespace lynx

@@ -555,6 +555,13 @@ def _aperture_arguments(owner, program: Program, batch_shape, dtype, rt):
     return A, pairs, _ptr(limits), stride
 
 
+def _pixel_positions(screen, dtype):
+    """xs, ys: where a ParameterBeam's image is evaluated -- the very expressions of `Screen.reading`, on the host alone."""
+    e = screen.extent.astype(dtype)
+    pitch = (screen.pixel_size * screen.binning).astype(dtype)
+    return np.arange(e[0], e[1], pitch[0], dtype=dtype), np.arange(e[2], e[3], pitch[1], dtype=dtype)
+
+
 def _screen_geometry(owner, program: Program, batch_shape, dtype, rt, particles: bool):
     """
     What the device needs to know about the program's active screens, remembered on `owner` until a screen setting or a
@@ -578,10 +585,8 @@ def _screen_geometry(owner, program: Program, batch_shape, dtype, rt, particles:
             nx, ny = len(xe) - 1, len(ye) - 1
             shapes.append((ny, nx))
             grid += [xe, ye]
-        else:  # (the very expressions of `Screen.reading`)
-            e = el.extent.astype(dtype)
-            pitch = (el.pixel_size * el.binning).astype(dtype)
-            xs, ys = np.arange(e[0], e[1], pitch[0], dtype=dtype), np.arange(e[2], e[3], pitch[1], dtype=dtype)
+        else:
+            xs, ys = _pixel_positions(el, dtype)
             nx, ny = len(xs), len(ys)
             shapes.append((nx, ny))
             grid += [xs, ys]
@@ -711,8 +716,9 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
     return trace, rec[..., :, (0, 2)].astype(dtype), device  # (mean x, y of the particles alive at every point)
 
 
-def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt):
-    """The ParameterBeam's trace: (trace, x and y of mu at every point, the device arrays a reverse pass reads)."""
+def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt, make_images=True):
+    """The ParameterBeam's trace: (trace, x and y of mu at every point, the device arrays a reverse pass reads).  Without
+    `make_images` the active screens are points of the trace and nothing else: no image is made or read."""
     late = _late()
     dtype, batch_shape, P = incoming.dtype, incoming.batch_shape, lat.S + 1
     mu_t, cov_t = rt.empty((lat.B, P, 7), dtype), rt.empty((lat.B, P, 7, 7), dtype)
@@ -720,7 +726,7 @@ def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, len
         rt.ctx, lat.handle, _ptr(e_in), _ptr(incoming._mu_d.device(rt)), _ptr(incoming._cov_d.device(rt)),
         _ptr(mu_t), _ptr(cov_t), _ptr(e_trace)))
     images = []
-    if program.screens:  # from the trace arrays where the kernels wrote them, before they are read back
+    if program.screens and make_images:  # from the trace arrays where the kernels wrote them, before they are read back
         shots = _screen_geometry(owner, program, batch_shape, dtype, rt, False)
         density = rt.empty((lat.B, shots["cells"]), dtype)
         rt.check(rt.lib.lynx_gaussian_images_along(
@@ -730,7 +736,7 @@ def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, len
     mu, cov = mu_t.numpy().reshape(*batch_shape, P, 7), cov_t.numpy().reshape(*batch_shape, P, 7, 7)
     energy = e_trace.numpy().reshape(*batch_shape, P)
     trace = late.BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype,
-                                        screens=[step for step, _ in program.screens], screen_images=images)
+                                        screens=[step for step, _ in program.screens], screen_images=images if make_images else None)
     if keep_outgoing:
         out = late.ParameterBeam.__new__(late.ParameterBeam)
         out._init_raw(Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
@@ -750,6 +756,8 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     `losses` (True or "particles"): active apertures are part of the trace (`lynx_track_particles_along_losses`).
     `screens`: active screens are part of the trace and make their images inside it (`lynx_track_particles_along_screens`,
     with the apertures if `losses`; `lynx_gaussian_images_along` on the moment trace of a ParameterBeam).
+    `screens="points"` (internal, a ParameterBeam: what `grad.track_along_vjp(..., image_targets=)` asks for): the active screens
+    are identity steps and points of the trace, `trace.screens` lists them, and no image is made or read.
     `trajectories` (a number K of particles or a 1-D array of particle indices): the trace also holds the coordinates of
     those particles at every point (`lynx_track_particles_along_trajectories`: one more small kernel behind the same
     call's particle kernel); None: the call is the one it was.
@@ -762,6 +770,9 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     program = _trace_plan(owner, leaves, bool(losses), bool(screens))
     if not isinstance(incoming, (late.ParameterBeam, late.ParticleBeam)):
         raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
+    points_only = isinstance(screens, str) and screens == "points"
+    if points_only and not isinstance(incoming, late.ParameterBeam):
+        raise TypeError('track_along: screens="points" is the trace of a ParameterBeam; a ParticleBeam\'s screens make their images')
     chosen = None if trajectories is None else chosen_particles(trajectories, incoming)
     rt = get_runtime()
     cache = owner.__dict__.setdefault("_trace_cache", LatticeCache())
@@ -773,7 +784,7 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
     if isinstance(incoming, late.ParticleBeam):
         trace, centre, device = _trace_particles(*shared, keep_outgoing, losses, rt, chosen)
     else:
-        trace, centre, device = _trace_parameters(*shared, keep_outgoing, rt)
+        trace, centre, device = _trace_parameters(*shared, keep_outgoing, rt, make_images=not points_only)
     trace.total_charge = incoming.total_charge
     if keep_device:
         trace._device = device

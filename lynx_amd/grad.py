@@ -56,7 +56,8 @@ class Gradients:
 
     def __init__(self, program, beam, raw_dev, energy_dev, particles=None, moments=None, chosen=None, screens=None, zeros=()):
         # what a pass may have besides `[B][E][8]` and the energy's, on the device: `particles`; `moments` = (mu, cov); `chosen`;
-        # `screens` = (the trace's active screens, dL/d(misalignment) `[B][screens][2]` or None: no image took a cotangent);
+        # `screens` = (the trace's active screens, dL/d(misalignment) `[B][screens][2]` -- or a list of such arrays, which are
+        # added -- or None: no image took a cotangent);
         # `zeros`: (element, parameter names) whose gradient is an exact zero
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
         self._particles_dev, self._moments, self._chosen_dev = particles, moments, chosen
@@ -126,7 +127,8 @@ class Gradients:
                 shape = np.asarray(el.misalignment).shape
                 if self._screen_shifts_dev is None:
                     return {"misalignment": np.zeros(shape)}
-                shifts = self._screen_shifts_dev.numpy().reshape(*self._batch_shape, len(self._screens), 2)
+                parts = self._screen_shifts_dev if isinstance(self._screen_shifts_dev, list) else [self._screen_shifts_dev]
+                shifts = sum(part.numpy() for part in parts).reshape(*self._batch_shape, len(self._screens), 2)
                 self._cache[id(element)] = {"misalignment": _unbroadcast(np.ascontiguousarray(shifts[..., k, :]), shape)}
                 return self._cache[id(element)]
         raw, total = self._host(), None
@@ -628,6 +630,89 @@ def _trace_mode(segment, beam, trajectories, losses, screens, cavities):
     return mode, program, leaves, chosen, cavity
 
 
+def _screen_of(key, program, leaves) -> int:
+    """The ordinal among the trace's active screens of what `key` means: the `Screen` itself, or whatever `trace.image_at`
+    takes (a name, the index of the point it observes) -- with that method's errors."""
+    from .trace import screen_ordinal
+
+    points = [step for step, _ in program.screens]
+    if getattr(key, "_swallows_beam", False):  # the Screen element itself
+        found = [k for k, (_, el) in enumerate(program.screens) if el is key]
+        if not found:
+            raise KeyError(f"{key!r} is not an active screen of this trace (screens at {points})")
+        return found[0]
+    return screen_ordinal([el.name for el in leaves], points, key)
+
+
+class _TargetLayout:
+    """Where the targets lie in what is uploaded: `offsets` per active screen (-1: no target), the `cells` of one row, the
+    scalars between two samples' rows (`stride`, 0: one row shared by the batch) and the host array itself."""
+
+    def __init__(self, offsets, cells, stride, host):
+        self.offsets, self.cells, self.stride, self.host = offsets, cells, stride, host
+
+
+class ImageTargets:
+    """
+    Target images of active screens, `{screen: target}` -- a key is whatever `trace.image_at` takes or the `Screen` itself, a
+    target is `(nx, ny)` or `(*batch, nx, ny)` of that screen's image.  Given to `track_along_vjp(..., image_targets=)` they
+    are uploaded ONCE, in the layout `lynx_gaussian_images_along_mse` reads, and stay on the device: the same object serves
+    every pass of a tuning loop.  All targets `(nx, ny)`: one row shared by the batch.
+    """
+
+    def __init__(self, targets: dict):
+        if not isinstance(targets, dict):
+            raise TypeError(f"ImageTargets: a dict {{screen: target image}}, not {type(targets)}")
+        self._given = [(key, np.array(target)) for key, target in targets.items()]  # (copies: the upload is made once)
+        self._remembered = None  # (what the layout depends on, the layout, the device array or None)
+
+    def _layout(self, program, leaves, beam) -> _TargetLayout:
+        """The targets against one trace's screens and one beam, refused by value; nothing touches the GPU."""
+        dtype, batch_shape = np.dtype(beam.dtype), tuple(beam.batch_shape)
+        shapes = [tuple(len(v) for v in engine._pixel_positions(el, dtype)) for _, el in program.screens]
+        key = (tuple(id(el) for _, el in program.screens), tuple(shapes), batch_shape, dtype.str)
+        if self._remembered is not None and self._remembered[0] == key:
+            return self._remembered[1]
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        named = {}
+        for given, target in self._given:
+            k = _screen_of(given, program, leaves)
+            name, shape = program.screens[k][1].name, shapes[k]
+            if k in named:
+                raise ValueError(f"track_along_vjp: screen {name!r} is given two target images")
+            fits = target.shape == shape
+            if not fits and target.ndim > 2:
+                try:
+                    fits = np.broadcast_shapes(target.shape, (*batch_shape, *shape)) == (*batch_shape, *shape)
+                except ValueError:
+                    fits = False
+            if not fits:
+                raise ValueError(f"track_along_vjp: the target image of screen {name!r} has shape {target.shape}, which is neither "
+                                 f"its image's {shape} (nx, ny) nor broadcasts to {(*batch_shape, *shape)} (*batch, nx, ny)")
+            named[k] = target
+        shared = all(target.ndim == 2 for target in named.values())
+        offsets, first = [], 0
+        for k, shape in enumerate(shapes):
+            offsets.append(first if k in named else -1)
+            first += shape[0] * shape[1] if k in named else 0
+        host = np.zeros((1 if shared else B, max(first, 1)), dtype=dtype)
+        for k, target in named.items():
+            cells = shapes[k][0] * shapes[k][1]
+            rows = target.reshape(1, cells) if shared else np.broadcast_to(target, (*batch_shape, *shapes[k])).reshape(B, cells)
+            host[:, offsets[k]:offsets[k] + cells] = rows
+        layout = _TargetLayout(offsets, first, 0 if shared else max(first, 1), host)
+        self._remembered = (key, layout, None)
+        return layout
+
+    def _device(self, rt, layout):
+        key, remembered, dev = self._remembered
+        assert remembered is layout
+        if dev is None:
+            dev = rt.to_device(layout.host)
+            self._remembered = (key, layout, dev)
+        return dev
+
+
 class TrackAlongVJP:
     """
     Vector-Jacobian product of `Segment.track_along`: gradients of any function of the beam moments and the energy at
@@ -647,16 +732,99 @@ class TrackAlongVJP:
     point given to every particle at that point; at most 64 leaf elements, `wrt_particles=True` in the call.
     """
 
-    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False, cavities=False):
+    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False, cavities=False, image_targets=None):
+        targets = image_targets is not None
+        if targets and not isinstance(image_targets, (dict, ImageTargets)):
+            raise TypeError(f"track_along_vjp: image_targets is a dict {{screen: target image}} or an ImageTargets, not {type(image_targets)}")
         # the mode, decided once: "moments" (a ParameterBeam's sweep), "particles", "trajectories", "survivors" or "kicks"
-        self.mode, self.program, self.leaves, self.chosen, self._cavity = _trace_mode(segment, beam, trajectories, losses, screens, cavities)
+        # (image targets need the screens in the trace's plan, and a ParticleBeam is refused as `screens=True` refuses it)
+        self.mode, self.program, self.leaves, self.chosen, self._cavity = _trace_mode(
+            segment, beam, trajectories, losses, True if targets and isinstance(screens, (bool, np.bool_)) else screens, cavities)
         self.segment, self.beam = segment, beam
         self._screens = bool(screens)  # (of "moments": the forward trace makes images, the call takes their cotangents)
-        # (a keyword is given only where it says something; apertures are identity steps of a ParameterBeam's trace)
-        plain = {**({"losses": True} if losses and self.mode == "moments" else {}), **({"screens": True} if screens else {})}
+        self._targets = self._image_loss = None
+        if targets:  # every refusal by value, before anything touches the GPU
+            self._targets = image_targets if isinstance(image_targets, ImageTargets) else ImageTargets(image_targets)
+            layout = self._targets._layout(self.program, self.leaves, beam)
+        # (a keyword is given only where it says something; apertures are identity steps of a ParameterBeam's trace; with
+        # image targets alone the screens are points of the trace and no image is made)
+        plain = {**({"losses": True} if losses and self.mode == "moments" else {}),
+                 **({"screens": True} if screens else {"screens": "points"} if targets else {})}
         options = {"survivors": {"losses": "particles"}, "trajectories": {"trajectories": self.chosen}}.get(self.mode, plain)
         self.trace = engine.track_along(segment, self.leaves, beam, keep_outgoing=True, keep_device=True, **options)
         self._set_records = self._survivor_set_records() if self.mode == "survivors" else None
+        if targets:
+            self._image_loss = self._evaluate_image_loss(layout)
+
+    def _evaluate_image_loss(self, layout):
+        """
+        lynx_gaussian_images_along_mse right behind the trace, on its stream: the loss [B][K] and the six adjoint sums
+        [B][K][6] of every screen with a target, float64, both kept on the device -> (loss, sums, which screens are named).
+        """
+        if not self.program.screens:  # (no active screen, and so no target: nothing to evaluate)
+            return None, None, []
+        rt = get_runtime()
+        beam, states = self.beam, self.trace._device
+        B, P, K = int(np.prod(beam.batch_shape, dtype=np.int64)), self.trace.num_points, len(self.program.screens)
+        shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+        targets_dev = self._targets._device(rt, layout)
+        loss, sums = rt.empty((B, K), np.float64), rt.empty((B, K, 6), np.float64)
+        rt.check(rt.lib.lynx_gaussian_images_along_mse(
+            rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), K, shots["rows"], _p(shots["grid"]),
+            _p(shots["misalignment"]), shots["stride"], (C.c_int64 * K)(*layout.offsets), _p(targets_dev), layout.stride,
+            _p(loss), _p(sums)))
+        return loss, sums, [offset >= 0 for offset in layout.offsets]
+
+    @property
+    def image_loss(self) -> dict:
+        """{screen name: (*batch,) float64}: the mean squared difference of every named screen's image to its target."""
+        if self._image_loss is None:
+            raise ValueError("track_along_vjp: image_loss needs target images -- pass image_targets= to track_along_vjp")
+        loss, _, named = self._image_loss
+        if not any(named):
+            return {}
+        host = loss.numpy().reshape(*self.beam.batch_shape, len(named))
+        return {el.name: np.ascontiguousarray(host[..., k]) for k, (_, el) in enumerate(self.program.screens) if named[k]}
+
+    def image_loss_of(self, screen) -> np.ndarray:
+        """`image_loss` of one screen: by whatever `trace.image_at` takes, or by the `Screen` itself."""
+        if self._image_loss is None:
+            raise ValueError("track_along_vjp: image_loss_of needs target images -- pass image_targets= to track_along_vjp")
+        loss, _, named = self._image_loss
+        k = _screen_of(screen, self.program, self.leaves)
+        if not named[k]:
+            raise KeyError(f"screen {self.program.screens[k][1].name!r} has no target image in this call's image_targets")
+        return np.ascontiguousarray(loss.numpy().reshape(*self.beam.batch_shape, len(named))[..., k])
+
+    def _image_loss_cotangents(self, image_loss_bar):
+        """`image_loss_bar` as (B, K) of the beam's dtype, zeros for a screen without a target; refused by value."""
+        if self._image_loss is None:
+            raise ValueError("track_along_vjp: image_loss_bar needs the image loss of the forward pass -- pass image_targets= "
+                             "to track_along_vjp")
+        named, batch_shape = self._image_loss[2], self.beam.batch_shape
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        bars = np.zeros((B, len(named)))
+
+        def over_batch(bar, name):
+            w = np.asarray(bar, dtype=np.float64)
+            try:
+                return np.broadcast_to(w, batch_shape).reshape(B)
+            except ValueError:
+                raise ValueError(f"track_along_vjp: image_loss_bar of screen {name!r} has shape {w.shape}, which does not "
+                                 f"broadcast to the batch {tuple(batch_shape)}") from None
+
+        if isinstance(image_loss_bar, dict):
+            for key, bar in image_loss_bar.items():
+                k = _screen_of(key, self.program, self.leaves)
+                name = self.program.screens[k][1].name
+                if not named[k]:
+                    raise KeyError(f"screen {name!r} has no target image in this call's image_targets")
+                bars[:, k] += over_batch(bar, name)
+        else:
+            for k, (_, el) in enumerate(self.program.screens):
+                if named[k]:
+                    bars[:, k] = over_batch(image_loss_bar, el.name)
+        return bars.astype(self.beam.dtype)
 
     def _survivor_set_records(self):
         """
@@ -755,14 +923,7 @@ class TrackAlongVJP:
         trace, elements = self.trace, [el for _, el in self.program.screens]
         named = []  # (screen, cotangent broadcast to its image), checked before anything is allocated
         for key, bar in screen_images_bar.items():
-            if getattr(key, "_swallows_beam", False):  # the Screen element itself
-                found = [k for k, el in enumerate(elements) if el is key]
-                if not found:
-                    raise KeyError(f"{key!r} is not an active screen of this trace (screens at {list(trace.screens)})")
-                k = found[0]
-            else:
-                image = trace.image_at(key)  # (KeyError for anything but an active screen of the trace)
-                k = next(n for n, own in enumerate(trace.screen_images) if own is image)
+            k = _screen_of(key, self.program, self.leaves)  # (KeyError for anything but an active screen of the trace)
             shape = trace.screen_images[k].shape
             w = np.asarray(bar)
             try:
@@ -783,7 +944,7 @@ class TrackAlongVJP:
         return flat
 
     def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, trajectories_bar=None,
-                 screen_images_bar: dict | None = None, wrt_particles: bool = False, **properties) -> Gradients:
+                 screen_images_bar: dict | None = None, wrt_particles: bool = False, image_loss_bar=None, **properties) -> Gradients:
         """
         `mu_bar` (*batch, P, 6|7), `cov_bar` (*batch, P, 6|7, 6|7) entry by entry, `energy_bar` (*batch, P): cotangents at
         every point; `properties`: cotangents (*batch, P) of any moment property of the trace and of `energy`;
@@ -795,6 +956,9 @@ class TrackAlongVJP:
         a key whatever `trace.image_at` takes or the `Screen` itself, a value broadcastable to that image (*batch, nx, ny);
         lynx_gaussian_images_along_backward reduces them on the device into the mu and cov cotangents at the screens' points,
         where the sweep picks them up, and `g[screen]["misalignment"]` is the gradient w.r.t. the screen's misalignment.
+        `image_loss_bar` (`image_targets=` of `track_along_vjp`): cotangents of `image_loss` -- a scalar or (*batch,) for every
+        screen with a target, or `{screen: bar}`; lynx_gaussian_images_along_mse_backward scales the sums the forward pass left
+        on the device and adds them into the mu and cov cotangents at the screens' points, `g[screen]["misalignment"]` as above.
         `wrt_particles=True` (`cavities=True` of `track_along_vjp`, a ParticleBeam): `Gradients.particles` (*batch, N, 7), the
         gradient w.r.t. every incoming particle, device-resident.
         """
@@ -802,6 +966,9 @@ class TrackAlongVJP:
             raise ValueError("track_along_vjp: wrt_particles=True needs the pass over the particles -- a ParticleBeam and "
                              "cavities=True of track_along_vjp (without a cavity g.mu and g.cov say the same)")
         wi = None if screen_images_bar is None else self._image_cotangents(screen_images_bar)
+        lb = None if image_loss_bar is None else self._image_loss_cotangents(image_loss_bar)
+        if lb is not None and not any(self._image_loss[2]):  # (no screen has a target: nothing to launch)
+            lb = None
         wb = None  # (a trace with trajectories and no cotangent on them: zeros)
         if trajectories_bar is not None or self.chosen is not None:
             wb = self._trajectory_cotangents(np.zeros(7) if trajectories_bar is None else trajectories_bar)
@@ -814,15 +981,15 @@ class TrackAlongVJP:
         # (an upload is named until its call has been enqueued, so that it stays allocated; no energy cotangent: no upload)
         eb_dev = rt.to_device(eb.astype(self.beam.dtype)) if np.any(eb) else None
         launch = getattr(self, "_launch_" + self.mode)  # (_launch_moments, _particles, _trajectories, _survivors, _kicks)
-        results = launch(rt, sweep, mb, cb, eb_dev, wi=wi, wb=wb, with_moments=with_moments, wrt_particles=wrt_particles)
+        results = launch(rt, sweep, mb, cb, eb_dev, wi=wi, lb=lb, wb=wb, with_moments=with_moments, wrt_particles=wrt_particles)
         return Gradients(self.program, self.beam, sweep.g_par, sweep.g_en, **results)
 
     # one method per mode, called alike (each names what it uses): the library call or calls -> `Gradients`' optional results
-    def _launch_moments(self, rt, sweep, mb, cb, eb_dev, wi, **_):
+    def _launch_moments(self, rt, sweep, mb, cb, eb_dev, wi, lb, **_):
         beam, states = self.beam, self.trace._device
         B, P = mb.shape[:2]
         mb_dev, cb_dev = rt.to_device(mb.astype(beam.dtype)), rt.to_device(cb.astype(beam.dtype))
-        shifts = None
+        shifts = loss_shifts = None
         if wi is not None:  # the images' cotangents go into mb_dev, cb_dev at the screens' points, on the same stream
             shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
             wi_dev = rt.to_device(np.ascontiguousarray(wi, dtype=beam.dtype))
@@ -830,10 +997,22 @@ class TrackAlongVJP:
             rt.check(rt.lib.lynx_gaussian_images_along_backward(
                 rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), shots["count"], shots["rows"],
                 _p(shots["grid"]), _p(shots["misalignment"]), shots["stride"], _p(wi_dev), _p(mb_dev), _p(cb_dev), _p(shifts)))
+        if lb is not None:  # ... and so do the image losses' cotangents times the sums of the forward pass
+            shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+            lb_dev = rt.to_device(np.ascontiguousarray(lb, dtype=beam.dtype))
+            loss_shifts = rt.empty((B, shots["count"], 2), beam.dtype)
+            rt.check(rt.lib.lynx_gaussian_images_along_mse_backward(
+                rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["cov"]), shots["count"], shots["rows"], _p(self._image_loss[1]),
+                _p(lb_dev), _p(mb_dev), _p(cb_dev), _p(loss_shifts)))
         rt.check(rt.lib.lynx_track_moments_along_backward(
             rt.ctx, sweep.lat.handle, _p(sweep.e_in), _p(states["mu"]), _p(states["cov"]), _p(mb_dev), _p(cb_dev), _p(eb_dev),
             _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
-        return dict(moments=(sweep.g_mu, sweep.g_cov), screens=([el for _, el in self.program.screens], shifts) if self._screens else None)
+        if shifts is not None and loss_shifts is not None:  # (both in one call: `Gradients` adds the two)
+            shifts = [shifts, loss_shifts]
+        elif loss_shifts is not None:
+            shifts = loss_shifts
+        with_screens = self._screens or self._targets is not None
+        return dict(moments=(sweep.g_mu, sweep.g_cov), screens=([el for _, el in self.program.screens], shifts) if with_screens else None)
 
     def _launch_particles(self, rt, sweep, mb, cb, eb_dev, **_):
         rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
@@ -876,7 +1055,7 @@ class TrackAlongVJP:
         return dict(moments=Gradients.NO_INCOMING_MOMENTS, zeros=[(el, ("x_max", "y_max")) for _, el, _ in self.program.apertures])
 
 
-def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False, cavities=False):
+def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False, cavities=False, image_targets=None):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
     callable vector-Jacobian product of the moments and energies at every point:
@@ -930,6 +1109,24 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
     image has underflowed to 0 gives gradient 0.  A ParticleBeam is a TypeError (its image is a histogram of counts);
     `losses=True` may be combined (apertures pass a ParameterBeam unchanged); at most 65535 samples.
 
+    `image_targets=` (a ParameterBeam): the loss every user of the path above writes, the mean squared difference of a screen's
+    image to a target image, evaluated on the device -- neither the image nor its cotangent is made, read back or uploaded:
+
+        targets = lynx_amd.grad.ImageTargets({"SCREEN": target})   # uploaded once, reusable over a loop (or pass the dict)
+        vjp = lynx_amd.grad.track_along_vjp(segment, parameter_beam, image_targets=targets)
+        vjp.image_loss                                            # {name: (*batch,) float64}; vjp.image_loss_of("SCREEN")
+        g = vjp(image_loss_bar=1.0 / peak**2, beta_x=...)         # a scalar or (*batch,) for every named screen, or {screen: bar}
+        g[segment.Q1]["k1"], g.mu, g.cov, g[segment.SCREEN]["misalignment"]
+
+    A key is whatever `trace.image_at` takes or the `Screen` itself, a target is (nx, ny) -- then one target serves the whole
+    batch -- or (*batch, nx, ny) of that screen's image.  The forward pass is the moment trace with the active screens as identity
+    steps (`vjp.trace.screens` lists them, `screen_images` is empty, `image_at` raises, the screens' `reading` is left alone);
+    lynx_gaussian_images_along_mse forms the density per pixel with the forward kernel's expression, so the loss is that of the
+    image `screens=True` would have shown, bit for bit, and keeps the loss and six adjoint sums per sample and screen on the
+    device; the call scales them by `image_loss_bar` (lynx_gaussian_images_along_mse_backward) in front of the sweep.  A screen
+    without a target gets misalignment gradient 0.  `screens=True` may be given as well: the images are made as above, and
+    `screen_images_bar` and `image_loss_bar` may both be used in one call.  Refusals are those of `screens=True`.
+
     `cavities=True` (a ParticleBeam): active cavities are no obstacle to the moment cotangents.  Behind a cavity's kick the
     moments are not a function of the moments in front of it, so the reverse call takes a second pass over the particles
     (lynx_track_particles_along_backward_cavities: the sweep of `track_vjp`, which parks every 4th state and walks back
@@ -945,7 +1142,7 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
     `losses=True`.  A lattice without a cavity is accepted (the same gradients by another way), and with a ParameterBeam
     `cavities=True` is the plain call.
     """
-    return TrackAlongVJP(segment, beam, trajectories, losses, screens, cavities)
+    return TrackAlongVJP(segment, beam, trajectories, losses, screens, cavities, image_targets)
 
 
 def track_vjp(segment, beam):

@@ -41,6 +41,25 @@ def _cumulative_s(lengths, batch_shape, dtype) -> np.ndarray:
     return s
 
 
+def screen_ordinal(names, screens, name_or_index) -> int:
+    """
+    The ordinal in `screens` (the points the active screens observe) of the screen that a name -- the element so named -- or
+    a point index (negative from the end; there are len(names) + 1 points) means; KeyError if no active screen stands there.
+    """
+    if isinstance(name_or_index, str):
+        if name_or_index not in names:
+            raise KeyError(f"no element named {name_or_index!r} in this trace")
+        k = names.index(name_or_index)
+    else:
+        k, points = int(name_or_index), len(names) + 1
+        if not -points <= k < points:
+            raise IndexError(f"point {k} of a trace of {points}")
+        k %= points
+    if k not in screens:
+        raise KeyError(f"{name_or_index!r}: no active screen of this trace observes point {k} (screens at {list(screens)})")
+    return list(screens).index(k)
+
+
 class BeamTrace(Beam):
     """
     :ivar s: position of every point, (P, *batch) -- cumulative `length`, per sample because lengths are batched; a
@@ -71,11 +90,13 @@ class BeamTrace(Beam):
     trajectory_lost_in = None
     screens = ()
     screen_images = ()
+    _images_made = True
 
     def _set_screens(self, screens, screen_images):
         self.screens = [int(k) for k in screens]
-        self.screen_images = list(screen_images)
-        assert len(self.screens) == len(self.screen_images), (self.screens, len(self.screen_images))
+        self._images_made = screen_images is not None  # (None: the screens are points of the trace, their images were not made)
+        self.screen_images = list(screen_images) if self._images_made else []
+        assert not self._images_made or len(self.screens) == len(self.screen_images), (self.screens, len(self.screen_images))
         assert all(0 <= k < self.num_points - 1 for k in self.screens), self.screens  # (a screen is an element: never the last point)
 
     def _set_common(self, energy, lengths, names, dtype, batch_shape):
@@ -167,15 +188,15 @@ class BeamTrace(Beam):
         `index_of` takes it, negative from the end).  A name resolves to the element so named and an index to a point;
         KeyError if no active screen of this trace stands there.
         """
-        if isinstance(name_or_index, str):
-            if name_or_index not in self.names:
-                raise KeyError(f"no element named {name_or_index!r} in this trace")
-            k = self.names.index(name_or_index)
-        else:
-            k = self.index_of(name_or_index)
-        if k not in self.screens:
-            raise KeyError(f"{name_or_index!r}: no active screen of this trace observes point {k} (screens at {list(self.screens)})")
-        return self.screen_images[list(self.screens).index(k)]
+        n = self.screen_at(name_or_index)
+        if not self._images_made:
+            raise KeyError(f"{name_or_index!r}: the images of this trace were not made (its screens are points of the trace alone); "
+                           "pass screens=True to have them made")
+        return self.screen_images[n]
+
+    def screen_at(self, name_or_index) -> int:
+        """Which of `screens` (its ordinal) a name or a point index means, by the rules and with the errors of `image_at`."""
+        return screen_ordinal(self.names, self.screens, name_or_index)
 
     def at(self, name_or_index) -> dict:
         """Everything known about one point: `s`, `name` (None for point 0), `energy`, `mu`, `cov` and every moment --
