@@ -205,6 +205,9 @@ int lynx_build_compose(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
 /* Segment.track on a ParticleBeam (reference: segment.py:340-356 -> element.py:83-92
  * `particles @ tm^T`, cavity.py:141-161,219-226).
  *   d_p_in / d_p_out [B][N][7]  (may alias; d_p_in [N][7] with LYNX_TRACK_SHARED_INPUT)
+ *   d_energy_in      [B]; may be NULL for a program without steps, unless d_energy_out is given
+ *   d_energy_out     [B] or NULL: the beam energy behind the last step (may be d_energy_in); a program without steps
+ *                    copies d_energy_in
  *   d_moments_out    [B][36] float64 or NULL (needs LYNX_TRACK_MOMENTS)
  *   d_observations   [B][n_observers][2] float64 or NULL: mean x and mean y of the beam entering
  *                    each LYNX_STEP_FLAG_OBSERVE step, in lattice order (BPM.reading, bpm.py:48-54);

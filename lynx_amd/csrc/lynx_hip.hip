@@ -1962,15 +1962,21 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
   p.a.merged_pairs = 0;
   int rc;
   // what this call writes for the caller may hold the incoming energy of the table kept for a reverse pass
-  // (kFeedsNoBuild: a call with steps says what it publishes behind its launch, BuildOrder::streamed)
+  // (kFeedsNoBuild: a call with steps says what it publishes behind its launch, BuildOrder::streamed; the outgoing energy
+  // of a program without steps is a copy on the main stream, below, that a later build may read: kFeedsBuild)
   caller_blocks_written(ctx, kFeedsNoBuild, {{d_p_out, (size_t)B * N * 7 * sizeof(T)},
-                                             {d_energy_out, (size_t)B * sizeof(T)},
                                              {d_moments_out, (size_t)B * LYNX_MOMENT_STRIDE * sizeof(double)},
                                              {d_observations, lat ? (size_t)B * lat->n_observers * 2 * sizeof(double) : 0}});
+  caller_blocks_written(ctx, S == 0 ? kFeedsBuild : kFeedsNoBuild, {{d_energy_out, (size_t)B * sizeof(T)}});
   // The build is always a launch of its own (in the streaming kernel's prologue it measured the same twice: NOTES.md,
   // "Tried and dropped in round 4"), so a call with steps always takes a slot of the ring and leaves a FwdTable.
   TrackTable t;
   if (S > 0 && (rc = track_table<T>(ctx, lat, B, N, S, d_energy_in, d_energy_out, flags, p, &t))) return rc;
+  // A program without steps has no table for the kernel to take the outgoing energy from: the beam leaves with the
+  // energy it came in with, copied here on the main stream.
+  if (S == 0 && d_energy_out && d_energy_out != d_energy_in) {
+    HIP_TRY(ctx, hipMemcpyAsync(d_energy_out, d_energy_in, (size_t)B * sizeof(T), hipMemcpyDefault, ctx->stream));
+  }
   if ((int64_t)B * p.a.chunks > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, "grid too large");
   // Workgroup records: a ring of buffers, so that the reduction of call n (side stream) can still read its records
   // while the streaming kernels of calls n+1.. write theirs.  The host makes sure the slot's previous reduction is done.
@@ -2044,7 +2050,7 @@ int lynx_track_particles(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, 
                          int flags, double* d_observations) {
   if (!ctx || !lat || !d_p_in) return fail(ctx, LYNX_ERR_INVALID, "null argument");
   if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "n_particles must be > 0");
-  if (lat->n_steps > 0 && !d_energy_in) return fail(ctx, LYNX_ERR_INVALID, "energy_in required");
+  if ((lat->n_steps > 0 || d_energy_out) && !d_energy_in) return fail(ctx, LYNX_ERR_INVALID, "energy_in required");
   if ((flags & (LYNX_TRACK_MOMENTS | LYNX_TRACK_COVARIANCE)) && !d_moments_out)
     return fail(ctx, LYNX_ERR_INVALID, "LYNX_TRACK_MOMENTS / LYNX_TRACK_COVARIANCE need d_moments_out");
   if ((flags & LYNX_TRACK_SHARED_INPUT) && d_p_in == d_p_out)

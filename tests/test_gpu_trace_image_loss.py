@@ -34,8 +34,9 @@ from oracle import lynx_oracle as o
 
 from . import image_loss_reference as il
 from . import screen_grad_reference as ref
+from .entry_calls import ints
 from .helpers import make_lattice
-from .test_gpu_entry_refusals import INVALID, NX, NY, B, P, env, ints  # noqa: F401 (`env` is a fixture)
+from .test_gpu_entry_refusals import INVALID, NX, NY, B, P, env  # noqa: F401 (`env` is a fixture)
 from .test_gpu_screen import TOL_IMAGE
 from .test_gpu_trace_grad import _chain
 from .test_gpu_trace_screens import MIS_B, SCREEN_A, SCREEN_B, make_screen, mis_a, two_screen_lattice
