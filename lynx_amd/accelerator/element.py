@@ -66,7 +66,7 @@ class Element:
     _row: tuple = ()
     _settings: tuple = ()
     _kept_on_broadcast: tuple = ()  # parameters `broadcast` passes on unrepeated
-    _transient: tuple = ("_lattice_cache", "_plan")  # never shared between an element and its copies
+    _transient: tuple = engine.OWNER_SLOTS  # never shared between an element and its copies
     _host_barrier = False
     _skippable: Optional[bool] = None
     _version = 0

@@ -56,7 +56,6 @@ def _late():
 
 
 @dataclass
-
 class Program:
     """A maximal stretch of the lattice one kernel launch can run: runs + active cavities."""
 
@@ -143,6 +142,44 @@ def partition(elements, fuse_observers: bool = False) -> list:
     return out
 
 
+# -------------------------------------------------------------------------------------------
+# what an owner remembers
+# -------------------------------------------------------------------------------------------
+
+# Everything the engine keeps on an owner (a Segment, or an Element tracked on its own) between two calls.  The first four
+# are memos of `_remembered` ({mode: (token, value)}), the last two the packed programs of `track` / `transfer_map` and of
+# `track_along`.  `Element._transient` is made from this tuple: a twin (`broadcast`) takes none of them along.
+OWNER_SLOTS = ("_plan", "_trace_plan", "_trace_limits", "_trace_screens", "_lattice_cache", "_trace_cache")
+
+
+def _held(owner, slot: str, make):
+    # through `__dict__`, never `setattr`: `Segment.__setattr__` bumps EPOCH and STRUCTURE, the very counters that say
+    # whether what is remembered here still holds
+    held = owner.__dict__.get(slot)
+    if held is None:
+        held = owner.__dict__[slot] = make()
+    return held
+
+
+def lattice_cache(owner) -> "LatticeCache":
+    """The packed programs of `track` and `transfer_map` on this owner."""
+    return _held(owner, "_lattice_cache", LatticeCache)
+
+
+def trace_cache(owner) -> "LatticeCache":
+    """The packed every-element-its-own-step programs of `track_along` on this owner."""
+    return _held(owner, "_trace_cache", LatticeCache)
+
+
+def _remembered(owner, slot: str, mode, token, make):
+    """`make()`, remembered in `slot` of `owner` per `mode` for as long as `token` compares equal."""
+    memos = _held(owner, slot, dict)
+    memo = memos.get(mode)
+    if memo is None or memo[0] != token:
+        memo = memos[mode] = (token, make())
+    return memo[1]
+
+
 def plan(owner, elements, raw: bool, fuse_observers: bool = False) -> list:
     """
     `partition(elements)` remembered on `owner` for as long as no attribute that can change the
@@ -159,19 +196,17 @@ def plan(owner, elements, raw: bool, fuse_observers: bool = False) -> list:
             ids = (ids, tuple(identities(el.elements) for el in items if isinstance(el, Segment)))
         return ids
 
+    def make():
+        items = partition(elements, fuse_observers)
+        for item in items:
+            if isinstance(item, Program):
+                item.raw = raw
+        return items
+
     # a Segment's own list says when it is changed in place (ElementList bumps STRUCTURE, and so do the lists of nested
     # segments): the list object itself stands for its contents; any other sequence is compared element by element
     ids = id(elements) if type(elements) is late.ElementList else identities(elements)
-    token = (STRUCTURE[0], raw, ids)
-    remembered = owner.__dict__.setdefault("_plan", {}).get(fuse_observers)
-    if remembered is not None and remembered[0] == token:
-        return remembered[1]
-    items = partition(elements, fuse_observers)
-    for item in items:
-        if isinstance(item, Program):
-            item.raw = raw
-    owner.__dict__["_plan"][fuse_observers] = (token, items)
-    return items
+    return _remembered(owner, "_plan", fuse_observers, (STRUCTURE[0], raw, ids), make)
 
 
 # -------------------------------------------------------------------------------------------
@@ -375,9 +410,25 @@ def _ptr(x):
     return None if x is None else C.c_void_p(x.ptr)
 
 
+def _outgoing_particles(incoming, particles: Dual, energy: Dual | None, moments: Dual | None):
+    """
+    The ParticleBeam that leaves a pass `incoming` entered.  `energy` None: no cavity was passed, the beam goes on with
+    the incoming beam's own energy object (and whatever device copies it holds).  The charges go on as they are, except
+    those of a lazily broadcast beam, which are stored once for all samples: the outgoing beam has particles per sample,
+    so it is handed the charges per sample too.
+    """
+    charges = incoming._charges
+    if charges is not None and incoming.is_shared:
+        charges = np.ascontiguousarray(incoming.particle_charges)
+    # (`_from_raw` spelled out here and in `run_program_parameters`, the two beams a `track` call makes: the classmethod's
+    # argument forwarding costs 0.6 us of a call that is bound by the host, see `_late`)
+    out = object.__new__(_late().ParticleBeam)
+    out._init_raw(particles, incoming._energy if energy is None else energy, charges, incoming.dtype, moments)
+    return out
+
+
 def run_program_particles(cache, program: Program, beam, moments: bool | None = None):
     """One pass of the streaming kernel: ParticleBeam -> ParticleBeam (`lynx_track_particles_new`)."""
-    ParticleBeam = _late().ParticleBeam
     rt = get_runtime()
     dtype = beam.dtype
     batch_shape = beam.batch_shape
@@ -404,18 +455,12 @@ def run_program_particles(cache, program: Program, beam, moments: bool | None = 
         obs = adopt(rt, blocks[3], (lat.B, len(program.observers), 2), _F64)
         for k, (_, element) in enumerate(program.observers):
             element._reading_from(obs, k, batch_shape, dtype)  # read back only if somebody looks at it
-    out = ParticleBeam.__new__(ParticleBeam)
-    charges = beam._charges
-    if charges is not None and beam.is_shared:
-        charges = np.ascontiguousarray(beam.particle_charges)
-    out._init_raw(Dual(dev=p_out), Dual(dev=e_out) if e_out is not None else beam._energy,
-                  charges, dtype, moments=Dual(dev=mom) if mom is not None else None)
-    return out
+    return _outgoing_particles(beam, Dual(dev=p_out), None if e_out is None else Dual(dev=e_out),
+                               None if mom is None else Dual(dev=mom))
 
 
 def run_program_parameters(cache, program: Program, beam):
     """ParameterBeam -> ParameterBeam (lynx_track_moments)."""
-    ParameterBeam = _late().ParameterBeam
     rt = get_runtime()
     dtype = beam.dtype
     batch_shape = beam.batch_shape
@@ -428,9 +473,8 @@ def run_program_parameters(cache, program: Program, beam):
     e_out = rt.empty(batch_shape, dtype) if lat.has_cavity_step else None
     rt.check(rt.lib.lynx_track_moments(rt.ctx, lat.handle, _ptr(e_in), _ptr(mu_in), _ptr(cov_in),
                                        _ptr(mu_out), _ptr(cov_out), _ptr(e_out)))
-    out = ParameterBeam.__new__(ParameterBeam)
-    out._init_raw(Dual(dev=mu_out), Dual(dev=cov_out),
-                  Dual(dev=e_out) if e_out is not None else beam._energy, beam.total_charge, dtype)
+    out = object.__new__(_late().ParameterBeam)  # (`_from_raw` spelled out, as in `_outgoing_particles`)
+    out._init_raw(Dual(dev=mu_out), Dual(dev=cov_out), Dual(dev=e_out) if e_out is not None else beam._energy, beam.total_charge, dtype)
     return out
 
 
@@ -445,7 +489,7 @@ def track(owner, elements, incoming, raw: bool = False):
         return incoming
     if not isinstance(incoming, (ParameterBeam, ParticleBeam)):
         raise TypeError(f"Parameter incoming is of invalid type {type(incoming)}")
-    cache = owner.__dict__.setdefault("_lattice_cache", LatticeCache())
+    cache = lattice_cache(owner)
     beam = incoming
     for item in plan(owner, elements, raw, fuse_observers=isinstance(incoming, ParticleBeam)):
         if isinstance(item, Program):
@@ -513,14 +557,9 @@ def trace_program(leaves, losses: bool = False, screens: bool = False) -> Progra
 
 def _trace_plan(owner, leaves, losses: bool = False, screens: bool = False) -> Program:
     """`trace_program` remembered on `owner` like `plan` remembers the partition of `track`, per (losses, screens) mode."""
-    token = (_late().STRUCTURE[0], tuple(map(id, leaves)))
     mode = (bool(losses), bool(screens))
-    remembered = owner.__dict__.setdefault("_trace_plan", {}).get(mode)
-    if remembered is not None and remembered[0] == token:
-        return remembered[1]
-    program = trace_program(leaves, *mode)
-    owner.__dict__["_trace_plan"][mode] = (token, program)
-    return program
+    token = (_late().STRUCTURE[0], tuple(map(id, leaves)))
+    return _remembered(owner, "_trace_plan", mode, token, lambda: trace_program(leaves, *mode))
 
 
 def _aperture_limits(owner, program: Program, batch_shape, dtype, rt):
@@ -529,22 +568,20 @@ def _aperture_limits(owner, program: Program, batch_shape, dtype, rt):
     0 when every limit is shared by the batch).  Remembered on `owner` until a limit is written.
     """
     elements = [el for _, el, _ in program.apertures]
-    key = (id(program), tuple(batch_shape), np.dtype(dtype).str, tuple(el._version for el in elements))
-    remembered = owner.__dict__.get("_trace_limits")
-    if remembered is not None and remembered[0] == key:
-        return remembered[1], remembered[2]
-    B = int(np.prod(batch_shape, dtype=np.int64))
-    values = []
-    for el in elements:
-        assert np.all(el.x_max >= 0) and np.all(el.y_max >= 0)  # aperture.py:74-76
-        values += [np.asarray(el.x_max, dtype=dtype), np.asarray(el.y_max, dtype=dtype)]
-    shared = all(v.size == 1 for v in values)
-    rows = [v.reshape(1) if shared else _broadcast_param(v, batch_shape, dtype, "Aperture").reshape(B) for v in values]
-    host = np.ascontiguousarray(np.stack(rows, axis=1).reshape(-1, len(elements), 2)) if rows else np.zeros((1, 1, 2), dtype=dtype)
-    limits = rt.to_device(host)
-    stride = 0 if shared else 2 * len(elements)
-    owner.__dict__["_trace_limits"] = (key, limits, stride)
-    return limits, stride
+
+    def make():
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        values = []
+        for el in elements:
+            assert np.all(el.x_max >= 0) and np.all(el.y_max >= 0)  # aperture.py:74-76
+            values += [np.asarray(el.x_max, dtype=dtype), np.asarray(el.y_max, dtype=dtype)]
+        shared = all(v.size == 1 for v in values)
+        rows = [v.reshape(1) if shared else _broadcast_param(v, batch_shape, dtype, "Aperture").reshape(B) for v in values]
+        host = np.ascontiguousarray(np.stack(rows, axis=1).reshape(-1, len(elements), 2)) if rows else np.zeros((1, 1, 2), dtype=dtype)
+        return rt.to_device(host), 0 if shared else 2 * len(elements)
+
+    token = (id(program), tuple(batch_shape), np.dtype(dtype).str, tuple(el._version for el in elements))
+    return _remembered(owner, "_trace_limits", None, token, make)
 
 
 def _aperture_arguments(owner, program: Program, batch_shape, dtype, rt):
@@ -570,40 +607,40 @@ def _screen_geometry(owner, program: Program, batch_shape, dtype, rt, particles:
     them (0: shared by the batch), the image shapes and the cells of one sample's images.  For a ParticleBeam the grid is
     every screen's `pixel_bin_edges` in the lattice's dtype (x edges, then y edges) and an image is (ny, nx); for a
     ParameterBeam it is the pixel positions `Screen.reading` evaluates the density at (xs, then ys), an image (len(xs),
-    len(ys)).
+    len(ys)).  "arguments" is (count, rows, grid, misalignments, stride) as the library takes them.
     """
-    elements = [el for _, el in program.screens]
-    key = (tuple((step, id(el), el._version) for step, el in program.screens), tuple(batch_shape), np.dtype(dtype).str, bool(particles))
-    remembered = owner.__dict__.get("_trace_screens")
-    if remembered is not None and remembered[0] == key:
-        return remembered[1]
-    B = int(np.prod(batch_shape, dtype=np.int64))
-    rows, grid, shapes, shifts = [], [], [], []
-    for (step, el) in program.screens:
-        if particles:
-            xe, ye = (np.ascontiguousarray(e.astype(dtype)) for e in el.pixel_bin_edges)
-            nx, ny = len(xe) - 1, len(ye) - 1
-            shapes.append((ny, nx))
-            grid += [xe, ye]
-        else:
-            xs, ys = _pixel_positions(el, dtype)
-            nx, ny = len(xs), len(ys)
-            shapes.append((nx, ny))
-            grid += [xs, ys]
-        assert nx >= 1 and ny >= 1, f"Screen {el.name!r} has no pixels"
-        rows += [step, nx, ny]
-        shifts.append(np.asarray(el.misalignment, dtype=dtype))
-    shared = all(v.size == 2 for v in shifts)
-    shifts = [v.reshape(1, 2) if shared else _broadcast_param(v, (*batch_shape, 2), dtype, "Screen").reshape(B, 2) for v in shifts]
-    geometry = {
-        "rows": (C.c_int32 * len(rows))(*rows), "count": len(elements), "shapes": shapes,
-        "cells": int(sum(a * b for a, b in shapes)),
-        "grid": rt.to_device(np.ascontiguousarray(np.concatenate(grid))),
-        "misalignment": rt.to_device(np.ascontiguousarray(np.stack(shifts, axis=1))),
-        "stride": 0 if shared else 2 * len(elements),
-    }
-    owner.__dict__["_trace_screens"] = (key, geometry)
-    return geometry
+    def make():
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        rows, grid, shapes, shifts = [], [], [], []
+        for (step, el) in program.screens:
+            if particles:
+                xe, ye = (np.ascontiguousarray(e.astype(dtype)) for e in el.pixel_bin_edges)
+                nx, ny = len(xe) - 1, len(ye) - 1
+                shapes.append((ny, nx))
+                grid += [xe, ye]
+            else:
+                xs, ys = _pixel_positions(el, dtype)
+                nx, ny = len(xs), len(ys)
+                shapes.append((nx, ny))
+                grid += [xs, ys]
+            assert nx >= 1 and ny >= 1, f"Screen {el.name!r} has no pixels"
+            rows += [step, nx, ny]
+            shifts.append(np.asarray(el.misalignment, dtype=dtype))
+        shared = all(v.size == 2 for v in shifts)
+        shifts = [v.reshape(1, 2) if shared else _broadcast_param(v, (*batch_shape, 2), dtype, "Screen").reshape(B, 2) for v in shifts]
+        geometry = {
+            "rows": (C.c_int32 * len(rows))(*rows), "count": len(program.screens), "shapes": shapes,
+            "cells": int(sum(a * b for a, b in shapes)),
+            "grid": rt.to_device(np.ascontiguousarray(np.concatenate(grid))),
+            "misalignment": rt.to_device(np.ascontiguousarray(np.stack(shifts, axis=1))),
+            "stride": 0 if shared else 2 * len(program.screens),
+        }
+        # the screen argument group of every entry point that takes one, in the order they all take it
+        geometry["arguments"] = (geometry["count"], geometry["rows"], _ptr(geometry["grid"]), _ptr(geometry["misalignment"]), geometry["stride"])
+        return geometry
+
+    token = (tuple((step, id(el), el._version) for step, el in program.screens), tuple(batch_shape), np.dtype(dtype).str, bool(particles))
+    return _remembered(owner, "_trace_screens", None, token, make)
 
 
 def _screen_images(flat, geometry, batch_shape, dtype):
@@ -651,7 +688,13 @@ def chosen_particles(trajectories, incoming) -> np.ndarray:
     return np.ascontiguousarray(chosen, dtype=np.int64)
 
 
-def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, losses, rt, chosen=None):
+# An argument group of `lynx_track_particles_along_trajectories`, the superset entry point, that the same call without
+# trajectories would not hand over either: -1 for the list's length.  (The screen group ends with the image counts.)
+_NO_APERTURES = (-1, None, None, 0)
+_NO_SCREENS = (-1, None, None, None, 0, None)
+
+
+def _trace_particles(*, owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt, losses, chosen=None):
     """The ParticleBeam's trace: (trace, x and y of the centroid at every point, the device arrays a reverse pass reads)."""
     late = _late()
     dtype, batch_shape, P = incoming.dtype, incoming.batch_shape, lat.S + 1
@@ -661,36 +704,40 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
     common = (rt.ctx, lat.handle, n, _ptr(e_in), _ptr(p_in), _ptr(p_out), _ptr(e_trace), _ptr(records),
               _ffi.TRACK_SHARED_INPUT if incoming.is_shared else 0)
     lost_at = rt.empty((lat.B, n), np.int32) if losses == "particles" else None  # (4 B N bytes: device memory, read back once)
-    images = []
-    paths = path_lost_in = None
+    # every argument group once: what it is when present, and its absent form
+    paths = path_lost_in = shots = counts = None
+    screens = _NO_SCREENS
     if chosen is not None:
-        # the superset entry point; -1 for a list the same call without trajectories would not hand over either
         K = len(chosen)
         d_chosen = rt.to_device(chosen)  # (referenced until the call is enqueued)
         paths = rt.empty((lat.B, P, K, 7), dtype)
         path_lost_in = rt.empty((lat.B, K), np.int32) if losses else None
-        apertures = (_aperture_arguments(owner, program, batch_shape, dtype, rt) if losses or program.screens
-                     else (-1, None, None, 0))
-        shots = _screen_geometry(owner, program, batch_shape, dtype, rt, True) if program.screens else None
-        counts = rt.empty((lat.B, shots["cells"]), np.int32) if shots else None
-        screens = ((shots["count"], shots["rows"], _ptr(shots["grid"]), _ptr(shots["misalignment"]), shots["stride"], _ptr(counts))
-                   if shots else (-1, None, None, None, 0, None))
-        rt.check(rt.lib.lynx_track_particles_along_trajectories(
-            *common, *apertures, _ptr(lost_at), *screens, K, _ptr(d_chosen), _ptr(paths), _ptr(path_lost_in)))
-        if shots:
-            images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
-    elif program.screens:
+        particles = (K, _ptr(d_chosen), _ptr(paths), _ptr(path_lost_in))
+
+    def aperture_group():  # (the screens entry takes the apertures too: there are none without `losses`)
+        return _aperture_arguments(owner, program, batch_shape, dtype, rt) if losses or program.screens else _NO_APERTURES
+
+    # (a first call uploads the limits and the pixel grid here, the limits first for chosen particles and last otherwise:
+    # the order each of the two entry points that take both has always had)
+    if chosen is not None:
+        apertures = aperture_group()
+    if program.screens:
         shots = _screen_geometry(owner, program, batch_shape, dtype, rt, True)
         counts = rt.empty((lat.B, shots["cells"]), np.int32)  # (zeroed by the call, on its stream)
-        rt.check(rt.lib.lynx_track_particles_along_screens(
-            *common, *_aperture_arguments(owner, program, batch_shape, dtype, rt), _ptr(lost_at), shots["count"], shots["rows"],
-            _ptr(shots["grid"]), _ptr(shots["misalignment"]), shots["stride"], _ptr(counts)))
-        images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
+        screens = (*shots["arguments"], _ptr(counts))
+    if chosen is None:
+        apertures = aperture_group()
+    # the entry point that takes the groups present and no other: the trajectories entry, a superset of the other three, for chosen particles alone
+    if chosen is not None:
+        entry, groups = rt.lib.lynx_track_particles_along_trajectories, (*apertures, _ptr(lost_at), *screens, *particles)
+    elif program.screens:
+        entry, groups = rt.lib.lynx_track_particles_along_screens, (*apertures, _ptr(lost_at), *screens)
     elif losses:
-        rt.check(rt.lib.lynx_track_particles_along_losses(
-            *common, *_aperture_arguments(owner, program, batch_shape, dtype, rt), _ptr(lost_at)))
+        entry, groups = rt.lib.lynx_track_particles_along_losses, (*apertures, _ptr(lost_at))
     else:
-        rt.check(rt.lib.lynx_track_particles_along(*common))
+        entry, groups = rt.lib.lynx_track_particles_along, ()
+    rt.check(entry(*common, *groups))
+    images = _screen_images(counts.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype) if shots else []
     rec = records.numpy().reshape(*batch_shape, P, _ffi.MOMENT_STRIDE)
     energy = e_trace.numpy().reshape(*batch_shape, P)
     trace = late.BeamTrace.from_records(rec, energy, lengths, names, dtype,
@@ -704,19 +751,15 @@ def _trace_particles(owner, program: Program, lat, incoming, e_in, e_trace, leng
         trace.lost_at = lost_at.numpy().reshape(*batch_shape, n)
     # a beam object has one particle count for all samples: with losses there is none to hand out
     if keep_outgoing and not (losses and not np.all(rec[..., -1, 35] == n)):
-        out = late.ParticleBeam.__new__(late.ParticleBeam)
-        own_charges = incoming._charges is not None and incoming.is_shared
-        out._init_raw(Dual(dev=p_out), Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
-                      np.ascontiguousarray(incoming.particle_charges) if own_charges else incoming._charges, dtype,
-                      moments=Dual(np.ascontiguousarray(rec[..., -1, :])))
-        trace.outgoing = out
+        e_out = Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else None
+        trace.outgoing = _outgoing_particles(incoming, Dual(dev=p_out), e_out, Dual(np.ascontiguousarray(rec[..., -1, :])))
     device = {"records": records} if paths is None else {"records": records, "trajectories": paths}
     if lost_at is not None:  # (what the reverse pass of a trace with losses makes its survivor sets from)
         device["lost_at"] = lost_at
     return trace, rec[..., :, (0, 2)].astype(dtype), device  # (mean x, y of the particles alive at every point)
 
 
-def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt, make_images=True):
+def _trace_parameters(*, owner, program: Program, lat, incoming, e_in, e_trace, lengths, names, keep_outgoing, rt, make_images=True):
     """The ParameterBeam's trace: (trace, x and y of mu at every point, the device arrays a reverse pass reads).  Without
     `make_images` the active screens are points of the trace and nothing else: no image is made or read."""
     late = _late()
@@ -730,19 +773,16 @@ def _trace_parameters(owner, program: Program, lat, incoming, e_in, e_trace, len
         shots = _screen_geometry(owner, program, batch_shape, dtype, rt, False)
         density = rt.empty((lat.B, shots["cells"]), dtype)
         rt.check(rt.lib.lynx_gaussian_images_along(
-            rt.ctx, dtype_code(dtype), lat.B, P, _ptr(mu_t), _ptr(cov_t), shots["count"], shots["rows"], _ptr(shots["grid"]),
-            _ptr(shots["misalignment"]), shots["stride"], _ptr(density)))
+            rt.ctx, dtype_code(dtype), lat.B, P, _ptr(mu_t), _ptr(cov_t), *shots["arguments"], _ptr(density)))
         images = _screen_images(density.numpy().reshape(lat.B, shots["cells"]), shots, batch_shape, dtype)
     mu, cov = mu_t.numpy().reshape(*batch_shape, P, 7), cov_t.numpy().reshape(*batch_shape, P, 7, 7)
     energy = e_trace.numpy().reshape(*batch_shape, P)
     trace = late.BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype,
                                         screens=[step for step, _ in program.screens], screen_images=images if make_images else None)
     if keep_outgoing:
-        out = late.ParameterBeam.__new__(late.ParameterBeam)
-        out._init_raw(Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
-                      Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy,
-                      incoming.total_charge, dtype)
-        trace.outgoing = out
+        trace.outgoing = late.ParameterBeam._from_raw(
+            Dual(np.ascontiguousarray(mu[..., -1, :])), Dual(np.ascontiguousarray(cov[..., -1, :, :])),
+            Dual(np.ascontiguousarray(energy[..., -1])) if lat.has_cavity_step else incoming._energy, incoming.total_charge, dtype)
     return trace, mu[..., :, (0, 2)], {"mu": mu_t, "cov": cov_t}
 
 
@@ -775,16 +815,16 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
         raise TypeError('track_along: screens="points" is the trace of a ParameterBeam; a ParticleBeam\'s screens make their images')
     chosen = None if trajectories is None else chosen_particles(trajectories, incoming)
     rt = get_runtime()
-    cache = owner.__dict__.setdefault("_trace_cache", LatticeCache())
     dtype, batch_shape = incoming.dtype, incoming.batch_shape
-    lat = _ready(cache, program, batch_shape, dtype, incoming._energy._host)
+    lat = _ready(trace_cache(owner), program, batch_shape, dtype, incoming._energy._host)
     e_in = incoming._energy.broadcast_device(rt, batch_shape)
     e_trace = rt.empty_result((lat.B, lat.S + 1), dtype)
-    shared = (owner, program, lat, incoming, e_in, e_trace, [getattr(el, "length", None) for el in leaves], [el.name for el in leaves])
+    made = dict(owner=owner, program=program, lat=lat, incoming=incoming, e_in=e_in, e_trace=e_trace, rt=rt, keep_outgoing=keep_outgoing,
+                lengths=[getattr(el, "length", None) for el in leaves], names=[el.name for el in leaves])
     if isinstance(incoming, late.ParticleBeam):
-        trace, centre, device = _trace_particles(*shared, keep_outgoing, losses, rt, chosen)
+        trace, centre, device = _trace_particles(**made, losses=losses, chosen=chosen)
     else:
-        trace, centre, device = _trace_parameters(*shared, keep_outgoing, rt, make_images=not points_only)
+        trace, centre, device = _trace_parameters(**made, make_images=not points_only)
     trace.total_charge = incoming.total_charge
     if keep_device:
         trace._device = device
@@ -801,22 +841,12 @@ def transfer_map(owner, elements, energy, dtype, raw: bool = False) -> np.ndarra
     rt = get_runtime()
     dtype = np.dtype(dtype)
     energy = np.asarray(energy, dtype=dtype)
-    batch_shape = energy.shape
     items = plan(owner, elements, raw)
     if not items:
-        out = np.zeros((*batch_shape, 7, 7), dtype=dtype)
-        out[..., range(7), range(7)] = 1
-        return out
+        return np.tile(np.eye(7, dtype=dtype), (*energy.shape, 1, 1))
     assert len(items) == 1 and isinstance(items[0], Program) and len(items[0].steps) == 1, (
         "transfer_map needs a skippable element list")
-    program = items[0]
-    cache = owner.__dict__.setdefault("_lattice_cache", LatticeCache())
-    lat = _ready(cache, program, batch_shape, dtype, energy)
-    e_in = rt.to_device(np.ascontiguousarray(energy))
-    steps = rt.empty((lat.B, 1, _ffi.STEP_STRIDE), dtype)
-    rt.check(rt.lib.lynx_build_compose(rt.ctx, lat.handle, _ptr(e_in), _ptr(steps), None))
-    table = steps.numpy()
-    return table[:, 0, :49].reshape(*batch_shape, 7, 7)
+    return _composed_map(rt, lattice_cache(owner), items[0], energy, dtype)
 
 
 def cavity_rmatrix(cavity, energy, dtype) -> np.ndarray:
@@ -826,7 +856,11 @@ def cavity_rmatrix(cavity, energy, dtype) -> np.ndarray:
     energy = np.asarray(energy, dtype=dtype)
     program = Program(raw=True)
     program.add_run_element(cavity, True)
-    cache = cavity.__dict__.setdefault("_lattice_cache", LatticeCache())
+    return _composed_map(rt, lattice_cache(cavity), program, energy, dtype)
+
+
+def _composed_map(rt, cache, program: Program, energy, dtype) -> np.ndarray:
+    """The map of a program of one step at `energy` (`lynx_build_compose`) -> host array (*energy.shape, 7, 7)."""
     lat = _ready(cache, program, energy.shape, dtype, energy)
     e_in = rt.to_device(np.ascontiguousarray(energy))
     steps = rt.empty((lat.B, 1, _ffi.STEP_STRIDE), dtype)

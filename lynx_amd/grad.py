@@ -306,7 +306,7 @@ class TrackVJP:
         self.program = items[0]
         beam = beam.materialized()  # the reverse pass indexes the incoming particles per sample
         self.beam = beam
-        self.cache = segment.__dict__.setdefault("_lattice_cache", engine.LatticeCache())
+        self.cache = engine.lattice_cache(segment)
         self.outgoing = engine.run_program_particles(self.cache, self.program, beam, moments=True)
 
     def __call__(self, mu_bar=None, cov_bar=None, wrt_particles: bool = False, readings: dict | None = None,
@@ -396,7 +396,7 @@ class MomentsVJP:
         for item in items:
             if not isinstance(item, engine.Program) and not getattr(item, "_fusable_observer", False):
                 raise NotImplementedError("track_vjp: lattices with an active Screen or Aperture are not differentiated")
-        self.cache = segment.__dict__.setdefault("_lattice_cache", engine.LatticeCache())
+        self.cache = engine.lattice_cache(segment)
         self.stretches = []  # (Program, beam entering it) / (BPM, None), in lattice order
         for k, item in enumerate(items):
             if isinstance(item, engine.Program):
@@ -770,9 +770,8 @@ class TrackAlongVJP:
         targets_dev = self._targets._device(rt, layout)
         loss, sums = rt.empty((B, K), np.float64), rt.empty((B, K, 6), np.float64)
         rt.check(rt.lib.lynx_gaussian_images_along_mse(
-            rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), K, shots["rows"], _p(shots["grid"]),
-            _p(shots["misalignment"]), shots["stride"], (C.c_int64 * K)(*layout.offsets), _p(targets_dev), layout.stride,
-            _p(loss), _p(sums)))
+            rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), *shots["arguments"],
+            (C.c_int64 * K)(*layout.offsets), _p(targets_dev), layout.stride, _p(loss), _p(sums)))
         return loss, sums, [offset >= 0 for offset in layout.offsets]
 
     @property
@@ -977,7 +976,7 @@ class TrackAlongVJP:
             _refuse_moments(self._cavity)
         mb, cb, eb = self._cotangents(mu_bar, cov_bar, energy_bar, readings, properties)
         rt = get_runtime()
-        sweep = _Sweep(rt, self.segment.__dict__.setdefault("_trace_cache", engine.LatticeCache()), self.program, self.beam)
+        sweep = _Sweep(rt, engine.trace_cache(self.segment), self.program, self.beam)
         # (an upload is named until its call has been enqueued, so that it stays allocated; no energy cotangent: no upload)
         eb_dev = rt.to_device(eb.astype(self.beam.dtype)) if np.any(eb) else None
         launch = getattr(self, "_launch_" + self.mode)  # (_launch_moments, _particles, _trajectories, _survivors, _kicks)
@@ -995,8 +994,8 @@ class TrackAlongVJP:
             wi_dev = rt.to_device(np.ascontiguousarray(wi, dtype=beam.dtype))
             shifts = rt.empty((B, shots["count"], 2), beam.dtype)
             rt.check(rt.lib.lynx_gaussian_images_along_backward(
-                rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), shots["count"], shots["rows"],
-                _p(shots["grid"]), _p(shots["misalignment"]), shots["stride"], _p(wi_dev), _p(mb_dev), _p(cb_dev), _p(shifts)))
+                rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), *shots["arguments"],
+                _p(wi_dev), _p(mb_dev), _p(cb_dev), _p(shifts)))
         if lb is not None:  # ... and so do the image losses' cotangents times the sums of the forward pass
             shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
             lb_dev = rt.to_device(np.ascontiguousarray(lb, dtype=beam.dtype))

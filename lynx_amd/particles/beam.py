@@ -10,6 +10,14 @@ ELECTRON_MASS_EV = 510998.95069  # beam.py:8
 class Beam:
     empty = "I'm an empty beam!"
 
+    @classmethod
+    def _from_raw(cls, *fields, **more):
+        """A beam of this class from the arguments of its `_init_raw` -- values that already are what a beam holds (`Dual`s,
+        arrays of the beam's dtype): nothing is converted, checked or copied."""
+        beam = cls.__new__(cls)
+        beam._init_raw(*fields, **more)
+        return beam
+
     @property
     def parameters(self) -> dict:
         return {k: getattr(self, k) for k in ("mu_x", "mu_xp", "mu_y", "mu_yp", "sigma_x", "sigma_xp",

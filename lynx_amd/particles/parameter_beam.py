@@ -30,9 +30,7 @@ class ParameterBeam(Beam):
         self.dtype = np.dtype(dtype)
 
     def _shallow_copy(self):
-        out = ParameterBeam.__new__(ParameterBeam)
-        out._init_raw(self._mu_d, self._cov_d, self._energy, self.total_charge, self.dtype)
-        return out
+        return ParameterBeam._from_raw(self._mu_d, self._cov_d, self._energy, self.total_charge, self.dtype)
 
     @property
     def batch_shape(self):

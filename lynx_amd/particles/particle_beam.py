@@ -89,9 +89,7 @@ class ParticleBeam(Beam):
         self._batch = batch
 
     def _shallow_copy(self):
-        out = ParticleBeam.__new__(ParticleBeam)
-        out._init_raw(self._particles, self._energy, self._charges, self.dtype, self._moments, self._batch)
-        return out
+        return ParticleBeam._from_raw(self._particles, self._energy, self._charges, self.dtype, self._moments, self._batch)
 
     @property
     def is_shared(self) -> bool:
@@ -214,8 +212,7 @@ class ParticleBeam(Beam):
         total_charge = np.asarray(total_charge, dtype=dtype)
         charges = (np.ones((*shape, n), dtype=dtype) * total_charge[..., None] / n
                    if np.any(total_charge != 0) else None)
-        beam = cls.__new__(cls)
-        beam._init_raw(Dual(dev=arr), Dual(np.asarray(energy, dtype=dtype)), charges, dtype)
+        beam = cls._from_raw(Dual(dev=arr), Dual(np.asarray(energy, dtype=dtype)), charges, dtype)
         if charges is None:
             beam._zero_charge_shape = shape
         return beam
@@ -346,9 +343,7 @@ class ParticleBeam(Beam):
         dbl = C.c_double * 6
         rt.check(rt.lib.lynx_fill_gaussian(rt.ctx, dtype_code(dtype), B, num_particles, dbl(*mu), dbl(*sigma),
                                            C.c_uint64(seed), C.c_void_p(arr.ptr)))
-        out = cls.__new__(cls)
-        out._init_raw(Dual(dev=arr), Dual(np.full(batch_shape, energy, dtype=dtype)), None, dtype)
-        return out
+        return cls._from_raw(Dual(dev=arr), Dual(np.full(batch_shape, energy, dtype=dtype)), None, dtype)
 
     def transformed_to(self, mu_x=None, mu_y=None, mu_xp=None, mu_yp=None, sigma_x=None, sigma_y=None,
                        sigma_xp=None, sigma_yp=None, sigma_s=None, sigma_p=None, energy=None,
@@ -412,10 +407,8 @@ class ParticleBeam(Beam):
             charges = self._charges
         else:
             charges = np.ones((*batch, n), dtype=self.dtype) * np.asarray(total_charge, self.dtype)[..., None] / n
-        beam = self.__class__.__new__(self.__class__)
-        beam._init_raw(Dual(dev=out), Dual(np.asarray(energy, dtype=self.dtype)),
-                       None if charges is None else np.asarray(charges, dtype=self.dtype), self.dtype)
-        return beam
+        return self._from_raw(Dual(dev=out), Dual(np.asarray(energy, dtype=self.dtype)),
+                              None if charges is None else np.asarray(charges, dtype=self.dtype), self.dtype)
 
     def broadcast(self, shape: tuple) -> "ParticleBeam":
         """
@@ -429,9 +422,7 @@ class ParticleBeam(Beam):
             d = max(len(stored), len(shape))
             batch = tuple(a * b for a, b in zip((1,) * (d - len(stored)) + tuple(stored),
                                                 (1,) * (d - len(shape)) + tuple(shape)))
-            out = self.__class__.__new__(self.__class__)
-            out._init_raw(self._particles, Dual(np.tile(self.energy, shape)), self._charges, self.dtype, self._moments, batch)
-            return out
+            return self._from_raw(self._particles, Dual(np.tile(self.energy, shape)), self._charges, self.dtype, self._moments, batch)
         if self.is_shared:
             return self.materialized().broadcast(shape)
         return self.__class__(

@@ -5,6 +5,10 @@ and each argument by value --, an allocated output reads back as seeded random n
 (`engine.track_along`, `engine.run_program_particles`, `engine.run_program_parameters`) are fabricated on the host: what
 `grad.py` does between its arguments and the C boundary is then a pure function, which tests/test_reverse_calls_host.py
 holds to a transcript.
+
+`fake_engine_gpu` leaves the forward passes as they are and replaces the runtime alone: the library then also plays the
+entry points of `lynx_amd/engine.py` that hand something back (a lattice handle, the blocks of `lynx_track_particles_new`,
+a read-back), so that tests/test_engine_calls_host.py holds the forward host path to a transcript in the same way.
 """
 
 import ctypes as C
@@ -22,6 +26,8 @@ class FakeArray:
     multiples of 1/4 drawn from a generator seeded by the allocation's ordinal in its runtime.
     """
 
+    fill = None  # what an array the library wrote reads back as, where seeded random numbers would not do
+
     def __init__(self, rt, how, shape, dtype, host=None):
         self.how, self.shape, self.dtype, self.host = how, tuple(int(n) for n in shape), np.dtype(dtype), host
         self.ordinal = len(rt.allocations)
@@ -31,6 +37,8 @@ class FakeArray:
     def numpy(self):
         if self.host is not None:
             return self.host.copy()
+        if self.fill is not None:
+            return np.ascontiguousarray(self.fill, dtype=self.dtype).reshape(self.shape)
         return (np.random.default_rng(self.ordinal).integers(-8, 9, size=self.shape) / 4.0).astype(self.dtype)
 
     def __array__(self, dtype=None, copy=None):
@@ -58,22 +66,110 @@ class FakeLibrary:
             return self._rt.allocations[value.value // 4096 - 1].tag()
         if isinstance(value, C.Array):
             return {"ctypes": [int(v) for v in value]}
+        if isinstance(value, dict):  # (what an entry point played below has already put by value)
+            return value
         raise AssertionError(f"an argument of type {type(value)} crossed the C boundary")
 
     def __getattr__(self, name):
         def entry(*args):
+            if name in self.UNRECORDED:
+                return 0
             self.calls.append(name)
-            self.records.append((name, [self._argument(a) for a in args]))
+            played = getattr(type(self), "_play_" + name.removeprefix("lynx_"), None)
+            self.records.append((name, [self._argument(a) for a in (args if played is None else played(self, *args))]))
             return 0
         return entry
+
+    # ---- the entry points of the forward host path that hand something back: each returns the arguments to record ----
+
+    UNRECORDED = ("lynx_lattice_destroy",)  # (a finaliser's call: when it comes is the garbage collector's matter)
+
+    def _allocation(self, pointer):
+        return self._rt.allocations[(pointer.value if isinstance(pointer, C.c_void_p) else pointer) // 4096 - 1]
+
+    @staticmethod
+    def _host_bytes(address, count, dtype):
+        """`count` scalars the host holds at `address`, as the upload they are."""
+        dtype = np.dtype(dtype)
+        return {"host": np.frombuffer(C.string_at(address, count * dtype.itemsize), dtype=dtype).copy()}
+
+    @staticmethod
+    def _structs(array, count):
+        return {"structs": [[int(getattr(item, name)) for name, _ in item._fields_] for item in array[:count]]}
+
+    def _play_lattice_create(self, ctx, code, B, E, elems, S, steps, pool, pool_size, handle):
+        from lynx_amd import _ffi
+
+        dtype = np.float32 if code == _ffi.F32 else np.float64
+        lattice = FakeArray(self._rt, "lattice", (B,), dtype)
+        lattice.S, lattice.step_flags = S, [int(step.flags) for step in steps[:S]]
+        handle._obj.value = lattice.ptr
+        return (ctx, code, B, E, self._structs(elems, E), S, self._structs(steps, S), self._host_bytes(pool, pool_size, dtype), pool_size)
+
+    def _play_lattice_update_params(self, handle, offset, size, block):
+        return handle, offset, size, self._host_bytes(block, size, self._allocation(handle).dtype)
+
+    def _play_lattice_set_flags(self, handle, elem_flags, step_flags):
+        lattice = self._allocation(handle)
+        lattice.step_flags = [int(f) for f in step_flags[:lattice.S]]
+        return handle, elem_flags, step_flags
+
+    def _play_track_particles_new(self, ctx, handle, n, e_in, p_in, flags, with_energy, blocks):
+        from lynx_amd import _ffi
+
+        rt, lattice = self._rt, self._allocation(handle)
+        B, dtype = lattice.shape[0], lattice.dtype
+        observers = sum(1 for f in lattice.step_flags if f & _ffi.STEP_FLAG_OBSERVE)
+        made = [FakeArray(rt, "library: particles", (B, n, 7), dtype),
+                FakeArray(rt, "library: energy", (B,), dtype) if with_energy else None,
+                FakeArray(rt, "library: moments", (B, _ffi.MOMENT_STRIDE), np.float64) if flags & (_ffi.TRACK_MOMENTS | _ffi.TRACK_COVARIANCE) else None,
+                FakeArray(rt, "library: readings", (B, observers, 2), np.float64) if observers else None]
+        if made[1] is not None:
+            made[1].fill = fabricated_energy((B,), made[1].ordinal)
+        if made[2] is not None:
+            made[2].fill = fabricated_records((B,), 1, 3, count=n)
+        for k, block in enumerate(made):
+            blocks[k] = None if block is None else block.ptr
+        return (ctx, handle, n, C.c_void_p(e_in), C.c_void_p(p_in), flags, with_energy,
+                {"blocks": [None if block is None else block.tag() for block in made]})
+
+    def _play_buf_d2h(self, ctx, host, pointer, nbytes):
+        block = self._allocation(pointer)
+        data = block.numpy().tobytes()
+        assert len(data) == nbytes, (block.tag(), nbytes)
+        C.memmove(host, data, nbytes)
+        return ctx, {"read back": block.tag()}, nbytes
+
+    def _play_particle_trace(self, *args):
+        """e_trace and the moment records of the four `lynx_track_particles_along*`: plausible values, as `BeamTrace` wants them."""
+        n, e_trace, records = args[2], self._allocation(args[6]), self._allocation(args[7])
+        B, P = records.shape[0], records.shape[1]
+        e_trace.fill = fabricated_energy((B, P), e_trace.ordinal)
+        records.fill = fabricated_records((B,), P, 1, nobody=self._rt.nobody if len(args) > 9 and args[9] > 0 else (), count=n)
+        return args
+
+    _play_track_particles_along = _play_track_particles_along_losses = _play_particle_trace
+    _play_track_particles_along_screens = _play_track_particles_along_trajectories = _play_particle_trace
+
+    def _play_track_moments_along(self, *args):
+        mu, cov, e_trace = (self._allocation(a) for a in args[5:8])
+        B, P = mu.shape[0], mu.shape[1]
+        mu.fill, cov.fill = fabricated_moments((B,), (P,), mu.dtype, 2)
+        e_trace.fill = fabricated_energy((B, P), e_trace.ordinal)
+        return args
 
 
 class FakeRuntime:
     ctx = None
+    closed = False
 
-    def __init__(self):
+    def __init__(self, nobody=()):
         self.allocations = []
+        self.nobody = tuple(nobody)  # the (flat sample, point) no particle of a trace with active apertures reaches
         self.lib = FakeLibrary(self)
+
+    def free(self, ptr):
+        pass
 
     def empty(self, shape, dtype):
         return FakeArray(self, "empty", shape, dtype)
@@ -96,8 +192,9 @@ class FakeRuntime:
         assert status == 0
 
 
-def fabricated_records(batch, P, seed=0, nobody=()):
-    """(*batch, P, 36) moment records of N particles drawn per sample and point; `nobody`: (flat sample, point) left empty."""
+def fabricated_records(batch, P, seed=0, nobody=(), count=N):
+    """(*batch, P, 36) moment records of N particles drawn per sample and point, said to be of `count`; `nobody`: (flat
+    sample, point) left empty."""
     rng = np.random.default_rng(seed)
     B = int(np.prod(batch, dtype=np.int64))
     rec = np.zeros((B, P, 36))
@@ -110,10 +207,40 @@ def fabricated_records(batch, P, seed=0, nobody=()):
             d = z - z.mean(axis=0)
             rec[b, k, :6], rec[b, k, 6] = z.mean(axis=0), 1.0
             rec[b, k, 7:28] = (d.T @ d / N)[rows, cols]
-            rec[b, k, 34], rec[b, k, 35] = 1.0, N
+            rec[b, k, 34], rec[b, k, 35] = 1.0, count
     for b, k in nobody:
         rec[b, k, :35], rec[b, k, 35] = np.nan, 0.0
     return rec.reshape(*batch, P, 36)
+
+
+def fabricated_moments(batch, lead, dtype, seed):
+    """mu (*batch, *lead, 7) and cov (*batch, *lead, 7, 7) of `fabricated_records`."""
+    rec = fabricated_records(batch, int(np.prod(lead, dtype=np.int64)), seed).reshape(*batch, *lead, 36)
+    mu, cov = np.zeros((*batch, *lead, 7)), np.zeros((*batch, *lead, 7, 7))
+    rows, cols = np.triu_indices(6)
+    mu[...] = rec[..., :7]
+    cov[..., rows, cols] = rec[..., 7:28]
+    cov[..., cols, rows] = rec[..., 7:28]
+    return mu.astype(dtype), cov.astype(dtype)
+
+
+def fabricated_energy(shape, seed):
+    """Energies a cavity may meet: 10 MeV and a few steps of 0.25 MeV above it."""
+    return 1e7 + 2.5e5 * np.random.default_rng(seed).integers(0, 9, size=shape)
+
+
+def fake_engine_gpu(monkeypatch, nobody=()):
+    """
+    `lynx_amd` with the runtime replaced and nothing else, until `monkeypatch` is undone: `engine.track`, `track_along`,
+    `transfer_map` and `cavity_rmatrix` run as they are, against a library that records.  Returns the runtime.
+    """
+    from lynx_amd import device, engine, grad
+    from lynx_amd.accelerator import diagnostics
+
+    rt = FakeRuntime(nobody)
+    for module in (device, engine, grad, diagnostics):
+        monkeypatch.setattr(module, "get_runtime", lambda: rt)
+    return rt
 
 
 def fake_gpu(monkeypatch, nobody=(), clamped=()):
@@ -128,15 +255,6 @@ def fake_gpu(monkeypatch, nobody=(), clamped=()):
     from lynx_amd.trace import BeamTrace
 
     rt, forward = FakeRuntime(), []
-
-    def moments_of(batch, lead, dtype, seed):
-        rec = fabricated_records(batch, int(np.prod(lead, dtype=np.int64)), seed).reshape(*batch, *lead, 36)
-        mu, cov = np.zeros((*batch, *lead, 7)), np.zeros((*batch, *lead, 7, 7))
-        rows, cols = np.triu_indices(6)
-        mu[...] = rec[..., :7]
-        cov[..., rows, cols] = rec[..., 7:28]
-        cov[..., cols, rows] = rec[..., 7:28]
-        return mu.astype(dtype), cov.astype(dtype)
 
     def track_along(owner, leaves, incoming, **kwargs):
         forward.append(kwargs)
@@ -160,32 +278,28 @@ def fake_gpu(monkeypatch, nobody=(), clamped=()):
             return trace
         program = engine._trace_plan(owner, leaves, bool(kwargs.get("losses")), bool(kwargs.get("screens")))
         shots = engine._screen_geometry(owner, program, batch, dtype, rt, False) if program.screens else {"shapes": []}
-        mu, cov = moments_of(batch, (P,), dtype, 2)
+        mu, cov = fabricated_moments(batch, (P,), dtype, 2)
         trace = BeamTrace.from_moments(mu, cov, energy, lengths, names, dtype, screens=[step for step, _ in program.screens],
                                        screen_images=[np.zeros((*batch, *shape), dtype) for shape in shots["shapes"]])
         trace._device = {"mu": rt.forward("mu", (B, P, 7), dtype), "cov": rt.forward("cov", (B, P, 7, 7), dtype)}
         return trace
 
     def run_program_particles(cache, program, beam, moments=None):
-        out = lx.ParticleBeam.__new__(lx.ParticleBeam)
         batch = beam.batch_shape
         rec = fabricated_records(batch, 1, 3).reshape(*batch, 36)
         record = rt.forward("moments", rec.shape)
         record.host = rec
-        out._init_raw(Dual(dev=rt.forward("particles", (*batch, beam.num_particles, 7), beam.dtype)), beam._energy, None, beam.dtype,
-                      moments=Dual(dev=record))
-        return out
+        return lx.ParticleBeam._from_raw(Dual(dev=rt.forward("particles", (*batch, beam.num_particles, 7), beam.dtype)), beam._energy, None,
+                                         beam.dtype, moments=Dual(dev=record))
 
     stretch = [0]
 
     def run_program_parameters(cache, program, beam):
         stretch[0] += 1
-        mu, cov = moments_of(beam.batch_shape, (), beam.dtype, 10 + stretch[0])
+        mu, cov = fabricated_moments(beam.batch_shape, (), beam.dtype, 10 + stretch[0])
         for c in clamped:
             cov[..., c, c] = np.resize(np.array([1e-20, 1e-21, 0.0, 4e-8], dtype=cov.dtype), cov[..., c, c].shape)
-        out = lx.ParameterBeam.__new__(lx.ParameterBeam)
-        out._init_raw(Dual(mu), Dual(cov), beam._energy, beam.total_charge, beam.dtype)
-        return out
+        return lx.ParameterBeam._from_raw(Dual(mu), Dual(cov), beam._energy, beam.total_charge, beam.dtype)
 
     class Lattice:
         handle = None
