@@ -573,6 +573,66 @@ int lynx_gaussian_images_along_mse_backward(lynx_ctx* ctx, int dtype, int64_t ba
                                             const double* d_sums, const void* d_loss_bar, void* d_mu_bar, void* d_cov_bar,
                                             void* d_grad_misalignment);
 
+/* The loss every tuning loop on a trace writes, evaluated on the device from the states the trace left there: a weighted
+ * sum of squared distances of named beam properties at chosen points to target values.  No cotangent array with a point
+ * axis is made on the host or moved.  Exactly one of the two state forms is given:
+ *   d_records       [B][n_points][36] float64, what lynx_track_particles_along* wrote (d_mu_trace, d_cov_trace NULL), or
+ *   d_mu_trace, d_cov_trace   [B][n_points][7], [B][n_points][7][7] in `dtype`, what lynx_track_moments_along wrote
+ *                   (d_records NULL)
+ *   d_energy_trace  [B][n_points] in `dtype`, the energy at every point
+ *   ddof            0 or 1: the records' variances are scaled by n / (n - ddof), n = slot 35 (unused for mu and cov)
+ *   target_points   host [n_target_points][2]: point (strictly increasing) and property mask, not 0 -- bit k is property k of
+ *                   mu_x mu_xp mu_y mu_yp mu_s mu_p (0..5), sigma_x .. sigma_p (6..11), sigma_xxp sigma_yyp (12, 13),
+ *                   emittance_x|y (14, 15), normalized_emittance_x|y (16, 17), beta_x|y (18, 19), alpha_x|y (20, 21),
+ *                   energy (22).  The T terms of a sample, T = the set bits of all masks, are ordered by (point, bit).
+ *   d_rows          [T][2] (row_stride = 0: one row set shared by the batch) or [B][T][2] (row_stride = 2 T) float64:
+ *                   (target, weight) of every term
+ *   d_values        [B][T] float64: the value of every term
+ *   d_point_loss    [B][n_target_points] float64: sum over a point's terms, in bit order, of weight (value - target)^2
+ *   d_loss          [B] float64: a sample's point losses added in point order
+ * The value of a term is formed in float64 for both dtypes (float32 states are widened on load; nothing is contracted):
+ *   records   s2_c = rec[tri(c, c)] n / (n - ddof), cross_a = rec[tri(a, a + 1)], mu_c = rec[c]
+ *   mu, cov   s2_c = max(cov_cc, floor), floor = 1e-20 rounded to `dtype`; cross_a = cov[a][a + 1]
+ *   both      sigma_c = sqrt(s2_c), sigma_xxp = cross_0, sigma_yyp = cross_2; per plane a = 0 | 2: q = s2_a s2_(a+1) -
+ *             cross_a^2, emittance = sqrt(max(q, tiny)), tiny the smallest normal number of `dtype`, beta = s2_a /
+ *             emittance, alpha = -cross_a / emittance, normalized_emittance = emittance gamma sqrt(1 - 1 / gamma^2) with
+ *             gamma = energy / 510998.95069 (0 at gamma == 0)
+ * -- the expressions grad.trace_property_cotangents differentiates, not the trace's property rounded to `dtype`.  A record
+ * with n == ddof gives the inf or NaN of that arithmetic.  One thread per (sample, target point), the target points by
+ * value in the kernel arguments, 64 per launch; a second small kernel adds a sample's point losses.  No atomics: the
+ * same call returns the same bits.  Between lynx_profile_begin and _end every launch of this entry and of its reverse half
+ * is one more entry of lynx_profile_launches.  LYNX_ERR_INVALID before anything is launched (lynx_last_error starts with "moment
+ * loss along the trace: ") for a null required argument, both or neither state form, batch, n_points or n_target_points
+ * <= 0, a dtype that is neither float32 nor float64, ddof outside 0 .. 1, a point outside the trace or not increasing,
+ * a mask that is 0 or has a bit above 22, a row stride that is neither 0 nor 2 T.                                      */
+int lynx_moments_along_loss(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const double* d_records,
+                            const void* d_mu_trace, const void* d_cov_trace, const void* d_energy_trace, int32_t ddof,
+                            int32_t n_target_points, const int32_t* target_points, const double* d_rows, int64_t row_stride,
+                            double* d_values, double* d_point_loss, double* d_loss);
+
+/* ... and its reverse half.  Arguments up to row_stride exactly as for lynx_moments_along_loss, and
+ *   d_loss_bar     [B] float64: the cotangents of d_loss
+ *   d_grad_trace   [B][n_points][36] float64, read and written (records form; d_mu_bar, d_cov_bar NULL): dL/d(record), an
+ *                  off-diagonal entry counted once -- what lynx_track_particles_along_backward* take
+ *   d_mu_bar, d_cov_bar   [B][n_points][7], [B][n_points][7][7] in `dtype`, read and written (mu, cov form; d_grad_trace
+ *                  NULL): entry by entry -- what lynx_track_moments_along_backward takes
+ *   d_energy_bar   [B][n_points] in `dtype`, read and written; may be NULL if no term is energy or normalized_emittance_*
+ * Per sample and term the bar is d_loss_bar[b] 2 weight (value - target), the value recomputed by the forward kernel's
+ * expression (the same bits), taken through the rule of grad.trace_property_cotangents (derivative 0 where s2 or q is
+ * clamped) and ADDED at the term's point: mu_<c> into slot c; sigma_<c> into the variance of c; sigma_xxp | yyp into the (a,
+ * a + 1) entry; emittance, normalized_emittance, beta and alpha of a plane into its two variances and its (a, a + 1)
+ * entry -- slots tri(c, c), tri(a, a + 1) of a record, cov_bar[c][c], cov_bar[a][a + 1] --; energy and
+ * normalized_emittance into d_energy_bar.  Nothing else is touched.  One thread per (sample, target point) accumulates
+ * its point's bars in float64 registers and does one read-add-write per touched entry (mu_bar, cov_bar, energy_bar
+ * rounded once, on the add); target points are distinct, so there are no atomics and the same call returns the same
+ * bits.  The refusals and the message's beginning are those of lynx_moments_along_loss, and: cotangents of the other
+ * state form, a NULL d_energy_bar with a term that depends on the energy.                                              */
+int lynx_moments_along_loss_backward(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const double* d_records,
+                                     const void* d_mu_trace, const void* d_cov_trace, const void* d_energy_trace, int32_t ddof,
+                                     int32_t n_target_points, const int32_t* target_points, const double* d_rows,
+                                     int64_t row_stride, const double* d_loss_bar, double* d_grad_trace, void* d_mu_bar,
+                                     void* d_cov_bar, void* d_energy_bar);
+
 /* Test hook: the float32 sine / cosine the cavity kick uses on the device (cavity.py:141-161
  * calls cos per particle), scalar (packed = 0) or two-per-lane (packed = 1) code path.        */
 int lynx_diag_phase_trig(lynx_ctx* ctx, int64_t n, const float* d_x, int32_t packed, float* d_sin,

@@ -125,6 +125,10 @@ SIGNATURES = {
                                             _i64, C.POINTER(_i64), _vp, _i64, _vp, _vp]),
     "lynx_gaussian_images_along_mse_backward": (_i, [_vp, _i, _i64, C.c_int32, _vp, C.c_int32, C.POINTER(C.c_int32), _vp,
                                                      _vp, _vp, _vp, _vp]),
+    "lynx_moments_along_loss": (_i, [_vp, _i, _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32),
+                                     _vp, _i64, _vp, _vp, _vp]),
+    "lynx_moments_along_loss_backward": (_i, [_vp, _i, _i64, C.c_int32, _vp, _vp, _vp, _vp, C.c_int32, C.c_int32,
+                                              C.POINTER(C.c_int32), _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "lynx_diag_phase_trig": (_i, [_vp, _i64, _vp, C.c_int32, _vp, _vp]),
     "lynx_aperture_mask": (_i, [_vp, _i, _i64, _i64, _vp, _vp, _vp, C.c_int32, C.c_int32, _vp, _vp, _vp, _vp]),
     "lynx_aperture_compact": (_i, [_vp, _i, _i64, _vp, _vp, _vp, _vp, _vp]),

@@ -24,6 +24,7 @@
 #include "lynx_grad_units.hpp"
 #include "lynx_trace.hpp"
 #include "lynx_trace_grad.hpp"
+#include "lynx_moment_loss.hpp"
 
 using namespace lynx;
 
@@ -3532,6 +3533,157 @@ int lynx_gaussian_images_along_mse_backward(lynx_ctx* ctx, int dtype, int64_t ba
                          (const T*)d_loss_bar, (T*)d_mu_bar, (T*)d_cov_bar, (T*)d_grad_misalignment);
     });
     HIP_TRY(ctx, hipGetLastError());
+  }
+  return LYNX_OK;
+}
+
+// ---- the moment loss along a trace ---------------------------------------------------------
+
+// What the two moment loss entries check alike, every refusal in front of anything else -> the number of terms in `*n_terms`.
+static int moment_loss_arguments(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const double* d_records,
+                                 const void* d_mu_trace, const void* d_cov_trace, const void* d_energy_trace, int32_t ddof,
+                                 int32_t n_target_points, const int32_t* target_points, const double* d_rows, int64_t row_stride,
+                                 int* n_terms, int* all_masks) {
+  if (!d_energy_trace || !target_points || !d_rows || batch <= 0 || n_points <= 0 || n_target_points <= 0)
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: bad argument");
+  if ((d_records != nullptr) == (d_mu_trace != nullptr || d_cov_trace != nullptr) || (d_mu_trace != nullptr) != (d_cov_trace != nullptr))
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: the states are records, or mu and cov, not both and not neither");
+  if (dtype != LYNX_F32 && dtype != LYNX_F64)
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: the dtype is float32 or float64");
+  if (ddof < 0 || ddof > 1)
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: ddof is 0 or 1");
+  int64_t terms = 0;
+  int masks = 0;
+  for (int32_t q = 0; q < n_target_points; ++q) {
+    const int32_t point = target_points[2 * q], mask = target_points[2 * q + 1];
+    if (point < 0 || point >= n_points || (q > 0 && point <= target_points[2 * q - 2]))
+      return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: the target points lie inside the trace and increase");
+    if (mask <= 0 || mask >= (1 << kMomentLossProperties))
+      return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: a property mask has bits 0 .. 22 and is not 0");
+    terms += __builtin_popcount((unsigned)mask);
+    masks |= mask;
+  }
+  if (row_stride != 0 && row_stride != 2 * terms)
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: the rows' sample stride is 0 or 2 * the number of terms");
+  if (batch > 0x7fffffffLL * kMomentLossThreads / kMomentLossPoints)  // (a launch has a thread per sample and point of its chunk)
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: bad argument (the batch is beyond 2^31 - 1)");
+  *n_terms = (int)terms;
+  *all_masks = masks;
+  return LYNX_OK;
+}
+
+// The target points of one launch, by value: points `first` .. `first + count - 1` and the ordinal of each one's first term.
+static MomentLossPoints moment_loss_chunk(const int32_t* target_points, int32_t first, int count, int* term) {
+  MomentLossPoints chunk;
+  for (int q = 0; q < kMomentLossPoints; ++q) {
+    chunk.point[q] = q < count ? target_points[2 * (first + q)] : 0;
+    chunk.mask[q] = q < count ? target_points[2 * (first + q) + 1] : 0;
+    chunk.term[q] = *term;
+    *term += __builtin_popcount((unsigned)chunk.mask[q]);
+  }
+  return chunk;
+}
+
+// Between lynx_profile_begin and _end every launch of the two entries is one more entry of lynx_profile_launches, in launch order.
+struct ProfiledLaunch {
+  lynx_ctx* ctx;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  hipError_t begin() {
+    if (!ctx->profiling) return hipSuccess;
+    if (const hipError_t e = hipEventCreateWithFlags(&e0, timing_event_flags(ctx))) return e;
+    return hipEventCreateWithFlags(&e1, timing_event_flags(ctx));
+  }
+  void end() {
+    if (ctx->profiling) ctx->prof_events.emplace_back(e0, e1);
+  }
+};
+
+static unsigned moment_loss_blocks(int64_t batch, int count) {
+  return (unsigned)((batch * count + kMomentLossThreads - 1) / kMomentLossThreads);
+}
+
+int lynx_moments_along_loss(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const double* d_records,
+                            const void* d_mu_trace, const void* d_cov_trace, const void* d_energy_trace, int32_t ddof,
+                            int32_t n_target_points, const int32_t* target_points, const double* d_rows, int64_t row_stride,
+                            double* d_values, double* d_point_loss, double* d_loss) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!d_values || !d_point_loss || !d_loss) return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: bad argument");
+  int n_terms = 0, masks = 0;
+  if (const int rc = moment_loss_arguments(ctx, dtype, batch, n_points, d_records, d_mu_trace, d_cov_trace, d_energy_trace, ddof,
+                                           n_target_points, target_points, d_rows, row_stride, &n_terms, &masks))
+    return rc;
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_values, (size_t)batch * n_terms * sizeof(double)},
+                                        {d_point_loss, (size_t)batch * n_target_points * sizeof(double)},
+                                        {d_loss, (size_t)batch * sizeof(double)}});
+  int term = 0;
+  for (int32_t first = 0; first < n_target_points; first += kMomentLossPoints) {
+    const int count = std::min<int32_t>(kMomentLossPoints, n_target_points - first);
+    const MomentLossPoints chunk = moment_loss_chunk(target_points, first, count, &term);
+    ProfiledLaunch stamp{ctx};
+    HIP_TRY(ctx, stamp.begin());
+    with_dtype(dtype, [&](auto zero) {
+      using T = decltype(zero);
+      const auto launch = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3(moment_loss_blocks(batch, count)), dim3(kMomentLossThreads), 0u, ctx->stream, stamp.e0,
+                              stamp.e1, 0u, d_records, (const T*)d_mu_trace, (const T*)d_cov_trace, (const T*)d_energy_trace, batch,
+                              (int)n_points, (int)ddof, chunk, (int)first, count, (int)n_target_points, n_terms, d_rows, row_stride,
+                              d_values, d_point_loss);
+      };
+      if (d_records) launch(k_moment_loss_fwd<T, true>);
+      else launch(k_moment_loss_fwd<T, false>);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    stamp.end();
+  }
+  ProfiledLaunch stamp{ctx};
+  HIP_TRY(ctx, stamp.begin());
+  hipExtLaunchKernelGGL(k_moment_loss_finish, dim3((unsigned)((batch + kMomentLossThreads - 1) / kMomentLossThreads)),
+                        dim3(kMomentLossThreads), 0u, ctx->stream, stamp.e0, stamp.e1, 0u, (const double*)d_point_loss, batch,
+                        (int)n_target_points, d_loss);
+  HIP_TRY(ctx, hipGetLastError());
+  stamp.end();
+  return LYNX_OK;
+}
+
+int lynx_moments_along_loss_backward(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const double* d_records,
+                                     const void* d_mu_trace, const void* d_cov_trace, const void* d_energy_trace, int32_t ddof,
+                                     int32_t n_target_points, const int32_t* target_points, const double* d_rows,
+                                     int64_t row_stride, const double* d_loss_bar, double* d_grad_trace, void* d_mu_bar,
+                                     void* d_cov_bar, void* d_energy_bar) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!d_loss_bar) return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: bad argument");
+  int n_terms = 0, masks = 0;
+  if (const int rc = moment_loss_arguments(ctx, dtype, batch, n_points, d_records, d_mu_trace, d_cov_trace, d_energy_trace, ddof,
+                                           n_target_points, target_points, d_rows, row_stride, &n_terms, &masks))
+    return rc;
+  if (d_records ? (!d_grad_trace || d_mu_bar || d_cov_bar) : (d_grad_trace || !d_mu_bar || !d_cov_bar))
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: the cotangents have the form of the states, records or mu and cov");
+  if ((masks & kMomentLossEnergy) && !d_energy_bar)
+    return fail(ctx, LYNX_ERR_INVALID, "moment loss along the trace: a term that depends on the energy needs the energy's cotangents");
+  const size_t es = dtype_size(dtype), points = (size_t)batch * n_points;
+  LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_grad_trace, points * LYNX_MOMENT_STRIDE * sizeof(double)},
+                                        {d_mu_bar, points * 7 * es},
+                                        {d_cov_bar, points * 49 * es},
+                                        {d_energy_bar, points * es}});
+  int term = 0;
+  for (int32_t first = 0; first < n_target_points; first += kMomentLossPoints) {
+    const int count = std::min<int32_t>(kMomentLossPoints, n_target_points - first);
+    const MomentLossPoints chunk = moment_loss_chunk(target_points, first, count, &term);
+    ProfiledLaunch stamp{ctx};
+    HIP_TRY(ctx, stamp.begin());
+    with_dtype(dtype, [&](auto zero) {
+      using T = decltype(zero);
+      const auto launch = [&](auto kernel) {
+        hipExtLaunchKernelGGL(kernel, dim3(moment_loss_blocks(batch, count)), dim3(kMomentLossThreads), 0u, ctx->stream, stamp.e0,
+                              stamp.e1, 0u, d_records, (const T*)d_mu_trace, (const T*)d_cov_trace, (const T*)d_energy_trace, batch,
+                              (int)n_points, (int)ddof, chunk, count, d_rows, row_stride, d_loss_bar, d_grad_trace, (T*)d_mu_bar,
+                              (T*)d_cov_bar, (T*)d_energy_bar);
+      };
+      if (d_records) launch(k_moment_loss_bwd<T, true>);
+      else launch(k_moment_loss_bwd<T, false>);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    stamp.end();
   }
   return LYNX_OK;
 }

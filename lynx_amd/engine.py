@@ -787,12 +787,13 @@ def _trace_parameters(*, owner, program: Program, lat, incoming, e_in, e_trace, 
 
 
 def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device: bool = False, losses=False, screens: bool = False,
-                trajectories=None):
+                trajectories=None, keep_energy: bool = False):
     """
     `Segment.track_along`: one launch sequence for the whole lattice (`lynx_track_particles_along` /
     `lynx_track_moments_along`).  The packed "every element its own step" lattice is cached on `owner` (its own
     LatticeCache: a parameter write between two calls rewrites that element's block only).  `keep_device`: the trace
-    keeps the device arrays the kernels wrote (`trace._device`) -- what the reverse pass of `grad.track_along_vjp` reads.
+    keeps the device arrays the kernels wrote (`trace._device`) -- what the reverse pass of `grad.track_along_vjp` reads;
+    `keep_energy`: among them the energies at every point, where the call wrote them (what the moment loss reads).
     `losses` (True or "particles"): active apertures are part of the trace (`lynx_track_particles_along_losses`).
     `screens`: active screens are part of the trace and make their images inside it (`lynx_track_particles_along_screens`,
     with the apertures if `losses`; `lynx_gaussian_images_along` on the moment trace of a ParameterBeam).
@@ -827,7 +828,7 @@ def track_along(owner, leaves, incoming, keep_outgoing: bool = True, keep_device
         trace, centre, device = _trace_parameters(**made, make_images=not points_only)
     trace.total_charge = incoming.total_charge
     if keep_device:
-        trace._device = device
+        trace._device = {**device, "energy": e_trace} if keep_energy else device
     for k, el in enumerate(leaves):  # an active BPM reads the beam that ENTERS it: point k (bpm.py:48-54)
         if getattr(el, "_fusable_observer", False):
             el.reading = np.stack([centre[..., k, 0], centre[..., k, 1]]).astype(dtype)

@@ -713,6 +713,113 @@ class ImageTargets:
         return dev
 
 
+# the properties a moment target may name, in the order of their codes: bit k of a point's mask in lynx_moments_along_loss
+MOMENT_PROPERTIES = (*("mu_" + c for c in _COORDINATES), *("sigma_" + c for c in _COORDINATES), "sigma_xxp", "sigma_yyp",
+                     "emittance_x", "emittance_y", "normalized_emittance_x", "normalized_emittance_y", "beta_x", "beta_y",
+                     "alpha_x", "alpha_y", "energy")
+_ENERGY_PROPERTIES = ("normalized_emittance_x", "normalized_emittance_y", "energy")  # what adds into the energy's cotangent
+
+
+class _MomentLayout:
+    """Where the moment targets lie in what is uploaded: `terms` [(point, name)] in (point, code) order, `points` [(point,
+    mask)], `first` the ordinal of each point's first term, the scalars between two samples' rows (`stride`, 0: one row set
+    shared by the batch) and the host rows (1 | B, T, 2) float64 of (target, weight)."""
+
+    def __init__(self, terms, stride, host):
+        self.terms, self.stride, self.host = terms, stride, host
+        self.points, self.first = [], []
+        for t, (point, name) in enumerate(terms):
+            if not self.points or self.points[-1][0] != point:
+                self.points.append([point, 0])
+                self.first.append(t)
+            self.points[-1][1] |= 1 << MOMENT_PROPERTIES.index(name)
+        self.energy = any(name in _ENERGY_PROPERTIES for _, name in terms)  # a term adds into the energy's cotangent
+        self.moments = any(name != "energy" for _, name in terms)  # a term adds into the moments' cotangents
+        self.arguments = (len(self.points), (C.c_int32 * (2 * len(self.points)))(*(v for pair in self.points for v in pair)))
+
+
+class MomentTargets:
+    """
+    Target values of beam properties at points of a trace, `{point: {property: target}}` -- a point is whatever
+    `trace.index_of` takes (an element's name: the point behind it; or a point index, negative from the end), a property one
+    of `MOMENT_PROPERTIES`, a target a scalar (one for the batch) or an array broadcastable to (*batch,).  `weights` has the
+    same nesting and the same shapes; a missing weight is 1.  Given to `track_along_vjp(..., moment_targets=)` the loss is
+
+        sum over the terms of weight (value - target)^2
+
+    with the terms ordered by (point index, the property's place in `MOMENT_PROPERTIES`): `terms`, the list of (point index,
+    name), once a layout exists.  The (target, weight) rows are uploaded ONCE, in the layout lynx_moments_along_loss reads,
+    and stay on the device: the same object serves every pass of a tuning loop.  All targets and weights scalars: one row set
+    shared by the batch.
+    """
+
+    def __init__(self, targets: dict, weights: dict | None = None):
+        for what, given in (("targets", targets), ("weights", {} if weights is None else weights)):
+            if not isinstance(given, dict) or not all(isinstance(named, dict) for named in given.values()):
+                raise TypeError(f"MomentTargets: {what} is a dict {{point: {{property: value}}}}, not {given!r}")
+            for named in given.values():
+                for name in named:
+                    if name not in MOMENT_PROPERTIES:
+                        raise KeyError(f"no cotangent rule for trace property {name!r}")
+        # (copies: the upload is made once)
+        self._given = [[(point, {name: np.array(value, dtype=np.float64) for name, value in named.items()}) for point, named in given.items()]
+                       for given in (targets, weights or {})]
+        if not any(named for _, named in self._given[0]):
+            raise ValueError("MomentTargets: no target is given")
+        self._remembered = None  # (what the layout depends on, the layout, the device array or None)
+
+    @property
+    def terms(self) -> list:
+        if self._remembered is None:
+            raise ValueError("MomentTargets: the terms are known once the targets have met a trace -- pass them to track_along_vjp")
+        return list(self._remembered[1].terms)
+
+    def _layout(self, names, batch_shape) -> _MomentLayout:
+        """The targets against the points of one trace (`names` of its elements) and one batch, refused by value; nothing
+        touches the GPU."""
+        from .trace import point_index
+
+        batch_shape = tuple(batch_shape)
+        key = (tuple(names), batch_shape)
+        if self._remembered is not None and self._remembered[0] == key:
+            return self._remembered[1]
+        B = int(np.prod(batch_shape, dtype=np.int64))
+        found = [{}, {}]  # (point, code) -> value, of the targets and of the weights
+        for what, given, values in (("target", self._given[0], found[0]), ("weight", self._given[1], found[1])):
+            for point, named in given:
+                k = point_index(names, point)
+                for name, value in named.items():
+                    if (k, MOMENT_PROPERTIES.index(name)) in values:
+                        raise ValueError(f"track_along_vjp: {name!r} at point {k} is given two {what}s")
+                    try:
+                        np.broadcast_to(value, batch_shape)
+                    except ValueError:
+                        raise ValueError(f"track_along_vjp: the {what} of {name!r} at point {k} has shape {value.shape}, which "
+                                         f"does not broadcast to the batch {batch_shape}") from None
+                    values[(k, MOMENT_PROPERTIES.index(name))] = value
+        for k, code in found[1]:
+            if (k, code) not in found[0]:
+                raise ValueError(f"track_along_vjp: a weight of {MOMENT_PROPERTIES[code]!r} at point {k}, which has no target")
+        order = sorted(found[0])
+        shared = all(value.ndim == 0 for values in found for value in values.values())
+        host = np.ones((1 if shared else B, len(order), 2))
+        for column, values in enumerate(found):
+            for t, term in enumerate(order):
+                if term in values:
+                    host[:, t, column] = values[term] if shared else np.broadcast_to(values[term], batch_shape).reshape(B)
+        layout = _MomentLayout([(k, MOMENT_PROPERTIES[code]) for k, code in order], 0 if shared else 2 * len(order), host)
+        self._remembered = (key, layout, None)
+        return layout
+
+    def _device(self, rt, layout):
+        key, remembered, dev = self._remembered
+        assert remembered is layout
+        if dev is None:
+            dev = rt.to_device(layout.host)
+            self._remembered = (key, layout, dev)
+        return dev
+
+
 class TrackAlongVJP:
     """
     Vector-Jacobian product of `Segment.track_along`: gradients of any function of the beam moments and the energy at
@@ -732,10 +839,14 @@ class TrackAlongVJP:
     point given to every particle at that point; at most 64 leaf elements, `wrt_particles=True` in the call.
     """
 
-    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False, cavities=False, image_targets=None):
+    def __init__(self, segment, beam, trajectories=None, losses=False, screens=False, cavities=False, image_targets=None,
+                 moment_targets=None):
         targets = image_targets is not None
         if targets and not isinstance(image_targets, (dict, ImageTargets)):
             raise TypeError(f"track_along_vjp: image_targets is a dict {{screen: target image}} or an ImageTargets, not {type(image_targets)}")
+        if moment_targets is not None and not isinstance(moment_targets, (dict, MomentTargets)):
+            raise TypeError("track_along_vjp: moment_targets is a dict {point: {property: target}} or a MomentTargets, not "
+                            f"{type(moment_targets)}")
         # the mode, decided once: "moments" (a ParameterBeam's sweep), "particles", "trajectories", "survivors" or "kicks"
         # (image targets need the screens in the trace's plan, and a ParticleBeam is refused as `screens=True` refuses it)
         self.mode, self.program, self.leaves, self.chosen, self._cavity = _trace_mode(
@@ -746,15 +857,116 @@ class TrackAlongVJP:
         if targets:  # every refusal by value, before anything touches the GPU
             self._targets = image_targets if isinstance(image_targets, ImageTargets) else ImageTargets(image_targets)
             layout = self._targets._layout(self.program, self.leaves, beam)
+        self._moment_targets = self._moment_layout = self._moment_loss = None
+        if moment_targets is not None:
+            self._moment_targets = moment_targets if isinstance(moment_targets, MomentTargets) else MomentTargets(moment_targets)
+            self._moment_layout = self._moment_targets._layout([el.name for el in self.leaves], beam.batch_shape)
         # (a keyword is given only where it says something; apertures are identity steps of a ParameterBeam's trace; with
         # image targets alone the screens are points of the trace and no image is made)
         plain = {**({"losses": True} if losses and self.mode == "moments" else {}),
                  **({"screens": True} if screens else {"screens": "points"} if targets else {})}
         options = {"survivors": {"losses": "particles"}, "trajectories": {"trajectories": self.chosen}}.get(self.mode, plain)
+        if self._moment_layout is not None:  # (the moment loss reads the energies where the trace wrote them)
+            options = {**options, "keep_energy": True}
         self.trace = engine.track_along(segment, self.leaves, beam, keep_outgoing=True, keep_device=True, **options)
         self._set_records = self._survivor_set_records() if self.mode == "survivors" else None
         if targets:
             self._image_loss = self._evaluate_image_loss(layout)
+        if self._moment_layout is not None:
+            self._moment_loss = self._evaluate_moment_loss(self._moment_layout)
+
+    def _moment_loss_arguments(self, rt, layout):
+        """What lynx_moments_along_loss and its reverse half are given alike: sizes, the states of the trace, the terms, the rows."""
+        from . import config
+
+        beam, states = self.beam, self.trace._device
+        B, P = int(np.prod(beam.batch_shape, dtype=np.int64)), self.trace.num_points
+        return (rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states.get("records")), _p(states.get("mu")), _p(states.get("cov")),
+                _p(states["energy"]), int(config.std_ddof), *layout.arguments, _p(self._moment_targets._device(rt, layout)), layout.stride)
+
+    def _evaluate_moment_loss(self, layout):
+        """
+        The refusals that need the trace, then lynx_moments_along_loss right behind it, on its stream: the value of every term
+        [B][T], the loss per target point [B][Q] and per sample [B], float64, all kept on the device -> (values, per point, loss).
+        """
+        if layout.moments and self._cavity is not None:  # (exactly where a moment cotangent is refused)
+            _refuse_moments(self._cavity)
+        if self.mode == "survivors":
+            B, P = int(np.prod(self.beam.batch_shape, dtype=np.int64)), self.trace.num_points
+            dead = np.asarray(self.trace.num_survivors).reshape(B, P) == 0
+            for point, name in layout.terms:
+                if name != "energy" and dead[:, point].any():  # (the energy is there at every point)
+                    self._refuse_cotangent_on_nobody(np.arange(P) == point, dead, repr(name))
+        rt = get_runtime()
+        B, T, Q = int(np.prod(self.beam.batch_shape, dtype=np.int64)), len(layout.terms), len(layout.points)
+        values, per_point, loss = rt.empty((B, T), np.float64), rt.empty((B, Q), np.float64), rt.empty((B,), np.float64)
+        rt.check(rt.lib.lynx_moments_along_loss(*self._moment_loss_arguments(rt, layout), _p(values), _p(per_point), _p(loss)))
+        return values, per_point, loss
+
+    def _need_moment_loss(self, what):
+        if self._moment_loss is None:
+            raise ValueError(f"track_along_vjp: {what} needs moment targets -- pass moment_targets= to track_along_vjp")
+        return self._moment_loss
+
+    @property
+    def moment_values(self) -> np.ndarray:
+        """(*batch, T) float64: the value of every term of the moment loss, in the order of `MomentTargets.terms`."""
+        values = self._need_moment_loss("moment_values")[0]
+        return values.numpy().reshape(*self.beam.batch_shape, len(self._moment_layout.terms))
+
+    @property
+    def moment_loss(self) -> np.ndarray:
+        """(*batch,) float64: the sum over the terms, in their order, of weight (value - target)^2."""
+        return self._need_moment_loss("moment_loss")[2].numpy().reshape(self.beam.batch_shape)
+
+    def moment_loss_of(self, point) -> np.ndarray:
+        """The part of `moment_loss` that one point's terms make: by whatever `trace.index_of` takes."""
+        per_point, layout = self._need_moment_loss("moment_loss_of")[1], self._moment_layout
+        k = self.trace.index_of(point)
+        found = [q for q, (at, _) in enumerate(layout.points) if at == k]
+        if not found:
+            raise KeyError(f"point {k} has no target in this call's moment_targets (targets at {[at for at, _ in layout.points]})")
+        return np.ascontiguousarray(per_point.numpy().reshape(*self.beam.batch_shape, len(layout.points))[..., found[0]])
+
+    def _moment_loss_cotangents(self, moment_loss_bar) -> np.ndarray:
+        """`moment_loss_bar` as (B,) float64; refused by value."""
+        if self._moment_loss is None:
+            raise ValueError("track_along_vjp: moment_loss_bar needs the moment loss of the forward pass -- pass moment_targets= "
+                             "to track_along_vjp")
+        w, batch_shape = np.asarray(moment_loss_bar, dtype=np.float64), tuple(self.beam.batch_shape)
+        try:
+            return np.ascontiguousarray(np.broadcast_to(w, batch_shape)).reshape(-1)
+        except ValueError:
+            raise ValueError(f"track_along_vjp: moment_loss_bar has shape {w.shape}, which does not broadcast to the batch "
+                             f"{batch_shape}") from None
+
+    # what the launches below share: a cotangent buffer is uploaded where the host made one and zero-filled on the device where
+    # the moment loss alone adds into it; then the loss's reverse half, in front of the sweep on the same stream
+    def _zeros(self, rt, shape, dtype):
+        zeros = rt.empty(shape, dtype)
+        rt.check(rt.lib.lynx_buf_memset(rt.ctx, _p(zeros), 0, int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize))
+        return zeros
+
+    def _points_shape(self, *tail):
+        return (int(np.prod(self.beam.batch_shape, dtype=np.int64)), self.trace.num_points, *tail)
+
+    def _record_buffer(self, rt, mb, cb):
+        if mb is None:
+            return self._zeros(rt, self._points_shape(_ffi.MOMENT_STRIDE), np.float64)
+        return rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+
+    def _moment_buffers(self, rt, mb, cb):
+        dtype = self.beam.dtype
+        if mb is None:
+            return self._zeros(rt, self._points_shape(7), dtype), self._zeros(rt, self._points_shape(7, 7), dtype)
+        return rt.to_device(mb.astype(dtype)), rt.to_device(cb.astype(dtype))
+
+    def _add_moment_loss(self, rt, ml, eb_dev, rec_dev=None, mb_dev=None, cb_dev=None):
+        if ml is None:
+            return
+        ml_dev = rt.to_device(ml)
+        rt.check(rt.lib.lynx_moments_along_loss_backward(
+            *self._moment_loss_arguments(rt, self._moment_layout), _p(ml_dev), _p(rec_dev), _p(mb_dev), _p(cb_dev), _p(eb_dev)))
 
     def _evaluate_image_loss(self, layout):
         """
@@ -943,7 +1155,8 @@ class TrackAlongVJP:
         return flat
 
     def __call__(self, mu_bar=None, cov_bar=None, energy_bar=None, readings: dict | None = None, trajectories_bar=None,
-                 screen_images_bar: dict | None = None, wrt_particles: bool = False, image_loss_bar=None, **properties) -> Gradients:
+                 screen_images_bar: dict | None = None, wrt_particles: bool = False, image_loss_bar=None, moment_loss_bar=None,
+                 **properties) -> Gradients:
         """
         `mu_bar` (*batch, P, 6|7), `cov_bar` (*batch, P, 6|7, 6|7) entry by entry, `energy_bar` (*batch, P): cotangents at
         every point; `properties`: cotangents (*batch, P) of any moment property of the trace and of `energy`;
@@ -958,6 +1171,10 @@ class TrackAlongVJP:
         `image_loss_bar` (`image_targets=` of `track_along_vjp`): cotangents of `image_loss` -- a scalar or (*batch,) for every
         screen with a target, or `{screen: bar}`; lynx_gaussian_images_along_mse_backward scales the sums the forward pass left
         on the device and adds them into the mu and cov cotangents at the screens' points, `g[screen]["misalignment"]` as above.
+        `moment_loss_bar` (`moment_targets=` of `track_along_vjp`): the cotangent of `moment_loss`, a scalar or (*batch,);
+        lynx_moments_along_loss_backward forms every term's bar from the states on the device and adds it into the cotangents
+        the sweep reads.  Alone -- no other cotangent of a moment or of the energy in the call -- nothing with a point axis is
+        made on the host: those cotangents are zero-filled on the device and the (*batch,) bars are the only upload.
         `wrt_particles=True` (`cavities=True` of `track_along_vjp`, a ParticleBeam): `Gradients.particles` (*batch, N, 7), the
         gradient w.r.t. every incoming particle, device-resident.
         """
@@ -968,26 +1185,32 @@ class TrackAlongVJP:
         lb = None if image_loss_bar is None else self._image_loss_cotangents(image_loss_bar)
         if lb is not None and not any(self._image_loss[2]):  # (no screen has a target: nothing to launch)
             lb = None
-        wb = None  # (a trace with trajectories and no cotangent on them: zeros)
-        if trajectories_bar is not None or self.chosen is not None:
-            wb = self._trajectory_cotangents(np.zeros(7) if trajectories_bar is None else trajectories_bar)
+        ml = None if moment_loss_bar is None else self._moment_loss_cotangents(moment_loss_bar)
         with_moments = mu_bar is not None or cov_bar is not None or bool(readings) or any(name != "energy" for name in properties)
+        # the moment loss as the call's only cotangent of a moment or of the energy: nothing with a point axis is made here
+        alone = ml is not None and not with_moments and energy_bar is None and not properties
+        wb = None  # (a trace with trajectories and no cotangent on them: zeros -- made on the device where the moment loss is alone)
+        if trajectories_bar is not None or (self.chosen is not None and not alone):
+            wb = self._trajectory_cotangents(np.zeros(7) if trajectories_bar is None else trajectories_bar)
         if with_moments and self._cavity is not None:
             _refuse_moments(self._cavity)
-        mb, cb, eb = self._cotangents(mu_bar, cov_bar, energy_bar, readings, properties)
+        mb, cb, eb = (None, None, None) if alone else self._cotangents(mu_bar, cov_bar, energy_bar, readings, properties)
+        with_moments = with_moments or (ml is not None and self._moment_layout.moments)
         rt = get_runtime()
         sweep = _Sweep(rt, engine.trace_cache(self.segment), self.program, self.beam)
         # (an upload is named until its call has been enqueued, so that it stays allocated; no energy cotangent: no upload)
-        eb_dev = rt.to_device(eb.astype(self.beam.dtype)) if np.any(eb) else None
+        eb_dev = rt.to_device(eb.astype(self.beam.dtype)) if eb is not None and np.any(eb) else None
+        if eb_dev is None and ml is not None and self._moment_layout.energy:
+            eb_dev = self._zeros(rt, self._points_shape(), self.beam.dtype)
         launch = getattr(self, "_launch_" + self.mode)  # (_launch_moments, _particles, _trajectories, _survivors, _kicks)
-        results = launch(rt, sweep, mb, cb, eb_dev, wi=wi, lb=lb, wb=wb, with_moments=with_moments, wrt_particles=wrt_particles)
+        results = launch(rt, sweep, mb, cb, eb_dev, wi=wi, lb=lb, wb=wb, ml=ml, with_moments=with_moments, wrt_particles=wrt_particles)
         return Gradients(self.program, self.beam, sweep.g_par, sweep.g_en, **results)
 
     # one method per mode, called alike (each names what it uses): the library call or calls -> `Gradients`' optional results
-    def _launch_moments(self, rt, sweep, mb, cb, eb_dev, wi, lb, **_):
+    def _launch_moments(self, rt, sweep, mb, cb, eb_dev, wi, lb, ml, **_):
         beam, states = self.beam, self.trace._device
-        B, P = mb.shape[:2]
-        mb_dev, cb_dev = rt.to_device(mb.astype(beam.dtype)), rt.to_device(cb.astype(beam.dtype))
+        B, P = self._points_shape()
+        mb_dev, cb_dev = self._moment_buffers(rt, mb, cb)
         shifts = loss_shifts = None
         if wi is not None:  # the images' cotangents go into mb_dev, cb_dev at the screens' points, on the same stream
             shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
@@ -1003,6 +1226,7 @@ class TrackAlongVJP:
             rt.check(rt.lib.lynx_gaussian_images_along_mse_backward(
                 rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["cov"]), shots["count"], shots["rows"], _p(self._image_loss[1]),
                 _p(lb_dev), _p(mb_dev), _p(cb_dev), _p(loss_shifts)))
+        self._add_moment_loss(rt, ml, eb_dev, mb_dev=mb_dev, cb_dev=cb_dev)
         rt.check(rt.lib.lynx_track_moments_along_backward(
             rt.ctx, sweep.lat.handle, _p(sweep.e_in), _p(states["mu"]), _p(states["cov"]), _p(mb_dev), _p(cb_dev), _p(eb_dev),
             _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
@@ -1013,19 +1237,23 @@ class TrackAlongVJP:
         with_screens = self._screens or self._targets is not None
         return dict(moments=(sweep.g_mu, sweep.g_cov), screens=([el for _, el in self.program.screens], shifts) if with_screens else None)
 
-    def _launch_particles(self, rt, sweep, mb, cb, eb_dev, **_):
-        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+    def _launch_particles(self, rt, sweep, mb, cb, eb_dev, ml, **_):
+        rec_dev = self._record_buffer(rt, mb, cb)
+        self._add_moment_loss(rt, ml, eb_dev, rec_dev=rec_dev)
         rt.check(rt.lib.lynx_track_particles_along_backward(
             rt.ctx, sweep.lat.handle, self.beam.num_particles, _p(sweep.e_in), _p(self.trace._device["records"]), _p(rec_dev),
             _p(eb_dev), _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
         return dict(moments=(sweep.g_mu, sweep.g_cov))
 
-    def _launch_trajectories(self, rt, sweep, mb, cb, eb_dev, wb, with_moments, **_):
+    def _launch_trajectories(self, rt, sweep, mb, cb, eb_dev, wb, ml, with_moments, **_):
         beam, states, K = self.beam, self.trace._device, len(self.chosen)
-        # without a moment cotangent the moment path does not run: no records in, no g.mu and g.cov out
-        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb)) if with_moments else None
+        # without a moment cotangent the moment path does not run: no records in, no g.mu and g.cov out (a moment loss of
+        # energies alone still adds into a record buffer, which the sweep is then not handed)
+        rec_dev = self._record_buffer(rt, mb if with_moments else None, cb) if with_moments or ml is not None else None
+        self._add_moment_loss(rt, ml, eb_dev, rec_dev=rec_dev)
+        rec_dev = rec_dev if with_moments else None
         g_mu, g_cov = (sweep.g_mu, sweep.g_cov) if with_moments else (None, None)
-        wb_dev = rt.to_device(wb)
+        wb_dev = self._zeros(rt, self._points_shape(K, 7), np.float64) if wb is None else rt.to_device(wb)
         g_chosen = rt.empty((*beam.batch_shape, K, 7), beam.dtype)
         rt.check(rt.lib.lynx_track_particles_along_backward_trajectories(
             rt.ctx, sweep.lat.handle, beam.num_particles, _p(sweep.e_in), _p(states["records"]) if with_moments else None,
@@ -1033,9 +1261,10 @@ class TrackAlongVJP:
             _p(states["trajectories"]), _p(wb_dev), _p(g_chosen)))
         return dict(moments=(g_mu, g_cov) if with_moments else None, chosen=g_chosen)
 
-    def _launch_kicks(self, rt, sweep, mb, cb, eb_dev, wrt_particles, **_):
+    def _launch_kicks(self, rt, sweep, mb, cb, eb_dev, ml, wrt_particles, **_):
         beam = self.beam
-        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+        rec_dev = self._record_buffer(rt, mb, cb)
+        self._add_moment_loss(rt, ml, eb_dev, rec_dev=rec_dev)
         g_p = rt.empty((*beam.batch_shape, beam.num_particles, 7), beam.dtype) if wrt_particles else None
         rt.check(rt.lib.lynx_track_particles_along_backward_cavities(
             rt.ctx, sweep.lat.handle, beam.num_particles, _p(sweep.e_in), _p(beam._particles.device(rt)),
@@ -1043,8 +1272,9 @@ class TrackAlongVJP:
             _p(sweep.g_par), _p(sweep.g_en), _p(g_p)))
         return dict(particles=g_p, moments=Gradients.NO_INCOMING_MOMENTS)
 
-    def _launch_survivors(self, rt, sweep, mb, cb, eb_dev, **_):
-        rec_dev = rt.to_device(_record_cotangents(mb.shape[:-1], mb, cb))
+    def _launch_survivors(self, rt, sweep, mb, cb, eb_dev, ml, **_):
+        rec_dev = self._record_buffer(rt, mb, cb)
+        self._add_moment_loss(rt, ml, eb_dev, rec_dev=rec_dev)
         A = len(self.program.apertures)
         at = (C.c_int32 * A)(*[step for step, _, _ in self.program.apertures])
         rt.check(rt.lib.lynx_track_particles_along_backward_losses(
@@ -1054,7 +1284,8 @@ class TrackAlongVJP:
         return dict(moments=Gradients.NO_INCOMING_MOMENTS, zeros=[(el, ("x_max", "y_max")) for _, el, _ in self.program.apertures])
 
 
-def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False, cavities=False, image_targets=None):
+def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=False, cavities=False, image_targets=None,
+                    moment_targets=None):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `vjp.trace`; its states stay on the device); returns the
     callable vector-Jacobian product of the moments and energies at every point:
@@ -1126,6 +1357,30 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
     without a target gets misalignment gradient 0.  `screens=True` may be given as well: the images are made as above, and
     `screen_images_bar` and `image_loss_bar` may both be used in one call.  Refusals are those of `screens=True`.
 
+    `moment_targets=` (both beam classes, every mode above): the loss nearly every tuning loop writes, a weighted sum of squared
+    distances of named beam properties at named points to target values, evaluated on the device from the states the trace left
+    there -- no cotangent array with a point axis is made on the host or uploaded:
+
+        targets = lynx_amd.grad.MomentTargets({"M1": {"beta_x": 4.0, "beta_y": 2.0}, -1: {"alpha_x": 0.0}},
+                                              weights={"M1": {"beta_x": 0.25}})      # uploaded once, reusable over a loop
+        vjp = lynx_amd.grad.track_along_vjp(segment, beam, moment_targets=targets)   # (or pass the dict of targets)
+        vjp.moment_loss                          # (*batch,) float64: sum of weight (value - target)^2 over `targets.terms`
+        vjp.moment_values, vjp.moment_loss_of("M1")                                  # (*batch, T); one point's part
+        g = vjp(moment_loss_bar=1.0)             # a scalar or (*batch,), alone or with any cotangent above
+        g[segment.Q1]["k1"], g.energy
+
+    A point is whatever `trace.index_of` takes, a property one of `MOMENT_PROPERTIES` (the 23 names `trace_property_cotangents`
+    has a rule for), a target or weight a scalar or broadcastable to (*batch,); a missing weight is 1.  The value of a term is
+    the float64 expression that `trace_property_cotangents` differentiates, formed from the device states -- NOT the trace's
+    property rounded to the beam's dtype: of a ParticleBeam's record sigma_c^2 = rec[cov_cc] n / (n - ddof) with the record's
+    own count n and `config.std_ddof` (a lone survivor's variance is the record's, not the 0 the trace shows), of a
+    ParameterBeam sigma_c^2 = max(cov_cc, 1e-20) with derivative 0 where clamped; emittance = sqrt(max(sigma^2 sigma_p^2 -
+    sigma_xxp^2, tiny)), derivative 0 where clamped, beta = sigma^2 / emittance, alpha = -sigma_xxp / emittance,
+    normalized_emittance = emittance gamma sqrt(1 - 1 / gamma^2) (lynx_moments_along_loss, right behind the trace on its stream;
+    lynx_moments_along_loss_backward in front of the sweep).  A target other than `energy` is refused where a moment cotangent is:
+    on a ParticleBeam behind an active cavity without `cavities=True`, and with `losses=True` on a point no particle of some
+    sample reaches.  May be given together with `image_targets=` and `screens=`.
+
     `cavities=True` (a ParticleBeam): active cavities are no obstacle to the moment cotangents.  Behind a cavity's kick the
     moments are not a function of the moments in front of it, so the reverse call takes a second pass over the particles
     (lynx_track_particles_along_backward_cavities: the sweep of `track_vjp`, which parks every 4th state and walks back
@@ -1141,7 +1396,7 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
     `losses=True`.  A lattice without a cavity is accepted (the same gradients by another way), and with a ParameterBeam
     `cavities=True` is the plain call.
     """
-    return TrackAlongVJP(segment, beam, trajectories, losses, screens, cavities, image_targets)
+    return TrackAlongVJP(segment, beam, trajectories, losses, screens, cavities, image_targets, moment_targets)
 
 
 def track_vjp(segment, beam):

@@ -60,6 +60,18 @@ def screen_ordinal(names, screens, name_or_index) -> int:
     return list(screens).index(k)
 
 
+def point_index(names, name_or_index) -> int:
+    """`BeamTrace.index_of` on the element names alone (there are len(names) + 1 points): what is known before a trace exists."""
+    if isinstance(name_or_index, str):
+        if name_or_index not in names:
+            raise KeyError(f"no element named {name_or_index!r} in this trace")
+        return list(names).index(name_or_index) + 1
+    k, points = int(name_or_index), len(names) + 1
+    if not -points <= k < points:
+        raise IndexError(f"point {k} of a trace of {points}")
+    return k % points
+
+
 class BeamTrace(Beam):
     """
     :ivar s: position of every point, (P, *batch) -- cumulative `length`, per sample because lengths are batched; a
@@ -173,14 +185,7 @@ class BeamTrace(Beam):
 
     def index_of(self, name_or_index) -> int:
         """Point index: an int as it is (negative from the end); a name -> the point behind the first element so named."""
-        if isinstance(name_or_index, str):
-            if name_or_index not in self.names:
-                raise KeyError(f"no element named {name_or_index!r} in this trace")
-            return self.names.index(name_or_index) + 1
-        k = int(name_or_index)
-        if not -self.num_points <= k < self.num_points:
-            raise IndexError(f"point {k} of a trace of {self.num_points}")
-        return k % self.num_points
+        return point_index(self.names, name_or_index)
 
     def image_at(self, name_or_index) -> np.ndarray:
         """
