@@ -325,6 +325,44 @@ int lynx_track_particles_along_trajectories(lynx_ctx* ctx, lynx_lattice* lat, in
 int lynx_track_moments_along(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                              const void* d_cov_in, void* d_mu_trace, void* d_cov_trace, void* d_energy_trace);
 
+/* Forward-mode pass of lynx_track_moments_along: the TANGENTS of the moments at EVERY point of the lattice along D
+ * directions in parameter space -- few parameters, every output: the orbit response matrix (d centroid at every BPM /
+ * d angle of every corrector), the Jacobian of the residuals of a least-squares matching, the curve d beta_x(s) / d k1.
+ * The program is the one the trace was made with (every element a step of its own, LYNX_STEP_FLAG_RAW; no limit on the
+ * number of elements beyond the trace's own); P = n_steps + 1.  For every direction
+ *   mu_dot[0] = 0, C_dot[0] = 0;   mu_dot[k] = M mu_dot[k-1] + Mdot mu[k-1],   C_dot[k] = M C_dot[k-1] M^T + X + X^T,
+ *   X = Mdot C[k-1] M^T,   Mdot = sum over the direction's entries at element k - 1 of weight . dM/d(parameter or energy)
+ * with mu[k], C[k] read from the forward trace; a step without an entry of the direction takes no Mdot term at all.
+ *   d_mu_trace [B][P][7], d_cov_trace [B][P][7][7]   what lynx_track_moments_along wrote (lattice dtype)
+ *   the directions, HOST arrays in CSR form: direction d has the entries dir_start[d] .. dir_start[d + 1] - 1
+ *     dir_start [n_directions + 1] (dir_start[0] = 0, dir_start[n_directions] = n_entries), dir_leaf [n_entries] the
+ *     element, dir_row [n_entries] its parameter row 0 .. 7 (the order of d_grad_params) or 8 for the energy at that
+ *     step, dir_weight [n_entries] float64.  Several entries of one direction: an element that occurs several times, a
+ *     vector parameter's rows, RBend's angle (which feeds e1 and e2 with weight 1/2), the incoming energy (row 8 at every
+ *     leaf, weight 1); two entries on one leaf are added.  A direction without entries gives zeros.
+ *   d_mu_dot [B][D][P][7], d_cov_dot [B][D][P][7][7]   float64 for every lattice dtype; entry 6 of mu_dot and row and
+ *     column 6 of cov_dot are exact zeros (the 7th coordinate is the constant 1)
+ * The derivative conventions are those of the reverse passes (dual evaluation of the map builders).  The sweep's own
+ * arithmetic is float64; fixed order, no atomics: the same call returns the same bits.  LYNX_ERR_INVALID before
+ * anything is launched (lynx_last_error starts with "beam trace tangents: ") for a null required argument,
+ * n_directions < 1, n_entries < 0, a dir_start that does not run from 0 to n_entries without decreasing, an entry whose
+ * leaf or row is out of range, a row the element's kind does not have, an empty program, a program that is not the
+ * trace's, and a program with a cavity step: behind a cavity the energy, and with it every later map, depends on the
+ * cavity's parameters, and a ParticleBeam's moments are not closed under its kick -- left for a later version.       */
+int lynx_track_moments_along_forward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                                     const void* d_cov_trace, const int32_t* dir_start, const int32_t* dir_leaf,
+                                     const int32_t* dir_row, const double* dir_weight, int32_t n_directions, int32_t n_entries,
+                                     double* d_mu_dot, double* d_cov_dot);
+
+/* ... of lynx_track_particles_along: the mean and the biased covariance of the particles obey the same recursion
+ * exactly, so the records become the states of the sweep above, on the device, and no pass over the particles is made.
+ *   d_trace_fwd [B][P][36] float64   what lynx_track_particles_along wrote
+ * Directions, outputs and refusals as above, and LYNX_ERR_INVALID for n_particles < 1.                               */
+int lynx_track_particles_along_forward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                       const double* d_trace_fwd, const int32_t* dir_start, const int32_t* dir_leaf,
+                                       const int32_t* dir_row, const double* dir_weight, int32_t n_directions, int32_t n_entries,
+                                       double* d_mu_dot, double* d_cov_dot);
+
 /* Reverse pass of lynx_track_moments_along: gradient of a scalar function of the moments and the energy at EVERY point
  * of the lattice (the losses written along a beamline: Twiss values at markers, beam sizes below an aperture, the
  * centroid at every BPM) with respect to every element parameter, the incoming energy and the incoming mu and cov.

@@ -24,6 +24,7 @@
 #include "lynx_grad_units.hpp"
 #include "lynx_trace.hpp"
 #include "lynx_trace_grad.hpp"
+#include "lynx_trace_jvp.hpp"
 #include "lynx_moment_loss.hpp"
 
 using namespace lynx;
@@ -259,6 +260,7 @@ struct lynx_ctx {
     Scratch steps[kTableSlots + 3];  // the ring of step tables, the reverse pass's own, the ParameterBeam lanes path's, the beam trace's
     Scratch trace[2];  // beam trace: the waves' slabs [B][waves][P][32] float64, the reference trajectory [B][P][8]
     Scratch trace_plan;  // ... with losses or screens: step codes and screen rows (TraceLosses.plan); lynx_ctx::trace_plan is what was uploaded last
+    Scratch trace_jvp;  // lynx_track_*_along_forward: the directions (TraceDirections; lynx_ctx::trace_dirs is what was uploaded last), the entries' weight . dM [B][n][49] float64, a ParticleBeam's states mu [B][P][7], C [B][P][49] float64
     Scratch image_grad;  // lynx_gaussian_images_along_backward: the workgroups' partial sums [B][chunks][6] float64, screen after screen
     Scratch image_loss;  // lynx_gaussian_images_along_mse: the workgroups' partial sums [B][chunks][7] float64 of one screen, reused screen after screen
     Scratch units[2 * kTableSlots];  // compact unit records of multi-step float32 programs (lynx_units.hpp) and their class-D extras, per table slot
@@ -271,6 +273,7 @@ struct lynx_ctx {
   static_assert(std::is_standard_layout<Scratch>::value && sizeof(ScratchSet) % sizeof(Scratch) == 0, "ScratchSet: Scratch members only");
   int32_t* d_spec_valid = nullptr;   // whether scratch.esteps holds (k_cavity_flags)
   std::vector<int64_t> trace_plan;
+  std::vector<int32_t> trace_dirs;   // the directions scratch.trace_jvp holds: dir_start | dir_leaf | dir_row | the weights' bits
   ncclComm_t comm = nullptr;
   int comm_ranks = 0;
   // The SIDE stream: what follows a streaming kernel without anything on this GPU waiting for it -- the reduction of
@@ -3063,6 +3066,176 @@ int lynx_track_particles_along_backward(lynx_ctx* ctx, lynx_lattice* lat, int64_
   return with_dtype(lat->dtype, [&](auto zero) {
     return particles_along_backward_t<decltype(zero)>(ctx, lat, d_energy_in, d_trace_fwd, d_grad_trace, d_energy_bar, d_grad_params,
                                                       d_grad_energy_in, d_grad_mean_in, d_grad_cov_in);
+  });
+}
+
+// ---- forward-mode pass of the beam trace: tangents of the moments at every point -------------
+
+// The directions of a forward-mode call as the host hands them over (CSR: dir_start [D + 1], the rest [n]).
+struct TraceDirectionList {
+  int32_t count, entries;
+  const int32_t *start, *leaf, *row;
+  const double* weight;
+};
+
+// Every refusal of the two forward-mode entry points about the lattice and the directions, before anything is launched.
+static int trace_forward_check(lynx_ctx* ctx, lynx_lattice* lat, const TraceDirectionList& dl) {
+  const std::string what = "beam trace tangents: ";
+  if (!dl.start || !dl.leaf || !dl.row || !dl.weight) return fail(ctx, LYNX_ERR_INVALID, what + "null argument");
+  if (dl.count < 1) return fail(ctx, LYNX_ERR_INVALID, what + "n_directions must be > 0");
+  if (dl.entries < 0) return fail(ctx, LYNX_ERR_INVALID, what + "n_entries must be >= 0");
+  if (lat->n_steps <= 0) return fail(ctx, LYNX_ERR_INVALID, what + "empty program");
+  if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, what + "bad batch");
+  for (int32_t s = 0; s < lat->n_steps; ++s) {
+    const lynx_step& st = lat->h_steps[s];
+    if (st.kind == LYNX_STEP_CAVITY)
+      return fail(ctx, LYNX_ERR_INVALID,
+                  what + "step " + std::to_string(s) + " is a cavity step (the energy behind it, and with it every later map, depends on "
+                         "its parameters, and the particles' moments are not closed under its kick)");
+    if (st.first != s || st.last != s + 1 || lat->n_elems != lat->n_steps)
+      return fail(ctx, LYNX_ERR_INVALID, what + "not the trace's program (every element a step of its own)");
+  }
+  if ((int64_t)lat->batch * (lat->n_steps + 1) > 0x7fffffffLL || (int64_t)lat->batch * dl.count > 0x7fffffffLL ||
+      ((int64_t)lat->batch * dl.entries + 63) / 64 > 0x7fffffffLL)
+    return fail(ctx, LYNX_ERR_INVALID, what + "batch x points, directions or entries too large for one launch");
+  if (dl.start[0] != 0 || dl.start[dl.count] != dl.entries)
+    return fail(ctx, LYNX_ERR_INVALID, what + "dir_start does not run from 0 to n_entries");
+  for (int32_t d = 0; d < dl.count; ++d)
+    if (dl.start[d + 1] < dl.start[d] || dl.start[d + 1] > dl.entries)
+      return fail(ctx, LYNX_ERR_INVALID, what + "dir_start decreases at direction " + std::to_string(d));
+  for (int32_t q = 0; q < dl.entries; ++q) {
+    const std::string entry = "entry " + std::to_string(q);
+    if (dl.leaf[q] < 0 || dl.leaf[q] >= lat->n_elems)
+      return fail(ctx, LYNX_ERR_INVALID, what + entry + ": leaf " + std::to_string(dl.leaf[q]) + " out of range");
+    if (dl.row[q] < 0 || dl.row[q] > kGradParams)
+      return fail(ctx, LYNX_ERR_INVALID, what + entry + ": row " + std::to_string(dl.row[q]) + " out of range");
+    const int kind = lat->h_elems[dl.leaf[q]].kind;
+    if (dl.row[q] != kGradParams && dl.row[q] >= bwd_kind_params(kind))  // (the energy: every kind, zero for one without parameters)
+      return fail(ctx, LYNX_ERR_INVALID,
+                  what + entry + ": an element of kind " + std::to_string(kind) + " has no parameter row " + std::to_string(dl.row[q]));
+  }
+  return LYNX_OK;
+}
+
+// Where a forward-mode call's scratch lies in scratch.trace_jvp: the directions, the entries' weight . dM, and (a
+// ParticleBeam) the states of the sweep.
+struct TraceForwardScratch {
+  TraceDirections dirs;
+  double *mdot, *mu, *cov;
+};
+
+// The directions on the device, the entries of each direction ordered by leaf (stable: entries on one leaf keep their
+// order) -- uploaded when they differ from what is there, like the trace's plan: the wait that upload needs is paid once
+// per set of directions, and a loop that asks for the same tangents again pays nothing.
+static int trace_forward_scratch(lynx_ctx* ctx, lynx_lattice* lat, const TraceDirectionList& dl, bool states, TraceForwardScratch* out) {
+  const int32_t D = dl.count, n = dl.entries;
+  const size_t ints = (size_t)D + 1 + 2 * (size_t)n, words = (ints + 1) / 2 * 2 + 2 * (size_t)n;  // (the weights: 8-aligned)
+  std::vector<int32_t> plan(words, 0);
+  int32_t* weights = plan.data() + (ints + 1) / 2 * 2;  // (two words each)
+  std::vector<int32_t> order(std::max(n, 1));
+  for (int32_t q = 0; q < n; ++q) order[q] = q;
+  for (int32_t d = 0; d < D; ++d)
+    std::stable_sort(order.begin() + dl.start[d], order.begin() + dl.start[d + 1],
+                     [&](int32_t a, int32_t b) { return dl.leaf[a] < dl.leaf[b]; });
+  for (int32_t d = 0; d <= D; ++d) plan[d] = dl.start[d];
+  for (int32_t q = 0; q < n; ++q) {
+    plan[(size_t)D + 1 + q] = dl.leaf[order[q]];
+    plan[(size_t)D + 1 + n + q] = dl.row[order[q]];
+    std::memcpy(weights + 2 * (size_t)q, dl.weight + order[q], sizeof(double));
+  }
+  const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
+  const size_t plan_bytes = (words * sizeof(int32_t) + 255) / 256 * 256;
+  const size_t mdot_scalars = std::max<size_t>((size_t)lat->batch * n * 49, 1);
+  const size_t need = plan_bytes + (mdot_scalars + (states ? (size_t)points * 56 : 0)) * sizeof(double);
+  Scratch& sc = ctx->scratch.trace_jvp;
+  const bool fresh = sc.bytes < need;
+  int rc;
+  if ((rc = ensure_scratch(ctx, sc, need))) return rc;
+  if (fresh || plan != ctx->trace_dirs) {
+    ctx->trace_dirs.clear();
+    HIP_TRY(ctx, hipMemcpyAsync(sc.buf, plan.data(), words * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, sync_main(ctx));  // (kernels of earlier calls have read the old directions; the host vector is ours again)
+    ctx->trace_dirs.swap(plan);
+  }
+  const int32_t* base = (const int32_t*)sc.buf;
+  out->dirs = TraceDirections{base, base + D + 1, base + D + 1 + n, (const double*)(base + (ints + 1) / 2 * 2), D, n};
+  out->mdot = (double*)((char*)sc.buf + plan_bytes);
+  out->mu = out->mdot + mdot_scalars;
+  out->cov = out->mu + points * 7;
+  return LYNX_OK;
+}
+
+// k_trace_tangent_maps, then the sweep over the states `d_mu`, `d_cov` of type ST.
+template <typename T, typename ST>
+static int trace_forward_sweep(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const TraceForwardScratch& fs,
+                               const void* d_mu, const void* d_cov, double* d_mu_dot, double* d_cov_dot) {
+  const int64_t B = lat->batch, threads = B * fs.dirs.entries;
+  if (threads > 0) {
+    hipLaunchKernelGGL(k_trace_tangent_maps<T>, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat),
+                       (const T*)d_energy_in, fs.dirs, fs.mdot);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL((k_trace_moments_jvp<T, ST>), dim3((unsigned)(B * fs.dirs.count)), dim3(64), 0, ctx->stream, (int)lat->n_steps,
+                     fs.dirs, (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf, (const ST*)d_mu, (const ST*)d_cov,
+                     (const double*)fs.mdot, d_mu_dot, d_cov_dot);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+// what both entry points do in front of the sweep: the parameters in memory (k_trace_tangent_maps reads them there), the
+// trace's table in the trace's own slot, the directions
+template <typename T>
+static int trace_forward_begin(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const TraceDirectionList& dl, bool states,
+                               TraceForwardScratch* fs) {
+  int rc;
+  if ((rc = sync_pool(ctx, lat))) return rc;
+  if ((rc = trace_forward_scratch(ctx, lat, dl, states, fs))) return rc;
+  ctx->main_idle = false;  // (the upload of new directions has waited for the stream: work follows it now)
+  return trace_table<T>(ctx, lat, d_energy_in);
+}
+
+static std::array<Written, 2> forward_writes(const lynx_lattice* lat, int32_t n_directions, double* d_mu_dot, double* d_cov_dot) {
+  const size_t cells = (size_t)lat->batch * std::max(n_directions, 0) * ((size_t)lat->n_steps + 1);
+  return {{{d_mu_dot, cells * 7 * sizeof(double)}, {d_cov_dot, cells * 49 * sizeof(double)}}};
+}
+
+int lynx_track_moments_along_forward(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                                     const void* d_cov_trace, const int32_t* dir_start, const int32_t* dir_leaf,
+                                     const int32_t* dir_row, const double* dir_weight, int32_t n_directions, int32_t n_entries,
+                                     double* d_mu_dot, double* d_cov_dot) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!lat || !d_energy_in || !d_mu_trace || !d_cov_trace || !d_mu_dot || !d_cov_dot)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace tangents: null argument");
+  const TraceDirectionList dl{n_directions, n_entries, dir_start, dir_leaf, dir_row, dir_weight};
+  if (const int rc = trace_forward_check(ctx, lat, dl)) return rc;
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, forward_writes(lat, n_directions, d_mu_dot, d_cov_dot));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    using T = decltype(zero);
+    TraceForwardScratch fs;
+    if (const int rc = trace_forward_begin<T>(ctx, lat, d_energy_in, dl, false, &fs)) return rc;
+    return trace_forward_sweep<T, T>(ctx, lat, d_energy_in, fs, d_mu_trace, d_cov_trace, d_mu_dot, d_cov_dot);
+  });
+}
+
+int lynx_track_particles_along_forward(lynx_ctx* ctx, lynx_lattice* lat, int64_t n_particles, const void* d_energy_in,
+                                       const double* d_trace_fwd, const int32_t* dir_start, const int32_t* dir_leaf,
+                                       const int32_t* dir_row, const double* dir_weight, int32_t n_directions, int32_t n_entries,
+                                       double* d_mu_dot, double* d_cov_dot) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!lat || !d_energy_in || !d_trace_fwd || !d_mu_dot || !d_cov_dot)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace tangents: null argument");
+  if (n_particles <= 0) return fail(ctx, LYNX_ERR_INVALID, "beam trace tangents: n_particles must be > 0");
+  const TraceDirectionList dl{n_directions, n_entries, dir_start, dir_leaf, dir_row, dir_weight};
+  if (const int rc = trace_forward_check(ctx, lat, dl)) return rc;
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, forward_writes(lat, n_directions, d_mu_dot, d_cov_dot));
+  return with_dtype(lat->dtype, [&](auto zero) {
+    using T = decltype(zero);
+    TraceForwardScratch fs;
+    if (const int rc = trace_forward_begin<T>(ctx, lat, d_energy_in, dl, true, &fs)) return rc;
+    const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
+    hipLaunchKernelGGL(k_trace_records_to_moments, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, fs.mu, fs.cov);
+    HIP_TRY(ctx, hipGetLastError());
+    return trace_forward_sweep<T, double>(ctx, lat, d_energy_in, fs, fs.mu, fs.cov, d_mu_dot, d_cov_dot);
   });
 }
 

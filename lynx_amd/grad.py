@@ -1399,6 +1399,217 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
     return TrackAlongVJP(segment, beam, trajectories, losses, screens, cavities, image_targets, moment_targets)
 
 
+# -------------------------------------------------------------------------------------------
+# forward mode: tangents of the beam ALONG the lattice
+# -------------------------------------------------------------------------------------------
+
+ENERGY_ROW = 8  # kGradParams: the row of a direction's entry that stands for the energy at that step
+
+
+def _jvp_directions(leaves, wrt):
+    """
+    `wrt` of `track_along_jvp` against the leaf elements of a lattice, refused by value -> the directions in the CSR form
+    lynx_track_*_along_forward reads: (dir_start (D + 1,) int32, dir_leaf (n,) int32, dir_row (n,) int32, dir_weight (n,)
+    float64).  An item is `(element, "name")`, `(element, "misalignment", 0 | 1)` or the string "energy".  An element object
+    that occurs several times has an entry per place; `RBend.angle` also feeds e1 and e2 with weight 1/2 (the rule of
+    `Gradients.__getitem__`); "energy" is one entry per leaf.
+    """
+    from .accelerator.magnets import Cavity, RBend
+
+    wrt = list(wrt)
+    if not wrt:
+        raise ValueError("track_along_jvp: wrt is empty -- name at least one (element, parameter) or 'energy'")
+    start, entries = [0], []
+    for item in wrt:
+        if isinstance(item, str):
+            if item != "energy":
+                raise KeyError(f"track_along_jvp: {item!r} -- the only direction given by a string is 'energy'")
+            entries += [(e, ENERGY_ROW, 1.0) for e in range(len(leaves))]
+            start.append(len(entries))
+            continue
+        if not isinstance(item, tuple) or len(item) not in (2, 3) or not isinstance(item[1], str):
+            raise TypeError(f"track_along_jvp: an item of wrt is (element, 'name'), (element, 'misalignment', 0 | 1) or 'energy', not {item!r}")
+        element, name = item[0], item[1]
+        places = [e for e, el in enumerate(leaves) if el is element]
+        if not places:
+            raise KeyError(f"track_along_jvp: {element!r} is not an element of this lattice")
+        rows = element._row_names() if element._kind in DIFFERENTIABLE_KINDS else []
+        vector = name + "_x" in rows
+        if vector and (len(item) != 3 or item[2] not in (0, 1)):
+            raise ValueError(f"track_along_jvp: {name!r} of {element!r} has two components -- name one: (element, {name!r}, 0 | 1)")
+        if not vector and len(item) == 3 and name in rows:
+            raise ValueError(f"track_along_jvp: {name!r} of {element!r} has one component, {item!r} names one of several")
+        slot = name + ("_x", "_y")[item[2]] if vector else name
+        if slot not in rows:
+            raise KeyError(f"track_along_jvp: {type(element).__name__} {element.name!r} has no differentiable parameter {name!r} "
+                           f"(it has {sorted(set(r.rsplit('_x', 1)[0].rsplit('_y', 1)[0] for r in rows))})")
+        if isinstance(element, Cavity) and name != "length":
+            raise NotImplementedError(f"track_along_jvp: {name!r} of Cavity {element.name!r} -- the energy behind a cavity, and with "
+                                      "it every later map, depends on it; cavities are not differentiated in forward mode yet")
+        feeds = [(rows.index(slot), 1.0)]
+        if isinstance(element, RBend) and name == "angle":  # e1 = e1_user + angle/2, e2 = e2_user + angle/2 (rbend.py:79-80)
+            feeds += [(rows.index("e1"), 0.5), (rows.index("e2"), 0.5)]
+        entries += [(e, row, weight) for e in places for row, weight in feeds]
+        start.append(len(entries))
+    return (np.array(start, dtype=np.int32), np.array([e for e, _, _ in entries], dtype=np.int32),
+            np.array([r for _, r, _ in entries], dtype=np.int32), np.array([w for _, _, w in entries], dtype=np.float64))
+
+
+def _jvp_program(segment, beam):
+    """Every refusal of `track_along_jvp` about the beam and the lattice, before anything touches the GPU -> (program, leaves)."""
+    from .particles.parameter_beam import ParameterBeam
+
+    if not isinstance(beam, (ParameterBeam, ParticleBeam)):
+        raise TypeError(f"track_along_jvp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
+    leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
+    program = engine._trace_plan(segment, leaves)  # (raises for an active Screen or Aperture, naming it)
+    for kind, first, _ in program.steps:
+        if kind == _ffi.STEP_CAVITY:
+            raise NotImplementedError(
+                f"track_along_jvp: active Cavity {leaves[first].name!r} -- behind a cavity the energy, and with it every later "
+                "map, depends on the cavity's parameters, and a ParticleBeam's moments are not closed under its kick; "
+                "forward-mode tangents through cavities are not offered yet (track_along_vjp differentiates such a lattice)")
+    return program, leaves
+
+
+class TrackAlongJVP:
+    """
+    Jacobian-vector products of `Segment.track_along` (lynx_track_moments_along_forward / lynx_track_particles_along_forward):
+    the tangents of the beam's mean and covariance at EVERY point of the lattice along each direction of `wrt` -- the shape
+    reverse mode does not have: few parameters, every output.  Without a kicking cavity every element is an affine map, so
+    one forward sweep of the moment recursion over the trace's states serves both beam classes, and no particle is tracked
+    a second time.  The sweep runs when the object is made; the tangents stay on the device until they are asked for.
+
+    A parameter given per sample has its tangent per sample; one shared by the batch (shape (1,)) gives every sample the
+    tangent with respect to the shared value.
+    """
+
+    def __init__(self, segment, beam, wrt):
+        self.program, self.leaves = _jvp_program(segment, beam)
+        self.wrt = list(wrt)
+        self._directions = _jvp_directions(self.leaves, self.wrt)
+        self.segment, self.beam = segment, beam
+        self.trace = engine.track_along(segment, self.leaves, beam, keep_outgoing=True, keep_device=True)
+        rt = get_runtime()
+        batch_shape, dtype = beam.batch_shape, beam.dtype
+        B, D, P = int(np.prod(batch_shape, dtype=np.int64)), len(self.wrt), self.trace.num_points
+        lat = engine._ready(engine.trace_cache(segment), self.program, batch_shape, dtype, beam._energy._host)
+        e_in = beam._energy.broadcast_device(rt, batch_shape)
+        self._mu_dot_dev, self._cov_dot_dev = rt.empty((B, D, P, 7), np.float64), rt.empty((B, D, P, 7, 7), np.float64)
+        start, leaf, row, weight = self._directions
+        as_ints = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        directions = (as_ints(start), as_ints(leaf), as_ints(row), weight.ctypes.data_as(C.POINTER(C.c_double)), D, len(leaf))
+        states = self.trace._device
+        if isinstance(beam, ParticleBeam):
+            rt.check(rt.lib.lynx_track_particles_along_forward(
+                rt.ctx, lat.handle, beam.num_particles, _p(e_in), _p(states["records"]), *directions, _p(self._mu_dot_dev),
+                _p(self._cov_dot_dev)))
+        else:
+            rt.check(rt.lib.lynx_track_moments_along_forward(
+                rt.ctx, lat.handle, _p(e_in), _p(states["mu"]), _p(states["cov"]), *directions, _p(self._mu_dot_dev),
+                _p(self._cov_dot_dev)))
+        self._mu_dot = self._cov_dot = None
+
+    @property
+    def mu_dot(self) -> np.ndarray:
+        """(*batch, D, P, 7) float64: the tangent of the mean at every point along every direction; entry 6 is an exact zero."""
+        if self._mu_dot is None:
+            self._mu_dot = self._mu_dot_dev.numpy().reshape(*self.beam.batch_shape, len(self.wrt), self.trace.num_points, 7)
+        return self._mu_dot
+
+    @property
+    def cov_dot(self) -> np.ndarray:
+        """(*batch, D, P, 7, 7) float64: the tangent of the covariance (a ParticleBeam's: the biased one); row and column 6 are
+        exact zeros."""
+        if self._cov_dot is None:
+            self._cov_dot = self._cov_dot_dev.numpy().reshape(*self.beam.batch_shape, len(self.wrt), self.trace.num_points, 7, 7)
+        return self._cov_dot
+
+    @property
+    def energy_dot(self) -> np.ndarray:
+        """(D,): the tangent of the energy at every point -- without a cavity the incoming one: 1 along "energy", 0 otherwise."""
+        return np.array([1.0 if isinstance(item, str) else 0.0 for item in self.wrt])
+
+    def tangent(self, name: str) -> np.ndarray:
+        """
+        (*batch, D, P) float64: the tangent of a property of the trace -- any of the 23 names `trace_property_cotangents` has a
+        rule for -- as the contraction of that rule's output for a unit cotangent with `mu_dot`, `cov_dot` and the energy's
+        tangent: the formulas are the reverse pass's own.  "energy" is exact: 1 along the "energy" direction, 0 otherwise.
+        """
+        shape = (*self.beam.batch_shape, len(self.wrt), self.trace.num_points)
+        energy_dot = self.energy_dot[:, None]
+        if name == "energy":
+            return np.broadcast_to(energy_dot, shape).copy()
+        mu_bar, cov_bar, energy_bar = trace_property_cotangents(self.trace, {name: 1.0})
+        out = np.einsum("...pi,...dpi->...dp", mu_bar, self.mu_dot) + np.einsum("...pij,...dpij->...dp", cov_bar, self.cov_dot)
+        if name in _ENERGY_PROPERTIES:
+            out = out + energy_bar[..., None, :] * energy_dot
+        return out
+
+    def reading_tangents(self, bpm) -> np.ndarray:
+        """(*batch, D, 2) float64: the tangent of a BPM's reading, the centroid (x, y) of the beam ENTERING it (the rule of
+        `_add_reading`); the BPM need not be active.  Of a BPM placed several times: at its first place."""
+        points = [k for k, el in enumerate(self.leaves) if el is bpm]
+        if not points:
+            raise KeyError(f"{bpm!r} is not an element of this lattice")
+        return np.ascontiguousarray(self.mu_dot[..., points[0], :][..., (0, 2)])
+
+
+def track_along_jvp(segment, beam, wrt):
+    """
+    Forward pass of `segment.track_along(beam)` (the trace is `jvp.trace`) and, right behind it, the forward-mode sweep: the
+    tangents of the moments at every point along every direction of `wrt`:
+
+        jvp = lynx_amd.grad.track_along_jvp(segment, beam, [(segment.Q3, "k1"), (segment.Q1, "misalignment", 0), "energy"])
+        jvp.mu_dot, jvp.cov_dot                  # (*batch, D, P, 7), (*batch, D, P, 7, 7) float64
+        jvp.tangent("beta_x")                    # (*batch, D, P): how beta_x at every point moves with each of them
+        jvp.reading_tangents(segment.BPM1)       # (*batch, D, 2)
+
+    An item of `wrt` is `(element, "name")`, `(element, "misalignment", 0 | 1)` or "energy" (the incoming beam energy).  Both
+    beam classes, both dtypes; the tangents are float64.  Refused before anything touches the GPU: a lattice with a Cavity
+    that has voltage, an active Screen or Aperture, a parameter the element does not have, an element that is not in the
+    lattice, an empty `wrt`.  The cost is one sweep per direction, each as long as ONE reverse sweep: where reverse mode
+    needs a call per output (a BPM and plane, a point of a curve), this needs a direction per parameter.
+    """
+    return TrackAlongJVP(segment, beam, wrt)
+
+
+class OrbitResponseMatrix:
+    """`matrix` (*batch, 2 n_bpm, n_corr): d(reading)/d(angle), the x rows first, then y; `bpms`, `correctors` in the order of
+    its rows and columns; `jvp`, the `TrackAlongJVP` it was read from."""
+
+    def __init__(self, matrix, bpms, correctors, jvp):
+        self.matrix, self.bpms, self.correctors, self.jvp = matrix, bpms, correctors, jvp
+
+
+def orbit_response_matrix(segment, beam, bpms=None, correctors=None) -> OrbitResponseMatrix:
+    """
+    The orbit response matrix of a lattice, in ONE forward-mode call: d(reading of every BPM)/d(angle of every corrector),
+    what orbit correction by pseudo-inverse starts from.  By default every BPM and every HorizontalCorrector /
+    VerticalCorrector of the flattened lattice, in lattice order.  A BPM need not be active: its reading is the centroid of
+    the beam entering it.  A BPM in front of a corrector reads an exact 0.
+    """
+    from .accelerator.diagnostics import BPM
+    from .accelerator.magnets import HorizontalCorrector, VerticalCorrector
+
+    leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
+
+    def unique(kinds):
+        return list({id(el): el for el in leaves if isinstance(el, kinds)}.values())
+
+    bpms = unique(BPM) if bpms is None else list(bpms)
+    correctors = unique((HorizontalCorrector, VerticalCorrector)) if correctors is None else list(correctors)
+    if not bpms or not correctors:
+        raise ValueError(f"orbit_response_matrix: {len(bpms)} BPMs and {len(correctors)} correctors -- the matrix needs one of each")
+    for bpm in bpms:
+        if not any(el is bpm for el in leaves):
+            raise KeyError(f"orbit_response_matrix: {bpm!r} is not an element of this lattice")
+    jvp = track_along_jvp(segment, beam, [(corrector, "angle") for corrector in correctors])
+    readings = np.stack([jvp.reading_tangents(bpm) for bpm in bpms], axis=-3)  # (*batch, n_bpm, D, 2)
+    matrix = np.concatenate([readings[..., 0], readings[..., 1]], axis=-2)
+    return OrbitResponseMatrix(np.ascontiguousarray(matrix), bpms, correctors, jvp)
+
+
 def track_vjp(segment, beam):
     """Forward pass through `segment`; returns the callable vector-Jacobian product."""
     from .particles.parameter_beam import ParameterBeam
