@@ -2562,6 +2562,23 @@ __global__ __launch_bounds__(256) void k_histogram2d(const T* __restrict__ p, in
   }
 }
 
+// What a ParameterBeam's image on a screen depends on: the beam's centre on the screen, the x-y block of its covariance
+// (a = cov[0][0], bb = cov[0][2], c = cov[2][2]) and det = a c - bb^2, all in the image's dtype.
+template <typename T>
+struct ScreenState {
+  T mx, my, a, bb, c, det;
+};
+
+// THE density of every image kernel, of the stand-alone Screen and of the screens along a trace: exp(log_prob) of
+// MultivariateNormal (screen.py:160-195), -maha/2 - log(2 pi) - log(det)/2, at (dx, dy) from the centre.  The image
+// loss and the image gradients along a trace promise the bits of the image the forward kernel writes: they call this.
+template <typename T>
+__device__ __forceinline__ T gaussian_density(const ScreenState<T> s, T dx, T dy) {
+  const T maha = (s.c * dx * dx - T(2) * s.bb * dx * dy + s.a * dy * dy) / s.det;
+  const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(s.det);
+  return (T)exp((double)logp);
+}
+
 // k_gaussian_image: Screen read-out of a ParameterBeam, one thread per pixel.
 template <typename T>
 __global__ __launch_bounds__(256) void k_gaussian_image(const T* __restrict__ mu, const T* __restrict__ cov,
@@ -2573,12 +2590,9 @@ __global__ __launch_bounds__(256) void k_gaussian_image(const T* __restrict__ mu
   const int i = (int)(pix / ny), j = (int)(pix % ny);
   const T mx = mu[b * 7 + 0], my = mu[b * 7 + 2];
   const T a = cov[b * 49 + 0], bb = cov[b * 49 + 2], c = cov[b * 49 + 2 * 7 + 2];
-  const T det = a * c - bb * bb;
+  const ScreenState<T> s{mx, my, a, bb, c, a * c - bb * bb};
   const T dx = xs[i] - mx, dy = ys[j] - my;
-  const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
-  // exp(log_prob) of MultivariateNormal: -maha/2 - log(2 pi) - log(det)/2
-  const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
-  image[(b * nx + (nx - 1 - i)) * (int64_t)ny + j] = (T)exp((double)logp);
+  image[(b * nx + (nx - 1 - i)) * (int64_t)ny + j] = gaussian_density<T>(s, dx, dy);
 }
 
 // ---------------------------------------------------------------------------------------

@@ -3520,63 +3520,79 @@ int lynx_gaussian_image(lynx_ctx* ctx, int dtype, int64_t batch, const void* d_m
   return LYNX_OK;
 }
 
-int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
-                               const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
-                               const void* d_misalignment, int64_t misalignment_stride, void* d_images) {
-  LYNX_MAIN_ENTRY(ctx);
-  if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !d_images || batch <= 0 || batch > 65535 ||
-      n_points <= 0 || n_screens <= 0)
-    return fail(ctx, LYNX_ERR_INVALID, "bad argument");
-  if (misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
-    return fail(ctx, LYNX_ERR_INVALID, "images along the trace: the misalignments' sample stride is 0 or 2 * n_screens");
-  int64_t cells = 0;
+// ---- the screen images of a ParameterBeam along a trace, their gradients and the image loss ----
+
+// A screen of the caller's rows [n_screens][3] (point, nx, ny), with where its part of every per-screen array begins.
+struct ImageScreen {
+  int32_t point, nx, ny;
+  int64_t cells;   // nx ny
+  int64_t grid;    // its pixel positions in d_grid (xs, then ys)
+  int64_t cell;    // its cells in a sample's images
+  int64_t chunks;  // workgroups of kImageGradCells cells
+  int64_t chunk;   // its chunks among all screens'
+};
+struct ImageScreens {
+  std::vector<ImageScreen> rows;
+  int64_t cells = 0, chunks = 0;  // of all screens
+};
+
+// What differs between the four entries' checks: the prefix of every refusal, what a bad argument is called, whether the
+// dtype and the misalignments' stride are checked, and whether a screen is held to the 32 bits the sum kernels count its
+// cells in.
+struct ImageEntryChecks {
+  const char* prefix;
+  const char* bad_argument;
+  bool dtype, stride, cell_limit;
+};
+constexpr ImageEntryChecks kImagesAlong{"images along the trace", "bad argument", false, true, false};
+constexpr ImageEntryChecks kImageGradients{"image gradients along the trace", "image gradients along the trace: bad argument", true, true, true};
+constexpr ImageEntryChecks kImageLoss{"image loss along the trace", "image loss along the trace: bad argument", true, true, true};
+constexpr ImageEntryChecks kImageLossBackward{"image loss along the trace", "image loss along the trace: bad argument", true, false, true};
+
+// The checks the four entries share, in the order they all make them (`given`: every pointer the entry needs is there),
+// and the one walk over the caller's rows -> `list`.
+static int image_screens(lynx_ctx* ctx, const ImageEntryChecks& entry, bool given, int dtype, int64_t batch, int32_t n_points,
+                         int32_t n_screens, const int32_t* screens, int64_t misalignment_stride, ImageScreens* list) {
+  const auto refuse = [&](const char* what) { return fail(ctx, LYNX_ERR_INVALID, std::string(entry.prefix) + ": " + what); };
+  if (!given || !screens || batch <= 0 || batch > 65535 || n_points <= 0 || n_screens <= 0)
+    return fail(ctx, LYNX_ERR_INVALID, entry.bad_argument);
+  if (entry.dtype && dtype != LYNX_F32 && dtype != LYNX_F64) return refuse("the dtype is float32 or float64");
+  if (entry.stride && misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
+    return refuse("the misalignments' sample stride is 0 or 2 * n_screens");
+  int64_t grid = 0;
   for (int32_t k = 0; k < n_screens; ++k) {
     const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    if (point < 0 || point >= n_points || nx < 1 || ny < 1)
-      return fail(ctx, LYNX_ERR_INVALID, "images along the trace: a screen's point lies inside the trace, and it has pixels");
-    cells += (int64_t)nx * ny;
-  }
-  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_images, (size_t)batch * cells * dtype_size(dtype)}});
-  int64_t grid = 0, cell = 0;
-  for (int32_t k = 0; k < n_screens; ++k) {
-    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    const unsigned gx = (unsigned)(((int64_t)nx * ny + 255) / 256);
-    with_dtype(dtype, [&](auto zero) {
-      using T = decltype(zero);
-      hipLaunchKernelGGL(k_gaussian_image_along<T>, dim3(gx, (unsigned)batch), dim3(256), 0, ctx->stream, (const T*)d_mu_trace,
-                         (const T*)d_cov_trace, (int)n_points, (int)point, (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx,
-                         (int)ny, (const T*)d_misalignment + 2 * k, misalignment_stride, (T*)d_images + cell, cells);
-    });
-    HIP_TRY(ctx, hipGetLastError());
+    if (point < 0 || point >= n_points || nx < 1 || ny < 1) return refuse("a screen's point lies inside the trace, and it has pixels");
+    const int64_t cells = (int64_t)nx * ny, chunks = (cells + kImageGradCells - 1) / kImageGradCells;
+    if (entry.cell_limit && cells > 0x7fffffffLL - kImageGradCells)  // (the kernel counts a screen's cells in 32 bits)
+      return refuse("a screen has fewer than 2^31 - 2048 pixels");
+    list->rows.push_back({point, nx, ny, cells, grid, list->cells, chunks, list->chunks});
     grid += (int64_t)nx + ny;
-    cell += (int64_t)nx * ny;
+    list->cells += cells;
+    list->chunks += chunks;
   }
   return LYNX_OK;
 }
 
-template <typename T>
-static int images_along_backward_t(lynx_ctx* ctx, int64_t batch, int32_t n_points, const void* d_mu_trace, const void* d_cov_trace,
-                                   int32_t n_screens, const int32_t* screens, const void* d_grid, const void* d_misalignment,
-                                   int64_t misalignment_stride, const void* d_images_bar, int64_t cells, void* d_mu_bar,
-                                   void* d_cov_bar, void* d_grad_misalignment) {
-  int64_t grid = 0, cell = 0, slab = 0;
+int lynx_gaussian_images_along(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
+                               const void* d_cov_trace, int32_t n_screens, const int32_t* screens, const void* d_grid,
+                               const void* d_misalignment, int64_t misalignment_stride, void* d_images) {
+  LYNX_MAIN_ENTRY(ctx);
+  ImageScreens list;
+  if (const int rc = image_screens(ctx, kImagesAlong, d_mu_trace && d_cov_trace && d_grid && d_misalignment && d_images, dtype, batch,
+                                   n_points, n_screens, screens, misalignment_stride, &list))
+    return rc;
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_images, (size_t)batch * list.cells * dtype_size(dtype)}});
   for (int32_t k = 0; k < n_screens; ++k) {
-    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    const int64_t chunks = ((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells;
-    double* d_slab = (double*)ctx->scratch.image_grad.buf + slab;
-    hipLaunchKernelGGL(k_gaussian_image_along_bwd<T>, dim3((unsigned)chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
-                       ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)point,
-                       (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx, (int)ny, (const T*)d_misalignment + 2 * k,
-                       misalignment_stride, (const T*)d_images_bar + cell, cells, d_slab);
+    const ImageScreen& s = list.rows[k];
+    with_dtype(dtype, [&](auto zero) {
+      using T = decltype(zero);
+      hipLaunchKernelGGL(k_gaussian_image_along<T>, dim3((unsigned)((s.cells + 255) / 256), (unsigned)batch), dim3(256), 0, ctx->stream,
+                         (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)s.point, (const T*)d_grid + s.grid,
+                         (const T*)d_grid + s.grid + s.nx, (int)s.nx, (int)s.ny, (const T*)d_misalignment + 2 * k, misalignment_stride,
+                         (T*)d_images + s.cell, list.cells);
+    });
     HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_gaussian_image_along_bwd_finish<T>, dim3((unsigned)batch), dim3(64), 0, ctx->stream,
-                       (const T*)d_cov_trace, (int)n_points, (int)point, (const double*)d_slab, (int)chunks, (T*)d_mu_bar,
-                       (T*)d_cov_bar, d_grad_misalignment ? (T*)d_grad_misalignment + 2 * k : (T*)nullptr,
-                       (int64_t)2 * n_screens);
-    HIP_TRY(ctx, hipGetLastError());
-    grid += (int64_t)nx + ny;
-    cell += (int64_t)nx * ny;
-    slab += batch * chunks * 6;
   }
   return LYNX_OK;
 }
@@ -3586,45 +3602,35 @@ int lynx_gaussian_images_along_backward(lynx_ctx* ctx, int dtype, int64_t batch,
                                         const void* d_misalignment, int64_t misalignment_stride, const void* d_images_bar,
                                         void* d_mu_bar, void* d_cov_bar, void* d_grad_misalignment) {
   LYNX_MAIN_ENTRY(ctx);
-  if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !d_images_bar || !d_mu_bar || !d_cov_bar ||
-      batch <= 0 || batch > 65535 || n_points <= 0 || n_screens <= 0)
-    return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: bad argument");
-  if (dtype != LYNX_F32 && dtype != LYNX_F64)
-    return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: the dtype is float32 or float64");
-  if (misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
-    return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: the misalignments' sample stride is 0 or 2 * n_screens");
-  int64_t cells = 0, slab = 0;
-  for (int32_t k = 0; k < n_screens; ++k) {
-    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    if (point < 0 || point >= n_points || nx < 1 || ny < 1)
-      return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: a screen's point lies inside the trace, and it has pixels");
-    if ((int64_t)nx * ny > 0x7fffffffLL - kImageGradCells)  // (the kernel counts a screen's cells in 32 bits)
-      return fail(ctx, LYNX_ERR_INVALID, "image gradients along the trace: a screen has fewer than 2^31 - 2048 pixels");
-    cells += (int64_t)nx * ny;
-    slab += batch * (((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells) * 6;
-  }
+  ImageScreens list;
+  if (const int rc = image_screens(ctx, kImageGradients,
+                                   d_mu_trace && d_cov_trace && d_grid && d_misalignment && d_images_bar && d_mu_bar && d_cov_bar, dtype,
+                                   batch, n_points, n_screens, screens, misalignment_stride, &list))
+    return rc;
   const size_t es = dtype_size(dtype);
   LYNX_MAIN_WRITES(ctx, kFeedsBuild, {{d_mu_bar, (size_t)batch * n_points * 7 * es},
                                       {d_cov_bar, (size_t)batch * n_points * 49 * es},
                                       {d_grad_misalignment, (size_t)batch * n_screens * 2 * es}});
-  if (const int rc = ensure_scratch(ctx, ctx->scratch.image_grad, (size_t)slab * sizeof(double))) return rc;
+  // (every screen its own slab [B][chunks][6], screen after screen)
+  if (const int rc = ensure_scratch(ctx, ctx->scratch.image_grad, (size_t)(batch * list.chunks * 6) * sizeof(double))) return rc;
   return with_dtype(dtype, [&](auto zero) {
-    return images_along_backward_t<decltype(zero)>(ctx, batch, n_points, d_mu_trace, d_cov_trace, n_screens, screens, d_grid,
-                                                   d_misalignment, misalignment_stride, d_images_bar, cells, d_mu_bar, d_cov_bar,
-                                                   d_grad_misalignment);
+    using T = decltype(zero);
+    for (int32_t k = 0; k < n_screens; ++k) {
+      const ImageScreen& s = list.rows[k];
+      double* d_slab = (double*)ctx->scratch.image_grad.buf + batch * s.chunk * 6;
+      hipLaunchKernelGGL(k_gaussian_image_along_bwd<T>, dim3((unsigned)s.chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
+                         ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)s.point,
+                         (const T*)d_grid + s.grid, (const T*)d_grid + s.grid + s.nx, (int)s.nx, (int)s.ny,
+                         (const T*)d_misalignment + 2 * k, misalignment_stride, (const T*)d_images_bar + s.cell, list.cells, d_slab);
+      HIP_TRY(ctx, hipGetLastError());
+      hipLaunchKernelGGL(k_gaussian_image_along_bwd_finish<T>, dim3((unsigned)batch), dim3(64), 0, ctx->stream,
+                         (const T*)d_cov_trace, (int)n_points, (int)s.point, (const double*)d_slab, (int)s.chunks, (T*)d_mu_bar,
+                         (T*)d_cov_bar, d_grad_misalignment ? (T*)d_grad_misalignment + 2 * k : (T*)nullptr,
+                         (int64_t)2 * n_screens);
+      HIP_TRY(ctx, hipGetLastError());
+    }
+    return (int)LYNX_OK;
   });
-}
-
-// The screens of the two image loss entries, checked alike: every refusal in front of anything else.
-static int image_loss_screens(lynx_ctx* ctx, int32_t n_points, int32_t n_screens, const int32_t* screens) {
-  for (int32_t k = 0; k < n_screens; ++k) {
-    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    if (point < 0 || point >= n_points || nx < 1 || ny < 1)
-      return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: a screen's point lies inside the trace, and it has pixels");
-    if ((int64_t)nx * ny > 0x7fffffffLL - kImageGradCells)  // (the kernel counts a screen's cells in 32 bits)
-      return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: a screen has fewer than 2^31 - 2048 pixels");
-  }
-  return LYNX_OK;
 }
 
 int lynx_gaussian_images_along_mse(lynx_ctx* ctx, int dtype, int64_t batch, int32_t n_points, const void* d_mu_trace,
@@ -3632,22 +3638,20 @@ int lynx_gaussian_images_along_mse(lynx_ctx* ctx, int dtype, int64_t batch, int3
                                    const void* d_misalignment, int64_t misalignment_stride, const int64_t* target_offsets,
                                    const void* d_targets, int64_t target_stride, double* d_loss, double* d_sums) {
   LYNX_MAIN_ENTRY(ctx);
-  if (!d_mu_trace || !d_cov_trace || !screens || !d_grid || !d_misalignment || !target_offsets || !d_targets || !d_loss ||
-      !d_sums || batch <= 0 || batch > 65535 || n_points <= 0 || n_screens <= 0)
-    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: bad argument");
-  if (dtype != LYNX_F32 && dtype != LYNX_F64)
-    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the dtype is float32 or float64");
-  if (misalignment_stride != 0 && misalignment_stride != 2 * (int64_t)n_screens)
-    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the misalignments' sample stride is 0 or 2 * n_screens");
-  if (const int rc = image_loss_screens(ctx, n_points, n_screens, screens)) return rc;
+  ImageScreens list;
+  if (const int rc = image_screens(ctx, kImageLoss,
+                                   d_mu_trace && d_cov_trace && d_grid && d_misalignment && target_offsets && d_targets && d_loss && d_sums,
+                                   dtype, batch, n_points, n_screens, screens, misalignment_stride, &list))
+    return rc;
   int64_t target_cells = 0, slab = 0;  // the cells the offsets name; the largest slab of one screen (screens reuse it in stream order)
   for (int32_t k = 0; k < n_screens; ++k) {
-    const int64_t cells = (int64_t)screens[3 * k + 1] * screens[3 * k + 2];
-    if (target_offsets[k] == -1) continue;
-    if (target_offsets[k] < 0)
+    const ImageScreen& s = list.rows[k];
+    const int64_t offset = target_offsets[k];
+    if (offset == -1) continue;
+    if (offset < 0)
       return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: a target's offset is -1 (no target) or not negative");
-    target_cells = std::max(target_cells, target_offsets[k] + cells);
-    slab = std::max(slab, batch * ((cells + kImageGradCells - 1) / kImageGradCells) * 7);
+    target_cells = std::max(target_cells, offset + s.cells);
+    slab = std::max(slab, batch * s.chunks * 7);
   }
   if (target_stride != 0 && target_stride < target_cells)
     return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the targets' sample stride is 0 or at least the cells the offsets name");
@@ -3658,25 +3662,21 @@ int lynx_gaussian_images_along_mse(lynx_ctx* ctx, int dtype, int64_t batch, int3
   HIP_TRY(ctx, hipMemsetAsync(d_loss, 0, (size_t)batch * n_screens * sizeof(double), ctx->stream));
   HIP_TRY(ctx, hipMemsetAsync(d_sums, 0, (size_t)batch * n_screens * 6 * sizeof(double), ctx->stream));
   double* d_slab = (double*)ctx->scratch.image_loss.buf;
-  int64_t grid = 0;
   for (int32_t k = 0; k < n_screens; ++k) {
-    const int32_t point = screens[3 * k], nx = screens[3 * k + 1], ny = screens[3 * k + 2];
-    if (target_offsets[k] >= 0) {
-      const int64_t chunks = ((int64_t)nx * ny + kImageGradCells - 1) / kImageGradCells;
-      with_dtype(dtype, [&](auto zero) {
-        using T = decltype(zero);
-        hipLaunchKernelGGL(k_gaussian_image_along_mse<T>, dim3((unsigned)chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
-                           ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)point,
-                           (const T*)d_grid + grid, (const T*)d_grid + grid + nx, (int)nx, (int)ny,
-                           (const T*)d_misalignment + 2 * k, misalignment_stride, (const T*)d_targets + target_offsets[k],
-                           target_stride, d_slab);
-      });
-      HIP_TRY(ctx, hipGetLastError());
-      hipLaunchKernelGGL(k_gaussian_image_along_mse_finish, dim3((unsigned)batch), dim3(64), 0, ctx->stream,
-                         (const double*)d_slab, (int)chunks, (int)(nx * ny), d_loss + k, d_sums + 6 * k, (int)n_screens);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-    grid += (int64_t)nx + ny;
+    const ImageScreen& s = list.rows[k];
+    if (target_offsets[k] < 0) continue;
+    with_dtype(dtype, [&](auto zero) {
+      using T = decltype(zero);
+      hipLaunchKernelGGL(k_gaussian_image_along_mse<T>, dim3((unsigned)s.chunks, (unsigned)batch), dim3(kImageGradThreads), 0,
+                         ctx->stream, (const T*)d_mu_trace, (const T*)d_cov_trace, (int)n_points, (int)s.point,
+                         (const T*)d_grid + s.grid, (const T*)d_grid + s.grid + s.nx, (int)s.nx, (int)s.ny,
+                         (const T*)d_misalignment + 2 * k, misalignment_stride, (const T*)d_targets + target_offsets[k],
+                         target_stride, d_slab);
+    });
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_gaussian_image_along_mse_finish, dim3((unsigned)batch), dim3(64), 0, ctx->stream,
+                       (const double*)d_slab, (int)s.chunks, (int)s.cells, d_loss + k, d_sums + 6 * k, (int)n_screens);
+    HIP_TRY(ctx, hipGetLastError());
   }
   return LYNX_OK;
 }
@@ -3685,24 +3685,22 @@ int lynx_gaussian_images_along_mse_backward(lynx_ctx* ctx, int dtype, int64_t ba
                                             int32_t n_screens, const int32_t* screens, const double* d_sums,
                                             const void* d_loss_bar, void* d_mu_bar, void* d_cov_bar, void* d_grad_misalignment) {
   LYNX_MAIN_ENTRY(ctx);
-  if (!d_cov_trace || !screens || !d_sums || !d_loss_bar || !d_mu_bar || !d_cov_bar || batch <= 0 || batch > 65535 ||
-      n_points <= 0 || n_screens <= 0)
-    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: bad argument");
-  if (dtype != LYNX_F32 && dtype != LYNX_F64)
-    return fail(ctx, LYNX_ERR_INVALID, "image loss along the trace: the dtype is float32 or float64");
-  if (const int rc = image_loss_screens(ctx, n_points, n_screens, screens)) return rc;
+  ImageScreens list;
+  if (const int rc = image_screens(ctx, kImageLossBackward, d_cov_trace && d_sums && d_loss_bar && d_mu_bar && d_cov_bar, dtype, batch,
+                                   n_points, n_screens, screens, 0, &list))
+    return rc;
   const size_t es = dtype_size(dtype);
   LYNX_MAIN_WRITES(ctx, kFeedsNoBuild, {{d_mu_bar, (size_t)batch * n_points * 7 * es},
                                         {d_cov_bar, (size_t)batch * n_points * 49 * es},
                                         {d_grad_misalignment, (size_t)batch * n_screens * 2 * es}});
   for (int32_t first = 0; first < n_screens; first += kImageLossScreens) {
     const int count = std::min<int32_t>(kImageLossScreens, n_screens - first);
-    ImageLossScreens rows;
-    for (int q = 0; q < kImageLossScreens; ++q) rows.point[q] = q < count ? screens[3 * (first + q)] : 0;
+    ImageLossScreens points;
+    for (int q = 0; q < kImageLossScreens; ++q) points.point[q] = q < count ? list.rows[first + q].point : 0;
     with_dtype(dtype, [&](auto zero) {
       using T = decltype(zero);
       hipLaunchKernelGGL(k_gaussian_image_along_mse_apply<T>, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, ctx->stream,
-                         (const T*)d_cov_trace, batch, (int)n_points, rows, (int)first, count, (int)n_screens, d_sums,
+                         (const T*)d_cov_trace, batch, (int)n_points, points, (int)first, count, (int)n_screens, d_sums,
                          (const T*)d_loss_bar, (T*)d_mu_bar, (T*)d_cov_bar, (T*)d_grad_misalignment);
     });
     HIP_TRY(ctx, hipGetLastError());

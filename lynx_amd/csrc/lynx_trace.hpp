@@ -984,10 +984,30 @@ __global__ __launch_bounds__(64) void k_trace_moments_lanes(LatticeDev lat, cons
 }
 
 // ---------------------------------------------------------------------------------------
-// k_gaussian_image_along: the image of a ParameterBeam on a screen inside the trace -- k_gaussian_image's formula
-// (screen.py:160-195) on mu, cov of ONE point of the moment trace, mu_x and mu_y less the screen's misalignment
-// (Screen._observe, formed in the lattice's dtype), one thread per pixel; the image is [nx][ny] at `image` + b * cells.
+// The screen images of a ParameterBeam along the trace, their gradients and the image loss: seven kernels on five shared
+// pieces, so that all of them see ONE image --
+//   trace_screen_state       a sample's ScreenState at a screen: mu, cov of ONE point of the moment trace, mu_x and mu_y
+//                            less the screen's misalignment (Screen._observe, formed in the lattice's dtype)
+//   gaussian_density         (lynx_device.hpp) the density of a cell, k_gaussian_image's own
+//   image_adjoint_add        a cell's part of the six adjoint sums
+//   image_block_sums<N>, image_sample_sums<N>   N float64 sums over a workgroup's cells into slab[b][chunk][N], and over a
+//                            sample's chunks from there: no atomics, one fixed order of additions
+//   image_entries_add        the five entries of mu_bar, cov_bar and the misalignment's gradient from the six sums
+// The loss and the gradients are those of the image the forward kernel writes, bit for bit, because there is no second
+// copy of any of these expressions to drift.
 // ---------------------------------------------------------------------------------------
+template <typename T>
+__device__ __forceinline__ ScreenState<T> trace_screen_state(const T* __restrict__ mu_trace, const T* __restrict__ cov_trace, int P,
+                                                             int point, const T* __restrict__ misalignment /* of this screen */,
+                                                             int64_t misalignment_stride, int64_t b) {
+  const T* mu = mu_trace + (b * P + point) * 7;
+  const T* cov = cov_trace + (b * P + point) * 49;
+  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
+  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
+  return {mx, my, a, bb, c, a * c - bb * bb};
+}
+
+// k_gaussian_image_along: one thread per pixel; the image is [nx][ny] at `image` + b * cells.
 template <typename T>
 __global__ __launch_bounds__(256) void k_gaussian_image_along(const T* __restrict__ mu_trace, const T* __restrict__ cov_trace,
                                                               int P, int point, const T* __restrict__ xs, const T* __restrict__ ys,
@@ -997,31 +1017,32 @@ __global__ __launch_bounds__(256) void k_gaussian_image_along(const T* __restric
   const int64_t pix = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (pix >= (int64_t)nx * ny) return;
   const int i = (int)(pix / ny), j = (int)(pix % ny);
-  const T* mu = mu_trace + (b * P + point) * 7;
-  const T* cov = cov_trace + (b * P + point) * 49;
-  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
-  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
-  const T det = a * c - bb * bb;
-  const T dx = xs[i] - mx, dy = ys[j] - my;
-  const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
-  const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
-  image[b * cells + (int64_t)(nx - 1 - i) * ny + j] = (T)exp((double)logp);
+  const ScreenState<T> st = trace_screen_state<T>(mu_trace, cov_trace, P, point, misalignment, misalignment_stride, b);
+  const T dx = xs[i] - st.mx, dy = ys[j] - st.my;
+  image[b * cells + (int64_t)(nx - 1 - i) * ny + j] = gaussian_density<T>(st, dx, dy);
 }
 
 // ---------------------------------------------------------------------------------------
-// k_gaussian_image_along_bwd: the adjoint of k_gaussian_image_along -- W = dL/d(image) of one screen, [nx][ny] in the
-// image's own (x-flipped) layout, reduced to six sums per sample:
+// The adjoint of an image: W = dL/d(image) of one screen reduced to six sums per sample,
 //   S0 = sum W I, Sx = sum W I ux, Sy = sum W I uy, Sxx = sum W I ux^2, Sxy = sum W I ux uy, Syy = sum W I uy^2,
-//   ux = (c dx - b dy) / det, uy = (a dy - b dx) / det  (d log I / d mx, d log I / d my).
-// I is formed anew from mu, cov with the very expression of the forward kernel: the gradient is that of the image the
-// caller saw, and no image is read back.  A workgroup sums kImageGradCells consecutive cells (flat index: coalesced loads
-// of W; i, j come from the cell index), float64 sums for both dtypes, across the wave with cross-lane adds, across the
-// four waves through LDS, and writes its six partial sums to slab[b][chunk][6].  No atomics:
-// k_gaussian_image_along_bwd_finish adds a sample's chunks in a fixed order.
+//   ux = (c dx - b dy) / det, uy = (a dy - b dx) / det  (d log I / d mx, d log I / d my),
+// in float64 for both dtypes.  image_adjoint_add adds one cell's part, wi = W I, to s[0 .. 5].
 // ---------------------------------------------------------------------------------------
 constexpr int kImageGradThreads = 256;
 constexpr int kImageGradCells = LYNX_IMAGE_GRAD_CELLS;  // cells one workgroup sums
 static_assert(kImageGradCells % kImageGradThreads == 0, "every thread of a workgroup takes as many cells");
+
+template <typename T>
+__device__ __forceinline__ void image_adjoint_add(double* s, double wi, const ScreenState<T> st, T dx, T dy) {
+  const double ux = (double)((st.c * dx - st.bb * dy) / st.det), uy = (double)((st.a * dy - st.bb * dx) / st.det);
+  const double wx = wi * ux, wy = wi * uy;
+  s[0] += wi;
+  s[1] += wx;
+  s[2] += wy;
+  s[3] += wx * ux;
+  s[4] += wx * uy;
+  s[5] += wy * uy;
+}
 
 __device__ __forceinline__ double image_grad_wave_sum(double v) {
 #pragma unroll
@@ -1029,6 +1050,65 @@ __device__ __forceinline__ double image_grad_wave_sum(double v) {
   return v;
 }
 
+// The N sums of a workgroup's threads -> slab[b][chunk][N]: across the wave with cross-lane adds, across the four waves,
+// 0 .. 3 in that order, through `part` in LDS.  No atomics: image_sample_sums adds a sample's chunks in a fixed order.
+template <int N>
+__device__ __forceinline__ void image_block_sums(double (&s)[N], double (*part)[N], double* __restrict__ slab, int64_t b, int chunks,
+                                                 int chunk, int tid) {
+#pragma unroll
+  for (int q = 0; q < N; ++q) s[q] = image_grad_wave_sum(s[q]);
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) part[tid >> 6][q] = s[q];
+  }
+  __syncthreads();
+  if (tid < N) {
+    double total = part[0][tid];
+#pragma unroll
+    for (int v = 1; v < kImageGradThreads / 64; ++v) total += part[v][tid];
+    slab[(b * chunks + chunk) * N + tid] = total;
+  }
+}
+
+// ... and of a sample from there, by one wave: lane l adds the chunks l, l + 64, ... in that order, then the lanes are
+// added across the wave; every lane has the sums.
+template <int N>
+__device__ __forceinline__ void image_sample_sums(double (&s)[N], const double* __restrict__ slab, int64_t b, int chunks, int lane) {
+#pragma unroll
+  for (int q = 0; q < N; ++q) s[q] = 0;
+  for (int chunk = lane; chunk < chunks; chunk += 64) {
+#pragma unroll
+    for (int q = 0; q < N; ++q) s[q] += slab[(b * chunks + chunk) * N + q];
+  }
+#pragma unroll
+  for (int q = 0; q < N; ++q) s[q] = image_grad_wave_sum(s[q]);
+}
+
+// The five entries the six sums make at the screen's point, ADDED there, and the misalignment's gradient, written:
+//   mu_bar[0] += Sx, mu_bar[2] += Sy, cov_bar[0][0] += (Sxx - c/det S0) / 2, cov_bar[2][2] += (Syy - a/det S0) / 2,
+//   cov_bar[0][2] and cov_bar[2][0] += (Sxy + b/det S0) / 2 each (their sum is the derivative by the covariance b),
+//   gm[at], gm[at + 1] = (-Sx, -Sy) unless gm is null.
+// a, b, c and det in float64 from `cov`; `rounded` takes every float64 value to T the caller's way.
+template <typename T, typename Rounded>
+__device__ __forceinline__ void image_entries_add(const double* s, const T* cov, T* mb, T* cb, T* gm, int64_t at,
+                                                  Rounded rounded) {
+  const double a = (double)cov[0], bb = (double)cov[2], c = (double)cov[2 * 7 + 2];
+  const double det = a * c - bb * bb;
+  mb[0] += rounded(s[1]);
+  mb[2] += rounded(s[2]);
+  cb[0] += rounded(0.5 * (s[3] - c / det * s[0]));
+  cb[2 * 7 + 2] += rounded(0.5 * (s[5] - a / det * s[0]));
+  const T cross = rounded(0.5 * (s[4] + bb / det * s[0]));
+  cb[2] += cross;
+  cb[2 * 7] += cross;
+  if (gm) {
+    gm[at] = rounded(-s[1]);
+    gm[at + 1] = rounded(-s[2]);
+  }
+}
+
+// k_gaussian_image_along_bwd: W is image_bar, [nx][ny] in the image's own (x-flipped) layout, and no image is read back.
+// A workgroup sums kImageGradCells consecutive cells (flat index: coalesced loads of W; i, j come from the cell index).
 template <typename T>
 __global__ __launch_bounds__(kImageGradThreads) void k_gaussian_image_along_bwd(
     const T* __restrict__ mu_trace, const T* __restrict__ cov_trace, int P, int point, const T* __restrict__ xs,
@@ -1039,53 +1119,24 @@ __global__ __launch_bounds__(kImageGradThreads) void k_gaussian_image_along_bwd(
   const int64_t b = blockIdx.y;
   const int chunks = gridDim.x, chunk = blockIdx.x, tid = threadIdx.x;
   const int n = nx * ny;
-  const T* mu = mu_trace + (b * P + point) * 7;
-  const T* cov = cov_trace + (b * P + point) * 49;
-  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
-  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
-  const T det = a * c - bb * bb;
+  const ScreenState<T> st = trace_screen_state<T>(mu_trace, cov_trace, P, point, misalignment, misalignment_stride, b);
   const T* w = image_bar + b * cells;
   double s[6] = {0, 0, 0, 0, 0, 0};
+  int k = 0;  // (outside the loop: the compiler then lays image_block_sums out behind the cells, as code written out here)
 #pragma unroll
-  for (int k = 0; k < kImageGradCells / kImageGradThreads; ++k) {
+  for (; k < kImageGradCells / kImageGradThreads; ++k) {
     const int cell = chunk * kImageGradCells + k * kImageGradThreads + tid;
     if (cell < n) {
       const int row = cell / ny, j = cell - row * ny, i = nx - 1 - row;
-      const T dx = xs[i] - mx, dy = ys[j] - my;
-      const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
-      const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
-      const T density = (T)exp((double)logp);
-      const double wi = (double)w[cell] * (double)density;
-      const double ux = (double)((c * dx - bb * dy) / det), uy = (double)((a * dy - bb * dx) / det);
-      const double wx = wi * ux, wy = wi * uy;
-      s[0] += wi;
-      s[1] += wx;
-      s[2] += wy;
-      s[3] += wx * ux;
-      s[4] += wx * uy;
-      s[5] += wy * uy;
+      const T dx = xs[i] - st.mx, dy = ys[j] - st.my;
+      const T density = gaussian_density<T>(st, dx, dy);
+      image_adjoint_add<T>(s, (double)w[cell] * (double)density, st, dx, dy);
     }
   }
-#pragma unroll
-  for (int q = 0; q < 6; ++q) s[q] = image_grad_wave_sum(s[q]);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 6; ++q) s_part[tid >> 6][q] = s[q];
-  }
-  __syncthreads();
-  if (tid < 6) {
-    double total = s_part[0][tid];
-#pragma unroll
-    for (int v = 1; v < kImageGradThreads / 64; ++v) total += s_part[v][tid];
-    slab[(b * chunks + chunk) * 6 + tid] = total;
-  }
+  image_block_sums<6>(s, s_part, slab, b, chunks, chunk, tid);
 }
 
-// ... and its finishing step, one wave per sample: lane l adds the chunks l, l + 64, ... in that order, the lanes are added
-// across the wave, and lane 0 forms the five entries
-//   mu_bar[0] += Sx, mu_bar[2] += Sy, cov_bar[0][0] += (Sxx - c/det S0) / 2, cov_bar[2][2] += (Syy - a/det S0) / 2,
-//   cov_bar[0][2] and cov_bar[2][0] += (Sxy + b/det S0) / 2 each (their sum is the derivative by the covariance b)
-// at the screen's point, and grad_misalignment = (-Sx, -Sy).  a, b, c and det in float64 here.
+// ... and its finishing step, one wave per sample: lane 0 adds the entries as they are, (T)s.
 template <typename T>
 __global__ __launch_bounds__(64) void k_gaussian_image_along_bwd_finish(const T* __restrict__ cov_trace, int P, int point,
                                                                         const double* __restrict__ slab, int chunks,
@@ -1094,41 +1145,19 @@ __global__ __launch_bounds__(64) void k_gaussian_image_along_bwd_finish(const T*
                                                                         int64_t grad_misalignment_stride) {
   const int64_t b = blockIdx.x;
   const int lane = threadIdx.x;
-  double s[6] = {0, 0, 0, 0, 0, 0};
-  for (int chunk = lane; chunk < chunks; chunk += 64) {
-#pragma unroll
-    for (int q = 0; q < 6; ++q) s[q] += slab[(b * chunks + chunk) * 6 + q];
-  }
-#pragma unroll
-  for (int q = 0; q < 6; ++q) s[q] = image_grad_wave_sum(s[q]);
+  double s[6];
+  image_sample_sums<6>(s, slab, b, chunks, lane);
   if (lane != 0) return;
-  const T* cov = cov_trace + (b * P + point) * 49;
-  const double a = (double)cov[0], bb = (double)cov[2], c = (double)cov[2 * 7 + 2];
-  const double det = a * c - bb * bb;
-  T* mb = mu_bar + (b * P + point) * 7;
-  T* cb = cov_bar + (b * P + point) * 49;
-  mb[0] += (T)s[1];
-  mb[2] += (T)s[2];
-  cb[0] += (T)(0.5 * (s[3] - c / det * s[0]));
-  cb[2 * 7 + 2] += (T)(0.5 * (s[5] - a / det * s[0]));
-  const T cross = (T)(0.5 * (s[4] + bb / det * s[0]));
-  cb[2] += cross;
-  cb[2 * 7] += cross;
-  if (grad_misalignment) {
-    grad_misalignment[b * grad_misalignment_stride] = (T)(-s[1]);
-    grad_misalignment[b * grad_misalignment_stride + 1] = (T)(-s[2]);
-  }
+  image_entries_add<T>(s, cov_trace + (b * P + point) * 49, mu_bar + (b * P + point) * 7, cov_bar + (b * P + point) * 49,
+                       grad_misalignment, b * grad_misalignment_stride, [](double v) { return (T)v; });
 }
 
 // ---------------------------------------------------------------------------------------
 // k_gaussian_image_along_mse: the mean squared difference of a screen's image to a target, and the six adjoint sums of that
-// loss, in ONE pass over the target -- neither the image nor its cotangent exists in memory.  Per cell the density I is
-// formed with the very expression of k_gaussian_image_along (the loss is that of the image the forward kernel would have
-// written, bit for bit), r = I - target, w = 2 r / cells in double, and seven float64 sums are kept:
-//   L = sum r^2,  S0, Sx, Sy, Sxx, Sxy, Syy = sum w I {1, ux, uy, ux^2, ux uy, uy^2}   (ux, uy as in k_gaussian_image_along_bwd)
-// The work split, the reduction and the slab are those of k_gaussian_image_along_bwd with seven values for six:
-// slab[b][chunk][7], no atomics.  `target` is this screen's part of sample 0's row; sample b's is target_stride further
-// (0: one target for the whole batch, which then stays in cache while every sample reads it).
+// loss, in ONE pass over the target -- neither the image nor its cotangent exists in memory.  Per cell r = I - target,
+// W = 2 r / cells in double, and a seventh sum is kept: L = sum r^2, slab[b][chunk][7].  `target` is this screen's part of
+// sample 0's row; sample b's is target_stride further (0: one target for the whole batch, which then stays in cache
+// while every sample reads it).
 // ---------------------------------------------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(kImageGradThreads) void k_gaussian_image_along_mse(
@@ -1140,67 +1169,35 @@ __global__ __launch_bounds__(kImageGradThreads) void k_gaussian_image_along_mse(
   const int64_t b = blockIdx.y;
   const int chunks = gridDim.x, chunk = blockIdx.x, tid = threadIdx.x;
   const int n = nx * ny;
-  const T* mu = mu_trace + (b * P + point) * 7;
-  const T* cov = cov_trace + (b * P + point) * 49;
-  const T mx = mu[0] - misalignment[b * misalignment_stride], my = mu[2] - misalignment[b * misalignment_stride + 1];
-  const T a = cov[0], bb = cov[2], c = cov[2 * 7 + 2];
-  const T det = a * c - bb * bb;
+  const ScreenState<T> st = trace_screen_state<T>(mu_trace, cov_trace, P, point, misalignment, misalignment_stride, b);
   const T* t = target + b * target_stride;
   const double scale = 2.0 / (double)n;
   double s[7] = {0, 0, 0, 0, 0, 0, 0};
+  int k = 0;  // (outside the loop, as in k_gaussian_image_along_bwd)
 #pragma unroll
-  for (int k = 0; k < kImageGradCells / kImageGradThreads; ++k) {
+  for (; k < kImageGradCells / kImageGradThreads; ++k) {
     const int cell = chunk * kImageGradCells + k * kImageGradThreads + tid;
     if (cell < n) {
       const int row = cell / ny, j = cell - row * ny, i = nx - 1 - row;
-      const T dx = xs[i] - mx, dy = ys[j] - my;
-      const T maha = (c * dx * dx - T(2) * bb * dx * dy + a * dy * dy) / det;
-      const T logp = T(-0.5) * maha - T(1.8378770664093453) - T(0.5) * t_log(det);
-      const T density = (T)exp((double)logp);
+      const T dx = xs[i] - st.mx, dy = ys[j] - st.my;
+      const T density = gaussian_density<T>(st, dx, dy);
       const double r = (double)density - (double)t[cell];
-      const double wi = scale * r * (double)density;
-      const double ux = (double)((c * dx - bb * dy) / det), uy = (double)((a * dy - bb * dx) / det);
-      const double wx = wi * ux, wy = wi * uy;
-      s[0] += wi;
-      s[1] += wx;
-      s[2] += wy;
-      s[3] += wx * ux;
-      s[4] += wx * uy;
-      s[5] += wy * uy;
+      image_adjoint_add<T>(s, scale * r * (double)density, st, dx, dy);
       s[6] += r * r;
     }
   }
-#pragma unroll
-  for (int q = 0; q < 7; ++q) s[q] = image_grad_wave_sum(s[q]);
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int q = 0; q < 7; ++q) s_part[tid >> 6][q] = s[q];
-  }
-  __syncthreads();
-  if (tid < 7) {
-    double total = s_part[0][tid];
-#pragma unroll
-    for (int v = 1; v < kImageGradThreads / 64; ++v) total += s_part[v][tid];
-    slab[(b * chunks + chunk) * 7 + tid] = total;
-  }
+  image_block_sums<7>(s, s_part, slab, b, chunks, chunk, tid);
 }
 
-// ... its finishing step, one wave per sample: lane l adds the chunks l, l + 64, ... in that order and the lanes are added
-// across the wave, as in k_gaussian_image_along_bwd_finish; lanes 0 .. 5 write sums[b][screen][6] and lane 6 writes
-// loss[b][screen] = L / cells.
+// ... its finishing step, one wave per sample: lane 0 writes sums[b][screen][6] and loss[b][screen] = L / cells.
 __global__ __launch_bounds__(64) void k_gaussian_image_along_mse_finish(const double* __restrict__ slab, int chunks, int cells,
                                                                         double* __restrict__ loss /* of this screen */,
                                                                         double* __restrict__ sums /* of this screen */,
                                                                         int n_screens) {
   const int64_t b = blockIdx.x;
   const int lane = threadIdx.x;
-  double s[7] = {0, 0, 0, 0, 0, 0, 0};
-  for (int chunk = lane; chunk < chunks; chunk += 64) {
-#pragma unroll
-    for (int q = 0; q < 7; ++q) s[q] += slab[(b * chunks + chunk) * 7 + q];
-  }
-#pragma unroll
-  for (int q = 0; q < 7; ++q) s[q] = image_grad_wave_sum(s[q]);
+  double s[7];
+  image_sample_sums<7>(s, slab, b, chunks, lane);
   if (lane == 0) {
 #pragma unroll
     for (int q = 0; q < 6; ++q) sums[b * n_screens * 6 + q] = s[q];
@@ -1210,8 +1207,7 @@ __global__ __launch_bounds__(64) void k_gaussian_image_along_mse_finish(const do
 
 // ---------------------------------------------------------------------------------------
 // k_gaussian_image_along_mse_apply: the reverse half.  One thread per sample walks the screens in order (two screens never
-// race on one point): the five entries of k_gaussian_image_along_bwd_finish from sums[b][k] and a, b, c, det in float64,
-// scaled by loss_bar[b][k], ADDED into mu_bar, cov_bar at the screen's point; grad_misalignment[b][k] = -loss_bar (Sx, Sy).
+// race on one point): the entries from sums[b][k], each scaled by loss_bar[b][k] before it is rounded, (T)(bar s).
 // A screen without a target has sums of 0: it adds 0 and gets (0, 0), by the same arithmetic.  The screens' points come by
 // value, kImageLossScreens of them per launch (screens `first` .. `first + count - 1`); launches follow each other on one
 // stream.
@@ -1232,24 +1228,10 @@ __global__ __launch_bounds__(64) void k_gaussian_image_along_mse_apply(const T* 
   if (b >= B) return;
   for (int q = 0; q < count; ++q) {
     const int k = first + q, point = screens.point[q];
-    const double* s = sums + (b * n_screens + k) * 6;
     const double bar = (double)loss_bar[b * n_screens + k];
-    const T* cov = cov_trace + (b * P + point) * 49;
-    const double a = (double)cov[0], bb = (double)cov[2], c = (double)cov[2 * 7 + 2];
-    const double det = a * c - bb * bb;
-    T* mb = mu_bar + (b * P + point) * 7;
-    T* cb = cov_bar + (b * P + point) * 49;
-    mb[0] += (T)(bar * s[1]);
-    mb[2] += (T)(bar * s[2]);
-    cb[0] += (T)(bar * (0.5 * (s[3] - c / det * s[0])));
-    cb[2 * 7 + 2] += (T)(bar * (0.5 * (s[5] - a / det * s[0])));
-    const T cross = (T)(bar * (0.5 * (s[4] + bb / det * s[0])));
-    cb[2] += cross;
-    cb[2 * 7] += cross;
-    if (grad_misalignment) {
-      grad_misalignment[(b * n_screens + k) * 2] = (T)(-(bar * s[1]));
-      grad_misalignment[(b * n_screens + k) * 2 + 1] = (T)(-(bar * s[2]));
-    }
+    image_entries_add<T>(sums + (b * n_screens + k) * 6, cov_trace + (b * P + point) * 49, mu_bar + (b * P + point) * 7,
+                         cov_bar + (b * P + point) * 49, grad_misalignment, (b * n_screens + k) * 2,
+                         [bar](double v) { return (T)(bar * v); });
   }
 }
 

@@ -56,12 +56,12 @@ class Gradients:
 
     def __init__(self, program, beam, raw_dev, energy_dev, particles=None, moments=None, chosen=None, screens=None, zeros=()):
         # what a pass may have besides `[B][E][8]` and the energy's, on the device: `particles`; `moments` = (mu, cov); `chosen`;
-        # `screens` = (the trace's active screens, dL/d(misalignment) `[B][screens][2]` -- or a list of such arrays, which are
-        # added -- or None: no image took a cotangent);
+        # `screens` = (the trace's active screens, the parts of dL/d(misalignment), each `[B][screens][2]`: they are added, and
+        # none is an exact zero);
         # `zeros`: (element, parameter names) whose gradient is an exact zero
         self._program, self._raw_dev, self._energy_dev = program, raw_dev, energy_dev
         self._particles_dev, self._moments, self._chosen_dev = particles, moments, chosen
-        self._screens, self._screen_shifts_dev = ([], None) if screens is None else (list(screens[0]), screens[1])
+        self._screens, self._screen_shifts_dev = ([], []) if screens is None else (list(screens[0]), list(screens[1]))
         self._batch_shape, self._energy_shape = tuple(beam.batch_shape), np.asarray(beam.energy).shape
         self._zeros, self._raw, self._cache = list(zeros), None, {}
 
@@ -125,10 +125,9 @@ class Gradients:
         for k, el in enumerate(self._screens):
             if el is element:  # the image sees mu_x - misalignment[0], mu_y - misalignment[1]: minus the mu cotangent there
                 shape = np.asarray(el.misalignment).shape
-                if self._screen_shifts_dev is None:
+                if not self._screen_shifts_dev:
                     return {"misalignment": np.zeros(shape)}
-                parts = self._screen_shifts_dev if isinstance(self._screen_shifts_dev, list) else [self._screen_shifts_dev]
-                shifts = sum(part.numpy() for part in parts).reshape(*self._batch_shape, len(self._screens), 2)
+                shifts = sum(part.numpy() for part in self._screen_shifts_dev).reshape(*self._batch_shape, len(self._screens), 2)
                 self._cache[id(element)] = {"misalignment": _unbroadcast(np.ascontiguousarray(shifts[..., k, :]), shape)}
                 return self._cache[id(element)]
         raw, total = self._host(), None
@@ -853,7 +852,7 @@ class TrackAlongVJP:
             segment, beam, trajectories, losses, True if targets and isinstance(screens, (bool, np.bool_)) else screens, cavities)
         self.segment, self.beam = segment, beam
         self._screens = bool(screens)  # (of "moments": the forward trace makes images, the call takes their cotangents)
-        self._targets = self._image_loss = None
+        self._targets = self._image_loss = self._shots = None
         if targets:  # every refusal by value, before anything touches the GPU
             self._targets = image_targets if isinstance(image_targets, ImageTargets) else ImageTargets(image_targets)
             layout = self._targets._layout(self.program, self.leaves, beam)
@@ -968,6 +967,16 @@ class TrackAlongVJP:
         rt.check(rt.lib.lynx_moments_along_loss_backward(
             *self._moment_loss_arguments(rt, self._moment_layout), _p(ml_dev), _p(rec_dev), _p(mb_dev), _p(cb_dev), _p(eb_dev)))
 
+    def _image_head(self, rt, *states):
+        """
+        What every image call begins with, (ctx, dtype, B, P, the named states of the trace), and the geometry of the trace's
+        screens, looked up once per `TrackAlongVJP` -> (head, geometry).
+        """
+        beam = self.beam
+        if self._shots is None:
+            self._shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+        return (rt.ctx, engine.dtype_code(beam.dtype), *self._points_shape(), *(_p(self.trace._device[s]) for s in states)), self._shots
+
     def _evaluate_image_loss(self, layout):
         """
         lynx_gaussian_images_along_mse right behind the trace, on its stream: the loss [B][K] and the six adjoint sums
@@ -976,14 +985,12 @@ class TrackAlongVJP:
         if not self.program.screens:  # (no active screen, and so no target: nothing to evaluate)
             return None, None, []
         rt = get_runtime()
-        beam, states = self.beam, self.trace._device
-        B, P, K = int(np.prod(beam.batch_shape, dtype=np.int64)), self.trace.num_points, len(self.program.screens)
-        shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+        head, shots = self._image_head(rt, "mu", "cov")
+        B, K = head[2], shots["count"]
         targets_dev = self._targets._device(rt, layout)
         loss, sums = rt.empty((B, K), np.float64), rt.empty((B, K, 6), np.float64)
         rt.check(rt.lib.lynx_gaussian_images_along_mse(
-            rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), *shots["arguments"],
-            (C.c_int64 * K)(*layout.offsets), _p(targets_dev), layout.stride, _p(loss), _p(sums)))
+            *head, *shots["arguments"], (C.c_int64 * K)(*layout.offsets), _p(targets_dev), layout.stride, _p(loss), _p(sums)))
         return loss, sums, [offset >= 0 for offset in layout.offsets]
 
     @property
@@ -1209,31 +1216,24 @@ class TrackAlongVJP:
     # one method per mode, called alike (each names what it uses): the library call or calls -> `Gradients`' optional results
     def _launch_moments(self, rt, sweep, mb, cb, eb_dev, wi, lb, ml, **_):
         beam, states = self.beam, self.trace._device
-        B, P = self._points_shape()
         mb_dev, cb_dev = self._moment_buffers(rt, mb, cb)
-        shifts = loss_shifts = None
+        shifts = []  # the parts of dL/d(misalignment), one per image call: `Gradients` adds them
         if wi is not None:  # the images' cotangents go into mb_dev, cb_dev at the screens' points, on the same stream
-            shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+            head, shots = self._image_head(rt, "mu", "cov")
             wi_dev = rt.to_device(np.ascontiguousarray(wi, dtype=beam.dtype))
-            shifts = rt.empty((B, shots["count"], 2), beam.dtype)
+            shifts.append(rt.empty((head[2], shots["count"], 2), beam.dtype))
             rt.check(rt.lib.lynx_gaussian_images_along_backward(
-                rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["mu"]), _p(states["cov"]), *shots["arguments"],
-                _p(wi_dev), _p(mb_dev), _p(cb_dev), _p(shifts)))
+                *head, *shots["arguments"], _p(wi_dev), _p(mb_dev), _p(cb_dev), _p(shifts[-1])))
         if lb is not None:  # ... and so do the image losses' cotangents times the sums of the forward pass
-            shots = engine._screen_geometry(self.segment, self.program, beam.batch_shape, beam.dtype, rt, False)
+            head, shots = self._image_head(rt, "cov")
             lb_dev = rt.to_device(np.ascontiguousarray(lb, dtype=beam.dtype))
-            loss_shifts = rt.empty((B, shots["count"], 2), beam.dtype)
+            shifts.append(rt.empty((head[2], shots["count"], 2), beam.dtype))
             rt.check(rt.lib.lynx_gaussian_images_along_mse_backward(
-                rt.ctx, engine.dtype_code(beam.dtype), B, P, _p(states["cov"]), shots["count"], shots["rows"], _p(self._image_loss[1]),
-                _p(lb_dev), _p(mb_dev), _p(cb_dev), _p(loss_shifts)))
+                *head, shots["count"], shots["rows"], _p(self._image_loss[1]), _p(lb_dev), _p(mb_dev), _p(cb_dev), _p(shifts[-1])))
         self._add_moment_loss(rt, ml, eb_dev, mb_dev=mb_dev, cb_dev=cb_dev)
         rt.check(rt.lib.lynx_track_moments_along_backward(
             rt.ctx, sweep.lat.handle, _p(sweep.e_in), _p(states["mu"]), _p(states["cov"]), _p(mb_dev), _p(cb_dev), _p(eb_dev),
             _p(sweep.g_par), _p(sweep.g_en), _p(sweep.g_mu), _p(sweep.g_cov)))
-        if shifts is not None and loss_shifts is not None:  # (both in one call: `Gradients` adds the two)
-            shifts = [shifts, loss_shifts]
-        elif loss_shifts is not None:
-            shifts = loss_shifts
         with_screens = self._screens or self._targets is not None
         return dict(moments=(sweep.g_mu, sweep.g_cov), screens=([el for _, el in self.program.screens], shifts) if with_screens else None)
 

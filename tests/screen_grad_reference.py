@@ -131,6 +131,12 @@ KERNEL_SCREENS = {
     "612x511": ARES_BINNING_4,
 }
 
+# A screen of exactly 65 workgroups, 3 x 43 691 = 64 x 2048 + 1 = 131 073 cells: the finishing kernels' lane l adds the chunks
+# l, l + 64, ..., so here lane 0 alone makes a second trip.  It is run apart from KERNEL_SCREENS, a batch of 2 once per dtype,
+# under the float32 bounds of 612 x 511 (the large screen next to it); tests/test_trace_screens_grad_host.py and
+# tests/test_trace_image_loss_host.py check that the float32 restatement itself stays inside them on this screen.
+SCREEN_OF_65_CHUNKS = dict(resolution=(3, 43691), pixel_size=(_PIXEL, _PIXEL), binning=1)
+
 # What tests/test_trace_screens_grad_host.py measures and asserts for the float32 restatement against the float64 one on
 # the float32 inputs: the worst entry relative to its uncancelled size, over samples 0 .. 3 of `mismatch_cotangent`, per
 # screen ("A", "B": the two screens of tests/test_gpu_trace_screens.py).  Measured (numpy; log det rounded correctly):

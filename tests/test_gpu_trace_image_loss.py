@@ -174,6 +174,20 @@ def test_the_kernels_alone_against_the_restatement(lx, dtype, label, shape, shar
         assert np.all(g[el]["length"] == 0)
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_a_screen_of_65_chunks_against_the_restatement(lx, monkeypatch, dtype):
+    """`ref.SCREEN_OF_65_CHUNKS` through the test above, a batch of 2: 64 lanes of the finishing kernel add one chunk each and
+    lane 0 a second one.  The float32 bounds are those of 612 x 511."""
+    from lynx_amd import _ffi
+
+    label = "3x43691"
+    assert -(-3 * 43691 // _ffi.IMAGE_GRAD_CELLS) == 65
+    monkeypatch.setitem(il.LOSS_SCREENS, label, ref.SCREEN_OF_65_CHUNKS)
+    monkeypatch.setitem(il.FLOAT32_ENTRY_DEVIATION, label, il.FLOAT32_ENTRY_DEVIATION[LARGEST])
+    monkeypatch.setitem(il.FLOAT32_LOSS_DEVIATION, label, il.FLOAT32_LOSS_DEVIATION[LARGEST])
+    test_the_kernels_alone_against_the_restatement(lx, dtype, label, (2,), False, False)
+
+
 # ---------------------------------------------------------------------------------------------
 # 7. agreement with the existing path
 # ---------------------------------------------------------------------------------------------
@@ -579,6 +593,89 @@ def test_the_reverse_entry_refuses_and_the_next_valid_call_returns_the_same_byte
     assert read(env, loss_arrays, outputs) == before and all(any(block) for block in before)
     status, message = backward_call(env, loss_arrays, g_mis=None)  # (the misalignment gradient is optional)
     assert status == 0, message
+    assert {name: env.a[name].numpy().tobytes() for name in env.keep} == env.keep
+
+
+def test_65_screens_of_one_pixel_through_both_entries(env):
+    """More screens than one launch of the reverse half takes (64): 65 screens of one pixel each on the four points of the
+    trace of tests/test_gpu_entry_refusals.py, screens 63 and 64 on one point, misalignments per sample, every third screen
+    without a target.  The loss, the reverse half's additions at every point and the misalignments' gradients against the
+    restatement, under the bounds of the single pixel ("1") of the kernels' own test; a screen without a target is all zeros."""
+    rt, dtype = env.rt, env.dtype
+    K = 65
+    rng = np.random.default_rng(65)
+    points = [((k + 1) // 2) % P for k in range(K)]
+    named = [k % 3 != 1 or k == 64 for k in range(K)]
+    assert points[63] == points[64] and named[0] and named[63] and named[64] and not all(named)
+    pixels = rng.uniform(-2e-4, 2e-4, (K, 2)).astype(dtype)  # a screen's grid: its one x, its one y
+    mis = (1e-5 * rng.standard_normal((B, K, 2))).astype(dtype)
+    bars = np.where(named, rng.uniform(0.5, 2.0, (B, K)) * rng.choice([-1.0, 1.0], (B, K)), 3.0).astype(dtype)  # (3: on nothing)
+    mu, cov = env.host["mu_tr"].reshape(B, P, 7), env.host["cov_tr"].reshape(B, P, 7, 7)
+    state = lambda s, k: (mu[s, points[k], 0] - mis[s, k, 0], mu[s, points[k], 2] - mis[s, k, 1],  # noqa: E731
+                          cov[s, points[k], 0, 0], cov[s, points[k], 0, 2], cov[s, points[k], 2, 2])
+    columns = {k: j for j, k in enumerate(reversed([k for k in range(K) if named[k]]))}  # (the targets in another order)
+    targets = np.zeros((B, len(columns)), dtype=dtype)
+    for k, j in columns.items():
+        for s in range(B):
+            targets[s, j] = rng.uniform(0.5, 1.5) * ref.density(*state(s, k), pixels[k, :1], pixels[k, 1:])[0][0, 0]
+    assert np.all(targets > 0)
+    if dtype == np.float64:
+        tol_entry = tol_loss = TOL_IMAGE[np.float64]
+    else:
+        tol_entry, tol_loss = FLOAT32_FACTOR * il.FLOAT32_ENTRY_DEVIATION["1"], FLOAT32_FACTOR * il.FLOAT32_LOSS_DEVIATION["1"]
+    want, worst32 = {}, 0.0
+    for k, j in columns.items():
+        for s in range(B):
+            arguments = (*state(s, k), pixels[k, :1], pixels[k, 1:], targets[s, j].reshape(1, 1))
+            want[s, k] = il.image_loss(*arguments)
+            if dtype == np.float32:  # (the float32 restatement itself stays inside the bound on these inputs)
+                loss32, single, _, _ = il.image_loss(*arguments, "float32")
+                ref_loss, entries, loss_size, sizes = want[s, k]
+                worst32 = max(worst32, abs(loss32 - ref_loss) / loss_size / tol_loss,
+                              *(abs(single[name] - entries[name]) / sizes[name] / tol_entry for name in ref.ENTRIES))
+    print(f"{np.dtype(dtype).name}: the float32 restatement is at most {worst32:.2f} of the bound away from the float64 one")
+    assert worst32 <= 0.5
+
+    own = dict(grid=rt.to_device(pixels.reshape(-1)), mis=rt.to_device(mis), targets=rt.to_device(targets), bars=rt.to_device(bars),
+               loss=rt.empty((B, K), np.float64), sums=rt.empty((B, K, 6), np.float64), g_mis=rt.empty((B, K, 2), dtype))
+    p = lambda name: C.c_void_p((own[name] if name in own else env.a[name]).ptr)  # noqa: E731
+    rows = ints([v for k in range(K) for v in (points[k], 1, 1)])
+    offsets = (C.c_int64 * K)(*[columns.get(k, -1) for k in range(K)])
+    rt.check(rt.lib.lynx_gaussian_images_along_mse(rt.ctx, env.code, B, P, p("mu_tr"), p("cov_tr"), K, rows, p("grid"), p("mis"), 2 * K,
+                                                   offsets, p("targets"), targets.shape[1], p("loss"), p("sums")))
+    zeroed(env, own, ["mu_bar_out", "cov_bar_out"])
+    rt.check(rt.lib.lynx_gaussian_images_along_mse_backward(rt.ctx, env.code, B, P, p("cov_tr"), K, rows, p("sums"), p("bars"),
+                                                            p("mu_bar_out"), p("cov_bar_out"), p("g_mis")))
+    loss, sums, g_mis = own["loss"].numpy(), own["sums"].numpy(), own["g_mis"].numpy().astype(np.float64)
+    g_mu, g_cov = env.a["mu_bar_out"].numpy().reshape(B, P, 7), env.a["cov_bar_out"].numpy().reshape(B, P, 7, 7)
+    at = {"mu_x": lambda s, q: g_mu[s, q, 0], "mu_y": lambda s, q: g_mu[s, q, 2], "cov_xx": lambda s, q: g_cov[s, q, 0, 0],
+          "cov_yy": lambda s, q: g_cov[s, q, 2, 2], "cov_xy": lambda s, q: g_cov[s, q, 0, 2]}
+    worst = {"loss": 0.0, "misalignment": 0.0, "entries": 0.0}
+    for s in range(B):
+        for k in range(K):
+            if not named[k]:
+                assert loss[s, k] == 0 and not sums[s, k].any() and not g_mis[s, k].any(), (s, k)
+                continue
+            ref_loss, entries, loss_size, sizes = want[s, k]
+            worst["loss"] = max(worst["loss"], abs(loss[s, k] - ref_loss) / loss_size / tol_loss)
+            for axis, name in enumerate(("mu_x", "mu_y")):
+                assert entries[name] != 0
+                distance = abs(g_mis[s, k, axis] + float(bars[s, k]) * entries[name]) / (abs(float(bars[s, k])) * sizes[name])
+                worst["misalignment"] = max(worst["misalignment"], distance / tol_entry)
+        for q in range(P):  # what the screens on a point add there, in their order
+            here = [k for k in range(K) if named[k] and points[k] == q]
+            assert len(here) > 1
+            for name in ref.ENTRIES:
+                total = sum(float(bars[s, k]) * want[s, k][1][name] for k in here)
+                size = sum(abs(float(bars[s, k])) * want[s, k][3][name] for k in here)
+                worst["entries"] = max(worst["entries"], abs(float(at[name](s, q)) - total) / size / tol_entry)
+    print(f"{np.dtype(dtype).name}: worst distances in units of the bound {worst}")
+    assert max(worst.values()) <= 1, worst
+    assert np.array_equal(g_cov[..., 0, 2], g_cov[..., 2, 0]) and np.all(g_mis[:, [0, 63, 64]] != 0)
+    seen_mu, seen_cov = np.zeros(7, dtype=bool), np.zeros((7, 7), dtype=bool)
+    seen_mu[[0, 2]] = True
+    seen_cov[[0, 0, 2, 2], [0, 2, 0, 2]] = True
+    assert np.all(g_mu[..., ~seen_mu] == 0) and np.all(g_cov[..., ~seen_cov] == 0)
     assert {name: env.a[name].numpy().tobytes() for name in env.keep} == env.keep
 
 

@@ -141,6 +141,19 @@ def test_the_kernel_alone_against_the_restatement(lx, dtype, label, shape, share
         assert np.all(g[el]["length"] == 0)
 
 
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_a_screen_of_65_chunks_against_the_restatement(lx, monkeypatch, dtype):
+    """`ref.SCREEN_OF_65_CHUNKS` through the test above, a batch of 2: 64 lanes of the finishing kernel add one chunk each and
+    lane 0 a second one.  The float32 bound is that of 612 x 511."""
+    from lynx_amd import _ffi
+
+    label = "3x43691"
+    assert -(-3 * 43691 // _ffi.IMAGE_GRAD_CELLS) == 65
+    monkeypatch.setitem(ref.KERNEL_SCREENS, label, ref.SCREEN_OF_65_CHUNKS)
+    monkeypatch.setitem(ref.FLOAT32_RESTATEMENT_DEVIATION, label, ref.FLOAT32_RESTATEMENT_DEVIATION[LARGEST])
+    test_the_kernel_alone_against_the_restatement(lx, dtype, label, (2,), False)
+
+
 # ---------------------------------------------------------------------------------------------
 # 5. the same call twice
 # ---------------------------------------------------------------------------------------------

@@ -98,6 +98,19 @@ def test_what_the_float32_operations_cost_the_restatement():
             assert constants[label] / 2 <= value <= constants[label], (label, value, constants[label])  # (the margin is small)
 
 
+def test_the_float32_restatement_on_the_screen_of_65_chunks_stays_inside_the_gpu_tests_bounds():
+    """The GPU test of `ref.SCREEN_OF_65_CHUNKS` (a batch of 2: samples 0 and 1) asserts 8 x the deviations of 612 x 511; the
+    float32 restatement itself is inside them on these inputs.  Measured: entries 1.09e-7 and 1.06e-7 of 6.76e-7, loss
+    9.07e-8 and 5.73e-8 of 3.56e-7."""
+    from .test_gpu_trace_screens_grad import FLOAT32_FACTOR, LARGEST
+
+    bounds = FLOAT32_FACTOR * il.FLOAT32_ENTRY_DEVIATION[LARGEST], FLOAT32_FACTOR * il.FLOAT32_LOSS_DEVIATION[LARGEST]
+    for sample in range(2):
+        measured = float32_deviation(ref.SCREEN_OF_65_CHUNKS, sample)
+        print(f"65 chunks, sample {sample}: entries {measured[0]:.3e} (bound {bounds[0]:.3e}), loss {measured[1]:.3e} (bound {bounds[1]:.3e})")
+        assert measured[0] <= bounds[0] / 2 and measured[1] <= bounds[1] / 2, (sample, measured, bounds)
+
+
 # ---------------------------------------------------------------------------------------------
 # 3. refusals by value
 # ---------------------------------------------------------------------------------------------
