@@ -1827,6 +1827,59 @@ template <typename T, int MOM, bool FULL, int UNROLL, bool XPOSE> constexpr int 
   return 1;
 }
 
+// The dynamic LDS of k_track_direct, in bytes from its start: the scratch slab (wave tiles / reduction), the step table
+// [S][64] with S + 1 scalars left free behind it (the launch's LDS size is what it always was), the observers' sums
+// [2 * n_observers][256] float64 -- `total` ends there --, and for merged tables the stash of four floats per lane
+// (kEntryStash) on the next 16 bytes.  The kernel carves by it, plan_track and table_merged_form size the launch by it.
+struct TrackLds {
+  size_t steps, observers, total, stash, stash_bytes;
+};
+template <typename T>
+__host__ __device__ constexpr TrackLds track_lds_layout(size_t scratch_bytes, size_t S, size_t n_observers) {
+  TrackLds l{};
+  l.steps = scratch_bytes;
+  l.observers = (scratch_bytes + (S * (LYNX_STEP_STRIDE + 1) + 1) * sizeof(T) + 7) / 8 * 8;
+  l.total = l.observers + 2 * n_observers * 256 * sizeof(double);
+  l.stash = (l.total + 15) / 16 * 16;
+  l.stash_bytes = (size_t)kTrackThreads * 4 * sizeof(float);
+  return l;
+}
+
+// Where the tiles of a workgroup and the particles of a lane lie.
+template <int UNROLL, bool XPOSE>
+struct TileGeometry {
+  static constexpr int64_t kTile = (int64_t)kTrackThreads * UNROLL;  // particles of a workgroup's tile
+  static constexpr int64_t kWaveSpan = 64 * UNROLL;                  // XPOSE: particles of a wave tile
+  static constexpr int64_t kLaneStep = XPOSE ? 1 : kTrackThreads;    // the distance between a lane's UNROLL particles
+  int wave, lane, chunk, tiles_per_wg;
+  int64_t end;         // particles of a sample
+  int64_t lane_first;  // first particle of this lane within a tile
+  __device__ __forceinline__ TileGeometry(int tid, int wave_, int lane_, int chunk_, int tiles_per_wg_, int64_t end_)
+      : wave(wave_), lane(lane_), chunk(chunk_), tiles_per_wg(tiles_per_wg_), end(end_),
+        lane_first(XPOSE ? (int64_t)wave_ * kWaveSpan + (int64_t)lane_ * UNROLL : (int64_t)tid) {}
+  // This workgroup's `tiles_per_wg` tiles of 256*UNROLL particles: one contiguous stretch (taking every
+  // `chunks`-th tile instead, so that a sample's workgroups advance side by side, measured 2-5 % slower).
+  __device__ __forceinline__ int64_t tile_of(int it) const { return (int64_t)chunk * tiles_per_wg + it; }
+  __device__ __forceinline__ int64_t wave_base(int64_t tile) const { return tile * kTile + (int64_t)wave * kWaveSpan; }
+  __device__ __forceinline__ bool wave_whole(int64_t tile) const { return wave_base(tile) + kWaveSpan <= end; }  // wave-uniform
+  __device__ __forceinline__ int64_t first_of(int64_t tile) const { return tile * kTile + lane_first; }
+  // nothing of `tile` is left for this wave (XPOSE) / this lane
+  __device__ __forceinline__ bool past_end(int64_t tile) const { return XPOSE ? (wave_base(tile) >= end) : (first_of(tile) >= end); }
+};
+
+// fetch wave tile `tile` of the sample at `src` if it is whole (a cut one is read particle by particle when its turn comes)
+template <typename T, int UNROLL>
+__device__ __forceinline__ void wave_tile_fetch_if_whole(const TileGeometry<UNROLL, true> g, const T* src, int64_t tile,
+                                                         lynx_u32x4 (&v)[7]) {
+  if (g.wave_whole(tile)) wave_tile_fetch(src + g.wave_base(tile) * 7, g.lane, v);
+}
+
+// the single map of a one-run program on one particle: from registers (float32) or from the table in LDS (float64)
+template <typename T, int N> __device__ __forceinline__ void apply_single_map(const T (&m0)[N], const T* s_steps, T (&z)[7]) {
+  if constexpr (sizeof(T) == 4) apply_step<T>(m0, LYNX_STEP_RUN, 0, z);
+  else apply_step<T>(s_steps, LYNX_STEP_RUN, 0, z);
+}
+
 template <typename T, int MOM, bool FULL, int UNROLL, bool XPOSE>
 __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, UNROLL, XPOSE>())) void k_track_direct(
     LatticeDev lat, TrackArgs a, const T* __restrict__ /* energy_in: the builders read it */, const T* p_in, T* p_out,
@@ -1835,30 +1888,23 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
   static_assert(!XPOSE || (UNROLL * 7 * sizeof(T) == 112), "XPOSE: a lane owns 112 bytes");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   announce_tail(a);
+  const TrackLds lds = track_lds_layout<T>(a.lds_scratch_bytes, lat.n_steps, a.n_observers);
   unsigned char* s_scratch = smem_raw;                                 // wave tiles / reduction
-  T* s_steps = reinterpret_cast<T*>(smem_raw + a.lds_scratch_bytes);    // [S][64]
+  T* s_steps = reinterpret_cast<T*>(smem_raw + lds.steps);              // [S][64]
   float* stash = reinterpret_cast<float*>(smem_raw + a.stash_offset) + threadIdx.x * 4;  // used with merged tables only
-  // (S + 1 scalars behind the table are left free: the launch's LDS size is what it always was)
   // observers (active BPMs): every lane's float64 sums of x and y at each of them, [2 * n_observers][256]
-  double* s_obs = reinterpret_cast<double*>(smem_raw + ((a.lds_scratch_bytes + ((size_t)lat.n_steps * (LYNX_STEP_STRIDE + 1) + 1) * sizeof(T) + 7) / 8 * 8)) + threadIdx.x;
+  double* s_obs = reinterpret_cast<double*>(smem_raw + lds.observers) + threadIdx.x;
 
   const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
+  const int wave = tid >> 6, lane = tid & 63;  // (declared here, not behind `S`: the wave-tile kernels' schedule depends on it)
   const unsigned wg = a.reversed ? gridDim.x - 1u - blockIdx.x : blockIdx.x;
   const int64_t b = wg / a.chunks;
   const int chunk = wg % a.chunks;
   const int64_t end = a.n_particles;
   const int S = lat.n_steps;
-  // This workgroup's `a.tiles_per_wg` tiles of 256*UNROLL particles: one contiguous stretch (taking every
-  // `chunks`-th tile instead, so that a sample's workgroups advance side by side, measured 2-5 % slower).
-  constexpr int64_t kTile = (int64_t)kTrackThreads * UNROLL;
-  constexpr int64_t kWaveSpan = 64 * UNROLL;  // XPOSE: particles of a wave tile
-  // first particle of this lane within a tile, and the distance between its UNROLL particles
-  const int64_t lane_first = XPOSE ? (int64_t)wave * kWaveSpan + (int64_t)lane * UNROLL : (int64_t)tid;
-  constexpr int64_t kLaneStep = XPOSE ? 1 : kTrackThreads;
+  using Geometry = TileGeometry<UNROLL, XPOSE>;
+  const Geometry g(tid, wave, lane, chunk, a.tiles_per_wg, end);
   unsigned char* s_wave = s_scratch + wave * kWaveTileBytes;  // XPOSE: this wave's private tile
-#define LYNX_TILE_OF(IT) ((int64_t)chunk * a.tiles_per_wg + (IT))
-#define LYNX_WAVE_BASE(TILE) ((TILE)*kTile + (int64_t)wave * kWaveSpan)
 
   // Software pipeline: the loads of a tile are issued one iteration ahead (the first ones
   // right here, before the step table is fetched), so a workgroup always has a tile of HBM
@@ -1867,17 +1913,14 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
   T* dst = p_out + b * end * 7;
   T zn[XPOSE ? 1 : UNROLL][7];   // !XPOSE: the next tile's particles
   lynx_u32x4 vn[XPOSE ? 7 : 1];  //  XPOSE: the next wave tile, flat
-  {
-    const int64_t tile = LYNX_TILE_OF(0);
-    if constexpr (XPOSE) {
-      if (LYNX_WAVE_BASE(tile) + kWaveSpan <= end) wave_tile_fetch(src + LYNX_WAVE_BASE(tile) * 7, lane, vn);
-    } else {
-      const int64_t i0 = tile * kTile + lane_first;
+  if constexpr (XPOSE) {
+    wave_tile_fetch_if_whole(g, src, g.tile_of(0), vn);
+  } else {
+    const int64_t i0 = g.first_of(g.tile_of(0));
 #pragma unroll
-      for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = i0 + (int64_t)u * kLaneStep;
-        load_particle(src + (i < end ? i : (i0 < end ? i0 : 0)) * 7, zn[u]);
-      }
+    for (int u = 0; u < UNROLL; ++u) {
+      const int64_t i = i0 + (int64_t)u * Geometry::kLaneStep;
+      load_particle(src + (i < end ? i : (i0 < end ? i0 : 0)) * 7, zn[u]);
     }
   }
 
@@ -1911,15 +1954,18 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
   constexpr bool kLdsResident = XPOSE && sizeof(T) == 8;
 
   for (int it = 0; it < a.tiles_per_wg; ++it) {
-    const int64_t tile = LYNX_TILE_OF(it);
-    const int64_t i0 = tile * kTile + lane_first;
-    if (XPOSE ? (LYNX_WAVE_BASE(tile) >= end) : (i0 >= end)) break;
+    const int64_t tile = g.tile_of(it);
+    const int64_t i0 = g.first_of(tile);
+    if (g.past_end(tile)) break;
     if (!kMapInRegs) LYNX_FORGET();  // fp64: keep the map in LDS, not in 98 hoisted VGPRs
-    const bool full = XPOSE && (LYNX_WAVE_BASE(tile) + kWaveSpan <= end);  // wave-uniform
+    const bool full = XPOSE && g.wave_whole(tile);  // wave-uniform
     sums.begin_iteration();
 
-    if constexpr (kLdsResident) {
-      T* mine = reinterpret_cast<T*>(s_wave) + lane * (UNROLL * 7);  // this lane's particles inside the tile
+    // The three forms of the tile loop: wave tiles resident in LDS (float64 XPOSE), wave tiles in registers (float32
+    // XPOSE), strided.  Each is kept whole in this body: a form moved into a function of its own is simplified before it
+    // is inlined and comes back as other instructions (NOTES.md, "k_track_direct: the geometry, the layout, ...").
+    if constexpr (kLdsResident) {  // -- wave tiles resident in LDS
+      T* mine =reinterpret_cast<T*>(s_wave) + lane * (UNROLL * 7);  // this lane's particles inside the tile
       if (full) {
         lynx_u32x4* l = reinterpret_cast<lynx_u32x4*>(s_wave);
         wave_fence();
@@ -1927,10 +1973,7 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
         for (int k = 0; k < 7; ++k) l[k * 64 + lane] = vn[k];
         wave_fence();
       }
-      if (it + 1 < a.tiles_per_wg) {
-        const int64_t tn = LYNX_TILE_OF(it + 1);
-        if (LYNX_WAVE_BASE(tn) + kWaveSpan <= end) wave_tile_fetch(src + LYNX_WAVE_BASE(tn) * 7, lane, vn);
-      }
+      if (it + 1 < a.tiles_per_wg) wave_tile_fetch_if_whole(g, src, g.tile_of(it + 1), vn);
 #pragma unroll 1
       for (int u = 0; u < UNROLL; ++u) {  // one particle at a time: register pressure, not issue rate, is what binds here
         const int64_t i = i0 + u;
@@ -1942,7 +1985,7 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
           load_particle(src + (i < end ? i : end - 1) * 7, z[0]);
         }
         if (one_run) {
-          apply_step<T>(s_steps, LYNX_STEP_RUN, 0, z[0]);
+          apply_single_map(m0, s_steps, z[0]);
         } else {
           const bool alive[1] = {i < end};
           apply_program_lane<T, 1, false>(lat, S, g_steps, s_steps, z, a.n_observers ? s_obs : nullptr, &alive);
@@ -1969,31 +2012,28 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
         wave_fence();
 #pragma unroll
         for (int k = 0; k < 7; ++k) vo[k] = l[k * 64 + lane];
-        wave_tile_store(dst + LYNX_WAVE_BASE(tile) * 7, lane, vo);
+        wave_tile_store(dst + g.wave_base(tile) * 7, lane, vo);
       }
     } else {
       T z[UNROLL][7];
-      if constexpr (XPOSE) {
+      if constexpr (XPOSE) {  // -- wave tiles in registers: how a tile becomes particles, and the request for the next
         if (full) {
           wave_tile_to_particles<T, UNROLL>(vn, s_wave, lane, z);
         } else {
 #pragma unroll
           for (int u = 0; u < UNROLL; ++u) load_particle(src + (i0 + u < end ? i0 + u : end - 1) * 7, z[u]);
         }
-        if (it + 1 < a.tiles_per_wg) {
-          const int64_t tn = LYNX_TILE_OF(it + 1);
-          if (LYNX_WAVE_BASE(tn) + kWaveSpan <= end) wave_tile_fetch(src + LYNX_WAVE_BASE(tn) * 7, lane, vn);
-        }
-      } else {
+        if (it + 1 < a.tiles_per_wg) wave_tile_fetch_if_whole(g, src, g.tile_of(it + 1), vn);
+      } else {  // -- strided: the particles fetched one iteration ago, and the loads of the next tile
 #pragma unroll
         for (int u = 0; u < UNROLL; ++u)
 #pragma unroll
           for (int c = 0; c < 7; ++c) z[u][c] = zn[u][c];
         if (it + 1 < a.tiles_per_wg) {  // prefetch the next tile of this workgroup
-          const int64_t j0 = LYNX_TILE_OF(it + 1) * kTile + lane_first;
+          const int64_t j0 = g.first_of(g.tile_of(it + 1));
 #pragma unroll
           for (int u = 0; u < UNROLL; ++u) {
-            const int64_t j = j0 + (int64_t)u * kLaneStep;
+            const int64_t j = j0 + (int64_t)u * Geometry::kLaneStep;
             load_particle(src + (j < end ? j : i0) * 7, zn[u]);
           }
         }
@@ -2001,17 +2041,14 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
       if (!one_run) {
         bool alive[UNROLL];
 #pragma unroll
-        for (int u = 0; u < UNROLL; ++u) alive[u] = i0 + (int64_t)u * kLaneStep < end;
+        for (int u = 0; u < UNROLL; ++u) alive[u] = i0 + (int64_t)u * Geometry::kLaneStep < end;
         apply_program_lane<T, UNROLL, kMapInRegs>(lat, S, g_steps, s_steps, z,
                                                   a.n_observers ? s_obs : nullptr, &alive, stash);
       }
 #pragma unroll
       for (int u = 0; u < UNROLL; ++u) {
-        const int64_t i = i0 + (int64_t)u * kLaneStep;
-        if (one_run) {
-          if (kMapInRegs) apply_step<T>(m0, LYNX_STEP_RUN, 0, z[u]);
-          else apply_step<T>(s_steps, LYNX_STEP_RUN, 0, z[u]);
-        }
+        const int64_t i = i0 + (int64_t)u * Geometry::kLaneStep;
+        if (one_run) apply_single_map(m0, s_steps, z[u]);
         if (MOM && it == 0 && u == 0) {
           // reference point of this wave's sums: the tracked particle of its first lane (which exists
           // whenever any of the wave's particles does: indices grow with the lane)
@@ -2027,14 +2064,12 @@ __global__ __launch_bounds__(kTrackThreads, (track_waves_per_simd<T, MOM, FULL, 
         if (a.store && full) {
           lynx_u32x4 vo[7];
           wave_tile_from_particles<T, UNROLL>(z, s_wave, lane, vo);
-          wave_tile_store(dst + LYNX_WAVE_BASE(tile) * 7, lane, vo);
+          wave_tile_store(dst + g.wave_base(tile) * 7, lane, vo);
         }
       }
     }
     sums.end_iteration();
   }
-#undef LYNX_TILE_OF
-#undef LYNX_WAVE_BASE
 
   if (a.n_observers) {
     // this workgroup's sums of x and y at every observer: lanes in lane order, float64 -- deterministic

@@ -1579,7 +1579,7 @@ static TrackPlan plan_track(lynx_ctx* ctx, const lynx_lattice* lat, int64_t B, i
   scratch = (scratch + 15) / 16 * 16;
   p.a.lds_scratch_bytes = (int32_t)scratch;
   p.a.n_observers = lat ? lat->n_observers : 0;
-  p.lds = (scratch + ((size_t)S * LYNX_STEP_STRIDE + S + 1) * sizeof(T) + 7) / 8 * 8 + (size_t)2 * p.a.n_observers * 256 * sizeof(double);
+  p.lds = track_lds_layout<T>(scratch, (size_t)S, (size_t)p.a.n_observers).total;
   p.grid = (unsigned)(B * chunks);
   return p;
 }
@@ -1605,51 +1605,53 @@ static int launch_streaming(lynx_ctx* ctx, const TrackPlan& p, K kernel, size_t 
   return LYNX_OK;
 }
 
+// What a launch of k_track_direct is made of, whichever instantiation it takes.
+struct DirectLaunch {
+  lynx_ctx* ctx;
+  const TrackPlan& p;
+  const LatticeDev& lv;
+  const void *d_energy_in, *d_p_in;
+  void *d_p_out, *d_energy_out;
+  const void* d_steps;
+  double *d_partials, *d_obs;
+};
+
 template <typename T, int MOM, bool FULL, int UNROLL, bool XPOSE>
-static int launch_direct_inst(lynx_ctx* ctx, const TrackPlan& p, const LatticeDev& lv, const void* d_energy_in,
-                              const void* d_p_in, void* d_p_out, void* d_energy_out, const void* d_steps,
-                              double* d_partials, double* d_obs) {
-  return launch_streaming(ctx, p, k_track_direct<T, MOM, FULL, UNROLL, XPOSE>, p.lds, lv, p.a, (const T*)d_energy_in,
-                          (const T*)d_p_in, (T*)d_p_out, (T*)d_energy_out, (const T*)d_steps, d_partials, d_obs);
+static int launch_direct_inst(const DirectLaunch& l) {
+  return launch_streaming(l.ctx, l.p, k_track_direct<T, MOM, FULL, UNROLL, XPOSE>, l.p.lds, l.lv, l.p.a, (const T*)l.d_energy_in,
+                          (const T*)l.d_p_in, (T*)l.d_p_out, (T*)l.d_energy_out, (const T*)l.d_steps, l.d_partials, l.d_obs);
 }
 
-#define LYNX_LAUNCH_ARGS ctx, p, lv, d_energy_in, d_p_in, d_p_out, d_energy_out, d_steps, d_partials, d_obs
-#define LYNX_LAUNCH_PARAMS                                                                                     \
-  lynx_ctx *ctx, const TrackPlan &p, const LatticeDev &lv, const void *d_energy_in, const void *d_p_in,        \
-      void *d_p_out, void *d_energy_out, const void *d_steps, double *d_partials, double *d_obs
-
 template <typename T, int MOM, bool FULL, int U>
-static int launch_direct_mu(LYNX_LAUNCH_PARAMS) {
+static int launch_direct_mu(const DirectLaunch& l) {
   if constexpr (U * 7 * sizeof(T) == 112) {
-    if (p.xpose) return launch_direct_inst<T, MOM, FULL, U, true>(LYNX_LAUNCH_ARGS);
+    if (l.p.xpose) return launch_direct_inst<T, MOM, FULL, U, true>(l);
   }
-  return launch_direct_inst<T, MOM, FULL, U, false>(LYNX_LAUNCH_ARGS);
+  return launch_direct_inst<T, MOM, FULL, U, false>(l);
 }
 
 template <typename T, int MOM, bool FULL>
-static int launch_direct_m(LYNX_LAUNCH_PARAMS) {
-  switch (p.unroll) {
-    case 1: return launch_direct_mu<T, MOM, FULL, 1>(LYNX_LAUNCH_ARGS);
-    case 2: return launch_direct_mu<T, MOM, FULL, 2>(LYNX_LAUNCH_ARGS);
+static int launch_direct_m(const DirectLaunch& l) {
+  switch (l.p.unroll) {
+    case 1: return launch_direct_mu<T, MOM, FULL, 1>(l);
+    case 2: return launch_direct_mu<T, MOM, FULL, 2>(l);
     default:
-      if constexpr (sizeof(T) == 4) return launch_direct_mu<T, MOM, FULL, 4>(LYNX_LAUNCH_ARGS);
-      else return fail(ctx, LYNX_ERR_INVALID, "float64: at most 2 particles per lane");
+      if constexpr (sizeof(T) == 4) return launch_direct_mu<T, MOM, FULL, 4>(l);
+      else return fail(l.ctx, LYNX_ERR_INVALID, "float64: at most 2 particles per lane");
   }
 }
 
 template <typename T>
-static int launch_direct(LYNX_LAUNCH_PARAMS, bool moments) {
-  const int mom = moments ? p.mom_mode : 0;
-  if (mom == 0) return launch_direct_m<T, 0, false>(LYNX_LAUNCH_ARGS);
+static int launch_direct(const DirectLaunch& l, bool moments) {
+  const int mom = moments ? l.p.mom_mode : 0;
+  if (mom == 0) return launch_direct_m<T, 0, false>(l);
   if constexpr (sizeof(T) == 4) {
-    if (mom == 3) return p.full_cov ? launch_direct_m<T, 3, true>(LYNX_LAUNCH_ARGS) : launch_direct_m<T, 3, false>(LYNX_LAUNCH_ARGS);
-    return p.full_cov ? launch_direct_m<T, 2, true>(LYNX_LAUNCH_ARGS) : launch_direct_m<T, 2, false>(LYNX_LAUNCH_ARGS);
+    if (mom == 3) return l.p.full_cov ? launch_direct_m<T, 3, true>(l) : launch_direct_m<T, 3, false>(l);
+    return l.p.full_cov ? launch_direct_m<T, 2, true>(l) : launch_direct_m<T, 2, false>(l);
   } else {
-    return p.full_cov ? launch_direct_m<T, 1, true>(LYNX_LAUNCH_ARGS) : launch_direct_m<T, 1, false>(LYNX_LAUNCH_ARGS);
+    return l.p.full_cov ? launch_direct_m<T, 1, true>(l) : launch_direct_m<T, 1, false>(l);
   }
 }
-#undef LYNX_LAUNCH_ARGS
-#undef LYNX_LAUNCH_PARAMS
 
 // ---- multi-step float32 programs as units (lynx_units.hpp) ------------------------------------
 
@@ -1713,33 +1715,38 @@ static int ensure_units_plan(lynx_ctx* ctx, lynx_lattice* lat, bool merged) {
   return LYNX_OK;
 }
 
+// What a launch of the unit kernels is made of, whichever instantiation it takes.
+struct UnitsLaunch {
+  lynx_ctx* ctx;
+  const TrackPlan& p;
+  int32_t U, S;
+  const void* d_p_in;
+  void *d_p_out, *d_energy_out;
+  const void *d_steps, *d_units, *d_extras;
+  double* d_partials;
+};
+
 template <int MOM, bool FULL, int PAIRS, bool PAIR_FORM = false>
-static int launch_units_inst(lynx_ctx* ctx, const TrackPlan& p, int32_t U, int32_t S, const void* d_p_in, void* d_p_out,
-                             void* d_energy_out, const void* d_steps, const void* d_units, const void* d_extras,
-                             double* d_partials) {
-  const size_t lds = units_lds_bytes((size_t)p.a.lds_scratch_bytes, U);
+static int launch_units_inst(const UnitsLaunch& l) {
+  const size_t lds = units_lds_bytes((size_t)l.p.a.lds_scratch_bytes, l.U);
   auto kernel = k_track_units<MOM, FULL, PAIRS>;
   if constexpr (PAIR_FORM) kernel = k_track_unit_pairs<MOM, FULL>;
-  return launch_streaming(ctx, p, kernel, lds, p.a, U, S, (const float*)d_p_in, (float*)d_p_out, (float*)d_energy_out,
-                          (const float*)d_steps, (const float*)d_units, (const float*)d_extras, d_partials);
+  return launch_streaming(l.ctx, l.p, kernel, lds, l.p.a, l.U, l.S, (const float*)l.d_p_in, (float*)l.d_p_out, (float*)l.d_energy_out,
+                          (const float*)l.d_steps, (const float*)l.d_units, (const float*)l.d_extras, l.d_partials);
 }
 
-static int launch_units(lynx_ctx* ctx, const TrackPlan& p, int32_t U, int32_t S, const void* d_p_in, void* d_p_out,
-                        void* d_energy_out, const void* d_steps, const void* d_units, const void* d_extras,
-                        double* d_partials, bool moments, bool pair_form) {
-#define LYNX_UNITS_ARGS ctx, p, U, S, d_p_in, d_p_out, d_energy_out, d_steps, d_units, d_extras, d_partials
+static int launch_units(const UnitsLaunch& l, bool moments, bool pair_form) {
+  const TrackPlan& p = l.p;
   // every unit proposed as a merged [run, cavity] pair of class U: k_track_unit_pairs
-  if (pair_form)
-    return moments ? launch_units_inst<3, false, 1, true>(LYNX_UNITS_ARGS) : launch_units_inst<0, false, 1, true>(LYNX_UNITS_ARGS);
+  if (pair_form) return moments ? launch_units_inst<3, false, 1, true>(l) : launch_units_inst<0, false, 1, true>(l);
   if (p.unroll == 4) {  // two pairs per lane
-    if (!moments) return launch_units_inst<0, false, 2>(LYNX_UNITS_ARGS);
-    if (p.mom_mode == 3) return p.full_cov ? launch_units_inst<3, true, 2>(LYNX_UNITS_ARGS) : launch_units_inst<3, false, 2>(LYNX_UNITS_ARGS);
-    return p.full_cov ? launch_units_inst<2, true, 2>(LYNX_UNITS_ARGS) : launch_units_inst<2, false, 2>(LYNX_UNITS_ARGS);
+    if (!moments) return launch_units_inst<0, false, 2>(l);
+    if (p.mom_mode == 3) return p.full_cov ? launch_units_inst<3, true, 2>(l) : launch_units_inst<3, false, 2>(l);
+    return p.full_cov ? launch_units_inst<2, true, 2>(l) : launch_units_inst<2, false, 2>(l);
   }
-  if (!moments) return launch_units_inst<0, false, 1>(LYNX_UNITS_ARGS);
-  if (p.mom_mode == 3) return p.full_cov ? launch_units_inst<3, true, 1>(LYNX_UNITS_ARGS) : launch_units_inst<3, false, 1>(LYNX_UNITS_ARGS);
-  return p.full_cov ? launch_units_inst<2, true, 1>(LYNX_UNITS_ARGS) : launch_units_inst<2, false, 1>(LYNX_UNITS_ARGS);
-#undef LYNX_UNITS_ARGS
+  if (!moments) return launch_units_inst<0, false, 1>(l);
+  if (p.mom_mode == 3) return p.full_cov ? launch_units_inst<3, true, 1>(l) : launch_units_inst<3, false, 1>(l);
+  return p.full_cov ? launch_units_inst<2, true, 1>(l) : launch_units_inst<2, false, 1>(l);
 }
 
 // The step table of one track call (S > 0): the slot of the ring it took, how it was built, and what the streaming kernel
@@ -1769,9 +1776,9 @@ static void table_merged_form(const lynx_ctx* ctx, const lynx_lattice* lat, int3
   p.a.merged_pairs = has_pair && sizeof(T) == 4 && p.unroll == 2 &&
                      !(flags & LYNX_TRACK_SEQUENTIAL_STEPS) && ctx->knobs.merge_steps;
   if (p.a.merged_pairs) {  // four floats of LDS per lane for pairs that take the rows form (kEntryStash)
-    p.lds = (p.lds + 15) / 16 * 16;
-    p.a.stash_offset = (int32_t)p.lds;
-    p.lds += (size_t)kTrackThreads * 4 * sizeof(float);
+    const TrackLds l = track_lds_layout<T>((size_t)p.a.lds_scratch_bytes, (size_t)S, (size_t)p.a.n_observers);
+    p.a.stash_offset = (int32_t)l.stash;
+    p.lds = l.stash + l.stash_bytes;
   }
 }
 
@@ -2031,9 +2038,9 @@ static int track_particles_t(lynx_ctx* ctx, lynx_lattice* lat, const LatticeDev&
     if (ctx->knobs.unit_pairs == 2 && !pair_form)
       rc = fail(ctx, LYNX_ERR_INVALID, "LYNX_UNIT_PAIRS=2: this call does not take the kernel for lattices of [run, cavity] pairs");
     else
-      rc = launch_units(ctx, p, t.n_units, S, d_p_in, d_p_out, d_energy_out, t.d_steps, t.d_units, t.d_extras, d_partials, moments, pair_form);
+      rc = launch_units({ctx, p, t.n_units, S, d_p_in, d_p_out, d_energy_out, t.d_steps, t.d_units, t.d_extras, d_partials}, moments, pair_form);
   } else {
-    rc = launch_direct<T>(ctx, p, lv, d_energy_in, d_p_in, d_p_out, d_energy_out, t.d_steps, d_partials, d_obs, moments);
+    rc = launch_direct<T>({ctx, p, lv, d_energy_in, d_p_in, d_p_out, d_energy_out, t.d_steps, d_partials, d_obs}, moments);
   }
   if (rc) {
     if (t.tail) --ctx->tail_seq;  // nothing will announce this number: a later build must not wait for it
