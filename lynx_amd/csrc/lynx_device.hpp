@@ -139,6 +139,27 @@ __host__ __device__ inline size_t build_scratch_bytes(int chunk, size_t elem_siz
   return (b + 15) / 16 * 16;
 }
 
+// The dynamic LDS of the workgroup build (k_build*, k_track_moments*): the build's scratch, the step table [S][64], the
+// energy in front of every step and behind the last [S + 1], the caller's tail; each offset counts from the region in front
+// (NOTES.md).  build_to_table and track_moments_sample carve by it; the three host callers size by `total`.
+struct BuildLds {
+  size_t steps;                // bytes from the start of the LDS (the scratch): the step table
+  size_t energies, tail, end;  // scalars of T: the energies from the table, the tail from the energies, the end from the tail
+  size_t total;                // bytes, all of it
+};
+__host__ __device__ inline BuildLds build_lds_layout(int chunk, size_t n_steps, size_t elem_size, size_t tail_scalars) {
+  BuildLds l{};
+  l.steps = build_scratch_bytes(chunk, elem_size);
+  l.energies = n_steps * LYNX_STEP_STRIDE;
+  l.tail = n_steps + 1;
+  l.end = tail_scalars;
+  l.total = l.steps + (l.energies + l.tail + l.end) * elem_size;
+  return l;
+}
+// The tail of the ParameterBeam kernels: mu [8], C [49], X = C M^T [49] -- and 16 scalars nobody uses, which the launch
+// has always provided (the LDS size of a launch is part of what was measured; it stays).
+constexpr int kMomentsTailScalars = 8 + 49 + 49 + 16;
+
 // Row r of D = A . Bm (7x7, row-major, float64), ascending k -- one lane per output row
 __device__ __forceinline__ void mat_product_row(const double* A, const double* Bm, double* D, int r) {
   double a[7], acc[7];
@@ -1240,8 +1261,9 @@ __device__ __forceinline__ void build_to_table(const LatticeDev& lat, const T* _
                                                T* __restrict__ steps_out, T* __restrict__ energy_out,
                                                int chunk, int merge_pairs) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  T* s_steps = reinterpret_cast<T*>(smem_raw + build_scratch_bytes(chunk, sizeof(T)));
-  T* s_energy = s_steps + (size_t)lat.n_steps * LYNX_STEP_STRIDE;
+  const BuildLds lds = build_lds_layout(chunk, (size_t)lat.n_steps, sizeof(T), 0);
+  T* s_steps = reinterpret_cast<T*>(smem_raw + lds.steps);
+  T* s_energy = s_steps + lds.energies;
   const int64_t b = blockIdx.x;
   // zero the coefficient slots so that run steps have defined padding
   for (int i = threadIdx.x; i < lat.n_steps * LYNX_STEP_STRIDE; i += blockDim.x) s_steps[i] = T(0);
@@ -2128,89 +2150,127 @@ __device__ __forceinline__ void write_moment_record(const double* s, double* dst
 }
 
 // THREADS / 36 sets of 36 threads; STAGE rows staged per pass (STAGE / sets per set).  One shape is used:
-//   <FINAL, 256, 70>    7 sets, 22 KB of LDS: the samples' records, or the groups of a level.
+//   <256, 70>    7 sets, 22 KB of LDS: the samples' records, or the groups of a level.  The two kernels share what follows.
+struct ReduceLds {
+  double *rows, *set, *s;  // [STAGE][36] staged rows; [kSets][36] the sets' sums; [36] the sums ([28..35]: the reference point)
+};
+template <int THREADS, int STAGE>
+__device__ __forceinline__ ReduceLds reduce_lds_carve(unsigned char* smem_raw) {
+  double* rows = reinterpret_cast<double*>(smem_raw);
+  return {rows, rows + STAGE * kPartialStride, rows + (STAGE + THREADS / kPartialStride) * kPartialStride};
+}
+
+// j in [7, 28): the pair (mi <= mj) of components of second moment j (row-major upper triangle); (0, 0) for any other j
+struct MomentPair { int mi, mj; };
+__device__ __forceinline__ MomentPair second_moment_pair(int j) {
+  MomentPair p{0, 0};
+  if (j >= 7 && j < 28) {
+    int k = j - 7, len = 6;
+    while (k >= len) { k -= len; --len; ++p.mi; }
+    p.mj = p.mi + k;
+  }
+  return p;
+}
+
+// Up to STAGE rows from row `base` of `src` on into the staging area with coalesced loads: all of a thread's loads are issued before the
+// first one is waited for.  (The barriers around it are the caller's.)
+template <int THREADS, int STAGE>
+__device__ __forceinline__ void reduce_stage_rows(const double* __restrict__ src, int base, int n_stage, double* s_rows, int tid) {
+  constexpr int kPerThread = (STAGE * kPartialStride + THREADS - 1) / THREADS;
+  double staged[kPerThread];
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int i = tid + k * THREADS;
+    staged[k] = i < n_stage * kPartialStride ? src[(int64_t)base * kPartialStride + i] : 0.0;
+  }
+#pragma unroll
+  for (int k = 0; k < kPerThread; ++k) {
+    const int i = tid + k * THREADS;
+    if (i < n_stage * kPartialStride) s_rows[i] = staged[k];
+  }
+}
+
+// The reference point of the rows that follow is the first staged row's (s[35] is set by reduce_fold_sets)
+__device__ __forceinline__ void reduce_pick_reference(const ReduceLds l, int tid) {
+  if (tid < 8) l.s[28 + tid] = tid < 7 ? l.rows[28 + tid] : 0.0;
+}
+
+// Rows [0, n) staged, reference point picked: `v` plus this thread's share of the sums -- value j of rows q, q + kSets, ...
+// moved to the reference point.  moment_slot_moved with everything that depends on j alone taken out of the row loop
+// (which pair of components a second moment belongs to, the reference point's two components): what is left per row is
+// six LDS reads and five multiply-adds, rows independent of each other.
+template <int kSets>
+__device__ __forceinline__ double reduce_add_staged(const ReduceLds l, int n, int q, int j, MomentPair p, double v) {
+  if (q < kSets && (j < 28 || j == 35)) {
+    if (j == 6 || j == 35) {
+#pragma unroll 4
+      for (int r = q; r < n; r += kSets) v += l.rows[r * kPartialStride + j];
+    } else if (j < 6) {
+      const double c0j = l.s[28 + j];
+#pragma unroll 4
+      for (int r = q; r < n; r += kSets) {
+        const double* row = l.rows + r * kPartialStride;
+        v += row[j] + row[35] * (row[28 + j] - c0j);
+      }
+    } else {
+      const double c0i = l.s[28 + p.mi], c0j = l.s[28 + p.mj];
+#pragma unroll 4
+      for (int r = q; r < n; r += kSets) {
+        const double* row = l.rows + r * kPartialStride;
+        const double ei = row[28 + p.mi] - c0i, ej = row[28 + p.mj] - c0j;
+        v += row[j] + ei * row[p.mj] + row[p.mi] * ej + row[35] * ei * ej;
+      }
+    }
+  }
+  return v;
+}
+
+// The sets' sums added in set order into s[0..27] and s[35]; every thread sees them on return
+template <int kSets>
+__device__ __forceinline__ void reduce_fold_sets(const ReduceLds l, int q, int j, int tid, double v) {
+  if (q < kSets) l.set[q * kPartialStride + j] = v;
+  __syncthreads();
+  if (tid < kPartialStride && (tid < 28 || tid == 35)) {
+    double t = 0.0;
+#pragma unroll
+    for (int k = 0; k < kSets; ++k) t += l.set[k * kPartialStride + tid];
+    l.s[tid] = t;
+  }
+  __syncthreads();
+}
+
+// (The level loop itself -- a group's rows [lo, hi), STAGE at a time, about the reference point of its first row -- stands
+// in both kernels: as a seventh function it made each of them some fifty instructions longer.)
 template <bool FINAL, int THREADS, int STAGE>
 __global__ __launch_bounds__(THREADS) void k_reduce_moments(const double* __restrict__ in, int rows, int rows_per_group,
                                                              int groups, double* __restrict__ out) {
   constexpr int kSets = THREADS / kPartialStride;
   static_assert(STAGE % kSets == 0, "every set takes the same number of staged rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* s_rows = reinterpret_cast<double*>(smem_raw);        // [STAGE][36]
-  double* s_set = s_rows + STAGE * kPartialStride;              // [kSets][36]
-  double* s = s_set + kSets * kPartialStride;                   // [36]
+  const ReduceLds l = reduce_lds_carve<THREADS, STAGE>(smem_raw);
   const int64_t b = blockIdx.x / groups;
   const int g = blockIdx.x % groups;
   const int tid = threadIdx.x;
   const int q = tid / kPartialStride, j = tid - q * kPartialStride;
+  const MomentPair p = second_moment_pair(j);
   const int lo = g * rows_per_group;
   const int hi = (lo + rows_per_group) < rows ? (lo + rows_per_group) : rows;
   const double* src = in + (b * (int64_t)rows + lo) * kPartialStride;
   double v = 0.0;
-  int mi = 0, mj = 0;  // j in [7, 28): the pair (mi <= mj) of components of second moment j (row-major upper triangle)
-  if (j >= 7 && j < 28) {
-    int k = j - 7, len = 6;
-    while (k >= len) { k -= len; --len; ++mi; }
-    mj = mi + k;
-  }
   for (int base = 0; base < hi - lo; base += STAGE) {
     const int n_stage = (hi - lo - base) < STAGE ? (hi - lo - base) : STAGE;
     __syncthreads();  // the previous pass is done with the staging area
-    {
-      // all of a thread's loads are issued before the first one is waited for
-      constexpr int kPerThread = (STAGE * kPartialStride + THREADS - 1) / THREADS;
-      double staged[kPerThread];
-#pragma unroll
-      for (int k = 0; k < kPerThread; ++k) {
-        const int i = tid + k * THREADS;
-        staged[k] = i < n_stage * kPartialStride ? src[(int64_t)base * kPartialStride + i] : 0.0;
-      }
-#pragma unroll
-      for (int k = 0; k < kPerThread; ++k) {
-        const int i = tid + k * THREADS;
-        if (i < n_stage * kPartialStride) s_rows[i] = staged[k];
-      }
-    }
+    reduce_stage_rows<THREADS, STAGE>(src, base, n_stage, l.rows, tid);
     __syncthreads();
-    if (base == 0 && tid < 8) s[28 + tid] = tid < 7 ? s_rows[28 + tid] : 0.0;  // the group's reference point (s[35] set below)
+    if (base == 0) reduce_pick_reference(l, tid);
     __syncthreads();
-    if (q < kSets && (j < 28 || j == 35)) {
-      // moment_slot_moved with everything that depends on j alone taken out of the row loop (which pair of
-      // components a second moment belongs to, the reference point's two components): what is left per row
-      // is six LDS reads and five multiply-adds, rows independent of each other
-      if (j == 6 || j == 35) {
-#pragma unroll 4
-        for (int r = q; r < n_stage; r += kSets) v += s_rows[r * kPartialStride + j];
-      } else if (j < 6) {
-        const double c0j = s[28 + j];
-#pragma unroll 4
-        for (int r = q; r < n_stage; r += kSets) {
-          const double* row = s_rows + r * kPartialStride;
-          v += row[j] + row[35] * (row[28 + j] - c0j);
-        }
-      } else {
-        const double c0i = s[28 + mi], c0j = s[28 + mj];
-#pragma unroll 4
-        for (int r = q; r < n_stage; r += kSets) {
-          const double* row = s_rows + r * kPartialStride;
-          const double ei = row[28 + mi] - c0i, ej = row[28 + mj] - c0j;
-          v += row[j] + ei * row[mj] + row[mi] * ej + row[35] * ei * ej;
-        }
-      }
-    }
+    v = reduce_add_staged<kSets>(l, n_stage, q, j, p, v);
   }
-  if (q < kSets) s_set[q * kPartialStride + j] = v;
-  __syncthreads();
-  if (tid < kPartialStride && (tid < 28 || tid == 35)) {
-    double t = 0.0;
-#pragma unroll
-    for (int k = 0; k < kSets; ++k) t += s_set[k * kPartialStride + tid];
-    s[tid] = t;
-  }
-  __syncthreads();
+  reduce_fold_sets<kSets>(l, q, j, tid, v);
   if (FINAL) {
-    write_moment_record(s, out + b * LYNX_MOMENT_STRIDE, tid);
+    write_moment_record(l.s, out + b * LYNX_MOMENT_STRIDE, tid);
   } else if (tid < kPartialStride) {
-    out[(b * (int64_t)groups + g) * kPartialStride + tid] = s[tid];
+    out[(b * (int64_t)groups + g) * kPartialStride + tid] = l.s[tid];
   }
 }
 
@@ -2234,56 +2294,13 @@ __global__ __launch_bounds__(THREADS) void k_reduce_moments_ticket(const double*
   constexpr int kSets = THREADS / kPartialStride;
   static_assert(STAGE % kSets == 0 && STAGE >= 64, "every set takes the same number of staged rows; the second level fits one pass");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  double* s_rows = reinterpret_cast<double*>(smem_raw);        // [STAGE][36]
-  double* s_set = s_rows + STAGE * kPartialStride;              // [kSets][36]
-  double* s = s_set + kSets * kPartialStride;                   // [36]
+  const ReduceLds l = reduce_lds_carve<THREADS, STAGE>(smem_raw);
   __shared__ int s_last;
   const int64_t b = blockIdx.x / groups;
   const int g = blockIdx.x % groups;
   const int tid = threadIdx.x;
   const int q = tid / kPartialStride, j = tid - q * kPartialStride;
-  int mi = 0, mj = 0;
-  if (j >= 7 && j < 28) {
-    int k = j - 7, len = 6;
-    while (k >= len) { k -= len; --len; ++mi; }
-    mj = mi + k;
-  }
-  // rows [0, n) staged in s_rows, reference point = the first one's: this thread's share of the sums (moment_slot_moved)
-  const auto add_staged = [&](int n, double v) {
-    if (q < kSets && (j < 28 || j == 35)) {
-      if (j == 6 || j == 35) {
-#pragma unroll 4
-        for (int r = q; r < n; r += kSets) v += s_rows[r * kPartialStride + j];
-      } else if (j < 6) {
-        const double c0j = s[28 + j];
-#pragma unroll 4
-        for (int r = q; r < n; r += kSets) {
-          const double* row = s_rows + r * kPartialStride;
-          v += row[j] + row[35] * (row[28 + j] - c0j);
-        }
-      } else {
-        const double c0i = s[28 + mi], c0j = s[28 + mj];
-#pragma unroll 4
-        for (int r = q; r < n; r += kSets) {
-          const double* row = s_rows + r * kPartialStride;
-          const double ei = row[28 + mi] - c0i, ej = row[28 + mj] - c0j;
-          v += row[j] + ei * row[mj] + row[mi] * ej + row[35] * ei * ej;
-        }
-      }
-    }
-    return v;
-  };
-  const auto fold_sets = [&](double v) {
-    if (q < kSets) s_set[q * kPartialStride + j] = v;
-    __syncthreads();
-    if (tid < kPartialStride && (tid < 28 || tid == 35)) {
-      double t = 0.0;
-#pragma unroll
-      for (int k = 0; k < kSets; ++k) t += s_set[k * kPartialStride + tid];
-      s[tid] = t;
-    }
-    __syncthreads();
-  };
+  const MomentPair p = second_moment_pair(j);
   // level one: this group's rows
   const int lo = g * rows_per_group;
   const int hi = (lo + rows_per_group) < rows ? (lo + rows_per_group) : rows;
@@ -2292,27 +2309,16 @@ __global__ __launch_bounds__(THREADS) void k_reduce_moments_ticket(const double*
   for (int base = 0; base < hi - lo; base += STAGE) {
     const int n_stage = (hi - lo - base) < STAGE ? (hi - lo - base) : STAGE;
     __syncthreads();
-    constexpr int kPerThread = (STAGE * kPartialStride + THREADS - 1) / THREADS;
-    double staged[kPerThread];
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-      const int i = tid + k * THREADS;
-      staged[k] = i < n_stage * kPartialStride ? src[(int64_t)base * kPartialStride + i] : 0.0;
-    }
-#pragma unroll
-    for (int k = 0; k < kPerThread; ++k) {
-      const int i = tid + k * THREADS;
-      if (i < n_stage * kPartialStride) s_rows[i] = staged[k];
-    }
+    reduce_stage_rows<THREADS, STAGE>(src, base, n_stage, l.rows, tid);
     __syncthreads();
-    if (base == 0 && tid < 8) s[28 + tid] = tid < 7 ? s_rows[28 + tid] : 0.0;
+    if (base == 0) reduce_pick_reference(l, tid);
     __syncthreads();
-    v = add_staged(n_stage, v);
+    v = reduce_add_staged<kSets>(l, n_stage, q, j, p, v);
   }
-  fold_sets(v);
+  reduce_fold_sets<kSets>(l, q, j, tid, v);
   // publish, take a ticket
   double* mine = level + (b * (int64_t)groups + g) * kPartialStride;
-  if (tid < kPartialStride) __hip_atomic_store(mine + tid, s[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (tid < kPartialStride) __hip_atomic_store(mine + tid, l.s[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();  // (s_waitcnt in front of the barrier: the stores have been issued by every thread)
   if (tid == 0) {
     const unsigned int ticket = __hip_atomic_fetch_add(tickets + b, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
@@ -2323,12 +2329,12 @@ __global__ __launch_bounds__(THREADS) void k_reduce_moments_ticket(const double*
   // level two: the group records, in group order
   const double* lv = level + b * (int64_t)groups * kPartialStride;
   for (int i = tid; i < groups * kPartialStride; i += THREADS)
-    s_rows[i] = __hip_atomic_load(lv + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    l.rows[i] = __hip_atomic_load(lv + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
-  if (tid < 8) s[28 + tid] = tid < 7 ? s_rows[28 + tid] : 0.0;
+  reduce_pick_reference(l, tid);
   __syncthreads();
-  fold_sets(add_staged(groups, 0.0));
-  write_moment_record(s, out + b * LYNX_MOMENT_STRIDE, tid);
+  reduce_fold_sets<kSets>(l, q, j, tid, reduce_add_staged<kSets>(l, groups, q, j, p, 0.0));
+  write_moment_record(l.s, out + b * LYNX_MOMENT_STRIDE, tid);
   if (tid == 0) __hip_atomic_store(tickets + b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
 }
 
@@ -2413,11 +2419,12 @@ __device__ __forceinline__ void track_moments_sample(const LatticeDev& lat, cons
                                                      const T* mu_in, const T* cov_in, T* mu_out,
                                                      T* cov_out, T* __restrict__ energy_out, int chunk) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-  T* s_steps = reinterpret_cast<T*>(smem_raw + build_scratch_bytes(chunk, sizeof(T)));
-  T* s_energy = s_steps + (size_t)lat.n_steps * LYNX_STEP_STRIDE;
-  T* s_mu = s_energy + lat.n_steps + 1;  // 8
-  T* s_cov = s_mu + 8;                   // 49
-  T* s_x = s_cov + 49;                   // 49 (the launch still provides 10 scalars behind it, unused)
+  const BuildLds lds = build_lds_layout(chunk, (size_t)lat.n_steps, sizeof(T), kMomentsTailScalars);
+  T* s_steps = reinterpret_cast<T*>(smem_raw + lds.steps);
+  T* s_energy = s_steps + lds.energies;
+  T* s_mu = s_energy + lds.tail;  // 8
+  T* s_cov = s_mu + 8;            // 49
+  T* s_x = s_cov + 49;            // 49 (kMomentsTailScalars: 16 more, unused)
 
   const int64_t b = blockIdx.x;
   const int lane = threadIdx.x;

@@ -1285,16 +1285,40 @@ static int allow_lds(lynx_ctx* ctx, K kernel, size_t bytes) {
 // workgroups there have drained, so a build that runs underneath the previous call's streaming kernel (`underneath`)
 // keeps the short one (128-sample shard of BASELINE config 4: 18 us alone either way, 117-150 us with the long chunk vs
 // the short chunk's share of the GPU under the streaming kernel).
+// Returns the chunk.  `short_float32`: the limit of 32 is k_build's; the ParameterBeam kernels never took it.
 template <typename T>
-static void build_shape(lynx_ctx* ctx, const lynx_lattice* lat, bool underneath, int* threads, int* chunk) {
+static int build_shape(lynx_ctx* ctx, const lynx_lattice* lat, bool underneath, bool short_float32) {
   const int64_t cus = compute_units(ctx);
   const bool deep = lat->batch * 2 <= cus && !underneath;
-  *threads = 256;
   // (float32, at most one workgroup per CU: 64 again -- half the rounds; the 128-sample shard of BASELINE config 4
   // underneath its streaming kernel: 0.1573 -> 0.1543 ms/step, medians of four, same box)
-  const int limit = deep ? 128 : ((sizeof(T) == 4 && lat->batch > cus) ? 32 : 64);
-  *chunk = build_chunk(lat->n_elems, limit);
+  const int limit = deep ? 128 : ((short_float32 && sizeof(T) == 4 && lat->batch > cus) ? 32 : 64);
+  return build_chunk(lat->n_elems, limit);
 }
+
+// (a program of many steps: its table takes most of the LDS, and shorter chunks -- more compose rounds -- leave it room)
+template <typename T>
+static int fit_build_chunk(int chunk, const lynx_lattice* lat, size_t tail_scalars) {
+  while (build_lds_layout(chunk, (size_t)lat->n_steps, sizeof(T), tail_scalars).total > (size_t)160 * 1024 && chunk > 8) chunk = (chunk + 1) / 2;
+  return chunk;
+}
+
+// Where a workgroup kernel reads the lattice's parameters from: `launch()` for d_pool in memory, `launch(pool)` for the pool
+// in the kernel's arguments -- its first 256 bytes when that is all of it, or all 1024 (lynx_device.hpp: InlinePool).
+template <typename T, typename F>
+static int with_pool_form(const lynx_lattice* lat, bool pool_in_args, F&& launch) {
+  if (!pool_in_args) return launch();
+  if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall)
+    return launch(*reinterpret_cast<const InlinePool<kInlinePoolSmall>*>(&lat->h_pool));
+  return launch(lat->h_pool);
+}
+// The kernel of each family that goes with a pool form
+template <typename T> static auto build_kernel() { return k_build<T>; }
+template <typename T, int BYTES> static auto build_kernel(const InlinePool<BYTES>&) { return k_build_inline<T, BYTES>; }
+template <typename T> static auto track_moments_kernel() { return k_track_moments<T>; }
+template <typename T, int BYTES> static auto track_moments_kernel(const InlinePool<BYTES>&) { return k_track_moments_inline<T, BYTES>; }
+template <typename T> static auto build_bwd_kernel() { return k_build_bwd<T>; }
+template <typename T, int BYTES> static auto build_bwd_kernel(const InlinePool<BYTES>&) { return k_build_bwd_inline<T, BYTES>; }
 
 // Whole-batch cavity predicates for this call's energies, on `stream`, in front of whatever builds maps
 // there (no-op for lattices without cavities).
@@ -1428,6 +1452,17 @@ static int launch_build_lanes(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stre
   return LYNX_OK;
 }
 
+// The unit records of a float32 step table that k_emit_steps did not write, behind the table's writer on `stream`
+static int launch_pack_units(lynx_ctx* ctx, const lynx_lattice* lat, int merged, hipStream_t stream, const void* d_steps,
+                             float* d_units, float* d_extras) {
+  const UnitPlan& up = lat->units[merged ? 1 : 0];
+  const int64_t n = lat->batch * up.n_units;
+  hipLaunchKernelGGL(k_pack_units, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, up, lat->batch, lat->n_steps,
+                     (const float*)d_steps, d_units, d_extras);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
 // `d_units` / `d_extras`: also pack the unit records of a multi-step float32 program (the lattice's unit plan for `merge_pairs` must have been made);
 // the lanes build does it while it writes the table, the workgroup build with k_pack_units behind it
 template <typename T>
@@ -1446,41 +1481,23 @@ static int launch_build(lynx_ctx* ctx, lynx_lattice* lat, hipStream_t stream, co
     const int rc = sync_pool(ctx, lat);
     return rc ? rc : launch_build_lanes<T>(ctx, lat, stream, d_energy_in, d_steps_out, d_energy_out, merge_pairs, d_units, d_extras);
   }
-  int threads, chunk;
-  build_shape<T>(ctx, lat, underneath, &threads, &chunk);
-  const auto lds_at = [&](int c) {
-    return build_scratch_bytes(c, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1) * sizeof(T);
+  const int chunk = fit_build_chunk<T>(build_shape<T>(ctx, lat, underneath, true), lat, 0);
+  const size_t lds = build_lds_layout(chunk, (size_t)lat->n_steps, sizeof(T), 0).total;
+  // (the cavity flags are in front of everything here, in launch_track_moments behind sync_pool and allow_lds: the orders
+  // never meet -- a lattice whose pool travels in the arguments has no cavity -- and each launcher keeps its own)
+  const auto launch = [&](const auto&... pool) -> int {
+    const auto kernel = build_kernel<T>(pool...);
+    if constexpr (sizeof...(pool) == 0)
+      if (const int stale = sync_pool(ctx, lat)) return stale;
+    if (const int refused = allow_lds(ctx, kernel, lds)) return refused;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)lat->batch), dim3(256), lds, stream, pool..., dev_view(lat), (const T*)d_energy_in,
+                       (T*)d_steps_out, (T*)d_energy_out, chunk, merge_pairs);
+    HIP_TRY(ctx, hipGetLastError());
+    return LYNX_OK;
   };
-  // (a program of many steps: its table takes most of the LDS, and shorter chunks -- more compose rounds -- leave it room)
-  while (lds_at(chunk) > (size_t)160 * 1024 && chunk > 8) chunk = (chunk + 1) / 2;
-  const size_t lds = lds_at(chunk);
-  int rc;
-  if (lat->prog_pool && ctx->knobs.inline_pool) {
-    if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall) {
-      if ((rc = allow_lds(ctx, k_build_inline<T, kInlinePoolSmall>, lds))) return rc;
-      hipLaunchKernelGGL((k_build_inline<T, kInlinePoolSmall>), dim3((unsigned)lat->batch), dim3((unsigned)threads), lds, stream,
-                         *reinterpret_cast<const InlinePool<kInlinePoolSmall>*>(&lat->h_pool), dev_view(lat),
-                         (const T*)d_energy_in, (T*)d_steps_out, (T*)d_energy_out, chunk, merge_pairs);
-    } else {
-      if ((rc = allow_lds(ctx, k_build_inline<T, kInlinePoolLarge>, lds))) return rc;
-      hipLaunchKernelGGL((k_build_inline<T, kInlinePoolLarge>), dim3((unsigned)lat->batch), dim3((unsigned)threads), lds, stream,
-                         lat->h_pool, dev_view(lat), (const T*)d_energy_in, (T*)d_steps_out, (T*)d_energy_out, chunk, merge_pairs);
-    }
-  } else {
-    if ((rc = sync_pool(ctx, lat)) || (rc = allow_lds(ctx, k_build<T>, lds))) return rc;
-    hipLaunchKernelGGL(k_build<T>, dim3((unsigned)lat->batch), dim3((unsigned)threads), lds, stream, dev_view(lat),
-                       (const T*)d_energy_in, (T*)d_steps_out, (T*)d_energy_out, chunk, merge_pairs);
-  }
-  HIP_TRY(ctx, hipGetLastError());
-  if constexpr (sizeof(T) == 4) {
-    if (d_units) {
-      const UnitPlan& up = lat->units[merge_pairs ? 1 : 0];
-      const int64_t n = lat->batch * up.n_units;
-      hipLaunchKernelGGL(k_pack_units, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, up, lat->batch,
-                         lat->n_steps, (const float*)d_steps_out, d_units, d_extras);
-      HIP_TRY(ctx, hipGetLastError());
-    }
-  }
+  if (const int rc = with_pool_form<T>(lat, lat->prog_pool && ctx->knobs.inline_pool, launch)) return rc;
+  if constexpr (sizeof(T) == 4)
+    if (d_units) return launch_pack_units(ctx, lat, merge_pairs, stream, d_steps_out, d_units, d_extras);
   return LYNX_OK;
 }
 
@@ -2162,7 +2179,8 @@ static int launch_build_bwd(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ener
   const size_t maps_bytes = (size_t)(2 * E + S + 1) * 49 * sizeof(T);
   const int maps_in_lds = lds + maps_bytes <= kBwdMapsLdsBytes;
   if (maps_in_lds) lds += maps_bytes;
-  const auto launch = [&](auto kernel, const auto&... pool) -> int {
+  const auto launch = [&](const auto&... pool) -> int {
+    const auto kernel = build_bwd_kernel<T>(pool...);
     if (const int refused = allow_lds(ctx, kernel, lds)) return refused;
     HIP_TRY(ctx, hipMemsetAsync(d_grad_params, 0, (size_t)B * E * kGradParams * sizeof(T), ctx->stream));
     hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(256), lds, ctx->stream, pool..., dev_view(lat), (const T*)d_energy_in,
@@ -2171,10 +2189,7 @@ static int launch_build_bwd(lynx_ctx* ctx, lynx_lattice* lat, const void* d_ener
     HIP_TRY(ctx, hipGetLastError());
     return LYNX_OK;
   };
-  if (!pool_in_args) return launch(k_build_bwd<T>);
-  if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall)
-    return launch(k_build_bwd_inline<T, kInlinePoolSmall>, *reinterpret_cast<const InlinePool<kInlinePoolSmall>*>(&lat->h_pool));
-  return launch(k_build_bwd_inline<T, kInlinePoolLarge>, lat->h_pool);
+  return with_pool_form<T>(lat, pool_in_args, launch);
 }
 
 // The sweep over the particles (k_track_bwd, k_track_bwd_units, k_track_bwd_inject): a workgroup walks `tiles_per_wg`
@@ -2297,8 +2312,6 @@ static int bwd_units_records(lynx_ctx* ctx, lynx_lattice* lat, int merged, const
 // them where they are (LYNX_BWD_REUSE_TABLE=0: never).  Otherwise build them into the reverse pass's own.
 template <typename T>
 static int bwd_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, int merged, size_t steps_bytes, BwdTable* t) {
-  const int64_t B = lat->batch;
-  const int32_t S = lat->n_steps;
   std::unique_lock<std::mutex> table_lock(ctx->mu);
   const lynx_ctx::FwdTable ft = ctx->fwd_table;
   table_lock.unlock();
@@ -2316,13 +2329,7 @@ static int bwd_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, 
     t->d_units = (float*)ctx->scratch.units[ft.slot].buf;
     t->d_extras = (float*)ctx->scratch.units[lynx_ctx::kTableSlots + ft.slot].buf;
   } else if (t->d_units) {  // the forward call walked the table itself (a single-map program): the records from its rows
-    if constexpr (sizeof(T) == 4) {
-      const UnitPlan& up = lat->units[merged ? 1 : 0];
-      const int64_t n = B * up.n_units;
-      hipLaunchKernelGGL(k_pack_units, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, up, B, S,
-                         (const float*)t->d_steps, t->d_units, t->d_extras);
-      HIP_TRY(ctx, hipGetLastError());
-    }
+    if constexpr (sizeof(T) == 4) return launch_pack_units(ctx, lat, merged, ctx->stream, t->d_steps, t->d_units, t->d_extras);
   }
   return LYNX_OK;
 }
@@ -2509,10 +2516,10 @@ int lynx_moments(lynx_ctx* ctx, int dtype, int64_t batch, int64_t n_particles, c
 template <typename T>
 static int launch_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
                                 const void* d_cov_in, void* d_mu_out, void* d_cov_out, void* d_energy_out) {
-  int rc;
   if constexpr (sizeof(T) == 4)  // (float64: 98 VGPRs of covariance per lane -- the compiler spills; workgroup form below)
   if (lat->n_steps > 0 && lat->batch >= ctx->knobs.lanes_build_min_batch) {
     // large batches: lanes = samples all the way (step table from the lanes build, then one lane per sample)
+    int rc;
     const size_t need = (size_t)lat->batch * lat->n_steps * LYNX_STEP_STRIDE * sizeof(T);
     if ((rc = ensure_scratch(ctx, ctx->scratch.steps[lynx_ctx::kTablePb], need))) return rc;
     if ((rc = launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch.steps[lynx_ctx::kTablePb].buf, nullptr, 0))) return rc;
@@ -2524,38 +2531,24 @@ static int launch_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_
   }
   // one workgroup per sample: one wave for big batches, four otherwise -- with chunks of up to 128 elements when the
   // batch leaves most of the GPU idle and the depth of the tree is what the call waits for (build_shape)
-  const int64_t cus = compute_units(ctx);
-  const bool deep = lat->batch * 2 <= cus;
   const unsigned threads = lat->batch <= 4096 ? 256u : 64u;
-  int chunk = build_chunk(lat->n_elems, deep ? 128 : 64);
-  const auto lds_at = [&](int c) {
-    return build_scratch_bytes(c, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1 + 8 + 49 + 49 + 16) * sizeof(T);
-  };
-  // (a program of many steps: its table takes most of the LDS, and shorter chunks -- more compose rounds -- leave it room)
-  while (lds_at(chunk) > (size_t)160 * 1024 && chunk > 8) chunk = (chunk + 1) / 2;
-  const size_t lds = lds_at(chunk);
-  if (lat->prog_pool && ctx->knobs.inline_pool) {  // (no cavities: no flags to evaluate)
-    if ((size_t)lat->pool_count * sizeof(T) <= (size_t)kInlinePoolSmall) {
-      if ((rc = allow_lds(ctx, k_track_moments_inline<T, kInlinePoolSmall>, lds))) return rc;
-      hipLaunchKernelGGL((k_track_moments_inline<T, kInlinePoolSmall>), dim3((unsigned)lat->batch), dim3(threads), lds, ctx->stream,
-                         *reinterpret_cast<const InlinePool<kInlinePoolSmall>*>(&lat->h_pool), dev_view(lat), (const T*)d_energy_in,
-                         (const T*)d_mu_in, (const T*)d_cov_in, (T*)d_mu_out, (T*)d_cov_out, (T*)d_energy_out, chunk);
-    } else {
-      if ((rc = allow_lds(ctx, k_track_moments_inline<T, kInlinePoolLarge>, lds))) return rc;
-      hipLaunchKernelGGL((k_track_moments_inline<T, kInlinePoolLarge>), dim3((unsigned)lat->batch), dim3(threads), lds, ctx->stream,
-                         lat->h_pool, dev_view(lat), (const T*)d_energy_in, (const T*)d_mu_in, (const T*)d_cov_in, (T*)d_mu_out,
-                         (T*)d_cov_out, (T*)d_energy_out, chunk);
-    }
+  const int chunk = fit_build_chunk<T>(build_shape<T>(ctx, lat, /* underneath */ false, /* short_float32 */ false), lat, kMomentsTailScalars);
+  const size_t lds = build_lds_layout(chunk, (size_t)lat->n_steps, sizeof(T), kMomentsTailScalars).total;
+  // (the cavity flags -- none where the pool travels in the arguments: such a lattice has no cavity -- come behind
+  // sync_pool and allow_lds here, in launch_build in front of both: each launcher keeps its own order)
+  const auto launch = [&](const auto&... pool) -> int {
+    const auto kernel = track_moments_kernel<T>(pool...);
+    if constexpr (sizeof...(pool) == 0)
+      if (const int stale = sync_pool(ctx, lat)) return stale;
+    if (const int refused = allow_lds(ctx, kernel, lds)) return refused;
+    if constexpr (sizeof...(pool) == 0)
+      if (const int failed = launch_cavity_flags<T>(ctx, lat, ctx->stream, d_energy_in)) return failed;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)lat->batch), dim3(threads), lds, ctx->stream, pool..., dev_view(lat), (const T*)d_energy_in,
+                       (const T*)d_mu_in, (const T*)d_cov_in, (T*)d_mu_out, (T*)d_cov_out, (T*)d_energy_out, chunk);
     HIP_TRY(ctx, hipGetLastError());
     return LYNX_OK;
-  }
-  if ((rc = sync_pool(ctx, lat)) || (rc = allow_lds(ctx, k_track_moments<T>, lds))) return rc;
-  if ((rc = launch_cavity_flags<T>(ctx, lat, ctx->stream, d_energy_in))) return rc;
-  hipLaunchKernelGGL(k_track_moments<T>, dim3((unsigned)lat->batch), dim3(threads), lds, ctx->stream, dev_view(lat),
-                     (const T*)d_energy_in, (const T*)d_mu_in, (const T*)d_cov_in, (T*)d_mu_out, (T*)d_cov_out,
-                     (T*)d_energy_out, chunk);
-  HIP_TRY(ctx, hipGetLastError());
-  return LYNX_OK;
+  };
+  return with_pool_form<T>(lat, lat->prog_pool && ctx->knobs.inline_pool, launch);
 }
 
 int lynx_track_moments(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_in,
@@ -2585,9 +2578,8 @@ static int trace_table(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in
     return rc;
   if (lat->n_steps == 0) return LYNX_OK;
   // no limit on the number of elements: where the workgroup build's table would not fit its LDS, lanes = samples
-  int threads, chunk;
-  build_shape<T>(ctx, lat, false, &threads, &chunk);
-  const size_t lds = build_scratch_bytes(chunk, sizeof(T)) + ((size_t)lat->n_steps * LYNX_STEP_STRIDE + lat->n_steps + 1) * sizeof(T);
+  // (by the chunk of build_shape as it stands, not the one launch_build would halve it to)
+  const size_t lds = build_lds_layout(build_shape<T>(ctx, lat, false, true), (size_t)lat->n_steps, sizeof(T), 0).total;
   return launch_build<T>(ctx, lat, ctx->stream, d_energy_in, ctx->scratch.steps[lynx_ctx::kTableTrace].buf, nullptr, 0, false, nullptr,
                          nullptr, lds > (size_t)64 * 1024);
 }
