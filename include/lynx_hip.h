@@ -363,6 +363,29 @@ int lynx_track_particles_along_forward(lynx_ctx* ctx, lynx_lattice* lat, int64_t
                                        const int32_t* dir_row, const double* dir_weight, int32_t n_directions, int32_t n_entries,
                                        double* d_mu_dot, double* d_cov_dot);
 
+/* ... of a ParameterBeam THROUGH cavity steps: a linac's response matrix.  The two entries above refuse a cavity step;
+ * this one walks through it.  A direction carries a tangent of the beam energy, e_dot[k] for the energy that enters
+ * step k: e_dot[0] = dir_energy_seed[d] (1 for the incoming energy, else 0), and behind a gaining cavity
+ * (LYNX_FLAG_CAV_GAIN) + weight . cos(phi) for an entry on its voltage, - weight . V sin(phi) pi/180 for one on its
+ * phase.  The tangent of a step's row -- its map and the 8 cavity coefficients -- is taken at the step's OWN entering
+ * energy, and an entry on row 8 (the energy at that step) contributes weight . e_dot[leaf] . d(row)/dE: the host gives
+ * such an entry, weight 1, to every leaf behind the first cavity whose voltage or phase a direction holds, and to every
+ * leaf for the incoming energy.  Behind the products of a gaining cavity follows the tangent of the cavity branch of
+ * lynx_track_moments_along (the kick on the incoming s, delta; C55 restored; the second-order terms in C44, C45, C54),
+ * with cos(a) - cos(phi) and sin(a) - sin(phi) formed without cancellation as in the reverse passes.
+ *   dir_energy_seed [n_directions]   HOST array, float64
+ *   d_energy_dot [B][D][P]           float64: e_dot at every point; every cell is written
+ * Everything else -- arguments, outputs, arithmetic, bit-for-bit repeatability -- as lynx_track_moments_along_forward,
+ * whose results this entry reproduces on a program without a cavity step.  LYNX_ERR_INVALID (lynx_last_error starts with
+ * "beam trace tangents: ") for that entry's refusals other than the cavity step, for a null dir_energy_seed or
+ * d_energy_dot, and for an entry on row 1, 2 or 3 (voltage, phase, frequency) of a cavity that is not a cavity step:
+ * without voltage the cavity is a drift-like element of a run and its map has no continuous limit there.           */
+int lynx_track_moments_along_forward_cavities(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                                              const void* d_cov_trace, const int32_t* dir_start, const int32_t* dir_leaf,
+                                              const int32_t* dir_row, const double* dir_weight, int32_t n_directions,
+                                              int32_t n_entries, double* d_mu_dot, double* d_cov_dot,
+                                              const double* dir_energy_seed, double* d_energy_dot);
+
 /* Reverse pass of lynx_track_moments_along: gradient of a scalar function of the moments and the energy at EVERY point
  * of the lattice (the losses written along a beamline: Twiss values at markers, beam sizes below an aperture, the
  * centroid at every BPM) with respect to every element parameter, the incoming energy and the incoming mu and cov.

@@ -108,6 +108,9 @@ SIGNATURES = {
                                               C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32, _vp, _vp]),
     "lynx_track_particles_along_forward": (_i, [_vp, _vp, _i64, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                                 C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32, _vp, _vp]),
+    "lynx_track_moments_along_forward_cavities": (_i, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
+                                                       C.POINTER(C.c_int32), C.POINTER(C.c_double), C.c_int32, C.c_int32, _vp, _vp,
+                                                       C.POINTER(C.c_double), _vp]),
     "lynx_track_moments_along_backward": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_track_particles_along_backward": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lynx_track_particles_along_backward_cavities": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),

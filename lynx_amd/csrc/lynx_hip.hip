@@ -3077,8 +3077,10 @@ struct TraceDirectionList {
   const double* weight;
 };
 
-// Every refusal of the two forward-mode entry points about the lattice and the directions, before anything is launched.
-static int trace_forward_check(lynx_ctx* ctx, lynx_lattice* lat, const TraceDirectionList& dl) {
+// Every refusal of the forward-mode entry points about the lattice and the directions, before anything is launched.
+// `cavities`: the entry that walks through cavity steps -- they are no refusal, a voltage, phase or frequency on a cavity
+// that is no step of its own is.
+static int trace_forward_check(lynx_ctx* ctx, lynx_lattice* lat, const TraceDirectionList& dl, bool cavities = false) {
   const std::string what = "beam trace tangents: ";
   if (!dl.start || !dl.leaf || !dl.row || !dl.weight) return fail(ctx, LYNX_ERR_INVALID, what + "null argument");
   if (dl.count < 1) return fail(ctx, LYNX_ERR_INVALID, what + "n_directions must be > 0");
@@ -3087,7 +3089,7 @@ static int trace_forward_check(lynx_ctx* ctx, lynx_lattice* lat, const TraceDire
   if (lat->batch <= 0 || lat->batch > 0x7fffffffLL) return fail(ctx, LYNX_ERR_INVALID, what + "bad batch");
   for (int32_t s = 0; s < lat->n_steps; ++s) {
     const lynx_step& st = lat->h_steps[s];
-    if (st.kind == LYNX_STEP_CAVITY)
+    if (st.kind == LYNX_STEP_CAVITY && !cavities)
       return fail(ctx, LYNX_ERR_INVALID,
                   what + "step " + std::to_string(s) + " is a cavity step (the energy behind it, and with it every later map, depends on "
                          "its parameters, and the particles' moments are not closed under its kick)");
@@ -3112,6 +3114,10 @@ static int trace_forward_check(lynx_ctx* ctx, lynx_lattice* lat, const TraceDire
     if (dl.row[q] != kGradParams && dl.row[q] >= bwd_kind_params(kind))  // (the energy: every kind, zero for one without parameters)
       return fail(ctx, LYNX_ERR_INVALID,
                   what + entry + ": an element of kind " + std::to_string(kind) + " has no parameter row " + std::to_string(dl.row[q]));
+    if (cavities && kind == LYNX_KIND_CAVITY && dl.row[q] >= 1 && dl.row[q] <= 3 && lat->h_steps[dl.leaf[q]].kind != LYNX_STEP_CAVITY)
+      return fail(ctx, LYNX_ERR_INVALID,
+                  what + entry + ": row " + std::to_string(dl.row[q]) + " of the cavity at leaf " + std::to_string(dl.leaf[q]) +
+                      ", which is not a cavity step (without voltage its map has no continuous limit in voltage, phase or frequency)");
   }
   return LYNX_OK;
 }
@@ -3121,14 +3127,20 @@ static int trace_forward_check(lynx_ctx* ctx, lynx_lattice* lat, const TraceDire
 struct TraceForwardScratch {
   TraceDirections dirs;
   double *mdot, *mu, *cov;
+  const double* seed;  // through cavities: the directions' energy seeds [D], behind the weights
+  void* energy;        // ... and the energy that enters every step [B][P], lattice dtype
 };
 
 // The directions on the device, the entries of each direction ordered by leaf (stable: entries on one leaf keep their
 // order) -- uploaded when they differ from what is there, like the trace's plan: the wait that upload needs is paid once
 // per set of directions, and a loop that asks for the same tangents again pays nothing.
-static int trace_forward_scratch(lynx_ctx* ctx, lynx_lattice* lat, const TraceDirectionList& dl, bool states, TraceForwardScratch* out) {
+// `seed` (through cavities): the energy seeds ride behind the weights, an entry's tangent is 64 wide and the energies
+// [B][P] follow.
+static int trace_forward_scratch(lynx_ctx* ctx, lynx_lattice* lat, const TraceDirectionList& dl, bool states, TraceForwardScratch* out,
+                                 const double* seed = nullptr) {
   const int32_t D = dl.count, n = dl.entries;
-  const size_t ints = (size_t)D + 1 + 2 * (size_t)n, words = (ints + 1) / 2 * 2 + 2 * (size_t)n;  // (the weights: 8-aligned)
+  const size_t ints = (size_t)D + 1 + 2 * (size_t)n;
+  const size_t words = (ints + 1) / 2 * 2 + 2 * (size_t)n + (seed ? 2 * (size_t)D : 0);  // (the weights, the seeds: 8-aligned)
   std::vector<int32_t> plan(words, 0);
   int32_t* weights = plan.data() + (ints + 1) / 2 * 2;  // (two words each)
   std::vector<int32_t> order(std::max(n, 1));
@@ -3142,10 +3154,11 @@ static int trace_forward_scratch(lynx_ctx* ctx, lynx_lattice* lat, const TraceDi
     plan[(size_t)D + 1 + n + q] = dl.row[order[q]];
     std::memcpy(weights + 2 * (size_t)q, dl.weight + order[q], sizeof(double));
   }
+  if (seed) std::memcpy(weights + 2 * (size_t)n, seed, (size_t)D * sizeof(double));
   const int64_t points = lat->batch * ((int64_t)lat->n_steps + 1);
   const size_t plan_bytes = (words * sizeof(int32_t) + 255) / 256 * 256;
-  const size_t mdot_scalars = std::max<size_t>((size_t)lat->batch * n * 49, 1);
-  const size_t need = plan_bytes + (mdot_scalars + (states ? (size_t)points * 56 : 0)) * sizeof(double);
+  const size_t mdot_scalars = std::max<size_t>((size_t)lat->batch * n * (seed ? LYNX_STEP_STRIDE : 49), 1);
+  const size_t need = plan_bytes + (mdot_scalars + (states ? (size_t)points * 56 : 0) + (seed ? (size_t)points : 0)) * sizeof(double);
   Scratch& sc = ctx->scratch.trace_jvp;
   const bool fresh = sc.bytes < need;
   int rc;
@@ -3161,6 +3174,8 @@ static int trace_forward_scratch(lynx_ctx* ctx, lynx_lattice* lat, const TraceDi
   out->mdot = (double*)((char*)sc.buf + plan_bytes);
   out->mu = out->mdot + mdot_scalars;
   out->cov = out->mu + points * 7;
+  out->seed = seed ? out->dirs.weight + n : nullptr;
+  out->energy = seed ? out->mdot + mdot_scalars : nullptr;  // (no states with a seed: a ParameterBeam's entry)
   return LYNX_OK;
 }
 
@@ -3185,10 +3200,10 @@ static int trace_forward_sweep(lynx_ctx* ctx, lynx_lattice* lat, const void* d_e
 // trace's table in the trace's own slot, the directions
 template <typename T>
 static int trace_forward_begin(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const TraceDirectionList& dl, bool states,
-                               TraceForwardScratch* fs) {
+                               TraceForwardScratch* fs, const double* seed = nullptr) {
   int rc;
   if ((rc = sync_pool(ctx, lat))) return rc;
-  if ((rc = trace_forward_scratch(ctx, lat, dl, states, fs))) return rc;
+  if ((rc = trace_forward_scratch(ctx, lat, dl, states, fs, seed))) return rc;
   ctx->main_idle = false;  // (the upload of new directions has waited for the stream: work follows it now)
   return trace_table<T>(ctx, lat, d_energy_in);
 }
@@ -3235,6 +3250,50 @@ int lynx_track_particles_along_forward(lynx_ctx* ctx, lynx_lattice* lat, int64_t
     hipLaunchKernelGGL(k_trace_records_to_moments, dim3((unsigned)points), dim3(64), 0, ctx->stream, d_trace_fwd, fs.mu, fs.cov);
     HIP_TRY(ctx, hipGetLastError());
     return trace_forward_sweep<T, double>(ctx, lat, d_energy_in, fs, fs.mu, fs.cov, d_mu_dot, d_cov_dot);
+  });
+}
+
+// ... through cavity steps (a ParameterBeam): the energy that enters every step and its tangent along every direction,
+// the entries' tangent rows at those energies, the sweep with the cavity branch's tangent (lynx_trace_jvp.hpp).
+template <typename T>
+static int trace_forward_sweep_cavities(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const TraceForwardScratch& fs,
+                                        const void* d_mu, const void* d_cov, double* d_mu_dot, double* d_cov_dot, double* d_energy_dot) {
+  const int64_t B = lat->batch, pairs = B * fs.dirs.count, threads = B * fs.dirs.entries;
+  const T* table = (const T*)ctx->scratch.steps[lynx_ctx::kTableTrace].buf;
+  hipLaunchKernelGGL(k_trace_energies<T>, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
+                     (const T*)d_energy_in, (T*)fs.energy);
+  HIP_TRY(ctx, hipGetLastError());
+  hipLaunchKernelGGL(k_trace_energy_tangents<T>, dim3((unsigned)((pairs + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat), table,
+                     fs.dirs, fs.seed, d_energy_dot);
+  HIP_TRY(ctx, hipGetLastError());
+  if (threads > 0) {
+    hipLaunchKernelGGL(k_trace_tangent_rows<T>, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, ctx->stream, dev_view(lat),
+                       (const T*)fs.energy, fs.dirs, (const double*)d_energy_dot, fs.mdot);
+    HIP_TRY(ctx, hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_trace_moments_jvp_kicks<T>, dim3((unsigned)pairs), dim3(64), 0, ctx->stream, (int)lat->n_steps, fs.dirs, table,
+                     (const T*)d_mu, (const T*)d_cov, (const double*)fs.mdot, d_mu_dot, d_cov_dot);
+  HIP_TRY(ctx, hipGetLastError());
+  return LYNX_OK;
+}
+
+int lynx_track_moments_along_forward_cavities(lynx_ctx* ctx, lynx_lattice* lat, const void* d_energy_in, const void* d_mu_trace,
+                                              const void* d_cov_trace, const int32_t* dir_start, const int32_t* dir_leaf,
+                                              const int32_t* dir_row, const double* dir_weight, int32_t n_directions,
+                                              int32_t n_entries, double* d_mu_dot, double* d_cov_dot,
+                                              const double* dir_energy_seed, double* d_energy_dot) {
+  LYNX_MAIN_ENTRY(ctx);
+  if (!lat || !d_energy_in || !d_mu_trace || !d_cov_trace || !d_mu_dot || !d_cov_dot || !dir_energy_seed || !d_energy_dot)
+    return fail(ctx, LYNX_ERR_INVALID, "beam trace tangents: null argument");
+  const TraceDirectionList dl{n_directions, n_entries, dir_start, dir_leaf, dir_row, dir_weight};
+  if (const int rc = trace_forward_check(ctx, lat, dl, true)) return rc;
+  const auto two = forward_writes(lat, n_directions, d_mu_dot, d_cov_dot);
+  LYNX_MAIN_WRITES(ctx, kFeedsBuild, {two[0], two[1], {d_energy_dot, two[0].bytes / 7}});
+  return with_dtype(lat->dtype, [&](auto zero) {
+    using T = decltype(zero);
+    TraceForwardScratch fs;
+    if (const int rc = trace_forward_begin<T>(ctx, lat, d_energy_in, dl, false, &fs, dir_energy_seed)) return rc;
+    return trace_forward_sweep_cavities<T>(ctx, lat, d_energy_in, fs, d_mu_trace, d_cov_trace, d_mu_dot, d_cov_dot, d_energy_dot);
   });
 }
 

@@ -33,6 +33,11 @@
 //   k_trace_records_to_moments   ParticleBeam: moment records [B][P][36] float64 -> mu, C of the sweep
 //                             (k_trace_records_to_states without its cotangent half)
 //   k_trace_moments_jvp       the sweep, one wave per (sample, direction)
+// and through gaining cavities (lynx_track_moments_along_forward_cavities; the section in front of
+// k_trace_energy_tangents):
+//   k_trace_energy_tangents   one thread per (sample, direction): the tangent of the beam energy at every point
+//   k_trace_tangent_rows      k_trace_tangent_maps at the step's own energy, with the 8 cavity coefficients: [B][n][64]
+//   k_trace_moments_jvp_kicks the same sweep with the tangent of the cavity branch behind a gaining cavity's products
 #pragma once
 
 #include "lynx_device.hpp"
@@ -100,6 +105,141 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) ==
 }
 
 // ---------------------------------------------------------------------------------------
+// Through gaining cavities (lynx_track_moments_along_forward_cavities, a ParameterBeam).  Two things change.  The energy
+// that enters step k is E_in + the sum of V cos(phi) over the gaining cavities in front of it, so a direction carries an
+// energy tangent e_dot[k] -- its seed at point 0 (1 for the incoming energy), + w cos(phi) at a gaining cavity for a
+// voltage entry, - w V sin(phi) pi/180 for a phase entry: the forward image of step 4 of build_bwd_sample -- and an
+// entry on the energy's row contributes weight . e_dot[leaf] . dR/dE.  And behind the products of a gaining cavity comes
+// the tangent of moment_cavity_branch, which needs the tangents of the step's 8 coefficients beside those of its map: an
+// entry's tangent is the row R = map | coefficients, 64 wide.
+//
+// k_trace_energy_tangents: grid = ceil(B D / 64), thread = (sample, direction): e_dot at every point, [B][D][P], every
+// cell written.  The entries of a direction are ordered by leaf, so one walk over the points consumes them in order.
+// Whether a cavity gains is what the table says of this sample's build (LYNX_FLAGS_OFFSET), as everywhere in the trace.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_energy_tangents(LatticeDev lat, const T* __restrict__ steps, TraceDirections dirs,
+                                                              const double* __restrict__ seed /* [D] */,
+                                                              double* __restrict__ energy_dot /* [B][D][P] */) {
+  const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const int D = dirs.count, S = lat.n_steps, P = S + 1;
+  if (t >= lat.batch * D) return;
+  const int64_t b = t / D;
+  const int d = (int)(t - b * D);
+  const T* pool = static_cast<const T*>(lat.pool);
+  double* out = energy_dot + t * P;
+  int q = dirs.start[d];
+  const int q_end = dirs.start[d + 1];
+  double e = seed[d];
+  for (int s = 0; s <= S; ++s) {
+    out[s] = e;
+    if (s == S) break;
+    for (; q < q_end && dirs.leaf[q] == s; ++q) {
+      const int row = dirs.row[q];
+      if (row != 1 && row != 2) continue;  // (of a cavity: voltage, phase)
+      const int desc = (int)steps[(b * S + s) * LYNX_STEP_STRIDE + LYNX_FLAGS_OFFSET];
+      if (((desc >> LYNX_DESC_KIND_SHIFT) & 3) != LYNX_STEP_CAVITY || !(desc & LYNX_FLAG_CAV_GAIN)) continue;
+      const lynx_elem el = lat.elems[lat.steps[s].first];
+      const T* p = pool + el.param_offset + b * (int64_t)el.batch_stride;
+      const double phi = (double)p[2] * (LYNX_PI / 180.0);
+      e += row == 1 ? dirs.weight[q] * cos(phi) : -dirs.weight[q] * (double)p[1] * sin(phi) * (LYNX_PI / 180.0);
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// k_trace_tangent_rows: k_trace_tangent_maps with the step's own entering energy as the value of the dual (`energy`
+// [B][P]: what k_trace_energies writes, the build's own sums), the coefficient output of the builders as step 3 of
+// build_bwd_sample asks for it, and weight . e_dot[leaf] as the factor of an entry on the energy's row (`energy_dot`:
+// k_trace_energy_tangents, launched in front; the entry's direction by bisection of dir_start).  64 float64 per
+// (sample, entry): 49 map entries, 8 coefficients, zeros.  Every thread writes its 64 cells.  The waves per SIMD: see
+// k_trace_tangent_maps -- the dual builders are k_build_bwd's, too.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 4 ? 7 : 1))) void k_trace_tangent_rows(LatticeDev lat, const T* __restrict__ energy /* [B][P] */, TraceDirections dirs,
+                                                           const double* __restrict__ energy_dot /* [B][D][P] */,
+                                                           double* __restrict__ rdot /* [B][n][64] */) {
+  const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  const int64_t n = dirs.entries;
+  if (t >= lat.batch * n) return;
+  const int64_t b = t / n;
+  const int q = (int)(t - b * n);
+  const int e = dirs.leaf[q], pidx = dirs.row[q];
+  const int P = lat.n_steps + 1;
+  double* out = rdot + t * LYNX_STEP_STRIDE;
+  for (int c = 0; c < LYNX_STEP_STRIDE; ++c) out[c] = 0.0;
+  const lynx_elem el = lat.elems[e];
+  const int np = bwd_kind_params_dev(el.kind);
+  if (np == 0) return;
+  const bool energy_task = pidx == kGradParams;
+  double w = dirs.weight[q];
+  if (energy_task) {
+    int lo = 0, hi = dirs.count;  // the last direction whose entries start at or in front of q
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (dirs.start[mid] <= q) lo = mid;
+      else hi = mid;
+    }
+    w *= energy_dot[(b * dirs.count + lo) * P + e];
+  }
+  const T* p = static_cast<const T*>(lat.pool) + el.param_offset + b * (int64_t)el.batch_stride;
+  Dual<T> dp[8];
+  for (int k = 0; k < 8; ++k) dp[k] = Dual<T>(k < np ? p[k] : T(0), (k == pidx) ? T(1) : T(0));
+  const Dual<T> de(energy[b * P + e], energy_task ? T(1) : T(0));
+  const bool cav_step = lat.steps[e].kind == LYNX_STEP_CAVITY;
+  Dual<T> dC[8];
+  for (int k = 0; k < 8; ++k) dC[k] = Dual<T>(T(0));
+  Dual<T> m16[16];
+  if (build_entries_u<Dual<T>>(el.kind, el.flags, dp, de, m16, cav_step ? dC : nullptr)) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) out[unit_entry_u(k)] = w * (double)m16[k].d;
+  } else {
+    Dual<T> dM[49];
+    build_element<Dual<T>>(el.kind, el.flags, dp, de, dM, cav_step ? dC : nullptr);
+    for (int c = 0; c < 49; ++c) out[c] = w * (double)dM[c].d;
+  }
+  if (cav_step)
+    for (int k = 0; k < 8; ++k) out[LYNX_COEF_OFFSET + k] = w * (double)dC[k].d;
+}
+
+// ---------------------------------------------------------------------------------------
+// jvp_cavity_branch: the tangent of moment_cavity_branch (lynx_device.hpp), lane 0 of a gaining cavity step behind the
+// linear products.  s_m, s_d: the step's row and its tangent (map | coefficients); s_mu, s_c: the state that ENTERED the
+// step; in_d: the tangents that entered it (mu_dot[4], mu_dot[5], C_dot[4][4], [4][5], [5][5]); s_md, s_cd: the linear
+// step's tangents, which the branch's entries go over.  With a = -z4 c2 + c3:
+//   mu'[5] = z5 c0 + c1 (cos a - c4),   mu'[4] += c5 z5^2 + c6 z4 z5 + c7 z4^2,   C'[5][5] = c55,
+//   C'[4][4] = C'[4][5] = C'[5][4] = c5 c55^2 + c6 c45 c55 + c7 c44^2
+// The differences cos a - cos phi and sin a - sin phi are formed as kick_cotangents forms them (sin_cosm1 of d = a - phi
+// and the addition theorems), and the phase's tangent enters as -c1 (sin a - sin phi) c3_dot -- d/dc3 and the path through
+// c4 = cos(phi) in one term, never two that cancel; the tangent of c4 itself is not read.
+// ---------------------------------------------------------------------------------------
+template <typename A>
+__device__ __forceinline__ void jvp_cavity_branch(const A* s_m, const A* s_d, const A* s_mu, const A* s_c, const A (&in_d)[5],
+                                                  A* s_md, A* s_cd) {
+  const A* c = s_m + LYNX_COEF_OFFSET;
+  const A* cdot = s_d + LYNX_COEF_OFFSET;
+  const A z4 = s_mu[4], z5 = s_mu[5], c44 = s_c[4 * 7 + 4], c45 = s_c[4 * 7 + 5], c55 = s_c[5 * 7 + 5];
+  const A zd4 = in_d[0], zd5 = in_d[1], cd44 = in_d[2], cd45 = in_d[3], cd55 = in_d[4];
+  A sphi, cphi, sd, cm1;
+  phase_sincos(c[LYNX_C_PHI], sphi, cphi);
+  sin_cosm1(-z4 * c[LYNX_C_BK], sd, cm1);
+  const A dsin = fma(sd, cphi, cm1 * sphi);   // sin(a) - sin(phi)
+  const A dcos = fma(sd, -sphi, cm1 * cphi);  // cos(a) - cos(phi)
+  const A sa = dsin + sphi;
+  const A ad = -zd4 * c[LYNX_C_BK] - z4 * cdot[LYNX_C_BK];  // a_dot without the phase's own term
+  s_md[5] = zd5 * c[LYNX_C_DSCALE] + z5 * cdot[LYNX_C_DSCALE] + cdot[LYNX_C_DKICK] * dcos -
+            c[LYNX_C_DKICK] * (sa * ad + dsin * cdot[LYNX_C_PHI]);
+  s_md[4] += cdot[LYNX_C_T566] * (z5 * z5) + A(2) * c[LYNX_C_T566] * z5 * zd5 + cdot[LYNX_C_T556] * z4 * z5 +
+             c[LYNX_C_T556] * (zd4 * z5 + z4 * zd5) + cdot[LYNX_C_T555] * (z4 * z4) + A(2) * c[LYNX_C_T555] * z4 * zd4;
+  const A v = cdot[LYNX_C_T566] * (c55 * c55) + A(2) * c[LYNX_C_T566] * c55 * cd55 + cdot[LYNX_C_T556] * c45 * c55 +
+              c[LYNX_C_T556] * (cd45 * c55 + c45 * cd55) + cdot[LYNX_C_T555] * (c44 * c44) + A(2) * c[LYNX_C_T555] * c44 * cd44;
+  s_cd[5 * 7 + 5] = cd55;
+  s_cd[4 * 7 + 4] = v;
+  s_cd[4 * 7 + 5] = v;
+  s_cd[5 * 7 + 4] = v;
+}
+
+// ---------------------------------------------------------------------------------------
 // k_trace_records_to_moments: grid = B * P, 64 threads.  Record layout of LYNX_MOMENT_STRIDE: [0..6] mean, [7..27] the
 // upper triangle of the biased covariance; the 7th row and column of C are zero (the 7th coordinate is 1 for every
 // particle).
@@ -137,14 +277,15 @@ __global__ __launch_bounds__(64) void k_trace_records_to_moments(const double* _
 // dependent products, and a wave would otherwise wait for memory once per step.  One lane owns every cell it writes, the
 // sums run in a fixed order, no atomics: the same call returns the same bits.
 // ---------------------------------------------------------------------------------------
-template <typename T, typename ST>
-__global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections dirs, const T* __restrict__ steps,
-                                                          const ST* __restrict__ mu_trace, const ST* __restrict__ cov_trace,
-                                                          const double* __restrict__ mdot /* [B][n][49] */,
-                                                          double* __restrict__ mu_dot /* [B][D][P][7] */,
-                                                          double* __restrict__ cov_dot /* [B][D][P][49] */) {
+template <typename T, typename ST, bool KICK>
+__device__ __forceinline__ void trace_moments_jvp_wave(int S, const TraceDirections& dirs, const T* __restrict__ steps,
+                                                       const ST* __restrict__ mu_trace, const ST* __restrict__ cov_trace,
+                                                       const double* __restrict__ mdot /* [B][n][kRow] */,
+                                                       double* __restrict__ mu_dot /* [B][D][P][7] */,
+                                                       double* __restrict__ cov_dot /* [B][D][P][49] */) {
   using A = double;  // the sweep's own arithmetic, whatever the lattice's dtype (see the head of this file)
-  __shared__ A s_m[64], s_mu[8], s_c[49], s_d[49], s_md[8], s_cd[49], s_y[49], s_z[49];
+  constexpr int kRow = KICK ? LYNX_STEP_STRIDE : 49;  // an entry's tangent: the map (KICK: and the 8 coefficients behind it)
+  __shared__ A s_m[64], s_mu[8], s_c[49], s_d[kRow], s_md[8], s_cd[49], s_y[49], s_z[49];
   const int D = dirs.count;
   const int64_t b = blockIdx.x / D;
   const int d = (int)(blockIdx.x - b * D);
@@ -156,7 +297,7 @@ __global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections
   const T* g_steps = steps + b * (int64_t)S * LYNX_STEP_STRIDE;
   const ST* g_mu = mu_trace + b * (int64_t)P * 7;
   const ST* g_c = cov_trace + b * (int64_t)P * 49;
-  const double* g_d = mdot + b * (int64_t)dirs.entries * 49;
+  const double* g_d = mdot + b * (int64_t)dirs.entries * kRow;
   double* o_mu = mu_dot + (b * D + d) * (int64_t)P * 7;
   double* o_c = cov_dot + (b * D + d) * (int64_t)P * 49;
   int q = dirs.start[d];
@@ -182,7 +323,7 @@ __global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections
     n_d = A(0);
     n_has = false;
     while (at == s) {  // (uniform)
-      n_d += g_d[(int64_t)q * 49 + cl];
+      n_d += g_d[(int64_t)q * kRow + (KICK ? lane : cl)];
       n_has = true;
       ++q;
       at = q < q_end ? dirs.leaf[q] : -1;
@@ -196,9 +337,22 @@ __global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections
       s_c[lane] = n_c;
       s_d[lane] = n_d;
     }
+    if constexpr (KICK) {
+      if (lane >= 49) s_d[lane] = n_d;  // the coefficients' tangents (zeros where the direction has no entry here)
+    }
     const bool has = n_has;
     if (s + 1 < S) fetch(s + 1);
     __syncthreads();
+    bool kick = false;                                               // (uniform) a gaining cavity: its branch follows the products
+    A in_d[5] = {A(0), A(0), A(0), A(0), A(0)};                      // ... on the tangents that ENTER the step, parked here
+    if constexpr (KICK) {
+      const int desc = (int)s_m[LYNX_FLAGS_OFFSET];
+      kick = ((desc >> LYNX_DESC_KIND_SHIFT) & 3) == LYNX_STEP_CAVITY && (desc & LYNX_FLAG_CAV_GAIN);
+      if (kick) {
+        in_d[0] = s_md[4], in_d[1] = s_md[5];
+        in_d[2] = s_cd[4 * 7 + 4], in_d[3] = s_cd[4 * 7 + 5], in_d[4] = s_cd[5 * 7 + 5];
+      }
+    }
     A y = s_cd[i * 7] * s_m[j * 7], z = A(0);  // Y = C_dot M^T
 #pragma unroll
     for (int k = 1; k < 7; ++k) y = fma(s_cd[i * 7 + k], s_m[j * 7 + k], y);
@@ -234,6 +388,17 @@ __global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections
     if (constant) cd = A(0);
     if (l7 == 6) md = A(0);
     __syncthreads();
+    if constexpr (KICK) {
+      if (kick) {  // moment_step_wave's barriers 3 and 4: the linear tangents written | lane 0's entries over them | their reads
+        if (lane < 7) s_md[lane] = md;
+        if (lane < 49) s_cd[lane] = cd;
+        __syncthreads();
+        if (lane == 0) jvp_cavity_branch<A>(s_m, s_d, s_mu, s_c, in_d, s_md, s_cd);
+        __syncthreads();
+        md = s_md[l7];
+        cd = s_cd[cl];
+      }
+    }
     if (lane < 7) {
       s_md[lane] = md;
       o_mu[(int64_t)(s + 1) * 7 + lane] = md;
@@ -245,6 +410,26 @@ __global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections
     // (no barrier here: what the next step writes first -- row, state, Mdot -- was last read in front of the barrier above,
     // and its own first barrier stands between these writes of mu_dot, C_dot and their reads)
   }
+}
+
+template <typename T, typename ST>
+__global__ __launch_bounds__(64) void k_trace_moments_jvp(int S, TraceDirections dirs, const T* __restrict__ steps,
+                                                          const ST* __restrict__ mu_trace, const ST* __restrict__ cov_trace,
+                                                          const double* __restrict__ mdot /* [B][n][49] */,
+                                                          double* __restrict__ mu_dot /* [B][D][P][7] */,
+                                                          double* __restrict__ cov_dot /* [B][D][P][49] */) {
+  trace_moments_jvp_wave<T, ST, false>(S, dirs, steps, mu_trace, cov_trace, mdot, mu_dot, cov_dot);
+}
+
+// ... through gaining cavities (a ParameterBeam's states): the same body with the cavity branch's tangent behind the
+// products, the entries' tangents 64 wide (k_trace_tangent_rows).
+template <typename T>
+__global__ __launch_bounds__(64) void k_trace_moments_jvp_kicks(int S, TraceDirections dirs, const T* __restrict__ steps,
+                                                                const T* __restrict__ mu_trace, const T* __restrict__ cov_trace,
+                                                                const double* __restrict__ rdot /* [B][n][64] */,
+                                                                double* __restrict__ mu_dot /* [B][D][P][7] */,
+                                                                double* __restrict__ cov_dot /* [B][D][P][49] */) {
+  trace_moments_jvp_wave<T, T, true>(S, dirs, steps, mu_trace, cov_trace, rdot, mu_dot, cov_dot);
 }
 
 }  // namespace lynx

@@ -1406,13 +1406,18 @@ def track_along_vjp(segment, beam, trajectories=None, losses=False, screens=Fals
 ENERGY_ROW = 8  # kGradParams: the row of a direction's entry that stands for the energy at that step
 
 
-def _jvp_directions(leaves, wrt):
+def _jvp_directions(leaves, wrt, cavities=False):
     """
     `wrt` of `track_along_jvp` against the leaf elements of a lattice, refused by value -> the directions in the CSR form
     lynx_track_*_along_forward reads: (dir_start (D + 1,) int32, dir_leaf (n,) int32, dir_row (n,) int32, dir_weight (n,)
     float64).  An item is `(element, "name")`, `(element, "misalignment", 0 | 1)` or the string "energy".  An element object
     that occurs several times has an entry per place; `RBend.angle` also feeds e1 and e2 with weight 1/2 (the rule of
     `Gradients.__getitem__`); "energy" is one entry per leaf.
+
+    `cavities` (lynx_track_moments_along_forward_cavities): `voltage`, `phase` and `frequency` of a Cavity that is an active
+    step of the trace's program are directions too, and a direction that holds the voltage or the phase of such a cavity gets
+    one energy entry of weight 1 per leaf BEHIND the first of them -- the energy there, and with it every later map, moves
+    with the direction; the device scales the entry by the energy's own tangent at that leaf.
     """
     from .accelerator.magnets import Cavity, RBend
 
@@ -1443,28 +1448,39 @@ def _jvp_directions(leaves, wrt):
         if slot not in rows:
             raise KeyError(f"track_along_jvp: {type(element).__name__} {element.name!r} has no differentiable parameter {name!r} "
                            f"(it has {sorted(set(r.rsplit('_x', 1)[0].rsplit('_y', 1)[0] for r in rows))})")
-        if isinstance(element, Cavity) and name != "length":
+        active = isinstance(element, Cavity) and cavities and not element.is_skippable  # (a cavity step of the trace's program)
+        if isinstance(element, Cavity) and name != "length" and not active:
             raise NotImplementedError(f"track_along_jvp: {name!r} of Cavity {element.name!r} -- the energy behind a cavity, and with "
                                       "it every later map, depends on it; cavities are not differentiated in forward mode yet")
         feeds = [(rows.index(slot), 1.0)]
         if isinstance(element, RBend) and name == "angle":  # e1 = e1_user + angle/2, e2 = e2_user + angle/2 (rbend.py:79-80)
             feeds += [(rows.index("e1"), 0.5), (rows.index("e2"), 0.5)]
         entries += [(e, row, weight) for e in places for row, weight in feeds]
+        if active and name in ("voltage", "phase"):
+            entries += [(e, ENERGY_ROW, 1.0) for e in range(places[0] + 1, len(leaves))]
         start.append(len(entries))
     return (np.array(start, dtype=np.int32), np.array([e for e, _, _ in entries], dtype=np.int32),
             np.array([r for _, r, _ in entries], dtype=np.int32), np.array([w for _, _, w in entries], dtype=np.float64))
 
 
-def _jvp_program(segment, beam):
+def _jvp_program(segment, beam, cavities=False):
     """Every refusal of `track_along_jvp` about the beam and the lattice, before anything touches the GPU -> (program, leaves)."""
     from .particles.parameter_beam import ParameterBeam
 
     if not isinstance(beam, (ParameterBeam, ParticleBeam)):
         raise TypeError(f"track_along_jvp needs a ParticleBeam or a ParameterBeam, not {type(beam)}")
+    if not isinstance(cavities, (bool, np.bool_)):
+        raise ValueError(f"track_along_jvp: cavities is True or False, not {cavities!r}")
     leaves = list(segment._leaves() if hasattr(segment, "_leaves") else [segment])
     program = engine._trace_plan(segment, leaves)  # (raises for an active Screen or Aperture, naming it)
     for kind, first, _ in program.steps:
-        if kind == _ffi.STEP_CAVITY:
+        if kind == _ffi.STEP_CAVITY and cavities:
+            if isinstance(beam, ParticleBeam):
+                raise NotImplementedError(
+                    f"track_along_jvp: active Cavity {leaves[first].name!r} with a ParticleBeam -- its moments are not closed "
+                    "under a cavity's kick, and forward mode makes no pass over the particles; a ParameterBeam of the same "
+                    "moments is differentiated (track_along_vjp(..., cavities=True) differentiates this beam in reverse mode)")
+        elif kind == _ffi.STEP_CAVITY:
             raise NotImplementedError(
                 f"track_along_jvp: active Cavity {leaves[first].name!r} -- behind a cavity the energy, and with it every later "
                 "map, depends on the cavity's parameters, and a ParticleBeam's moments are not closed under its kick; "
@@ -1482,12 +1498,18 @@ class TrackAlongJVP:
 
     A parameter given per sample has its tangent per sample; one shared by the batch (shape (1,)) gives every sample the
     tangent with respect to the shared value.
+
+    `cavities=True` (a ParameterBeam; lynx_track_moments_along_forward_cavities): active cavities are steps of the sweep -- the
+    tangent of the cavity branch follows a gaining cavity's products, every map is differentiated at its own step's energy, and
+    a direction carries the energy's tangent with it (`energy_dot`, per sample, direction and point).
     """
 
-    def __init__(self, segment, beam, wrt):
-        self.program, self.leaves = _jvp_program(segment, beam)
+    def __init__(self, segment, beam, wrt, cavities=False):
+        self.program, self.leaves = _jvp_program(segment, beam, cavities)
         self.wrt = list(wrt)
-        self._directions = _jvp_directions(self.leaves, self.wrt)
+        self._directions = _jvp_directions(self.leaves, self.wrt, bool(cavities))
+        # through cavity steps only where there is one: a lattice without takes the plain path, bit for bit
+        self._kicks = bool(cavities) and any(kind == _ffi.STEP_CAVITY for kind, _, _ in self.program.steps)
         self.segment, self.beam = segment, beam
         self.trace = engine.track_along(segment, self.leaves, beam, keep_outgoing=True, keep_device=True)
         rt = get_runtime()
@@ -1500,7 +1522,14 @@ class TrackAlongJVP:
         as_ints = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
         directions = (as_ints(start), as_ints(leaf), as_ints(row), weight.ctypes.data_as(C.POINTER(C.c_double)), D, len(leaf))
         states = self.trace._device
-        if isinstance(beam, ParticleBeam):
+        self._energy_dot_dev = self._energy_dot = None
+        if self._kicks:
+            seed = np.array([1.0 if isinstance(item, str) else 0.0 for item in self.wrt])
+            self._energy_dot_dev = rt.empty((B, D, P), np.float64)
+            rt.check(rt.lib.lynx_track_moments_along_forward_cavities(
+                rt.ctx, lat.handle, _p(e_in), _p(states["mu"]), _p(states["cov"]), *directions, _p(self._mu_dot_dev),
+                _p(self._cov_dot_dev), seed.ctypes.data_as(C.POINTER(C.c_double)), _p(self._energy_dot_dev)))
+        elif isinstance(beam, ParticleBeam):
             rt.check(rt.lib.lynx_track_particles_along_forward(
                 rt.ctx, lat.handle, beam.num_particles, _p(e_in), _p(states["records"]), *directions, _p(self._mu_dot_dev),
                 _p(self._cov_dot_dev)))
@@ -1527,7 +1556,12 @@ class TrackAlongJVP:
 
     @property
     def energy_dot(self) -> np.ndarray:
-        """(D,): the tangent of the energy at every point -- without a cavity the incoming one: 1 along "energy", 0 otherwise."""
+        """(D,): the tangent of the energy at every point -- without a cavity the incoming one: 1 along "energy", 0 otherwise.
+        Through cavity steps (`cavities=True` on a lattice that has one): (*batch, D, P) float64, read from the device."""
+        if self._kicks:
+            if self._energy_dot is None:
+                self._energy_dot = self._energy_dot_dev.numpy().reshape(*self.beam.batch_shape, len(self.wrt), self.trace.num_points)
+            return self._energy_dot
         return np.array([1.0 if isinstance(item, str) else 0.0 for item in self.wrt])
 
     def tangent(self, name: str) -> np.ndarray:
@@ -1537,7 +1571,7 @@ class TrackAlongJVP:
         tangent: the formulas are the reverse pass's own.  "energy" is exact: 1 along the "energy" direction, 0 otherwise.
         """
         shape = (*self.beam.batch_shape, len(self.wrt), self.trace.num_points)
-        energy_dot = self.energy_dot[:, None]
+        energy_dot = self.energy_dot if self._kicks else self.energy_dot[:, None]
         if name == "energy":
             return np.broadcast_to(energy_dot, shape).copy()
         mu_bar, cov_bar, energy_bar = trace_property_cotangents(self.trace, {name: 1.0})
@@ -1555,7 +1589,7 @@ class TrackAlongJVP:
         return np.ascontiguousarray(self.mu_dot[..., points[0], :][..., (0, 2)])
 
 
-def track_along_jvp(segment, beam, wrt):
+def track_along_jvp(segment, beam, wrt, cavities=False):
     """
     Forward pass of `segment.track_along(beam)` (the trace is `jvp.trace`) and, right behind it, the forward-mode sweep: the
     tangents of the moments at every point along every direction of `wrt`:
@@ -1570,8 +1604,13 @@ def track_along_jvp(segment, beam, wrt):
     that has voltage, an active Screen or Aperture, a parameter the element does not have, an element that is not in the
     lattice, an empty `wrt`.  The cost is one sweep per direction, each as long as ONE reverse sweep: where reverse mode
     needs a call per output (a BPM and plane, a point of a curve), this needs a direction per parameter.
+
+    `cavities=True` (a ParameterBeam): a lattice with cavities that have voltage is differentiated, too -- a linac's response
+    matrix.  `(cavity, "voltage" | "phase" | "frequency")` of such a cavity are directions; `jvp.energy_dot` is then
+    (*batch, D, P), the tangent of the beam energy at every point.  A ParticleBeam on such a lattice is refused (its moments
+    are not closed under the kick); a lattice without an active cavity takes the plain path for both beam classes.
     """
-    return TrackAlongJVP(segment, beam, wrt)
+    return TrackAlongJVP(segment, beam, wrt, cavities)
 
 
 class OrbitResponseMatrix:
@@ -1582,12 +1621,14 @@ class OrbitResponseMatrix:
         self.matrix, self.bpms, self.correctors, self.jvp = matrix, bpms, correctors, jvp
 
 
-def orbit_response_matrix(segment, beam, bpms=None, correctors=None) -> OrbitResponseMatrix:
+def orbit_response_matrix(segment, beam, bpms=None, correctors=None, cavities=False) -> OrbitResponseMatrix:
     """
     The orbit response matrix of a lattice, in ONE forward-mode call: d(reading of every BPM)/d(angle of every corrector),
     what orbit correction by pseudo-inverse starts from.  By default every BPM and every HorizontalCorrector /
     VerticalCorrector of the flattened lattice, in lattice order.  A BPM need not be active: its reading is the centroid of
-    the beam entering it.  A BPM in front of a corrector reads an exact 0.
+    the beam entering it.  A BPM in front of a corrector reads an exact 0.  `cavities=True` (a ParameterBeam): through
+    accelerating cavities, as `track_along_jvp` takes it -- the response behind a cavity is damped by its map, and the energy
+    behind it sets every later one.
     """
     from .accelerator.diagnostics import BPM
     from .accelerator.magnets import HorizontalCorrector, VerticalCorrector
@@ -1604,7 +1645,7 @@ def orbit_response_matrix(segment, beam, bpms=None, correctors=None) -> OrbitRes
     for bpm in bpms:
         if not any(el is bpm for el in leaves):
             raise KeyError(f"orbit_response_matrix: {bpm!r} is not an element of this lattice")
-    jvp = track_along_jvp(segment, beam, [(corrector, "angle") for corrector in correctors])
+    jvp = track_along_jvp(segment, beam, [(corrector, "angle") for corrector in correctors], cavities)
     readings = np.stack([jvp.reading_tangents(bpm) for bpm in bpms], axis=-3)  # (*batch, n_bpm, D, 2)
     matrix = np.concatenate([readings[..., 0], readings[..., 1]], axis=-2)
     return OrbitResponseMatrix(np.ascontiguousarray(matrix), bpms, correctors, jvp)
