@@ -61,7 +61,7 @@ for dtype in (np.float32, np.float64):
         segment, beam, screen, _, given, _ = loss_case(lx, label, dtype, (3,), False, False)
         vjp = grad.track_along_vjp(segment, beam, image_targets={screen: given})
         save(f"loss {label} {name}", images=segment.track_along(beam, screens=True).image_at("SCREEN"), loss=vjp.image_loss_of(screen),
-             sums=vjp._image_loss[1].numpy(), **gradients(vjp(image_loss_bar=np.array([1.0, -0.5, 2.0])), [screen]))
+             sums=vjp._image_loss.sums.numpy(), **gradients(vjp(image_loss_bar=np.array([1.0, -0.5, 2.0])), [screen]))
         vjp, screen, W, _ = kernel_case(lx, label, dtype, (3,), False)
         save(f"gradients {label} {name}", **gradients(vjp(screen_images_bar={screen: W}), [screen]))
     # 65 screens of one pixel behind a drift each; every third one without a target
@@ -75,6 +75,6 @@ for dtype in (np.float32, np.float64):
     named = [screen for k, screen in enumerate(screens) if k % 3 != 1 or k == 64]
     vjp = grad.track_along_vjp(segment, beam, image_targets={screen: rng.uniform(1e6, 1e7, (3, 1, 1)).astype(dtype) for screen in named})
     bars = {screen: rng.uniform(0.5, 2.0, 3) for screen in named}
-    save(f"65 screens {name}", loss=np.stack([vjp.image_loss_of(screen) for screen in named]), sums=vjp._image_loss[1].numpy(),
+    save(f"65 screens {name}", loss=np.stack([vjp.image_loss_of(screen) for screen in named]), sums=vjp._image_loss.sums.numpy(),
          **gradients(vjp(image_loss_bar=bars), screens))
 print(f"{len(list(out_dir.glob('*.npz')))} cases written to {out_dir}")

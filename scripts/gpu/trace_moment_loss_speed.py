@@ -93,11 +93,11 @@ def kernel_times(segment, beam, targets, keywords, repeats):
 
     forward, reverse = [], []
     vjp = grad.track_along_vjp(segment, beam, moment_targets=targets, **keywords)
-    layout = vjp._moment_layout
+    loss = vjp._moment_loss  # (the `MomentLoss` of lynx_amd/grad/targets.py: both halves' arguments, the forward half's launch)
     for _ in range(repeats):
-        forward.append(sum(profiled(lambda: vjp._evaluate_moment_loss(layout))))
+        forward.append(sum(profiled(lambda: loss.forward(rt))))
         ml = rt.to_device(np.ones(int(np.prod(beam.batch_shape))))
-        args = vjp._moment_loss_arguments(rt, layout)
+        args = loss.arguments(rt)
         B, P = vjp._points_shape()
         states = vjp.trace._device
         if "records" in states:

@@ -1,13 +1,18 @@
 """
-A transcript of every reverse call `lynx_amd/grad.py` makes, without a GPU: per case the keyword arguments given to
+A transcript of every call `lynx_amd.grad` makes, without a GPU: per case the keyword arguments given to
 `engine.track_along`, every library call with every argument by value (tests/reverse_host_fakes.py), everything
 `Gradients` hands out, and for a refusal the exception's type and text.  Only the public API of `lynx_amd.grad` is used,
-so the script runs unchanged on any commit's `grad.py`:
+so the cases run unchanged on any commit's `lynx_amd.grad` -- given fakes that stand in for the runtime where that commit
+asks for it: `fake_gpu` replaces `device.get_runtime`, and both files were made on commits whose `grad.py` bound a copy of
+its own, with a `fake_gpu` that replaced `grad.get_runtime` as well:
 
-    python -m tests.golden.make_reverse_calls        # writes tests/golden/reverse_calls.npz
+    python -m tests.golden.make_reverse_calls reverse    # writes tests/golden/reverse_calls.npz: `CASES`
+    python -m tests.golden.make_reverse_calls targets    # writes tests/golden/target_calls.npz: `TARGET_CASES`
 
-tests/test_reverse_calls_host.py replays `CASES` and compares with that file byte for byte.  The file is made on the
-commit BEFORE a change to `grad.py`, never with the code under test.
+`CASES` are `track_vjp` and the five modes of `track_along_vjp`; `TARGET_CASES` are `image_targets=`, `moment_targets=` and
+forward mode (`track_along_jvp`, `orbit_response_matrix`), with what their objects hand out and every allocation in order.
+tests/test_reverse_calls_host.py replays both and compares with the files byte for byte.  A file is made on the commit
+BEFORE a change to `lynx_amd.grad`, never with the code under test.
 """
 
 import json
@@ -19,18 +24,23 @@ import pytest
 from tests.reverse_host_fakes import FakeArray, fake_gpu
 
 PATH = Path(__file__).resolve().parent / "reverse_calls.npz"
+TARGET_PATH = Path(__file__).resolve().parent / "target_calls.npz"
 PROPERTIES = ("mu_x", "mu_xp", "mu_y", "mu_yp", "mu_s", "mu_p", "sigma_x", "sigma_xp", "sigma_y", "sigma_yp", "sigma_s",
               "sigma_p", "sigma_xxp", "sigma_yyp", "emittance_x", "emittance_y", "normalized_emittance_x",
               "normalized_emittance_y", "beta_x", "beta_y", "alpha_x", "alpha_y")  # tests/test_trace_grad_host.py
 BEAM_PROPERTIES = ("mu_y", "sigma_x", "sigma_p", "sigma_xxp", "sigma_yyp")
-CASES = {}
+CASES, TARGET_CASES = {}, {}
 
 
-def case(name, **fake):
+def case(name, cases=CASES, **fake):
     def register(fn):
-        CASES[name] = (fn, fake)
+        cases[name] = (fn, fake)
         return fn
     return register
+
+
+def target_case(name, **fake):
+    return case(name, TARGET_CASES, **fake)
 
 
 def handed_out(g, segment):
@@ -64,12 +74,19 @@ class Log:
         self.events.append({"label": label, "gradients": None if segment is None else handed_out(value, segment)})
         return value
 
+    def value(self, label, thunk):
+        """Run `thunk`; record what it raised or the value it returned: arrays, scalars, strings, lists and dicts of them."""
+        try:
+            self.events.append({"label": label, "value": thunk()})
+        except Exception as error:  # noqa: BLE001
+            self.events.append({"label": label, "raised": type(error).__name__, "text": str(error)})
+
 
 def transcript(name):
     """The transcript of one case as a tree of dicts, lists, scalars and arrays."""
     import lynx_amd as lx
 
-    fn, fake = CASES[name]
+    fn, fake = CASES[name] if name in CASES else TARGET_CASES[name]
     log = Log()
     ddof = lx.config.std_ddof
     with pytest.MonkeyPatch.context() as monkeypatch:
@@ -78,7 +95,10 @@ def transcript(name):
             fn(lx, log)
         finally:
             lx.config.std_ddof = ddof
-    return {"forward": list(forward), "calls": [{"entry": entry, "arguments": args} for entry, args in rt.lib.records], "events": log.events}
+    out = {"forward": list(forward), "calls": [{"entry": entry, "arguments": args} for entry, args in rt.lib.records], "events": log.events}
+    if name in TARGET_CASES:  # ... and every allocation in order: an upload made once shows as one
+        out["allocations"] = [f"{a.how} {list(a.shape)} {a.dtype.str}" for a in rt.allocations]
+    return out
 
 
 # ---- the cases --------------------------------------------------------------------------------------------------------
@@ -446,6 +466,282 @@ def _(lx, log):
     log.attempt("65536 samples with screens", lambda: make(lx.Segment([lx.Drift(f(1.0), name="D"), screen]), many, screens=True))
 
 
+# ---- the cases of target_calls.npz: image targets, moment targets, forward mode ---------------------------------------------
+
+
+def screened(lx, batch, dtype):
+    """(segment, first, last, quad): SCR_FIRST (5 x 4 pixels), D, Q, SCR_LAST (3 x 2) -- both screens active."""
+    pixels = dict(pixel_size=(1e-4, 1e-4), is_active=True, dtype=dtype)
+    first = lx.Screen(resolution=(5, 4), misalignment=np.array([1e-5, -2e-5]), name="SCR_FIRST", **pixels)
+    last = lx.Screen(resolution=(3, 2), misalignment=np.zeros((*batch, 2)), name="SCR_LAST", **pixels)
+    quad = lx.Quadrupole(full(batch, 0.2, dtype), k1=spread(batch, 1, 2, dtype), name="Q", dtype=dtype)
+    return lx.Segment([first, lx.Drift(full(batch, 1.0, dtype), name="D", dtype=dtype), quad, last]), first, last, quad
+
+
+def image_targets_case(batch, dtype):
+    def run(lx, log):
+        rng = np.random.default_rng(31)
+        make = lx.grad.track_along_vjp
+        segment, first, last, quad = screened(lx, batch, dtype)
+        beam = parameter_beam(lx, batch, dtype)
+        t_first, t_last, per_sample = draw(rng, (5, 4)), draw(rng, (3, 2)), draw(rng, (*batch, 5, 4))
+        log.attempt("no dict", lambda: make(segment, beam, image_targets=[t_last]))
+        log.attempt("ImageTargets of no dict", lambda: lx.grad.ImageTargets([t_last]))
+        log.attempt("an unknown key", lambda: make(segment, beam, image_targets={"NOPE": t_last}))
+        log.attempt("the quadrupole as a key", lambda: make(segment, beam, image_targets={quad: t_last}))
+        log.attempt("a target that does not fit", lambda: make(segment, beam, image_targets={first: t_last}))
+        log.attempt("a per-sample target that does not fit", lambda: make(segment, beam, image_targets={last: np.ones((5, 3, 2))}))
+        log.attempt("two targets for one screen", lambda: make(segment, beam, image_targets={first: t_first, "SCR_FIRST": t_first}))
+        log.attempt("a ParticleBeam", lambda: make(segment, particle_beam(lx, batch, dtype), image_targets={last: t_last}))
+        without = log.attempt("screens alone", lambda: make(segment, beam, screens=True))
+        log.attempt("image_loss_bar without targets", lambda: without(image_loss_bar=1.0))
+        log.value("image_loss without targets", lambda: without.image_loss)
+        log.value("image_loss_of without targets", lambda: without.image_loss_of(last))
+        # two active screens, one with a target shared by the batch
+        vjp = log.attempt("one shared target", lambda: make(segment, beam, image_targets={last: t_last}))
+        log.value("image_loss", lambda: vjp.image_loss)
+        log.value("image_loss_of, by element", lambda: vjp.image_loss_of(last))
+        log.value("image_loss_of, by point", lambda: vjp.image_loss_of(3))
+        log.value("image_loss_of a point without a screen", lambda: vjp.image_loss_of(4))
+        log.value("image_loss_of a screen without a target", lambda: vjp.image_loss_of("SCR_FIRST"))
+        log.value("image_loss_of no screen", lambda: vjp.image_loss_of("Q"))
+        log.attempt("a scalar bar", lambda: vjp(image_loss_bar=0.5), segment)
+        log.attempt("a bar over the batch, beside a property", lambda: vjp(image_loss_bar=draw(rng, batch), beta_x=1.0))
+        log.attempt("a dict of bars, one screen named twice", lambda: vjp(image_loss_bar={last: 2.0, "SCR_LAST": draw(rng, batch)}, energy_bar=draw(rng, (*batch, 5))))
+        log.attempt("an empty dict of bars", lambda: vjp(image_loss_bar={}, mu_bar=draw(rng, (*batch, 5, 7))))
+        log.attempt("no bar", lambda: vjp(sigma_x=1.0), segment)
+        log.attempt("a bar of a screen without a target", lambda: vjp(image_loss_bar={first: 1.0}))
+        log.attempt("a bar that does not broadcast", lambda: vjp(image_loss_bar=np.ones(5)))
+        log.attempt("a bar in a dict that does not broadcast", lambda: vjp(image_loss_bar={last: np.ones((7, 2))}))
+        log.attempt("screen_images_bar without screens", lambda: vjp(screen_images_bar={last: 1.0}))
+        # a target per sample beside a shared one: a row per sample
+        both = log.attempt("a target per sample", lambda: make(segment, beam, image_targets={"SCR_LAST": t_last, 0: per_sample}))
+        log.value("image_loss of both", lambda: both.image_loss)
+        log.attempt("a dict of bars for both", lambda: both(image_loss_bar={first: draw(rng, batch), 3: 0.25}), segment)
+        # a dict is uploaded per pass, an ImageTargets once
+        for _ in range(2):
+            again = log.attempt("a dict again", lambda: make(segment, beam, image_targets={last: t_last}))
+            log.attempt("its bar", lambda: again(image_loss_bar=1.0))
+        targets = lx.grad.ImageTargets({first: t_first})
+        for _ in range(2):
+            again = log.attempt("the same ImageTargets", lambda: make(segment, beam, image_targets=targets))
+            log.attempt("its bar", lambda: again(image_loss_bar=1.0))
+        # with the images as well: both cotangents in one call
+        images = log.attempt("screens and targets", lambda: make(segment, beam, screens=True, image_targets=targets, losses=True))
+        log.attempt("both cotangents", lambda: images(screen_images_bar={last: draw(rng, (3, 2))}, image_loss_bar=draw(rng, batch), alpha_y=0.5), segment)
+        log.events.append({"label": "the layout of the image cotangents", "value": images._image_cotangents({"SCR_LAST": 0.5})})
+        first.is_active = last.is_active = False
+        idle = log.attempt("targets and no active screen", lambda: make(segment, beam, image_targets={}))
+        log.value("image_loss of no screen", lambda: idle.image_loss)
+        log.attempt("a bar of no screen", lambda: idle(image_loss_bar=1.0, mu_x=1.0))
+    return run
+
+
+target_case("image targets, (2,) float64")(image_targets_case((2,), np.float64))
+target_case("image targets, (2, 3) float32")(image_targets_case((2, 3), np.float32))
+
+
+def matched(lx, batch, dtype, mode):
+    """(segment, beam, keywords of track_along_vjp) of a mode: Q1, D1, M1, Q2, M2, with an aperture or a cavity where the mode needs one."""
+    f = lambda v: full(batch, v, dtype)  # noqa: E731
+    elements = [lx.Quadrupole(f(0.2), k1=spread(batch, 1, 2, dtype), name="Q1", dtype=dtype), lx.Drift(f(0.5), name="D1", dtype=dtype), lx.Marker(name="M1"),
+                lx.Quadrupole(f(0.2), k1=f(-1.5), name="Q2", dtype=dtype), lx.Marker(name="M2")]
+    if mode == "survivors":
+        elements.insert(3, lx.Aperture(x_max=f(1e-3), y_max=f(1e-3), is_active=True, name="COL", dtype=dtype))
+    if mode in ("kicks", "behind a cavity"):
+        elements[1] = lx.Cavity(f(1.0), voltage=f(1e7), phase=f(0.0), frequency=f(1.3e9), name="CAV", dtype=dtype)
+    beam = parameter_beam(lx, batch, dtype) if mode == "moments" else particle_beam(lx, batch, dtype)
+    keywords = {"trajectories": {"trajectories": [2, 0]}, "behind a cavity": {"trajectories": [2, 0]}, "survivors": {"losses": True}, "kicks": {"cavities": True}}
+    return lx.Segment(elements), beam, keywords.get(mode, {})
+
+
+def moment_targets_case(batch, dtype, mode):
+    def run(lx, log):
+        rng = np.random.default_rng(32)
+        segment, beam, keywords = matched(lx, batch, dtype, mode)
+        P = len(segment.elements) + 1
+        per_sample = batch != (2,)  # (a target and a weight per sample: a row set per sample)
+        targets = lx.grad.MomentTargets({"M1": {"beta_x": 4.0 + draw(rng, batch) if per_sample else 4.0, "beta_y": 2.0}, -1: {"sigma_x": 1e-4, "energy": 1e8, "normalized_emittance_y": 1e-6}},
+                                        weights={"M1": {"beta_y": 0.5 + np.abs(draw(rng, batch[-1:])) if per_sample else 0.25}, P - 1: {"energy": 1e-12}})
+        log.value("terms before a trace", lambda: targets.terms)
+        for _ in range(2):  # the same object in two passes: its rows are uploaded once
+            vjp = log.attempt("the targets", lambda: lx.grad.track_along_vjp(segment, beam, moment_targets=targets, **keywords))
+        log.value("terms", lambda: [list(term) for term in targets.terms])
+        log.value("the same terms", lambda: vjp._moment_targets.terms == targets.terms)
+        log.value("moment_values", lambda: vjp.moment_values)
+        log.value("moment_loss", lambda: vjp.moment_loss)
+        log.value("moment_loss_of M1", lambda: vjp.moment_loss_of("M1"))
+        log.value("moment_loss_of the last point", lambda: vjp.moment_loss_of(-1))
+        log.value("moment_loss_of a point without a target", lambda: vjp.moment_loss_of(0))
+        log.value("moment_loss_of no point", lambda: vjp.moment_loss_of("M7"))
+        more = {"wrt_particles": True} if mode == "kicks" else {"trajectories_bar": draw(rng, (*batch, P, 2, 6))} if mode == "trajectories" else {}
+        log.attempt("the bar alone, a scalar", lambda: vjp(moment_loss_bar=1.0), segment)
+        log.attempt("the bar alone, over the batch", lambda: vjp(moment_loss_bar=draw(rng, batch), **more))
+        log.attempt("beside mu_bar", lambda: vjp(moment_loss_bar=2.0, mu_bar=draw(rng, (*batch, P, 6)), **more), segment)
+        log.attempt("beside a property", lambda: vjp(moment_loss_bar=draw(rng, batch), beta_x=draw(rng, (*batch, P))))
+        log.attempt("beside energy_bar", lambda: vjp(moment_loss_bar=0.5, energy_bar=draw(rng, (*batch, P))))
+        log.attempt("beside the energy as a property", lambda: vjp(moment_loss_bar=0.5, energy=1.0))
+        log.attempt("no bar", lambda: vjp(sigma_y=1.0))
+        log.attempt("a bar that does not broadcast", lambda: vjp(moment_loss_bar=np.ones(5)))
+        # terms of the energy alone, from a dict: no moment cotangent comes of them
+        energies = log.attempt("energy alone", lambda: lx.grad.track_along_vjp(segment, beam, moment_targets={"M2": {"energy": 1.1e8}, 1: {"energy": 1e8}}, **keywords))
+        log.value("its values", lambda: energies.moment_values)
+        log.attempt("its bar", lambda: energies(moment_loss_bar=1.0), segment)
+        log.attempt("its bar beside a property", lambda: energies(moment_loss_bar=1.0, sigma_x=draw(rng, (*batch, P))))
+    return run
+
+
+for _mode in ("moments", "particles", "trajectories", "survivors", "kicks"):
+    target_case(f"moment targets, {_mode}, (2,) float32")(moment_targets_case((2,), np.float32, _mode))
+target_case("moment targets, moments, (2, 3) float64")(moment_targets_case((2, 3), np.float64, "moments"))
+target_case("moment targets, particles, (2, 3) float64")(moment_targets_case((2, 3), np.float64, "particles"))
+
+
+@target_case("moment targets, refusals and the three together")
+def _(lx, log):
+    batch, dtype = (2,), np.float64
+    make, Targets = lx.grad.track_along_vjp, lx.grad.MomentTargets
+    segment, beam, _ = matched(lx, batch, dtype, "moments")
+    log.attempt("no dict", lambda: make(segment, beam, moment_targets=[1.0]))
+    log.attempt("MomentTargets of no dict", lambda: Targets([("M1", "beta_x", 1.0)]))
+    log.attempt("a point without a dict", lambda: Targets({"M1": 1.0}))
+    log.attempt("weights of no dict", lambda: Targets({"M1": {"beta_x": 1.0}}, weights=[1.0]))
+    log.attempt("no target", lambda: Targets({"M1": {}}))
+    log.attempt("an unknown property", lambda: make(segment, beam, moment_targets={"M1": {"beta_z": 1.0}}))
+    log.attempt("an unknown property of a weight", lambda: Targets({"M1": {"beta_x": 1.0}}, weights={"M1": {"gamma": 1.0}}))
+    log.attempt("a weight without a target", lambda: make(segment, beam, moment_targets=Targets({"M1": {"beta_x": 1.0}}, weights={"M2": {"beta_x": 1.0}})))
+    log.attempt("a doubled target", lambda: make(segment, beam, moment_targets={"M1": {"beta_x": 1.0}, 3: {"beta_x": 2.0}}))
+    log.attempt("a doubled weight", lambda: make(segment, beam, moment_targets=Targets({"M1": {"beta_x": 1.0}}, weights={"M1": {"beta_x": 1.0}, -3: {"beta_x": 2.0}})))
+    log.attempt("a target that does not broadcast", lambda: make(segment, beam, moment_targets={"M1": {"beta_x": np.ones(3)}}))
+    log.attempt("a weight that does not broadcast", lambda: make(segment, beam, moment_targets=Targets({"M1": {"beta_x": 1.0}}, weights={"M1": {"beta_x": np.ones((2, 2))}})))
+    log.attempt("no such element", lambda: make(segment, beam, moment_targets={"M7": {"beta_x": 1.0}}))
+    log.attempt("no such point", lambda: make(segment, beam, moment_targets={6: {"beta_x": 1.0}}))
+    plain = log.attempt("no targets", lambda: make(segment, beam))
+    log.attempt("moment_loss_bar without targets", lambda: plain(moment_loss_bar=1.0))
+    for name in ("moment_values", "moment_loss"):
+        log.value(f"{name} without targets", lambda: getattr(plain, name))
+    log.value("moment_loss_of without targets", lambda: plain.moment_loss_of("M1"))
+    # a ParticleBeam behind an active cavity: a moment's target is refused where its cotangent is, the energy's is not
+    behind, particles, keywords = matched(lx, batch, dtype, "behind a cavity")
+    log.attempt("a target behind a cavity", lambda: make(behind, particles, moment_targets={"M1": {"beta_x": 1.0}}))
+    log.attempt("a target behind a cavity, with trajectories", lambda: make(behind, particles, moment_targets={-1: {"energy": 1.1e8, "beta_x": 1.0}}, **keywords))
+    chosen = log.attempt("the energy behind a cavity, with trajectories", lambda: make(behind, particles, moment_targets={-1: {"energy": 1.1e8}}, **keywords))
+    log.attempt("its bar alone", lambda: chosen(moment_loss_bar=1.0), behind)
+    log.attempt("its bar beside the trajectories'", lambda: chosen(moment_loss_bar=1.0, trajectories_bar=np.ones(6)), behind)
+    log.attempt("a property behind the cavity", lambda: chosen(moment_loss_bar=1.0, beta_x=1.0))
+    # image targets, images and moment targets in one call
+    rng = np.random.default_rng(33)
+    screens, first, last, quad = screened(lx, batch, dtype)
+    three = log.attempt("all three", lambda: make(screens, beam, screens=True, image_targets={last: draw(rng, (3, 2))}, moment_targets={"Q": {"beta_x": 3.0}}))
+    log.attempt("all three bars", lambda: three(screen_images_bar={first: 1.0}, image_loss_bar=1.0, moment_loss_bar=1.0), screens)
+    log.attempt("all three bars and a property", lambda: three(screen_images_bar={first: 1.0}, image_loss_bar=1.0, moment_loss_bar=1.0, alpha_x=draw(rng, (*batch, 5))))
+
+
+@target_case("moment targets, losses, nobody left at a point", nobody=((1, 5), (1, 6)))
+def _(lx, log):
+    batch, dtype = (2,), np.float64
+    segment, beam, keywords = matched(lx, batch, dtype, "survivors")
+    make = lx.grad.track_along_vjp
+    log.attempt("a target where nobody is", lambda: make(segment, beam, moment_targets={5: {"sigma_x": 1e-4}}, **keywords))
+    log.attempt("a target where nobody is, behind one that is fine", lambda: make(segment, beam, moment_targets={2: {"mu_x": 0.0}, "M2": {"alpha_y": 0.0}}, **keywords))
+    vjp = log.attempt("the energy there and a moment in front", lambda: make(segment, beam, moment_targets={5: {"energy": 1e8}, 4: {"sigma_x": 1e-4}}, **keywords))
+    log.value("moment_values", lambda: vjp.moment_values)
+    log.attempt("the bar", lambda: vjp(moment_loss_bar=np.array([1.0, -0.5])), segment)
+    w = np.zeros((*batch, 7))
+    w[1, 5] = 1.0
+    log.attempt("a cotangent where nobody is", lambda: vjp(moment_loss_bar=1.0, sigma_x=w))
+
+
+def forward_lattice(lx, batch, dtype):
+    """(segment, quad, bend, bpm, corrector): Q, RB, BPM, HC, Q again, VC -- the quadrupole object placed twice."""
+    f = lambda v: full(batch, v, dtype)  # noqa: E731
+    mixed, bpm = mixed_lattice(lx, batch, dtype, bpm_active=False)
+    _, quad, bend, _, corrector = mixed.elements
+    return lx.Segment([quad, bend, bpm, corrector, quad, lx.VerticalCorrector(f(0.1), angle=f(1e-4), name="VC", dtype=dtype)]), quad, bend, bpm, corrector
+
+
+def handed_out_forward(lx, log, jvp, bpm):
+    for name in ("mu_dot", "cov_dot", "energy_dot"):
+        log.value(name, lambda: getattr(jvp, name))
+    for name in ("beta_x", "normalized_emittance_y", "energy", "sigma_p", "gamma"):
+        log.value(f"the tangent of {name}", lambda: jvp.tangent(name))
+    log.value("the tangents of a reading", lambda: jvp.reading_tangents(bpm))
+    log.value("the tangents of no element's reading", lambda: jvp.reading_tangents(lx.BPM(name="OTHER")))
+
+
+def forward_case(batch, dtype, particles):
+    def run(lx, log):
+        segment, quad, bend, bpm, corrector = forward_lattice(lx, batch, dtype)
+        beam = particle_beam(lx, batch, dtype) if particles else parameter_beam(lx, batch, dtype)
+        make, matrix = lx.grad.track_along_jvp, lx.grad.orbit_response_matrix
+        wrt = [(quad, "k1"), (bend, "angle"), (quad, "misalignment", 1), "energy", (corrector, "angle")]
+        jvp = log.attempt("five directions", lambda: make(segment, beam, wrt))
+        handed_out_forward(lx, log, jvp, bpm)
+        # `cavities=True` on a lattice without an active cavity is the plain call, for both beam classes
+        same = log.attempt("cavities=True without a cavity", lambda: make(segment, beam, [(quad, "misalignment", 0), "energy"], cavities=True))
+        log.value("energy_dot", lambda: same.energy_dot)
+        log.value("the tangent of energy", lambda: same.tangent("energy"))
+
+        def response(**given):
+            found = matrix(segment, beam, **given)
+            return {"matrix": found.matrix, "bpms": [el.name for el in found.bpms], "correctors": [el.name for el in found.correctors],
+                    "directions": len(found.jvp.wrt)}
+
+        log.value("the response matrix", response)
+        log.value("the response matrix of given lists", lambda: response(bpms=[bpm, bpm], correctors=[segment.VC]))
+        log.value("the response matrix, cavities=True", lambda: response(cavities=True))
+        # every refusal of `wrt`
+        other = lx.Drift(full(batch, 1.0, dtype), name="OTHER", dtype=dtype)
+        for label, bad in (("empty", []), ("a string", ["k1"]), ("no tuple", [quad]), ("four items", [(quad, "k1", 0, 1)]), ("no name", [(quad, 1)]),
+                           ("not of the lattice", [(other, "length")]), ("a vector without a component", [(quad, "misalignment")]),
+                           ("a vector with component 2", [(quad, "misalignment", 2)]), ("a scalar with a component", [(quad, "k1", 0)]),
+                           ("no such parameter", [(bend, "k1")]), ("a BPM's parameter", [(bpm, "angle")]), ("no such parameter, with a component", [(bend, "k7", 0)])):
+            log.attempt(f"wrt: {label}", lambda: make(segment, beam, bad))
+        log.attempt("no beam", lambda: make(segment, None, wrt))
+        for bad in ("yes", 1, None):
+            log.attempt(f"cavities={bad!r}", lambda: make(segment, beam, wrt, cavities=bad))
+        drift = lx.Drift(full(batch, 1.0, dtype), name="D", dtype=dtype)
+        log.attempt("an active screen", lambda: make(lx.Segment([drift, lx.Screen(is_active=True, name="SCR7")]), beam, [(drift, "length")]))
+        aperture = lx.Aperture(x_max=full(batch, 1e-3, dtype), y_max=full(batch, 1e-3, dtype), is_active=True, name="AP1", dtype=dtype)
+        log.attempt("an active aperture", lambda: make(lx.Segment([drift, aperture]), beam, [(drift, "length")], cavities=True))
+        log.attempt("the response matrix without a BPM", lambda: matrix(lx.Segment([drift, corrector]), beam))
+        log.attempt("the response matrix without a corrector", lambda: matrix(lx.Segment([drift, bpm]), beam))
+        log.attempt("the response matrix of no lists", lambda: matrix(segment, beam, bpms=[], correctors=[]))
+        log.attempt("the response matrix of another BPM", lambda: matrix(segment, beam, bpms=[lx.BPM(name="OTHER")]))
+        log.attempt("the response matrix of another corrector", lambda: matrix(segment, beam, correctors=[lx.HorizontalCorrector(full(batch, 0.1, dtype), name="HC9", dtype=dtype)]))
+    return run
+
+
+target_case("forward mode, ParameterBeam, (2,) float64")(forward_case((2,), np.float64, False))
+target_case("forward mode, ParticleBeam, (2, 3) float32")(forward_case((2, 3), np.float32, True))
+
+
+@target_case("forward mode, cavities")
+def _(lx, log):
+    batch, dtype = (2,), np.float64
+    segment, bpm = with_cavity(lx, batch, dtype)  # (Q, CAV1, BPM, RB)
+    cavity, quad, bend = segment.CAV1, segment.Q, segment.RB
+    idle = lx.Cavity(full(batch, 1.0, dtype), voltage=full(batch, 0.0, dtype), phase=full(batch, 0.0, dtype), frequency=full(batch, 1.3e9, dtype), name="IDLE", dtype=dtype)
+    corrector = lx.HorizontalCorrector(full(batch, 0.1, dtype), angle=full(batch, 1e-4, dtype), name="HC", dtype=dtype)
+    segment = lx.Segment([corrector, *segment.elements, idle])
+    beam, particles = parameter_beam(lx, batch, dtype), particle_beam(lx, batch, dtype)
+    make = lx.grad.track_along_jvp
+    wrt = [(cavity, "voltage"), (quad, "k1"), (cavity, "phase"), "energy", (cavity, "frequency"), (cavity, "length"), (bend, "angle"), (idle, "length")]
+    log.attempt("without the switch", lambda: make(segment, beam, wrt[1:2]))
+    log.attempt("without the switch, a ParticleBeam", lambda: make(segment, particles, wrt[1:2]))
+    log.attempt("a ParticleBeam", lambda: make(segment, particles, wrt[1:2], cavities=True))
+    log.attempt("the voltage of a cavity without any", lambda: make(segment, beam, [(idle, "voltage")], cavities=True))
+    cavity.voltage = full(batch, 0.0, dtype)
+    log.attempt("the voltage of a cavity switched off, without the switch", lambda: make(segment, beam, [(cavity, "phase")]))
+    cavity.voltage = spread(batch, 1e7, 2e7, dtype)
+    jvp = log.attempt("through the cavity", lambda: make(segment, beam, wrt, cavities=True))
+    handed_out_forward(lx, log, jvp, bpm)
+    found = log.attempt("the response matrix", lambda: lx.grad.orbit_response_matrix(segment, beam, cavities=True))
+    log.value("its matrix", lambda: found.matrix)
+    log.value("its energy_dot", lambda: found.jvp.energy_dot)
+    log.attempt("the response matrix without the switch", lambda: lx.grad.orbit_response_matrix(segment, beam))
+
+
 # ---- the file ---------------------------------------------------------------------------------------------------------
 
 
@@ -486,8 +782,14 @@ def load(path):
 
 
 if __name__ == "__main__":
+    import sys
+
+    files = {"reverse": (PATH, CASES), "targets": (TARGET_PATH, TARGET_CASES)}
+    if sys.argv[1:] not in (["reverse"], ["targets"]):
+        sys.exit("usage: python -m tests.golden.make_reverse_calls reverse | targets")
+    path, cases = files[sys.argv[1]]
     arrays = []
-    index = {name: flatten(transcript(name), arrays) for name in CASES}
-    save(PATH, index, arrays)
+    index = {name: flatten(transcript(name), arrays) for name in cases}
+    save(path, index, arrays)
     calls = sum(len(entry["calls"]) for entry in index.values())
-    print(f"{len(CASES)} cases, {calls} library calls, {len(arrays)} arrays, {PATH.stat().st_size} bytes")
+    print(f"{len(cases)} cases, {calls} library calls, {len(arrays)} arrays, {path.stat().st_size} bytes")

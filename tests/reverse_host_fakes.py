@@ -1,9 +1,9 @@
 """
-What the host tests of the reverse passes (`lynx_amd/grad.py`) share: a runtime, a library and device arrays that exist
-on the host alone, and the two fixtures built on them.  The library records every call in full -- the entry point's name
+What the host tests of the reverse and forward-mode passes (the package `lynx_amd/grad/`) share: a runtime, a library and
+device arrays that exist on the host alone, and the two fixtures built on them.  The library records every call in full -- the entry point's name
 and each argument by value --, an allocated output reads back as seeded random numbers, and the forward passes
 (`engine.track_along`, `engine.run_program_particles`, `engine.run_program_parameters`) are fabricated on the host: what
-`grad.py` does between its arguments and the C boundary is then a pure function, which tests/test_reverse_calls_host.py
+the package does between its arguments and the C boundary is then a pure function, which tests/test_reverse_calls_host.py
 holds to a transcript.
 
 `fake_engine_gpu` leaves the forward passes as they are and replaces the runtime alone: the library then also plays the
@@ -91,6 +91,7 @@ class FakeLibrary:
     def _host_bytes(address, count, dtype):
         """`count` scalars the host holds at `address`, as the upload they are."""
         dtype = np.dtype(dtype)
+        address = C.cast(address, C.c_void_p).value if isinstance(address, C._Pointer) else address
         return {"host": np.frombuffer(C.string_at(address, count * dtype.itemsize), dtype=dtype).copy()}
 
     @staticmethod
@@ -157,6 +158,20 @@ class FakeLibrary:
         mu.fill, cov.fill = fabricated_moments((B,), (P,), mu.dtype, 2)
         e_trace.fill = fabricated_energy((B, P), e_trace.ordinal)
         return args
+
+    # ---- the forward-mode sweeps: the directions (CSR) and the energy seeds are host arrays the call reads in place ----
+
+    def _directions(self, start, leaf, row, weight, n_directions, n_entries):
+        return (self._host_bytes(start, n_directions + 1, np.int32), self._host_bytes(leaf, n_entries, np.int32),
+                self._host_bytes(row, n_entries, np.int32), self._host_bytes(weight, n_entries, np.float64), n_directions, n_entries)
+
+    def _play_track_moments_along_forward(self, *args):
+        return (*args[:5], *self._directions(*args[5:11]), *args[11:])
+
+    _play_track_particles_along_forward = _play_track_moments_along_forward
+
+    def _play_track_moments_along_forward_cavities(self, *args):
+        return (*args[:5], *self._directions(*args[5:11]), *args[11:13], self._host_bytes(args[13], args[9], np.float64), args[14])
 
 
 class FakeRuntime:
@@ -234,11 +249,11 @@ def fake_engine_gpu(monkeypatch, nobody=()):
     `lynx_amd` with the runtime replaced and nothing else, until `monkeypatch` is undone: `engine.track`, `track_along`,
     `transfer_map` and `cavity_rmatrix` run as they are, against a library that records.  Returns the runtime.
     """
-    from lynx_amd import device, engine, grad
+    from lynx_amd import device, engine
     from lynx_amd.accelerator import diagnostics
 
     rt = FakeRuntime(nobody)
-    for module in (device, engine, grad, diagnostics):
+    for module in (device, engine, diagnostics):
         monkeypatch.setattr(module, "get_runtime", lambda: rt)
     return rt
 
@@ -250,7 +265,8 @@ def fake_gpu(monkeypatch, nobody=(), clamped=()):
     `clamped`: the coordinates whose variance a fabricated outgoing ParameterBeam has at 1e-20 and below.
     """
     import lynx_amd as lx
-    from lynx_amd import engine, grad
+    import lynx_amd.grad  # noqa: F401 (`import lynx_amd` does not import it)
+    from lynx_amd import device, engine
     from lynx_amd.device import Dual
     from lynx_amd.trace import BeamTrace
 
@@ -258,7 +274,14 @@ def fake_gpu(monkeypatch, nobody=(), clamped=()):
 
     def track_along(owner, leaves, incoming, **kwargs):
         forward.append(kwargs)
-        leaves, batch, dtype = list(leaves), incoming.batch_shape, incoming.dtype
+        trace = fabricated_trace(owner, list(leaves), incoming, **kwargs)
+        if kwargs.get("keep_energy"):  # (asked to keep the energies the real pass also leaves them on the device)
+            B = int(np.prod(incoming.batch_shape, dtype=np.int64))
+            trace._device["energy"] = rt.forward("energy", (B, trace.num_points), incoming.dtype)
+        return trace
+
+    def fabricated_trace(owner, leaves, incoming, **kwargs):
+        batch, dtype = incoming.batch_shape, incoming.dtype
         B, P = int(np.prod(batch, dtype=np.int64)), len(leaves) + 1
         energy = np.broadcast_to(np.asarray(incoming.energy, dtype=np.float64)[..., None], (*batch, P)) * np.linspace(1.0, 1.5, P)
         lengths, names = [1.0] * (P - 1), [el.name for el in leaves]
@@ -307,7 +330,7 @@ def fake_gpu(monkeypatch, nobody=(), clamped=()):
         def __init__(self, program):
             self.E = len(program.leaves)
 
-    def device(self, runtime=None):
+    def on_device(self, runtime=None):
         if self._dev is None:
             self._dev = rt.to_device(self._host)
         return self._dev
@@ -318,8 +341,8 @@ def fake_gpu(monkeypatch, nobody=(), clamped=()):
     patch.setattr(engine, "run_program_parameters", run_program_parameters)
     patch.setattr(engine, "_ready", lambda cache, program, *a, **k: Lattice(program))
     patch.setattr(engine, "get_runtime", lambda: rt)
-    patch.setattr(grad, "get_runtime", lambda: rt)
-    patch.setattr(Dual, "device", device)
+    patch.setattr(device, "get_runtime", lambda: rt)  # (`lynx_amd.grad` asks the module, every time)
+    patch.setattr(Dual, "device", on_device)
     patch.setattr(Dual, "broadcast_device",
                   lambda self, runtime, shape: rt.to_device(np.ascontiguousarray(np.broadcast_to(self.host(), tuple(shape)))))
     return rt, forward
@@ -340,11 +363,10 @@ def recorded(monkeypatch):
 @pytest.fixture
 def no_gpu(monkeypatch):
     """Anything that asks for the GPU runtime fails the test."""
-    from lynx_amd import device, engine, grad
+    from lynx_amd import device, engine
 
     def refuse(*args, **kwargs):
         raise AssertionError("track_along_vjp touched the GPU runtime")
 
     monkeypatch.setattr(device, "get_runtime", refuse)
     monkeypatch.setattr(engine, "get_runtime", refuse)
-    monkeypatch.setattr(grad, "get_runtime", refuse)

@@ -289,7 +289,7 @@ def test_one_direction_on_a_cavity_phase_and_a_quadrupole_behind_it(lx, monkeypa
         start, leaf, row, weight = own(leaves, [(leaves[0], "phase"), (leaves[2], "k1")], cavities)
         return np.array([0, len(leaf)], dtype=np.int32), leaf, row, weight * np.where(row == 1, 0.5, 1.0)  # (k1 with weight 1/2)
 
-    monkeypatch.setattr(lx.grad, "_jvp_directions", merged)
+    monkeypatch.setattr(lx.grad.jvp, "_jvp_directions", merged)  # (the module that holds `TrackAlongJVP`)
     _against_restatement(lx, desc, lambda el: [(el[0], "phase")], [[(0, "phase", None, 1.0), (2, "k1", None, 0.5)]], B=B)
 
 

@@ -1,9 +1,10 @@
 """
-Every reverse call of `lynx_amd/grad.py` against the transcript in tests/golden/reverse_calls.npz, without a GPU: the
+Every call of `lynx_amd.grad` against the transcripts in tests/golden/reverse_calls.npz (`track_vjp` and the five modes of
+`track_along_vjp`) and tests/golden/target_calls.npz (`image_targets=`, `moment_targets=`, forward mode), without a GPU: the
 keyword arguments of the forward trace, every library call with every argument (uploads by dtype, shape and bytes,
-allocations by how they were made), everything `Gradients` hands out, and every refusal's type and text.  The transcript
-was made by tests/golden/make_reverse_calls.py on the commit before `grad.py` was last restructured: a reverse pass that
-uploads another byte, allocates in another way or launches another entry point fails here.
+allocations by how they were made), everything `Gradients` and the loss and tangent objects hand out, and every refusal's
+type and text.  Each transcript was made by tests/golden/make_reverse_calls.py on the commit before `lynx_amd.grad` was
+last restructured: a pass that uploads another byte, allocates in another way or launches another entry point fails here.
 """
 
 import numpy as np
@@ -13,8 +14,8 @@ from .golden import make_reverse_calls as golden
 
 
 @pytest.fixture(scope="module")
-def recorded_file():
-    return golden.load(golden.PATH)
+def recorded_files():
+    return {path: golden.load(path) for path in (golden.PATH, golden.TARGET_PATH)}
 
 
 def differences(want, got, want_arrays, got_arrays, where="", nan_equal=False):
@@ -38,16 +39,31 @@ def differences(want, got, want_arrays, got_arrays, where="", nan_equal=False):
     return [] if type(want) is type(got) and want == got else [f"{where}: {want!r} became {got!r}"]
 
 
-def test_the_file_holds_these_cases_and_is_small(recorded_file):
-    assert sorted(recorded_file[0]) == sorted(golden.CASES)
+def replayed(recorded, name):
+    index, arrays = recorded
+    got_arrays = []
+    got = golden.flatten(golden.transcript(name), got_arrays)
+    assert got["calls"] or "refusals" in name  # (the case reached the library)
+    return differences(index[name], got, arrays, got_arrays)
+
+
+def test_the_file_holds_these_cases_and_is_small(recorded_files):
+    assert sorted(recorded_files[golden.PATH][0]) == sorted(golden.CASES)
     assert golden.PATH.stat().st_size < 100_000
 
 
 @pytest.mark.parametrize("name", list(golden.CASES))
-def test_the_calls_are_the_recorded_ones(recorded_file, name):
-    index, arrays = recorded_file
-    got_arrays = []
-    got = golden.flatten(golden.transcript(name), got_arrays)
-    assert got["calls"] or "refusals" in name  # (the case reached the library)
-    found = differences(index[name], got, arrays, got_arrays)
+def test_the_calls_are_the_recorded_ones(recorded_files, name):
+    found = replayed(recorded_files[golden.PATH], name)
+    assert not found, "\n".join(found[:20])
+
+
+def test_the_target_file_holds_these_cases_and_is_small(recorded_files):
+    assert sorted(recorded_files[golden.TARGET_PATH][0]) == sorted(golden.TARGET_CASES)
+    assert golden.TARGET_PATH.stat().st_size < 100_000
+
+
+@pytest.mark.parametrize("name", list(golden.TARGET_CASES))
+def test_the_target_calls_are_the_recorded_ones(recorded_files, name):
+    found = replayed(recorded_files[golden.TARGET_PATH], name)
     assert not found, "\n".join(found[:20])

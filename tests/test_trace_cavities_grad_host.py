@@ -29,14 +29,13 @@ def test_the_entry_point_is_declared_with_twelve_arguments():
 
 
 def _no_gpu(monkeypatch):
-    from lynx_amd import device, engine, grad
+    from lynx_amd import device, engine
 
     def no_gpu(*args, **kwargs):
         raise AssertionError("track_along_vjp touched the GPU runtime")
 
     monkeypatch.setattr(device, "get_runtime", no_gpu)
     monkeypatch.setattr(engine, "get_runtime", no_gpu)
-    monkeypatch.setattr(grad, "get_runtime", no_gpu)
 
 
 def test_refusals_are_raised_before_any_gpu_call(monkeypatch):

@@ -115,7 +115,6 @@ def test_refusals_with_cavities_are_raised_before_any_gpu_call(monkeypatch):
 
     monkeypatch.setattr(device, "get_runtime", no_gpu)
     monkeypatch.setattr(engine, "get_runtime", no_gpu)
-    monkeypatch.setattr(grad, "get_runtime", no_gpu)
     f = lambda v: np.array([v], dtype=np.float32)  # noqa: E731
     particles = lx.ParticleBeam(o.gaussian_particles((1,), 16, seed=1), f(1e8))
     parameters = lx.ParameterBeam.from_parameters(sigma_x=f(1e-4), sigma_xp=f(1e-5), energy=f(1e8))

@@ -235,25 +235,14 @@ MODES = ("moments", "particles", "trajectories", "survivors", "kicks")
 @pytest.fixture
 def recorded_with_energy(monkeypatch):
     """
-    The fake runtime with the fabricated forward pass; asked to keep the energies it also leaves them on the device, as the
-    real `engine.track_along` does, and the incoming energy over the batch is a forward array (the real one is uploaded once
+    The fake runtime with the fabricated forward pass (asked to keep the energies it also leaves them on the device, as the
+    real `engine.track_along` does); the incoming energy over the batch is a forward array (the real one is uploaded once
     and remembered on the beam): (lynx_amd, the runtime, the keyword arguments of every forward pass).
     """
     import lynx_amd as lx
-    from lynx_amd import engine
     from lynx_amd.device import Dual
 
     rt, forward = fake_gpu(monkeypatch)
-    fabricated = engine.track_along
-
-    def track_along(owner, leaves, incoming, **kwargs):
-        trace = fabricated(owner, leaves, incoming, **kwargs)
-        if kwargs.get("keep_energy"):
-            batch = int(np.prod(incoming.batch_shape, dtype=np.int64))
-            trace._device["energy"] = rt.forward("energy", (batch, trace.num_points), incoming.dtype)
-        return trace
-
-    monkeypatch.setattr(engine, "track_along", track_along)
     monkeypatch.setattr(Dual, "broadcast_device", lambda self, runtime, shape: rt.forward("e_in", tuple(shape), self.host().dtype))
     return lx, rt, forward
 
