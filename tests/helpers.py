@@ -33,6 +33,32 @@ def make_lattice(desc, dtype, lx=None):
     return (elements if lx is not None else None), specs
 
 
+def _some(rng, shape, draw, p=0.5):
+    """`draw(shape)` in a random subset of the samples, 0 in the others: a whole-batch any() that some samples take."""
+    return np.where(rng.random(shape) < p, draw(shape), 0.0)
+
+
+def criterion(particles, x_max, y_max, shape):
+    """The normalised quantities whose distance from 1 says how close to the boundary a particle is: (k, *batch, N)."""
+    x, y = particles[..., 0], particles[..., 2]
+    xm, ym = np.asarray(x_max, dtype=np.float64)[..., None], np.asarray(y_max, dtype=np.float64)[..., None]
+    with np.errstate(all="ignore"):
+        if shape == "elliptical":
+            return np.stack([x ** 2 / xm ** 2 + y ** 2 / ym ** 2])
+        return np.stack([np.abs(x) / xm, np.abs(y) / ym])
+
+
+def build(desc, dtype, lx=None):
+    """`make_lattice` with ("aperture", dict(x_max, y_max, shape)) entries: identity markers in the oracle's chain."""
+    plain = [("marker", {}) if kind == "aperture" else (kind, kw) for kind, kw in desc]
+    elements, specs = make_lattice(plain, dtype, lx)
+    for k, (kind, kw) in enumerate(desc):
+        if kind == "aperture" and lx is not None:
+            elements[k] = lx.Aperture(x_max=np.asarray(kw["x_max"], dtype=dtype), y_max=np.asarray(kw["y_max"], dtype=dtype),
+                                      shape=kw["shape"], is_active=kw.get("is_active", True), name=f"AP{k}", dtype=dtype)
+    return elements, specs
+
+
 def rel_err(got, ref):
     """max |got-ref| / max|ref| per trailing coordinate (robust to zeros), NaN-aware."""
     got, ref = np.asarray(got, dtype=np.float64), np.asarray(ref, dtype=np.float64)

@@ -31,6 +31,7 @@ import numpy as np
 from oracle import lynx_oracle as o
 
 from . import hp_maps as hp
+from .trace_jvp_reference import chain as _chain
 
 KIND = {"drift": hp.KIND_DRIFT, "quadrupole": hp.KIND_QUADRUPOLE, "dipole": hp.KIND_DIPOLE, "rbend": hp.KIND_DIPOLE,
         "hcor": hp.KIND_HCOR, "vcor": hp.KIND_VCOR, "solenoid": hp.KIND_SOLENOID, "undulator": hp.KIND_UNDULATOR}
@@ -116,15 +117,18 @@ class AffineReference:
     `gradients` of both beam classes: {(e, name): (B,) or (B, 2), "energy": (B,), ...}.
     """
 
-    def __init__(self, desc, energy):
+    def __init__(self, desc, energy, single=False):
+        """`single`: maps and their derivatives rounded through `f32` (and a ParameterBeam's states of the along forms at
+        every point) -- what rounding its inputs to float32 does to a result, for the conditioning of a drawn float32 case."""
         from .helpers import make_lattice
 
+        self.q = f32 if single else (lambda a: a)
         self.desc = desc
         self.energy = np.asarray(energy, dtype=np.float64)
         self.B = len(self.energy)
         _, self.specs = make_lattice(desc, np.float64)
         assert all(o.is_skippable(s) or s["kind"] == "bpm" for s in self.specs), "an active cavity: not an affine lattice"
-        self.maps = [o.element_transfer_map(s, self.energy, np.float64) for s in self.specs]
+        self.maps = [self.q(o.element_transfer_map(s, self.energy, np.float64)) for s in self.specs]
         self.active_bpms = [e for e, s in enumerate(self.specs) if s["kind"] == "bpm" and s.get("is_active")]
         self._dmaps = None
 
@@ -136,7 +140,7 @@ class AffineReference:
                     self._dmaps.append(None)
                     continue
                 per = [map_derivatives(kind, kw, b, self.B, self.energy[b]) for b in range(self.B)]
-                self._dmaps.append({name: np.stack([p[name] for p in per]) for name in per[0]})
+                self._dmaps.append({name: self.q(np.stack([p[name] for p in per])) for name in per[0]})
         return self._dmaps
 
     def _contract(self, tbars):
@@ -206,6 +210,175 @@ class AffineReference:
         out["mu"], out["cov"] = mbar, Cbar
         return out
 
+    # ---- the along forms: a cotangent at EVERY point (P = elements + 1), and forward-mode tangents -------------------------
+
+    def parameter_states(self, mu, cov):
+        """([mu at the P points], [cov at the P points]) of the moment recursion (`single`: rounded at every point)."""
+        m, C = self.q(np.asarray(mu, dtype=np.float64)), self.q(np.asarray(cov, dtype=np.float64))
+        mus, covs = [m], [C]
+        for T in self.maps:
+            m, C = self.q(np.einsum("bij,bj->bi", T, m)), self.q(T @ C @ np.swapaxes(T, -1, -2))
+            mus.append(m)
+            covs.append(C)
+        return mus, covs
+
+    def particle_states(self, P):
+        z = np.asarray(P, dtype=np.float64)
+        states = [z]
+        for T in self.maps:
+            z = z @ np.swapaxes(T, -1, -2)
+            states.append(z)
+        return states
+
+    def parameter_gradients_along(self, mu, cov, w_mu, w_cov, w_e=None, readings=None):
+        """
+        `parameter_gradients` with w_mu (B, P, 7), w_cov (B, P, 7, 7) and w_e (B, P) given at every point: the cotangent of
+        point k joins the sweep when it passes point k.  The energy at every point is the incoming one, so "energy" takes
+        w_e.sum(-1) besides the maps' term.
+        """
+        w_mu, w_cov = np.asarray(w_mu, dtype=np.float64), np.asarray(w_cov, dtype=np.float64)
+        mus, covs = self.parameter_states(mu, cov)
+        E = len(self.maps)
+        mbar, Cbar = w_mu[:, E].copy(), w_cov[:, E].copy()
+        tbars = [None] * E
+        for e in range(E - 1, -1, -1):
+            T, m, C = self.maps[e], mus[e], covs[e]
+            tbars[e] = (np.einsum("bi,bj->bij", mbar, m) + Cbar @ T @ np.swapaxes(C, -1, -2)
+                        + np.swapaxes(Cbar, -1, -2) @ T @ C)
+            mbar = np.einsum("bji,bj->bi", T, mbar) + w_mu[:, e]
+            Cbar = np.swapaxes(T, -1, -2) @ Cbar @ T + w_cov[:, e]
+            r = self._reading(readings, e)
+            if r is not None:
+                mbar[:, 0] += r[:, 0]
+                mbar[:, 2] += r[:, 1]
+        out = self._contract(tbars)
+        if w_e is not None:
+            out["energy"] = out["energy"] + np.asarray(w_e, dtype=np.float64).sum(axis=-1)
+        out["mu"], out["cov"] = mbar, Cbar
+        return out
+
+    def particle_gradients_along(self, P, w_mu, w_cov, w_e=None, readings=None, alive=None, trajectories_bar=None, chosen=None):
+        """
+        `particle_gradients` with w_mu (B, P, 6), w_cov (B, P, 6, 6), w_e (B, P) at every point.  `alive` (P, B, N) bool: the
+        mean and biased covariance of a point are over the particles alive there, and its z_bar goes to those alone, with
+        that point's count (an active BPM reads the centroid of the particles alive in front of it).  `trajectories_bar`
+        (B, P, K, 7) with `chosen` (K,): row [:, k, j] is added to z_bar of particle chosen[j] at point k, repeats add.
+        Adds "particles" (B, N, 7); "mu" (B, 7) and "cov" (B, 7, 7), the moment cotangents carried back to the incoming mean
+        and biased covariance (not with `alive`: no single set came in; "cov" is the symmetric part -- the particles fix
+        no more); "chosen_particles" (B, K, 7): row j is the cotangent of its own trajectory alone.
+        """
+        states = self.particle_states(P)
+        B, N = states[0].shape[:2]
+        E = len(self.maps)
+        w_mu, w_cov = np.asarray(w_mu, dtype=np.float64), np.asarray(w_cov, dtype=np.float64)
+        a_all = np.ones((E + 1, B, N), dtype=bool) if alive is None else np.asarray(alive, dtype=bool)
+        tb = None if trajectories_bar is None else np.asarray(trajectories_bar, dtype=np.float64)
+
+        def injected(k):
+            a = a_all[k][..., None].astype(np.float64)
+            n = np.maximum(a_all[k].sum(axis=-1), 1)[:, None, None]
+            q = states[k][..., :6]
+            d = (q - (q * a).sum(axis=1, keepdims=True) / n) * a
+            W = w_cov[:, k]
+            zb = np.zeros((B, N, 7))
+            zb[..., :6] = a * (w_mu[:, k][:, None, :] + d @ np.swapaxes(W + np.swapaxes(W, -1, -2), -1, -2)) / n
+            if tb is not None:
+                for j, p in enumerate(chosen):
+                    zb[:, p] += tb[:, k, j]
+            return zb, a[..., 0] / n[..., 0]
+
+        zbar, _ = injected(E)
+        tbars = [None] * E
+        for e in range(E - 1, -1, -1):
+            tbars[e] = np.einsum("bni,bnj->bij", zbar, states[e])
+            here, share = injected(e)
+            zbar = zbar @ self.maps[e] + here
+            r = self._reading(readings, e)
+            if r is not None:
+                zbar[..., 0] += r[:, None, 0] * share
+                zbar[..., 2] += r[:, None, 1] * share
+        out = self._contract(tbars)
+        if w_e is not None:
+            out["energy"] = out["energy"] + np.asarray(w_e, dtype=np.float64).sum(axis=-1)
+        out["particles"] = zbar
+        if alive is None:
+            mbar, Cbar = np.zeros((B, 7)), np.zeros((B, 7, 7))
+            for k in range(E, -1, -1):
+                if k < E:
+                    T = self.maps[k]
+                    mbar, Cbar = np.einsum("bji,bj->bi", T, mbar), np.swapaxes(T, -1, -2) @ Cbar @ T
+                    r = self._reading(readings, k)
+                    if r is not None:
+                        mbar[:, 0] += r[:, 0]
+                        mbar[:, 2] += r[:, 1]
+                mbar[:, :6] += w_mu[:, k]
+                Cbar[:, :6, :6] += w_cov[:, k]
+            out["mu"], out["cov"] = mbar, (Cbar + np.swapaxes(Cbar, -1, -2)) / 2
+        if tb is not None:
+            rows = np.zeros((B, len(chosen), 7))
+            for k in range(E, -1, -1):
+                if k < E:
+                    rows = rows @ self.maps[k]
+                rows = rows + tb[:, k]
+            out["chosen_particles"] = rows
+        return out
+
+    def _direction_maps(self, direction):
+        """{leaf: Mdot (B, 7, 7)} of a direction [(leaf, name, component or None, weight)]; "energy": dM/dE of that leaf."""
+        dmaps, out = self.dmaps(), {}
+        for leaf, name, component, weight in direction:
+            if dmaps[leaf] is None:
+                continue  # (a kind without a row: its map does not depend on anything, the energy included)
+            D = dmaps[leaf][name]
+            D = D if component is None else D[:, component]
+            out[leaf] = out.get(leaf, 0.0) + weight * D
+        return out
+
+    def parameter_tangents(self, mu, cov, direction):
+        """(mu_dot (B, P, 7), cov_dot (B, P, 7, 7)) of the moment recursion along one direction."""
+        mus, covs = self.parameter_states(mu, cov)
+        mdots = self._direction_maps(direction)
+        md, cd = np.zeros_like(mus[0]), np.zeros_like(covs[0])
+        mu_dot, cov_dot = [md], [cd]
+        for e, T in enumerate(self.maps):
+            md, cd = np.einsum("bij,bj->bi", T, md), T @ cd @ np.swapaxes(T, -1, -2)
+            if e in mdots:
+                md = md + np.einsum("bij,bj->bi", mdots[e], mus[e])
+                X = mdots[e] @ covs[e] @ np.swapaxes(T, -1, -2)
+                cd = cd + X + np.swapaxes(X, -1, -2)
+            mu_dot.append(md)
+            cov_dot.append(cd)
+        return np.stack(mu_dot, axis=1), np.stack(cov_dot, axis=1)
+
+    def particle_tangents(self, P, direction):
+        """
+        ... of the PARTICLES: z_dot' = M z_dot + Mdot z per particle, the tangents of the mean and of the biased covariance
+        taken from the particles -- not from the moment recursion, whose closure under affine maps is what the kernels use.
+        A particle is carried as mean + deviation, so that z_dot - mean(z_dot) is never formed by a subtraction: along a
+        direction that moves every particle alike (a corrector's angle, a misalignment) the covariance's tangent is the
+        exact zero it is, not the rounding of N equal numbers' mean.
+        """
+        states = self.particle_states(P)
+        mdots = self._direction_maps(direction)
+        B, N = states[0].shape[:2]
+        md, dd = np.zeros((B, 7)), np.zeros((B, N, 6))
+        mu_dot, cov_dot = [], []
+        for k in range(len(self.maps) + 1):
+            if k:
+                T = self.maps[k - 1]
+                md, dd = np.einsum("bij,bj->bi", T, md), dd @ np.swapaxes(T[:, :6, :6], -1, -2)
+                if k - 1 in mdots:
+                    before = states[k - 1]
+                    mean = before.mean(axis=1)
+                    md = md + np.einsum("bij,bj->bi", mdots[k - 1], mean)
+                    dd = dd + (before - mean[:, None, :])[..., :6] @ np.swapaxes(mdots[k - 1][:, :6, :6], -1, -2)
+            d = (states[k] - states[k].mean(axis=1, keepdims=True))[..., :6]
+            X = np.zeros((B, 7, 7))
+            X[:, :6, :6] = np.einsum("bni,bnj->bij", dd, d) / N
+            mu_dot.append(md)
+            cov_dot.append(X + np.swapaxes(X, -1, -2))
+        return np.stack(mu_dot, axis=1), np.stack(cov_dot, axis=1)
+
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the oracle's losses and their central differences
@@ -245,6 +418,23 @@ FLOOR = {"length": 1e-2, "k1": 1e-2, "tilt": 1e-2, "misalignment": 1e-3, "angle"
          "k": 1e-2, "particles": 1e-1, "mu": 1e-1, "cov": 1e-6, "direction": 1e1}
 
 
+def chain_moments(beams):
+    """(mu (B, P, k), cov (B, P, k, k), energy (B, P)) of a chain of oracle beams: a ParameterBeam's own (k = 7), the particles'
+    mean and biased covariance (k = 6)."""
+    mus, covs = [], []
+    for b in beams:
+        if "particles" in b:
+            Q = b["particles"][..., :6]
+            mean = Q.mean(axis=-2)
+            d = Q - mean[..., None, :]
+            mus.append(mean)
+            covs.append(np.einsum("...ni,...nj->...ij", d, d) / Q.shape[-2])
+        else:
+            mus.append(b["mu"])
+            covs.append(b["cov"])
+    return np.stack(mus, axis=1), np.stack(covs, axis=1), np.stack([b["energy"] for b in beams], axis=1)
+
+
 def _tile(value, K):
     value = np.asarray(value, dtype=np.float64)
     return np.tile(value, (K,) + (1,) * (value.ndim - 1))
@@ -263,8 +453,11 @@ class OracleCase:
     TWO_STEP_AGREEMENT of max(|ref|, scale), and none is an AssertionError.
     """
 
-    def __init__(self, desc, energy, w_mu, w_cov, particles=None, mu=None, cov=None, direction=None, readings=None):
+    def __init__(self, desc, energy, w_mu, w_cov, particles=None, mu=None, cov=None, direction=None, readings=None, w_e=None):
+        """`w_mu` (B, P, k), `w_cov` (B, P, k, k) and `w_e` (B, P): the ALONG loss, the sum over the P points of the oracle's
+        element-by-element chain of <w_mu, mu> + <w_cov, cov> + w_e (E - E_0), E_0 the unperturbed energy at the point."""
         self.desc, self.energy = desc, np.asarray(energy, dtype=np.float64)
+        self.w_e = None if w_e is None else np.asarray(w_e, dtype=np.float64)
         self.B = len(self.energy)
         self.w_mu, self.w_cov = np.asarray(w_mu, dtype=np.float64), np.asarray(w_cov, dtype=np.float64)
         self.particles, self.mu, self.cov, self.direction = particles, mu, cov, direction
@@ -284,6 +477,21 @@ class OracleCase:
         w_mu, w_cov = _tile(self.w_mu, K), _tile(self.w_cov, K)
         readings = None if self.readings is None else [np.tile(np.asarray(r, dtype=np.float64), (1, K)) for r in self.readings]
 
+        def beam():
+            if self.particles is not None:
+                return o.particle_beam(arrays["particles"], arrays["energy"], np.float64)
+            return o.parameter_beam(arrays["mu"], arrays["cov"], arrays["energy"], np.float64)
+
+        if self.w_mu.ndim == 3:
+            assert self.readings is None and self.direction is None, "the along loss has neither readings nor a direction"
+            w_e, e_0 = _tile(self.w_e, K), _tile(self.energies_along(), K)
+
+            def along():
+                mu, cov, energy = chain_moments(_chain(specs, beam()))
+                return (np.sum(w_mu * mu, axis=(-1, -2)) + np.sum(w_cov * cov, axis=(-1, -2, -3)) + np.sum(w_e * (energy - e_0), axis=-1))
+
+            return specs, arrays, along
+
         def loss():
             if self.particles is not None:
                 return particle_loss(specs, arrays["particles"], arrays["energy"], w_mu, w_cov, readings)
@@ -293,6 +501,51 @@ class OracleCase:
 
     def loss(self):
         return self._build(1)[2]()
+
+    def energies_along(self):
+        """(B, P): the unperturbed energy at every point of the chain."""
+        if "energies" not in self._known:
+            from .helpers import make_lattice
+
+            _, specs = make_lattice(self.desc, np.float64)
+            incoming = (o.particle_beam(self.particles, self.energy, np.float64) if self.particles is not None
+                        else o.parameter_beam(self.mu, self.cov, self.energy, np.float64))
+            self._known["energies"] = chain_moments(_chain(specs, incoming))[2]
+        return self._known["energies"]
+
+    def tangents(self, q, allowance=1.0):
+        """
+        (mu_dot (B, P, k), cov_dot (B, P, k, k), energy_dot (B, P), and per array the quotient's own rounding (B,)): central
+        differences of the chain's moments at every point along quantity q, at the first step of RELATIVE_STEPS whose two
+        quotients (h and h / 4) agree to TWO_STEP_AGREEMENT of each array's largest entry, per sample.  The rounding is
+        `allowance` x 8 eps max |value| / h (tests/trace_jvp_reference.py, ROUNDING), with h / 4: the narrower step's, the larger.
+        """
+        B, tried = self.B, []
+        eps = 8 * np.finfo(np.float64).eps * allowance
+        for rel in RELATIVE_STEPS:
+            specs, arrays, _ = self._build(4)
+            array, index, _, magnitude = self._target(specs, arrays, q)
+            h = rel * magnitude
+            for v, d in enumerate((h, -h, h / 4, -h / 4)):
+                array[(slice(v * B, (v + 1) * B), *index)] += d
+            incoming = (o.particle_beam(arrays["particles"], arrays["energy"], np.float64) if self.particles is not None
+                        else o.parameter_beam(arrays["mu"], arrays["cov"], arrays["energy"], np.float64))
+            values = chain_moments(_chain(specs, incoming))
+            out, noise, worst = [], [], 0.0
+            for a in values:
+                rows = lambda v: a[v * B:(v + 1) * B]  # noqa: E731
+                step = lambda s: s.reshape(-1, *([1] * (a.ndim - 1)))  # noqa: E731
+                wide, narrow = (rows(0) - rows(1)) / step(2 * h), (rows(2) - rows(3)) / step(h / 2)
+                top = np.max(np.abs(wide).reshape(B, -1), axis=1)
+                noise.append(eps * np.max(np.abs(rows(0)).reshape(B, -1), axis=1) / (h / 4))
+                gap = np.max(np.abs(wide - narrow).reshape(B, -1), axis=1)
+                # (an array that does not move at all -- the energy along a magnet's parameter -- agrees with itself)
+                worst = max(worst, float(np.max(np.where(gap <= noise[-1], 0.0, gap / np.maximum(top, 1e-300)))))
+                out.append(wide)
+            tried.append((rel, worst))
+            if worst <= TWO_STEP_AGREEMENT:
+                return (*out, *noise)
+        raise AssertionError(("no step at which the oracle's central differences agree with themselves", q, tried))
 
     def forward(self):
         """The oracle's outgoing beam."""

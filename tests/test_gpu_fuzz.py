@@ -20,7 +20,7 @@ import pytest
 
 from oracle import lynx_oracle as o
 
-from .helpers import assert_parameter_beam, make_lattice, rel_err
+from .helpers import _some, assert_parameter_beam, make_lattice, rel_err
 from .test_gpu_parity import KICK_MOMENTS, TOL_KICK_F64, TOL_MOM, TOL_P, VARIANTS
 
 pytestmark = pytest.mark.gpu
@@ -61,11 +61,6 @@ def _record_seed(record_property):
 # ---------------------------------------------------------------------------------------------------------------------
 # drawing
 # ---------------------------------------------------------------------------------------------------------------------
-
-
-def _some(rng, shape, draw, p=0.5):
-    """`draw(shape)` in a random subset of the samples, 0 in the others: a whole-batch any() that some samples take."""
-    return np.where(rng.random(shape) < p, draw(shape), 0.0)
 
 
 def _element(rng, kind, shape, drawn):

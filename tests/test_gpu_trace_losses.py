@@ -22,7 +22,7 @@ import pytest
 
 from oracle import lynx_oracle as o
 
-from .helpers import MOMENT_KEYS, biased_covariance, covariance_distances, make_lattice, moment_distances, rel_err
+from .helpers import MOMENT_KEYS, biased_covariance, build, covariance_distances, criterion, make_lattice, moment_distances, rel_err
 from .test_gpu_parity import KICK_MOMENTS, TOL_KICK_F64, TOL_MOM
 from .test_gpu_trace import SIGMA, chain, correlated_particles, point, upcast
 
@@ -46,27 +46,6 @@ def lx(built_library):
 # ---------------------------------------------------------------------------------------------
 # the expectation
 # ---------------------------------------------------------------------------------------------
-
-
-def criterion(particles, x_max, y_max, shape):
-    """The normalised quantities whose distance from 1 says how close to the boundary a particle is: (k, *batch, N)."""
-    x, y = particles[..., 0], particles[..., 2]
-    xm, ym = np.asarray(x_max, dtype=np.float64)[..., None], np.asarray(y_max, dtype=np.float64)[..., None]
-    with np.errstate(all="ignore"):
-        if shape == "elliptical":
-            return np.stack([x ** 2 / xm ** 2 + y ** 2 / ym ** 2])
-        return np.stack([np.abs(x) / xm, np.abs(y) / ym])
-
-
-def build(desc, dtype, lx=None):
-    """`make_lattice` with ("aperture", dict(x_max, y_max, shape)) entries: identity markers in the oracle's chain."""
-    plain = [("marker", {}) if kind == "aperture" else (kind, kw) for kind, kw in desc]
-    elements, specs = make_lattice(plain, dtype, lx)
-    for k, (kind, kw) in enumerate(desc):
-        if kind == "aperture" and lx is not None:
-            elements[k] = lx.Aperture(x_max=np.asarray(kw["x_max"], dtype=dtype), y_max=np.asarray(kw["y_max"], dtype=dtype),
-                                      shape=kw["shape"], is_active=kw.get("is_active", True), name=f"AP{k}", dtype=dtype)
-    return elements, specs
 
 
 def expectation(desc, P, energy, dtype):

@@ -19,9 +19,10 @@ import pytest
 
 from oracle import lynx_oracle as o
 
+from .helpers import build
 from .test_gpu_parity import TOL_MOM
-from .test_gpu_trace_grad import _chain, _check_parameters, _particle_lattice, _worst_distance
-from .test_gpu_trace_losses import build, criterion
+from .test_gpu_trace_grad import _check_parameters, _particle_lattice, _worst_distance
+from .trace_grad_cases import _moments_of, _sized_apertures, _survivor_chain
 
 pytestmark = pytest.mark.gpu
 
@@ -165,58 +166,6 @@ def test_the_entry_points_refuse_bad_arguments_before_any_launch(lx):
 # ---------------------------------------------------------------------------------------------
 # the reference: the oracle's particle chain with the survivors of every point
 # ---------------------------------------------------------------------------------------------
-
-
-def _survivor_chain(desc, specs, particles, energy):
-    """
-    `element_track` element by element in float64 (an aperture is a marker there), `o.aperture_mask` on the particles
-    that ENTER every active aperture: (beams at the P points, alive (P, *batch, N) bool, lost_at, the smallest distance of
-    a particle still alive from an edge in the `criterion` measure).
-    """
-    beams = _chain(specs, o.particle_beam(particles, energy, np.float64))
-    alive = np.ones(particles.shape[:-1], dtype=bool)
-    lost_at = np.full(particles.shape[:-1], -1, dtype=np.int32)
-    masks, margin, ordinal = [], np.inf, 0
-    for k, (kind, kw) in enumerate(desc):
-        masks.append(alive.copy())
-        if kind == "aperture" and kw.get("is_active", True):
-            keep = o.aperture_mask(beams[k]["particles"], kw["x_max"], kw["y_max"], kw["shape"])
-            crit = criterion(beams[k]["particles"], kw["x_max"], kw["y_max"], kw["shape"])
-            margin = min(margin, float(np.min(np.abs(crit - 1.0)[:, alive]))) if alive.any() else margin
-            lost_at[alive & ~keep] = ordinal
-            alive = alive & keep
-            ordinal += 1
-    masks.append(alive.copy())
-    return beams, np.array(masks), lost_at, margin
-
-
-def _moments_of(q, alive):
-    """Mean (*batch, 6) and biased covariance (*batch, 6, 6) of the particles `alive` (*batch, N) marks, in float64."""
-    w = alive[..., None].astype(np.float64)
-    n = alive.sum(axis=-1)[..., None]
-    mean = (q * w).sum(axis=-2) / n
-    d = (q - mean[..., None, :]) * w
-    return mean, np.einsum("...ni,...nj->...ij", d, d) / n[..., None]
-
-
-def _sized_apertures(desc, particles, energy, places, fractions):
-    """
-    `desc` with an active aperture in front of each element `places` names (indices into `desc`), rectangular and
-    elliptical in turn along the lattice; the limits of each are its fraction of `fractions` times the rms sizes of the
-    particles still alive where it stands (the apertures in front of it sized, the ones behind it open).
-    """
-    out = list(desc)
-    for place in sorted(places, reverse=True):
-        out.insert(place, ("aperture", None))
-    order = [k for k, (kind, _) in enumerate(out) if kind == "aperture"]
-    for count, (k, fraction) in enumerate(zip(order, fractions)):
-        so_far = [("marker", {}) if kw is None else (kind, kw) for kind, kw in out]
-        _, specs = build(so_far, np.float64)
-        beams, masks, _, _ = _survivor_chain(so_far, specs, particles, energy)
-        _, cov = _moments_of(beams[k]["particles"][..., :6], masks[k])
-        out[k] = ("aperture", dict(x_max=fraction * np.sqrt(cov[..., 0, 0]), y_max=fraction * np.sqrt(cov[..., 2, 2]),
-                                   shape=("rectangular", "elliptical")[count % 2]))
-    return out
 
 
 def _fd_case():
